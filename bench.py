@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path named by BASELINE.json: batched SO_FJSSP env steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1], per GPU): 4096 generated 10-job x 5-machine
 SO_FJSSP instances (generator seeds 1000 + global env id, fluid LP solved on the
 host before the timed region), random policy from a pre-generated action tensor
 resident in HBM, ONE bench step = ONE launch of the per-step HIP kernel over all
 envs through the C ABI (fjsp_env_step, autoreset on, so every launch advances
-every env by exactly one environment step).
+every env by exactly one environment step).  The timed region is exactly K steps.
+
+--dump-outputs DIR writes what the last timed step returned to its caller
+(state f64[envs, 20], reward f64[envs], done as f32[envs], over the whole job in
+global env order) as DIR/<name>.npy.  Inputs and the number of steps before the
+dump depend on the arguments alone, so two builds can be compared array for array.
+Above 64 MB in all, a fixed seeded sample of env rows is written, with their
+global ids in DIR/env_ids.npy.
 
 Prints ONE JSON line (rank 0): metric env-steps/s (whole job), plus
   roofline      the step kernel's algorithmic HBM bytes per launch / its mean launch
@@ -52,6 +59,29 @@ def csrc_hash():
     return h.hexdigest()
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+SETTLE_STEPS = 8192             # untimed steps (in regions of K) between the warm-up and the timed region
+
+
+def dump_outputs(out_dir, outputs):
+    """outputs: name -> numpy array with the env axis first (f32 / f64).  Writes DIR/<name>.npy, at most
+    DUMP_LIMIT_BYTES in all; above that, the rows of a fixed seeded sample of envs (ids in env_ids.npy).
+    Returns a description for the JSON line."""
+    import numpy as np
+    n = next(iter(outputs.values())).shape[0]
+    row_bytes = sum(a.nbytes // n for a in outputs.values())
+    rows = None
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)          # (4 KB for the .npy headers)
+        rows = np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+        outputs = dict({name: a[rows] for name, a in outputs.items()}, env_ids=rows.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": {name: list(a.shape) for name, a in outputs.items()},
+            "sampled_envs": None if rows is None else len(rows)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -61,7 +91,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the K timed launches from a captured HIP graph (auto: when K <= 256, where a region is launch-bound at its edges)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state / reward / done the last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -115,12 +149,10 @@ def main():
         env.step(actions[i % Tbuf], autoreset=True)
     sync_all()
 
-    # The timed region is EXACTLY `steps` launches between barrier + synchronize on both sides.  A region of a few
-    # launches lasts a fraction of a millisecond -- launch ramp-up and clock noise dominate it -- so the region is
-    # repeated (at least 25 times and until 50 ms have been timed, at most 2 000 times) and the MEDIAN region is
-    # reported; every region is the max over ranks.
+    # The timed region is EXACTLY `steps` launches between barrier + synchronize on both sides, timed once by the wall
+    # clock (the max over ranks).
     # Short regions (the driver's --steps 20) are launch-bound at their edges: the K launches are captured once into a HIP
-    # graph and a region replays it -- the same K step launches on the same stream, one host call instead of K.
+    # graph and the region replays it -- the same K step launches on the same stream, one host call instead of K.
     graph = None
     if args.graph == "on" or (args.graph == "auto" and args.steps <= 256):
         side = torch.cuda.Stream()
@@ -136,50 +168,68 @@ def main():
                 env.step(actions[i % Tbuf], autoreset=True)
         sync_all()
 
-    def timed_region(k, with_events=True):
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0 = time.perf_counter()
-        if with_events:
-            ev0.record()
+    def run_steps(first):
         if graph is not None:
             graph.replay()
         else:
-            for i in range(k):
-                env.step(actions[(step_ctr[0] + i) % Tbuf], autoreset=True)
-        if with_events:
-            ev1.record()
-        sync_all()
-        dt = time.perf_counter() - t0
-        step_ctr[0] += k
-        return dt, (ev0.elapsed_time(ev1) if with_events else None)
+            for i in range(args.steps):
+                env.step(actions[(first + i) % Tbuf], autoreset=True)
 
-    step_ctr = [args.warmup]
-    regions = []
-    local_dts = []
-    total_t = 0.0
-    # Short regions: the two event records around the K launches are stream operations of their own (a few microseconds of a
-    # 0.2 ms region), so the wall-clock regions run without them and the HIP-event figure of the roofline comes from a second
-    # set of regions of the same K launches, timed by events only.
-    split_events = graph is not None
-    while len(regions) < 25 or (total_t < 0.05 and len(regions) < 2000):
-        dt, ev_ms = timed_region(args.steps, with_events=not split_events)
-        local_dts.append(dt)
-        if world > 1:
-            tt = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dt = float(tt.item())
-        regions.append((dt, ev_ms))
-        total_t += dt
-    if split_events:
-        ev_regions = [timed_region(args.steps, with_events=True)[1] for _ in range(max(25, min(len(regions), 200)))]
-    else:
-        ev_regions = [r[1] for r in regions]
-    regions.sort(key=lambda r: r[0])
-    elapsed_local = sorted(local_dts)[len(local_dts) // 2]       # this rank's own median region (before the max over ranks)
-    elapsed, _ = regions[len(regions) // 2]
-    region_ms = sorted(ev_regions)[len(ev_regions) // 2]
+    # Clocks and the launch path reach their steady state only after many regions (a region timed after a few warm-up
+    # steps alone reads ~4 % slow), so untimed regions of the same K steps, each synchronized like the timed one, follow
+    # the warm-up until SETTLE_STEPS steps have run: a FIXED count, so that what the timed steps compute depends on the
+    # arguments alone.
+    settle_regions = -(-SETTLE_STEPS // args.steps)
+    for r in range(settle_regions):
+        run_steps(args.warmup + r * args.steps)
+        sync_all()
+
+    # A short region: the two event records around the K launches are stream operations of their own (a few microseconds
+    # of a 0.2 ms region), so the wall-clock region runs without them and the HIP-event figure of the roofline comes from
+    # further replays of the same K launches after it, timed by events only.
+    with_events = graph is None
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    if with_events:
+        ev0.record()
+    run_steps(args.warmup + settle_regions * args.steps)
+    if with_events:
+        ev1.record()
+    sync_all()
+    elapsed_local = time.perf_counter() - t0
+    elapsed = elapsed_local
+    if world > 1:
+        tt = torch.tensor([elapsed_local], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+    # what the last timed step handed its caller (fjsp_env_step writes env.state / reward / done in place)
+    timed_outputs = {"state": env.state.clone(), "reward": env.reward.clone(), "done": env.done.to(torch.float32)}
     status = env.read()["status"]
     assert int((status != 0).sum().item()) == 0, "an environment reported an error status during the bench"
+
+    dumped = None
+    if args.dump_outputs:
+        outs = {}
+        for name, t in timed_outputs.items():
+            if world > 1:                  # every rank holds N rows: gather them in global env order
+                t = t if backend == "nccl" else t.cpu()
+                parts = [torch.empty_like(t) for _ in range(world)]
+                dist.all_gather(parts, t)
+                t = torch.cat(parts)
+            outs[name] = t.cpu().numpy()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, outs)
+
+    if with_events:
+        region_ms, n_ev_regions = ev0.elapsed_time(ev1), 1
+    else:
+        ev_regions = []
+        for _ in range(200):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); graph.replay(); e1.record()
+            torch.cuda.synchronize()
+            ev_regions.append(e0.elapsed_time(e1))
+        region_ms, n_ev_regions = sorted(ev_regions)[len(ev_regions) // 2], len(ev_regions)
 
     # ---- roofline leg: per-launch HIP events on the launch stream ------------------
     n_ev = min(args.steps, 400)
@@ -332,8 +382,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "timed_regions": len(regions),
-            "region_ms_min_median_max": [regions[0][0] * 1e3, elapsed * 1e3, regions[-1][0] * 1e3],
+            "region_ms": elapsed * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -350,14 +399,16 @@ def main():
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_note": traffic_note,
                          "kernel": step_kernel_name, "bytes_per_env_step": env.step_bytes,
                          "bytes_per_launch": bytes_per_launch, "launch_us_hip_events": region_us,
-                         "hip_event_regions": ("%d further regions of the same K launches, bracketed by HIP events on the launch stream (the "
-                                               "wall-clock regions of a short run carry no event records)" % len(ev_regions)) if split_events
-                                              else "the wall-clock regions themselves, bracketed by HIP events on the launch stream",
+                         "hip_event_regions": ("median of %d further replays of the same K launches, bracketed by HIP events on the launch "
+                                               "stream (the wall-clock region of a short run carries no event records)" % n_ev_regions)
+                                              if not with_events else "the wall-clock region itself, bracketed by HIP events on the launch stream",
                          "launch_us_per_launch_events": kern_us},
             "cpu_baseline": cpu,
             "cpu_baseline_multicore": cpu_mt,
             "fused": fused,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         print(json.dumps(out))
     if world > 1:
         dist.barrier()
