@@ -40,7 +40,7 @@ def _hipcc():
 def build_library(force=False, verbose=False):
     """Compile the HIP kernels + C ABI for gfx950 into libfjsp_amd.so."""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES + CPP_SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))]
+    deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".inc"))]
     deps.append(os.path.join(REPO_DIR, "include", "fjsp_amd.h"))
     if not force and not _newer(LIB_PATH, deps):
         return LIB_PATH

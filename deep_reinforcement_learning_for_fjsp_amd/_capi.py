@@ -60,6 +60,9 @@ SIGNATURES = {
     "fjsp_env_rollout": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "fjsp_env_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_env_machine_time_end": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "fjsp_env_record_schedule": (C.c_int, [_vp, _i32]),
+    "fjsp_env_schedule_capacity": (C.c_int, [_vp]),
+    "fjsp_env_schedule": (C.c_int, [_vp, _vp, _vp, _vp]),
     "fjsp_env_energy": (C.c_int, [_vp, _vp, _vp]),
     "fjsp_env_fluid_tables": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "fjsp_env_step_bytes": (_i64, [_vp]),

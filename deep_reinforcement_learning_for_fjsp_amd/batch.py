@@ -25,6 +25,7 @@ ST_BAD_TASK_RULE = 1
 ST_BAD_MACHINE_RULE = 2
 ST_STEP_AFTER_DONE = 4
 ST_NO_EVENT = 8
+ST_SCHEDULE_OVERFLOW = 16
 
 
 ENV_SEED_STRIDE = 1000003          # env e draws random.choice from the stream seeded rng_seed + e * ENV_SEED_STRIDE
@@ -278,6 +279,32 @@ class EnvBatch(object):
             out["energy_consumption"] = torch.zeros(self.N, dtype=torch.int64, device=self.device)
             check(self._lib.fjsp_env_energy(self._h, _ptr(out["energy_consumption"]), self._stream()))
         return out
+
+    def record_schedule(self, on=True):
+        """Start (on=True) or stop recording the dispatched schedule (fjsp_env_record_schedule).  Every env must be
+        between episodes: right after construction, after reset() or once every env is done (FJSP_E_STATE otherwise).
+        While recording is on, every step / step_async / rollout / fused policy rollout stores one record per dispatch.
+        Synchronises the device first, so steps still queued on any stream count."""
+        check(self._lib.fjsp_env_record_schedule(self._h, 1 if on else 0))
+        self.schedule_capacity = int(self._lib.fjsp_env_schedule_capacity(self._h))
+        return self.schedule_capacity
+
+    def schedule(self, out=None):
+        """The recorded schedule of every env's current episode (fjsp_env_schedule; SO_FJSSP.py:182-184 per dispatched
+        operation).  Returns (table int32[N, cap, 6], length int32[N]) on the device: table[i, s] = (r, j, n, m,
+        time_begin, time_end) of env i's s-th dispatch -- kind r, stage j, job number n within kind r, machine m --
+        and -1 for s >= length[i].  A finished episode stays readable until the env is reset (explicitly or by
+        autoreset at its next step).  deep_reinforcement_learning_for_fjsp_amd.schedule works on it on the host."""
+        cap = int(self._lib.fjsp_env_schedule_capacity(self._h))
+        if cap == 0:
+            raise RuntimeError("schedule(): recording is off; call record_schedule() first")
+        if out is None:
+            table = torch.empty(self.N, cap, 6, dtype=torch.int32, device=self.device)
+        else:
+            table = _check_output("out", out, (self.N, cap, 6), torch.int32, self.device)
+        length = torch.empty(self.N, dtype=torch.int32, device=self.device)
+        check(self._lib.fjsp_env_schedule(self._h, _ptr(table), _ptr(length), self._stream()))
+        return table, length
 
     def set_lp_threads(self, n_threads):
         """Host threads of the order-arrival LP service (0 = all cores)."""

@@ -181,21 +181,30 @@ __host__ __device__ inline T *env_ptr(const DevBatch &b, int env, uint32_t off) 
     return reinterpret_cast<T *>(b.envs + (size_t)env * b.L.e_stride + off);
 }
 
+// Dispatch records of fjsp_env_record_schedule (SO_FJSSP.py:182-184): slot-major [cap][N], 16 bytes per dispatch, slot =
+// the env's step_count at the dispatch:  x = k | m << 16 | flags << 24 (flags bit 0: written), y = job number n within its
+// kind, z = time_begin, w = time_end.  rec == nullptr: recording is off and the launchers run the plain kernels.
+constexpr uint32_t kRecWritten = 1u;
+struct SchedRec {
+    uint4 *rec = nullptr;
+    int32_t cap = 0;         // slots per env: operations of the largest instance of the batch
+};
+
 // kernel launchers (fjsp_kernels.hip); all asynchronous on `st`, 0 = launched
 int launch_fluid_tables(const DevBatch &b, hipStream_t st);
 int launch_reset(const DevBatch &b, const uint8_t *mask, double *state, hipStream_t st);
 // ready (nullable, multi-order batches): asynchronous arrival service, see fjsp_env_step_async
 int launch_step(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
-                uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready = nullptr);
+                uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready = nullptr, const SchedRec &rec = SchedRec{});
 // the same step by the group kernels (fjsp_group.hip; DevBatch::grp batches only)
 int launch_step_group(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
-                      uint8_t *done, int16_t *trace_km, hipStream_t st);
+                      uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec = SchedRec{});
 int launch_rollout_group(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
-                         double *state_last, hipStream_t st);
+                         double *state_last, hipStream_t st, const SchedRec &rec = SchedRec{});
 size_t rollout_lds_bytes(const DevBatch &b);
 size_t step_lds_bytes(const DevBatch &b);     // dynamic LDS of one reset / step / arrival workgroup
 int launch_rollout(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
-                   double *state_last, hipStream_t st);
+                   double *state_last, hipStream_t st, const SchedRec &rec = SchedRec{});
 // multi-order: resume the envs whose pending LP has been solved (x in e_xin)
 // ids u32[n_pending] / x_list f64[n_pending][KP][MP]: the parked envs and their LP solutions (device)
 int launch_arrival(const DevBatch &b, const double *mo, int n_pending, const uint32_t *ids, const double *x_list, double *state,
@@ -211,7 +220,10 @@ struct ActorParams;
 struct PolicyRolloutIO;
 size_t policy_rollout_lds_bytes(const DevBatch &b, int S);
 int launch_actor_forward(const ActorParams &ap, const double *state, int n, float *probs, hipStream_t st);
-int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st);
+int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st,
+                          const SchedRec &rec = SchedRec{});
+// the recorded schedule as the public table (fjsp_env_schedule): i32[N][cap][6] = (r, j, n, m, begin, end), -1 past len[i]
+int launch_schedule_unpack(const DevBatch &b, const SchedRec &rec, int32_t *table, int32_t *len, hipStream_t st);
 int launch_read(const DevBatch &b, int64_t *delay, int32_t *makespan, int32_t *completion, int32_t *step_time,
                 int32_t *step_count, uint8_t *done, uint32_t *status, hipStream_t st);
 

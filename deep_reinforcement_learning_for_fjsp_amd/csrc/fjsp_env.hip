@@ -65,6 +65,8 @@ struct fjsp_env {
     int device = 0;
     std::vector<void *> allocs;
     std::vector<int> inst_K, inst_M;   // per packed instance
+    int ops_max = 0;                   // operations of the largest instance, orders that arrive later included (schedule slots)
+    SchedRec sched;                    // dispatch records while recording is on (fjsp_env_record_schedule); rec == nullptr: off
     int64_t step_bytes = 0;
     // scratch for the non-fused rollout fallback
     uint8_t *d_done_scratch = nullptr;
@@ -446,6 +448,12 @@ int fjsp_env_create(const fjsp_instances *s, int32_t first, int32_t n_inst, int3
             }
         }
         e->inst_K.push_back(in.K); e->inst_M.push_back(in.M);
+        {
+            int ops = 0;                                     // sum over orders and kinds of count[s][r] * J_r
+            for (int so = 0; so < in.S; ++so)
+                for (int r = 0; r < in.R; ++r) ops += in.count[(size_t)so * in.R + r] * in.Jr[r];
+            e->ops_max = std::max(e->ops_max, ops);
+        }
         uint32_t *kA = reinterpret_cast<uint32_t *>(ip(i, L.i_kA)), *kB = reinterpret_cast<uint32_t *>(ip(i, L.i_kB));
         uint32_t *elig = reinterpret_cast<uint32_t *>(ip(i, L.i_elig)), *first4 = reinterpret_cast<uint32_t *>(ip(i, L.i_f4));
         uint32_t *jinfo = reinterpret_cast<uint32_t *>(ip(i, L.i_jinfo));
@@ -665,6 +673,7 @@ void fjsp_env_destroy(fjsp_env *e) {
     {
         DeviceGuard guard(e->device);
         for (void *p : e->allocs) (void)hipFree(p);
+        if (e->sched.rec) (void)hipFree(e->sched.rec);
         if (e->h_pending) (void)hipHostFree(e->h_pending);
         if (e->h_lp_in) (void)hipHostFree(e->h_lp_in);
         if (e->h_lp_x) (void)hipHostFree(e->h_lp_x);
@@ -1000,7 +1009,7 @@ int fjsp_env_step_async(fjsp_env *e, const uint8_t *d_actions, const double *d_m
     DeviceGuard guard(e->device);
     hipStream_t st = (hipStream_t)stream;
     if (!e->b.mord) {                               // nothing ever parks: the plain step, every env ready
-        if (launch_step(e->b, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, nullptr, st) != 0) { set_error("step_kernel launch failed"); return FJSP_E_HIP; }
+        if (launch_step(e->b, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, nullptr, st, nullptr, e->sched) != 0) { set_error("step_kernel launch failed"); return FJSP_E_HIP; }
         HIP_TRY(hipMemsetAsync(d_ready, 1, (size_t)e->b.N, st));
         return FJSP_OK;
     }
@@ -1029,7 +1038,8 @@ int fjsp_env_step_async(fjsp_env *e, const uint8_t *d_actions, const double *d_m
         DevBatch b2 = e->b;
         b2.pending_count = slot->d_count;
         b2.lp_in = slot->d_lp_in;
-        if (launch_step(b2, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, nullptr, st, d_ready) != 0) {
+        // (a step that parks has dispatched already: its record is written in this launch, arrival_kernel adds none)
+        if (launch_step(b2, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, nullptr, st, d_ready, e->sched) != 0) {
             set_error("step_kernel launch failed"); return FJSP_E_HIP;
         }
         const size_t KP = (size_t)e->b.KP;
@@ -1074,7 +1084,7 @@ int fjsp_env_step_traced(fjsp_env *e, const uint8_t *d_actions, const double *d_
     if (!async_idle(e)) { set_error("fjsp_env_step: environments are parked in the asynchronous arrival service; call fjsp_env_arrivals_flush first"); return FJSP_E_STATE; }
     if (reinterpret_cast<uintptr_t>(d_actions) & 1) { set_error("fjsp_env_step_traced: d_actions must be 2-byte aligned"); return FJSP_E_ARG; }
     DeviceGuard guard(e->device);
-    if (launch_step(e->b, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, d_trace_km, (hipStream_t)stream) != 0) {
+    if (launch_step(e->b, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, d_trace_km, (hipStream_t)stream, nullptr, e->sched) != 0) {
         set_error("step_kernel launch failed"); return FJSP_E_HIP;
     }
     if (e->b.mord) return service_arrivals(e, d_mo, d_state, d_reward, d_done, d_trace_km, (hipStream_t)stream);
@@ -1095,7 +1105,7 @@ int fjsp_env_rollout(fjsp_env *e, const uint8_t *d_actions, const double *d_mo, 
     DeviceGuard guard(e->device);
     hipStream_t st = (hipStream_t)stream;
     if (!e->b.mord && rollout_lds_bytes(e->b) <= 64 * 1024) {
-        if (launch_rollout(e->b, d_actions, d_mo, T, d_trace_km, d_reward, d_state_last, st) != 0) {
+        if (launch_rollout(e->b, d_actions, d_mo, T, d_trace_km, d_reward, d_state_last, st, e->sched) != 0) {
             set_error("rollout_kernel launch failed"); return FJSP_E_HIP;
         }
         return FJSP_OK;
@@ -1104,7 +1114,7 @@ int fjsp_env_rollout(fjsp_env *e, const uint8_t *d_actions, const double *d_mo, 
     const size_t N = (size_t)e->b.N;
     for (int s2 = 0; s2 < T; ++s2) {
         if (launch_step(e->b, d_actions + (size_t)s2 * N * 2, d_mo, 2, d_state_last, d_reward ? d_reward + (size_t)s2 * N : nullptr,
-                        e->d_done_scratch, d_trace_km ? d_trace_km + (size_t)s2 * N * 2 : nullptr, st) != 0) {
+                        e->d_done_scratch, d_trace_km ? d_trace_km + (size_t)s2 * N * 2 : nullptr, st, nullptr, e->sched) != 0) {
             set_error("step_kernel launch failed"); return FJSP_E_HIP;
         }
         if (e->b.mord) {
@@ -1157,7 +1167,7 @@ int fjsp_env_rollout_policy(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_par
     io.state_in = d_state_in; io.epsilon = d_epsilon; io.seed = d_seed; io.pair_div = pair_div;
     io.o_state = buf->states; io.o_actions = buf->actions; io.o_reward = buf->rewards; io.o_next = buf->next_states;
     io.o_done = buf->dones; io.o_valid = buf->valid; io.o_flat = d_flat_actions; io.o_logp = d_log_prob; io.state_last = d_state_last;
-    if (launch_rollout_policy(e->b, actor_of(actor), io, d_mo, T, (hipStream_t)stream) != 0) {
+    if (launch_rollout_policy(e->b, actor_of(actor), io, d_mo, T, (hipStream_t)stream, e->sched) != 0) {
         set_error("rollout_policy_kernel launch failed"); return FJSP_E_HIP;
     }
     buf->len = T;
@@ -1178,6 +1188,62 @@ int fjsp_env_read(fjsp_env *e, int64_t *d_delay_time_sum, int32_t *d_makespan, i
         HIP_TRY(hipMemcpy(&err, e->d_lp_err, 4, hipMemcpyDeviceToHost));
         if (err) { e->failed = true; set_error("an order-arrival LP failed on the device (code " + std::to_string(err) + "); the batch is unusable: destroy it"); return FJSP_E_LP; }
     }
+    return FJSP_OK;
+}
+
+int fjsp_env_record_schedule(fjsp_env *e, int32_t on) {
+    if (!e) { set_error("fjsp_env_record_schedule: null env"); return FJSP_E_ARG; }
+    if (e->failed) { set_error("fjsp_env_record_schedule: the order-arrival service of this batch failed earlier; destroy the batch"); return FJSP_E_STATE; }
+    if (!async_idle(e)) { set_error("fjsp_env_record_schedule: environments are parked in the asynchronous arrival service; call fjsp_env_arrivals_flush first"); return FJSP_E_STATE; }
+    DeviceGuard guard(e->device);
+    const size_t N = (size_t)e->b.N;
+    // the episode state read below must include every step still queued, on whatever stream the caller used
+    HIP_TRY(hipDeviceSynchronize());
+    {   // every env must be between episodes: done (as create leaves it) or reset with nothing dispatched yet
+        int32_t *d_cnt = nullptr;
+        HIP_TRY(hipMalloc(&d_cnt, N * 5));
+        uint8_t *d_done = reinterpret_cast<uint8_t *>(d_cnt + N);
+        std::vector<int32_t> cnt(N);
+        std::vector<uint8_t> done(N);
+        const bool ok = launch_read(e->b, nullptr, nullptr, nullptr, nullptr, d_cnt, d_done, nullptr, nullptr) == 0 &&
+                        hipDeviceSynchronize() == hipSuccess &&
+                        hipMemcpy(cnt.data(), d_cnt, N * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                        hipMemcpy(done.data(), d_done, N, hipMemcpyDeviceToHost) == hipSuccess;
+        (void)hipFree(d_cnt);
+        if (!ok) { set_error("fjsp_env_record_schedule: read-back of the episode state failed"); return FJSP_E_HIP; }
+        for (size_t i = 0; i < N; ++i)
+            if (!done[i] && cnt[i] != 0) {
+                set_error("fjsp_env_record_schedule: env " + std::to_string(i) + " is mid-episode; switch recording after create, after a reset or once every env is done");
+                return FJSP_E_STATE;
+            }
+    }
+    if (!on) {
+        if (e->sched.rec) HIP_TRY(hipFree(e->sched.rec));
+        e->sched = SchedRec{};
+        return FJSP_OK;
+    }
+    if (e->sched.rec) return FJSP_OK;
+    if (e->ops_max <= 0) { set_error("fjsp_env_record_schedule: the batch has no operations"); return FJSP_E_STATE; }
+    uint4 *d = nullptr;
+    HIP_TRY(hipMalloc(&d, (size_t)e->ops_max * N * sizeof(uint4)));
+    if (hipMemset(d, 0, (size_t)e->ops_max * N * sizeof(uint4)) != hipSuccess) {
+        (void)hipFree(d);
+        set_error("fjsp_env_record_schedule: hipMemset of the record table failed");
+        return FJSP_E_HIP;
+    }
+    e->sched.rec = d;
+    e->sched.cap = e->ops_max;
+    return FJSP_OK;
+}
+
+int fjsp_env_schedule_capacity(const fjsp_env *e) { return (e && e->sched.rec) ? e->sched.cap : 0; }
+
+int fjsp_env_schedule(fjsp_env *e, int32_t *d_table, int32_t *d_len, void *stream) {
+    if (!e || !d_table) { set_error("fjsp_env_schedule: null argument"); return FJSP_E_ARG; }
+    if (!e->sched.rec) { set_error("fjsp_env_schedule: recording is off (fjsp_env_record_schedule)"); return FJSP_E_STATE; }
+    if (!async_idle(e)) { set_error("fjsp_env_schedule: environments are parked in the asynchronous arrival service; call fjsp_env_arrivals_flush first"); return FJSP_E_STATE; }
+    DeviceGuard guard(e->device);
+    if (launch_schedule_unpack(e->b, e->sched, d_table, d_len, (hipStream_t)stream) != 0) { set_error("schedule_unpack_kernel launch failed"); return FJSP_E_HIP; }
     return FJSP_OK;
 }
 

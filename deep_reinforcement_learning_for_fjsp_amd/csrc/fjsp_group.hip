@@ -195,6 +195,8 @@ struct GE {
     uint32_t res;              // fused kernel, small batches: byte offset (from g_lds) of this row's RESIDENT copy of the instance's
                                // fluid numbers, {arrival, rate} table and processing times (g_make_resident)
     int resident;              // wave-uniform (a kernel argument): the rows have resident copies; 0 = read from memory
+    uint4 *rec;                // recording kernels only (REC): the dispatch records, slot-major [rec_cap][nenv] (SchedRec)
+    int rec_cap, nenv;
 };
 
 // the (operation x machine) rows {arrival, rate} of a lane's slots, in flight while the step decides (g_cols_issue)
@@ -478,8 +480,9 @@ GDEV int g_machine_select(GE<V> &e, const DevBatch &b, bool go, int a1, int k_se
 
 // SO_FJSSP.py:176-250: dispatch job r_sel (its current operation type k_sel) on m_sel, then advance the clock until some
 // operation type is available again (or the episode ends), for the rows with `go`.  The event loop runs on the job and
-// machine lanes alone.
-template <int V>
+// machine lanes alone.  REC (recording kernels): lane 0 of every row with `go` also stores the dispatch record
+// (task.time_begin / machine / time_end, :182-184) in slot step_count of its env's column of e.rec.
+template <int V, bool REC = false>
 GDEV void g_dispatch_advance(GE<V> &e, bool go, int r_sel, int k_sel, int m_sel, int pm) {
     // the job's word, first operation | J_r, due date: from its lane
     const int rs = go ? r_sel : 0;
@@ -491,6 +494,14 @@ GDEV void g_dispatch_advance(GE<V> &e, bool go, int r_sel, int k_sel, int m_sel,
     const int nj = (int)(jw_sel & 0xFFu) + 1, Jr = (int)((ji_sel >> 8) & 0xFFu);   // the job is at stage nj - 1; it moves on
     const bool last = nj == Jr;
     const int time_end = e.t + pm;                                           // :184
+    if constexpr (REC) {
+        // one job per kind: the job number within its kind is 0
+        const bool fits = e.step_count < e.rec_cap;
+        if (go && fits && e.l == 0)
+            e.rec[(size_t)e.step_count * (uint32_t)e.nenv + (uint32_t)e.env] =
+                make_uint4((uint32_t)k_sel | ((uint32_t)m_sel << 16) | (kRecWritten << 24), 0u, (uint32_t)e.t, (uint32_t)time_end);
+        e.status |= (go && !fits) ? (uint32_t)FJSP_ST_SCHEDULE_OVERFLOW : 0u;
+    }
     const bool jmine = go && e.l == r_sel;
     e.jwl = jmine ? jst_pack(kNoSeq, (uint32_t)nj) : e.jwl;                  // :186-191
     e.emc = jmine ? em_next : e.emc;
@@ -845,7 +856,7 @@ GDEV void g_restart(GE<V> &e, const DevBatch &b, bool on) {
 #define GSTAMP_PARAM
 #define GSTAMP_ARG
 #endif
-template <int V, int MPC, bool EARLY>
+template <int V, int MPC, bool EARLY, bool REC = false>
 GDEV double g_step(GE<V> &e, const DevBatch &b, bool go_in, int a0, int a1, const MoW &mo, bool need_obs, double *state_out,
                    bool gap_need, const GCols<MPC> &cr, int *k_out, int *m_out GSTAMP_PARAM) {
     constexpr bool is_mo = V == FJSP_VARIANT_MO_FJSSP_DISCRETES;
@@ -887,7 +898,7 @@ GDEV double g_step(GE<V> &e, const DevBatch &b, bool go_in, int a0, int a1, cons
 #endif
     go = go && m_sel >= 0;
     GSTAMP(5);
-    g_dispatch_advance<V>(e, go, rs, k_sel, m_sel, pm);
+    g_dispatch_advance<V, REC>(e, go, rs, k_sel, m_sel, pm);
     GSTAMP(6);
 #if defined(FJSP_GABLATE) && FJSP_GABLATE == 4
     return 0.0;                                                                   // diagnostic: stop after dispatch_and_advance
@@ -932,100 +943,12 @@ GDEV void g_make_resident(GE<V> &e, const DevBatch &b, uint32_t block_off) {
 }
 
 // ------------------------------------------------------------------------ kernels
-// One step of every environment of a group batch (fjsp_kernels.hip step_kernel for the same batch gives the same results)
-// EARLY: request the gap_ave rows together with the state (small batches: a wave is alone on its SIMD and nothing else hides
-// the memory round trip); otherwise they are fetched where they are used and the kernel keeps to 128 registers
-template <int V, int MPC, bool EARLY>
-__global__ __launch_bounds__(EARLY ? 256 : 64, EARLY ? 1 : 4) void gstep_kernel(DevBatch b, const uint8_t *actions, const double *mo, int autoreset, double *state_out,
-                                                   double *reward_out, uint8_t *done_out, int16_t *trace_km) {
-    GE<V> e;
-    GSTAMP_DECL;
-    GSTAMP_BEGIN();
-    // (small batches are launched four waves to a workgroup -- a quarter of the workgroups to dispatch; the waves never meet)
-    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wave_id = (int)blockIdx.x * (int)(blockDim.x >> 6) + wib;
-    unsigned char *const my_lds = g_lds + (size_t)wib * group_lds_bytes<MPC, EARLY>();
-    // the action pair of the row's environment (2-byte aligned: checked by the host entry points)
-    const int env_raw = wave_id * 4 + (int)(__lane_id() >> 4);
-    const int env0 = min(env_raw, b.N - 1);
-    const uint32_t araw = reinterpret_cast<const uint16_t *>(actions)[env0];
-    MoW mw = {0.0, 1.0, 0.0, 0.0};
-    if (V == FJSP_VARIANT_MO_FJSSP_DISCRETES && mo) {
-        const double2 m01 = *reinterpret_cast<const double2 *>(mo + (size_t)env0 * 4), m23 = *reinterpret_cast<const double2 *>(mo + (size_t)env0 * 4 + 2);
-        mw.w0 = m01.x; mw.w1 = m01.y; mw.cn = m23.x; mw.tn = m23.y;
-    }
-    GCols<MPC> cr;
-    bool gap_need = false;
-    g_open<V, EARLY>(e, b, wave_id, my_lds, group_rows<MPC, EARLY>(), []() {});
-    gap_need = env_raw < b.N && rule_wants_gap_ave<V>(araw);
-    const int a0 = (int)(araw & 0xFFu), a1 = (int)(araw >> 8);
-    bool go = e.live;
-    GSTAMP(0);
-    if (wave_any(go && e.done != 0)) {
-        const bool was_done = go && e.done != 0;
-        if (autoreset == 1) g_restart<V>(e, b, was_done);
-        else {
-            if (was_done && autoreset == 0) e.status |= FJSP_ST_STEP_AFTER_DONE;      // 2: idle silently
-            go = go && !was_done;
-        }
-    }
-    int k_sel = -1, m_sel = -1;
-    GSTAMP(1);
-    // small batches: Machine.gap_ave's operands are requested now (the machines that are idle are known), used after task_select
-    if (EARLY && wave_any(gap_need && go)) g_cols_issue<V, MPC>(e, b, gap_need && go, cr);
-    const double reward = g_step<V, MPC, EARLY>(e, b, go, a0, a1, mw, state_out != nullptr, state_out, gap_need && go, cr, &k_sel, &m_sel GSTAMP_ARG);
-    if (e.live && e.l == 0) {
-        if (reward_out) reward_out[e.env] = reward;
-        if (done_out) done_out[e.env] = (uint8_t)e.done;
-        if (trace_km) { trace_km[(size_t)e.env * 2] = (int16_t)k_sel; trace_km[(size_t)e.env * 2 + 1] = (int16_t)m_sel; }
-    }
-    g_store<V>(e, b);
-    GSTAMP(8);
-    GSTAMP_FLUSH();
-}
-
-// T fused steps per launch with the actions given (rule sweeps): the environments live in registers for the whole
-// launch.  Same outputs as fjsp_kernels.hip rollout_kernel.
-template <int V, int MPC, bool EARLY>
-__global__ __launch_bounds__(EARLY ? 256 : 64, EARLY ? 1 : 2) void grollout_kernel(DevBatch b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km,
-                                                      double *reward_out, double *state_last, int resident) {
-    GE<V> e;
-    GSTAMP_DECL;
-    GSTAMP_BEGIN();
-    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wave_id = (int)blockIdx.x * (int)(blockDim.x >> 6) + wib;
-    unsigned char *const my_lds = g_lds + (size_t)wib * group_lds_bytes<MPC, EARLY>();
-    g_open<V, EARLY>(e, b, wave_id, my_lds, group_rows<MPC, EARLY>(), []() {});
-    // (small batches, one wave to a workgroup: the static tables next to the rows, see res_bytes)
-    if (!EARLY && resident) g_make_resident<V, MPC>(e, b, (uint32_t)group_lds_bytes<MPC, EARLY>() + (uint32_t)(__lane_id() >> 4) * res_bytes<MPC>());
-    MoW mw = {0.0, 1.0, 0.0, 0.0};
-    if (V == FJSP_VARIANT_MO_FJSSP_DISCRETES && mo) {
-        mw.w0 = mo[(size_t)e.env * 4]; mw.w1 = mo[(size_t)e.env * 4 + 1]; mw.cn = mo[(size_t)e.env * 4 + 2]; mw.tn = mo[(size_t)e.env * 4 + 3];
-    }
-    for (int s = 0; s < T; ++s) {
-        const size_t o = (size_t)s * b.N + e.env;
-        const bool go = e.live && !e.done && !(e.status & (FJSP_ST_BAD_TASK_RULE | FJSP_ST_BAD_MACHINE_RULE | FJSP_ST_NO_EVENT));
-        if (!wave_any(go)) {
-            if (e.live && e.l == 0) {
-                if (trace_km) { trace_km[o * 2] = -1; trace_km[o * 2 + 1] = -1; }
-                if (reward_out) reward_out[o] = 0.0;
-            }
-            continue;
-        }
-        const uint32_t araw = reinterpret_cast<const uint16_t *>(actions)[o];
-        const bool gap_need = go && rule_wants_gap_ave<V>(araw);
-        GCols<MPC> cr;
-        if (EARLY) g_cols_issue<V, MPC>(e, b, gap_need, cr);
-        int k_sel = -1, m_sel = -1;
-        const double reward = g_step<V, MPC, EARLY>(e, b, go, (int)(araw & 0xFFu), (int)(araw >> 8), mw, state_last != nullptr, state_last,
-                                             gap_need, cr, &k_sel, &m_sel GSTAMP_ARG);
-        if (e.live && e.l == 0) {
-            if (trace_km) { trace_km[o * 2] = (int16_t)k_sel; trace_km[o * 2 + 1] = (int16_t)m_sel; }
-            if (reward_out) reward_out[o] = reward;
-        }
-    }
-    g_store<V>(e, b);
-}
+#define FJSP_REC 0
+#include "fjsp_group_kernels.inc"
+#undef FJSP_REC
+#define FJSP_REC 1
+#include "fjsp_group_kernels.inc"
+#undef FJSP_REC
 
 }  // namespace grp
 
@@ -1071,28 +994,33 @@ static unsigned group_waves_per_block() {
 }
 template <int V>
 static int launch_step_group_v(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
-                               uint8_t *done, int16_t *trace_km, hipStream_t st) {
+                               uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec) {
     const bool early = group_early(b);
     const unsigned wpb = early ? group_waves_per_block() : 1u, waves = (unsigned)((b.N + 3) / 4);
     const dim3 grid((waves + wpb - 1) / wpb);
 #define FJSP_GSTEP(MPC, E) group_allow_lds(&grp::gstep_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()); hipLaunchKernelGGL((grp::gstep_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()), st, b, actions, mo, autoreset, state, reward, done, trace_km)
-    if (b.MP <= 5) { if (early) { FJSP_GSTEP(5, true); } else { FJSP_GSTEP(5, false); } }
+#define FJSP_GSTEP_REC(MPC, E) group_allow_lds(&grp::gstep_rec_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()); hipLaunchKernelGGL((grp::gstep_rec_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()), st, b, actions, mo, autoreset, state, reward, done, trace_km, rec)
+    if (rec.rec) {          // recording (fjsp_env_record_schedule): the same step, plus the dispatch records
+        if (b.MP <= 5) { if (early) { FJSP_GSTEP_REC(5, true); } else { FJSP_GSTEP_REC(5, false); } }
+        else { if (early) { FJSP_GSTEP_REC(8, true); } else { FJSP_GSTEP_REC(8, false); } }
+    } else if (b.MP <= 5) { if (early) { FJSP_GSTEP(5, true); } else { FJSP_GSTEP(5, false); } }
     else { if (early) { FJSP_GSTEP(8, true); } else { FJSP_GSTEP(8, false); } }
 #undef FJSP_GSTEP
+#undef FJSP_GSTEP_REC
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int launch_step_group(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
-                      uint8_t *done, int16_t *trace_km, hipStream_t st) {
+                      uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec) {
     if (!b.grp) return -1;
-    if (b.variant == FJSP_VARIANT_SO_FJSSP) return launch_step_group_v<FJSP_VARIANT_SO_FJSSP>(b, actions, mo, autoreset, state, reward, done, trace_km, st);
+    if (b.variant == FJSP_VARIANT_SO_FJSSP) return launch_step_group_v<FJSP_VARIANT_SO_FJSSP>(b, actions, mo, autoreset, state, reward, done, trace_km, st, rec);
     if (b.variant == FJSP_VARIANT_MO_FJSSP_DISCRETES)
-        return launch_step_group_v<FJSP_VARIANT_MO_FJSSP_DISCRETES>(b, actions, mo, autoreset, state, reward, done, trace_km, st);
+        return launch_step_group_v<FJSP_VARIANT_MO_FJSSP_DISCRETES>(b, actions, mo, autoreset, state, reward, done, trace_km, st, rec);
     return -1;
 }
 
 template <int V>
 static int launch_rollout_group_v(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
-                                  double *state_last, hipStream_t st) {
+                                  double *state_last, hipStream_t st, const SchedRec &rec) {
     const bool early = group_early_rollout(b);
     const unsigned wpb = early ? group_waves_per_block() : 1u, waves = (unsigned)((b.N + 3) / 4);
     const dim3 grid((waves + wpb - 1) / wpb);
@@ -1104,17 +1032,22 @@ static int launch_rollout_group_v(const DevBatch &b, const uint8_t *actions, con
     const int resident = (!early && (res_forced >= 0 ? res_forced != 0 : waves_per_cu * (lean_lds + res_lds) <= (size_t)152 * 1024)) ? 1 : 0;
     const size_t extra = resident ? res_lds : 0;
 #define FJSP_GROLL(MPC, E) group_allow_lds(&grp::grollout_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + extra); hipLaunchKernelGGL((grp::grollout_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + extra), st, b, actions, mo, T, trace_km, reward, state_last, resident)
-    if (b.MP <= 5) { if (early) { FJSP_GROLL(5, true); } else { FJSP_GROLL(5, false); } }
+#define FJSP_GROLL_REC(MPC, E) group_allow_lds(&grp::grollout_rec_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + extra); hipLaunchKernelGGL((grp::grollout_rec_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + extra), st, b, actions, mo, T, trace_km, reward, state_last, resident, rec)
+    if (rec.rec) {
+        if (b.MP <= 5) { if (early) { FJSP_GROLL_REC(5, true); } else { FJSP_GROLL_REC(5, false); } }
+        else { if (early) { FJSP_GROLL_REC(8, true); } else { FJSP_GROLL_REC(8, false); } }
+    } else if (b.MP <= 5) { if (early) { FJSP_GROLL(5, true); } else { FJSP_GROLL(5, false); } }
     else { if (early) { FJSP_GROLL(8, true); } else { FJSP_GROLL(8, false); } }
 #undef FJSP_GROLL
+#undef FJSP_GROLL_REC
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int launch_rollout_group(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
-                         double *state_last, hipStream_t st) {
+                         double *state_last, hipStream_t st, const SchedRec &rec) {
     if (!b.grp) return -1;
-    if (b.variant == FJSP_VARIANT_SO_FJSSP) return launch_rollout_group_v<FJSP_VARIANT_SO_FJSSP>(b, actions, mo, T, trace_km, reward, state_last, st);
+    if (b.variant == FJSP_VARIANT_SO_FJSSP) return launch_rollout_group_v<FJSP_VARIANT_SO_FJSSP>(b, actions, mo, T, trace_km, reward, state_last, st, rec);
     if (b.variant == FJSP_VARIANT_MO_FJSSP_DISCRETES)
-        return launch_rollout_group_v<FJSP_VARIANT_MO_FJSSP_DISCRETES>(b, actions, mo, T, trace_km, reward, state_last, st);
+        return launch_rollout_group_v<FJSP_VARIANT_MO_FJSSP_DISCRETES>(b, actions, mo, T, trace_km, reward, state_last, st, rec);
     return -1;
 }
 

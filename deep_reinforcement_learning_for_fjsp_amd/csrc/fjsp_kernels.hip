@@ -232,6 +232,9 @@ struct W {
     const uint16_t *pw_i;    // MO_DFJSP: power_mrj_dict, same layout as p_i
     const double *col_i;
     unsigned char *er;
+    // recording kernels only (REC): the dispatch records, slot-major [rec_cap][N] (SchedRec)
+    uint4 *rec;
+    int rec_cap;
     STAMP_FIELDS
 };
 
@@ -988,7 +991,9 @@ __device__ __forceinline__ int order_arrive(W<KC, V> &w, const DevBatch *b, int 
 
 // SO_FJSSP.py:176-250: dispatch the FIFO head of k_sel on m_sel, then advance
 // the clock until some operation type is available again (or the episode ends).
-template <int KC, int V>
+// REC (recording kernels): lane 0 also stores the dispatch record (task.time_begin / machine / time_end, :182-184) in slot
+// step_count of the env's column of w.rec.
+template <int KC, int V, bool REC = false>
 __device__ __forceinline__ void dispatch_and_advance(W<KC, V> &w, const DevBatch *b, int k_sel, int m_sel, int pm,
                                                      double un_sel, int en_sel) {
     const int cs = k_sel >> 6, ls = k_sel & 63;
@@ -997,6 +1002,7 @@ __device__ __forceinline__ void dispatch_and_advance(W<KC, V> &w, const DevBatch
     const int Jr = (int)((kb >> 8) & 0xFFu);
     int time_end = w.t + pm;                                                 // :184
     int machine_end = time_end;
+    int time_begin = w.t;                                                    // :182 (kDyn: shifted by a window covering it)
     if (V == kDyn) {
         // MO_DFJSP_breakdown.py:204-231: the windows of m_sel in file order; a window that covers the start or
         // begins inside the task stretches the task, one that begins exactly at its end only delays the machine
@@ -1005,7 +1011,7 @@ __device__ __forceinline__ void dispatch_and_advance(W<KC, V> &w, const DevBatch
         const int q1 = bko[m_sel + 1];
         for (int q = bko[m_sel]; q < q1; ++q) {
             const int bs = bk[2 * q], be = bk[2 * q + 1];
-            if (bs <= w.t && w.t < be) { time_end += be - w.t; machine_end = time_end; }
+            if (bs <= w.t && w.t < be) { time_begin += be - w.t; time_end += be - w.t; machine_end = time_end; }
             else if (w.t < bs && bs < time_end) { time_end += be - bs; machine_end = time_end; }
             else if (bs == time_end) machine_end += be - bs;
             else if (bs > time_end) break;
@@ -1015,6 +1021,18 @@ __device__ __forceinline__ void dispatch_and_advance(W<KC, V> &w, const DevBatch
         const int tl = rl(w.tlast_m, m_sel);
         if (tl >= 0) w.energy += (long long)(w.t - tl) * (long long)rl(w.ipw_m, m_sel);
         if (w.lane == m_sel) w.tlast_m = time_end;
+    }
+    if constexpr (REC) {
+        // job number within its kind (Kind.number_start + n, class_FJSSP.py:212-216): the job's index minus the kind's first
+        const int jn = w.single_job ? 0 : job - (int)(rlu(pick<KC>(w.kA, cs), ls) & 0xFFFFu);
+        if (w.step_count < w.rec_cap) {
+            if (w.lane == 0)
+                w.rec[(size_t)w.step_count * (uint32_t)b->N + (uint32_t)w.env] =
+                    make_uint4((uint32_t)k_sel | ((uint32_t)m_sel << 16) | (kRecWritten << 24), (uint32_t)jn, (uint32_t)time_begin,
+                               (uint32_t)time_end);
+        } else {
+            w.status |= FJSP_ST_SCHEDULE_OVERFLOW;
+        }
     }
     const int nj = (int)(kb & 0xFFu) + 1;       // the FIFO head of (r, j) is at stage j; it moves to j + 1
     if (w.jreg) {
@@ -1429,7 +1447,7 @@ __device__ __forceinline__ void init_episode(W<KC, V> &w, const DevBatch *b, dou
 // First half of step() (SO_FJSSP.py:168-250): rule pair -> (operation type, machine), dispatch, event loop.
 // compute_params() must be current on entry.  Returns true when the step goes on to its second half now
 // (false: an error status was set, or -- multi-order batches -- the env parked at an order arrival).
-template <int KC, int V, int RING = 2>
+template <int KC, int V, int RING = 2, bool REC = false>
 __device__ __forceinline__ bool env_step_decide(W<KC, V> &w, const DevBatch *b, int a0, int a1, int *k_out, int *m_out) {
     const bool is_mo = V == FJSP_VARIANT_MO_FJSSP_DISCRETES, is_sf = V == FJSP_VARIANT_SO_SFJSP;
     *k_out = -1; *m_out = -1;
@@ -1455,7 +1473,7 @@ __device__ __forceinline__ bool env_step_decide(W<KC, V> &w, const DevBatch *b, 
     w.rng_calls += (uint32_t)(k_sel + m_sel + pm) + (uint32_t)un_sel; return false;   // diagnostic: stop after machine_select
 #endif
     if (k_sel < 0 || m_sel < 0) return false;       // status carries the MyError / undefined-behaviour bit
-    dispatch_and_advance<KC, V>(w, b, k_sel, m_sel, pm, un_sel, en_sel);
+    dispatch_and_advance<KC, V, REC>(w, b, k_sel, m_sel, pm, un_sel, en_sel);
     STAMP(w, 4);
 #if defined(FJSP_ABLATE) && FJSP_ABLATE == 9
     return false;                                                                 // diagnostic: stop after dispatch_and_advance
@@ -1525,11 +1543,11 @@ __device__ __forceinline__ void obs_refresh(W<KC, V> &w) {
     wave_sync();
 }
 
-template <int KC, int V, int RING = 2>
+template <int KC, int V, int RING = 2, bool REC = false>
 __device__ __forceinline__ double env_step(W<KC, V> &w, const DevBatch *b, int a0, int a1, const double *mo,
                                            double *state_out, int *k_out, int *m_out, bool need_obs = true, float *x_lds = nullptr) {
     if (need_obs && w.obs_stale) obs_refresh<KC, V>(w);
-    if (!env_step_decide<KC, V, RING>(w, b, a0, a1, k_out, m_out)) return 0.0;
+    if (!env_step_decide<KC, V, RING, REC>(w, b, a0, a1, k_out, m_out)) return 0.0;
     return env_step_finish<KC, V, RING>(w, mo, state_out, need_obs, x_lds);
 }
 
@@ -1601,174 +1619,6 @@ __global__ __launch_bounds__(256) void reset_kernel(DevBatch b, const uint8_t *m
     store_dynamic<KC, V>(w, false);
 }
 
-// One step of every environment.  Single-order variants share the observation tail inside the workgroup
-// (observe_tail above): every live wave of a workgroup passes the same four barriers, whatever happened to its
-// environment (finished episode, invalid rule), so nothing below returns between the first barrier and the last.
-// SJ: one job per kind in every instance of the batch (compile-time: the single-job kernel carries none of the list walks,
-// statistics rows or their registers)
-template <int KC, int V, bool SJ>
-// (four chunks of per-lane operation state do not fit 128 VGPRs: K > 128 runs at half the occupancy instead of spilling)
-__global__ __launch_bounds__(256, KC >= 4 ? 2 : (KC == 2 ? 3 : 4)) void step_kernel(DevBatch b, const uint8_t *actions, const double *mo, int autoreset,
-                                                      double *state_out, double *reward_out, uint8_t *done_out,
-                                                      int16_t *trace_km, uint8_t *ready) {
-    constexpr bool SHARED = FJSP_SHARED_TAIL && !is_mord_v<V>;
-    const int wave = uni((int)(threadIdx.x >> 6));   // wave-uniform: keeps every record pointer in SGPRs
-    const int env_raw = blockIdx.x * (blockDim.x >> 6) + wave;
-    // the waves past the last environment of a partial workgroup address the last environment until their loads are
-    // out and leave then: no kernel argument has to arrive before the state loads can be issued
-    const int env = min(env_raw, b.N - 1);
-#if defined(FJSP_ABLATE) && FJSP_ABLATE == 5
-    return;                                     // diagnostic: launch overhead only
-#endif
-    W<KC, V> w;
-    STAMP_BEGIN(w);
-    // The action pair (wave-uniform, 2-byte aligned: checked by the host entry points) comes through the VECTOR memory
-    // path and is only moved to scalar registers after the state loads are out: a scalar load of it here would be waited
-    // for at once -- scalar loads return out of order, every wait on one drains them all -- one full memory round trip
-    // before the first state load could be issued.
-    const uint32_t araw = reinterpret_cast<const uint16_t *>(actions)[env];
-    const uint32_t lds_stride = (uint32_t)lds_bytes_per_wave(b.JP, b.MP, kWave * KC, false);
-    open_env<KC, V, SJ ? 1 : 0>(w, &b, env, fjsp_lds + wave * lds_stride, false, true, true);
-    if (env_raw >= b.N) return;                       // (a finished wave no longer counts at the workgroup's barriers)
-    const int a0 = uni((int)(araw & 0xFFu)), a1 = uni((int)(araw >> 8));
-    STAMP(w, 0);
-#if defined(FJSP_ABLATE) && FJSP_ABLATE == 4
-    store_dynamic<KC, V>(w, false);                // diagnostic: state in / state out only
-    return;
-#endif
-    if (is_mord_v<V> && ready) {
-        // asynchronous arrival service (fjsp_env_step_async): environments parked at an order arrival sit this launch
-        // out (ready = 0), one that arrival_kernel has just finished in this same call keeps the outputs it was given
-        if (w.pending == 2) { if (w.lane == 0) env_ptr<EnvScalars>(b, env, 0)->pending = 0; return; }
-        if (w.pending == 1) { if (w.lane == 0) ready[env] = 0; return; }
-    }
-    const bool need_obs = state_out != nullptr;
-    bool go = true;                  // this wave's environment takes a step in this launch
-    if (w.done) {
-        if (autoreset != 1) {        // 0: flag the misuse; 2: idle silently (non-fused rollout fallback)
-            if (autoreset == 0) w.status |= FJSP_ST_STEP_AFTER_DONE;
-            go = false;
-        } else {
-            init_episode<KC, V>(w, &b, nullptr, true);
-        }
-    } else if (w.single_job || !w.stats_ok) {
-        compute_params<KC, V>(w);            // a handful of selects; batches with longer lists found the statistics in the record
-    }
-    STAMP(w, 1);
-#if defined(FJSP_ABLATE) && FJSP_ABLATE == 3
-    store_dynamic<KC, V>(w, false);                // diagnostic: + compute_params
-    return;
-#endif
-    int k_sel = -1, m_sel = -1;
-    double reward = 0.0;
-    const double *mo_e = mo ? mo + (size_t)env * 4 : nullptr;
-    if constexpr (!SHARED) {
-        if (go) reward = env_step<KC, V, 8>(w, &b, a0, a1, mo_e, state_out, &k_sel, &m_sel, need_obs);
-        if (go && w.pending) {
-            // an order arrived inside this step: park the env for the host LP service (fjsp_env.hip), which
-            // finishes the step with arrival_kernel; the outputs of this env are written there
-            if (w.lane == 0) {
-                int16_t *stash = reinterpret_cast<int16_t *>(w.er + b.L.e_lpq) + 2 * b.KP;
-                stash[0] = (int16_t)k_sel; stash[1] = (int16_t)m_sel;
-            }
-            // take a slot of the service's staging area and leave the LP inputs there: the host fetches the
-            // inputs of all parked envs with one copy
-            uint32_t slot = 0;
-            if (w.lane == 0) { slot = atomicAdd(b.pending_count, 1u); if (slot < (uint32_t)b.N) b.pending_count[1 + slot] = (uint32_t)env; }
-            slot = min(uniu(slot), (uint32_t)b.N - 1u);     // (N slots: an env parks at most once per service; see service_arrivals)
-            wave_sync_global();
-            const uint32_t *src = reinterpret_cast<const uint32_t *>(w.er + b.L.e_lpq);     // u16[2][KP] as KP words
-            uint32_t *dst = reinterpret_cast<uint32_t *>(b.lp_in + (size_t)slot * 2 * b.KP);
-            for (int i = w.lane; i < b.KP; i += kWave) dst[i] = src[i];
-            if (ready && w.lane == 0) ready[env] = 0;
-            store_dynamic<KC, V>(w, false, false);        // (statistics are stale until arrival_kernel finishes the step)
-            return;
-        }
-    } else {
-        if (go && need_obs && w.obs_stale) obs_refresh<KC, V>(w);
-        if (go) go = env_step_decide<KC, V, 8>(w, &b, a0, a1, &k_sel, &m_sel);
-#if defined(FJSP_ABLATE) && (FJSP_ABLATE == 7 || FJSP_ABLATE == 8 || FJSP_ABLATE == 9)
-        store_dynamic<KC, V>(w, false);
-        return;
-#endif
-        double frv[KC], grv[KC];
-        long long tard_unproc = 0;
-        if (go) {
-            w.step_count++;                                                  // SO_FJSSP.py:252
-            compute_params<KC, V>(w);
-            STAMP(w, 5);
-#if !(defined(FJSP_ABLATE) && FJSP_ABLATE == 2)
-            tard_unproc = observe_prepare<KC, V>(w, !need_obs, frv, grv);
-#endif
-            STAMP(w, 6);
-        }
-#if !(defined(FJSP_ABLATE) && FJSP_ABLATE == 2)
-        if (need_obs) {              // (uniform over the grid: a kernel argument)
-            // the walker runs the sequential tail of every environment of the workgroup; slots whose wave has
-            // nothing to observe (finished episode, error) announce an empty row
-            const int nslots = min(4, b.N - (int)blockIdx.x * 4);
-            const int walker = min((int)(blockIdx.x & 3u), nslots - 1);
-            if (!go && w.lane == 0) w.hdrL[H_N8] = 0;
-            tail_sync<true>();
-            STAMP(w, 7);
-            if (wave == walker) tail_pass<V, 8>(fjsp_lds, lds_stride, nslots, kWave * KC);
-            tail_sync<true>();
-            STAMP(w, 8);
-            if (go) { observe_deviations<KC, V>(w, frv, grv); wave_sync(); }     // (the standard deviations: no walk, no barrier)
-            STAMP(w, 9);
-            STAMP(w, 10);
-            if (go) {
-                observe_finish<KC, V, 8>(w);
-#if !(defined(FJSP_ABLATE) && FJSP_ABLATE == 1)
-                emit_state<KC, V>(w, state_out, false);
-#endif
-                STAMP(w, 11);
-            }
-        } else if (go) {
-            w.obs_stale = 1;
-        }
-#endif
-        if (go) reward = step_reward<KC, V>(w, mo_e, V == FJSP_VARIANT_SO_SFJSP ? 0 : tard_unproc);
-    }
-    if (w.lane == 0) {
-        if (reward_out) reward_out[env] = reward;
-        if (done_out) done_out[env] = (uint8_t)w.done;
-        if (trace_km) { trace_km[(size_t)env * 2] = (int16_t)k_sel; trace_km[(size_t)env * 2 + 1] = (int16_t)m_sel; }
-        if (ready) ready[env] = 1;
-    }
-    store_dynamic<KC, V>(w, false);
-    STAMP(w, 12);
-    STAMP_FLUSH(w);
-}
-
-// T fused steps per launch: the environment lives in registers + LDS for the whole episode.
-template <int KC, int V>
-__global__ __launch_bounds__(256, (KC == 1 && V == FJSP_VARIANT_SO_FJSSP) ? 4 : 1) void rollout_kernel(DevBatch b, const uint8_t *actions, const double *mo, int T,
-                                                      int16_t *trace_km, double *reward_out, double *state_last) {
-    const int wave = uni((int)(threadIdx.x >> 6));   // wave-uniform: keeps every record pointer in SGPRs
-    const int env = blockIdx.x * (blockDim.x >> 6) + wave;
-    if (env >= b.N) return;
-    W<KC, V> w;
-    open_env<KC, V>(w, &b, env, fjsp_lds + wave * lds_bytes_per_wave(b.JP, b.MP, b.KP, true), true, true);
-    compute_params<KC, V>(w);
-    for (int s = 0; s < T; ++s) {
-        const size_t o = (size_t)s * b.N + env;
-        int k_sel = -1, m_sel = -1;
-        double reward = 0.0;
-        const bool live = !w.done && !(w.status & (FJSP_ST_BAD_TASK_RULE | FJSP_ST_BAD_MACHINE_RULE | FJSP_ST_NO_EVENT));
-        if (live) {
-            const int a0 = actions[o * 2], a1 = actions[o * 2 + 1];
-            reward = env_step<KC, V>(w, &b, uni(a0), uni(a1), mo ? mo + (size_t)env * 4 : nullptr, state_last, &k_sel, &m_sel,
-                                     state_last != nullptr);
-        }
-        if (w.lane == 0) {
-            if (trace_km) { trace_km[o * 2] = (int16_t)k_sel; trace_km[o * 2 + 1] = (int16_t)m_sel; }
-            if (reward_out) reward_out[o] = reward;
-        }
-    }
-    store_dynamic<KC, V>(w, true);
-}
-
 // ------------------------------------------------------------------ policy inside the launch
 // Actor forward for a batch of states, one wavefront per state, 16 per workgroup, weights in LDS: the per-step
 // counterpart of what rollout_policy_kernel evaluates in place (same device function, same arithmetic).
@@ -1787,68 +1637,12 @@ __global__ __launch_bounds__(1024) void actor_forward_kernel(ActorParams ap, con
     if (lane < ap.A) probs[(size_t)row * ap.A + lane] = ps[lane];
 }
 
-// The T-step rollout with the actor inside the launch (replaces the per-step loop MPPPO.py:245-252: policy
-// inference, sampling, env.step, buffer append): one wavefront per environment for the whole episode, sixteen
-// per workgroup sharing the actor's weights in LDS.  Per step: actor_probs on the current state, sample_action
-// by lane 0 (the counter-based stream of fjsp_policy_sample: same seed, same actions as the per-step path),
-// the environment step, the buffer row.  Finished environments idle; their rows are marked invalid.
-template <int KC, int V>
-__global__ __launch_bounds__(1024) void rollout_policy_kernel(DevBatch b, ActorParams ap, PolicyRolloutIO io, const double *mo, int T) {
-    float *lds = reinterpret_cast<float *>(fjsp_lds);
-    actor_lds_fill(lds, ap, (int)threadIdx.x, (int)blockDim.x);
-    __syncthreads();                                   // (the only workgroup barrier: waves may leave after it)
-    const int wave = uni((int)(threadIdx.x >> 6));
-    const int env = blockIdx.x * 16 + wave;
-    if (env >= b.N) return;
-    const uint32_t env_stride = (uint32_t)lds_bytes_per_wave(b.JP, b.MP, b.KP, false);
-    unsigned char *wave_lds = fjsp_lds + ((actor_lds_floats(ap.S) * 4 + 255) & ~(size_t)255) +
-                              (size_t)wave * (env_stride + (32 + kActorH + kActorAP) * 4);
-    float *xs = reinterpret_cast<float *>(wave_lds + env_stride);
-    float *hs = xs + 32, *ps = hs + kActorH;
-    W<KC, V> w;
-    open_env<KC, V>(w, &b, env, wave_lds, false, true);
-    compute_params<KC, V>(w);
-    const int S = ap.S, A = ap.A, N = b.N;
-    if (w.lane < S) xs[w.lane] = (float)io.state_in[(size_t)env * S + w.lane];
-    const float eps = io.epsilon[0];
-    const uint64_t seed = io.seed[0];
-    const double *mo_e = mo ? mo + (size_t)env * 4 : nullptr;
-    wave_sync();
-    for (int t = 0; t < T; ++t) {
-        const size_t row = (size_t)t * N + env;
-        const bool live = !w.done && !(w.status & (FJSP_ST_BAD_TASK_RULE | FJSP_ST_BAD_MACHINE_RULE | FJSP_ST_NO_EVENT));
-        if (!live) {
-            if (w.done) w.status |= FJSP_ST_STEP_AFTER_DONE;       // what the per-step loop flags for the same launches
-            // (rows of finished environments are masked by `valid`; they still get finite contents -- the last state,
-            // like the per-step loop leaves there -- because masked arithmetic multiplies them by zero)
-            if (w.lane < S) { io.o_state[row * S + w.lane] = xs[w.lane]; io.o_next[row * S + w.lane] = xs[w.lane]; }
-            if (w.lane == 0) {
-                io.o_valid[row] = 0.0f; io.o_reward[row] = 0.0f; io.o_done[row] = 1.0f;
-                io.o_actions[row * 2] = 0.0f; io.o_actions[row * 2 + 1] = 0.0f; io.o_flat[row] = 0.0f; io.o_logp[row] = 0.0f;
-            }
-            continue;
-        }
-        if (w.lane < S) io.o_state[row * S + w.lane] = xs[w.lane];
-        actor_probs(lds, xs, hs, ps, S, A);
-        int action = 0;
-        float logp = 0.0f;
-        if (w.lane == 0) {
-            const SampledAction sa = sample_action(ps, A, eps, seed, (uint64_t)t, env);
-            action = sa.action; logp = sa.log_prob;
-        }
-        action = uni(action);
-        const int a0 = io.pair_div > 0 ? action / io.pair_div : action, a1 = io.pair_div > 0 ? action % io.pair_div : 0;
-        int k_sel, m_sel;
-        const double reward = env_step<KC, V>(w, &b, a0, a1, mo_e, io.state_last, &k_sel, &m_sel, true, xs);
-        if (w.lane < S) io.o_next[row * S + w.lane] = xs[w.lane];
-        if (w.lane == 0) {
-            io.o_actions[row * 2] = (float)a0; io.o_actions[row * 2 + 1] = (float)a1;
-            io.o_reward[row] = (float)reward; io.o_done[row] = (float)w.done; io.o_valid[row] = 1.0f;
-            io.o_flat[row] = (float)action; io.o_logp[row] = logp;
-        }
-    }
-    store_dynamic<KC, V>(w, false, false);
-}
+#define FJSP_REC 0
+#include "fjsp_kernels_dispatch.inc"
+#undef FJSP_REC
+#define FJSP_REC 1
+#include "fjsp_kernels_dispatch.inc"
+#undef FJSP_REC
 
 // Multi-order: finish the step of every env parked at an order arrival.  The host service has solved the
 // fluid LP of the env's live state (class_FJSSP.py:239) and left x in the env record; this kernel runs
@@ -1985,11 +1779,25 @@ int launch_reset(const DevBatch &b, const uint8_t *mask, double *state, hipStrea
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int launch_step(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
-                uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready) {
-    if (b.grp && !ready) return launch_step_group(b, actions, mo, autoreset, state, reward, done, trace_km, st);
+                uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready, const SchedRec &rec) {
+    if (b.grp && !ready) return launch_step_group(b, actions, mo, autoreset, state, reward, done, trace_km, st, rec);
     const size_t lds = step_lds_bytes(b);
     if (dispatch(b, [&](auto kc, auto v) {
             constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            if (rec.rec) {         // recording (fjsp_env_record_schedule): the same step, plus the dispatch records
+                if constexpr (!is_mord_v<V>) {
+                    if (b.single_job) {
+                        allow_lds(&step_rec_kernel<KC, V, true>, lds);
+                        hipLaunchKernelGGL((step_rec_kernel<KC, V, true>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, autoreset, state,
+                                           reward, done, trace_km, ready, rec);
+                        return;
+                    }
+                }
+                allow_lds(&step_rec_kernel<KC, V, false>, lds);
+                hipLaunchKernelGGL((step_rec_kernel<KC, V, false>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, autoreset, state, reward,
+                                   done, trace_km, ready, rec);
+                return;
+            }
             if constexpr (!is_mord_v<V>) {
                 if (b.single_job) {
                     allow_lds(&step_kernel<KC, V, true>, lds);
@@ -2006,11 +1814,17 @@ int launch_step(const DevBatch &b, const uint8_t *actions, const double *mo, int
 }
 size_t rollout_lds_bytes(const DevBatch &b) { return 4 * lds_bytes_per_wave(b.JP, b.MP, b.KP, true); }
 int launch_rollout(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
-                   double *state_last, hipStream_t st) {
-    if (b.grp) return launch_rollout_group(b, actions, mo, T, trace_km, reward, state_last, st);
+                   double *state_last, hipStream_t st, const SchedRec &rec) {
+    if (b.grp) return launch_rollout_group(b, actions, mo, T, trace_km, reward, state_last, st, rec);
     const size_t lds = rollout_lds_bytes(b);
     if (dispatch(b, [&](auto kc, auto v) {
             constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            if (rec.rec) {
+                allow_lds(&rollout_rec_kernel<KC, V>, lds);
+                hipLaunchKernelGGL((rollout_rec_kernel<KC, V>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, T, trace_km, reward,
+                                   state_last, rec);
+                return;
+            }
             allow_lds(&rollout_kernel<KC, V>, lds);
             hipLaunchKernelGGL((rollout_kernel<KC, V>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, T, trace_km, reward,
                                state_last);
@@ -2028,12 +1842,19 @@ int launch_actor_forward(const ActorParams &ap, const double *state, int n, floa
     hipLaunchKernelGGL(actor_forward_kernel, dim3((unsigned)((n + 15) / 16)), dim3(1024), lds, st, ap, state, n, probs);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
-int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st) {
+int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st,
+                          const SchedRec &rec) {
     if (b.mord || b.KC != 1) return -1;                 // order arrivals need the host LP service between steps; K <= 64
     const size_t lds = policy_rollout_lds_bytes(b, ap.S);
     if (dispatch(b, [&](auto kc, auto v) {
             constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
             if constexpr (!is_mord_v<V> && KC == 1) {
+                if (rec.rec) {
+                    allow_lds(&rollout_policy_rec_kernel<KC, V>, lds);
+                    hipLaunchKernelGGL((rollout_policy_rec_kernel<KC, V>), dim3((unsigned)((b.N + 15) / 16)), dim3(1024), lds, st, b, ap, io, mo, T,
+                                       rec);
+                    return;
+                }
                 allow_lds(&rollout_policy_kernel<KC, V>, lds);
                 hipLaunchKernelGGL((rollout_policy_kernel<KC, V>), dim3((unsigned)((b.N + 15) / 16)), dim3(1024), lds, st, b, ap, io, mo, T);
             }
@@ -2052,6 +1873,36 @@ int launch_arrival(const DevBatch &b, const double *mo, int n_pending, const uin
     };
     const int rc = b.variant == FJSP_VARIANT_MO_DFJSP ? dispatch_kc<kDyn>(b.KC, go) : dispatch_kc<kMord>(b.KC, go);
     if (rc != 0) return -1;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// fjsp_env_schedule: the slot-major records of every env -> i32[N][cap][6] (r, j, n, m, begin, end), one thread per (env, slot);
+// slots at or past the env's step_count hold -1.  k -> (r, j) from the instance record's kind words (i_kB).
+__global__ __launch_bounds__(256) void schedule_unpack_kernel(DevBatch b, SchedRec rec, int32_t *table, int32_t *len) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)b.N * (size_t)rec.cap) return;
+    const int env = (int)(idx / (size_t)rec.cap), slot = (int)(idx % (size_t)rec.cap);
+    const int n = env_ptr<const EnvScalars>(b, env, 0)->step_count;
+    if (len && slot == 0) len[env] = n;
+    int32_t *o = table + idx * 6;
+    if (slot >= n) {
+        for (int q = 0; q < 6; ++q) o[q] = -1;
+        return;
+    }
+    const uint4 r4 = rec.rec[(size_t)slot * (uint32_t)b.N + (uint32_t)env];
+    const int k = (int)(r4.x & 0xFFFFu);
+    const bool ok = ((r4.x >> 24) & kRecWritten) && k < b.KP;
+    const uint32_t kb = ok ? inst_ptr<const uint32_t>(b, env % b.n_inst, b.L.i_kB)[k] : 0xFFFFFFFFu;
+    o[0] = ok ? (int)((kb >> 16) & 0xFFu) : -1;
+    o[1] = ok ? (int)(kb & 0xFFu) : -1;
+    o[2] = ok ? (int)r4.y : -1;
+    o[3] = ok ? (int)((r4.x >> 16) & 0xFFu) : -1;
+    o[4] = ok ? (int)r4.z : -1;
+    o[5] = ok ? (int)r4.w : -1;
+}
+int launch_schedule_unpack(const DevBatch &b, const SchedRec &rec, int32_t *table, int32_t *len, hipStream_t st) {
+    const size_t n = (size_t)b.N * (size_t)rec.cap;
+    if (!rec.rec || n == 0) return -1;
+    hipLaunchKernelGGL(schedule_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b, rec, table, len);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int launch_read(const DevBatch &b, int64_t *delay, int32_t *makespan, int32_t *completion, int32_t *step_time,

@@ -53,6 +53,12 @@ class BatchedMODFJSP(object):
     def read(self):
         return self.batch.read()
 
+    def record_schedule(self, on=True):
+        return self.batch.record_schedule(on)
+
+    def schedule(self, out=None):
+        return self.batch.schedule(out)
+
 
 class MO_DFJSP_Environment(object):
     """Drop-in for environments/MO_DFJSP_breakdown.py:12 (N = 1 view of the batched kernels).

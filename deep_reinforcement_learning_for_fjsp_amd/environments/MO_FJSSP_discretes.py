@@ -51,6 +51,12 @@ class BatchedMOFJSSP(object):
     def read(self):
         return self.batch.read()
 
+    def record_schedule(self, on=True):
+        return self.batch.record_schedule(on)
+
+    def schedule(self, out=None):
+        return self.batch.schedule(out)
+
 
 class MO_FJSSP_Environment(object):
     """Drop-in for environments/MO_FJSSP_discretes.py:12 (N = 1 view of the batched kernels)."""

@@ -60,6 +60,12 @@ class BatchedSOFJSSP(object):
     def read(self):
         return self.batch.read()
 
+    def record_schedule(self, on=True):
+        return self.batch.record_schedule(on)
+
+    def schedule(self, out=None):
+        return self.batch.schedule(out)
+
     def check_status(self):
         """Raise what the reference would have raised for the first env with an error bit."""
         st = self.batch.read()["status"].cpu().numpy()

@@ -39,6 +39,12 @@ class BatchedSOSFJSP(object):
     def read(self):
         return self.batch.read()
 
+    def record_schedule(self, on=True):
+        return self.batch.record_schedule(on)
+
+    def schedule(self, out=None):
+        return self.batch.schedule(out)
+
 
 class SO_SFJSP_Environment(object):
     """Drop-in for environments/SO_SFJSP.py:11 (N = 1 view of the batched kernels)."""

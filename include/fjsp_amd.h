@@ -50,7 +50,9 @@ enum {
     FJSP_ST_BAD_TASK_RULE = 1,    /* MyError, SO_FJSSP.py:297                          */
     FJSP_ST_BAD_MACHINE_RULE = 2, /* MyError, SO_FJSSP.py:321                          */
     FJSP_ST_STEP_AFTER_DONE = 4,  /* reference: undefined (ValueError on max([]))      */
-    FJSP_ST_NO_EVENT = 8          /* reference: ValueError min([]) at SO_FJSSP.py:207  */
+    FJSP_ST_NO_EVENT = 8,         /* reference: ValueError min([]) at SO_FJSSP.py:207  */
+    FJSP_ST_SCHEDULE_OVERFLOW = 16 /* a dispatch record had no slot left (never expected:
+                                      the table holds every operation of the instance) */
 };
 
 /* environment variants sharing the SO_FJSSP skeleton */
@@ -236,6 +238,26 @@ int fjsp_env_read(fjsp_env *e, int64_t *d_delay_time_sum, int32_t *d_makespan, i
 int fjsp_env_machine_time_end(fjsp_env *e, int32_t *d_tend, int32_t m_stride, void *stream);
 /* energy_consumption i64[N] of a FJSP_VARIANT_MO_DFJSP batch (MO_DFJSP_breakdown.py:253-256). */
 int fjsp_env_energy(fjsp_env *e, int64_t *d_energy, void *stream);
+/* The dispatched schedule (SO_FJSSP.py:176-196: task.time_begin / machine / time_end and machine.task_list, with the
+ * breakdown shifts of MO_DFJSP_breakdown.py:203-247).  While recording is on, every dispatch -- fjsp_env_step(_traced),
+ * fjsp_env_step_async (in the call where the step dispatched, before it parks), fjsp_env_rollout and
+ * fjsp_env_rollout_policy, both kernel families -- stores one 16-byte record in slot step_count of its env; the plain
+ * kernels run while it is off.  The table always holds each env's CURRENT episode: after a step that returns done it
+ * holds the finished one until the env is reset, explicitly or by autoreset at its next step, so callers that use
+ * autoreset read it after the done step.
+ *
+ * fjsp_env_record_schedule: on != 0 allocates the [cap][N] record table (cap = operations of the largest instance of the
+ * batch, sum over orders and kinds of count[s][r] * J_r, orders that arrive later included) and selects the recording
+ * kernels; on == 0 frees it.  FJSP_E_STATE if any env is mid-episode (call after create or when every env is done).
+ * Synchronises the device first, so steps still queued on any stream are taken into account. */
+int fjsp_env_record_schedule(fjsp_env *e, int32_t on);
+/* cap (slots per env), 0 when recording is off. */
+int fjsp_env_schedule_capacity(const fjsp_env *e);
+/* SO_FJSSP.py:182-184 per dispatched operation: d_table i32[N][cap][6] = (r, j, n, m, time_begin, time_end) in dispatch
+ * order -- kind r, stage j, job number n within kind r (counted over all orders, class_FJSSP.py:212-216), machine m --
+ * and -1 past d_len[i]; d_len i32[N] (nullable) = the env's step_count.  Stream-ordered, no host synchronisation.
+ * FJSP_E_STATE when recording is off or envs are parked at an order arrival (fjsp_env_arrivals_flush first). */
+int fjsp_env_schedule(fjsp_env *e, int32_t *d_table, int32_t *d_len, void *stream);
 /* fluid tables of env i copied to host (tests): rate/arr [K*M] k-major, rate_sum/time_sum [K]. */
 int fjsp_env_fluid_tables(fjsp_env *e, int32_t i, double *h_rate, double *h_arr,
                           double *h_rate_sum, double *h_time_sum);
