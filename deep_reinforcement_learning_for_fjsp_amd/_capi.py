@@ -46,6 +46,7 @@ SIGNATURES = {
     "fjsp_instances_set_x": (C.c_int, [_vp, _i32, _vp]),
     "fjsp_fluid_lp": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "fjsp_env_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _pp]),
+    "fjsp_env_create_family": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _i32, _pp]),
     "fjsp_env_destroy": (None, [_vp]),
     "fjsp_env_num_envs": (C.c_int, [_vp]),
     "fjsp_env_state_size": (C.c_int, [_vp]),
@@ -64,6 +65,15 @@ SIGNATURES = {
     "fjsp_env_schedule_capacity": (C.c_int, [_vp]),
     "fjsp_env_schedule": (C.c_int, [_vp, _vp, _vp, _vp]),
     "fjsp_env_energy": (C.c_int, [_vp, _vp, _vp]),
+    "fjsp_snapshot_create": (C.c_int, [_vp, _i32, _pp]),
+    "fjsp_snapshot_destroy": (None, [_vp]),
+    "fjsp_snapshot_size": (C.c_int, [_vp]),
+    "fjsp_snapshot_capacity": (C.c_int, [_vp]),
+    "fjsp_snapshot_save": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "fjsp_snapshot_load": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "fjsp_snapshot_errors": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "fjsp_snapshot_to_host": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
+    "fjsp_snapshot_from_host": (C.c_int, [_vp, _vp, _i64, _pp]),
     "fjsp_env_fluid_tables": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
     "fjsp_env_step_bytes": (_i64, [_vp]),
     "fjsp_env_kernel_family": (_i32, [_vp]),

@@ -86,14 +86,84 @@ def _check_output(name, t, shape, dtype, device):
     return t
 
 
+class EnvSnapshot(object):
+    """Saved states of n environments (fjsp_snapshot_*; EnvBatch.snapshot / restore).
+
+    On the device: every entry's env record -- the whole episode state the kernels keep -- and, when the batch recorded
+    its schedule, the entry's dispatch records.  Next to them, as device tensors: the rows of the batch's `state`,
+    `reward` and `done` tensors AS THE LAST CALL LEFT THEM (after step(state=False) or rollout(state=False) the state
+    rows are stale, as the record's obs_stale flag says; the next call that returns a state rebuilds it), and `instance`
+    int32[n], the instance index (env % n_inst) of every entry.  `env_ids` is the saved env of every entry (numpy, None
+    when the snapshot was taken with a device index tensor).  A snapshot loads into any batch that plays the same
+    instances with the same variant and kernel family, whatever its N (FJSP_E_ARG otherwise)."""
+
+    def __init__(self, lib, handle, n, n_inst, device, env_ids, instance, state, reward, done):
+        self._lib, self._h = lib, handle
+        self.n, self.n_inst, self.device = int(n), int(n_inst), device
+        self.env_ids, self.instance = env_ids, instance
+        self.state, self.reward, self.done = state, reward, done
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self._lib.fjsp_snapshot_destroy(h)
+            self._h = None
+
+    @property
+    def capacity(self):
+        """Dispatch-record slots per entry (0: the snapshot holds no schedule records)."""
+        return int(self._lib.fjsp_snapshot_capacity(self._h))
+
+    def errors(self):
+        """Loads refused since the last call because the entry came from another instance (fjsp_snapshot_errors;
+        synchronises)."""
+        n = C.c_int64(0)
+        check(self._lib.fjsp_snapshot_errors(self._h, C.byref(n)))
+        return int(n.value)
+
+    def instance_host(self):
+        """int64 numpy array: the instance index of every entry."""
+        return self.instance.cpu().numpy().astype(np.int64)
+
+    def to_bytes(self):
+        """The snapshot as bytes (device buffer + compatibility fingerprint + the state / reward / done rows)."""
+        import io
+        n = C.c_int64(0)
+        check(self._lib.fjsp_snapshot_to_host(self._h, None, C.byref(n)))
+        blob = np.empty(int(n.value), np.uint8)
+        check(self._lib.fjsp_snapshot_to_host(self._h, blob.ctypes.data_as(C.c_void_p), C.byref(n)))
+        f = io.BytesIO()
+        np.savez(f, blob=blob, state=self.state.cpu().numpy(), reward=self.reward.cpu().numpy(), done=self.done.cpu().numpy(),
+                 instance=self.instance.cpu().numpy(), n_inst=np.int64(self.n_inst),
+                 env_ids=self.env_ids if self.env_ids is not None else np.full(0, -1, np.int64))
+        return f.getvalue()
+
+    @classmethod
+    def from_bytes(cls, batch, data):
+        """A snapshot on `batch`'s device from to_bytes() output; FJSP_E_ARG unless `batch` plays the instances (variant,
+        kernel family) the bytes were saved from."""
+        import io
+        z = np.load(io.BytesIO(data), allow_pickle=False)
+        blob = np.ascontiguousarray(z["blob"])
+        h = C.c_void_p()
+        check(batch._lib.fjsp_snapshot_from_host(batch._h, blob.ctypes.data_as(C.c_void_p), int(blob.size), C.byref(h)))
+        dev = batch.device
+        env_ids = z["env_ids"] if z["env_ids"].size else None
+        return cls(batch._lib, h, int(batch._lib.fjsp_snapshot_size(h)), int(z["n_inst"]), dev, env_ids,
+                   torch.as_tensor(z["instance"]).to(dev), torch.as_tensor(z["state"]).to(dev),
+                   torch.as_tensor(z["reward"]).to(dev), torch.as_tensor(z["done"]).to(dev))
+
+
 class EnvBatch(object):
     """fjsp_env handle + the device tensors it writes into."""
 
     def __init__(self, instances, n_envs, first=0, n_inst=None, variant=VARIANT_SO_FJSSP, device=0, rng_seed=0,
-                 first_env=0):
+                 first_env=0, kernel_family=None):
         """first_env: GLOBAL id of this batch's environment 0 when the batch is one shard of a larger job (one
         rank of `bench.py --gpus N` / examples/train_ppo.py).  The random.choice stream of an environment is a
-        function of its global id, so the traces of a sharded job equal the unsharded job's bit for bit."""
+        function of its global id, so the traces of a sharded job equal the unsharded job's bit for bit.
+        kernel_family: None = the library's choice (row kernels where the batch fits them, unless FJSP_STEP_IMPL=wave),
+        0 = one wave per environment, 1 = the row kernels (fjsp_env_create_family; FjspError if the batch does not fit)."""
         if not torch.cuda.is_available():
             raise RuntimeError("EnvBatch needs an MI355X: the environment kernels have no CPU path")
         self._lib = _capi.lib()
@@ -105,8 +175,14 @@ class EnvBatch(object):
         self.first_env = int(first_env)
         # the kernels seed env e (local) with seed + e * ENV_SEED_STRIDE: shift the base by the shard's offset
         lib_seed = (int(rng_seed) + self.first_env * ENV_SEED_STRIDE) & (2 ** 64 - 1)
-        check(self._lib.fjsp_env_create(instances.handle, int(first), int(n_inst), int(n_envs), int(variant),
-                                        self.device_index, lib_seed, C.byref(self._h)))
+        if kernel_family is None:
+            check(self._lib.fjsp_env_create(instances.handle, int(first), int(n_inst), int(n_envs), int(variant),
+                                            self.device_index, lib_seed, C.byref(self._h)))
+        else:
+            if kernel_family not in (0, 1):
+                raise ValueError("kernel_family must be None, 0 or 1, got %r" % (kernel_family,))
+            check(self._lib.fjsp_env_create_family(instances.handle, int(first), int(n_inst), int(n_envs), int(variant),
+                                                   self.device_index, lib_seed, int(kernel_family), C.byref(self._h)))
         self.N = int(n_envs)
         self.n_inst = int(n_inst)
         self.first = int(first)
@@ -262,6 +338,103 @@ class EnvBatch(object):
         check(self._lib.fjsp_env_rollout(self._h, _ptr(actions), _ptr(mo), int(T), _ptr(tr), _ptr(rw),
                                          _ptr(self.state) if state else None, self._stream()))
         return tr, rw, (self.state if state else None)
+
+    # -- saved states ----------------------------------------------------------------
+    def snapshot(self, envs=None, out=None):
+        """Save the episode state of envs (None: every env; a host sequence / numpy array, or an int device tensor,
+        of env indices) into a new EnvSnapshot, or into `out` (an EnvSnapshot of this fingerprint with as many entries).
+        Stream-ordered: no host synchronisation unless `envs` is on the host.  The dispatch records are saved too while
+        the batch records its schedule (record_schedule).  Host indices outside [0, N) raise ValueError; a device index
+        outside [0, N) leaves an empty entry (instance -1, zero rows) that every restore refuses, and the kernel counts it
+        (snap.errors())."""
+        valid = None
+        if envs is None:
+            n, idx, env_ids = self.N, None, np.arange(self.N, dtype=np.int64)
+            rows = slice(None)
+        elif torch.is_tensor(envs) and envs.device.type != "cpu":
+            idx = envs.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+            n, env_ids = idx.numel(), None
+            valid = (idx >= 0) & (idx < self.N)
+            rows = idx.long().clamp(0, self.N - 1)
+        else:
+            env_ids = np.asarray(envs.cpu() if torch.is_tensor(envs) else envs, dtype=np.int64).reshape(-1)
+            if env_ids.size == 0 or env_ids.min() < 0 or env_ids.max() >= self.N:
+                raise ValueError("snapshot(): env indices must lie in [0, %d)" % self.N)
+            n = env_ids.size
+            idx = torch.as_tensor(env_ids.astype(np.int32)).to(self.device)
+            rows = idx.long()
+        if out is None:
+            h = C.c_void_p()
+            check(self._lib.fjsp_snapshot_create(self._h, int(n), C.byref(h)))
+            snap = EnvSnapshot(self._lib, h, n, self.n_inst, self.device, None, None, None, None, None)
+        else:
+            if not isinstance(out, EnvSnapshot) or out.n != n:
+                raise ValueError("snapshot(out=...): an EnvSnapshot with %d entries is needed" % n)
+            snap = out
+        check(self._lib.fjsp_snapshot_save(snap._h, self._h, _ptr(idx), self._stream()))
+        snap.env_ids = env_ids
+        if idx is None:
+            snap.instance = torch.arange(self.N, dtype=torch.int32, device=self.device) % self.n_inst
+        else:
+            snap.instance = idx % self.n_inst
+        snap.state, snap.reward, snap.done = self.state[rows].clone(), self.reward[rows].clone(), self.done[rows].clone()
+        if valid is not None:          # (the same rule as the kernel: an entry of a bad index is never loaded)
+            snap.instance = torch.where(valid, snap.instance, torch.full_like(snap.instance, -1))
+            snap.state.masked_fill_(~valid[:, None], 0.0); snap.reward.masked_fill_(~valid, 0.0); snap.done.masked_fill_(~valid, 0)
+        return snap
+
+    def restore(self, snap, src=None, check=False, rows=True):
+        """Load saved states: env i <- entry src[i] wherever src[i] >= 0 (src: int[N], -1 = keep env i; None: entry i
+        for i < snap.n).  The entry must come from an env of the same instance (i % n_inst): a host `src` (or None) is
+        checked here, before anything is launched (ValueError); a device `src` is checked by the kernel, which leaves a
+        mismatched env untouched and counts it (snap.errors(); check=True calls it and raises ValueError).  The rows of
+        `state` / `reward` / `done` are restored with the envs (see EnvSnapshot); rows=False skips them (they are then
+        left as they were, not those of the loaded states: for callers that go on with state=False and read(), such as
+        the lookahead's branch batch).  Random rules replay bit for bit only in the env slot (and batch rng_seed /
+        first_env) the entry was saved from; deterministic rules anywhere."""
+        if not isinstance(snap, EnvSnapshot):
+            raise ValueError("restore(): an EnvSnapshot is needed")
+        if snap.n_inst != self.n_inst:
+            raise ValueError("restore(): the snapshot was taken from a batch of %d instances, this one has %d" % (snap.n_inst, self.n_inst))
+        if src is None or not (torch.is_tensor(src) and src.device.type != "cpu"):
+            if src is None:
+                h_src = np.full(self.N, -1, np.int64)
+                m = min(self.N, snap.n)
+                h_src[:m] = np.arange(m)
+            else:
+                h_src = np.asarray(src.cpu() if torch.is_tensor(src) else src, dtype=np.int64).reshape(-1)
+                if h_src.shape != (self.N,):
+                    raise ValueError("restore(): src must have %d entries, got %d" % (self.N, h_src.size))
+            use = h_src >= 0
+            if np.any(h_src[use] >= snap.n):
+                raise ValueError("restore(): src entries must lie in [-1, %d)" % snap.n)
+            inst = snap.env_ids % self.n_inst if snap.env_ids is not None else snap.instance_host()
+            bad = np.nonzero(use & (inst[np.where(use, h_src, 0)] != np.arange(self.N) % self.n_inst))[0]
+            if bad.size:
+                raise ValueError("restore(): env %d plays instance %d, entry %d holds instance %d"
+                                 % (bad[0], bad[0] % self.n_inst, h_src[bad[0]], inst[h_src[bad[0]]]))
+            d_src = None if src is None else torch.as_tensor(h_src.astype(np.int32)).to(self.device)
+            s = torch.as_tensor(h_src).to(self.device) if rows else None
+        else:
+            d_src = src.to(dtype=torch.int32).contiguous().reshape(-1)
+            if d_src.numel() != self.N:
+                raise ValueError("restore(): src must have %d entries, got %d" % (self.N, d_src.numel()))
+            s = d_src.long()
+        rc = self._lib.fjsp_snapshot_load(snap._h, self._h, _ptr(d_src), self._stream())
+        if rc < 0:
+            _capi.check(rc)
+        if rows:        # the rows of state / reward / done follow the same rule as the kernel
+            ar = torch.arange(self.N, dtype=torch.int64, device=self.device)
+            sc = s.clamp(0, snap.n - 1)
+            take = (s >= 0) & (s < snap.n) & (snap.instance.long()[sc] == ar % self.n_inst)
+            self.state.copy_(torch.where(take[:, None], snap.state[sc], self.state))
+            self.reward.copy_(torch.where(take, snap.reward[sc], self.reward))
+            self.done.copy_(torch.where(take, snap.done[sc], self.done))
+        if check:
+            bad = snap.errors()
+            if bad:
+                raise ValueError("restore(): %d envs were given an entry of another instance and kept their state" % bad)
+        return self
 
     # -- read back -----------------------------------------------------------------
     def read(self):

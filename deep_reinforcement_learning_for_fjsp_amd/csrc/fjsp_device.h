@@ -224,6 +224,19 @@ int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const Policy
                           const SchedRec &rec = SchedRec{});
 // the recorded schedule as the public table (fjsp_env_schedule): i32[N][cap][6] = (r, j, n, m, begin, end), -1 past len[i]
 int launch_schedule_unpack(const DevBatch &b, const SchedRec &rec, int32_t *table, int32_t *len, hipStream_t st);
+// saved env states (fjsp_snapshot.hip; buffer layout there): n entries of e_stride bytes, their headers, [cap][n]
+// dispatch records (cap == 0: none), and the device counter of loads refused for an instance mismatch
+struct SnapBuf {
+    unsigned char *env = nullptr;
+    int2 *hdr = nullptr;
+    uint4 *rec = nullptr;
+    unsigned long long *err = nullptr;
+    int32_t n = 0, cap = 0;
+};
+// entry q <- env idx[q] (idx == nullptr: env q); records too when rec.rec != nullptr and s.cap > 0 (then s.cap == rec.cap)
+int launch_snapshot_save(const DevBatch &b, const SchedRec &rec, const SnapBuf &s, const int32_t *idx, hipStream_t st);
+// env i <- entry src[i] where src[i] >= 0 and the entry's instance is i % n_inst (src == nullptr: entry i for i < s.n)
+int launch_snapshot_load(const DevBatch &b, const SchedRec &rec, const SnapBuf &s, const int32_t *src, hipStream_t st);
 int launch_read(const DevBatch &b, int64_t *delay, int32_t *makespan, int32_t *completion, int32_t *step_time,
                 int32_t *step_count, uint8_t *done, uint32_t *status, hipStream_t st);
 

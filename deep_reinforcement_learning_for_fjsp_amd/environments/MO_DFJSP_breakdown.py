@@ -17,7 +17,7 @@ import torch
 from .. import instances as _inst
 from ..batch import EnvBatch, VARIANT_MO_DFJSP
 from ..utilities.Utility_Class import MyError
-from .SO_FJSSP import _MachineView, _raise_for_status
+from .SO_FJSSP import _MachineView, _episode_getstate, _episode_setstate, _raise_for_status
 
 
 class BatchedMODFJSP(object):
@@ -58,6 +58,12 @@ class BatchedMODFJSP(object):
 
     def schedule(self, out=None):
         return self.batch.schedule(out)
+
+    def snapshot(self, envs=None, out=None):
+        return self.batch.snapshot(envs, out)
+
+    def restore(self, snap, src=None, check=False, rows=True):
+        return self.batch.restore(snap, src, check, rows)
 
 
 class MO_DFJSP_Environment(object):
@@ -106,6 +112,13 @@ class MO_DFJSP_Environment(object):
         self.reward = None
         self._act = torch.zeros(1, 2, dtype=torch.uint8, device=self._batch.device)
         self._mo = torch.zeros(1, 4, dtype=torch.float64, device=self._batch.device)
+
+    # pickling / copy.deepcopy carry the episode: the copy continues from the same point, independently of the original
+    def __getstate__(self):
+        return _episode_getstate(self)
+
+    def __setstate__(self, st):
+        _episode_setstate(self, st)
 
     def _refresh(self):
         vals = {k: int(v.item()) for k, v in self._batch.read().items()}

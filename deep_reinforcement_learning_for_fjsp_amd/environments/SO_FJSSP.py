@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import instances as _inst
-from ..batch import (EnvBatch, ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT, ST_STEP_AFTER_DONE,
+from ..batch import (EnvBatch, EnvSnapshot, ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT, ST_STEP_AFTER_DONE,
                      VARIANT_SO_FJSSP)
 from ..utilities.Utility_Class import MyError
 
@@ -30,6 +30,39 @@ def _raise_for_status(status):
         raise ValueError("step() called on a finished episode (reference: max() arg is an empty sequence)")
     if status & ST_NO_EVENT:
         raise ValueError("min() arg is an empty sequence")   # SO_FJSSP.py:207
+
+
+# -- pickling / deepcopy with the episode (shared by the drop-in classes) ---------------------------------------------
+_DEVICE_ATTRS = ("_set", "_batch", "_arrays")          # rebuilt on load
+_TENSOR_ATTRS = ("_actions", "_act", "_mo")            # per-class staging tensors: travel as host tensors
+
+
+def _episode_getstate(env):
+    """The env's instance (arrays, machine data), its batch's construction arguments, its Python-side attributes and
+    a snapshot of the episode on the device (EnvSnapshot.to_bytes)."""
+    a = env._set.arrays(0)
+    dyn = (a.power, a.idle_power, a.bk_n, a.bk) if hasattr(a, "power") else None
+    b = env._batch
+    attrs = {k: v for k, v in env.__dict__.items() if k not in _DEVICE_ATTRS and k not in _TENSOR_ATTRS}
+    tensors = {k: getattr(env, k).cpu() for k in _TENSOR_ATTRS if hasattr(env, k)}
+    return dict(arrays=(a.Jr, a.p, a.elig_n, a.elig_list, a.count, a.arrive, a.delivery, a.ddt, a.x), dynamic=dyn,
+                variant=b.variant, device=b.device_index, rng_seed=b.rng_seed, attrs=attrs, tensors=tensors,
+                episode=b.snapshot().to_bytes())
+
+
+def _episode_setstate(env, st):
+    """Inverse of _episode_getstate: a new batch of one env on the same instance and random stream (slot 0, same
+    rng_seed: random rules continue bit for bit), the attributes, and the episode loaded into it."""
+    Jr, p, elig_n, elig_list, count, arrive, delivery, ddt, x = st["arrays"]
+    env._set = _inst.InstanceSet(1).set_raw(0, Jr, p, elig_n, elig_list, count, arrive, delivery, ddt).set_x(0, x)
+    if st["dynamic"] is not None:
+        env._set.set_dynamic(0, *st["dynamic"])
+    env._arrays = env._set.arrays(0)
+    env._batch = EnvBatch(env._set, 1, variant=st["variant"], device=st["device"], rng_seed=st["rng_seed"])
+    env.__dict__.update(st["attrs"])
+    for k, v in st["tensors"].items():
+        setattr(env, k, v.to(env._batch.device))
+    env._batch.restore(EnvSnapshot.from_bytes(env._batch, st["episode"]))
 
 
 class BatchedSOFJSSP(object):
@@ -65,6 +98,12 @@ class BatchedSOFJSSP(object):
 
     def schedule(self, out=None):
         return self.batch.schedule(out)
+
+    def snapshot(self, envs=None, out=None):
+        return self.batch.snapshot(envs, out)
+
+    def restore(self, snap, src=None, check=False, rows=True):
+        return self.batch.restore(snap, src, check, rows)
 
     def check_status(self):
         """Raise what the reference would have raised for the first env with an error bit."""
@@ -134,13 +173,18 @@ class SO_FJSSP_Environment(object):
         self.completion_time = 0
         self._actions = torch.zeros(1, 2, dtype=torch.uint8, device=self._batch.device)
 
-    # pickling: A3C hands whole env objects to worker processes (A3C_v5.1.py:147-156)
+    # pickling: A3C hands whole env objects to worker processes (A3C_v5.1.py:147-156).  The copy carries the episode:
+    # it continues from the same point, independently of the original (copy.deepcopy goes the same way)
     def __getstate__(self):
-        a = self._arrays
-        return dict(arrays=(a.Jr, a.p, a.elig_n, a.elig_list, a.count, a.arrive, a.delivery, a.ddt, a.x),
-                    file_name=self.file_name, device=self._device, rng_seed=self._rng_seed)
+        st = _episode_getstate(self)
+        st.update(file_name=self.file_name)
+        return st
 
     def __setstate__(self, st):
+        if "episode" in st:
+            _episode_setstate(self, st)
+            return
+        # a state dict without an episode (instance arrays, file name, device, seed): a fresh env, as before
         Jr, p, elig_n, elig_list, count, arrive, delivery, ddt, x = st["arrays"]
         self._device, self.file_name = st["device"], st["file_name"]
         self._set = _inst.InstanceSet(1).set_raw(0, Jr, p, elig_n, elig_list, count, arrive, delivery, ddt).set_x(0, x)

@@ -11,7 +11,7 @@ import torch
 from .. import instances as _inst
 from ..batch import EnvBatch, VARIANT_SO_SFJSP
 from ..utilities.Utility_Class import MyError
-from .SO_FJSSP import _MachineView, _raise_for_status
+from .SO_FJSSP import _MachineView, _episode_getstate, _episode_setstate, _raise_for_status
 
 
 class BatchedSOSFJSP(object):
@@ -44,6 +44,12 @@ class BatchedSOSFJSP(object):
 
     def schedule(self, out=None):
         return self.batch.schedule(out)
+
+    def snapshot(self, envs=None, out=None):
+        return self.batch.snapshot(envs, out)
+
+    def restore(self, snap, src=None, check=False, rows=True):
+        return self.batch.restore(snap, src, check, rows)
 
 
 class SO_SFJSP_Environment(object):
@@ -80,6 +86,13 @@ class SO_SFJSP_Environment(object):
         self.done = False
         self.state = None
         self._act = torch.zeros(1, 2, dtype=torch.uint8, device=self._batch.device)
+
+    # pickling / copy.deepcopy carry the episode: the copy continues from the same point, independently of the original
+    def __getstate__(self):
+        return _episode_getstate(self)
+
+    def __setstate__(self, st):
+        _episode_setstate(self, st)
 
     def _refresh(self):
         vals = {k: int(v.item()) for k, v in self._batch.read().items()}

@@ -1,0 +1,216 @@
+"""Rollout lookahead over fixed dispatching rules (the rollout algorithm with fixed actions as base heuristics).
+
+At every decision each environment of the source batch is branched once per candidate action: the episode state is
+saved (EnvBatch.snapshot) and loaded into a branch batch of P x N envs on the same instances (EnvBatch.restore, branch
+env p * N + i <- source env i), branch block p plays candidate p to the end of the episode in one fused launch, and the
+source env takes the candidate whose branch ended with the lowest objective (the first one on ties).
+
+With deterministic candidates the dynamics and the objective are functions of the action sequence, so following the
+chosen candidate from the next state reproduces its branch's objective: the objective the lookahead reaches is never
+above the best fixed candidate's.  Random-rule candidates (SO_FJSSP task rule 6 / machine rule 5 style
+random.choice rules) are allowed, but a branch continues on its own slot's random stream, so the bound does not hold
+for them.  Out of scope: truncated horizons and learned base policies.
+"""
+import numpy as np
+import torch
+
+from .batch import (EnvBatch, ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT, ST_SCHEDULE_OVERFLOW, VARIANT_MO_DFJSP,
+                    VARIANT_MO_FJSSP_DISCRETES, VARIANT_SO_DFJSP, VARIANT_SO_FJSSP, VARIANT_SO_SFJSP)
+
+OBJECTIVES = ("makespan", "tardiness", "energy")
+_FLAT = (VARIANT_SO_SFJSP, VARIANT_MO_FJSSP_DISCRETES)
+# valid actions per variant: (task rules, machine rules) of the pair variants, flat action count of the flat ones
+ACTION_RANGES = {VARIANT_SO_FJSSP: (6, 5), VARIANT_SO_DFJSP: (6, 5), VARIANT_MO_DFJSP: (12, 10),     # SO_FJSSP.py:30, MO_DFJSP_breakdown.py:32
+                 VARIANT_SO_SFJSP: (20,), VARIANT_MO_FJSSP_DISCRETES: (18,)}                       # SO_SFJSP.py:25, MO_FJSSP_discretes.py:26
+# status bits that stop an env for good (it will never be done): a rule index the env does not have, no next event,
+# a dispatch record with no slot
+_ERR_BITS = ST_BAD_TASK_RULE | ST_BAD_MACHINE_RULE | ST_NO_EVENT | ST_SCHEDULE_OVERFLOW
+
+
+def _objective_values(batch, objective, r=None):
+    r = batch.read() if r is None else r
+    if callable(objective):
+        v = objective(r)
+        if not torch.is_tensor(v) or v.shape != (batch.N,):
+            raise ValueError("objective(read()) must return a tensor of shape (%d,)" % batch.N)
+        return v.to(torch.float64)
+    if objective == "makespan":
+        return r["makespan"].to(torch.float64)
+    if objective == "tardiness":
+        return r["delay_time_sum"].to(torch.float64)
+    if objective == "energy":
+        if "energy_consumption" not in r:
+            raise ValueError("objective 'energy' needs a MO_DFJSP batch")
+        return r["energy_consumption"].to(torch.float64)
+    raise ValueError("objective must be one of %s or a callable on read()" % (OBJECTIVES,))
+
+
+def candidate_pairs(candidates, variant):
+    """uint8[P, 2] action pairs of the candidates: (task rule, machine rule) pairs, or flat action indices for the
+    flat-action variants (SO_SFJSP, MO_FJSSP_discretes).  Every candidate must be an action of the variant (ValueError
+    otherwise): an env given an undefined rule stops with an error bit and would never finish its rollout."""
+    if variant not in ACTION_RANGES:
+        raise ValueError("unknown variant %r" % (variant,))
+    rng = ACTION_RANGES[variant]
+    if len(candidates) == 0:
+        raise ValueError("rollout_dispatch: at least one candidate is needed")
+    out = np.zeros((len(candidates), 2), np.int64)
+    for p, c in enumerate(candidates):
+        if variant in _FLAT:
+            if np.ndim(c) != 0:
+                raise ValueError("this variant takes flat actions (ints), got %r" % (c,))
+            out[p, 0] = int(c)
+        else:
+            if np.ndim(c) != 1 or len(c) != 2:
+                raise ValueError("this variant takes (task rule, machine rule) pairs, got %r" % (c,))
+            out[p] = [int(c[0]), int(c[1])]
+        if not all(0 <= out[p, q] < rng[q] for q in range(len(rng))):
+            raise ValueError("candidate %r is not an action of this variant (%s)"
+                             % (c, "flat actions 0..%d" % (rng[0] - 1) if len(rng) == 1 else
+                                "task rules 0..%d, machine rules 0..%d" % (rng[0] - 1, rng[1] - 1)))
+    return out.astype(np.uint8)
+
+
+def check_branch_shape(n_envs, n_inst, n_candidates):
+    """The branch batch holds n_candidates x n_envs envs; branch env p * N + i plays instance (p * N + i) % n_inst,
+    which is source env i's instance only when N is a multiple of n_inst."""
+    if n_candidates <= 0:
+        raise ValueError("rollout_dispatch: at least one candidate is needed")
+    if n_envs % n_inst != 0:
+        raise ValueError("rollout_dispatch: the source batch's N (%d) must be a multiple of its instance count (%d)"
+                         % (n_envs, n_inst))
+    return n_candidates * n_envs
+
+
+def make_branch(batch, n_candidates):
+    """An EnvBatch of n_candidates x N envs on the source batch's instances, variant and kernel family (asked for
+    explicitly: the record layouts of the two families differ, and the snapshot fingerprint includes the family)."""
+    n = check_branch_shape(batch.N, batch.n_inst, n_candidates)
+    return EnvBatch(batch.instances, n, first=batch.first, n_inst=batch.n_inst, variant=batch.variant,
+                    device=batch.device_index, rng_seed=batch.rng_seed, first_env=batch.first_env,
+                    kernel_family=batch.kernel_family)
+
+
+def _check_status(r, who):
+    bad = (r["status"].long() & _ERR_BITS) != 0
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0, 0].item())
+        raise RuntimeError("rollout_dispatch: %s env %d carries error status %d (FJSP_ST_* bits): it cannot finish its "
+                           "episode" % (who, i, int(r["status"][i].item())))
+
+
+def _ops_per_env(batch):
+    ops = []
+    for i in range(batch.n_inst):
+        a = batch.instances.arrays(batch.first + i)
+        ops.append(int((np.asarray(a.count).reshape(a.S, a.R) * np.asarray(a.Jr)[None, :]).sum()))
+    ops = np.asarray(ops, np.int64)
+    return torch.as_tensor(ops[np.arange(batch.N) % batch.n_inst], device=batch.device)
+
+
+def rollout_dispatch(batch, candidates, objective, mo=None, branch=None, timings=None):
+    """Play every env of `batch` (an EnvBatch or a Batched* wrapper, reset and not yet stepped, or mid-episode) to the end,
+    choosing at every decision the candidate whose rollout to the end gives the lowest objective.
+
+    candidates: P action pairs (task rule, machine rule), or flat actions for SO_SFJSP / MO_FJSSP_discretes.
+    objective: "makespan", "tardiness" (delay_time_sum), "energy" (MO_DFJSP) or a callable taking read()'s dict and
+    returning a tensor[N] to minimise.  mo: f64[N, 4] step arguments of the MO variants (as EnvBatch.step takes them).
+    branch: an EnvBatch of P x N envs made by make_branch (reused across calls), or None to build one.
+    timings: a dict that receives the seconds spent per part (snapshot, restore, rollout, read, step), synchronised.
+
+    Returns dict(actions=uint8[D, N, 2] numpy, the action applied at decision d (env i's d-th step from here; rows past
+    an env's end repeat its last choice and are not applied), steps=int[N] decisions each env took, objective=tensor[N]
+    of the finished episodes, branch=the branch batch)."""
+    batch = getattr(batch, "batch", batch)
+    pairs = candidate_pairs(candidates, batch.variant)
+    P, N = len(pairs), batch.N
+    check_branch_shape(N, batch.n_inst, P)
+    if branch is None:
+        branch = make_branch(batch, P)
+    elif (not isinstance(branch, EnvBatch) or branch.N != P * N or branch.n_inst != batch.n_inst
+          or branch.kernel_family != batch.kernel_family):
+        raise ValueError("rollout_dispatch: branch must be an EnvBatch of %d envs on the source's instances and kernel family"
+                         % (P * N))
+    dev = batch.device
+    if mo is not None:
+        mo = torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).contiguous()
+        mo_branch = mo.repeat(P, 1).contiguous()
+    else:
+        mo_branch = None
+    pairs_dev = torch.as_tensor(pairs, device=dev)                                  # [P, 2]
+    branch_act = pairs_dev[:, None, :].expand(P, N, 2).reshape(P * N, 2)            # one candidate per block
+    src = np.tile(np.arange(N, dtype=np.int64), P)
+    ops = _ops_per_env(batch)
+    branch_ops = ops.repeat(P)
+    snap, src_dev = None, None
+    chosen_all, steps = [], torch.zeros(N, dtype=torch.int64, device=dev)
+    last = torch.zeros(N, 2, dtype=torch.uint8, device=dev)
+    act_buf = None
+    clock = _Clock(timings, dev)
+    prev_live, prev_count = None, None
+    while True:
+        r = batch.read()
+        _check_status(r, "source")
+        live = r["done"] == 0
+        count = r["step_count"].long()
+        if prev_live is not None and bool((prev_live & live & (count <= prev_count)).any()):
+            raise RuntimeError("rollout_dispatch: a source env did not advance in its step")
+        if not bool(live.any()):
+            break
+        prev_live, prev_count = live, count
+        T = int(torch.where(live, ops - r["step_count"].long(), torch.zeros_like(ops)).max().item())
+        clock.start()
+        snap = batch.snapshot(out=snap)
+        clock.lap("snapshot")
+        if src_dev is None:
+            branch.restore(snap, src, rows=False)     # the branch map, validated once on the host
+            src_dev = torch.as_tensor(src.astype(np.int32), device=dev)
+        else:
+            branch.restore(snap, src_dev, rows=False)   # (the branch plays with state=False: its state rows are not needed)
+        clock.lap("restore")
+        if act_buf is None or act_buf.shape[0] < T:
+            act_buf = branch_act[None].expand(T, P * N, 2).contiguous()
+        branch.rollout(act_buf[:T], trace=False, rewards=False, mo=mo_branch, state=False)
+        clock.lap("rollout")
+        rb = branch.read()
+        _check_status(rb, "branch")
+        while not bool((rb["done"] != 0).all()):       # (every step dispatches one operation: not expected to run)
+            before = rb["step_count"].long()
+            left = int((branch_ops - before).clamp(min=1).max().item())
+            if act_buf.shape[0] < left:
+                act_buf = branch_act[None].expand(left, P * N, 2).contiguous()
+            branch.rollout(act_buf[:left], trace=False, rewards=False, mo=mo_branch, state=False)
+            rb = branch.read()
+            _check_status(rb, "branch")
+            if not bool(((rb["done"] != 0) | (rb["step_count"].long() > before)).all()):
+                raise RuntimeError("rollout_dispatch: a branch env neither finished nor advanced")
+        cost = _objective_values(branch, objective, rb).reshape(P, N)
+        best = torch.argmin(cost, dim=0)                                             # first minimum over candidates
+        clock.lap("read")
+        act = torch.where(live[:, None], pairs_dev[best], last)
+        batch.rollout(act[None].contiguous(), trace=False, rewards=False, mo=mo, state=False)
+        clock.lap("step")
+        steps += live.long()
+        last = act
+        chosen_all.append(act)
+    actions = torch.stack(chosen_all).cpu().numpy() if chosen_all else np.zeros((0, N, 2), np.uint8)
+    return dict(actions=actions, steps=steps.cpu().numpy(), objective=_objective_values(batch, objective), branch=branch)
+
+
+class _Clock(object):
+    def __init__(self, timings, dev):
+        self.t, self.dev, self.t0 = timings, dev, None
+
+    def start(self):
+        if self.t is not None:
+            import time
+            torch.cuda.synchronize(self.dev)
+            self.t0 = time.perf_counter()
+
+    def lap(self, what):
+        if self.t is not None:
+            import time
+            torch.cuda.synchronize(self.dev)
+            now = time.perf_counter()
+            self.t[what] = self.t.get(what, 0.0) + now - self.t0
+            self.t0 = now

@@ -152,6 +152,12 @@ typedef struct fjsp_env fjsp_env;
  * variant: FJSP_VARIANT_*; FJSP_VARIANT_MO_DFJSP needs instances with machine data. */
 int  fjsp_env_create(const fjsp_instances *s, int32_t first, int32_t n_inst, int32_t n_envs,
                      int32_t variant, int32_t device, uint64_t rng_seed, fjsp_env **out);
+/* fjsp_env_create with the kernel family chosen by the caller instead of the environment (fjsp_env_kernel_family):
+ * family -1 = as fjsp_env_create (row kernels where the batch fits them unless FJSP_STEP_IMPL=wave), 0 = one wave per
+ * environment, 1 = the row kernels (FJSP_E_UNSUPPORTED if the batch does not fit them).  The environment variable is
+ * not read for 0 and 1: a batch that must match another one's family (a snapshot's fingerprint) is made this way. */
+int  fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_inst, int32_t n_envs, int32_t variant,
+                            int32_t device, uint64_t rng_seed, int32_t family, fjsp_env **out);
 void fjsp_env_destroy(fjsp_env *e);
 int  fjsp_env_num_envs(const fjsp_env *e);
 int  fjsp_env_state_size(const fjsp_env *e);   /* 20 (SO_FJSSP) / 18 (SO_SFJSP) / 25 (MO_FJSSP_discretes) / 30 (MO_DFJSP) */
@@ -258,6 +264,52 @@ int fjsp_env_schedule_capacity(const fjsp_env *e);
  * and -1 past d_len[i]; d_len i32[N] (nullable) = the env's step_count.  Stream-ordered, no host synchronisation.
  * FJSP_E_STATE when recording is off or envs are parked at an order arrival (fjsp_env_arrivals_flush first). */
 int fjsp_env_schedule(fjsp_env *e, int32_t *d_table, int32_t *d_len, void *stream);
+/* ------------------------------------------------------------------------- *
+ * Saved environment states (csrc/fjsp_snapshot.hip): copy, rewind and branch episodes on the device
+ * ------------------------------------------------------------------------- */
+typedef struct fjsp_snapshot fjsp_snapshot;
+
+/* A snapshot holds n entries; an entry is one env's whole record (the episode state the kernels keep per env) and, if
+ * the snapshot was created while `e` was recording its schedule, the env's dispatch records.  It is bound to e's
+ * FINGERPRINT, not to e: the record layout, the shape fields of the batch (operation / machine / job paddings, variant,
+ * kernel family, number of instances) and a hash of the packed instance slab.  Any batch with the same fingerprint --
+ * the same instances played by the same variant and kernel family, whatever its N -- may save into it and load from
+ * it; any other batch gets FJSP_E_ARG.
+ * Save and load are stream-ordered, do not synchronise with the host and can be captured in a graph.  Both return
+ * FJSP_E_STATE while envs are parked in the asynchronous arrival service (fjsp_env_arrivals_flush first) and once the
+ * batch's arrival service has failed.
+ * RANDOM RULES: an env draws random.choice from the stream of its SLOT (rng_seed + env * 1000003, with the draw counter
+ * in its record).  An entry loaded into another slot, or into a batch with another rng_seed or first env, continues on
+ * that slot's stream: only a load into the same global env id replays the random rules bit for bit.  Deterministic
+ * rules replay exactly wherever the entry is loaded.
+ *
+ * fjsp_snapshot_create: n entries, sized for e's layout, plus cap dispatch records per entry if e records at that
+ * moment (fjsp_env_record_schedule). */
+int  fjsp_snapshot_create(const fjsp_env *e, int32_t n, fjsp_snapshot **out);
+void fjsp_snapshot_destroy(fjsp_snapshot *s);
+int  fjsp_snapshot_size(const fjsp_snapshot *s);        /* n */
+int  fjsp_snapshot_capacity(const fjsp_snapshot *s);    /* dispatch-record slots per entry, 0 = none */
+/* entry q <- env d_idx[q] of e (d_idx i32[n], device; NULL: envs 0..n-1, FJSP_E_ARG if n > N), with its dispatch
+ * records when e records and s has room for them.  An entry remembers its instance (env % n_inst); an index outside
+ * [0, N) leaves an entry that every load refuses and counts as an error (fjsp_snapshot_errors). */
+int fjsp_snapshot_save(fjsp_snapshot *s, fjsp_env *e, const int32_t *d_idx, void *stream);
+/* env i <- entry d_src[i] for every i with d_src[i] >= 0 (d_src i32[N], device, -1 = keep env i; NULL: entry i for
+ * i < n).  The kernel refuses an entry saved from another instance than i % n_inst (or an index >= n): env i is left
+ * untouched and the snapshot's device error counter grows.  Nothing is ever written into an env of another instance.
+ * If e records its schedule the entries' dispatch records are loaded too; FJSP_E_STATE if the last save into s was
+ * from a batch that did not record (s holds no records).  A snapshot with records loads into a batch that does not
+ * record; the records are then ignored. */
+int fjsp_snapshot_load(fjsp_snapshot *s, fjsp_env *e, const int32_t *d_src, void *stream);
+/* Synchronises the device, returns the number of loads refused since the last call (and of bad save indices) in
+ * *count, and clears the counter. */
+int fjsp_snapshot_errors(fjsp_snapshot *s, int64_t *count);
+/* Serialised form (pickling): h_out == NULL -> *nbytes = the size needed; otherwise copies the fingerprint and the
+ * buffer into h_out (*nbytes: its size in, the size written out).  Synchronises the device first.
+ * fjsp_snapshot_from_host: a new snapshot on e's device from those bytes; FJSP_E_ARG unless e has the fingerprint the
+ * bytes were saved with. */
+int fjsp_snapshot_to_host(fjsp_snapshot *s, void *h_out, int64_t *nbytes);
+int fjsp_snapshot_from_host(const fjsp_env *e, const void *h_in, int64_t nbytes, fjsp_snapshot **out);
+
 /* fluid tables of env i copied to host (tests): rate/arr [K*M] k-major, rate_sum/time_sum [K]. */
 int fjsp_env_fluid_tables(fjsp_env *e, int32_t i, double *h_rate, double *h_arr,
                           double *h_rate_sum, double *h_time_sum);
