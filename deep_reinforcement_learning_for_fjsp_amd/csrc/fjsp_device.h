@@ -94,7 +94,7 @@ struct Layout {
     // group-kernel batches only (DevBatch::grp): the static per-operation rows once more, packed for one 16-lane row per
     // environment -- slot s (k = 16 s + l): 16 x uint4 {kB, elig | fmask << 8, due date of the kind's job, 0}, then
     // 16 x double2 {fluid_rate_sum, fluid_time_sum}: two 16-byte loads per lane and slot  [written by fluid_tables_kernel];
-    // behind the four slots one line of per-lane words (machine / job / instance: fjsp_env.hip) and the jobs' due dates
+    // behind the four slots one line of per-lane words (machine / job / instance: pack_row_words, fjsp_env.hip) and the jobs' due dates
     uint32_t i_op;
     // ... and the {arrival, rate} table once more MACHINE-major, f64[MP][64][2]: Machine.gap_ave reads whole machines, and in
     // large batches only the candidate ones (fjsp_group.hip g_gap_ave_lean: 5 lines per candidate instead of the whole table)
@@ -121,8 +121,8 @@ struct Layout {
     uint32_t e_lpq;     // u16[2][KP] LP inputs of the pending arrival: Q[k], n_now[k]; then i16[2] stashed (k, m) of the step
 };
 
-// Offsets that follow from the padded sizes alone (the host's layout code in fjsp_env.hip places these fields first,
-// in this order, and fjsp_env_create verifies the two agree): the kernels take them from here -- compile-time for the
+// Offsets that follow from the padded sizes alone (the host's layout code, plan_layout in fjsp_env.hip, places these fields
+// first, in this order, and verifies the two agree): the kernels take them from here -- compile-time for the
 // per-k rows, two shifts for the head of the env record -- instead of fetching them from the kernel arguments, and the
 // constants fold into the loads' immediate offsets.
 struct FixedOffsets {

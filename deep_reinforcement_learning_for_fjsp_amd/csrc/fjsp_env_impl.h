@@ -1,0 +1,89 @@
+// The env handle behind the C ABI, shared by fjsp_env.hip (create, step, read-back), fjsp_arrivals.hip (order-arrival
+// services) and fjsp_snapshot.hip (saved states).  Private: not part of include/fjsp_amd.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/fjsp_amd.h"
+#include "fjsp_device.h"
+#include "fjsp_host.h"
+
+namespace fjsp {
+struct LpCache; struct LpPool; struct AsyncRing;   // fjsp_arrivals.hip
+
+// What only the order-arrival services of multi-order batches use (fjsp_arrivals.hip)
+struct ArrivalService {
+    // pinned staging of the blocking host service: [0] = count, then env ids | LP inputs per slot | solutions per slot
+    uint32_t *h_pending = nullptr;
+    uint16_t *h_lp_in = nullptr;
+    double *h_lp_x = nullptr;
+    LpPool *pool = nullptr;
+    AsyncRing *ring = nullptr;  // the asynchronous service (fjsp_env_step_async), built by its first call
+    LpCache *cache = nullptr;   // solved LPs of the host services
+    int lp_threads = 0;         // 0 = default (min(host cores, 16))
+    int64_t lp_solves = 0;      // order-arrival LPs solved so far (host services)
+    int64_t parked = 0;         // envs currently parked in the asynchronous service (host view)
+    // device LP service (fjsp_lp_device.hip): chosen at create time when the largest tableau of the batch fits the CU's LDS
+    bool lp_device = false;
+    size_t lp_lds = 0;
+    uint32_t *d_lp_err = nullptr;                // [0] nonzero: an LP failed on the device (reported at the next synchronising call)
+    unsigned long long *d_lp_solved = nullptr;   // LPs solved on the device so far, [1] their pivots
+};
+}  // namespace fjsp
+
+struct fjsp_env {
+    fjsp::DevBatch b{};
+    int device = 0;
+    std::vector<void *> dev_allocs, host_allocs;   // device / pinned memory, freed by fjsp_env_destroy
+    std::vector<int> inst_K, inst_M;   // per packed instance
+    int ops_max = 0;                   // operations of the largest instance, orders that arrive later included (schedule slots)
+    fjsp::SchedRec sched;              // dispatch records while recording is on (fjsp_env_record_schedule); rec == nullptr: off
+    uint64_t inst_hash = 0;            // FNV-1a of the packed instance slab as uploaded (snapshot compatibility, fjsp_snapshot_*)
+    int64_t step_bytes = 0;
+    uint8_t *d_done_scratch = nullptr; // scratch for the non-fused rollout fallback
+    const fjsp_instances *src = nullptr;   // the instances [first, first + n_inst) the batch plays (the host LPs read them)
+    int first = 0;
+    bool failed = false;        // the arrival service failed mid-step: parked envs are in limbo, the handle refuses further steps
+    fjsp::ArrivalService arr;
+};
+
+namespace fjsp {
+inline bool hip_ok(hipError_t e, const char *what) {
+    if (e == hipSuccess) return true;
+    set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return false;
+}
+#define HIP_TRY(expr)                                  \
+    do {                                               \
+        if (!hip_ok((expr), #expr)) return FJSP_E_HIP; \
+    } while (0)
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        // (the common case -- the caller is already on the batch's device -- costs one hipGetDevice: the per-step
+        // calls are launch-bound on the host)
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev); else prev = -1;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// The refusals the entry points share, after their own argument checks; who names the entry point in the message.
+// kIntact: the arrival service has not failed; kIdle: no env is parked in the asynchronous service; d_actions, if
+// given, is 2-byte aligned.
+enum : unsigned { kIntact = 1, kIdle = 2 };
+int usable(const fjsp_env *e, const char *who, unsigned need, const uint8_t *d_actions = nullptr);
+
+// fjsp_arrivals.hip: after a step launch of a multi-order batch, solve the LP of every env it parked at an order arrival
+// and let arrival_kernel finish those steps (a failure marks the handle failed)
+int service_arrivals(fjsp_env *e, const double *d_mo, double *d_state, double *d_reward, uint8_t *d_done, int16_t *d_trace,
+                     hipStream_t st);
+bool async_idle(const fjsp_env *e);
+void arrivals_release(ArrivalService &a);   // joins the LP threads first; on the handle's device
+}  // namespace fjsp

@@ -39,6 +39,12 @@ struct Instance {
         for (int s = 0; s < S; ++s) n += jobs_of_order(s);
         return n;
     }
+    int ops_total() const {           // operations over all orders: sum of count[s][r] * J_r
+        int n = 0;
+        for (int s = 0; s < S; ++s)
+            for (int r = 0; r < R; ++r) n += count[(size_t)s * R + r] * Jr[r];
+        return n;
+    }
 };
 
 void set_error(const std::string &msg);

@@ -4,13 +4,11 @@
 # listed in .gpurunignore: remove its line there for the one gpurun call that needs the libraries.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-CSRC=$ROOT/deep_reinforcement_learning_for_fjsp_amd/csrc
 LEVELS=${LEVELS:-"1 2 3 4 7 8 9"}
 mkdir -p $ROOT/.diag
 for l in $LEVELS; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -DFJSP_ABLATE=$l -Wno-unused-function \
-    -I $ROOT/include -I $CSRC $CSRC/fjsp_kernels.hip $CSRC/fjsp_env.hip $CSRC/fjsp_rollout_buffer.hip $CSRC/fjsp_ppo.hip $CSRC/fjsp_mlp_train.hip $CSRC/fjsp_policy_mlp.hip $CSRC/fjsp_instance.cpp $CSRC/fjsp_lp.cpp \
-    -o $ROOT/.diag/libfjsp_ablate$l.so -lpthread &
+  (cd $ROOT && python3 -c "from deep_reinforcement_learning_for_fjsp_amd import _build
+_build.build_library(force=True, out='.diag/libfjsp_ablate$l.so', defines=['FJSP_ABLATE=$l'])") &
 done
 wait
 ls -la $ROOT/.diag/

@@ -1,7 +1,8 @@
 """Function-by-function comparison of two device builds of the kernel sources: instruction text (branch labels
 normalised) and the resource usage the compiler reports.  Used to check that a change leaves existing kernels' code alone.
 
-    for f in fjsp_kernels fjsp_group; do      # once in a checkout of the parent (-> DIR_A), once in this tree (-> DIR_B)
+    for f in fjsp_kernels fjsp_group fjsp_lp_device fjsp_snapshot fjsp_rollout_buffer fjsp_ppo fjsp_mlp_train fjsp_policy_mlp; do
+      # (every .hip with kernels) once in a checkout of the parent (-> DIR_A), once in this tree (-> DIR_B)
       hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -I include \\
             -I deep_reinforcement_learning_for_fjsp_amd/csrc --cuda-device-only -S \\
             deep_reinforcement_learning_for_fjsp_amd/csrc/$f.hip -o DIR/$f.s -Rpass-analysis=kernel-resource-usage 2> DIR/$f.rpass
@@ -11,6 +12,8 @@ normalised) and the resource usage the compiler reports.  Used to check that a c
 Prints one line per function of DIR_A (SAME / DIFF instruction text, res= / res! resource usage, instruction counts,
 VGPRs) and one per function only DIR_B has (NEW), then the count of identical functions.
 """
+import glob
+import os
 import re
 import sys
 
@@ -50,7 +53,7 @@ def parse_remarks(path):
 
 def main(a, b):
     same = total = 0
-    for f in ("fjsp_kernels", "fjsp_group"):
+    for f in sorted(os.path.basename(p)[:-2] for p in glob.glob(os.path.join(a, "*.s"))):
         fa, fb = parse_asm("%s/%s.s" % (a, f)), parse_asm("%s/%s.s" % (b, f))
         ra, rb = parse_remarks("%s/%s.rpass" % (a, f)), parse_remarks("%s/%s.rpass" % (b, f))
         for k in sorted(fa):

@@ -4,20 +4,15 @@ step kernel takes per wave (s_memtime deltas summed by lane 0 of every wave, wai
 claims: the stamps perturb the schedule; read the shares.  Usage: tools/stamp_group.py [--build-only|--no-build] [N]"""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 out = os.path.join(REPO, ".diag", "libfjsp_gstamps.so")
-csrc = os.path.join(REPO, "deep_reinforcement_learning_for_fjsp_amd", "csrc")
-srcs = [os.path.join(csrc, f) for f in ("fjsp_kernels.hip", "fjsp_group.hip", "fjsp_env.hip", "fjsp_rollout_buffer.hip", "fjsp_ppo.hip",
-                                         "fjsp_mlp_train.hip", "fjsp_instance.cpp", "fjsp_lp.cpp")]
 os.makedirs(os.path.dirname(out), exist_ok=True)
 if "--no-build" not in sys.argv:
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                    "-DFJSP_GSTAMPS", "-Wno-unused-function", "-I", os.path.join(REPO, "include"), "-I", csrc] + srcs +
-                   ["-o", out, "-lpthread"], check=True)
+    from deep_reinforcement_learning_for_fjsp_amd import _build
+    _build.build_library(force=True, out=out, defines=["FJSP_GSTAMPS"])
 if "--build-only" in sys.argv:
     sys.exit(0)
 os.environ["FJSP_AMD_LIB"] = out
