@@ -30,10 +30,13 @@ def _p(t):
 
 
 def supported(module_layers, device):
+    """Linear-ReLU-Linear-ReLU-Linear on the GPU of the shapes the kernels take: hidden width <= 256
+    (fjsp_relu_bwd_bias) and <= 32 outputs (fjsp_ppo_actor_loss)."""
     lin = [l for l in module_layers if isinstance(l, nn.Linear)]
     act = [l for l in module_layers if not isinstance(l, nn.Linear)]
     return (torch.device(device).type == "cuda" and len(lin) == 3 and len(act) == 2 and all(isinstance(a, nn.ReLU) for a in act)
-            and lin[0].out_features == lin[1].in_features == lin[1].out_features == lin[2].in_features and lin[0].out_features <= 1024)
+            and lin[0].out_features == lin[1].in_features == lin[1].out_features == lin[2].in_features and lin[0].out_features <= 256
+            and lin[2].out_features <= 32)
 
 
 class FusedMLP(object):
