@@ -93,6 +93,8 @@ SIGNATURES = {
     "fjsp_rollout_ptr": (_vp, [_vp, _i32]),
     "fjsp_actor_forward": (C.c_int, [C.POINTER(ActorParams), _vp, _i32, _vp, _vp]),
     "fjsp_env_rollout_policy": (C.c_int, [_vp, _vp, C.POINTER(ActorParams), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fjsp_env_play_policy": (C.c_int, [_vp, C.POINTER(ActorParams), _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
     "fjsp_ppo_partials": (C.c_int, [_i32]),
     "fjsp_ppo_actor_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_ppo_critic_loss": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -599,6 +599,37 @@ int fjsp_env_rollout_policy(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_par
     return FJSP_OK;
 }
 
+int fjsp_env_play_policy(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
+                         int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
+                         const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
+                         double *d_reward_last, uint8_t *d_done_last, void *stream) {
+    if (!e || T <= 0 || n_greedy < 0 || pair_div < 0 || !d_state_in || n_state_in <= 0 || !d_steps_out || !d_state_last ||
+        !d_reward_last || !d_done_last) {
+        set_error("fjsp_env_play_policy: bad arguments"); return FJSP_E_ARG;
+    }
+    if (const int rc = usable(e, "fjsp_env_play_policy", kIntact)) return rc;
+    if (!actor_ok(actor) || actor->state_size != e->b.state_size) {
+        set_error("fjsp_env_play_policy: the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32)"); return FJSP_E_UNSUPPORTED;
+    }
+    if (pair_div > 0 && actor->n_actions % pair_div != 0) {
+        set_error("fjsp_env_play_policy: pair_div does not divide n_actions"); return FJSP_E_ARG;
+    }
+    if (n_greedy < e->b.N && !d_seed) { set_error("fjsp_env_play_policy: sampling envs need d_seed"); return FJSP_E_ARG; }
+    if (!d_state_src && n_state_in < e->b.N) { set_error("fjsp_env_play_policy: d_state_in has fewer rows than the batch"); return FJSP_E_ARG; }
+    if (e->b.mord || e->b.KC != 1 || policy_rollout_lds_bytes(e->b, actor->state_size) > 160 * 1024) {
+        set_error("fjsp_env_play_policy: single-order batches of at most 64 operation types only"); return FJSP_E_UNSUPPORTED;
+    }
+    DeviceGuard guard(e->device);
+    PolicyPlayIO io;
+    io.state_in = d_state_in; io.state_src = d_state_src; io.n_state_in = n_state_in; io.seed = d_seed; io.first = d_first;
+    io.pair_div = pair_div; io.n_greedy = n_greedy; io.actions_out = d_actions_out; io.steps_out = d_steps_out;
+    io.state_last = d_state_last; io.reward_last = d_reward_last; io.done_last = d_done_last;
+    if (launch_play_policy(e->b, actor_of(actor), io, d_mo, T, (hipStream_t)stream, e->sched) != 0) {
+        set_error("play_policy_kernel launch failed"); return FJSP_E_HIP;
+    }
+    return FJSP_OK;
+}
+
 int fjsp_env_read(fjsp_env *e, int64_t *d_delay_time_sum, int32_t *d_makespan, int32_t *d_completion,
                   int32_t *d_step_time, int32_t *d_step_count, uint8_t *d_done, uint32_t *d_status, void *stream) {
     if (!e) { set_error("fjsp_env_read: null env"); return FJSP_E_ARG; }

@@ -1862,6 +1862,26 @@ int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const Policy
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int launch_play_policy(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, hipStream_t st,
+                       const SchedRec &rec) {
+    if (b.mord || b.KC != 1) return -1;                 // as launch_rollout_policy
+    const size_t lds = policy_rollout_lds_bytes(b, ap.S);
+    if (dispatch(b, [&](auto kc, auto v) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            if constexpr (!is_mord_v<V> && KC == 1) {
+                if (rec.rec) {
+                    allow_lds(&play_policy_rec_kernel<KC, V>, lds);
+                    hipLaunchKernelGGL((play_policy_rec_kernel<KC, V>), dim3((unsigned)((b.N + 15) / 16)), dim3(1024), lds, st, b, ap, io, mo, T,
+                                       rec);
+                    return;
+                }
+                allow_lds(&play_policy_kernel<KC, V>, lds);
+                hipLaunchKernelGGL((play_policy_kernel<KC, V>), dim3((unsigned)((b.N + 15) / 16)), dim3(1024), lds, st, b, ap, io, mo, T);
+            }
+        }) != 0) return -1;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_arrival(const DevBatch &b, const double *mo, int n_pending, const uint32_t *ids, const double *x_list, double *state,
                    double *reward, uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready, bool mark_resumed, const uint32_t *n_dev) {
     const size_t lds = step_lds_bytes(b);

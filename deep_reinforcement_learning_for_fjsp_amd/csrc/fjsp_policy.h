@@ -108,6 +108,23 @@ struct PolicyRolloutIO {
     double *state_last;          // [N][S] state after the last step of every env (the batch's state buffer)
 };
 
+// What the policy play (fjsp_env_play_policy) reads and writes: no buffer rows, only the decoded actions and where
+// every env ended.
+struct PolicyPlayIO {
+    const double *state_in;      // [n_state_in][S] start states; env i reads row state_src[i] (state_src == nullptr: row i)
+    const int32_t *state_src;    // [N] or nullptr
+    int n_state_in;
+    const uint64_t *seed;        // [1]   sampling stream (nullptr when every env is greedy)
+    const uint8_t *first;        // [N][2] action of step 0 in the env encoding, or nullptr: the actor decides
+    int pair_div;                // > 0: action -> (a / div, a % div); 0: flat action
+    int n_greedy;                // envs [0, n_greedy) take the argmax, the others sample
+    uint8_t *actions_out;        // [T][N][2] or nullptr: the action applied at each step
+    int32_t *steps_out;          // [N] steps taken in this call
+    double *state_last;          // [N][S] state, reward and done flag after every env's last step (the batch's rows)
+    double *reward_last;         // [N]
+    uint8_t *done_last;          // [N]
+};
+
 // LDS-only hand-off between the lanes of one wave (see wave_sync() in fjsp_kernels.hip)
 __device__ __forceinline__ void actor_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");

@@ -1,0 +1,285 @@
+"""Decoding a trained dispatching policy on the device: greedy play, best-of-K sampling, and a policy rollout lookahead.
+
+All three share one launch, fjsp_env_play_policy (play_policy_kernel, csrc/fjsp_kernels_dispatch.inc): every env plays to
+the end of its episode with the actor evaluated inside the environment kernel and no rollout-buffer traffic.  The actor is
+an agents.MPPPO ActorNet; the kernel takes those of the in-kernel shape (state_size <= 32 -> 128 -> 128 -> n_actions
+<= 32).  Other actors (MPPPO's 200 x 5 nets), order-arrival batches and batches of more than 64 operation types run the
+same decoding as a per-step loop (actor, argmax or fjsp_policy_sample, one env step), only more slowly.
+
+- play: every env to the end, greedy (argmax of the actor's probabilities) or sampled (epsilon 0).
+- best_of: k episodes per env in a k x N branch batch, block 0 greedy and the others sampled; each source env ends its
+  episode with the best one.
+- policy_lookahead: the rollout algorithm of lookahead.rollout_dispatch with the greedy actor as base policy: at every
+  decision branch block p applies candidate p and plays greedily to the end, all in one launch.
+
+Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
+must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _capi
+from .batch import EnvBatch, ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT
+from .lookahead import (ACTION_RANGES, OBJECTIVES, _Clock, _check_status, _objective_values, _ops_per_env, candidate_pairs,
+                        check_branch_shape, make_branch)
+
+_E_UNSUPPORTED = -5
+# the status bits at which an env stops playing (the kernel's and fjsp_env_rollout's `live` test)
+_STOP_BITS = ST_BAD_TASK_RULE | ST_BAD_MACHINE_RULE | ST_NO_EVENT
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _unwrap(batch, mo):
+    return getattr(batch, "batch", batch), (getattr(batch, "mo", None) if mo is None else mo)
+
+
+def action_encoding(actor, batch):
+    """(n_actions, pair_div) of the batch's variant for `actor`: pair_div = the machine-rule count of the pair variants,
+    0 for the flat ones (lookahead.ACTION_RANGES).  ValueError unless the actor maps state_size inputs to n_actions."""
+    if batch.variant not in ACTION_RANGES:
+        raise ValueError("unknown variant %r" % (batch.variant,))
+    rng = ACTION_RANGES[batch.variant]
+    n_actions, pair_div = int(np.prod(rng)), (rng[1] if len(rng) == 2 else 0)
+    lin = [m for m in actor.modules() if isinstance(m, torch.nn.Linear)]
+    if not lin:
+        raise ValueError("the actor has no nn.Linear layers")
+    if lin[0].in_features != batch.state_size or lin[-1].out_features != n_actions:
+        raise ValueError("the actor maps %d inputs to %d actions; this batch has states of %d and %d actions"
+                         % (lin[0].in_features, lin[-1].out_features, batch.state_size, n_actions))
+    return n_actions, pair_div
+
+
+def _check_objective(objective):
+    if not callable(objective) and objective not in OBJECTIVES:
+        raise ValueError("objective must be one of %s or a callable on read()" % (OBJECTIVES,))
+
+
+def _recording(b):
+    return b._lib.fjsp_env_schedule_capacity(b._h) > 0
+
+
+def _branch_for(batch, n_blocks, branch, who):
+    if branch is None:
+        return make_branch(batch, n_blocks)
+    if (not isinstance(branch, EnvBatch) or branch.N != n_blocks * batch.N or branch.n_inst != batch.n_inst
+            or branch.kernel_family != batch.kernel_family):
+        raise ValueError("%s: branch must be an EnvBatch of %d envs on the source's instances and kernel family"
+                         % (who, n_blocks * batch.N))
+    return branch
+
+
+def _seed_tensor(seed, dev):
+    return torch.tensor([int(np.array(int(seed) & (2 ** 64 - 1), dtype=np.uint64).view(np.int64))], dtype=torch.int64, device=dev)
+
+
+def play(batch, actor, greedy=True, seed=0, mo=None, max_steps=None, first=None, state_src=None, state_in=None,
+         record_actions=False, fused=True):
+    """Play every live env of `batch` from its current state to the end of its episode with `actor`.
+
+    greedy: True = the first index of the largest probability (torch.argmax), False = a draw from the stream of
+    fjsp_policy_sample with epsilon 0 and `seed` (counter = step index within this call, env = local index).
+    mo: f64[N, 4] step arguments of the MO variants (as EnvBatch.step takes them).  max_steps: upper bound on the steps
+    (default: the largest count of remaining operations).  first: u8[N, 2] actions in the env encoding that step 0
+    applies instead of the actor's.  state_in / state_src: env i starts from row state_src[i] of state_in (f64[M, S];
+    default: the batch's own state rows, row i).  record_actions: also return the applied actions.
+    fused=False, or an actor / batch the kernel refuses, runs the per-step loop instead; with an actor of the in-kernel
+    shape it takes the probabilities from the same device code (fjsp_actor_forward), so both give the same episode bit
+    for bit.
+
+    The batch's state / reward / done rows end as a step leaves them after each env's last step.  Returns
+    dict(actions=u8[T, N, 2] device tensor or None -- the action applied at each step, zero past an env's end --,
+    steps=i32[N] device tensor of the steps each env took)."""
+    batch, mo = _unwrap(batch, mo)
+    _, pair_div = action_encoding(actor, batch)
+    return _play(batch, actor, pair_div, batch.N if greedy else 0, seed, mo, max_steps, first, state_src, state_in,
+                 record_actions, fused)
+
+
+def _play(b, actor, pair_div, n_greedy, seed, mo, T, first, src, state_in, record_actions, fused):
+    from .agents.MPPPO.MPPPO import native_actor_params
+    N, dev = b.N, b.device
+    if mo is not None:
+        mo = torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).contiguous()
+    if first is not None:
+        first = torch.as_tensor(first, device=dev).to(torch.uint8).reshape(N, 2).contiguous()
+    state_in = b.state if state_in is None else state_in
+    if state_in.dim() != 2 or state_in.shape[1] != b.state_size:
+        raise ValueError("play: state_in must have shape (M, %d)" % b.state_size)
+    state_in = state_in.to(device=dev, dtype=torch.float64).contiguous()
+    if src is not None:
+        src = torch.as_tensor(src, device=dev).to(torch.int32).reshape(-1).contiguous()
+        if src.numel() != N or int(src.min()) < 0 or int(src.max()) >= state_in.shape[0]:
+            raise ValueError("play: state_src must hold %d rows of state_in (0..%d)" % (N, state_in.shape[0] - 1))
+        if state_in.data_ptr() == b.state.data_ptr():
+            state_in = state_in.clone()          # (the kernel writes the batch's rows while other waves read the map)
+    elif state_in.shape[0] != N:
+        raise ValueError("play: without state_src, state_in must have %d rows" % N)
+    if T is None:
+        r = b.read()
+        left = torch.where(r["done"] == 0, _ops_per_env(b) - r["step_count"].long(), torch.zeros(N, dtype=torch.int64, device=dev))
+        T = int(left.max().item())
+    T = max(int(T), 1)           # (one launch even when every env is done: it still hands back the start rows)
+    acts = torch.zeros(T, N, 2, dtype=torch.uint8, device=dev) if record_actions else None
+    steps = torch.zeros(N, dtype=torch.int32, device=dev)
+    seed_t = _seed_tensor(seed, dev)
+    ap = native_actor_params(actor) if fused else None
+    if ap is not None:
+        rc = b._lib.fjsp_env_play_policy(b._h, C.byref(ap), int(pair_div), int(n_greedy), _ptr(seed_t), T, _ptr(mo), _ptr(state_in),
+                                         int(state_in.shape[0]), _ptr(src), _ptr(first), _ptr(acts), _ptr(steps), b._p_state,
+                                         b._p_reward, b._p_done, b._stream())
+        if rc != _E_UNSUPPORTED:
+            _capi.check(rc)
+            return dict(actions=acts, steps=steps)
+    _play_loop(b, actor, pair_div, n_greedy, seed_t, T, mo, state_in, src, first, acts, steps)
+    return dict(actions=acts, steps=steps)
+
+
+def _play_loop(b, actor, pair_div, n_greedy, seed_t, T, mo, state_in, src, first, acts, steps):
+    """The per-step form of play_policy_kernel.  Each step goes through fjsp_env_rollout with T = 1, which steps only the
+    envs that are neither done nor stopped by an error bit (EnvBatch.step would flag a done env with STEP_AFTER_DONE)."""
+    from .agents.MPPPO.MPPPO import native_actor_forward, native_actor_params
+    N, dev = b.N, b.device
+    x = state_in[src.long()] if src is not None else state_in
+    if x.data_ptr() != b.state.data_ptr():
+        b.state.copy_(x)
+    native = native_actor_params(actor) is not None
+    A = [m for m in actor.modules() if isinstance(m, torch.nn.Linear)][-1].out_features
+    eps = torch.zeros((), dtype=torch.float32, device=dev)
+    pair = torch.zeros(N, 2, dtype=torch.uint8, device=dev)
+    flat = torch.zeros(N, dtype=torch.float32, device=dev)
+    logp = torch.zeros(N, dtype=torch.float32, device=dev)
+    r = b.read()
+    for t in range(T):
+        live = (r["done"] == 0) & ((r["status"].long() & _STOP_BITS) == 0)
+        if not bool(live.any()):
+            break
+        if t == 0 and first is not None:
+            a = first
+        else:
+            with torch.no_grad():
+                probs = native_actor_forward(actor, b.state) if native else actor(b.state.float())
+            probs = probs.float().contiguous()
+            if n_greedy < N:
+                _capi.check(b._lib.fjsp_policy_sample(_ptr(probs), N, A, int(pair_div), _ptr(eps), _ptr(seed_t), t, _ptr(pair),
+                                                      _ptr(flat), _ptr(logp), b._stream()))
+            if n_greedy > 0:
+                g = torch.argmax(probs[:n_greedy], dim=1)
+                pair[:n_greedy, 0] = (g // pair_div if pair_div else g).to(torch.uint8)
+                pair[:n_greedy, 1] = (g % pair_div if pair_div else torch.zeros_like(g)).to(torch.uint8)
+            a = pair
+        _, rw, _ = b.rollout(a[None], trace=False, rewards=True, mo=mo, state=True)
+        b.reward.copy_(torch.where(live, rw[0], b.reward))
+        if acts is not None:
+            acts[t] = torch.where(live[:, None], a, acts[t])
+        steps += live.to(torch.int32)
+        r = b.read()
+    b.done.copy_(r["done"])
+
+
+def best_of(batch, actor, k, objective, seed=0, mo=None, branch=None):
+    """Decode every env k times and keep the best episode.  A branch batch of k x N envs (recording iff the source
+    records) starts from the source's saved states; block 0 plays greedily in the source's own env slots, so it is
+    exactly the source's greedy episode, random rules included, and blocks 1..k-1 sample (seed as in play).  Each source
+    env then takes the first block with the lowest objective (its state, objective and, if recording, schedule).
+
+    objective: as lookahead.rollout_dispatch.  branch: an EnvBatch of k x N envs (lookahead.make_branch), reused across
+    calls, or None.  Returns dict(objective=tensor[N] of the source's finished episodes, best=i64[N] winning block,
+    branch=the branch batch)."""
+    batch, mo = _unwrap(batch, mo)
+    k = int(k)
+    if k < 1:
+        raise ValueError("best_of: k must be at least 1, got %d" % k)
+    _check_objective(objective)
+    _, pair_div = action_encoding(actor, batch)
+    N, dev = batch.N, batch.device
+    branch = _branch_for(batch, k, branch, "best_of")
+    if _recording(branch) != _recording(batch):
+        branch.record_schedule(_recording(batch))
+    src = np.tile(np.arange(N, dtype=np.int64), k)
+    branch.restore(batch.snapshot(), src, rows=False)
+    mo_b = None if mo is None else torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).repeat(k, 1)
+    _play(branch, actor, pair_div, N, seed, mo_b, None, None, torch.as_tensor(src, device=dev), batch.state, False, True)
+    rb = branch.read()
+    _check_status(rb, "best_of branch")
+    if not bool((rb["done"] != 0).all()):
+        raise RuntimeError("best_of: a branch env did not finish its episode")
+    best = torch.argmin(_objective_values(branch, objective, rb).reshape(k, N), dim=0)            # first minimum
+    win = branch.snapshot(best * N + torch.arange(N, device=dev))
+    batch.restore(win, rows=True)
+    return dict(objective=_objective_values(batch, objective), best=best, branch=branch)
+
+
+def policy_lookahead(batch, actor, objective, candidates=None, mo=None, branch=None, timings=None):
+    """lookahead.rollout_dispatch with the greedy actor as base policy: at every decision, branch block p applies
+    candidate p through play's `first` and plays greedily to the end, all in one launch; each source env takes the
+    candidate whose branch ended with the lowest objective (the first one on ties).
+
+    candidates: as rollout_dispatch; None = every action of the variant.  Arguments, error handling, `timings` parts and
+    the returned dict are those of rollout_dispatch.  When neither the candidates nor the actor's greedy choices use a
+    random.choice rule, the dynamics are deterministic and the greedy choice is always among the candidates, so by the
+    rollout algorithm's improvement property the objective reached is never above the greedy play's.  Random-rule
+    actions continue on their branch slot's random stream, and the bound does not hold for them."""
+    batch, mo = _unwrap(batch, mo)
+    _check_objective(objective)
+    _, pair_div = action_encoding(actor, batch)
+    if candidates is None:
+        rng = ACTION_RANGES[batch.variant]
+        candidates = [(a, m) for a in range(rng[0]) for m in range(rng[1])] if len(rng) == 2 else list(range(rng[0]))
+    pairs = candidate_pairs(candidates, batch.variant)
+    P, N = len(pairs), batch.N
+    check_branch_shape(N, batch.n_inst, P)
+    branch = _branch_for(batch, P, branch, "policy_lookahead")
+    dev = batch.device
+    if mo is not None:
+        mo = torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).contiguous()
+        mo_branch = mo.repeat(P, 1).contiguous()
+    else:
+        mo_branch = None
+    pairs_dev = torch.as_tensor(pairs, device=dev)                                       # [P, 2]
+    first = pairs_dev[:, None, :].expand(P, N, 2).reshape(P * N, 2).contiguous()        # candidate p in block p
+    src = np.tile(np.arange(N, dtype=np.int64), P)
+    src_dev = torch.as_tensor(src.astype(np.int32), device=dev)
+    ops = _ops_per_env(batch)
+    snap, restored = None, False
+    chosen_all, steps = [], torch.zeros(N, dtype=torch.int64, device=dev)
+    last = torch.zeros(N, 2, dtype=torch.uint8, device=dev)
+    clock = _Clock(timings, dev)
+    prev_live, prev_count = None, None
+    while True:
+        r = batch.read()
+        _check_status(r, "source")
+        live = r["done"] == 0
+        count = r["step_count"].long()
+        if prev_live is not None and bool((prev_live & live & (count <= prev_count)).any()):
+            raise RuntimeError("policy_lookahead: a source env did not advance in its step")
+        if not bool(live.any()):
+            break
+        prev_live, prev_count = live, count
+        T = int(torch.where(live, ops - count, torch.zeros_like(ops)).max().item())
+        clock.start()
+        snap = batch.snapshot(out=snap)
+        clock.lap("snapshot")
+        branch.restore(snap, src_dev if restored else src, rows=False)      # (the host map is validated once)
+        restored = True
+        clock.lap("restore")
+        _play(branch, actor, pair_div, P * N, 0, mo_branch, T, first, src_dev, batch.state, False, True)
+        clock.lap("rollout")
+        rb = branch.read()
+        _check_status(rb, "branch")
+        if not bool((rb["done"] != 0).all()):
+            raise RuntimeError("policy_lookahead: a branch env did not finish its episode")
+        best = torch.argmin(_objective_values(branch, objective, rb).reshape(P, N), dim=0)     # first minimum over candidates
+        clock.lap("read")
+        act = torch.where(live[:, None], pairs_dev[best], last)
+        batch.rollout(act[None].contiguous(), trace=False, rewards=False, mo=mo, state=True)    # (state: the next actor input)
+        clock.lap("step")
+        steps += live.long()
+        last = act
+        chosen_all.append(act)
+    actions = torch.stack(chosen_all).cpu().numpy() if chosen_all else np.zeros((0, N, 2), np.uint8)
+    return dict(actions=actions, steps=steps.cpu().numpy(), objective=_objective_values(batch, objective), branch=branch)

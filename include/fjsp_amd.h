@@ -398,6 +398,27 @@ int fjsp_env_rollout_policy(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_par
                             const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
                             float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream);
 
+/* Decoding a trained actor (MPPPO.py:245-252 without the buffer, the action of pick_action_and_log_prob :272-284):
+ * every env plays from its current state to the end of its episode in ONE launch, the actor inside the environment
+ * kernel.  Envs [0, n_greedy) take the first index of the largest probability (torch.argmax over the probabilities
+ * fjsp_actor_forward returns); the others draw from the stream of fjsp_policy_sample with epsilon 0 (same *d_seed,
+ * counter = step index within this call, env = local index).  An action a is applied as (a / pair_div, a % pair_div),
+ * or (a, 0) when pair_div == 0.  d_first u8[N][2] (nullable): the action step 0 applies instead, in the env encoding.
+ * Env i starts from row d_state_src[i] of d_state_in f64[n_state_in][S] (d_state_src i32[N] nullable: row i); the
+ * rows must be the envs' current states, and d_state_in may be d_state_last only without a map.  An env stops once it
+ * is done or carries FJSP_ST_BAD_TASK_RULE / BAD_MACHINE_RULE / NO_EVENT; T (steps, > 0) is an upper bound.
+ * Outputs: d_actions_out u8[T][N][2] (nullable) the action applied at each step, rows past an env's end untouched;
+ * d_steps_out i32[N] the steps each env took; d_state_last f64[N][S], d_reward_last f64[N], d_done_last u8[N] the
+ * state, reward and done flag after each env's last step (an env that took none: its start row, reward untouched).
+ * FJSP_E_ARG: null env or output, T <= 0, n_greedy < 0, null d_state_in, pair_div < 0 or not dividing n_actions,
+ * null d_seed while an env samples, fewer than N rows without a map.  FJSP_E_UNSUPPORTED where
+ * fjsp_env_rollout_policy refuses (actor not state_size <= 32 -> 128 -> 128 -> n_actions <= 32, order arrivals,
+ * more than 64 operation types, LDS): callers fall back to the per-step loop.  Recording batches record the schedule. */
+int fjsp_env_play_policy(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
+                         int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
+                         const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
+                         double *d_reward_last, uint8_t *d_done_last, void *stream);
+
 /* pick_action_and_log_prob (agents/MPPPO/MPPPO.py:272-284) for one vector step in ONE launch: samples
  * Categorical(d_probs[env]) (f32[n][n_actions], the actor's softmax output), applies the epsilon-random
  * override (*d_epsilon, device scalar so that captured graphs can change it), and writes the flat action

@@ -1,0 +1,329 @@
+"""GPU: decoding a trained actor on the device (fjsp_env_play_policy, policy_search.play / best_of / policy_lookahead)
+against the per-step loop that does the same with one launch per step."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import helpers as H
+
+pytestmark = pytest.mark.gpu
+
+DET_SO = [(a, b) for a in range(5) for b in range(4)]         # SO_FJSSP pairs without the random.choice rules (6th / 5th)
+
+
+@pytest.fixture(scope="module")
+def torch_gpu(built):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch
+
+
+@pytest.fixture
+def kernel_only(monkeypatch):
+    """The kernel path must run: the per-step loop raises if play falls back to it."""
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    loop = PS._play_loop
+
+    def boom(*a, **k):
+        raise AssertionError("play fell back to the per-step loop")
+
+    def on(flag):
+        monkeypatch.setattr(PS, "_play_loop", boom if flag else loop)
+    return on
+
+
+def _actor(torch, S, A, seed, hidden=128, layers=2):
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import ActorNet
+    torch.manual_seed(seed)
+    return ActorNet(S, hidden, layers, A).cuda()
+
+
+def _gen_10x5(n, seed):
+    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
+    return fi.InstanceSet(n).generate_range(seed, fi.bench_10x5_params()).solve_fluid()
+
+
+def _host(x):
+    return None if x is None else x.cpu().numpy().copy()
+
+
+def _read(b):
+    return {k: v.cpu().numpy() for k, v in b.read().items()}
+
+
+def _outcome(b, res):
+    out = dict(actions=_host(res["actions"]), steps=_host(res["steps"]), read=_read(b), state=H.bits(_host(b.state)),
+               done=_host(b.done), reward=H.bits(_host(b.reward)))
+    if b._lib.fjsp_env_schedule_capacity(b._h) > 0:
+        out["schedule"] = [_host(x) for x in b.schedule()]
+    return out
+
+
+def _same(a, b, what):
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            _same(a[k], b[k], "%s/%s" % (what, k))
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), what
+        for i, (x, y) in enumerate(zip(a, b)):
+            _same(x, y, "%s[%d]" % (what, i))
+    elif a is None:
+        assert b is None, what
+    else:
+        x, y = np.asarray(a), np.asarray(b)
+        assert x.dtype == y.dtype and x.shape == y.shape, what
+        assert np.array_equal(x, y), what
+
+
+def _kernel_vs_loop(torch, make, actor, kernel_only, mo=None, **kw):
+    """Two identical recording batches from reset: play through the kernel and through the per-step loop."""
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    outs = []
+    for fused in (True, False):
+        b = make()
+        b.record_schedule()
+        b.reset()
+        kernel_only(fused)
+        res = PS.play(b, actor, mo=mo, fused=fused, record_actions=True, **kw)
+        kernel_only(False)
+        outs.append(_outcome(b, res))
+    _same(outs[0], outs[1], "kernel vs loop")
+    got = outs[0]
+    assert np.all(got["read"]["done"] == 1) and np.all(got["read"]["status"] == 0)
+    assert np.array_equal(got["steps"], got["read"]["step_count"])
+    return got
+
+
+def _ops(s, n_inst, N):
+    ops = []
+    for i in range(n_inst):
+        a = s.arrays(i)
+        ops.append(int((np.asarray(a.count).reshape(a.S, a.R) * np.asarray(a.Jr)[None, :]).sum()))
+    return np.asarray(ops)[np.arange(N) % n_inst]
+
+
+@pytest.mark.parametrize("family", [0, 1])
+def test_greedy_kernel_equals_loop_so_fjssp(torch_gpu, kernel_only, family):
+    """4096 generated 10x5 envs in both kernel families: actions, steps, read(), final rows and schedule bit for bit."""
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    s, N = _gen_10x5(64, 300), 4096
+    make = lambda: EnvBatch(s, N, rng_seed=4, kernel_family=family)
+    assert make().kernel_family == family
+    actor = _actor(torch, 20, 30, 1)
+    got = _kernel_vs_loop(torch, make, actor, kernel_only)
+    assert np.array_equal(got["steps"], _ops(s, 64, N))
+
+
+@pytest.mark.parametrize("suite", ["so_sfjsp", "mo_discretes", "so_dfjsp"])
+def test_greedy_kernel_equals_loop_suites(torch_gpu, kernel_only, suite):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd.batch import (EnvBatch, VARIANT_MO_FJSSP_DISCRETES, VARIANT_SO_DFJSP,
+                                                                VARIANT_SO_SFJSP)
+    variant, S, A = {"so_sfjsp": (VARIANT_SO_SFJSP, 18, 20), "mo_discretes": (VARIANT_MO_FJSSP_DISCRETES, 25, 18),
+                     "so_dfjsp": (VARIANT_SO_DFJSP, 20, 30)}[suite]
+    insts, _, _ = H.load_suite(suite)
+    insts = [a for a in insts if a.S == 1 and a.K <= 64]        # what the kernel takes: single-order, <= 64 operation types
+    assert len(insts) >= 2
+    s = H.instance_set_from(insts)
+    N = 8 * len(insts)
+    mo = None
+    if variant == VARIANT_MO_FJSSP_DISCRETES:
+        mo = torch.tensor([[0.5, 0.5, 800.0, 300.0]], dtype=torch.float64, device="cuda").repeat(N, 1)
+    make = lambda: EnvBatch(s, N, variant=variant, rng_seed=6)
+    actor = _actor(torch, S, A, 2)
+    _kernel_vs_loop(torch, make, actor, kernel_only, mo=mo)
+    _kernel_vs_loop(torch, make, actor, kernel_only, mo=mo, greedy=False, seed=17)
+
+
+def test_sampled_kernel_equals_loop(torch_gpu, kernel_only):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    s, N = _gen_10x5(32, 310), 1024
+    make = lambda: EnvBatch(s, N, rng_seed=5)
+    actor = _actor(torch, 20, 30, 3)
+    a = _kernel_vs_loop(torch, make, actor, kernel_only, greedy=False, seed=11)
+    b = _kernel_vs_loop(torch, make, actor, kernel_only, greedy=False, seed=12)
+    assert not np.array_equal(a["actions"], b["actions"])
+    g = _kernel_vs_loop(torch, make, actor, kernel_only, greedy=True, seed=11)
+    assert not np.array_equal(a["actions"], g["actions"])
+
+
+def test_mid_episode_through_a_branch_map(torch_gpu, kernel_only):
+    """A source stepped by fixed actions, saved, loaded into a 3 x N branch without its rows: the kernel reads the
+    source's rows through the map and plays what the per-step loop plays on a branch restored with its rows; block 0
+    plays what the source itself plays."""
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    from deep_reinforcement_learning_for_fjsp_amd.lookahead import make_branch
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    NI, N = 32, 256
+    s = _gen_10x5(NI, 320)
+    src = EnvBatch(s, N, rng_seed=7)
+    src.record_schedule()
+    src.reset()
+    acts = torch.tensor(DET_SO, dtype=torch.uint8, device="cuda")[torch.arange(N, device="cuda") % 20]
+    for t in range(4):
+        src.step(acts)
+    snap = src.snapshot()
+    actor = _actor(torch, 20, 30, 4)
+    tile = np.tile(np.arange(N), 3)
+    outs = []
+    for fused in (True, False):
+        br = make_branch(src, 3)
+        br.record_schedule()
+        kernel_only(fused)
+        if fused:
+            br.restore(snap, tile, rows=False)
+            res = PS.play(br, actor, greedy=False, seed=21, state_in=src.state, state_src=torch.as_tensor(tile, device="cuda"),
+                          record_actions=True)
+        else:
+            br.restore(snap, tile, rows=True)
+            res = PS.play(br, actor, greedy=False, seed=21, fused=False, record_actions=True)
+        kernel_only(False)
+        outs.append(_outcome(br, res))
+    _same(outs[0], outs[1], "branch: kernel vs loop")
+    assert np.all(outs[0]["read"]["done"] == 1)
+    kernel_only(True)
+    res = PS.play(src, actor, greedy=False, seed=21, record_actions=True)
+    kernel_only(False)
+    own = _outcome(src, res)
+    br0 = outs[0]
+    assert np.array_equal(own["actions"], br0["actions"][:, :N]) and np.array_equal(own["steps"], br0["steps"][:N])
+    for k in own["read"]:
+        assert np.array_equal(own["read"][k], br0["read"][k][:N]), k
+    assert np.array_equal(own["state"], br0["state"][:N])
+    assert np.array_equal(own["schedule"][0], br0["schedule"][0][:N])
+
+
+def test_forced_first_action(torch_gpu, kernel_only):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    s, N = _gen_10x5(16, 330), 512
+    make = lambda: EnvBatch(s, N, rng_seed=8)
+    actor = _actor(torch, 20, 30, 5)
+    first = torch.tensor(DET_SO, dtype=torch.uint8, device="cuda")[torch.arange(N, device="cuda") % 20]
+    got = _kernel_vs_loop(torch, make, actor, kernel_only, first=first)
+    assert np.array_equal(got["actions"][0], _host(first))
+    free = _kernel_vs_loop(torch, make, actor, kernel_only)
+    assert not np.array_equal(got["actions"][0], free["actions"][0])
+
+
+def test_best_of_recording(torch_gpu):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    from deep_reinforcement_learning_for_fjsp_amd import schedule as sch
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    NI, N, k = 64, 512, 8
+    s = _gen_10x5(NI, 340)
+    actor = _actor(torch, 20, 30, 6)
+    twin = EnvBatch(s, N, rng_seed=9)
+    twin.reset()
+    PS.play(twin, actor)
+    greedy = twin.read()["makespan"].cpu().numpy().astype(np.float64)
+    b = EnvBatch(s, N, rng_seed=9)
+    b.record_schedule()
+    b.reset()
+    res = PS.best_of(b, actor, k, "makespan", seed=3)
+    obj, best = res["objective"].cpu().numpy(), res["best"].cpu().numpy()
+    assert res["branch"].N == k * N and res["branch"]._lib.fjsp_env_schedule_capacity(res["branch"]._h) > 0
+    assert np.all(obj <= greedy)
+    assert np.array_equal(obj[best == 0], greedy[best == 0])
+    assert np.any(obj < greedy) and np.any(best > 0)
+    rb, r = _read(res["branch"]), _read(b)
+    win = best * N + np.arange(N)
+    for key in r:
+        assert np.array_equal(r[key], rb[key][win]), key
+    assert np.array_equal(r["makespan"].astype(np.float64), obj)
+    table, length = [_host(x) for x in b.schedule()]
+    for e in range(0, N, 7):
+        a = s.arrays(e % NI)
+        rows = sch.rows(table, length, e)
+        assert sch.validate(a, rows, 0) == [], e
+        assert sch.objectives(a, rows, 0)["makespan"] == r["makespan"][e], e
+
+
+def test_policy_lookahead_never_loses_to_its_base_policy(torch_gpu):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    NI = N = 128
+    s = _gen_10x5(NI, 350)
+    actor = _actor(torch, 20, 30, 7)
+    with torch.no_grad():                    # no random.choice rule among the greedy choices: task rule 5, machine rule 4
+        rand = [a for a in range(30) if a // 5 == 5 or a % 5 == 4]
+        actor.layers[-1].bias[rand] = -1e4
+    twin = EnvBatch(s, N, rng_seed=10)
+    twin.reset()
+    g = PS.play(twin, actor, record_actions=True)
+    acts_g = _host(g["actions"]).astype(np.int64)
+    live = np.arange(acts_g.shape[0])[:, None] < _host(g["steps"])[None, :]
+    assert np.all((acts_g[..., 0] < 5) & (acts_g[..., 1] < 4) | ~live)
+    greedy = twin.read()["makespan"].cpu().numpy().astype(np.float64)
+    b = EnvBatch(s, N, rng_seed=10)
+    b.reset()
+    timings = {}
+    res = PS.policy_lookahead(b, actor, "makespan", candidates=DET_SO, timings=timings)
+    got = res["objective"].cpu().numpy()
+    assert np.all(got <= greedy)
+    assert set(timings) == {"snapshot", "restore", "rollout", "read", "step"}
+    assert np.array_equal(res["steps"], _ops(s, NI, N))
+    fresh = EnvBatch(s, N, rng_seed=10)
+    fresh.reset()
+    fresh.rollout(torch.from_numpy(res["actions"]).cuda(), trace=False, rewards=False)
+    assert np.array_equal(fresh.read()["makespan"].cpu().numpy().astype(np.float64), got)
+
+
+def test_fallback_decodes_what_the_kernel_refuses(torch_gpu):
+    """A 200 x 5 actor and a MO_DFJSP batch with order arrivals: the kernel answers FJSP_E_UNSUPPORTED, play decodes to the
+    end through the per-step loop, and the returned actions replay to the same objective."""
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import _capi
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    from deep_reinforcement_learning_for_fjsp_amd._capi import ActorParams
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import native_actor_params
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, VARIANT_MO_DFJSP
+    lib = _capi.lib()
+    s, N = _gen_10x5(16, 360), 64
+    wide = _actor(torch, 20, 30, 8, hidden=200, layers=5)
+    b = EnvBatch(s, N, rng_seed=11)
+    b.reset()
+    steps = torch.zeros(N, dtype=torch.int32, device="cuda")
+    p = lambda t: C.c_void_p(t.data_ptr())
+    lin = [m for m in wide.modules() if isinstance(m, torch.nn.Linear)]
+    ap = ActorParams(p(lin[0].weight), p(lin[0].bias), p(lin[1].weight), p(lin[1].bias), p(lin[-1].weight), p(lin[-1].bias), 20, 200, 30)
+    assert lib.fjsp_env_play_policy(b._h, C.byref(ap), 5, N, None, 10, None, b._p_state, N, None, None, None, p(steps),
+                                    b._p_state, b._p_reward, b._p_done, b._stream()) == -5
+    res = PS.play(b, wide, greedy=False, seed=4, record_actions=True)
+    r = _read(b)
+    assert np.all(r["done"] == 1) and np.array_equal(_host(res["steps"]), _ops(s, 16, N))
+    fresh = EnvBatch(s, N, rng_seed=11)
+    fresh.reset()
+    fresh.rollout(res["actions"], trace=False, rewards=False)
+    _same(_read(fresh), r, "replay 200 x 5")
+
+    insts, _, _ = H.load_suite("mo_dfjsp")
+    insts = [a for a in insts if a.name.startswith("gen")]         # small instances with arrivals and breakdowns
+    assert any(a.S > 1 for a in insts)
+    ds = H.instance_set_from(insts)
+    N = 2 * len(insts)
+    mo = torch.zeros(N, 4, dtype=torch.float64, device="cuda"); mo[:, 0] = 1.0
+    d = EnvBatch(ds, N, variant=VARIANT_MO_DFJSP, rng_seed=12)
+    d.reset()
+    narrow = _actor(torch, 30, 30, 9)                               # in-kernel shape, but the batch has order arrivals
+    assert native_actor_params(narrow) is not None
+    assert lib.fjsp_env_play_policy(d._h, C.byref(native_actor_params(narrow)), 10, N, None, 10, p(mo), d._p_state, N, None, None,
+                                    None, p(torch.zeros(N, dtype=torch.int32, device="cuda")), d._p_state, d._p_reward,
+                                    d._p_done, d._stream()) == -5
+    actor = _actor(torch, 30, 120, 10, hidden=200, layers=5)          # MPPPO's MO_DFJSP net: 12 x 10 actions
+    res = PS.play(d, actor, mo=mo, record_actions=True)
+    r = _read(d)
+    assert np.all(r["done"] == 1)
+    fresh = EnvBatch(ds, N, variant=VARIANT_MO_DFJSP, rng_seed=12)
+    fresh.reset()
+    fresh.rollout(res["actions"], trace=False, rewards=False, mo=mo)
+    got = _read(fresh)
+    for key in ("makespan", "delay_time_sum", "step_count", "done", "status"):
+        assert np.array_equal(got[key], r[key]), key
