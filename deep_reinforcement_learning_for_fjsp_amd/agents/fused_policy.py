@@ -6,10 +6,14 @@ actor, SAC_Discrete.py:85-103):  sample(state) -> (a_task, a_machine) int64 tens
 softmax(task(state.float())) and softmax(machine(cat(state.float(), a_task))) exactly as
 SAC_Discrete.py:277-284 does with two Categorical objects -- same distributions, but the random numbers come from a
 counter-based splitmix64 stream per row (seed, row, draws made so far) instead of torch's generator, like the
-environment kernels' own streams.  The kernel reads transposed copies of the weights, refreshed at every call unless the
-sampler was built with static_weights=True (frozen networks), so a call captured into a HIP graph follows later updates.
+environment kernels' own streams.  Each draw is the inverse CDF of u over the f32 probabilities: the first action whose
+running sum exceeds u, or, when rounding leaves the sum below 1 and u at or above it, the last action with a non-zero
+probability (like Categorical, it never draws a probability that is exactly 0).  The kernel reads transposed copies
+of the weights, refreshed at every call unless the sampler was built with static_weights=True (frozen networks), so a
+call captured into a HIP graph follows later updates.
 
-GPU only; `supported()` says whether a stack fits the kernel (<= 6 linear layers, widths <= 256, <= 64 outputs, f32).
+GPU only; `supported()` says whether a stack fits the kernel (<= 6 linear layers, widths <= 256, <= 64 outputs, f32);
+the sampler also needs a state of at most 255 features (the machine network's input is the state and one more).
 """
 import ctypes as C
 
@@ -84,6 +88,8 @@ class PolicyPairSampler:
         self.machine = _Net(machine_layers, static_weights) if machine_layers is not None else None
         self.device = self.task.lin[0].weight.device
         self.S = int(self.task.dims[0])
+        if self.S >= 256:
+            raise ValueError("PolicyPairSampler: the state has %d features; the kernel takes at most 255" % self.S)
         if self.machine is not None and int(self.machine.dims[0]) != self.S + 1:
             raise ValueError("PolicyPairSampler: the machine network takes the state and the task action")
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -131,7 +137,9 @@ class PolicyPairSampler:
 
 
 def expected_draw(probs, seed, row, draw):
-    """Host restatement of the kernel's inverse-CDF draw for one row (tests): probs f32[outputs] as the kernel returned them."""
+    """Host restatement of the kernel's inverse-CDF draw for one row (tests): probs f32[outputs] as the kernel returned them.
+    The first action whose f32 running sum of probabilities exceeds u; when the final sum lands below 1 and u at or above
+    it, the last action with a non-zero probability."""
     mask = (1 << 64) - 1
     z = (int(seed) + int(row) * 0x9E3779B97F4A7C15 + int(draw) * 1000003) & mask
     z = (z + 0x9E3779B97F4A7C15) & mask
@@ -140,8 +148,11 @@ def expected_draw(probs, seed, row, draw):
     z ^= z >> 31
     u = np.float32(z >> 40) * np.float32(1.0 / 16777216.0)
     c = np.float32(0.0)
+    last = len(probs) - 1
     for a, p in enumerate(np.asarray(probs, dtype=np.float32)):
         c = np.float32(c + p)
         if u < c:
             return a
-    return len(probs) - 1
+        if p > 0:
+            last = a
+    return last

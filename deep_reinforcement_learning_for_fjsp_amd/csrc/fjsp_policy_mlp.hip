@@ -10,7 +10,9 @@
 // consecutive words: with torch's [out][in] every lane streams its own row, a wave touches 64 cache lines per load and the
 // launch moves 8x the weights through L2 -- and four broadcast float4 reads of the inputs), then one lane per row does the
 // softmax (expf(x - max) / sum, f32 as torch) and draws the action by inverse CDF from a counter-based splitmix64 stream
-// (seed, row, per-row draw counter kept in device memory, so a launch replayed from a HIP graph keeps drawing fresh numbers).
+// (seed, row, per-row draw counter kept in device memory, so a launch replayed from a HIP graph keeps drawing fresh numbers):
+// the first action whose f32 running sum of probabilities exceeds u, or, when rounding leaves that sum below 1 and u at or
+// above it, the last action with a non-zero probability (Categorical never draws a probability of 0).
 //
 // Supported shapes: Linear-ReLU-...-Linear with 1..6 linear layers, every width <= 256, <= 64 outputs.  Not a training path:
 // forward + sample only (the networks' updates stay where they were).
@@ -110,6 +112,7 @@ __device__ int softmax_sample(float *logits, int no, unsigned long long seed, un
     // u in [0, 1): 24 random bits, the stream of this row (fjsp_common.h splitmix64)
     const unsigned long long h = fjsp::splitmix64(seed + (unsigned long long)row * 0x9E3779B97F4A7C15ull + (unsigned long long)draw * 1000003ull);
     const float u = (float)(h >> 40) * (1.0f / 16777216.0f);
+    // the first a with u < c (c: the f32 running sum of the probabilities)
     int pick = no - 1;
     float c = 0.0f;
     bool found = false;
@@ -119,6 +122,10 @@ __device__ int softmax_sample(float *logits, int no, unsigned long long seed, un
         c += p;
         if (!found && u < c) { pick = a; found = true; }
     }
+    // the final c can land below 1; a u at or above it takes the last action with p > 0, never one whose probability
+    // underflowed to 0 (rare: the walk back stays out of the loop above)
+    if (!found)
+        while (pick > 0 && !(logits[pick * kRows] * inv > 0.0f)) --pick;
     return pick;
 }
 

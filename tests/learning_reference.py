@@ -74,7 +74,40 @@ def forward(params, x):
     with np.errstate(invalid="ignore", divide="ignore"):
         rel1 = np.where(m1 > 0, np.abs(z1) / m1, np.inf)
         rel2 = np.where(m2 > 0, np.abs(z2) / m2, np.inf)
-    return dict(x=x, z1=z1, m1=m1, k1=k1, h1=h1, z2=z2, m2=m2, k2=k2, h2=h2, out=out, m_out=m_out, rel1=rel1, rel2=rel2)
+    return dict(x=x, z1=z1, m1=m1, k1=k1, h1=h1, z2=z2, m2=m2, k2=k2, h2=h2, out=out, m_out=m_out, rel1=rel1, rel2=rel2,
+                ms=[m1, m2], rels=[rel1, rel2])
+
+
+def forward_layers_k(dims):
+    """forward_k for any depth: dims = [inputs, widths..., outputs] -> K of every layer's pre-activations,
+    K_1 = dims[0] + 2, K_l = K_(l-1) + dims[l-1] + 2."""
+    ks = [dims[0] + 2]
+    for l in range(2, len(dims)):
+        ks.append(ks[-1] + dims[l - 1] + 2)
+    return ks
+
+
+def forward_layers(params, x):
+    """Linear-ReLU-...-Linear with 1..6 linear layers, params = [W1, b1, ..., WL, bL] (f64, torch layout [out][in]).
+    x: f32[n, inputs] -> dict of the f64 logits `out`, their abs-magnitudes `m_out`, and per hidden layer its
+    pre-activations `zs`, magnitudes `ms`, ReLU masks `masks` and distances from 0 relative to the magnitude `rels`."""
+    assert len(params) % 2 == 0 and 1 <= len(params) // 2 <= 6
+    h = as64(x)
+    mh = np.abs(h)
+    zs, ms, masks, rels = [], [], [], []
+    n_layers = len(params) // 2
+    for l in range(n_layers):
+        W, b = params[2 * l], params[2 * l + 1]
+        z = h @ W.T + b
+        m = mh @ np.abs(W).T + np.abs(b)
+        if l + 1 == n_layers:
+            return dict(x=as64(x), out=z, m_out=m, zs=zs, ms=ms, masks=masks, rels=rels)
+        k = z > 0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rels.append(np.where(m > 0, np.abs(z) / m, np.inf))
+        zs.append(z); ms.append(m); masks.append(k)
+        h = np.where(k, z, 0.0)
+        mh = np.where(k, m, 0.0)
 
 
 def softmax(out):
@@ -178,13 +211,17 @@ def backward(params, fw, dout, dout_mag, k_dout, depth_w, depth_b):
 
 
 # ---------------------------------------------------------------------------------------------------------- sample filter
-def keep_samples(fw, k1, k2, k_out=None, act=None, s_tol=64.0):
+def keep_samples(fw, k1, k2=None, k_out=None, act=None, s_tol=64.0):
     """Boolean mask of the samples whose branches f32 rounding cannot flip, and the number dropped.
     Drops a sample when a hidden pre-activation lies within K u mag of 0 (mag > 0: exact structural zeros stay), or,
     with `act` (an actor_loss result), its ratio lies within its error of 1 - eps or 1 + eps, or s1 and s2 differ by
-    less than their error without being equal."""
-    keep = ~((fw["rel1"] <= k1 * U) & (fw["m1"] > 0)).any(1)
-    keep &= ~((fw["rel2"] <= k2 * U) & (fw["m2"] > 0)).any(1)
+    less than their error without being equal.  fw: a forward() result with the K of its two hidden layers (k1, k2), or
+    a forward_layers() result with k1 the list of K of its hidden layers (forward_layers_k(dims)[:-1])."""
+    ks = list(k1) if k2 is None else [k1, k2]
+    assert len(ks) == len(fw["rels"])
+    keep = np.ones(fw["x"].shape[0], dtype=bool)
+    for rel, m, k in zip(fw["rels"], fw["ms"], ks):
+        keep &= ~((rel <= k * U) & (m > 0)).any(1)
     if act is not None:
         r, band = act["ratio"], (k_out + s_tol) * U * act["ratio_L"] * act["ratio"]
         keep &= np.abs(r - act["lo"]) > band
