@@ -214,6 +214,14 @@ class EnvBatch(object):
         # capture graphs; torch.cuda.current_stream() builds a Stream object first, five times the cost)
         return C.c_void_p(torch._C._cuda_getCurrentRawStream(self.device_index))
 
+    def row_build(self, fused=False):
+        """The row-kernel build (kernel_family 1) that a step (fused=False) or a rollout (fused=True) of this batch runs,
+        as the launcher decides it (fjsp_env_row_build): dict(early=0/1, mpc=5/8, resident=0/1).  FjspError for a batch
+        of the one-wave-per-environment family."""
+        out = (C.c_int32 * 3)()
+        check(self._lib.fjsp_env_row_build(self._h, 1 if fused else 0, out))
+        return dict(early=int(out[0]), mpc=int(out[1]), resident=int(out[2]))
+
     def env_seed(self, e):
         """random.choice stream seed of (local) env e (matches open_env() in fjsp_kernels.hip)."""
         return (self.rng_seed + (self.first_env + e) * ENV_SEED_STRIDE) & (2 ** 64 - 1)

@@ -201,6 +201,9 @@ int launch_step_group(const DevBatch &b, const uint8_t *actions, const double *m
                       uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec = SchedRec{});
 int launch_rollout_group(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
                          double *state_last, hipStream_t st, const SchedRec &rec = SchedRec{});
+// the build those two launch (fused: launch_rollout_group), decided in one place (fjsp_env_row_build reports it)
+struct GroupBuild { int early, mpc, resident; };
+GroupBuild group_build(const DevBatch &b, bool fused);
 size_t rollout_lds_bytes(const DevBatch &b);
 size_t step_lds_bytes(const DevBatch &b);     // dynamic LDS of one reset / step / arrival workgroup
 int launch_rollout(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,

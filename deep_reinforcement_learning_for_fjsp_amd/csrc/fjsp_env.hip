@@ -496,6 +496,13 @@ int fjsp_env_state_size(const fjsp_env *e) { return e ? e->b.state_size : 0; }
 int fjsp_env_device(const fjsp_env *e) { return e ? e->device : -1; }
 int64_t fjsp_env_step_bytes(const fjsp_env *e) { return e ? e->step_bytes : 0; }
 int fjsp_env_kernel_family(const fjsp_env *e) { return e ? e->b.grp : 0; }
+int fjsp_env_row_build(const fjsp_env *e, int32_t fused, int32_t *out3) {
+    if (!e || !out3) { set_error("fjsp_env_row_build: null argument"); return FJSP_E_ARG; }
+    if (!e->b.grp) { set_error("fjsp_env_row_build: the batch is stepped by the one-wave-per-environment kernels"); return FJSP_E_UNSUPPORTED; }
+    const GroupBuild g = group_build(e->b, fused != 0);
+    out3[0] = g.early; out3[1] = g.mpc; out3[2] = g.resident;
+    return FJSP_OK;
+}
 int fjsp_env_lp_on_device(const fjsp_env *e) { return (e && e->arr.lp_device) ? 1 : 0; }
 
 int fjsp_env_reset(fjsp_env *e, const uint8_t *d_mask, double *d_state, void *stream) {

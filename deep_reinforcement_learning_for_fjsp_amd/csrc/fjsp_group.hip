@@ -992,18 +992,36 @@ static unsigned group_waves_per_block() {
     static const unsigned w = [] { const char *v = getenv("FJSP_GROUP_WPB"); const int x = v ? atoi(v) : 4; return (unsigned)(x == 1 || x == 2 ? x : 4); }();
     return w;
 }
+// The build a launch runs: early or lean (above), the machine capacity MPC of the batch's largest machine count, and for the
+// fused kernel whether the static tables are resident in LDS -- when the waves a CU gets (256 CUs, one wave per workgroup in the
+// lean build) fit its LDS with them.  The launchers below and fjsp_env_row_build take it from here.
+GroupBuild group_build(const DevBatch &b, bool fused) {
+    GroupBuild g;
+    g.early = (fused ? group_early_rollout(b) : group_early(b)) ? 1 : 0;
+    g.mpc = b.MP <= 5 ? 5 : 8;
+    g.resident = 0;
+    if (fused && !g.early) {
+        const unsigned waves = (unsigned)((b.N + 3) / 4), waves_per_cu = (waves + 255u) / 256u;
+        const size_t res_lds = 4 * (size_t)(g.mpc == 5 ? grp::res_bytes<5>() : grp::res_bytes<8>());
+        const size_t lean_lds = g.mpc == 5 ? grp::group_lds_bytes<5, false>() : grp::group_lds_bytes<8, false>();
+        static const int res_forced = [] { const char *v = getenv("FJSP_GROUP_RESIDENT"); return v ? atoi(v) : -1; }();
+        g.resident = (res_forced >= 0 ? res_forced != 0 : waves_per_cu * (lean_lds + res_lds) <= (size_t)152 * 1024) ? 1 : 0;
+    }
+    return g;
+}
 template <int V>
 static int launch_step_group_v(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
                                uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec) {
-    const bool early = group_early(b);
+    const GroupBuild gb = group_build(b, false);
+    const bool early = gb.early != 0;
     const unsigned wpb = early ? group_waves_per_block() : 1u, waves = (unsigned)((b.N + 3) / 4);
     const dim3 grid((waves + wpb - 1) / wpb);
 #define FJSP_GSTEP(MPC, E) group_allow_lds(&grp::gstep_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()); hipLaunchKernelGGL((grp::gstep_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()), st, b, actions, mo, autoreset, state, reward, done, trace_km)
 #define FJSP_GSTEP_REC(MPC, E) group_allow_lds(&grp::gstep_rec_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()); hipLaunchKernelGGL((grp::gstep_rec_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()), st, b, actions, mo, autoreset, state, reward, done, trace_km, rec)
     if (rec.rec) {          // recording (fjsp_env_record_schedule): the same step, plus the dispatch records
-        if (b.MP <= 5) { if (early) { FJSP_GSTEP_REC(5, true); } else { FJSP_GSTEP_REC(5, false); } }
+        if (gb.mpc == 5) { if (early) { FJSP_GSTEP_REC(5, true); } else { FJSP_GSTEP_REC(5, false); } }
         else { if (early) { FJSP_GSTEP_REC(8, true); } else { FJSP_GSTEP_REC(8, false); } }
-    } else if (b.MP <= 5) { if (early) { FJSP_GSTEP(5, true); } else { FJSP_GSTEP(5, false); } }
+    } else if (gb.mpc == 5) { if (early) { FJSP_GSTEP(5, true); } else { FJSP_GSTEP(5, false); } }
     else { if (early) { FJSP_GSTEP(8, true); } else { FJSP_GSTEP(8, false); } }
 #undef FJSP_GSTEP
 #undef FJSP_GSTEP_REC
@@ -1021,22 +1039,18 @@ int launch_step_group(const DevBatch &b, const uint8_t *actions, const double *m
 template <int V>
 static int launch_rollout_group_v(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
                                   double *state_last, hipStream_t st, const SchedRec &rec) {
-    const bool early = group_early_rollout(b);
+    const GroupBuild gb = group_build(b, true);
+    const bool early = gb.early != 0;
     const unsigned wpb = early ? group_waves_per_block() : 1u, waves = (unsigned)((b.N + 3) / 4);
     const dim3 grid((waves + wpb - 1) / wpb);
-    // resident static tables (lean build): when the waves a CU gets -- 256 CUs, one wave per workgroup -- fit its LDS with them
-    const unsigned waves_per_cu = (waves + 255u) / 256u;
-    const size_t res_lds = 4 * (size_t)(b.MP <= 5 ? grp::res_bytes<5>() : grp::res_bytes<8>());
-    const size_t lean_lds = b.MP <= 5 ? grp::group_lds_bytes<5, false>() : grp::group_lds_bytes<8, false>();
-    static const int res_forced = [] { const char *v = getenv("FJSP_GROUP_RESIDENT"); return v ? atoi(v) : -1; }();
-    const int resident = (!early && (res_forced >= 0 ? res_forced != 0 : waves_per_cu * (lean_lds + res_lds) <= (size_t)152 * 1024)) ? 1 : 0;
-    const size_t extra = resident ? res_lds : 0;
+    const int resident = gb.resident;
+    const size_t extra = resident ? 4 * (size_t)(gb.mpc == 5 ? grp::res_bytes<5>() : grp::res_bytes<8>()) : 0;
 #define FJSP_GROLL(MPC, E) group_allow_lds(&grp::grollout_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + extra); hipLaunchKernelGGL((grp::grollout_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + extra), st, b, actions, mo, T, trace_km, reward, state_last, resident)
 #define FJSP_GROLL_REC(MPC, E) group_allow_lds(&grp::grollout_rec_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + extra); hipLaunchKernelGGL((grp::grollout_rec_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + extra), st, b, actions, mo, T, trace_km, reward, state_last, resident, rec)
     if (rec.rec) {
-        if (b.MP <= 5) { if (early) { FJSP_GROLL_REC(5, true); } else { FJSP_GROLL_REC(5, false); } }
+        if (gb.mpc == 5) { if (early) { FJSP_GROLL_REC(5, true); } else { FJSP_GROLL_REC(5, false); } }
         else { if (early) { FJSP_GROLL_REC(8, true); } else { FJSP_GROLL_REC(8, false); } }
-    } else if (b.MP <= 5) { if (early) { FJSP_GROLL(5, true); } else { FJSP_GROLL(5, false); } }
+    } else if (gb.mpc == 5) { if (early) { FJSP_GROLL(5, true); } else { FJSP_GROLL(5, false); } }
     else { if (early) { FJSP_GROLL(8, true); } else { FJSP_GROLL(8, false); } }
 #undef FJSP_GROLL
 #undef FJSP_GROLL_REC
