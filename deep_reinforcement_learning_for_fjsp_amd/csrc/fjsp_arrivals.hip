@@ -402,7 +402,7 @@ int async_launch(fjsp_env *e, AsyncBatch *slot, const uint8_t *d_actions, const 
     b2.pending_count = slot->d_count;
     b2.lp_in = slot->d_lp_in;
     // (a step that parks has dispatched already: its record is written in this launch, arrival_kernel adds none)
-    if (launch_step(b2, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, nullptr, st, d_ready, e->sched) != 0) {
+    if (launch_step(b2, e->plan, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, nullptr, st, d_ready, e->sched) != 0) {
         set_error("step_kernel launch failed"); return FJSP_E_HIP;
     }
     const size_t KP = (size_t)e->b.KP;
@@ -458,7 +458,7 @@ int fjsp_env_step_async(fjsp_env *e, const uint8_t *d_actions, const double *d_m
     DeviceGuard guard(e->device);
     hipStream_t st = (hipStream_t)stream;
     if (!e->b.mord) {                               // nothing ever parks: the plain step, every env ready
-        if (launch_step(e->b, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, nullptr, st, nullptr, e->sched) != 0) { set_error("step_kernel launch failed"); return FJSP_E_HIP; }
+        if (launch_step(e->b, e->plan, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, nullptr, st, nullptr, e->sched) != 0) { set_error("step_kernel launch failed"); return FJSP_E_HIP; }
         HIP_TRY(hipMemsetAsync(d_ready, 1, (size_t)e->b.N, st));
         return FJSP_OK;
     }

@@ -190,23 +190,37 @@ struct SchedRec {
     int32_t cap = 0;         // slots per env: operations of the largest instance of the batch
 };
 
+// The build of the row kernels (fjsp_group.hip) a launch runs: the early or the lean variant, the machine capacity MPC, for
+// the fused kernel whether the static tables are resident in LDS, and the waves per workgroup.
+struct GroupBuild { int early, mpc, resident; unsigned wpb; };
+// What a handle's launchers need beyond DevBatch (which is a kernel argument: a field more there changes the device code).
+// Filled once, at create (plan_launch in fjsp_env.hip, the library's only reader of the FJSP_* environment variables),
+// and kept in the handle: fjsp_env_row_build reports what is stored here, the launchers launch it.
+struct LaunchPlan {
+    GroupBuild step{}, fused{};   // row-kernel batches (DevBatch::grp): per-step launches, the fused rollout
+    size_t lds_pad = 0;           // diagnostic: extra dynamic LDS of a per-step launch (FJSP_GROUP_LDS_PAD)
+    // values the diagnostic variables force, -1 = not set: FJSP_GROUP_EARLY, FJSP_GROUP_RESIDENT, FJSP_GROUP_WPB (1, 2 or 4),
+    // FJSP_LP_IMPL (0 host, 1 device)
+    int early_forced = -1, resident_forced = -1, wpb_forced = -1, lp_device_forced = -1;
+};
+// the rules of GroupBuild, in one place (fjsp_group.hip); reads the forced values of `p`
+GroupBuild group_build(const DevBatch &b, bool fused, const LaunchPlan &p);
+
 // kernel launchers (fjsp_kernels.hip); all asynchronous on `st`, 0 = launched
 int launch_fluid_tables(const DevBatch &b, hipStream_t st);
 int launch_reset(const DevBatch &b, const uint8_t *mask, double *state, hipStream_t st);
+// row-kernel batches go to launch_step_group unless `ready` is given
 // ready (nullable, multi-order batches): asynchronous arrival service, see fjsp_env_step_async
-int launch_step(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
+int launch_step(const DevBatch &b, const LaunchPlan &p, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
                 uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready = nullptr, const SchedRec &rec = SchedRec{});
-// the same step by the group kernels (fjsp_group.hip; DevBatch::grp batches only)
-int launch_step_group(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
-                      uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec = SchedRec{});
-int launch_rollout_group(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
-                         double *state_last, hipStream_t st, const SchedRec &rec = SchedRec{});
-// the build those two launch (fused: launch_rollout_group), decided in one place (fjsp_env_row_build reports it)
-struct GroupBuild { int early, mpc, resident; };
-GroupBuild group_build(const DevBatch &b, bool fused);
+// the same step by the group kernels (fjsp_group.hip; DevBatch::grp batches only): the builds p.step and p.fused
+int launch_step_group(const DevBatch &b, const LaunchPlan &p, const uint8_t *actions, const double *mo, int autoreset, double *state,
+                      double *reward, uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec = SchedRec{});
+int launch_rollout_group(const DevBatch &b, const LaunchPlan &p, const uint8_t *actions, const double *mo, int T, int16_t *trace_km,
+                         double *reward, double *state_last, hipStream_t st, const SchedRec &rec = SchedRec{});
 size_t rollout_lds_bytes(const DevBatch &b);
 size_t step_lds_bytes(const DevBatch &b);     // dynamic LDS of one reset / step / arrival workgroup
-int launch_rollout(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
+int launch_rollout(const DevBatch &b, const LaunchPlan &p, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
                    double *state_last, hipStream_t st, const SchedRec &rec = SchedRec{});
 // multi-order: resume the envs whose pending LP has been solved (x in e_xin)
 // ids u32[n_pending] / x_list f64[n_pending][KP][MP]: the parked envs and their LP solutions (device)

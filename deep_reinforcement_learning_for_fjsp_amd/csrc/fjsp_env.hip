@@ -113,11 +113,13 @@ int check_instance(const Instance &in, int variant, bool class_fjsp, Shape &sh) 
     return FJSP_OK;
 }
 
-// Stage 2: the kernel family.  One 16-lane row per environment (fjsp_group.hip): FJSP_STEP_IMPL=wave (family -1) or family 0
-// keeps such batches on the one-wave-per-environment kernels; family 1 asks for the row kernels, FJSP_E_UNSUPPORTED if the
-// batch does not fit them.
-int choose_family(DevBatch &b, const Shape &sh, int family) {
-    const char *impl = getenv("FJSP_STEP_IMPL");
+// Stage 2: the kernel family and the build of it the handle launches, kept in its LaunchPlan.  The one place where the
+// library reads its environment variables: at every create.  One 16-lane row per environment (fjsp_group.hip):
+// FJSP_STEP_IMPL=wave (family -1) or family 0 keeps such batches on the one-wave-per-environment kernels; family 1 asks for
+// the row kernels, FJSP_E_UNSUPPORTED if the batch does not fit them.  The row kernels' builds: group_build (fjsp_group.hip).
+int plan_launch(DevBatch &b, LaunchPlan &p, const Shape &sh, int family) {
+    auto knob = [](const char *name) { const char *v = getenv(name); return v ? atoi(v) : -1; };
+    const char *impl = getenv("FJSP_STEP_IMPL"), *lp = getenv("FJSP_LP_IMPL"), *pad = getenv("FJSP_GROUP_LDS_PAD");
     const bool fits = b.single_job && sh.K <= 64 && sh.M <= 8 && sh.J <= 15 &&
                       (b.variant == FJSP_VARIANT_SO_FJSSP || b.variant == FJSP_VARIANT_MO_FJSSP_DISCRETES);
     if (family == 1 && !fits) {
@@ -126,8 +128,13 @@ int choose_family(DevBatch &b, const Shape &sh, int family) {
         return FJSP_E_UNSUPPORTED;
     }
     b.grp = (fits && (family == 1 || (family == -1 && !(impl && strcmp(impl, "wave") == 0)))) ? 1 : 0;
-    const char *kv = getenv("FJSP_GROUP_KENV");
-    b.kenv_first = (kv && atoi(kv) == 0) ? 0 : 1;
+    b.kenv_first = knob("FJSP_GROUP_KENV") == 0 ? 0 : 1;
+    p.early_forced = knob("FJSP_GROUP_EARLY");
+    p.resident_forced = knob("FJSP_GROUP_RESIDENT");
+    p.wpb_forced = knob("FJSP_GROUP_WPB");
+    p.lds_pad = pad ? (size_t)atol(pad) : 0;
+    p.lp_device_forced = lp ? (strcmp(lp, "device") == 0 ? 1 : 0) : -1;
+    if (b.grp) { p.step = group_build(b, false, p); p.fused = group_build(b, true, p); }
     return FJSP_OK;
 }
 
@@ -339,8 +346,7 @@ void choose_lp_service(fjsp_env *e) {
         lds_max = std::max(lds_max, lp_device_lds_bytes(in.K, in.M, nx, in.R, b.MP));
         if (nx + 1 + (in.K + in.M + in.K - in.R) + 1 > lp_device_max_columns()) lds_max = (size_t)1 << 30;
     }
-    const char *impl = getenv("FJSP_LP_IMPL");
-    const bool want_device = impl ? strcmp(impl, "device") == 0 : b.N >= 16384;
+    const bool want_device = e->plan.lp_device_forced >= 0 ? e->plan.lp_device_forced != 0 : b.N >= 16384;
     e->arr.lp_device = lds_max <= 156 * 1024 && want_device;
     e->arr.lp_lds = e->arr.lp_device ? lds_max : 0;
 }
@@ -455,7 +461,7 @@ int fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_ins
     b.mord = (sh.S > 1 || dyn) ? 1 : 0; b.SP = sh.S; b.RP = sh.R;     // MO_DFJSP always runs on the per-env fluid tables
     b.single_job = (sh.single_job && !b.mord) ? 1 : 0;
     b.kmax = sh.K;
-    int rc = choose_family(b, sh, family);
+    int rc = plan_launch(b, e->plan, sh, family);
     if (rc == FJSP_OK) rc = plan_layout(b, sh);
     if (rc != FJSP_OK) return rc;
 
@@ -499,7 +505,7 @@ int fjsp_env_kernel_family(const fjsp_env *e) { return e ? e->b.grp : 0; }
 int fjsp_env_row_build(const fjsp_env *e, int32_t fused, int32_t *out3) {
     if (!e || !out3) { set_error("fjsp_env_row_build: null argument"); return FJSP_E_ARG; }
     if (!e->b.grp) { set_error("fjsp_env_row_build: the batch is stepped by the one-wave-per-environment kernels"); return FJSP_E_UNSUPPORTED; }
-    const GroupBuild g = group_build(e->b, fused != 0);
+    const GroupBuild &g = fused ? e->plan.fused : e->plan.step;
     out3[0] = g.early; out3[1] = g.mpc; out3[2] = g.resident;
     return FJSP_OK;
 }
@@ -518,7 +524,7 @@ int fjsp_env_step_traced(fjsp_env *e, const uint8_t *d_actions, const double *d_
     if (!e || !d_actions) { set_error("fjsp_env_step: null argument"); return FJSP_E_ARG; }
     if (const int rc = usable(e, "fjsp_env_step", kIntact | kIdle, d_actions)) return rc;
     DeviceGuard guard(e->device);
-    if (launch_step(e->b, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, d_trace_km, (hipStream_t)stream, nullptr, e->sched) != 0) {
+    if (launch_step(e->b, e->plan, d_actions, d_mo, autoreset ? 1 : 0, d_state, d_reward, d_done, d_trace_km, (hipStream_t)stream, nullptr, e->sched) != 0) {
         set_error("step_kernel launch failed"); return FJSP_E_HIP;
     }
     if (e->b.mord) return service_arrivals(e, d_mo, d_state, d_reward, d_done, d_trace_km, (hipStream_t)stream);
@@ -537,7 +543,7 @@ int fjsp_env_rollout(fjsp_env *e, const uint8_t *d_actions, const double *d_mo, 
     DeviceGuard guard(e->device);
     hipStream_t st = (hipStream_t)stream;
     if (!e->b.mord && rollout_lds_bytes(e->b) <= 64 * 1024) {
-        if (launch_rollout(e->b, d_actions, d_mo, T, d_trace_km, d_reward, d_state_last, st, e->sched) != 0) {
+        if (launch_rollout(e->b, e->plan, d_actions, d_mo, T, d_trace_km, d_reward, d_state_last, st, e->sched) != 0) {
             set_error("rollout_kernel launch failed"); return FJSP_E_HIP;
         }
         return FJSP_OK;
@@ -545,7 +551,7 @@ int fjsp_env_rollout(fjsp_env *e, const uint8_t *d_actions, const double *d_mo, 
     // instance too large for the LDS-resident fused kernel: T step launches on the same stream
     const size_t N = (size_t)e->b.N;
     for (int s2 = 0; s2 < T; ++s2) {
-        if (launch_step(e->b, d_actions + (size_t)s2 * N * 2, d_mo, 2, d_state_last, d_reward ? d_reward + (size_t)s2 * N : nullptr,
+        if (launch_step(e->b, e->plan, d_actions + (size_t)s2 * N * 2, d_mo, 2, d_state_last, d_reward ? d_reward + (size_t)s2 * N : nullptr,
                         e->d_done_scratch, d_trace_km ? d_trace_km + (size_t)s2 * N * 2 : nullptr, st, nullptr, e->sched) != 0) {
             set_error("step_kernel launch failed"); return FJSP_E_HIP;
         }

@@ -36,6 +36,7 @@ struct ArrivalService {
 
 struct fjsp_env {
     fjsp::DevBatch b{};
+    fjsp::LaunchPlan plan;             // which build of the kernels the launchers run for this batch, decided at create (plan_launch)
     int device = 0;
     std::vector<void *> dev_allocs, host_allocs;   // device / pinned memory, freed by fjsp_env_destroy
     std::vector<int> inst_K, inst_M;   // per packed instance

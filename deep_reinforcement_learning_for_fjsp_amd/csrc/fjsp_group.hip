@@ -36,11 +36,10 @@
 // Compiled with -ffp-contract=off: a*b+c must round twice like CPython.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../../include/fjsp_amd.h"
 #include "fjsp_common.h"
 #include "fjsp_device.h"
+#include "fjsp_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -964,105 +963,73 @@ extern "C" int fjsp_debug_read_gstamps(unsigned long long *out16, int reset) {
 #endif
 
 // ------------------------------------------------------------------ host launchers
-// Which build of the step.  Per-step launches of batches that leave a SIMD a single wave (4 environments per wave, 1 024 SIMDs:
+// The build a launch runs is decided once, when the batch is created: group_build() below holds the rules, plan_launch
+// (fjsp_env.hip) calls it for the per-step and the fused kernel and keeps both in the handle's LaunchPlan.  The two launchers
+// take the build from there, turn it into template arguments (dispatch_row) and launch (fjsp_launch.h).
+//
+// Early or lean.  Per-step launches of batches that leave a SIMD a single wave (4 environments per wave, 1 024 SIMDs:
 // up to 4 096 environments, a little beyond) run the variant that requests everything at the top -- nothing else hides a
 // memory round trip there; larger batches the register-lean one (measured crossover between 4 096 and 6 144 environments:
 // 8.09 vs 8.43 us at 4 096, 9.29 vs 9.08 us at 6 144).  The fused kernel always runs the lean build: its environment stays
 // in registers and LDS across steps, the early build's requests are redundant there and its registers cost the second
 // wave (4 096 envs: 771 -> 905 M env-steps/s with states, 1.08 -> 1.40 G without; 8 192: 809 M -> 1.49 G).
 // FJSP_GROUP_EARLY=0/1 overrides both (A/B runs).
-static int group_early_forced() {
-    static const int forced = [] { const char *v = getenv("FJSP_GROUP_EARLY"); return v ? atoi(v) : -1; }();
-    return forced;
-}
-static bool group_early(const DevBatch &b) { return group_early_forced() >= 0 ? group_early_forced() != 0 : b.N <= 5120; }
-static bool group_early_rollout(const DevBatch &) { return group_early_forced() >= 0 ? group_early_forced() != 0 : false; }
-// DIAGNOSTIC knob (A/B runs of the occupancy a batch size needs): FJSP_GROUP_LDS_PAD=<bytes> of extra dynamic LDS per wave
-static size_t group_lds_pad() {
-    static const size_t pad = [] { const char *v = getenv("FJSP_GROUP_LDS_PAD"); return v ? (size_t)atol(v) : (size_t)0; }();
-    return pad;
-}
-template <typename K>
-static inline void group_allow_lds(K kernel, size_t lds) {          // (as allow_lds of fjsp_kernels.hip: on every launch, per device)
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-// small-batch kernels: waves per workgroup (FJSP_GROUP_WPB=1|2|4 for A/B runs)
-static unsigned group_waves_per_block() {
-    static const unsigned w = [] { const char *v = getenv("FJSP_GROUP_WPB"); const int x = v ? atoi(v) : 4; return (unsigned)(x == 1 || x == 2 ? x : 4); }();
-    return w;
-}
-// The build a launch runs: early or lean (above), the machine capacity MPC of the batch's largest machine count, and for the
-// fused kernel whether the static tables are resident in LDS -- when the waves a CU gets (256 CUs, one wave per workgroup in the
-// lean build) fit its LDS with them.  The launchers below and fjsp_env_row_build take it from here.
-GroupBuild group_build(const DevBatch &b, bool fused) {
+// MPC: the machine capacity of the batch's largest machine count.
+// Resident: the fused kernel keeps the static tables in LDS when the waves a CU gets (256 CUs, one wave per workgroup in the
+// lean build) fit its LDS with them (FJSP_GROUP_RESIDENT=0/1 for A/B runs).
+// Waves per workgroup: 4 in the early build (FJSP_GROUP_WPB=1|2|4 for A/B runs), 1 in the lean one.
+GroupBuild group_build(const DevBatch &b, bool fused, const LaunchPlan &p) {
     GroupBuild g;
-    g.early = (fused ? group_early_rollout(b) : group_early(b)) ? 1 : 0;
+    g.early = (p.early_forced >= 0 ? p.early_forced != 0 : (!fused && b.N <= 5120)) ? 1 : 0;
     g.mpc = b.MP <= 5 ? 5 : 8;
     g.resident = 0;
     if (fused && !g.early) {
-        const unsigned waves = (unsigned)((b.N + 3) / 4), waves_per_cu = (waves + 255u) / 256u;
+        const unsigned waves_per_cu = (waves_for(b.N) + 255u) / 256u;
         const size_t res_lds = 4 * (size_t)(g.mpc == 5 ? grp::res_bytes<5>() : grp::res_bytes<8>());
         const size_t lean_lds = g.mpc == 5 ? grp::group_lds_bytes<5, false>() : grp::group_lds_bytes<8, false>();
-        static const int res_forced = [] { const char *v = getenv("FJSP_GROUP_RESIDENT"); return v ? atoi(v) : -1; }();
-        g.resident = (res_forced >= 0 ? res_forced != 0 : waves_per_cu * (lean_lds + res_lds) <= (size_t)152 * 1024) ? 1 : 0;
+        g.resident = (p.resident_forced >= 0 ? p.resident_forced != 0 : waves_per_cu * (lean_lds + res_lds) <= (size_t)152 * 1024) ? 1 : 0;
     }
+    g.wpb = !g.early ? 1u : (p.wpb_forced == 1 || p.wpb_forced == 2 ? (unsigned)p.wpb_forced : 4u);
     return g;
 }
-template <int V>
-static int launch_step_group_v(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
-                               uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec) {
-    const GroupBuild gb = group_build(b, false);
-    const bool early = gb.early != 0;
-    const unsigned wpb = early ? group_waves_per_block() : 1u, waves = (unsigned)((b.N + 3) / 4);
-    const dim3 grid((waves + wpb - 1) / wpb);
-#define FJSP_GSTEP(MPC, E) group_allow_lds(&grp::gstep_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()); hipLaunchKernelGGL((grp::gstep_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()), st, b, actions, mo, autoreset, state, reward, done, trace_km)
-#define FJSP_GSTEP_REC(MPC, E) group_allow_lds(&grp::gstep_rec_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()); hipLaunchKernelGGL((grp::gstep_rec_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + group_lds_pad()), st, b, actions, mo, autoreset, state, reward, done, trace_km, rec)
-    if (rec.rec) {          // recording (fjsp_env_record_schedule): the same step, plus the dispatch records
-        if (gb.mpc == 5) { if (early) { FJSP_GSTEP_REC(5, true); } else { FJSP_GSTEP_REC(5, false); } }
-        else { if (early) { FJSP_GSTEP_REC(8, true); } else { FJSP_GSTEP_REC(8, false); } }
-    } else if (gb.mpc == 5) { if (early) { FJSP_GSTEP(5, true); } else { FJSP_GSTEP(5, false); } }
-    else { if (early) { FJSP_GSTEP(8, true); } else { FJSP_GSTEP(8, false); } }
-#undef FJSP_GSTEP
-#undef FJSP_GSTEP_REC
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-int launch_step_group(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
-                      uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec) {
+
+// one instantiation per (variant, machine capacity, early or lean): f(v, mpc, early) returns what its launch returned
+template <class F>
+static int dispatch_row(const DevBatch &b, const GroupBuild &g, F &&f) {
+    auto build = [&](auto v) {
+        if (g.mpc == 5) return g.early ? f(v, int_c<5>{}, std::true_type{}) : f(v, int_c<5>{}, std::false_type{});
+        return g.early ? f(v, int_c<8>{}, std::true_type{}) : f(v, int_c<8>{}, std::false_type{});
+    };
     if (!b.grp) return -1;
-    if (b.variant == FJSP_VARIANT_SO_FJSSP) return launch_step_group_v<FJSP_VARIANT_SO_FJSSP>(b, actions, mo, autoreset, state, reward, done, trace_km, st, rec);
-    if (b.variant == FJSP_VARIANT_MO_FJSSP_DISCRETES)
-        return launch_step_group_v<FJSP_VARIANT_MO_FJSSP_DISCRETES>(b, actions, mo, autoreset, state, reward, done, trace_km, st, rec);
-    return -1;
+    switch (b.variant) {
+    case FJSP_VARIANT_SO_FJSSP: return build(int_c<FJSP_VARIANT_SO_FJSSP>{});
+    case FJSP_VARIANT_MO_FJSSP_DISCRETES: return build(int_c<FJSP_VARIANT_MO_FJSSP_DISCRETES>{});
+    default: return -1;
+    }
 }
 
-template <int V>
-static int launch_rollout_group_v(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
-                                  double *state_last, hipStream_t st, const SchedRec &rec) {
-    const GroupBuild gb = group_build(b, true);
-    const bool early = gb.early != 0;
-    const unsigned wpb = early ? group_waves_per_block() : 1u, waves = (unsigned)((b.N + 3) / 4);
-    const dim3 grid((waves + wpb - 1) / wpb);
-    const int resident = gb.resident;
-    const size_t extra = resident ? 4 * (size_t)(gb.mpc == 5 ? grp::res_bytes<5>() : grp::res_bytes<8>()) : 0;
-#define FJSP_GROLL(MPC, E) group_allow_lds(&grp::grollout_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + extra); hipLaunchKernelGGL((grp::grollout_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + extra), st, b, actions, mo, T, trace_km, reward, state_last, resident)
-#define FJSP_GROLL_REC(MPC, E) group_allow_lds(&grp::grollout_rec_kernel<V, MPC, E>, wpb * grp::group_lds_bytes<MPC, E>() + extra); hipLaunchKernelGGL((grp::grollout_rec_kernel<V, MPC, E>), grid, dim3(64 * wpb), (wpb * grp::group_lds_bytes<MPC, E>() + extra), st, b, actions, mo, T, trace_km, reward, state_last, resident, rec)
-    if (rec.rec) {
-        if (gb.mpc == 5) { if (early) { FJSP_GROLL_REC(5, true); } else { FJSP_GROLL_REC(5, false); } }
-        else { if (early) { FJSP_GROLL_REC(8, true); } else { FJSP_GROLL_REC(8, false); } }
-    } else if (gb.mpc == 5) { if (early) { FJSP_GROLL(5, true); } else { FJSP_GROLL(5, false); } }
-    else { if (early) { FJSP_GROLL(8, true); } else { FJSP_GROLL(8, false); } }
-#undef FJSP_GROLL
-#undef FJSP_GROLL_REC
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+int launch_step_group(const DevBatch &b, const LaunchPlan &p, const uint8_t *actions, const double *mo, int autoreset, double *state,
+                      double *reward, uint8_t *done, int16_t *trace_km, hipStream_t st, const SchedRec &rec) {
+    const GroupBuild &g = p.step;
+    return dispatch_row(b, g, [&](auto v, auto mpc, auto early) {
+        constexpr int V = decltype(v)::value, MPC = decltype(mpc)::value;
+        constexpr bool E = decltype(early)::value;
+        const size_t lds = g.wpb * grp::group_lds_bytes<MPC, E>() + p.lds_pad;
+        return launch_rec(&grp::gstep_kernel<V, MPC, E>, &grp::gstep_rec_kernel<V, MPC, E>, rec, grid_for_rows(b.N, g.wpb), dim3(64 * g.wpb), lds,
+                          st, b, actions, mo, autoreset, state, reward, done, trace_km);
+    });
 }
-int launch_rollout_group(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
-                         double *state_last, hipStream_t st, const SchedRec &rec) {
-    if (!b.grp) return -1;
-    if (b.variant == FJSP_VARIANT_SO_FJSSP) return launch_rollout_group_v<FJSP_VARIANT_SO_FJSSP>(b, actions, mo, T, trace_km, reward, state_last, st, rec);
-    if (b.variant == FJSP_VARIANT_MO_FJSSP_DISCRETES)
-        return launch_rollout_group_v<FJSP_VARIANT_MO_FJSSP_DISCRETES>(b, actions, mo, T, trace_km, reward, state_last, st, rec);
-    return -1;
+
+int launch_rollout_group(const DevBatch &b, const LaunchPlan &p, const uint8_t *actions, const double *mo, int T, int16_t *trace_km,
+                         double *reward, double *state_last, hipStream_t st, const SchedRec &rec) {
+    const GroupBuild &g = p.fused;
+    return dispatch_row(b, g, [&](auto v, auto mpc, auto early) {
+        constexpr int V = decltype(v)::value, MPC = decltype(mpc)::value;
+        constexpr bool E = decltype(early)::value;
+        const size_t lds = g.wpb * grp::group_lds_bytes<MPC, E>() + (g.resident ? 4 * (size_t)grp::res_bytes<MPC>() : 0);
+        return launch_rec(&grp::grollout_kernel<V, MPC, E>, &grp::grollout_rec_kernel<V, MPC, E>, rec, grid_for_rows(b.N, g.wpb), dim3(64 * g.wpb),
+                          lds, st, b, actions, mo, T, trace_km, reward, state_last, g.resident);
+    });
 }
 
 }  // namespace fjsp

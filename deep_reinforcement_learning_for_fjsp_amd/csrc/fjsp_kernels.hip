@@ -43,6 +43,7 @@
 
 #include "../../include/fjsp_amd.h"
 #include "fjsp_device.h"
+#include "fjsp_launch.h"
 #include "fjsp_common.h"
 #include "fjsp_pyset.h"
 #include "fjsp_policy.h"
@@ -1730,30 +1731,24 @@ __global__ void read_kernel(DevBatch b, int64_t *delay, int32_t *makespan, int32
 }
 
 // ------------------------------------------------------------------ host launchers
-static inline dim3 grid_for(int N) { return dim3((unsigned)((N + 3) / 4)); }
-// Dynamic LDS beyond the 64 KB default must be allowed per kernel (up to the 160 KB of a gfx950 CU; create refuses
-// batches beyond that, step_lds_bytes()).
-template <class K>
-static inline void allow_lds(K kernel, size_t lds) {
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
+// Every launcher: the dynamic LDS of its workgroups, then one launch()/launch_rec() (fjsp_launch.h) of the instantiation the
+// dispatchers below pick from the batch -- the argument list is named once, the recording twin gets `rec` appended.
 size_t step_lds_bytes(const DevBatch &b) { return 4 * lds_bytes_per_wave(b.JP, b.MP, b.KP, false); }
 
 int launch_fluid_tables(const DevBatch &b, hipStream_t st) {
     const int n = b.n_inst * b.KP;
-    hipLaunchKernelGGL(fluid_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch(fluid_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b);
 }
 
 // one instantiation per (chunk count, environment variant): the variant is a compile-time
 // parameter so SO_FJSSP's kernels carry none of the subclasses' code or registers
+// (f returns what its launch returned; -1: no such instantiation)
 template <int V, class F>
 static int dispatch_kc(int kc, F &&f) {
     switch (kc) {
-    case 1: f(std::integral_constant<int, 1>{}, std::integral_constant<int, V>{}); return 0;
-    case 2: f(std::integral_constant<int, 2>{}, std::integral_constant<int, V>{}); return 0;
-    case 4: f(std::integral_constant<int, 4>{}, std::integral_constant<int, V>{}); return 0;
+    case 1: return f(int_c<1>{}, int_c<V>{});
+    case 2: return f(int_c<2>{}, int_c<V>{});
+    case 4: return f(int_c<4>{}, int_c<V>{});
     default: return -1;
     }
 }
@@ -1768,68 +1763,43 @@ static int dispatch(const DevBatch &b, F &&f) {
     default: return -1;
     }
 }
+// ... and, for the step, whether every kind has a single job (SJ; the multi-order variants have no such build)
+template <class F>
+static int dispatch_sj(const DevBatch &b, F &&f) {
+    return dispatch(b, [&](auto kc, auto v) {
+        if constexpr (!is_mord_v<decltype(v)::value>)
+            if (b.single_job) return f(kc, v, std::true_type{});
+        return f(kc, v, std::false_type{});
+    });
+}
 
 int launch_reset(const DevBatch &b, const uint8_t *mask, double *state, hipStream_t st) {
     const size_t lds = step_lds_bytes(b);
-    if (dispatch(b, [&](auto kc, auto v) {
-            allow_lds(&reset_kernel<decltype(kc)::value, decltype(v)::value>, lds);
-            hipLaunchKernelGGL((reset_kernel<decltype(kc)::value, decltype(v)::value>), grid_for(b.N), dim3(256), lds, st, b,
-                               mask, state);
-        }) != 0) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return dispatch(b, [&](auto kc, auto v) {
+        return launch(&reset_kernel<decltype(kc)::value, decltype(v)::value>, grid_for(b.N), dim3(256), lds, st, b, mask, state);
+    });
 }
-int launch_step(const DevBatch &b, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
+int launch_step(const DevBatch &b, const LaunchPlan &p, const uint8_t *actions, const double *mo, int autoreset, double *state, double *reward,
                 uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready, const SchedRec &rec) {
-    if (b.grp && !ready) return launch_step_group(b, actions, mo, autoreset, state, reward, done, trace_km, st, rec);
+    if (b.grp && !ready) return launch_step_group(b, p, actions, mo, autoreset, state, reward, done, trace_km, st, rec);
     const size_t lds = step_lds_bytes(b);
-    if (dispatch(b, [&](auto kc, auto v) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            if (rec.rec) {         // recording (fjsp_env_record_schedule): the same step, plus the dispatch records
-                if constexpr (!is_mord_v<V>) {
-                    if (b.single_job) {
-                        allow_lds(&step_rec_kernel<KC, V, true>, lds);
-                        hipLaunchKernelGGL((step_rec_kernel<KC, V, true>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, autoreset, state,
-                                           reward, done, trace_km, ready, rec);
-                        return;
-                    }
-                }
-                allow_lds(&step_rec_kernel<KC, V, false>, lds);
-                hipLaunchKernelGGL((step_rec_kernel<KC, V, false>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, autoreset, state, reward,
-                                   done, trace_km, ready, rec);
-                return;
-            }
-            if constexpr (!is_mord_v<V>) {
-                if (b.single_job) {
-                    allow_lds(&step_kernel<KC, V, true>, lds);
-                    hipLaunchKernelGGL((step_kernel<KC, V, true>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, autoreset, state, reward,
-                                       done, trace_km, ready);
-                    return;
-                }
-            }
-            allow_lds(&step_kernel<KC, V, false>, lds);
-            hipLaunchKernelGGL((step_kernel<KC, V, false>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, autoreset, state, reward, done,
-                               trace_km, ready);
-        }) != 0) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return dispatch_sj(b, [&](auto kc, auto v, auto sj) {
+        constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+        constexpr bool SJ = decltype(sj)::value;
+        return launch_rec(&step_kernel<KC, V, SJ>, &step_rec_kernel<KC, V, SJ>, rec, grid_for(b.N), dim3(256), lds, st, b, actions, mo,
+                          autoreset, state, reward, done, trace_km, ready);
+    });
 }
 size_t rollout_lds_bytes(const DevBatch &b) { return 4 * lds_bytes_per_wave(b.JP, b.MP, b.KP, true); }
-int launch_rollout(const DevBatch &b, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
+int launch_rollout(const DevBatch &b, const LaunchPlan &p, const uint8_t *actions, const double *mo, int T, int16_t *trace_km, double *reward,
                    double *state_last, hipStream_t st, const SchedRec &rec) {
-    if (b.grp) return launch_rollout_group(b, actions, mo, T, trace_km, reward, state_last, st, rec);
+    if (b.grp) return launch_rollout_group(b, p, actions, mo, T, trace_km, reward, state_last, st, rec);
     const size_t lds = rollout_lds_bytes(b);
-    if (dispatch(b, [&](auto kc, auto v) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            if (rec.rec) {
-                allow_lds(&rollout_rec_kernel<KC, V>, lds);
-                hipLaunchKernelGGL((rollout_rec_kernel<KC, V>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, T, trace_km, reward,
-                                   state_last, rec);
-                return;
-            }
-            allow_lds(&rollout_kernel<KC, V>, lds);
-            hipLaunchKernelGGL((rollout_kernel<KC, V>), grid_for(b.N), dim3(256), lds, st, b, actions, mo, T, trace_km, reward,
-                               state_last);
-        }) != 0) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return dispatch(b, [&](auto kc, auto v) {
+        constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+        return launch_rec(&rollout_kernel<KC, V>, &rollout_rec_kernel<KC, V>, rec, grid_for(b.N), dim3(256), lds, st, b, actions, mo, T,
+                          trace_km, reward, state_last);
+    });
 }
 
 size_t policy_rollout_lds_bytes(const DevBatch &b, int S) {
@@ -1838,62 +1808,45 @@ size_t policy_rollout_lds_bytes(const DevBatch &b, int S) {
 }
 int launch_actor_forward(const ActorParams &ap, const double *state, int n, float *probs, hipStream_t st) {
     const size_t lds = actor_lds_floats(ap.S) * 4 + 16 * (32 + kActorH + kActorAP) * 4;
-    allow_lds(&actor_forward_kernel, lds);
-    hipLaunchKernelGGL(actor_forward_kernel, dim3((unsigned)((n + 15) / 16)), dim3(1024), lds, st, ap, state, n, probs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch(&actor_forward_kernel, grid_for16(n), dim3(1024), lds, st, ap, state, n, probs);
 }
+// the policy kernels: 16 environments per workgroup; built for one chunk (K <= 64) of the single-order variants only
 int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st,
                           const SchedRec &rec) {
     if (b.mord || b.KC != 1) return -1;                 // order arrivals need the host LP service between steps; K <= 64
     const size_t lds = policy_rollout_lds_bytes(b, ap.S);
-    if (dispatch(b, [&](auto kc, auto v) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            if constexpr (!is_mord_v<V> && KC == 1) {
-                if (rec.rec) {
-                    allow_lds(&rollout_policy_rec_kernel<KC, V>, lds);
-                    hipLaunchKernelGGL((rollout_policy_rec_kernel<KC, V>), dim3((unsigned)((b.N + 15) / 16)), dim3(1024), lds, st, b, ap, io, mo, T,
-                                       rec);
-                    return;
-                }
-                allow_lds(&rollout_policy_kernel<KC, V>, lds);
-                hipLaunchKernelGGL((rollout_policy_kernel<KC, V>), dim3((unsigned)((b.N + 15) / 16)), dim3(1024), lds, st, b, ap, io, mo, T);
-            }
-        }) != 0) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return dispatch(b, [&](auto kc, auto v) {
+        constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+        if constexpr (!is_mord_v<V> && KC == 1)
+            return launch_rec(&rollout_policy_kernel<KC, V>, &rollout_policy_rec_kernel<KC, V>, rec, grid_for16(b.N), dim3(1024), lds, st, b, ap,
+                              io, mo, T);
+        else
+            return -1;
+    });
 }
-
 int launch_play_policy(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, hipStream_t st,
                        const SchedRec &rec) {
     if (b.mord || b.KC != 1) return -1;                 // as launch_rollout_policy
     const size_t lds = policy_rollout_lds_bytes(b, ap.S);
-    if (dispatch(b, [&](auto kc, auto v) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            if constexpr (!is_mord_v<V> && KC == 1) {
-                if (rec.rec) {
-                    allow_lds(&play_policy_rec_kernel<KC, V>, lds);
-                    hipLaunchKernelGGL((play_policy_rec_kernel<KC, V>), dim3((unsigned)((b.N + 15) / 16)), dim3(1024), lds, st, b, ap, io, mo, T,
-                                       rec);
-                    return;
-                }
-                allow_lds(&play_policy_kernel<KC, V>, lds);
-                hipLaunchKernelGGL((play_policy_kernel<KC, V>), dim3((unsigned)((b.N + 15) / 16)), dim3(1024), lds, st, b, ap, io, mo, T);
-            }
-        }) != 0) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return dispatch(b, [&](auto kc, auto v) {
+        constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+        if constexpr (!is_mord_v<V> && KC == 1)
+            return launch_rec(&play_policy_kernel<KC, V>, &play_policy_rec_kernel<KC, V>, rec, grid_for16(b.N), dim3(1024), lds, st, b, ap, io,
+                              mo, T);
+        else
+            return -1;
+    });
 }
 
+// (only the two multi-order variants have an arrival_kernel: its own two-way choice, not dispatch())
 int launch_arrival(const DevBatch &b, const double *mo, int n_pending, const uint32_t *ids, const double *x_list, double *state,
                    double *reward, uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready, bool mark_resumed, const uint32_t *n_dev) {
     const size_t lds = step_lds_bytes(b);
-    const dim3 grid((unsigned)(((n_dev ? b.N : n_pending) + 3) / 4));
     auto go = [&](auto kc, auto v) {
-        allow_lds(&arrival_kernel<decltype(kc)::value, decltype(v)::value>, lds);
-        hipLaunchKernelGGL((arrival_kernel<decltype(kc)::value, decltype(v)::value>), grid, dim3(256), lds, st, b, mo,
-                           n_pending, ids, x_list, state, reward, done, trace_km, ready, mark_resumed ? 1 : 0, n_dev);
+        return launch(&arrival_kernel<decltype(kc)::value, decltype(v)::value>, grid_for(n_dev ? b.N : n_pending), dim3(256), lds, st, b, mo,
+                      n_pending, ids, x_list, state, reward, done, trace_km, ready, mark_resumed ? 1 : 0, n_dev);
     };
-    const int rc = b.variant == FJSP_VARIANT_MO_DFJSP ? dispatch_kc<kDyn>(b.KC, go) : dispatch_kc<kMord>(b.KC, go);
-    if (rc != 0) return -1;
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return b.variant == FJSP_VARIANT_MO_DFJSP ? dispatch_kc<kDyn>(b.KC, go) : dispatch_kc<kMord>(b.KC, go);
 }
 // fjsp_env_schedule: the slot-major records of every env -> i32[N][cap][6] (r, j, n, m, begin, end), one thread per (env, slot);
 // slots at or past the env's step_count hold -1.  k -> (r, j) from the instance record's kind words (i_kB).
@@ -1922,14 +1875,12 @@ __global__ __launch_bounds__(256) void schedule_unpack_kernel(DevBatch b, SchedR
 int launch_schedule_unpack(const DevBatch &b, const SchedRec &rec, int32_t *table, int32_t *len, hipStream_t st) {
     const size_t n = (size_t)b.N * (size_t)rec.cap;
     if (!rec.rec || n == 0) return -1;
-    hipLaunchKernelGGL(schedule_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b, rec, table, len);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch(schedule_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b, rec, table, len);
 }
 int launch_read(const DevBatch &b, int64_t *delay, int32_t *makespan, int32_t *completion, int32_t *step_time,
                 int32_t *step_count, uint8_t *done, uint32_t *status, hipStream_t st) {
-    hipLaunchKernelGGL(read_kernel, dim3((unsigned)((b.N + 255) / 256)), dim3(256), 0, st, b, delay, makespan,
-                       completion, step_time, step_count, done, status);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch(read_kernel, dim3((unsigned)((b.N + 255) / 256)), dim3(256), 0, st, b, delay, makespan, completion, step_time, step_count,
+                  done, status);
 }
 
 #ifdef FJSP_STAMPS

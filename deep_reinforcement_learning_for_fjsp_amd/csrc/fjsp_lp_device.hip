@@ -22,6 +22,7 @@
 #include "../../include/fjsp_amd.h"
 #include "fjsp_common.h"
 #include "fjsp_device.h"
+#include "fjsp_launch.h"
 
 #pragma clang fp contract(off)
 
@@ -507,12 +508,9 @@ __global__ __launch_bounds__(kThreads) void lp_device_kernel(DevBatch b, const u
 
 int launch_lp_device(const DevBatch &b, const uint32_t *count_dev, int count_host, const uint32_t *ids, const uint16_t *lp_in, double *lp_x,
                      uint32_t *err, unsigned long long *solved, size_t lds, hipStream_t st) {
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(lp_device_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const int grid = count_dev ? (b.N < 256 ? b.N : 256) : count_host;
     if (grid <= 0) return 0;
-    hipLaunchKernelGGL(lp_device_kernel, dim3((unsigned)grid), dim3(kThreads), lds, st, b, count_dev, count_host, ids, lp_in, lp_x, err, solved, (uint32_t)lds);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch(lp_device_kernel, dim3((unsigned)grid), dim3(kThreads), lds, st, b, count_dev, count_host, ids, lp_in, lp_x, err, solved, (uint32_t)lds);
 }
 
 }  // namespace fjsp

@@ -324,14 +324,15 @@ int64_t fjsp_env_step_bytes(const fjsp_env *e);
 /* Which kernel family steps this batch: 0 = one wavefront per environment (csrc/fjsp_kernels.hip: every variant and
  * shape), 1 = one 16-lane row per environment (csrc/fjsp_group.hip: SO_FJSSP / SO_DFJSP / MO_FJSSP_discretes batches of
  * one job per kind, one order, <= 64 operation types, <= 8 machines, <= 15 jobs -- the reference's 10x5 and Brandimarte
- * shapes).  Same results either way; the environment variable FJSP_STEP_IMPL=wave at create time forces 0. */
+ * shapes).  Same results either way; the environment variable FJSP_STEP_IMPL=wave at create time forces 0 (create is
+ * where the library reads every FJSP_* variable: what they decide stays with the handle). */
 int fjsp_env_kernel_family(const fjsp_env *e);
-/* Which build of the row kernels a launch of this batch runs (kernel family 1), from the host function the launchers
- * themselves decide with: out3 = {early, mpc, resident} of the per-step launch (fused = 0: fjsp_env_step and its kin) or
+/* Which build of the row kernels a launch of this batch runs (kernel family 1): decided once, when the batch is created,
+ * and stored in the handle, from where the launchers take it and this call reports it: out3 = {early, mpc, resident} of the per-step launch (fused = 0: fjsp_env_step and its kin) or
  * of the fused launch (fused = 1: fjsp_env_rollout).  early: 1 = the small-batch build that requests everything at the top
  * of a step, 0 = the register-lean build; mpc: the machine capacity the kernels were compiled for (5 or 8); resident: 1 =
  * the fused kernel keeps the instance's static tables in LDS (always 0 for fused = 0).  FJSP_GROUP_EARLY /
- * FJSP_GROUP_RESIDENT are included.  FJSP_E_UNSUPPORTED for a batch of the one-wave-per-environment family. */
+ * FJSP_GROUP_RESIDENT, as set when the batch was created, are included.  FJSP_E_UNSUPPORTED for a batch of the one-wave-per-environment family. */
 int fjsp_env_row_build(const fjsp_env *e, int32_t fused, int32_t *out3);
 /* Order arrivals (SO_FJSSP.py:218-231) re-solve the fluid LP on the host, one LP per arriving env, spread
  * over n_threads host threads (0 = default: min(host cores, 16)).  fjsp_env_lp_solves: LPs solved so far. */
