@@ -517,7 +517,12 @@ int fjsp_env_lp_device_solve(fjsp_env *e, int32_t env, const int32_t *Q, const i
     const DevBatch &b = e->b;
     const Instance &in = e->src->v[(size_t)e->first + (size_t)(env % b.n_inst)];
     std::vector<uint16_t> lpq((size_t)2 * b.KP, 0);
-    for (int k = 0; k < in.K; ++k) { lpq[(size_t)k] = (uint16_t)Q[k]; lpq[(size_t)b.KP + k] = (uint16_t)n_now[k]; }
+    for (int k = 0; k < in.K; ++k) {          // the staging arrays hold 16-bit counts (a batch has at most 65535 jobs)
+        if (Q[k] < 0 || Q[k] > 65535 || n_now[k] < 0 || n_now[k] > 65535) {
+            set_error("fjsp_env_lp_device_solve: Q[k] and n_now[k] must lie in 0 ... 65535"); return FJSP_E_ARG;
+        }
+        lpq[(size_t)k] = (uint16_t)Q[k]; lpq[(size_t)b.KP + k] = (uint16_t)n_now[k];
+    }
     const uint32_t id = (uint32_t)env;
     // (slot 0 of the staging arrays; the batch must be idle: no parked environments)
     HIP_TRY(hipDeviceSynchronize());

@@ -10,7 +10,8 @@
 //     sequential scan over the rows with its tolerances, run by one lane over values the other lanes have laid out --, same
 //     elimination arithmetic (f64 divide, multiply, subtract: -ffp-contract=off, no FMA; the host's AVX clones are built
 //     without FMA for the same reason), same clean-up of tiny negative right-hand sides, same extraction of x;
-//   * so x is BIT-IDENTICAL to fjsp_lp.cpp's (tests/test_gpu_parity.py::test_device_lp_equals_the_host_lp), and the
+//   * so x is BIT-IDENTICAL to fjsp_lp.cpp's (tests/test_gpu_lp_device.py, every compiled width; tests/lp_reference.py
+//     restates both files in numpy and counts which branches the tested LPs take), and the
 //     environment's trajectory does not depend on where its LPs were solved;
 //   * the tableau of the reference's industrial instances (K = 31, M = 20: 79 rows x 137 columns) is 87 KB: it lives in
 //     LDS (160 KB per CU); a batch whose largest possible tableau does not fit keeps the host service (fjsp_env.hip
@@ -147,7 +148,10 @@ __device__ __forceinline__ int lp_pivots(const LpTab tab, const int w, const int
         // with its expressions) put strictly beyond the tolerance from them, the scan's result is the FIRST
         // LEXICOGRAPHIC MINIMUM among the former -- an order-independent quantity -- and the whole set is narrowed
         // column by column with the rows in lanes; anything else (near-ties with different ratios, more than 128 rows)
-        // takes the sequential scan below.
+        // takes the sequential scan below.  (More than 128 rows: no batch the create rule admits has them -- nr >= 129 needs
+        // K >= 49 operation types at M <= 32, hence nc >= K + nr + 2 >= 180 columns and 129 * 180 * 8 B of tableau, beyond the
+        // 156 KB of choose_lp_service; tests/test_lp_reference.py sweeps every admissible shape.  The guard here, the scan's
+        // later bases and the elimination loop from row 128 below are kept, unreached, until a measured build without them.)
         int r = -1;
         double ar = 0.0, vr = 0.0;
         double acol[2] = {0.0, 0.0};          // column s of rows l and 64 + l: the elimination's factors (later rows: from LDS)
@@ -336,7 +340,7 @@ __device__ __forceinline__ int lp_pivots(const LpTab tab, const int w, const int
                 }
             }
         }
-        for (int i = 128 + w; i < nr; i += kWaves) {                  // (rows beyond the factors held in lanes)
+        for (int i = 128 + w; i < nr; i += kWaves) {                  // (rows beyond the factors held in lanes: none in an admitted batch)
             if (i == r) continue;
             double *rowi = &T[(size_t)i * nc];
             const double f = rowi[s];

@@ -345,7 +345,9 @@ int64_t fjsp_env_lp_solves(const fjsp_env *e);
  * ~6x slower on the device than on a host core, 256 run at once: below that size the host service with its cache of solved
  * LPs is as fast or faster (DESIGN.md has the measurements).  FJSP_LP_IMPL=device / host at create time overrides the size rule.
  * fjsp_env_lp_device_solve (test hook): the device solver on one LP of env's instance -- Q[K], n_now[K] as
- * class_FJSSP.py:234-237 builds them -- x f64[K*M] (k-major) to the host; the batch must have no parked environments. */
+ * class_FJSSP.py:234-237 builds them -- x f64[K*M] (k-major) to the host; the batch must have no parked environments.
+ * The device stages both as 16-bit counts: a Q[k] or n_now[k] outside 0 ... 65535 is FJSP_E_ARG (never a truncated value);
+ * Q[k] = 0 is FJSP_E_LP, as the host solver refuses it, and leaves the handle usable. */
 int fjsp_env_lp_on_device(const fjsp_env *e);
 /* Pivots the device simplex has executed so far, all LPs together (0 when the batch keeps the host service; synchronises). */
 int64_t fjsp_env_lp_device_pivots(const fjsp_env *e);

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import helpers as H
+from tests.lp_reference import lp_highs as _lp_highs      # (shared with tests/test_lp_reference.py)
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -149,44 +150,6 @@ def test_generator_is_seeded_and_in_range(built):
     big = fi.InstanceSet(1).generate(0, 7, fi.reference_generator_params(1.0, 15, 3)).arrays(0)
     assert 3 <= big.R <= 12 and big.S == 3 and 40 <= big.p[big.p > 0].min() and big.p.max() <= 400
     assert (big.count >= 5).all() and (big.count <= 50).all() and big.arrive[0] == 0
-
-
-def _lp_highs(a, Q, now):
-    """Independent formulation of class_FJSSP.py:246-280 solved by scipy/HiGHS."""
-    from scipy.optimize import linprog
-    K, M = a.p.shape
-    cols = [(k, m) for k in range(K) for m in range(M) if a.p[k, m] > 0]
-    idx = {km: i for i, km in enumerate(cols)}
-    n = len(cols) + 1
-    A, b = [], []
-    for k in range(K):
-        row = np.zeros(n); row[-1] = 1.0
-        for m in range(M):
-            if a.p[k, m] > 0:
-                row[idx[(k, m)]] = -(1.0 / a.p[k, m]) / Q[k]
-        A.append(row); b.append(0.0)
-    for m in range(M):
-        row = np.zeros(n)
-        for k in range(K):
-            if a.p[k, m] > 0:
-                row[idx[(k, m)]] = 1.0
-        A.append(row); b.append(1.0)
-    koff = np.concatenate(([0], np.cumsum(a.Jr)))
-    for r in range(len(a.Jr)):
-        for j in range(int(a.Jr[r]) - 1):
-            k = int(koff[r]) + j
-            if now[k + 1] == 0:
-                row = np.zeros(n)
-                for m in range(M):
-                    if a.p[k + 1, m] > 0:
-                        row[idx[(k + 1, m)]] += 1.0 / a.p[k + 1, m]
-                    if a.p[k, m] > 0:
-                        row[idx[(k, m)]] -= 1.0 / a.p[k, m]
-                A.append(row); b.append(0.0)
-    c = np.zeros(n); c[-1] = -1.0
-    res = linprog(c, A_ub=np.array(A), b_ub=np.array(b), bounds=[(0, 1)] * len(cols) + [(None, None)], method="highs")
-    assert res.status == 0
-    return -res.fun, np.array(A), np.array(b), idx
 
 
 def test_fluid_lp_is_optimal_and_deterministic(built):
