@@ -182,6 +182,10 @@ struct GE {
     // lane = machine
     int tend, mjob, mcnt;      // mcnt: operation types the machine can process (static)
     double obs_prev;           // lane (8 + i) & 15: observation i of the previous step
+    // early build, autoreset: the reset observation of the rows restarted by this launch, in flight until g_restart_merge
+    // puts it into obs_prev (nothing reads obs_prev before the end of the step: g_restart)
+    double obs_re;
+    bool re_on;
     // row-uniform
     int K, M, njobs;
     uint32_t mmask;
@@ -342,12 +346,15 @@ template <int V, int MPC>
 GDEV void g_cols_issue(const GE<V> &e, const DevBatch &b, bool need, GCols<MPC> &cr) {
     const double2 *colm = reinterpret_cast<const double2 *>(e.ir + b.L.i_colm);
     const uint32_t idle = need ? (~e.busy & e.mmask) : 0u;
+    // (the machine outside, its slots inside: one predicated region per machine holds the loads of its slots)
 #pragma unroll
-    for (int s = 0; s < GS; ++s) {
+    for (int m = 0; m < MPC; ++m) {
 #pragma unroll
-        for (int m = 0; m < MPC; ++m) {
-            cr.c[s][m] = make_double2(0.0, 0.0);
-            if (SLOT_ON(e, s) && ((idle >> m) & 1u)) cr.c[s][m] = colm[m * 64 + 16 * s + e.l];
+        for (int s = 0; s < GS; ++s) cr.c[s][m] = make_double2(0.0, 0.0);
+        if ((idle >> m) & 1u) {
+#pragma unroll
+            for (int s = 0; s < GS; ++s)
+                if (SLOT_ON(e, s)) cr.c[s][m] = colm[m * 64 + 16 * s + e.l];
         }
     }
 }
@@ -420,9 +427,12 @@ GDEV double g_gap_ave_lean(const GE<V> &e, const DevBatch &b, bool need, uint32_
 // CPython set involved iterates in ascending order (fjsp_pyset.h), the candidate lists are bit masks and "first
 // extremum wins" is the lowest machine lane that attains it.  gap_rows: the rows whose LDS rows hold Machine.gap_ave's
 // operands.  Returns m or -1 (status set); *pm_out its processing time.
-template <int V, bool EARLY>
+// EARLY: the chosen operation's column is a fetch that depends on task_select, and a wave that is alone on its SIMD pays its
+// whole latency unless something runs meanwhile.  So the column is requested first, then come `after_issue` (g_step lays out
+// Machine.gap_ave's operands there), the gap_ave walk and its division, and only the key consumes the column.
+template <int V, bool EARLY, class F>
 GDEV int g_machine_select(GE<V> &e, const DevBatch &b, bool go, int a1, int k_sel, uint32_t em_sel, uint32_t idle, bool gap_rows,
-                          int *pm_out) {
+                          int *pm_out, F &&after_issue) {
     constexpr bool is_mo = V == FJSP_VARIANT_MO_FJSSP_DISCRETES;
     const uint32_t sel = idle & em_sel, fsel = idle & (em_sel >> 8);         // (idle has the low 8 bits only)
     e.status |= (go && sel == 0) ? (uint32_t)FJSP_ST_NO_EVENT : 0u;
@@ -443,25 +453,42 @@ GDEV int g_machine_select(GE<V> &e, const DevBatch &b, bool go, int a1, int k_se
     C = run ? C : 0u;
     const bool mem = ((C >> e.l) & 1u) != 0;            // (C has bits below 8 only)
     int pm = 0;
+    uint16_t pm16 = 0;          // (early: the processing time as loaded -- widening it is a use, and a use is a wait)
     double g = 0.0;
+    double2 ar = make_double2(0.0, 0.0);
+    if constexpr (EARLY) {
+        // Loads return in order and the wait counter counts them: a wait for anything requested earlier that came behind the
+        // column's request would wait for the column too.  What is still out -- the rows of g_cols_issue, the reset observation
+        // of g_restart -- has had the whole of task_select to arrive, so it is waited for HERE, explicitly (s_waitcnt vmcnt(0),
+        // gfx9 encoding; the empty asm statements keep it behind k_sel and between the two groups of loads).
+        asm volatile("" : : "v"(k_sel) : "memory");
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        asm volatile("" : : : "memory");
+    }
     if (((run ? sel : 0u) >> e.l) & 1u) {
         // lane m: p[m][k_sel] and gap_rj_dict[m][k_sel] (class_FJSSP.py:137-142); op-major layout: the column of k_sel is MP
         // contiguous entries per array.  k_sel has not been dispatched yet -- it is available -- so its unprocessed is
         // its arrival
         const int o = k_sel * e.MP + e.l;
-        double2 ar;
         if (e.resident) { pm = res_P(e.res)[o]; ar = res_C(e.res)[e.l * 64 + k_sel]; }   // (the machine-major copy holds the same entries)
-        else { pm = reinterpret_cast<const uint16_t *>(e.ir + b.L.i_p)[o]; ar = reinterpret_cast<const double2 *>(e.ir + b.L.i_col)[o]; }
-        g = ar.x - (ar.x - (double)e.t * ar.y);
+        else { pm16 = reinterpret_cast<const uint16_t *>(e.ir + b.L.i_p)[o]; ar = reinterpret_cast<const double2 *>(e.ir + b.L.i_col)[o]; }
+        if constexpr (!EARLY) { pm = e.resident ? pm : (int)pm16; g = ar.x - (ar.x - (double)e.t * ar.y); }
     }
+    after_issue();
     const bool need3 = m_gave && gap_rows && (C & (C - 1)) != 0;     // (a list of one is returned without ranking it)
     if (wave_any(need3)) {
         // Machine.gap_ave (class_FJSSP.py:144-146): the strictly sequential sum of the machine's row / (n + 1e-18)
         double gave;
         if (EARLY) gave = g_walk<V>(e, need3 && e.l < e.M, e.l) / ((double)e.mcnt + 1e-18);       // (rows: g_gap_rows)
         else gave = g_gap_ave_lean<V>(e, b, need3, C);
+        if constexpr (EARLY) {
+            // (the column's values pass through an empty asm statement that takes the walk's result: they are not waited for before it)
+            asm volatile("" : "+v"(ar.x), "+v"(ar.y), "+v"(pm16) : "v"(gave));
+            pm = e.resident ? pm : (int)pm16;
+            g = ar.x - (ar.x - (double)e.t * ar.y);
+        }
         g = need3 ? gave : g;
-    }
+    } else if constexpr (EARLY) { pm = e.resident ? pm : (int)pm16; g = ar.x - (ar.x - (double)e.t * ar.y); }
     uint64_t key = sortable(g);
     key = m_pt ? sortable_min_i32(pm) : key;
     key = (m_rnd || (m_gave && !need3)) ? 0ull : key;   // no ranking: every member ties
@@ -699,8 +726,13 @@ GDEV void g_emit(GE<V> &e, bool on, double cur, const double *sstate, double *st
 }
 
 // Bind the four rows of a wave to their records and bring the environments in: every load is independent of the
-// others (bounds come from the kernel arguments), one memory round trip.  `between` runs after the loads are out and
-// before they are waited for (the kernels request the gap_ave rows there).
+// others (bounds come from the kernel arguments).  `between` runs after the loads are out and before they are waited for.
+// EARLY (a wave alone on its SIMD: nothing hides a wait): ONE memory round trip, and the compiled code has to show it -- no
+// vmcnt wait between the first and the last load.  Independent loads are not enough for that: a load under a lane predicate
+// gets an exec region, and the copy that merges its result with the other lanes' zero is a use, i.e. a wait for everything
+// requested so far, in the middle of the requests.  So the early build loads straight-line from clamped indices and masks on
+// arrival, and takes every value at the end (see there).  The lean build keeps the predicated form: its resident waves hide
+// the second trip, and it requests no line it can do without.
 template <int V, bool EARLY, class F>
 GDEV void g_open(GE<V> &e, const DevBatch &b, int wave_id, unsigned char *lds, int rows_per_env, F &&between) {
     using FO = FixedOffsets;
@@ -731,28 +763,61 @@ GDEV void g_open(GE<V> &e, const DevBatch &b, int wave_id, unsigned char *lds, i
     const int duej = reinterpret_cast<const int32_t *>(op + 2048 + 64)[e.l];
     uint4 A[GS];
     double2 B[GS];
-#pragma unroll
-    for (int s = 0; s < GS; ++s) {
-        A[s] = make_uint4(0u, 0u, 0u, 0u); B[s] = make_double2(0.0, 0.0);
-        if (16 * s + e.l < kq) {
-            const unsigned char *slot = op + s * 512;
-            // the two operation words from the 8-byte copy (the due date comes from the job's lane, g_observe)
-            const uint2 a8 = reinterpret_cast<const uint2 *>(ir + b.L.i_op8)[16 * s + e.l];
-            A[s] = make_uint4(a8.x, a8.y, 0u, 0u);
-            if (EARLY) B[s] = reinterpret_cast<const double2 *>(slot + 256)[e.l];      // (large batches: g_gather_current, g_observe)
-        }
-    }
-    const uint32_t asgw = reinterpret_cast<const uint32_t *>(er + FO::e_asg((uint32_t)MP, (uint32_t)JP, 64u, true))[e.l];
-    uint32_t jwl = 0;
-    if (e.l < b.jcap) jwl = reinterpret_cast<const uint32_t *>(er + FO::e_jst((uint32_t)MP))[e.l];
+    uint32_t asgw, jwl = 0;
     int tend = 0, mjob = -1;
-    if (e.l < MP) {
-        tend = reinterpret_cast<const int32_t *>(er + FO::e_tend())[e.l];
-        mjob = reinterpret_cast<const int32_t *>(er + FO::e_mjob((uint32_t)MP))[e.l];
+    long long sc, sc2 = 0;
+    if constexpr (EARLY) {
+        // straight-line: a lane without an operation type (or job, or machine) reads the LAST entry its row reads anyway (a line
+        // the row fetches: no byte more, never an address outside the instance's or the environment's record) and drops the
+        // value once it has arrived.  A load under a lane predicate sits in an exec region of its own, and the merge of its
+        // result with the zero of the other lanes made the compiler wait for the loads issued so far inside the second
+        // region: two memory round trips in a row instead of one.
+        const uint2 *op8 = reinterpret_cast<const uint2 *>(ir + b.L.i_op8);
+        const int klast = max(kq, 1) - 1;
+        uint2 a8[GS];
+#pragma unroll
+        for (int s = 0; s < GS; ++s) {
+            const int k = min(16 * s + e.l, klast);
+            a8[s] = op8[k];
+            B[s] = reinterpret_cast<const double2 *>(op + (k >> 4) * 512 + 256)[k & 15];
+        }
+        asgw = reinterpret_cast<const uint32_t *>(er + FO::e_asg((uint32_t)MP, (uint32_t)JP, 64u, true))[e.l];
+        jwl = reinterpret_cast<const uint32_t *>(er + FO::e_jst((uint32_t)MP))[min(e.l, max(b.jcap, 1) - 1)];
+        const int ml = min(e.l, MP - 1);
+        tend = reinterpret_cast<const int32_t *>(er + FO::e_tend())[ml];
+        mjob = reinterpret_cast<const int32_t *>(er + FO::e_mjob((uint32_t)MP))[ml];
+        sc = reinterpret_cast<const long long *>(er)[e.l];                        // EnvScalars words 0..15
+        sc2 = reinterpret_cast<const long long *>(er)[16 + min(e.l, 1)];          // obs_prev[8], [9]
+        // ---- mask: exactly the values of the predicated form
+#pragma unroll
+        for (int s = 0; s < GS; ++s) {
+            const bool has = 16 * s + e.l < kq;
+            A[s] = make_uint4(has ? a8[s].x : 0u, has ? a8[s].y : 0u, 0u, 0u);
+            B[s] = make_double2(has ? B[s].x : 0.0, has ? B[s].y : 0.0);
+        }
+        jwl = e.l < b.jcap ? jwl : 0u;
+        tend = e.l < MP ? tend : 0; mjob = e.l < MP ? mjob : -1;
+        sc2 = e.l < 2 ? sc2 : 0ll;
+    } else {
+#pragma unroll
+        for (int s = 0; s < GS; ++s) {
+            A[s] = make_uint4(0u, 0u, 0u, 0u); B[s] = make_double2(0.0, 0.0);
+            if (16 * s + e.l < kq) {
+                // the two operation words from the 8-byte copy (the due date comes from the job's lane, g_observe; the fluid
+                // numbers: g_gather_current, g_observe)
+                const uint2 a8 = reinterpret_cast<const uint2 *>(ir + b.L.i_op8)[16 * s + e.l];
+                A[s] = make_uint4(a8.x, a8.y, 0u, 0u);
+            }
+        }
+        asgw = reinterpret_cast<const uint32_t *>(er + FO::e_asg((uint32_t)MP, (uint32_t)JP, 64u, true))[e.l];
+        if (e.l < b.jcap) jwl = reinterpret_cast<const uint32_t *>(er + FO::e_jst((uint32_t)MP))[e.l];
+        if (e.l < MP) {
+            tend = reinterpret_cast<const int32_t *>(er + FO::e_tend())[e.l];
+            mjob = reinterpret_cast<const int32_t *>(er + FO::e_mjob((uint32_t)MP))[e.l];
+        }
+        sc = reinterpret_cast<const long long *>(er)[e.l];            // EnvScalars words 0..15
+        if (e.l < 2) sc2 = reinterpret_cast<const long long *>(er)[16 + e.l];         // obs_prev[8], [9]
     }
-    const long long sc = reinterpret_cast<const long long *>(er)[e.l];            // EnvScalars words 0..15
-    long long sc2 = 0;
-    if (e.l < 2) sc2 = reinterpret_cast<const long long *>(er)[16 + e.l];         // obs_prev[8], [9]
     // (the slots in use are known from the batch until the instance words arrive: the requests of `between` cover them all)
     e.nslots = (b.kmax + 15) >> 4;
     between();
@@ -790,6 +855,15 @@ GDEV void g_open(GE<V> &e, const DevBatch &b, int wave_id, unsigned char *lds, i
     e.tard_done = bcl<5>(sc); e.delay_sum = bcl<6>(sc);
     e.t_arr = bc<7>(lo); e.misc = bcu<7>((uint32_t)hi);
     e.obs_prev = __longlong_as_double(e.l >= 8 ? sc : sc2);
+    e.obs_re = 0.0; e.re_on = false;
+    if constexpr (EARLY) {
+        // (every value of the prologue is taken HERE, through empty asm statements: left alone the compiler sinks the masks behind
+        // the requests of g_restart and g_cols_issue, and the wait for a prologue load -- loads return in order -- would then wait
+        // for those requests too)
+#pragma unroll
+        for (int s = 0; s < GS; ++s) asm volatile("" : "+v"(e.kB[s]), "+v"(e.em[s]), "+v"(e.rsum[s]), "+v"(e.tsum[s]));
+        asm volatile("" : "+v"(e.asgw), "+v"(e.jwl), "+v"(e.tend), "+v"(e.mjob), "+v"(e.obs_prev), "+v"(e.duej), "+v"(e.jinfo));
+    }
     e.env_seed = b.rng_seed + (uint64_t)e.env * 1000003ULL;
 }
 
@@ -830,7 +904,10 @@ GDEV void g_store(const GE<V> &e, const DevBatch &b) {
 
 // SO_FJSSP.py:51-76 reset of the rows with `on`, as the autoreset path of a step needs it (fresh-object semantics; the
 // observation of the reset state was published per instance by reset_kernel: Layout::i_obs0); rng_calls survives
-template <int V>
+// EARLY: the fetched observation stays in a register of its own (obs_re, re_on) and nothing waits for it here; g_restart_merge
+// puts it into obs_prev at the end of the step, where obs_prev is first read.  (A restarted row's observation is current --
+// misc -- so g_obs_refresh never writes its obs_prev in between.)
+template <int V, bool EARLY>
 GDEV void g_restart(GE<V> &e, const DevBatch &b, bool on) {
     const int oi = (e.l - 8) & 15;
     double o0 = 0.0;
@@ -842,8 +919,14 @@ GDEV void g_restart(GE<V> &e, const DevBatch &b, bool on) {
         e.n_un = e.njobs; e.seq_ctr = (uint32_t)e.njobs;
         if (e.l < e.njobs) e.jwl = jst_pack((uint32_t)e.l, 0u);               // class_FJSSP.py:225 (job n = kind n)
         e.asgw = 0xFFFFFFFFu;                                                   // :304 unprocessed = arrival
-        e.obs_prev = o0;
+        if constexpr (!EARLY) e.obs_prev = o0;
     }
+    if constexpr (EARLY) { e.obs_re = o0; e.re_on = on; }
+}
+template <int V>
+GDEV void g_restart_merge(GE<V> &e) {
+    e.obs_prev = e.re_on ? e.obs_re : e.obs_prev;
+    e.re_on = false;
 }
 
 // One step() of the rows with go_in.  need_obs: the caller wants the state vector.  cr: the gap_ave rows requested for
@@ -876,10 +959,6 @@ GDEV double g_step(GE<V> &e, const DevBatch &b, bool go_in, int a0, int a1, cons
     const uint32_t idle = ~e.busy & e.mmask;
     const int r_sel = g_task_select<V>(e, go, a0, idle);
     GSTAMP(3);
-    if (EARLY && wave_any(gap_need)) {         // (after task_select: the rows requested at the start of the step have had time to arrive)
-        g_gap_rows<V, MPC>(e, gap_need, cr);
-        lds_sync();
-    }
 #if defined(FJSP_GABLATE) && FJSP_GABLATE == 2
     e.rng_calls += (uint32_t)r_sel; return 0.0;                                  // diagnostic: stop after task_select
 #endif
@@ -887,10 +966,17 @@ GDEV double g_step(GE<V> &e, const DevBatch &b, bool go_in, int a0, int a1, cons
     const int rs = go ? r_sel : 0;
     GSTAMP(4);
     // the job's current operation type and its elig | fmask: from the job's lane
-    const int k_sel = gread((int)(e.jinfo & 0xFFu) + (int)(e.jwl & 0xFFu), rs, e.gb);
-    const uint32_t em_sel = greadu(e.emc, rs, e.gb);
+    int k_sel = gread((int)(e.jinfo & 0xFFu) + (int)(e.jwl & 0xFFu), rs, e.gb);
+    uint32_t em_sel = greadu(e.emc, rs, e.gb);
+    if constexpr (EARLY) asm volatile("" : "+v"(k_sel), "+v"(em_sel));      // (both permutes out before either is waited for)
     int pm = 0;
-    const int m_sel = g_machine_select<V, EARLY>(e, b, go, a1, k_sel, em_sel, idle, gap_need, &pm);
+    const int m_sel = g_machine_select<V, EARLY>(e, b, go, a1, k_sel, em_sel, idle, gap_need, &pm, [&]() {
+        // (behind the request for the chosen operation's column; the rows requested at the start of the step have arrived)
+        if (EARLY && wave_any(gap_need)) {
+            g_gap_rows<V, MPC>(e, gap_need, cr);
+            lds_sync();
+        }
+    });
     *k_out = go ? k_sel : -1; *m_out = m_sel;
 #if defined(FJSP_GABLATE) && FJSP_GABLATE == 3
     e.rng_calls += (uint32_t)(m_sel + pm); return 0.0;                           // diagnostic: stop after machine_select
@@ -910,6 +996,7 @@ GDEV double g_step(GE<V> &e, const DevBatch &b, bool go_in, int a0, int a1, cons
     const double cur = g_observe<V, EARLY>(e, b, go, !need_obs, &tard_unproc);   // :256
 #endif
     GSTAMP(7);
+    if constexpr (EARLY) g_restart_merge<V>(e);
     if (need_obs) g_emit<V>(e, go, cur, reinterpret_cast<const double *>(e.ir + b.L.i_ss), state_out);
     else e.misc |= go ? 1u << 24 : 0u;
     return g_reward<V>(e, go, mo, tard_unproc);

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(EARLY ? 256 : 64, EARLY ? 1 : 4) void FJSP_K(gstep)
     GSTAMP(0);
     if (wave_any(go && e.done != 0)) {
         const bool was_done = go && e.done != 0;
-        if (autoreset == 1) g_restart<V>(e, b, was_done);
+        if (autoreset == 1) g_restart<V, EARLY>(e, b, was_done);
         else {
             if (was_done && autoreset == 0) e.status |= FJSP_ST_STEP_AFTER_DONE;      // 2: idle silently
             go = go && !was_done;
