@@ -6,6 +6,12 @@ raises -- there is no Python/CPU fallback for the accelerated path.
 import ctypes as C
 import os
 
+# PyTorch-ROCm ships its own libamdhip64; the process must hold ONE HIP runtime, the one torch's device tensors and
+# streams belong to.  Importing torch before the library is loaded makes the loader resolve the library's HIP symbols
+# against that runtime (loaded the other way round, the system runtime under /opt/rocm comes up next to torch's and
+# sees no device).
+import torch
+
 from ._build import LIB_PATH
 
 _lib = None
@@ -13,6 +19,9 @@ _lib = None
 # name -> (restype, argtypes); keep in step with include/fjsp_amd.h
 _vp, _i32, _i64, _u64, _dbl, _cp = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double, C.c_char_p
 _pp = C.POINTER(C.c_void_p)
+
+# fjsp_status (include/fjsp_amd.h): what a call returns instead of 0
+FJSP_E_ARG, FJSP_E_IO, FJSP_E_FORMAT, FJSP_E_LP, FJSP_E_UNSUPPORTED, FJSP_E_HIP, FJSP_E_STATE = -1, -2, -3, -4, -5, -6, -7
 
 
 class GenParams(C.Structure):
@@ -129,11 +138,6 @@ def lib():
         raise ImportError(
             "%s is missing: the HIP extension is the product and there is no fallback. "
             "Run `python -c 'import __graft_entry__ as g; g.build()'` from the repo root." % LIB_PATH)
-    # PyTorch-ROCm ships its own libamdhip64; the process must hold ONE HIP runtime, the one torch's device
-    # tensors and streams belong to.  Importing torch first makes the loader resolve this library's HIP
-    # symbols against that runtime (loaded the other way round, the system runtime under /opt/rocm comes
-    # up next to torch's and sees no device).
-    import torch  # noqa: F401
     handle = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(handle, name)  # AttributeError if the symbol is not exported
@@ -149,3 +153,14 @@ def check(rc):
     if rc < 0:
         raise FjspError(rc, lib().fjsp_last_error().decode("utf-8", "replace"))
     return rc
+
+
+def ptr(t):
+    """The device pointer argument of a tensor, or None (NULL) for None."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream(device_index):
+    """The stream argument: the raw handle of torch's CURRENT stream on the device, looked up per call (callers switch
+    streams and capture graphs; torch.cuda.current_stream() builds a Stream object first, five times the cost)."""
+    return C.c_void_p(torch._C._cuda_getCurrentRawStream(device_index))

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from ... import _capi
-from ..._capi import check
+from ..._capi import check, ptr as _p, stream as _stream
 
 
 class Replay_Buffer(object):
@@ -82,17 +82,13 @@ class RolloutBuffer(object):
             self._lib.fjsp_rollout_destroy(h)
             self._h = None
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def add_experience(self, states, actions, rewards, next_states, dones, active=None):
         """One batched transition (f64 env outputs, u8 actions/dones) appended at the write cursor."""
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        check(self._lib.fjsp_rollout_append(self._h, p(states), p(actions), p(rewards), p(next_states), p(dones),
-                                            p(active), self._stream()))
+        check(self._lib.fjsp_rollout_append(self._h, _p(states), _p(actions), _p(rewards), _p(next_states), _p(dones),
+                                            _p(active), _stream(self.device.index)))
 
     def compute_returns(self, gamma):
-        check(self._lib.fjsp_rollout_returns(self._h, float(gamma), self._stream()))
+        check(self._lib.fjsp_rollout_returns(self._h, float(gamma), _stream(self.device.index)))
         return self.returns[:len(self)]
 
     def normalised_returns(self, gamma, normalized=True, standardized=True):
@@ -101,7 +97,7 @@ class RolloutBuffer(object):
         if getattr(self, "_norm", None) is None or self._norm.shape != self.returns.shape:
             self._norm = torch.zeros_like(self.returns)
         check(self._lib.fjsp_rollout_returns_normalised(self._h, float(gamma), 1 if normalized else 0, 1 if standardized else 0,
-                                                        C.c_void_p(self._norm.data_ptr()), self._stream()))
+                                                        _p(self._norm), _stream(self.device.index)))
         return self._norm[:n]
 
     def sample(self):

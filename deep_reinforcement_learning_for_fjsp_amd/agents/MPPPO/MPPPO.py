@@ -33,6 +33,7 @@ from torch.distributions import Categorical
 
 from ..Base_Agent import Base_Agent
 from ..linear import run_layers
+from ..native_actor import native_actor_forward, native_actor_params
 from ... import distributed as fdist
 
 HYPER = {   # utilities/data_structures/Config.py "MP_PPO"
@@ -353,7 +354,7 @@ class FusedSampler(object):
 
     def __init__(self, N, T, n_actions, pair_div, device):
         from ... import _capi
-        self._lib, self._check = _capi.lib(), _capi.check
+        self._lib, self._check, self._ptr, self._stream = _capi.lib(), _capi.check, _capi.ptr, _capi.stream
         self.N, self.A, self.div = int(N), int(n_actions), int(pair_div)
         self.eps = torch.zeros((), dtype=torch.float32, device=device)
         self.seed = torch.zeros((), dtype=torch.int64, device=device)
@@ -368,47 +369,11 @@ class FusedSampler(object):
         self.seed.fill_((torch.initial_seed() * 0x9E3779B1 + self.rounds * 0x85EBCA77) & 0x7FFFFFFFFFFFFFFF)
 
     def sample(self, probs, t, log_prob_row):
-        import ctypes as C
-        p = probs.contiguous()
-        stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
-        ptr = lambda x: C.c_void_p(x.data_ptr())
+        p, ptr = probs.contiguous(), self._ptr
         self._check(self._lib.fjsp_policy_sample(ptr(p), self.N, self.A, self.div, ptr(self.eps), ptr(self.seed), int(t),
-                                                 ptr(self.pair), ptr(self.flat_actions[t]), ptr(log_prob_row), stream))
+                                                 ptr(self.pair), ptr(self.flat_actions[t]), ptr(log_prob_row),
+                                                 self._stream(p.device.index)))
         return self.pair
-
-
-def native_actor_params(actor):
-    """fjsp_actor_params for an ActorNet of the in-kernel shape (state_size <= 32 -> 128 -> 128 -> n_actions <= 32, on
-    the GPU), or None when the network has another shape: device pointers into the nn.Linear parameters themselves
-    (the optimiser updates them in place, so the kernels always read the current policy)."""
-    from ..._capi import ActorParams
-    import ctypes as C
-    lin = [l for l in actor.layers if isinstance(l, nn.Linear)]
-    if len(lin) != 3 or not lin[0].weight.is_cuda:
-        return None
-    S, H, A = lin[0].in_features, lin[0].out_features, lin[2].out_features
-    if H != 128 or lin[1].in_features != 128 or lin[1].out_features != 128 or lin[2].in_features != 128 or S > 32 or A > 32:
-        return None
-    tensors = [lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias]
-    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        return None
-    return ActorParams(*[C.c_void_p(t.data_ptr()) for t in tensors], S, H, A)
-
-
-def native_actor_forward(actor, states64, out=None):
-    """ActorNet.forward through the library's actor kernel (fjsp_actor_forward): f64[n, S] states -> f32[n, A]
-    probabilities, the arithmetic the fused policy rollout performs inside the environment kernel."""
-    from ... import _capi
-    import ctypes as C
-    ap = native_actor_params(actor)
-    if ap is None:
-        raise ValueError("the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32) on the GPU")
-    states64 = states64.contiguous()
-    n = states64.shape[0]
-    probs = torch.empty(n, ap.n_actions, dtype=torch.float32, device=states64.device) if out is None else out
-    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(states64.device.index))
-    _capi.check(_capi.lib().fjsp_actor_forward(C.byref(ap), C.c_void_p(states64.data_ptr()), n, C.c_void_p(probs.data_ptr()), stream))
-    return probs
 
 
 def fused_policy_rollout(env, learner, memory, fused, old_log_prob, exploration, T):
@@ -422,14 +387,14 @@ def fused_policy_rollout(env, learner, memory, fused, old_log_prob, exploration,
         return False
     batch = env.batch
     mo = getattr(env, "mo", None)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    p = _capi.ptr
     memory.clear()
     state = env.reset()
     fused.new_round(exploration)
-    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(batch.device_index))
     rc = _capi.lib().fjsp_env_rollout_policy(batch._h, memory._h, C.byref(ap), p(fused.eps), p(fused.seed), fused.div, int(T), p(mo),
-                                            p(state), p(fused.flat_actions), p(old_log_prob), p(batch.state), stream)
-    if rc == -5:                      # FJSP_E_UNSUPPORTED
+                                            p(state), p(fused.flat_actions), p(old_log_prob), p(batch.state),
+                                            _capi.stream(batch.device_index))
+    if rc == _capi.FJSP_E_UNSUPPORTED:
         return False
     _capi.check(rc)
     batch.done.fill_(1)               # (read() reports the per-env flags; the vector mirror is refreshed lazily)

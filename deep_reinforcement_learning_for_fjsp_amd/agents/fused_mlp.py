@@ -15,18 +15,13 @@ for the forward-only advantage pass.
 The parameters stay the `nn.Parameter`s of the wrapped module -- re-homed as views of the flat buffer -- so
 everything else (acting, checkpoints, equalise_policies, the in-kernel actor of the fused rollout) sees them as before.
 """
-import ctypes as C
-
 import torch
 from torch import nn
 
 from .. import _capi
+from .._capi import ptr as _p, stream as _stream
 
 SPLIT_K = 128           # chunks of the batch in the split-K weight gradient (see agents/linear.py)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def supported(module_layers, device):
@@ -83,9 +78,6 @@ class FusedMLP(object):
             self._buf[n] = b
         return b
 
-    def _stream(self):
-        return C.c_void_p(torch._C._cuda_getCurrentRawStream(self.device.index))
-
     # -- forward ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, x):
@@ -104,14 +96,14 @@ class FusedMLP(object):
         b = self._buffers(actions_f32.shape[0])
         _capi.check(self._lib.fjsp_ppo_actor_loss(_p(b["out"]), _p(actions_f32), _p(old_log_prob), _p(advantages), b["out"].shape[0], self.out,
                                                   float(clip_epsilon), _p(count), _p(b["dout"]), _p(b["loss_partial"]), _p(b["loss"]),
-                                                  self._stream()))
+                                                  _stream(self.device.index)))
         return b["loss"]
 
     @torch.no_grad()
     def critic_loss(self, returns, count):
         b = self._buffers(returns.shape[0])
         _capi.check(self._lib.fjsp_ppo_critic_loss(_p(b["out"]), _p(returns), b["out"].shape[0], _p(count), _p(b["dout"]), _p(b["loss_partial"]),
-                                                   _p(b["loss"]), self._stream()))
+                                                   _p(b["loss"]), _stream(self.device.index)))
         return b["loss"]
 
     # -- backward: gradients of every parameter into the flat gradient buffer -------------------------------------
@@ -130,7 +122,7 @@ class FusedMLP(object):
 
     def _bias_grad(self, dz, h, out_view, b):
         _capi.check(self._lib.fjsp_relu_bwd_bias(_p(dz), _p(h), dz.shape[0], dz.shape[1], _p(b["partial"]), b["nparts"], _p(out_view),
-                                                 self._stream()))
+                                                 _stream(self.device.index)))
 
     @torch.no_grad()
     def backward(self):
@@ -175,7 +167,7 @@ class FusedMLP(object):
         b = self.train_pass_buffers(n)
         _capi.check(self._lib.fjsp_mlp_train_pass(int(mode), _p(self.flat), _p(x), n, self.lin[0].in_features, self.H, self.out, _p(aux0), _p(aux1),
                                                   _p(aux2), _p(count), float(clip_epsilon), _p(b["partial"]), b["groups"], _p(b["loss_partial"]),
-                                                  _p(self.grad), _p(b["loss"]), self._stream()))
+                                                  _p(self.grad), _p(b["loss"]), _stream(self.device.index)))
         return b["loss"]
 
     @torch.no_grad()
@@ -192,13 +184,13 @@ class FusedMLP(object):
             _capi.check(self._lib.fjsp_mlp_train_step_values(
                 1, _p(self.flat), _p(x), n, self.lin[0].in_features, self.H, self.out, _p(aux0), _p(aux1), _p(aux2), _p(count), float(clip_epsilon),
                 _p(b["partial"]), b["groups"], _p(b["loss_partial"]), _p(self.grad), _p(b["loss"]), _p(self.exp_avg), _p(self.exp_avg_sq),
-                self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, _p(self.step_count), _p(b["sumsq"]), _p(values_out), self._stream()))
+                self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, _p(self.step_count), _p(b["sumsq"]), _p(values_out), _stream(self.device.index)))
             return b["loss"]
         _capi.check(self._lib.fjsp_mlp_train_step(int(mode), _p(self.flat), _p(x), n, self.lin[0].in_features, self.H, self.out, _p(aux0),
                                                   _p(aux1), _p(aux2), _p(count), float(clip_epsilon), _p(b["partial"]), b["groups"],
                                                   _p(b["loss_partial"]), _p(self.grad), _p(b["loss"]), _p(self.exp_avg), _p(self.exp_avg_sq),
                                                   self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, _p(self.step_count),
-                                                  _p(b["sumsq"]), self._stream()))
+                                                  _p(b["sumsq"]), _stream(self.device.index)))
         return b["loss"]
 
     # -- optimiser step --------------------------------------------------------------------------------------------
@@ -208,4 +200,4 @@ class FusedMLP(object):
             all_reduce(self.grad)                                                  # ONE collective per optimiser step
         _capi.check(self._lib.fjsp_adam_clip_step(_p(self.flat), _p(self.grad), _p(self.exp_avg), _p(self.exp_avg_sq), self.numel,
                                                   self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, _p(self.step_count),
-                                                  _p(self.scratch), self._stream()))
+                                                  _p(self.scratch), _stream(self.device.index)))

@@ -7,13 +7,14 @@ libfjsp_amd.so (csrc/fjsp_kernels.hip); nothing in this module computes a step
 on the host.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
 import torch
 
 from . import _capi
-from ._capi import check
+from ._capi import check, ptr as _ptr
 
 VARIANT_SO_FJSSP = 0
 VARIANT_SO_SFJSP = 1
@@ -29,10 +30,6 @@ ST_SCHEDULE_OVERFLOW = 16
 
 
 ENV_SEED_STRIDE = 1000003          # env e draws random.choice from the stream seeded rng_seed + e * ENV_SEED_STRIDE
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _splitmix64(z):
@@ -171,6 +168,9 @@ class EnvBatch(object):
         n_inst = len(instances) - first if n_inst is None else n_inst
         self.device_index = int(device)
         self.device = torch.device("cuda", self.device_index)
+        # the stream argument of this batch's calls, self._stream(): _capi.stream on its device, bound as a partial
+        # (no Python frame of its own: the per-step call is launch-bound on the host)
+        self._stream = functools.partial(_capi.stream, self.device_index)
         self._h = C.c_void_p()
         self.first_env = int(first_env)
         # the kernels seed env e (local) with seed + e * ENV_SEED_STRIDE: shift the base by the shard's offset
@@ -208,11 +208,6 @@ class EnvBatch(object):
         if h is not None and h.value:
             self._lib.fjsp_env_destroy(h)
             self._h = None
-
-    def _stream(self):
-        # (the raw handle of torch's CURRENT stream on this device, looked up per call: callers switch streams and
-        # capture graphs; torch.cuda.current_stream() builds a Stream object first, five times the cost)
-        return C.c_void_p(torch._C._cuda_getCurrentRawStream(self.device_index))
 
     def row_build(self, fused=False):
         """The row-kernel build (kernel_family 1) that a step (fused=False) or a rollout (fused=True) of this batch runs,

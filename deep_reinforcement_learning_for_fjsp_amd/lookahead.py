@@ -5,12 +5,18 @@ saved (EnvBatch.snapshot) and loaded into a branch batch of P x N envs on the sa
 env p * N + i <- source env i), branch block p plays candidate p to the end of the episode in one fused launch, and the
 source env takes the candidate whose branch ended with the lowest objective (the first one on ties).
 
+That decision loop (decide_by_rollouts) is written once, with two ways of playing a branch to the end: rollout_dispatch
+keeps every block on its candidate (the fused rule rollout), policy_search.policy_lookahead applies the candidate once
+and goes on with a greedy actor.  What they and policy_search.best_of share around it is here too.
+
 With deterministic candidates the dynamics and the objective are functions of the action sequence, so following the
 chosen candidate from the next state reproduces its branch's objective: the objective the lookahead reaches is never
 above the best fixed candidate's.  Random-rule candidates (SO_FJSSP task rule 6 / machine rule 5 style
 random.choice rules) are allowed, but a branch continues on its own slot's random stream, so the bound does not hold
-for them.  Out of scope: truncated horizons and learned base policies.
+for them.  Out of scope: truncated horizons.
 """
+import time
+
 import numpy as np
 import torch
 
@@ -27,7 +33,7 @@ ACTION_RANGES = {VARIANT_SO_FJSSP: (6, 5), VARIANT_SO_DFJSP: (6, 5), VARIANT_MO_
 _ERR_BITS = ST_BAD_TASK_RULE | ST_BAD_MACHINE_RULE | ST_NO_EVENT | ST_SCHEDULE_OVERFLOW
 
 
-def _objective_values(batch, objective, r=None):
+def objective_values(batch, objective, r=None):
     r = batch.read() if r is None else r
     if callable(objective):
         v = objective(r)
@@ -71,14 +77,13 @@ def candidate_pairs(candidates, variant):
     return out.astype(np.uint8)
 
 
-def check_branch_shape(n_envs, n_inst, n_candidates):
+def check_branch_shape(n_envs, n_inst, n_candidates, who="rollout_dispatch"):
     """The branch batch holds n_candidates x n_envs envs; branch env p * N + i plays instance (p * N + i) % n_inst,
     which is source env i's instance only when N is a multiple of n_inst."""
     if n_candidates <= 0:
-        raise ValueError("rollout_dispatch: at least one candidate is needed")
+        raise ValueError("%s: at least one candidate is needed" % who)
     if n_envs % n_inst != 0:
-        raise ValueError("rollout_dispatch: the source batch's N (%d) must be a multiple of its instance count (%d)"
-                         % (n_envs, n_inst))
+        raise ValueError("%s: the source batch's N (%d) must be a multiple of its instance count (%d)" % (who, n_envs, n_inst))
     return n_candidates * n_envs
 
 
@@ -91,15 +96,36 @@ def make_branch(batch, n_candidates):
                     kernel_family=batch.kernel_family)
 
 
-def _check_status(r, who):
+def branch_for(batch, n_blocks, branch, who):
+    """`branch` if it is a batch of n_blocks x N envs on the source's instances and family, a new one for None."""
+    if branch is None:
+        return make_branch(batch, n_blocks)
+    if (not isinstance(branch, EnvBatch) or branch.N != n_blocks * batch.N or branch.n_inst != batch.n_inst
+            or branch.kernel_family != batch.kernel_family):
+        raise ValueError("%s: branch must be an EnvBatch of %d envs on the source's instances and kernel family" % (who, n_blocks * batch.N))
+    return branch
+
+
+def mo_rows(mo, N, dev, blocks=1):
+    """The step arguments `mo` as f64[N, 4] on the device; for a branch batch, f64[blocks x N, 4] with row p * N + i =
+    mo[i].  None stays None."""
+    if mo is None:
+        return None
+    mo = torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).contiguous()
+    return mo if blocks == 1 else mo.repeat(blocks, 1)
+
+
+def check_status(r, who, caller):
+    """RuntimeError if an env of read()'s `r` cannot finish.  who: "source" / "branch"; caller: the user's call."""
     bad = (r["status"].long() & _ERR_BITS) != 0
     if bool(bad.any()):
         i = int(torch.nonzero(bad)[0, 0].item())
-        raise RuntimeError("rollout_dispatch: %s env %d carries error status %d (FJSP_ST_* bits): it cannot finish its "
-                           "episode" % (who, i, int(r["status"][i].item())))
+        raise RuntimeError("%s: %s env %d carries error status %d (FJSP_ST_* bits): it cannot finish its episode"
+                           % (caller, who, i, int(r["status"][i].item())))
 
 
-def _ops_per_env(batch):
+def ops_per_env(batch):
+    """i64[N] device tensor: the operations of every env's instance = the steps of its episode."""
     ops = []
     for i in range(batch.n_inst):
         a = batch.instances.arrays(batch.first + i)
@@ -108,13 +134,85 @@ def _ops_per_env(batch):
     return torch.as_tensor(ops[np.arange(batch.N) % batch.n_inst], device=batch.device)
 
 
+class Clock(object):
+    """Seconds per named part into the dict `timings`, synchronised at every lap; nothing for timings=None."""
+
+    def __init__(self, timings, dev):
+        self.t, self.dev, self.t0 = timings, dev, None
+
+    def start(self):
+        if self.t is not None:
+            torch.cuda.synchronize(self.dev)
+            self.t0 = time.perf_counter()
+
+    def lap(self, what):
+        if self.t is not None:
+            torch.cuda.synchronize(self.dev)
+            now = time.perf_counter()
+            self.t[what] = self.t.get(what, 0.0) + now - self.t0
+            self.t0 = now
+
+
+def decide_by_rollouts(batch, pairs, objective, mo, branch, timings, who, state, play_branch):
+    """Play the source EnvBatch `batch` to the end by rollout decisions (the module docstring's loop); returns
+    rollout_dispatch's dict.  pairs: candidate_pairs' uint8[P, 2]; objective, mo, branch, timings: as rollout_dispatch
+    takes them; who: the function the user called, for error messages; state: whether the source step returns a state
+    (the next decision's actor input).  play_branch(branch, T, mo_branch, src_dev, clock) plays the restored branch
+    batch to the end and returns its read(): T bounds the steps any env has left, mo_branch is mo per branch env,
+    src_dev the device map branch env -> source env; it calls clock.lap("rollout") between its launch and its read."""
+    P, N, dev = len(pairs), batch.N, batch.device
+    check_branch_shape(N, batch.n_inst, P, who)
+    branch = branch_for(batch, P, branch, who)
+    mo = mo_rows(mo, N, dev)
+    mo_branch = mo_rows(mo, N, dev, P)
+    pairs_dev = torch.as_tensor(pairs, device=dev)                                  # [P, 2]
+    src = np.tile(np.arange(N, dtype=np.int64), P)
+    src_dev = torch.as_tensor(src.astype(np.int32), device=dev)
+    ops = ops_per_env(batch)
+    snap, restored = None, False
+    chosen_all, steps = [], torch.zeros(N, dtype=torch.int64, device=dev)
+    last = torch.zeros(N, 2, dtype=torch.uint8, device=dev)
+    clock = Clock(timings, dev)
+    prev_live, prev_count = None, None
+    while True:
+        r = batch.read()
+        check_status(r, "source", who)
+        live = r["done"] == 0
+        count = r["step_count"].long()
+        if prev_live is not None and bool((prev_live & live & (count <= prev_count)).any()):
+            raise RuntimeError("%s: a source env did not advance in its step" % who)
+        if not bool(live.any()):
+            break
+        prev_live, prev_count = live, count
+        T = int(torch.where(live, ops - count, torch.zeros_like(ops)).max().item())
+        clock.start()
+        snap = batch.snapshot(out=snap)
+        clock.lap("snapshot")
+        branch.restore(snap, src_dev if restored else src, rows=False)      # (the host map is validated once)
+        restored = True
+        clock.lap("restore")
+        rb = play_branch(branch, T, mo_branch, src_dev, clock)
+        cost = objective_values(branch, objective, rb).reshape(P, N)
+        best = torch.argmin(cost, dim=0)                                             # first minimum over candidates
+        clock.lap("read")
+        act = torch.where(live[:, None], pairs_dev[best], last)
+        batch.rollout(act[None].contiguous(), trace=False, rewards=False, mo=mo, state=state)
+        clock.lap("step")
+        steps += live.long()
+        last = act
+        chosen_all.append(act)
+    actions = torch.stack(chosen_all).cpu().numpy() if chosen_all else np.zeros((0, N, 2), np.uint8)
+    return dict(actions=actions, steps=steps.cpu().numpy(), objective=objective_values(batch, objective), branch=branch)
+
+
 def rollout_dispatch(batch, candidates, objective, mo=None, branch=None, timings=None):
     """Play every env of `batch` (an EnvBatch or a Batched* wrapper, reset and not yet stepped, or mid-episode) to the end,
     choosing at every decision the candidate whose rollout to the end gives the lowest objective.
 
     candidates: P action pairs (task rule, machine rule), or flat actions for SO_SFJSP / MO_FJSSP_discretes.
     objective: "makespan", "tardiness" (delay_time_sum), "energy" (MO_DFJSP) or a callable taking read()'s dict and
-    returning a tensor[N] to minimise.  mo: f64[N, 4] step arguments of the MO variants (as EnvBatch.step takes them).
+    returning a tensor[N] to minimise.  mo: f64[N, 4] step arguments of the MO variants (as EnvBatch.step takes them);
+    a wrapper's own `mo` is NOT picked up when none is given (policy_search's functions do pick it up): pass it.
     branch: an EnvBatch of P x N envs made by make_branch (reused across calls), or None to build one.
     timings: a dict that receives the seconds spent per part (snapshot, restore, rollout, read, step), synchronised.
 
@@ -124,93 +222,23 @@ def rollout_dispatch(batch, candidates, objective, mo=None, branch=None, timings
     batch = getattr(batch, "batch", batch)
     pairs = candidate_pairs(candidates, batch.variant)
     P, N = len(pairs), batch.N
-    check_branch_shape(N, batch.n_inst, P)
-    if branch is None:
-        branch = make_branch(batch, P)
-    elif (not isinstance(branch, EnvBatch) or branch.N != P * N or branch.n_inst != batch.n_inst
-          or branch.kernel_family != batch.kernel_family):
-        raise ValueError("rollout_dispatch: branch must be an EnvBatch of %d envs on the source's instances and kernel family"
-                         % (P * N))
-    dev = batch.device
-    if mo is not None:
-        mo = torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).contiguous()
-        mo_branch = mo.repeat(P, 1).contiguous()
-    else:
-        mo_branch = None
-    pairs_dev = torch.as_tensor(pairs, device=dev)                                  # [P, 2]
-    branch_act = pairs_dev[:, None, :].expand(P, N, 2).reshape(P * N, 2)            # one candidate per block
-    src = np.tile(np.arange(N, dtype=np.int64), P)
-    ops = _ops_per_env(batch)
-    branch_ops = ops.repeat(P)
-    snap, src_dev = None, None
-    chosen_all, steps = [], torch.zeros(N, dtype=torch.int64, device=dev)
-    last = torch.zeros(N, 2, dtype=torch.uint8, device=dev)
-    act_buf = None
-    clock = _Clock(timings, dev)
-    prev_live, prev_count = None, None
-    while True:
-        r = batch.read()
-        _check_status(r, "source")
-        live = r["done"] == 0
-        count = r["step_count"].long()
-        if prev_live is not None and bool((prev_live & live & (count <= prev_count)).any()):
-            raise RuntimeError("rollout_dispatch: a source env did not advance in its step")
-        if not bool(live.any()):
-            break
-        prev_live, prev_count = live, count
-        T = int(torch.where(live, ops - r["step_count"].long(), torch.zeros_like(ops)).max().item())
-        clock.start()
-        snap = batch.snapshot(out=snap)
-        clock.lap("snapshot")
-        if src_dev is None:
-            branch.restore(snap, src, rows=False)     # the branch map, validated once on the host
-            src_dev = torch.as_tensor(src.astype(np.int32), device=dev)
-        else:
-            branch.restore(snap, src_dev, rows=False)   # (the branch plays with state=False: its state rows are not needed)
-        clock.lap("restore")
-        if act_buf is None or act_buf.shape[0] < T:
-            act_buf = branch_act[None].expand(T, P * N, 2).contiguous()
-        branch.rollout(act_buf[:T], trace=False, rewards=False, mo=mo_branch, state=False)
+    branch_act = torch.as_tensor(pairs, device=batch.device)[:, None, :].expand(P, N, 2).reshape(P * N, 2)   # candidate p in block p
+    act_buf = []                  # [branch_act repeated over the steps]: built at the first decision, T only shrinks
+
+    def play_branch(branch, T, mo_branch, src_dev, clock):
+        if not act_buf or act_buf[0].shape[0] < T:
+            act_buf[:] = [branch_act[None].expand(T, P * N, 2).contiguous()]
+        branch.rollout(act_buf[0][:T], trace=False, rewards=False, mo=mo_branch, state=False)
         clock.lap("rollout")
         rb = branch.read()
-        _check_status(rb, "branch")
-        while not bool((rb["done"] != 0).all()):       # (every step dispatches one operation: not expected to run)
+        check_status(rb, "branch", "rollout_dispatch")
+        while not bool((rb["done"] != 0).all()):       # (a step dispatches one operation: not expected to run; T still bounds it)
             before = rb["step_count"].long()
-            left = int((branch_ops - before).clamp(min=1).max().item())
-            if act_buf.shape[0] < left:
-                act_buf = branch_act[None].expand(left, P * N, 2).contiguous()
-            branch.rollout(act_buf[:left], trace=False, rewards=False, mo=mo_branch, state=False)
+            branch.rollout(act_buf[0][:T], trace=False, rewards=False, mo=mo_branch, state=False)
             rb = branch.read()
-            _check_status(rb, "branch")
+            check_status(rb, "branch", "rollout_dispatch")
             if not bool(((rb["done"] != 0) | (rb["step_count"].long() > before)).all()):
                 raise RuntimeError("rollout_dispatch: a branch env neither finished nor advanced")
-        cost = _objective_values(branch, objective, rb).reshape(P, N)
-        best = torch.argmin(cost, dim=0)                                             # first minimum over candidates
-        clock.lap("read")
-        act = torch.where(live[:, None], pairs_dev[best], last)
-        batch.rollout(act[None].contiguous(), trace=False, rewards=False, mo=mo, state=False)
-        clock.lap("step")
-        steps += live.long()
-        last = act
-        chosen_all.append(act)
-    actions = torch.stack(chosen_all).cpu().numpy() if chosen_all else np.zeros((0, N, 2), np.uint8)
-    return dict(actions=actions, steps=steps.cpu().numpy(), objective=_objective_values(batch, objective), branch=branch)
+        return rb
 
-
-class _Clock(object):
-    def __init__(self, timings, dev):
-        self.t, self.dev, self.t0 = timings, dev, None
-
-    def start(self):
-        if self.t is not None:
-            import time
-            torch.cuda.synchronize(self.dev)
-            self.t0 = time.perf_counter()
-
-    def lap(self, what):
-        if self.t is not None:
-            import time
-            torch.cuda.synchronize(self.dev)
-            now = time.perf_counter()
-            self.t[what] = self.t.get(what, 0.0) + now - self.t0
-            self.t0 = now
+    return decide_by_rollouts(batch, pairs, objective, mo, branch, timings, "rollout_dispatch", False, play_branch)

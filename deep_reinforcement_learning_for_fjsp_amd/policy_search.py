@@ -9,8 +9,9 @@ same decoding as a per-step loop (actor, argmax or fjsp_policy_sample, one env s
 - play: every env to the end, greedy (argmax of the actor's probabilities) or sampled (epsilon 0).
 - best_of: k episodes per env in a k x N branch batch, block 0 greedy and the others sampled; each source env ends its
   episode with the best one.
-- policy_lookahead: the rollout algorithm of lookahead.rollout_dispatch with the greedy actor as base policy: at every
-  decision branch block p applies candidate p and plays greedily to the end, all in one launch.
+- policy_lookahead: the rollout algorithm of lookahead.rollout_dispatch with the greedy actor as base policy: the same
+  decision loop (lookahead.decide_by_rollouts), in which branch block p applies candidate p and plays greedily to the
+  end, all in one launch.
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -21,17 +22,14 @@ import numpy as np
 import torch
 
 from . import _capi
-from .batch import EnvBatch, ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT
-from .lookahead import (ACTION_RANGES, OBJECTIVES, _Clock, _check_status, _objective_values, _ops_per_env, candidate_pairs,
-                        check_branch_shape, make_branch)
+from ._capi import ptr as _ptr
+from .agents.native_actor import native_actor_forward, native_actor_params
+from .batch import ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT
+from .lookahead import (ACTION_RANGES, OBJECTIVES, branch_for, candidate_pairs, check_status, decide_by_rollouts, mo_rows,
+                        objective_values, ops_per_env)
 
-_E_UNSUPPORTED = -5
 # the status bits at which an env stops playing (the kernel's and fjsp_env_rollout's `live` test)
 _STOP_BITS = ST_BAD_TASK_RULE | ST_BAD_MACHINE_RULE | ST_NO_EVENT
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _unwrap(batch, mo):
@@ -63,16 +61,6 @@ def _recording(b):
     return b._lib.fjsp_env_schedule_capacity(b._h) > 0
 
 
-def _branch_for(batch, n_blocks, branch, who):
-    if branch is None:
-        return make_branch(batch, n_blocks)
-    if (not isinstance(branch, EnvBatch) or branch.N != n_blocks * batch.N or branch.n_inst != batch.n_inst
-            or branch.kernel_family != batch.kernel_family):
-        raise ValueError("%s: branch must be an EnvBatch of %d envs on the source's instances and kernel family"
-                         % (who, n_blocks * batch.N))
-    return branch
-
-
 def _seed_tensor(seed, dev):
     return torch.tensor([int(np.array(int(seed) & (2 ** 64 - 1), dtype=np.uint64).view(np.int64))], dtype=torch.int64, device=dev)
 
@@ -101,10 +89,8 @@ def play(batch, actor, greedy=True, seed=0, mo=None, max_steps=None, first=None,
 
 
 def _play(b, actor, pair_div, n_greedy, seed, mo, T, first, src, state_in, record_actions, fused):
-    from .agents.MPPPO.MPPPO import native_actor_params
     N, dev = b.N, b.device
-    if mo is not None:
-        mo = torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).contiguous()
+    mo = mo_rows(mo, N, dev)
     if first is not None:
         first = torch.as_tensor(first, device=dev).to(torch.uint8).reshape(N, 2).contiguous()
     state_in = b.state if state_in is None else state_in
@@ -121,7 +107,7 @@ def _play(b, actor, pair_div, n_greedy, seed, mo, T, first, src, state_in, recor
         raise ValueError("play: without state_src, state_in must have %d rows" % N)
     if T is None:
         r = b.read()
-        left = torch.where(r["done"] == 0, _ops_per_env(b) - r["step_count"].long(), torch.zeros(N, dtype=torch.int64, device=dev))
+        left = torch.where(r["done"] == 0, ops_per_env(b) - r["step_count"].long(), torch.zeros(N, dtype=torch.int64, device=dev))
         T = int(left.max().item())
     T = max(int(T), 1)           # (one launch even when every env is done: it still hands back the start rows)
     acts = torch.zeros(T, N, 2, dtype=torch.uint8, device=dev) if record_actions else None
@@ -132,7 +118,7 @@ def _play(b, actor, pair_div, n_greedy, seed, mo, T, first, src, state_in, recor
         rc = b._lib.fjsp_env_play_policy(b._h, C.byref(ap), int(pair_div), int(n_greedy), _ptr(seed_t), T, _ptr(mo), _ptr(state_in),
                                          int(state_in.shape[0]), _ptr(src), _ptr(first), _ptr(acts), _ptr(steps), b._p_state,
                                          b._p_reward, b._p_done, b._stream())
-        if rc != _E_UNSUPPORTED:
+        if rc != _capi.FJSP_E_UNSUPPORTED:
             _capi.check(rc)
             return dict(actions=acts, steps=steps)
     _play_loop(b, actor, pair_div, n_greedy, seed_t, T, mo, state_in, src, first, acts, steps)
@@ -142,7 +128,6 @@ def _play(b, actor, pair_div, n_greedy, seed, mo, T, first, src, state_in, recor
 def _play_loop(b, actor, pair_div, n_greedy, seed_t, T, mo, state_in, src, first, acts, steps):
     """The per-step form of play_policy_kernel.  Each step goes through fjsp_env_rollout with T = 1, which steps only the
     envs that are neither done nor stopped by an error bit (EnvBatch.step would flag a done env with STEP_AFTER_DONE)."""
-    from .agents.MPPPO.MPPPO import native_actor_forward, native_actor_params
     N, dev = b.N, b.device
     x = state_in[src.long()] if src is not None else state_in
     if x.data_ptr() != b.state.data_ptr():
@@ -197,21 +182,20 @@ def best_of(batch, actor, k, objective, seed=0, mo=None, branch=None):
     _check_objective(objective)
     _, pair_div = action_encoding(actor, batch)
     N, dev = batch.N, batch.device
-    branch = _branch_for(batch, k, branch, "best_of")
+    branch = branch_for(batch, k, branch, "best_of")
     if _recording(branch) != _recording(batch):
         branch.record_schedule(_recording(batch))
     src = np.tile(np.arange(N, dtype=np.int64), k)
     branch.restore(batch.snapshot(), src, rows=False)
-    mo_b = None if mo is None else torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).repeat(k, 1)
-    _play(branch, actor, pair_div, N, seed, mo_b, None, None, torch.as_tensor(src, device=dev), batch.state, False, True)
+    _play(branch, actor, pair_div, N, seed, mo_rows(mo, N, dev, k), None, None, torch.as_tensor(src, device=dev), batch.state, False, True)
     rb = branch.read()
-    _check_status(rb, "best_of branch")
+    check_status(rb, "branch", "best_of")
     if not bool((rb["done"] != 0).all()):
         raise RuntimeError("best_of: a branch env did not finish its episode")
-    best = torch.argmin(_objective_values(branch, objective, rb).reshape(k, N), dim=0)            # first minimum
+    best = torch.argmin(objective_values(branch, objective, rb).reshape(k, N), dim=0)            # first minimum
     win = branch.snapshot(best * N + torch.arange(N, device=dev))
     batch.restore(win, rows=True)
-    return dict(objective=_objective_values(batch, objective), best=best, branch=branch)
+    return dict(objective=objective_values(batch, objective), best=best, branch=branch)
 
 
 def policy_lookahead(batch, actor, objective, candidates=None, mo=None, branch=None, timings=None):
@@ -232,54 +216,16 @@ def policy_lookahead(batch, actor, objective, candidates=None, mo=None, branch=N
         candidates = [(a, m) for a in range(rng[0]) for m in range(rng[1])] if len(rng) == 2 else list(range(rng[0]))
     pairs = candidate_pairs(candidates, batch.variant)
     P, N = len(pairs), batch.N
-    check_branch_shape(N, batch.n_inst, P)
-    branch = _branch_for(batch, P, branch, "policy_lookahead")
-    dev = batch.device
-    if mo is not None:
-        mo = torch.as_tensor(mo, dtype=torch.float64, device=dev).reshape(N, 4).contiguous()
-        mo_branch = mo.repeat(P, 1).contiguous()
-    else:
-        mo_branch = None
-    pairs_dev = torch.as_tensor(pairs, device=dev)                                       # [P, 2]
-    first = pairs_dev[:, None, :].expand(P, N, 2).reshape(P * N, 2).contiguous()        # candidate p in block p
-    src = np.tile(np.arange(N, dtype=np.int64), P)
-    src_dev = torch.as_tensor(src.astype(np.int32), device=dev)
-    ops = _ops_per_env(batch)
-    snap, restored = None, False
-    chosen_all, steps = [], torch.zeros(N, dtype=torch.int64, device=dev)
-    last = torch.zeros(N, 2, dtype=torch.uint8, device=dev)
-    clock = _Clock(timings, dev)
-    prev_live, prev_count = None, None
-    while True:
-        r = batch.read()
-        _check_status(r, "source")
-        live = r["done"] == 0
-        count = r["step_count"].long()
-        if prev_live is not None and bool((prev_live & live & (count <= prev_count)).any()):
-            raise RuntimeError("policy_lookahead: a source env did not advance in its step")
-        if not bool(live.any()):
-            break
-        prev_live, prev_count = live, count
-        T = int(torch.where(live, ops - count, torch.zeros_like(ops)).max().item())
-        clock.start()
-        snap = batch.snapshot(out=snap)
-        clock.lap("snapshot")
-        branch.restore(snap, src_dev if restored else src, rows=False)      # (the host map is validated once)
-        restored = True
-        clock.lap("restore")
+    first = torch.as_tensor(pairs, device=batch.device)[:, None, :].expand(P, N, 2).reshape(P * N, 2).contiguous()   # candidate p in block p
+
+    def play_branch(branch, T, mo_branch, src_dev, clock):
         _play(branch, actor, pair_div, P * N, 0, mo_branch, T, first, src_dev, batch.state, False, True)
         clock.lap("rollout")
         rb = branch.read()
-        _check_status(rb, "branch")
+        check_status(rb, "branch", "policy_lookahead")
         if not bool((rb["done"] != 0).all()):
             raise RuntimeError("policy_lookahead: a branch env did not finish its episode")
-        best = torch.argmin(_objective_values(branch, objective, rb).reshape(P, N), dim=0)     # first minimum over candidates
-        clock.lap("read")
-        act = torch.where(live[:, None], pairs_dev[best], last)
-        batch.rollout(act[None].contiguous(), trace=False, rewards=False, mo=mo, state=True)    # (state: the next actor input)
-        clock.lap("step")
-        steps += live.long()
-        last = act
-        chosen_all.append(act)
-    actions = torch.stack(chosen_all).cpu().numpy() if chosen_all else np.zeros((0, N, 2), np.uint8)
-    return dict(actions=actions, steps=steps.cpu().numpy(), objective=_objective_values(batch, objective), branch=branch)
+        return rb
+
+    # (the source step returns a state: the next decision's actor input)
+    return decide_by_rollouts(batch, pairs, objective, mo, branch, timings, "policy_lookahead", True, play_branch)

@@ -25,7 +25,7 @@ def main():
     from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import PPO, ActorNet
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
     from deep_reinforcement_learning_for_fjsp_amd.environments import BatchedSOFJSSP
-    from deep_reinforcement_learning_for_fjsp_amd.lookahead import _ops_per_env
+    from deep_reinforcement_learning_for_fjsp_amd.lookahead import ops_per_env
 
     N = args.envs
     if args.actor:
@@ -55,7 +55,7 @@ def main():
     pairs = [(a, m) for a in range(6) for m in range(5)]
     ev = EnvBatch(s, len(pairs) * N, rng_seed=3)
     ev.reset()
-    T = int(_ops_per_env(ev).max())
+    T = int(ops_per_env(ev).max())
     acts = torch.tensor(pairs, dtype=torch.uint8, device="cuda")[:, None, :].expand(len(pairs), N, 2).reshape(1, -1, 2)
     _, sec = timed(lambda: ev.rollout(acts.expand(T, -1, 2).contiguous(), trace=False, rewards=False, state=False))
     report("best fixed rule pair", ev.read()["makespan"].reshape(len(pairs), N).min(0).values, sec)

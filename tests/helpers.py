@@ -1,4 +1,5 @@
 """Shared test helpers: golden-fixture access and oracle drivers (test infrastructure)."""
+import contextlib
 import hashlib
 import os
 
@@ -145,9 +146,6 @@ def assert_state_close(got, want, what="", mo=False, sf=False, dyn=False):
         np.testing.assert_allclose(got[..., c], want[..., c], rtol=POW_RTOL, atol=atol, err_msg="%s (state entry %d)" % (what, c))
 
 
-import contextlib
-
-
 @contextlib.contextmanager
 def env_var(name, value):
     """Set (or with None: leave) an environment variable for the duration of a block."""
@@ -162,3 +160,78 @@ def env_var(name, value):
                 del os.environ[name]
             else:
                 os.environ[name] = old
+
+
+# -- GPU tests of saved states, lookaheads and policy decoding -----------------------------------------------------------
+DET_SO = [(a, b) for a in range(5) for b in range(4)]         # SO_FJSSP pairs without the random.choice rules (6th / 5th)
+
+
+def gen_10x5(n, seed):
+    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
+    return fi.InstanceSet(n).generate_range(seed, fi.bench_10x5_params()).solve_fluid()
+
+
+def ops(s, n_inst, N, first=0):
+    """Operations (= steps of an episode) of every env of a batch of N envs on instances first .. first + n_inst - 1."""
+    out = []
+    for i in range(n_inst):
+        a = s.arrays(first + i)
+        out.append(int((np.asarray(a.count).reshape(a.S, a.R) * np.asarray(a.Jr)[None, :]).sum()))
+    return np.asarray(out)[np.arange(N) % n_inst]
+
+
+def host(x):
+    return None if x is None else x.cpu().numpy().copy()
+
+
+def read(b):
+    return {k: v.cpu().numpy() for k, v in b.read().items()}
+
+
+def same(a, b, what):
+    """Nested dicts / sequences of arrays (or None): same keys, lengths, dtypes, shapes and values, floats by bits."""
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            same(a[k], b[k], "%s/%s" % (what, k))
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), what
+        for i, (x, y) in enumerate(zip(a, b)):
+            same(x, y, "%s[%d]" % (what, i))
+    elif a is None:
+        assert b is None, what
+    else:
+        x, y = np.asarray(a), np.asarray(b)
+        assert x.dtype == y.dtype and x.shape == y.shape, what
+        if x.dtype.kind == "f":
+            x, y = bits(x), bits(y)
+        assert np.array_equal(x, y), what
+
+
+def play_outcome(b, res):
+    """Everything policy_search.play leaves behind: its result, read(), the batch's rows (floats as bits), the schedule."""
+    out = dict(actions=host(res["actions"]), steps=host(res["steps"]), read=read(b), state=bits(host(b.state)),
+               done=host(b.done), reward=bits(host(b.reward)))
+    if b._lib.fjsp_env_schedule_capacity(b._h) > 0:
+        out["schedule"] = [host(x) for x in b.schedule()]
+    return out
+
+
+def kernel_vs_loop(make, actor, kernel_only, mo=None, **kw):
+    """Two identical recording batches from reset: play through the kernel and through the per-step loop.  kernel_only:
+    the test module's fixture that makes the per-step loop raise while the kernel path must run."""
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    outs = []
+    for fused in (True, False):
+        b = make()
+        b.record_schedule()
+        b.reset()
+        kernel_only(fused)
+        res = PS.play(b, actor, mo=mo, fused=fused, record_actions=True, **kw)
+        kernel_only(False)
+        outs.append(play_outcome(b, res))
+    same(outs[0], outs[1], "kernel vs loop")
+    got = outs[0]
+    assert np.all(got["read"]["done"] == 1) and np.all(got["read"]["status"] == 0)
+    assert np.array_equal(got["steps"], got["read"]["step_count"])
+    return got

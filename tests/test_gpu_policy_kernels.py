@@ -404,12 +404,11 @@ def test_greedy_decode_takes_the_first_of_tied_probabilities(torch_gpu, kernel_o
     """fjsp_env_play_policy's greedy branch on exact ties: every step applies the lowest tied index (torch.argmax),
     kernel == per-step loop, on a pair-action env (SO_FJSSP, 30 actions) and a flat-action env (SO_SFJSP, 20)."""
     torch = torch_gpu
-    from tests.test_gpu_policy_search import _gen_10x5, _kernel_vs_loop
     from tests import helpers as H
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, VARIANT_SO_SFJSP
     from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import native_actor_forward
     if suite == "so_fjssp":
-        s, N, S, A, div, tied = _gen_10x5(16, 320), 256, 20, 30, 5, [7, 13, 22]
+        s, N, S, A, div, tied = H.gen_10x5(16, 320), 256, 20, 30, 5, [7, 13, 22]
         make = lambda: EnvBatch(s, N, rng_seed=9)
     else:
         insts, _, _ = H.load_suite("so_sfjsp")
@@ -423,7 +422,7 @@ def test_greedy_decode_takes_the_first_of_tied_probabilities(torch_gpu, kernel_o
     pr = _host(probs)
     assert np.array_equal(pr[:, tied[0]], pr[:, tied[1]]) and np.array_equal(pr[:, tied[0]], pr[:, tied[2]])
     assert np.all(_host(torch.argmax(probs, 1)) == tied[0])
-    got = _kernel_vs_loop(torch, make, actor, kernel_only)
+    got = H.kernel_vs_loop(make, actor, kernel_only)
     acts, steps = got["actions"], got["steps"]
     want = (tied[0] // div, tied[0] % div) if div else (tied[0], 0)
     T = acts.shape[0]

@@ -9,8 +9,6 @@ from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-DET_SO = [(a, b) for a in range(5) for b in range(4)]         # SO_FJSSP pairs without the random.choice rules (6th / 5th)
-
 
 @pytest.fixture(scope="module")
 def torch_gpu(built):
@@ -39,82 +37,17 @@ def _actor(torch, S, A, seed, hidden=128, layers=2):
     return ActorNet(S, hidden, layers, A).cuda()
 
 
-def _gen_10x5(n, seed):
-    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
-    return fi.InstanceSet(n).generate_range(seed, fi.bench_10x5_params()).solve_fluid()
-
-
-def _host(x):
-    return None if x is None else x.cpu().numpy().copy()
-
-
-def _read(b):
-    return {k: v.cpu().numpy() for k, v in b.read().items()}
-
-
-def _outcome(b, res):
-    out = dict(actions=_host(res["actions"]), steps=_host(res["steps"]), read=_read(b), state=H.bits(_host(b.state)),
-               done=_host(b.done), reward=H.bits(_host(b.reward)))
-    if b._lib.fjsp_env_schedule_capacity(b._h) > 0:
-        out["schedule"] = [_host(x) for x in b.schedule()]
-    return out
-
-
-def _same(a, b, what):
-    if isinstance(a, dict):
-        assert a.keys() == b.keys(), what
-        for k in a:
-            _same(a[k], b[k], "%s/%s" % (what, k))
-    elif isinstance(a, (list, tuple)):
-        assert len(a) == len(b), what
-        for i, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, "%s[%d]" % (what, i))
-    elif a is None:
-        assert b is None, what
-    else:
-        x, y = np.asarray(a), np.asarray(b)
-        assert x.dtype == y.dtype and x.shape == y.shape, what
-        assert np.array_equal(x, y), what
-
-
-def _kernel_vs_loop(torch, make, actor, kernel_only, mo=None, **kw):
-    """Two identical recording batches from reset: play through the kernel and through the per-step loop."""
-    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
-    outs = []
-    for fused in (True, False):
-        b = make()
-        b.record_schedule()
-        b.reset()
-        kernel_only(fused)
-        res = PS.play(b, actor, mo=mo, fused=fused, record_actions=True, **kw)
-        kernel_only(False)
-        outs.append(_outcome(b, res))
-    _same(outs[0], outs[1], "kernel vs loop")
-    got = outs[0]
-    assert np.all(got["read"]["done"] == 1) and np.all(got["read"]["status"] == 0)
-    assert np.array_equal(got["steps"], got["read"]["step_count"])
-    return got
-
-
-def _ops(s, n_inst, N):
-    ops = []
-    for i in range(n_inst):
-        a = s.arrays(i)
-        ops.append(int((np.asarray(a.count).reshape(a.S, a.R) * np.asarray(a.Jr)[None, :]).sum()))
-    return np.asarray(ops)[np.arange(N) % n_inst]
-
-
 @pytest.mark.parametrize("family", [0, 1])
 def test_greedy_kernel_equals_loop_so_fjssp(torch_gpu, kernel_only, family):
     """4096 generated 10x5 envs in both kernel families: actions, steps, read(), final rows and schedule bit for bit."""
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
-    s, N = _gen_10x5(64, 300), 4096
+    s, N = H.gen_10x5(64, 300), 4096
     make = lambda: EnvBatch(s, N, rng_seed=4, kernel_family=family)
     assert make().kernel_family == family
     actor = _actor(torch, 20, 30, 1)
-    got = _kernel_vs_loop(torch, make, actor, kernel_only)
-    assert np.array_equal(got["steps"], _ops(s, 64, N))
+    got = H.kernel_vs_loop(make, actor, kernel_only)
+    assert np.array_equal(got["steps"], H.ops(s, 64, N))
 
 
 @pytest.mark.parametrize("suite", ["so_sfjsp", "mo_discretes", "so_dfjsp"])
@@ -134,20 +67,20 @@ def test_greedy_kernel_equals_loop_suites(torch_gpu, kernel_only, suite):
         mo = torch.tensor([[0.5, 0.5, 800.0, 300.0]], dtype=torch.float64, device="cuda").repeat(N, 1)
     make = lambda: EnvBatch(s, N, variant=variant, rng_seed=6)
     actor = _actor(torch, S, A, 2)
-    _kernel_vs_loop(torch, make, actor, kernel_only, mo=mo)
-    _kernel_vs_loop(torch, make, actor, kernel_only, mo=mo, greedy=False, seed=17)
+    H.kernel_vs_loop(make, actor, kernel_only, mo=mo)
+    H.kernel_vs_loop(make, actor, kernel_only, mo=mo, greedy=False, seed=17)
 
 
 def test_sampled_kernel_equals_loop(torch_gpu, kernel_only):
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
-    s, N = _gen_10x5(32, 310), 1024
+    s, N = H.gen_10x5(32, 310), 1024
     make = lambda: EnvBatch(s, N, rng_seed=5)
     actor = _actor(torch, 20, 30, 3)
-    a = _kernel_vs_loop(torch, make, actor, kernel_only, greedy=False, seed=11)
-    b = _kernel_vs_loop(torch, make, actor, kernel_only, greedy=False, seed=12)
+    a = H.kernel_vs_loop(make, actor, kernel_only, greedy=False, seed=11)
+    b = H.kernel_vs_loop(make, actor, kernel_only, greedy=False, seed=12)
     assert not np.array_equal(a["actions"], b["actions"])
-    g = _kernel_vs_loop(torch, make, actor, kernel_only, greedy=True, seed=11)
+    g = H.kernel_vs_loop(make, actor, kernel_only, greedy=True, seed=11)
     assert not np.array_equal(a["actions"], g["actions"])
 
 
@@ -160,11 +93,11 @@ def test_mid_episode_through_a_branch_map(torch_gpu, kernel_only):
     from deep_reinforcement_learning_for_fjsp_amd.lookahead import make_branch
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
     NI, N = 32, 256
-    s = _gen_10x5(NI, 320)
+    s = H.gen_10x5(NI, 320)
     src = EnvBatch(s, N, rng_seed=7)
     src.record_schedule()
     src.reset()
-    acts = torch.tensor(DET_SO, dtype=torch.uint8, device="cuda")[torch.arange(N, device="cuda") % 20]
+    acts = torch.tensor(H.DET_SO, dtype=torch.uint8, device="cuda")[torch.arange(N, device="cuda") % 20]
     for t in range(4):
         src.step(acts)
     snap = src.snapshot()
@@ -183,13 +116,13 @@ def test_mid_episode_through_a_branch_map(torch_gpu, kernel_only):
             br.restore(snap, tile, rows=True)
             res = PS.play(br, actor, greedy=False, seed=21, fused=False, record_actions=True)
         kernel_only(False)
-        outs.append(_outcome(br, res))
-    _same(outs[0], outs[1], "branch: kernel vs loop")
+        outs.append(H.play_outcome(br, res))
+    H.same(outs[0], outs[1], "branch: kernel vs loop")
     assert np.all(outs[0]["read"]["done"] == 1)
     kernel_only(True)
     res = PS.play(src, actor, greedy=False, seed=21, record_actions=True)
     kernel_only(False)
-    own = _outcome(src, res)
+    own = H.play_outcome(src, res)
     br0 = outs[0]
     assert np.array_equal(own["actions"], br0["actions"][:, :N]) and np.array_equal(own["steps"], br0["steps"][:N])
     for k in own["read"]:
@@ -201,13 +134,13 @@ def test_mid_episode_through_a_branch_map(torch_gpu, kernel_only):
 def test_forced_first_action(torch_gpu, kernel_only):
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
-    s, N = _gen_10x5(16, 330), 512
+    s, N = H.gen_10x5(16, 330), 512
     make = lambda: EnvBatch(s, N, rng_seed=8)
     actor = _actor(torch, 20, 30, 5)
-    first = torch.tensor(DET_SO, dtype=torch.uint8, device="cuda")[torch.arange(N, device="cuda") % 20]
-    got = _kernel_vs_loop(torch, make, actor, kernel_only, first=first)
-    assert np.array_equal(got["actions"][0], _host(first))
-    free = _kernel_vs_loop(torch, make, actor, kernel_only)
+    first = torch.tensor(H.DET_SO, dtype=torch.uint8, device="cuda")[torch.arange(N, device="cuda") % 20]
+    got = H.kernel_vs_loop(make, actor, kernel_only, first=first)
+    assert np.array_equal(got["actions"][0], H.host(first))
+    free = H.kernel_vs_loop(make, actor, kernel_only)
     assert not np.array_equal(got["actions"][0], free["actions"][0])
 
 
@@ -217,7 +150,7 @@ def test_best_of_recording(torch_gpu):
     from deep_reinforcement_learning_for_fjsp_amd import schedule as sch
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
     NI, N, k = 64, 512, 8
-    s = _gen_10x5(NI, 340)
+    s = H.gen_10x5(NI, 340)
     actor = _actor(torch, 20, 30, 6)
     twin = EnvBatch(s, N, rng_seed=9)
     twin.reset()
@@ -232,12 +165,12 @@ def test_best_of_recording(torch_gpu):
     assert np.all(obj <= greedy)
     assert np.array_equal(obj[best == 0], greedy[best == 0])
     assert np.any(obj < greedy) and np.any(best > 0)
-    rb, r = _read(res["branch"]), _read(b)
+    rb, r = H.read(res["branch"]), H.read(b)
     win = best * N + np.arange(N)
     for key in r:
         assert np.array_equal(r[key], rb[key][win]), key
     assert np.array_equal(r["makespan"].astype(np.float64), obj)
-    table, length = [_host(x) for x in b.schedule()]
+    table, length = [H.host(x) for x in b.schedule()]
     for e in range(0, N, 7):
         a = s.arrays(e % NI)
         rows = sch.rows(table, length, e)
@@ -250,7 +183,7 @@ def test_policy_lookahead_never_loses_to_its_base_policy(torch_gpu):
     from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
     NI = N = 128
-    s = _gen_10x5(NI, 350)
+    s = H.gen_10x5(NI, 350)
     actor = _actor(torch, 20, 30, 7)
     with torch.no_grad():                    # no random.choice rule among the greedy choices: task rule 5, machine rule 4
         rand = [a for a in range(30) if a // 5 == 5 or a % 5 == 4]
@@ -258,18 +191,18 @@ def test_policy_lookahead_never_loses_to_its_base_policy(torch_gpu):
     twin = EnvBatch(s, N, rng_seed=10)
     twin.reset()
     g = PS.play(twin, actor, record_actions=True)
-    acts_g = _host(g["actions"]).astype(np.int64)
-    live = np.arange(acts_g.shape[0])[:, None] < _host(g["steps"])[None, :]
+    acts_g = H.host(g["actions"]).astype(np.int64)
+    live = np.arange(acts_g.shape[0])[:, None] < H.host(g["steps"])[None, :]
     assert np.all((acts_g[..., 0] < 5) & (acts_g[..., 1] < 4) | ~live)
     greedy = twin.read()["makespan"].cpu().numpy().astype(np.float64)
     b = EnvBatch(s, N, rng_seed=10)
     b.reset()
     timings = {}
-    res = PS.policy_lookahead(b, actor, "makespan", candidates=DET_SO, timings=timings)
+    res = PS.policy_lookahead(b, actor, "makespan", candidates=H.DET_SO, timings=timings)
     got = res["objective"].cpu().numpy()
     assert np.all(got <= greedy)
     assert set(timings) == {"snapshot", "restore", "rollout", "read", "step"}
-    assert np.array_equal(res["steps"], _ops(s, NI, N))
+    assert np.array_equal(res["steps"], H.ops(s, NI, N))
     fresh = EnvBatch(s, N, rng_seed=10)
     fresh.reset()
     fresh.rollout(torch.from_numpy(res["actions"]).cuda(), trace=False, rewards=False)
@@ -283,26 +216,26 @@ def test_fallback_decodes_what_the_kernel_refuses(torch_gpu):
     from deep_reinforcement_learning_for_fjsp_amd import _capi
     from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
     from deep_reinforcement_learning_for_fjsp_amd._capi import ActorParams
-    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import native_actor_params
+    from deep_reinforcement_learning_for_fjsp_amd.agents.native_actor import native_actor_params
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, VARIANT_MO_DFJSP
     lib = _capi.lib()
-    s, N = _gen_10x5(16, 360), 64
+    s, N = H.gen_10x5(16, 360), 64
     wide = _actor(torch, 20, 30, 8, hidden=200, layers=5)
     b = EnvBatch(s, N, rng_seed=11)
     b.reset()
     steps = torch.zeros(N, dtype=torch.int32, device="cuda")
-    p = lambda t: C.c_void_p(t.data_ptr())
+    p = _capi.ptr
     lin = [m for m in wide.modules() if isinstance(m, torch.nn.Linear)]
     ap = ActorParams(p(lin[0].weight), p(lin[0].bias), p(lin[1].weight), p(lin[1].bias), p(lin[-1].weight), p(lin[-1].bias), 20, 200, 30)
     assert lib.fjsp_env_play_policy(b._h, C.byref(ap), 5, N, None, 10, None, b._p_state, N, None, None, None, p(steps),
                                     b._p_state, b._p_reward, b._p_done, b._stream()) == -5
     res = PS.play(b, wide, greedy=False, seed=4, record_actions=True)
-    r = _read(b)
-    assert np.all(r["done"] == 1) and np.array_equal(_host(res["steps"]), _ops(s, 16, N))
+    r = H.read(b)
+    assert np.all(r["done"] == 1) and np.array_equal(H.host(res["steps"]), H.ops(s, 16, N))
     fresh = EnvBatch(s, N, rng_seed=11)
     fresh.reset()
     fresh.rollout(res["actions"], trace=False, rewards=False)
-    _same(_read(fresh), r, "replay 200 x 5")
+    H.same(H.read(fresh), r, "replay 200 x 5")
 
     insts, _, _ = H.load_suite("mo_dfjsp")
     insts = [a for a in insts if a.name.startswith("gen")]         # small instances with arrivals and breakdowns
@@ -319,11 +252,11 @@ def test_fallback_decodes_what_the_kernel_refuses(torch_gpu):
                                     d._p_done, d._stream()) == -5
     actor = _actor(torch, 30, 120, 10, hidden=200, layers=5)          # MPPPO's MO_DFJSP net: 12 x 10 actions
     res = PS.play(d, actor, mo=mo, record_actions=True)
-    r = _read(d)
+    r = H.read(d)
     assert np.all(r["done"] == 1)
     fresh = EnvBatch(ds, N, variant=VARIANT_MO_DFJSP, rng_seed=12)
     fresh.reset()
     fresh.rollout(res["actions"], trace=False, rewards=False, mo=mo)
-    got = _read(fresh)
+    got = H.read(fresh)
     for key in ("makespan", "delay_time_sum", "step_count", "done", "status"):
         assert np.array_equal(got[key], r[key]), key

@@ -11,19 +11,11 @@ from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-DET_SO = [(a, b) for a in range(5) for b in range(4)]         # SO_FJSSP pairs without the random.choice rules (6th / 5th)
-
-
 @pytest.fixture(scope="module")
 def torch_gpu(built):
     import torch
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     return torch
-
-
-def _gen_10x5(n, seed):
-    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
-    return fi.InstanceSet(n).generate_range(seed, fi.bench_10x5_params()).solve_fluid()
 
 
 def _training_dist(n, seed):
@@ -34,54 +26,19 @@ def _training_dist(n, seed):
     return s.solve_fluid()
 
 
-def _ops(s, first, n_inst, N):
-    ops = []
-    for i in range(n_inst):
-        a = s.arrays(first + i)
-        ops.append(int((np.asarray(a.count).reshape(a.S, a.R) * np.asarray(a.Jr)[None, :]).sum()))
-    return np.asarray(ops)[np.arange(N) % n_inst]
-
-
-def _host(x):
-    return None if x is None else x.cpu().numpy().copy()
-
-
-def _read(b):
-    return {k: v.cpu().numpy() for k, v in b.read().items()}
-
-
 def _play_steps(torch, b, acts, mo):
     """Per-step path: every step's (state, reward, done, trace), then read() and schedule()."""
     out = []
     tr = torch.zeros(b.N, 2, dtype=torch.int16, device=b.device)
     for t in range(acts.shape[0]):
         st, rw, dn = b.step(acts[t], mo=mo, trace_out=tr)
-        out.append((_host(st), _host(rw), _host(dn), _host(tr)))
-    return out, _read(b), [_host(x) for x in b.schedule()]
+        out.append((H.host(st), H.host(rw), H.host(dn), H.host(tr)))
+    return out, H.read(b), [H.host(x) for x in b.schedule()]
 
 
 def _play_rollout(torch, b, acts, mo):
     tr, rw, st = b.rollout(acts, mo=mo)
-    return (_host(tr), _host(rw), _host(st)), _read(b), [_host(x) for x in b.schedule()]
-
-
-def _same(a, b, what):
-    if isinstance(a, dict):
-        assert a.keys() == b.keys(), what
-        for k in a:
-            _same(a[k], b[k], "%s/%s" % (what, k))
-    elif isinstance(a, (list, tuple)):
-        assert len(a) == len(b), what
-        for i, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, "%s[%d]" % (what, i))
-    elif a is None:
-        assert b is None, what
-    else:
-        x, y = np.asarray(a), np.asarray(b)
-        assert x.dtype == y.dtype and x.shape == y.shape, what
-        if x.dtype.kind == "f":
-            x, y = H.bits(x), H.bits(y)
-        assert np.array_equal(x, y), what
+    return (H.host(tr), H.host(rw), H.host(st)), H.read(b), [H.host(x) for x in b.schedule()]
 
 
 def _rewind_case(torch, b, acts, t1, mo=None):
@@ -97,12 +54,12 @@ def _rewind_case(torch, b, acts, t1, mo=None):
     first = _play_steps(torch, b, rest, mo)
     b.restore(snap, check=True)
     again = _play_steps(torch, b, rest, mo)
-    _same(first, again, "per-step replay")
+    H.same(first, again, "per-step replay")
     b.restore(snap)
     fused = _play_rollout(torch, b, rest, mo)
     b.restore(snap)
     fused2 = _play_rollout(torch, b, rest, mo)
-    _same(fused, fused2, "fused replay")
+    H.same(fused, fused2, "fused replay")
     # fused vs per-step: same choices, rewards where an env stepped, same end state, read() and schedule table
     (tr, rw, st), rd, sched = fused
     steps, rd_s, sched_s = first
@@ -116,7 +73,7 @@ def _rewind_case(torch, b, acts, t1, mo=None):
             assert np.array_equal(rd[k] & ~4, rd_s[k] & ~4)
         else:
             assert np.array_equal(rd[k], rd_s[k]), k
-    _same(sched, sched_s, "schedule fused vs per-step")
+    H.same(sched, sched_s, "schedule fused vs per-step")
     assert np.all(rd["done"] == 1)
     return snap
 
@@ -134,13 +91,13 @@ def test_rewind_is_exact(torch_gpu, case):
     if case == "multijob":
         s, variant, n_task, n_machine, NI = _training_dist(16, 700), 0, 6, 5, 16
     else:
-        s, NI = _gen_10x5(32, 600), 32
+        s, NI = H.gen_10x5(32, 600), 32
         variant, n_task, n_machine = {"rows": (0, 6, 5), "wave": (0, 6, 5), "so_sfjsp": (VARIANT_SO_SFJSP, 20, 1),
                                       "mo_discretes": (VARIANT_MO_FJSSP_DISCRETES, 18, 1)}[case]
     with H.env_var("FJSP_STEP_IMPL", "wave" if case == "wave" else None):
         b = EnvBatch(s, N, variant=variant, rng_seed=77)
     assert b.kernel_family == (0 if case in ("wave", "multijob", "so_sfjsp") else 1)
-    T = int(_ops(s, 0, NI, N).max())
+    T = int(H.ops(s, NI, N).max())
     acts = _random_acts(torch, N, T, n_task, n_machine, 31)
     mo = None
     if variant == VARIANT_MO_FJSSP_DISCRETES:
@@ -161,7 +118,7 @@ def test_rewind_is_exact_with_arrivals_and_breakdowns(torch_gpu, lp):
     with H.env_var("FJSP_LP_IMPL", lp):
         b = EnvBatch(s, N, variant=VARIANT_MO_DFJSP, rng_seed=5)
     assert b.lp_on_device == (1 if lp == "device" else 0)
-    T = int(_ops(s, 0, len(insts), N).max())
+    T = int(H.ops(s, len(insts), N).max())
     acts = _random_acts(torch, N, T, 12, 10, 17)
     mo = torch.zeros(N, 4, dtype=torch.float64, device="cuda"); mo[:, 0] = 1.0
     assert any(a.S > 1 for a in insts) and any(int(np.sum(a.bk_n)) > 0 for a in insts)
@@ -177,8 +134,8 @@ def test_rewind_fused_policy_rollout(torch_gpu, family):
     from deep_reinforcement_learning_for_fjsp_amd._capi import ActorParams, check
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
     N = 128
-    s = _gen_10x5(8, 90)
-    T = int(_ops(s, 0, 8, N).max())
+    s = H.gen_10x5(8, 90)
+    T = int(H.ops(s, 8, N).max())
     with H.env_var("FJSP_STEP_IMPL", "wave" if family == "wave" else None):
         b = EnvBatch(s, N, rng_seed=8)
     b.record_schedule()
@@ -208,10 +165,10 @@ def test_rewind_fused_policy_rollout(torch_gpu, family):
             check(lib.fjsp_env_rollout_policy(b._h, buf, C.byref(ap), C.c_void_p(eps.data_ptr()), C.c_void_p(seed.data_ptr()), 5, T,
                                               None, C.c_void_p(st0.data_ptr()), C.c_void_p(flat.data_ptr()),
                                               C.c_void_p(logp.data_ptr()), C.c_void_p(last.data_ptr()), b._stream()))
-            outs.append((_host(flat), _host(logp), _host(last), _read(b), [_host(x) for x in b.schedule()]))
+            outs.append((H.host(flat), H.host(logp), H.host(last), H.read(b), [H.host(x) for x in b.schedule()]))
         finally:
             lib.fjsp_rollout_destroy(buf)
-    _same(outs[0], outs[1], "fused policy replay")
+    H.same(outs[0], outs[1], "fused policy replay")
 
 
 def test_branch_across_batches(torch_gpu):
@@ -219,37 +176,37 @@ def test_branch_across_batches(torch_gpu):
     every branch block continues exactly as a twin of the source stepped with that block's deterministic pair."""
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
-    NI, N, P = 64, 512, len(DET_SO)
-    s = _gen_10x5(NI, 1234)
-    T = int(_ops(s, 0, NI, N).max())
+    NI, N, P = 64, 512, len(H.DET_SO)
+    s = H.gen_10x5(NI, 1234)
+    T = int(H.ops(s, NI, N).max())
     src = EnvBatch(s, N, rng_seed=9)
     twin = EnvBatch(s, N, rng_seed=9)
     br = EnvBatch(s, P * N, rng_seed=9)
     assert src.kernel_family == br.kernel_family == 1 and P * N > 5120 >= N
     for x in (src, twin, br):
         x.record_schedule()
-    pre = torch.from_numpy(np.tile(np.array(DET_SO, np.uint8)[np.arange(N) % P][None], (5, 1, 1))).cuda()
+    pre = torch.from_numpy(np.tile(np.array(H.DET_SO, np.uint8)[np.arange(N) % P][None], (5, 1, 1))).cuda()
     src.reset(); twin.reset()
     for t in range(5):
         src.step(pre[t]); twin.step(pre[t])
     snap = src.snapshot()
     twin_snap = twin.snapshot()
     br.restore(snap, np.tile(np.arange(N), P))
-    pairs = torch.tensor(DET_SO, dtype=torch.uint8, device="cuda")
+    pairs = torch.tensor(H.DET_SO, dtype=torch.uint8, device="cuda")
     act_b = pairs[:, None, :].expand(P, N, 2).reshape(P * N, 2).contiguous()
     st_b, rw_b = [], []
     for t in range(T - 5):
         st, rw, _ = br.step(act_b)
-        st_b.append(_host(st)); rw_b.append(_host(rw))
-    tab_b, len_b = [_host(x) for x in br.schedule()]
+        st_b.append(H.host(st)); rw_b.append(H.host(rw))
+    tab_b, len_b = [H.host(x) for x in br.schedule()]
     for p in (0, 7, 19):
         twin.restore(twin_snap)
         a = pairs[p][None].expand(N, 2).contiguous()
         for t in range(T - 5):
             st, rw, _ = twin.step(a)
-            assert np.array_equal(H.bits(st_b[t][p * N:(p + 1) * N]), H.bits(_host(st))), (p, t)
-            assert np.array_equal(H.bits(rw_b[t][p * N:(p + 1) * N]), H.bits(_host(rw))), (p, t)
-        tab, ln = [_host(x) for x in twin.schedule()]
+            assert np.array_equal(H.bits(st_b[t][p * N:(p + 1) * N]), H.bits(H.host(st))), (p, t)
+            assert np.array_equal(H.bits(rw_b[t][p * N:(p + 1) * N]), H.bits(H.host(rw))), (p, t)
+        tab, ln = [H.host(x) for x in twin.schedule()]
         assert np.array_equal(tab_b[p * N:(p + 1) * N], tab) and np.array_equal(len_b[p * N:(p + 1) * N], ln), p
 
 
@@ -257,8 +214,8 @@ def test_same_slot_in_another_batch_replays_random_rules(torch_gpu):
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, EnvSnapshot
     NI, N = 16, 64
-    s = _gen_10x5(NI, 55)
-    T = int(_ops(s, 0, NI, N).max())
+    s = H.gen_10x5(NI, 55)
+    T = int(H.ops(s, NI, N).max())
     acts = torch.full((T, N, 2), 0, dtype=torch.uint8, device="cuda")
     acts[..., 0], acts[..., 1] = 5, 4                               # both random.choice rules
     a = EnvBatch(s, N, rng_seed=123, first_env=256)
@@ -271,15 +228,15 @@ def test_same_slot_in_another_batch_replays_random_rules(torch_gpu):
     for t in range(6, T):
         sa, ra, _ = a.step(acts[t])
         sb, rb, _ = bb.step(acts[t])
-        assert np.array_equal(H.bits(_host(sa)), H.bits(_host(sb))) and np.array_equal(H.bits(_host(ra)), H.bits(_host(rb))), t
-    _same(_read(a), _read(bb), "read")
+        assert np.array_equal(H.bits(H.host(sa)), H.bits(H.host(sb))) and np.array_equal(H.bits(H.host(ra)), H.bits(H.host(rb))), t
+    H.same(H.read(a), H.read(bb), "read")
 
 
 def test_errors(torch_gpu):
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd._capi import FjspError
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, VARIANT_MO_DFJSP, VARIANT_SO_SFJSP
-    s = _gen_10x5(4, 10)
+    s = H.gen_10x5(4, 10)
     b = EnvBatch(s, 8, rng_seed=1)
     b.reset()
     b.step(torch.zeros(8, 2, dtype=torch.uint8, device="cuda"))
@@ -291,14 +248,14 @@ def test_errors(torch_gpu):
     # instance mismatch, device src: env untouched, counted
     b2 = EnvBatch(s, 8, rng_seed=1)
     b2.reset()
-    before = _read(b2)
+    before = H.read(b2)
     b2.restore(snap, torch.tensor(bad, dtype=torch.int32, device="cuda"))
     assert snap.errors() > 0
-    _same(before, _read(b2), "untouched env")
+    H.same(before, H.read(b2), "untouched env")
     with pytest.raises(ValueError):
         b2.restore(snap, torch.tensor(bad, dtype=torch.int32, device="cuda"), check=True)
     # other instance set, other variant: FJSP_E_ARG
-    for other in (EnvBatch(_gen_10x5(4, 11), 8), EnvBatch(s, 8, variant=VARIANT_SO_SFJSP)):
+    for other in (EnvBatch(H.gen_10x5(4, 11), 8), EnvBatch(s, 8, variant=VARIANT_SO_SFJSP)):
         with pytest.raises(FjspError) as ei:
             other.restore(snap)
         assert ei.value.code == -1
@@ -398,21 +355,21 @@ def test_lookahead_beats_every_fixed_pair_so_fjssp(torch_gpu):
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
     from deep_reinforcement_learning_for_fjsp_amd.lookahead import rollout_dispatch
     NI = N = 256
-    s = _gen_10x5(NI, 9000)
-    T = int(_ops(s, 0, NI, N).max())
+    s = H.gen_10x5(NI, 9000)
+    T = int(H.ops(s, NI, N).max())
     fixed = []
-    ev = EnvBatch(s, len(DET_SO) * N, rng_seed=2)
+    ev = EnvBatch(s, len(H.DET_SO) * N, rng_seed=2)
     ev.reset()
-    pairs = torch.tensor(DET_SO, dtype=torch.uint8, device="cuda")
-    ev.rollout(pairs[:, None, :].expand(len(DET_SO), N, 2).reshape(1, -1, 2).expand(T, -1, 2).contiguous(), trace=False,
+    pairs = torch.tensor(H.DET_SO, dtype=torch.uint8, device="cuda")
+    ev.rollout(pairs[:, None, :].expand(len(H.DET_SO), N, 2).reshape(1, -1, 2).expand(T, -1, 2).contiguous(), trace=False,
                rewards=False, state=False)
-    fixed = ev.read()["makespan"].cpu().numpy().reshape(len(DET_SO), N)
+    fixed = ev.read()["makespan"].cpu().numpy().reshape(len(H.DET_SO), N)
     b = EnvBatch(s, N, rng_seed=2)
     b.reset()
-    res = rollout_dispatch(b, DET_SO, "makespan")
+    res = rollout_dispatch(b, H.DET_SO, "makespan")
     got = res["objective"].cpu().numpy()
     assert np.all(got <= fixed.min(0))
-    ops = _ops(s, 0, NI, N)
+    ops = H.ops(s, NI, N)
     assert np.array_equal(res["steps"], ops)
     for e in np.random.RandomState(1).choice(N, 24, replace=False).tolist():
         a = s.arrays(e)
@@ -431,7 +388,7 @@ def test_lookahead_beats_every_fixed_pair_mo_dfjsp(torch_gpu):
     NI = len(insts)
     N = 4 * NI
     cands = [(a, m) for a in range(4) for m in range(3)]            # deterministic task / machine rules
-    T = int(_ops(s, 0, NI, N).max())
+    T = int(H.ops(s, NI, N).max())
     ev = EnvBatch(s, len(cands) * N, variant=VARIANT_MO_DFJSP, rng_seed=2)
     mo = torch.zeros(len(cands) * N, 4, dtype=torch.float64, device="cuda"); mo[:, 0] = 1.0
     ev.reset()
@@ -451,7 +408,7 @@ def test_bad_device_save_index_leaves_an_entry_no_restore_takes(torch_gpu):
     restore from it leaves the env and its rows as they were."""
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
-    s = _gen_10x5(4, 12)
+    s = H.gen_10x5(4, 12)
     b = EnvBatch(s, 8, rng_seed=1)
     b.reset()
     b.step(torch.zeros(8, 2, dtype=torch.uint8, device="cuda"))
@@ -459,18 +416,18 @@ def test_bad_device_save_index_leaves_an_entry_no_restore_takes(torch_gpu):
     assert snap.errors() == 2
     assert snap.instance.cpu().tolist() == [0, 1, -1, -1]
     assert not bool(snap.state[2:].any()) and not bool(snap.done[2:].any())
-    before, st = _read(b), _host(b.state)
+    before, st = H.read(b), H.host(b.state)
     b.restore(snap, torch.tensor([-1, -1, 2, -1, -1, -1, -1, -1], dtype=torch.int32, device="cuda"))
     assert snap.errors() == 1
-    _same(before, _read(b), "untouched env")
-    assert np.array_equal(H.bits(st), H.bits(_host(b.state)))
+    H.same(before, H.read(b), "untouched env")
+    assert np.array_equal(H.bits(st), H.bits(H.host(b.state)))
 
 
 def test_kernel_family_is_a_create_argument(torch_gpu):
     from deep_reinforcement_learning_for_fjsp_amd._capi import FjspError
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
     from deep_reinforcement_learning_for_fjsp_amd.lookahead import make_branch
-    s = _gen_10x5(4, 13)
+    s = H.gen_10x5(4, 13)
     with H.env_var("FJSP_STEP_IMPL", "wave"):
         assert EnvBatch(s, 8).kernel_family == 0
         rows = EnvBatch(s, 8, kernel_family=1)           # the argument, not the environment variable, decides
@@ -489,7 +446,7 @@ def test_lookahead_stops_on_an_env_that_cannot_finish(torch_gpu):
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
     from deep_reinforcement_learning_for_fjsp_amd.lookahead import rollout_dispatch
-    s = _gen_10x5(4, 14)
+    s = H.gen_10x5(4, 14)
     b = EnvBatch(s, 8, rng_seed=1)
     b.reset()
     a = torch.zeros(8, 2, dtype=torch.uint8, device="cuda")
@@ -497,6 +454,6 @@ def test_lookahead_stops_on_an_env_that_cannot_finish(torch_gpu):
     b.step(a)
     assert int(b.read()["status"][3].item()) & 1
     with pytest.raises(RuntimeError):
-        rollout_dispatch(b, DET_SO[:4], "makespan")
+        rollout_dispatch(b, H.DET_SO[:4], "makespan")
     with pytest.raises(ValueError):
         rollout_dispatch(b, [(6, 5)], "makespan")                # refused before anything is created

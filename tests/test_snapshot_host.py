@@ -116,10 +116,10 @@ def test_lookahead_objective_names():
             return dict(makespan=torch.tensor([5, 6, 7], dtype=torch.int32),
                         delay_time_sum=torch.tensor([1, 2, 3], dtype=torch.int64))
 
-    assert L._objective_values(_B(), "makespan").tolist() == [5.0, 6.0, 7.0]
-    assert L._objective_values(_B(), "tardiness").tolist() == [1.0, 2.0, 3.0]
-    assert L._objective_values(_B(), lambda r: r["makespan"] + r["delay_time_sum"]).tolist() == [6.0, 8.0, 10.0]
+    assert L.objective_values(_B(), "makespan").tolist() == [5.0, 6.0, 7.0]
+    assert L.objective_values(_B(), "tardiness").tolist() == [1.0, 2.0, 3.0]
+    assert L.objective_values(_B(), lambda r: r["makespan"] + r["delay_time_sum"]).tolist() == [6.0, 8.0, 10.0]
     with pytest.raises(ValueError):
-        L._objective_values(_B(), "energy")                       # not a MO_DFJSP batch
+        L.objective_values(_B(), "energy")                       # not a MO_DFJSP batch
     with pytest.raises(ValueError):
-        L._objective_values(_B(), "throughput")
+        L.objective_values(_B(), "throughput")

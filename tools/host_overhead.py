@@ -10,7 +10,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from deep_reinforcement_learning_for_fjsp_amd import instances as fi
-from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, global_actions, _ptr
+from deep_reinforcement_learning_for_fjsp_amd._capi import ptr as _ptr
+from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, global_actions
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 s = fi.InstanceSet(N).generate_range(1000, fi.bench_10x5_params()).solve_fluid()

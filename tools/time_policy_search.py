@@ -26,7 +26,7 @@ from deep_reinforcement_learning_for_fjsp_amd import instances as fi  # noqa: E4
 from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS  # noqa: E402
 from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import ActorNet, native_actor_params  # noqa: E402
 from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch  # noqa: E402
-from deep_reinforcement_learning_for_fjsp_amd.lookahead import _ops_per_env  # noqa: E402
+from deep_reinforcement_learning_for_fjsp_amd.lookahead import ops_per_env  # noqa: E402
 
 DET_SO = [(a, b) for a in range(5) for b in range(4)]
 
@@ -74,7 +74,7 @@ s = fi.InstanceSet(256).generate_range(1000, fi.bench_10x5_params()).solve_fluid
 torch.manual_seed(0)
 actor = ActorNet(20, 128, 2, 30).cuda()
 b = EnvBatch(s, N, rng_seed=1)
-T = int(_ops_per_env(b).max().item())
+T = int(ops_per_env(b).max().item())
 
 # greedy play, kernel only (explicit step bound: no read-back), and the whole call
 med, lo, hi = event_timed(b.reset, lambda: PS.play(b, actor, max_steps=T), args.reps)
@@ -94,7 +94,7 @@ emit(what="play_greedy_per_step_loop", seconds_median=med, seconds_min=lo, secon
 lib = _capi.lib()
 buf = C.c_void_p()
 _capi.check(lib.fjsp_rollout_create(40, N, 20, 0, C.byref(buf)))
-p = lambda t: C.c_void_p(t.data_ptr())
+p = _capi.ptr
 eps = torch.zeros(1, dtype=torch.float32, device="cuda")
 seed = torch.tensor([7], dtype=torch.int64, device="cuda")
 flat = torch.zeros(40, N, dtype=torch.float32, device="cuda")
