@@ -56,6 +56,11 @@ SIGNATURES = {
     "fjsp_fluid_lp": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "fjsp_env_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _pp]),
     "fjsp_env_create_family": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _i32, _pp]),
+    "fjsp_env_create_generated": (C.c_int, [C.POINTER(GenParams), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
+    "fjsp_env_regenerate": (C.c_int, [_vp, _u64, _u64]),
+    "fjsp_env_generated_stats": (C.c_int, [_vp, C.POINTER(_i64 * 4)]),
+    "fjsp_env_generated_times": (C.c_int, [_vp, C.POINTER(_dbl * 5)]),
+    "fjsp_env_instance_read": (C.c_int, [_vp, _i32, C.POINTER(_i32 * 6), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_dbl), _vp]),
     "fjsp_env_destroy": (None, [_vp]),
     "fjsp_env_num_envs": (C.c_int, [_vp]),
     "fjsp_env_state_size": (C.c_int, [_vp]),

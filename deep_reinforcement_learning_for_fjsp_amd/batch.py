@@ -183,9 +183,14 @@ class EnvBatch(object):
                 raise ValueError("kernel_family must be None, 0 or 1, got %r" % (kernel_family,))
             check(self._lib.fjsp_env_create_family(instances.handle, int(first), int(n_inst), int(n_envs), int(variant),
                                                    self.device_index, lib_seed, int(kernel_family), C.byref(self._h)))
+        self.first = int(first)
+        self.gen_params = None
+        self._bind(n_envs, n_inst, variant, rng_seed)
+
+    def _bind(self, n_envs, n_inst, variant, rng_seed):
+        """What every constructor does once the handle exists: sizes, kernel family, the output tensors."""
         self.N = int(n_envs)
         self.n_inst = int(n_inst)
-        self.first = int(first)
         self.variant = int(variant)
         self.rng_seed = int(rng_seed)
         self.state_size = self._lib.fjsp_env_state_size(self._h)
@@ -202,6 +207,89 @@ class EnvBatch(object):
         # the action tensor must have are prepared once
         self._p_state, self._p_reward, self._p_done = _ptr(self.state), _ptr(self.reward), _ptr(self.done)
         self._act_shape = torch.Size((self.N, 2))
+
+    @classmethod
+    def generated(cls, params, n_envs, seed_base, n_inst=None, variant=VARIANT_SO_FJSSP, device=0, rng_seed=0, first_env=0,
+                  family=-1):
+        """A batch whose instances are generated and solved on the device (fjsp_env_create_generated): env q plays
+        instance q % n_inst = what InstanceSet.generate_range(seed_base, params) + solve_fluid() make of seed
+        seed_base + first_env + q % n_inst.  first_env shifts the instance seeds and the env random streams alike, so a
+        shard [first_env, first_env + n_envs) is a slice of the one-GPU batch.  There is no InstanceSet (`instances` is
+        None; instance_arrays(i) reads an instance back); regenerate() refills the batch in place.  One order only
+        (params.S == 1), not VARIANT_MO_DFJSP: FjspError(FJSP_E_UNSUPPORTED)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("EnvBatch needs an MI355X: the environment kernels have no CPU path")
+        if family not in (-1, 0, 1):
+            raise ValueError("family must be -1, 0 or 1, got %r" % (family,))
+        self = cls.__new__(cls)
+        self._lib = _capi.lib()
+        self.instances = None
+        n_inst = int(n_envs) if n_inst is None else int(n_inst)
+        self.device_index = int(device)
+        self.device = torch.device("cuda", self.device_index)
+        self._stream = functools.partial(_capi.stream, self.device_index)
+        self._h = C.c_void_p()
+        self.first_env, self.first = int(first_env), 0
+        self.gen_params, self.seed_base, self.family = params, int(seed_base), int(family)
+        mask = 2 ** 64 - 1
+        check(self._lib.fjsp_env_create_generated(C.byref(params), n_inst, int(n_envs), int(variant), self.device_index,
+                                                  (int(rng_seed) + self.first_env * ENV_SEED_STRIDE) & mask, int(family),
+                                                  (self.seed_base + self.first_env) & mask, C.byref(self._h)))
+        self._bind(n_envs, n_inst, variant, rng_seed)
+        return self
+
+    def regenerate(self, seed_base, rng_seed=None):
+        """New instances in place (fjsp_env_regenerate): instance i becomes that of seed seed_base + first_env + i, its
+        fluid LP is solved, the fluid tables are rebuilt; every env is left done (call reset()) with its random stream
+        restarted from rng_seed (None: the batch's).  No allocation, no host instance set.  Synchronises.  If an
+        instance cannot be played (FjspError names it and its seed) the batch refuses every call until a regenerate
+        succeeds."""
+        if self.gen_params is None:
+            raise _capi.FjspError(_capi.FJSP_E_STATE, "regenerate(): the batch was not made by EnvBatch.generated")
+        rng_seed = self.rng_seed if rng_seed is None else int(rng_seed)
+        mask = 2 ** 64 - 1
+        rc = self._lib.fjsp_env_regenerate(self._h, (int(seed_base) + self.first_env) & mask,
+                                           (rng_seed + self.first_env * ENV_SEED_STRIDE) & mask)
+        # the cached rows are those of the old instances, whatever the outcome
+        self.state.zero_(); self.reward.zero_(); self.done.fill_(1)
+        check(rc)
+        self.seed_base, self.rng_seed = int(seed_base), rng_seed
+        self.step_bytes = int(self._lib.fjsp_env_step_bytes(self._h))
+        return self
+
+    def instance_dims(self, i):
+        """dict(R, M, K, S, jobs0, jobs) of instance i, from the InstanceSet or, for a generated batch, the device."""
+        if self.instances is not None:
+            return self.instances.dims(self.first + int(i))
+        d = (C.c_int32 * 6)()
+        check(self._lib.fjsp_env_instance_read(self._h, int(i), C.byref(d), None, None, None, None, None, None, None, None, None))
+        return dict(R=d[0], M=d[1], K=d[2], S=d[3], jobs0=d[4], jobs=d[5])
+
+    def instance_arrays(self, i):
+        """instances.InstanceArrays (with x) of instance i of a generated batch, read back from the device
+        (fjsp_env_instance_read); of any other batch, its InstanceSet's arrays."""
+        from .instances import InstanceArrays
+        if self.instances is not None:
+            return self.instances.arrays(self.first + int(i))
+        d = self.instance_dims(i)
+        R, M, K, S = d["R"], d["M"], d["K"], d["S"]
+        Jr, p, elig_n = np.zeros(R, np.int32), np.zeros((K, M), np.int32), np.zeros(K, np.int32)
+        elig_list, count = np.zeros((K, M), np.int32), np.zeros((S, R), np.int32)
+        arrive, delivery, x = np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros((K, M), np.float64)
+        ddt = C.c_double()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        check(self._lib.fjsp_env_instance_read(self._h, int(i), None, ptr(Jr), ptr(p), ptr(elig_n), ptr(elig_list), ptr(count),
+                                               ptr(arrive), ptr(delivery), C.byref(ddt), ptr(x)))
+        return InstanceArrays(R, M, K, S, Jr, p, elig_n, elig_list, count, arrive, delivery, ddt.value, x)
+
+    def generated_stats(self):
+        """Of the last generated() / regenerate(): dict(instances, lp_device, lp_host, device_pivots), and `ms`: the
+        milliseconds of the generate kernel, the LP launches, the host LP route, fluid tables + reset, the whole call."""
+        out, ms = (C.c_int64 * 4)(), (C.c_double * 5)()
+        check(self._lib.fjsp_env_generated_stats(self._h, C.byref(out)))
+        check(self._lib.fjsp_env_generated_times(self._h, C.byref(ms)))
+        return dict(instances=int(out[0]), lp_device=int(out[1]), lp_host=int(out[2]), device_pivots=int(out[3]),
+                    ms=dict(generate=ms[0], lp_device=ms[1], lp_host=ms[2], tables_reset=ms[3], total=ms[4]))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -496,15 +584,18 @@ class EnvBatch(object):
         return int(self._lib.fjsp_env_lp_device_pivots(self._h))
 
     def machine_time_end(self):
-        d = self.instances.dims(self.first)
-        mp = max(self.instances.dims(self.first + i)["M"] for i in range(self.n_inst)) if self.n_inst > 1 else d["M"]
+        if self.instances is None:
+            mp = int(self.gen_params.M)
+        else:
+            d = self.instances.dims(self.first)
+            mp = max(self.instances.dims(self.first + i)["M"] for i in range(self.n_inst)) if self.n_inst > 1 else d["M"]
         out = torch.zeros(self.N, mp, dtype=torch.int32, device=self.device)
         check(self._lib.fjsp_env_machine_time_end(self._h, _ptr(out), int(mp), self._stream()))
         return out
 
     def fluid_tables(self, i):
         import numpy as np
-        d = self.instances.dims(self.first + (i % self.n_inst))
+        d = self.instance_dims(i % self.n_inst)
         K, M = d["K"], d["M"]
         rate = np.zeros((K, M)); arr = np.zeros((K, M)); rs = np.zeros(K); ts = np.zeros(K)
         p = lambda a: a.ctypes.data_as(C.c_void_p)

@@ -40,12 +40,6 @@ bool host_alloc(fjsp_env *e, size_t bytes, T **h) {
 
 // ---- fjsp_env_create_family, stage by stage
 
-// largest sizes over the instances of a batch
-struct Shape {
-    int K = 0, M = 0, J = 0, S = 1, R = 0, B = 1;    // B: breakdown windows of one instance (MO_DFJSP)
-    bool single_job = true;                           // one order, one job per kind, in every instance
-};
-
 // Stage 1 (before any HIP call): the kernels can play `in` as `variant`; its sizes go into *sh.
 int check_instance(const Instance &in, int variant, bool class_fjsp, Shape &sh) {
     const bool dyn = variant == FJSP_VARIANT_MO_DFJSP;
@@ -111,6 +105,28 @@ int check_instance(const Instance &in, int variant, bool class_fjsp, Shape &sh) 
     sh.S = std::max(sh.S, in.S); sh.R = std::max(sh.R, in.R);
     sh.K = std::max(sh.K, in.K); sh.M = std::max(sh.M, in.M); sh.J = std::max(sh.J, nj);
     return FJSP_OK;
+}
+
+}  // namespace
+
+namespace fjsp {
+// Stages 2 and 3 of a create: the batch's sizes from its largest instance, then plan_launch and plan_layout
+int plan_batch(DevBatch &b, LaunchPlan &p, const Shape &sh, int n_inst, int n_envs, int variant, uint64_t rng_seed, int family) {
+    const bool dyn = variant == FJSP_VARIANT_MO_DFJSP;
+    b.N = n_envs; b.n_inst = n_inst;
+    b.KC = sh.K <= 64 ? 1 : (sh.K <= 128 ? 2 : 4);
+    b.KP = b.KC * kWave;
+    b.MP = sh.M;
+    b.variant = variant;
+    b.n_obs = variant == FJSP_VARIANT_SO_FJSSP ? 10 : (dyn ? 15 : 9);
+    b.n_static = variant == FJSP_VARIANT_MO_FJSSP_DISCRETES ? 7 : 0;
+    b.state_size = b.n_static + 2 * b.n_obs;
+    b.rng_seed = rng_seed;
+    b.mord = (sh.S > 1 || dyn) ? 1 : 0; b.SP = sh.S; b.RP = sh.R;     // MO_DFJSP always runs on the per-env fluid tables
+    b.single_job = (sh.single_job && !b.mord) ? 1 : 0;
+    b.kmax = sh.K;
+    const int rc = plan_launch(b, p, sh, family);
+    return rc == FJSP_OK ? plan_layout(b, sh) : rc;
 }
 
 // Stage 2: the kernel family and the build of it the handle launches, kept in its LaunchPlan.  The one place where the
@@ -192,6 +208,9 @@ int plan_layout(DevBatch &b, const Shape &sh) {
     return FJSP_OK;
 }
 
+}  // namespace fjsp
+
+namespace {
 // Stage 4, the static state row (i_ss)
 void pack_static_state(const Instance &in, int variant, double *ss) {
     if (variant == FJSP_VARIANT_MO_FJSSP_DISCRETES) {
@@ -400,6 +419,10 @@ int upload_batch(fjsp_env *e, const std::vector<unsigned char> &islab) {
 
 namespace fjsp {
 int usable(const fjsp_env *e, const char *who, unsigned need, const uint8_t *d_actions) {
+    if (e->gen_failed) {
+        set_error(std::string(who) + ": the last fjsp_env_regenerate of this batch failed; regenerate it from other seeds first");
+        return FJSP_E_STATE;
+    }
     if ((need & kIntact) && e->failed) {
         set_error(std::string(who) + ": the order-arrival service of this batch failed earlier; destroy the batch");
         return FJSP_E_STATE;
@@ -449,20 +472,7 @@ int fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_ins
     std::unique_ptr<fjsp_env, void (*)(fjsp_env *)> e(new fjsp_env(), fjsp_env_destroy);
     e->device = device; e->src = s; e->first = first;
     DevBatch &b = e->b;
-    b.N = n_envs; b.n_inst = n_inst;
-    b.KC = sh.K <= 64 ? 1 : (sh.K <= 128 ? 2 : 4);
-    b.KP = b.KC * kWave;
-    b.MP = sh.M;
-    b.variant = variant;
-    b.n_obs = variant == FJSP_VARIANT_SO_FJSSP ? 10 : (dyn ? 15 : 9);
-    b.n_static = variant == FJSP_VARIANT_MO_FJSSP_DISCRETES ? 7 : 0;
-    b.state_size = b.n_static + 2 * b.n_obs;
-    b.rng_seed = rng_seed;
-    b.mord = (sh.S > 1 || dyn) ? 1 : 0; b.SP = sh.S; b.RP = sh.R;     // MO_DFJSP always runs on the per-env fluid tables
-    b.single_job = (sh.single_job && !b.mord) ? 1 : 0;
-    b.kmax = sh.K;
-    int rc = plan_launch(b, e->plan, sh, family);
-    if (rc == FJSP_OK) rc = plan_layout(b, sh);
+    int rc = plan_batch(b, e->plan, sh, n_inst, n_envs, variant, rng_seed, family);
     if (rc != FJSP_OK) return rc;
 
     std::vector<unsigned char> islab((size_t)n_inst * b.L.i_stride, 0);
@@ -494,6 +504,7 @@ void fjsp_env_destroy(fjsp_env *e) {
         for (void *p : e->host_allocs) (void)hipHostFree(p);
         if (e->sched.rec) (void)hipFree(e->sched.rec);
     }
+    generated_release(e);
     delete e;
 }
 
@@ -746,6 +757,7 @@ int fjsp_pyset_and_order(uint32_t idle_mask, const int32_t *machines, int32_t n,
 
 int fjsp_env_fluid_tables(fjsp_env *e, int32_t i, double *h_rate, double *h_arr, double *h_rate_sum, double *h_time_sum) {
     if (!e || i < 0 || i >= e->b.N) { set_error("fjsp_env_fluid_tables: bad arguments"); return FJSP_E_ARG; }
+    if (const int rc = usable(e, "fjsp_env_fluid_tables", 0)) return rc;
     DeviceGuard guard(e->device);
     const int inst = i % e->b.n_inst;
     const int K = e->inst_K[(size_t)inst], M = e->inst_M[(size_t)inst];

@@ -13,6 +13,13 @@
 
 namespace fjsp {
 struct LpCache; struct LpPool; struct AsyncRing;   // fjsp_arrivals.hip
+struct GenState;                                   // fjsp_generate.hip
+
+// largest sizes over the instances of a batch
+struct Shape {
+    int K = 0, M = 0, J = 0, S = 1, R = 0, B = 1;    // B: breakdown windows of one instance (MO_DFJSP)
+    bool single_job = true;                           // one order, one job per kind, in every instance
+};
 
 // What only the order-arrival services of multi-order batches use (fjsp_arrivals.hip)
 struct ArrivalService {
@@ -49,6 +56,10 @@ struct fjsp_env {
     int first = 0;
     bool failed = false;        // the arrival service failed mid-step: parked envs are in limbo, the handle refuses further steps
     fjsp::ArrivalService arr;
+    // handles of fjsp_env_create_generated only (fjsp_generate.hip): the device generator's buffers and parameters.  Such a
+    // handle has no host instance set (src == nullptr) and never a multi-order batch, the only reader of src.
+    fjsp::GenState *gen = nullptr;
+    bool gen_failed = false;    // the last fjsp_env_regenerate failed: reset / step / rollout are refused until one succeeds
 };
 
 namespace fjsp {
@@ -86,5 +97,11 @@ int usable(const fjsp_env *e, const char *who, unsigned need, const uint8_t *d_a
 int service_arrivals(fjsp_env *e, const double *d_mo, double *d_state, double *d_reward, uint8_t *d_done, int16_t *d_trace,
                      hipStream_t st);
 bool async_idle(const fjsp_env *e);
+// fjsp_env.hip, stages 2 and 3 of a create: the kernel family and its builds (the library's only reader of the FJSP_*
+// environment variables), then the record layouts; both from the batch's largest sizes alone
+int plan_batch(DevBatch &b, LaunchPlan &p, const Shape &sh, int n_inst, int n_envs, int variant, uint64_t rng_seed, int family);   // both
+int plan_launch(DevBatch &b, LaunchPlan &p, const Shape &sh, int family);
+int plan_layout(DevBatch &b, const Shape &sh);
+void generated_release(fjsp_env *e);        // fjsp_generate.hip: frees e->gen (its device memory is in e->dev_allocs)
 void arrivals_release(ArrivalService &a);   // joins the LP threads first; on the handle's device
 }  // namespace fjsp

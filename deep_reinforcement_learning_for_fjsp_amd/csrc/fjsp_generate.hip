@@ -1,0 +1,743 @@
+// Training instances generated ON THE DEVICE: fjsp_env_create_generated / fjsp_env_regenerate (include/fjsp_amd.h).
+//
+// The host path of a fresh batch is fjsp_instances_generate (one splitmix64 stream per instance, fjsp_instance.cpp),
+// fjsp_instances_solve_fluid (the order-0 fluid LP, fjsp_lp.cpp), pack_instance (fjsp_env.hip), two uploads and a new
+// allocation.  A generated handle owns its instance records and refills them in place from a seed:
+//   generate_pack_kernel    record i from (seed_base + i, parameters): byte for byte what pack_instance(generate(...)) writes,
+//                           except x and the static state row, which need the LP; the LP inputs (Q, n_now); and on which
+//                           of two lists the instance goes -- its order-0 tableau fits the LDS of a CU, or it does not
+//   lp_device_kernel        (fjsp_lp_device.hip, unchanged) over the fitting list, in bounded chunks of staging slots
+//   solve_fluid_lp          (fjsp_lp.cpp) on host threads for the other list: the two solvers are pivot for pivot the same
+//   generate_finish_kernel  x from the staging slot into the record, the static state row
+//   fluid_tables_kernel, reset_kernel (fjsp_kernels.hip, unchanged), every env marked done: the state a create leaves
+//
+// The generator's stream advances by a constant per draw, so draw i is a pure function of (seed, i).  One wave per
+// instance: lane 0 walks the one serial chain there is -- the number of eligible machines of every operation type decides
+// where the next type's draws start, K dependent hashes -- and the lanes then run their own operation types' shuffles and
+// processing times from those offsets, and write the record's rows side by side.  (One lane per instance would leave the
+// per-type machine lists in scratch memory and the record writes uncoalesced.)
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <system_error>
+#include <thread>
+
+#include "fjsp_env_impl.h"
+#include "fjsp_launch.h"
+
+#pragma clang fp contract(off)
+
+namespace fjsp {
+
+// per instance, written by generate_pack_kernel and read back by the host in the call's one synchronisation
+struct GenInfo {
+    int32_t status;      // 0 or a negative FJSP_E_* code
+    int32_t K, R, nj;    // operation types, kinds, jobs
+    int32_t nx;          // eligible (operation type, machine) pairs
+    int32_t lds;         // LDS bytes of the order-0 tableau (lp_device_lds_bytes)
+    int32_t ops;         // operations (schedule slots)
+    int32_t delivery;    // delivery time of the order
+};
+static_assert(sizeof(GenInfo) == 32, "GenInfo is eight words");
+
+struct GenArgs {
+    fjsp_gen_params g;
+    uint64_t seed_base;
+    int32_t class_fjsp;      // SO_DFJSP: the order's delivery time is every job's due date, every machine needs an operation
+    int32_t allow_device;    // 0: every LP goes to the host list (FJSP_LP_IMPL=host)
+    int32_t kmax;            // operation types of the largest possible instance: stride of the eligible-list rows
+    int32_t RP;
+    uint8_t *elig;           // [n_inst][kmax][MP] machine_rj_dict in FILE order (zeros behind each list)
+    GenInfo *info;           // [n_inst]
+    uint32_t *counts;        // [0] length of fit_ids, [1] of host_ids, [2] largest fitting tableau (bytes), [3] first instance whose LP left no rate
+    uint32_t *fit_ids;       // [n_inst] instances whose LP runs on the device, in arrival order
+    uint32_t *host_ids;      // [n_inst] the others
+    uint16_t *lp_in;         // [slot of fit_ids][2][KP] (Q, n_now), lp_device_kernel's format
+};
+
+constexpr int kGenMaxK = kWave * kMaxKC;
+constexpr uint32_t kLpLdsLimit = 156 * 1024;
+constexpr int kLpMaxColumns = 512;          // lp_device_max_columns(), verified by the host at create
+
+namespace {
+__device__ inline uint64_t gen_draw(uint64_t seed, uint32_t i) {      // draw i (0-based) of Rng(seed), fjsp_instance.cpp
+    uint64_t z = seed + (uint64_t)(i + 1u) * 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+__device__ inline int gen_randint(uint64_t seed, uint32_t i, int a, int b) {
+    return a + (int)(((gen_draw(seed, i) >> 32) * (uint64_t)(b - a + 1)) >> 32);
+}
+// lp_device_lds_bytes (fjsp_lp_device.hip) restated for the device; the host compares the two for every instance
+__device__ inline uint32_t gen_lp_lds_bytes(int K, int M, int nx, int R, int MP) {
+    const size_t nr = (size_t)K + M + (K - R), nc = (size_t)nx + 1 + nr + 1;
+    const size_t bytes = nr * nc * 8 + nc * 8 + 2 * nr * 8 + nr * 4 + (size_t)K * M * 2 + (size_t)K * 2 + nr * 2 + (size_t)K * MP * 2 + (size_t)K * 8 + 128;
+    return (uint32_t)((bytes + 15) & ~(size_t)15);
+}
+}  // namespace
+
+// One wave per instance.
+__global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArgs a) {
+    __shared__ uint8_t s_el[kGenMaxK * kMaxM];       // the shuffle of operation type k, then its eligible list
+    __shared__ uint16_t s_p[kGenMaxK * kMaxM];       // p[k][m], 0 = ineligible
+    __shared__ double s_tr[kGenMaxK];                // time_rj: mean processing time over the eligible list
+    __shared__ uint32_t s_off[kGenMaxK], s_poff[kGenMaxK];   // first shuffle draw / first processing-time draw of type k
+    __shared__ uint16_t s_rk[kGenMaxK], s_koff[kGenMaxK + 1], s_jbeg[kGenMaxK + 1], s_cnt[kGenMaxK];
+    __shared__ uint8_t s_n[kGenMaxK], s_jk[kGenMaxK], s_Jr[kGenMaxK];
+    __shared__ int32_t s_hdr[8];                     // R, K, status, nx, first count draw, nj, delivery, ops
+    const int inst = (int)blockIdx.x, l = (int)threadIdx.x;
+    if (inst >= b.n_inst) return;
+    const fjsp_gen_params &g = a.g;
+    const uint64_t seed = a.seed_base + (uint64_t)inst;
+    const int M = g.M, MP = b.MP, KP = b.KP;
+    unsigned char *rec = b.inst + (size_t)inst * b.L.i_stride;
+    const Layout &L = b.L;
+
+    // ---- R, J_r, the kinds' first operation types
+    const int R = gen_randint(seed, 0u, g.R_min, g.R_max);                                       // :42
+    const bool r_ok = R >= 1 && R <= a.RP && R <= kGenMaxK;
+    for (int r = l; r_ok && r < R; r += kWave) s_Jr[r] = (uint8_t)gen_randint(seed, 1u + (uint32_t)r, g.J_min, g.J_max);   // :46,71
+    __syncthreads();
+    if (l == 0) {
+        int K = 0, st = r_ok ? 0 : FJSP_E_FORMAT;
+        for (int r = 0; st == 0 && r < R; ++r) {
+            const int J = s_Jr[r];
+            if (J < 1 || K + J > KP || K + J > a.kmax) { st = FJSP_E_FORMAT; break; }
+            s_koff[r] = (uint16_t)K;
+            for (int j = 0; j < J; ++j) { s_rk[K + j] = (uint16_t)r; s_jk[K + j] = (uint8_t)j; }
+            K += J;
+        }
+        if (st == 0) s_koff[R] = (uint16_t)K;
+        // the one serial chain: n of type k decides where type k + 1's draws start                 :73
+        uint32_t pos = 1u + (uint32_t)R, nx = 0;
+        for (int k = 0; st == 0 && k < K; ++k) {
+            const int n = gen_randint(seed, pos, 1, M);
+            if (n < 1 || n > M) { st = FJSP_E_FORMAT; break; }
+            s_n[k] = (uint8_t)n; s_off[k] = pos + 1u;
+            pos += 1u + (uint32_t)n;
+            nx += (uint32_t)n;
+        }
+        uint32_t q = pos;                                                                          // :74 draws follow all shuffles
+        for (int k = 0; st == 0 && k < K; ++k) { s_poff[k] = q; q += s_n[k]; }
+        s_hdr[0] = R; s_hdr[1] = K; s_hdr[2] = st; s_hdr[3] = (int)nx; s_hdr[4] = (int)q;
+    }
+    __syncthreads();
+    const int K = s_hdr[1], nx = s_hdr[3];
+    int status = s_hdr[2];
+    if (status != 0) {
+        if (l == 0) a.info[inst] = GenInfo{status, 0, 0, 0, 0, 0, 0, 0};
+        return;
+    }
+    // ---- per operation type: choice(M, n, replace=False) as a Fisher-Yates prefix, then the processing times
+    for (int k = l; k < K; k += kWave) {
+        uint8_t *perm = s_el + k * kMaxM;
+        uint16_t *pk = s_p + k * kMaxM;
+        const int n = s_n[k];
+        for (int m = 0; m < M; ++m) { perm[m] = (uint8_t)m; pk[m] = 0; }
+        for (int i = 0; i < n; ++i) {
+            int j = gen_randint(seed, s_off[k] + (uint32_t)i, i, M - 1);
+            j = j < i ? i : (j > M - 1 ? M - 1 : j);
+            const uint8_t t = perm[i]; perm[i] = perm[j]; perm[j] = t;
+        }
+        long sum = 0;
+        for (int i = 0; i < n; ++i) {
+            const int pv = gen_randint(seed, s_poff[k] + (uint32_t)i, g.p_min, g.p_max);
+            pk[perm[i]] = (uint16_t)pv;
+            sum += pv;
+        }
+        for (int m = n; m < M; ++m) perm[m] = 0;
+        s_tr[k] = (double)sum / (double)n;                                                         // :78
+    }
+    for (int r = l; r < R; r += kWave) s_cnt[r] = (uint16_t)gen_randint(seed, (uint32_t)s_hdr[4] + (uint32_t)r, g.N_min, g.N_max);   // :80
+    __syncthreads();
+    if (l == 0) {
+        int nj = 0, ops = 0;
+        double acc = 0.0;                                                                          // :81-82, strictly left to right
+        for (int r = 0; r < R; ++r) { s_jbeg[r] = (uint16_t)nj; nj += s_cnt[r]; ops += (int)s_cnt[r] * (int)s_Jr[r]; }
+        s_jbeg[R] = (uint16_t)nj;
+        for (int k = 0; k < K; ++k) acc = acc + s_tr[k] * (double)s_cnt[s_rk[k]];
+        const double gap = acc * g.DDT / (double)(M * 2);
+        const double dl = 0.0 + gap;                                                               // :85-86 (one order: arrives at 0)
+        s_hdr[5] = nj; s_hdr[6] = (int)dl; s_hdr[7] = ops;
+        if (nj > b.JP || nj > 65535) s_hdr[2] = FJSP_E_FORMAT;
+    }
+    __syncthreads();
+    const int nj = s_hdr[5], delivery = s_hdr[6];
+    status = s_hdr[2];
+    // SO_DFJSP divides by the number of operation types of every machine (check_instance, fjsp_env.hip)
+    int ops_m = 0;
+    if (l < M)
+        for (int k = 0; k < K; ++k) ops_m += s_p[k * kMaxM + l] > 0 ? 1 : 0;
+    if (a.class_fjsp && __any(l < M && ops_m == 0) && status == 0) status = FJSP_E_UNSUPPORTED;
+    const uint32_t lds = gen_lp_lds_bytes(K, M, nx, R, MP);
+    if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[7], delivery};
+    if (status != 0) return;
+
+    // ---- the record (pack_instance, fjsp_env.hip); the slab was zeroed before the launch
+    if (l == 0) *reinterpret_cast<InstHeader *>(rec) = InstHeader{K, M, R, nj};
+    uint16_t *ocnt = reinterpret_cast<uint16_t *>(rec + L.i_ocnt);
+    uint32_t *kA = reinterpret_cast<uint32_t *>(rec + L.i_kA), *kB = reinterpret_cast<uint32_t *>(rec + L.i_kB);
+    uint32_t *elig = reinterpret_cast<uint32_t *>(rec + L.i_elig), *first4 = reinterpret_cast<uint32_t *>(rec + L.i_f4);
+    uint32_t *jinfo = reinterpret_cast<uint32_t *>(rec + L.i_jinfo);
+    int32_t *due = reinterpret_cast<int32_t *>(rec + L.i_due);
+    uint16_t *p = reinterpret_cast<uint16_t *>(rec + L.i_p);
+    uint8_t *el_out = a.elig + (size_t)inst * (size_t)a.kmax * (size_t)MP;
+    for (int r = l; r < R; r += kWave) {
+        const int c = s_cnt[r], J = s_Jr[r], jb = s_jbeg[r];
+        ocnt[r] = (uint16_t)c;
+        // class_FJSSP.py:214-218 with Python's round (half to even: rint in the default rounding mode)
+        const long r_due = (long)rint((double)((long)delivery * J) / (double)c);
+        for (int n = 0; n < c; ++n) {
+            due[jb + n] = a.class_fjsp ? delivery : (int32_t)(long)rint((double)(r_due * n) / (double)c);
+            jinfo[jb + n] = (uint32_t)s_koff[r] | ((uint32_t)J << 16);
+        }
+    }
+    for (int k = l; k < K; k += kWave) {
+        const int r = s_rk[k], j = s_jk[k], J = s_Jr[r], n = s_n[k];
+        kA[k] = (uint32_t)s_jbeg[r] | ((uint32_t)s_cnt[r] << 16);
+        kB[k] = (uint32_t)j | ((uint32_t)J << 8) | ((uint32_t)(r & 0xFF) << 16) | ((uint32_t)((j == J - 1 ? 1u : 0u) | 2u) << 24);
+        uint32_t em = 0, f4 = 0;
+        for (int m = 0; m < M; ++m) {
+            const uint16_t pv = s_p[k * kMaxM + m];
+            if (pv > 0) em |= 1u << m;
+            p[(size_t)k * MP + m] = pv;
+            el_out[(size_t)k * MP + m] = s_el[k * kMaxM + m];
+        }
+        for (int q = 0; q < n && q < 4; ++q) f4 |= (uint32_t)s_el[k * kMaxM + q] << (8 * q);
+        elig[k] = em;
+        first4[k] = f4;
+    }
+    if (b.grp && l < 16) {
+        // the row kernels' head line (pack_instance): one job per kind there, job index == kind index, the job's number is 0
+        uint32_t w = l < M ? (uint32_t)ops_m : 0u;
+        if (l < R) {
+            w |= (uint32_t)s_koff[l] << 8; w |= (uint32_t)s_Jr[l] << 16;
+            const int c = s_cnt[l];
+            const long r_due = (long)rint((double)((long)delivery * s_Jr[l]) / (double)c);
+            reinterpret_cast<int32_t *>(rec + L.i_op + 2048 + 64)[l] = a.class_fjsp ? delivery : (int32_t)(long)rint((double)(r_due * 0) / (double)c);
+        }
+        w |= (uint32_t)(l == 0 ? K : (l == 1 ? M : (l == 2 ? nj : 0))) << 24;
+        reinterpret_cast<uint32_t *>(rec + L.i_op + 2048)[l] = w;
+    }
+    // ---- the order-0 LP: Q[k] = count[r], n_now[k] = (j == 0 ? count[r] : 0) (solve_order0), and where it is solved
+    const int nc = nx + 1 + (K + M + K - R) + 1;
+    const bool fit = a.allow_device && lds <= kLpLdsLimit && nc <= kLpMaxColumns;
+    if (l == 0) {
+        if (fit) {
+            s_hdr[0] = (int)atomicAdd(a.counts + 0, 1u);
+            atomicMax(a.counts + 2, lds);
+        } else {
+            a.host_ids[atomicAdd(a.counts + 1, 1u)] = (uint32_t)inst;
+        }
+    }
+    __syncthreads();
+    if (fit) {
+        const uint32_t slot = (uint32_t)s_hdr[0];
+        if (l == 0) a.fit_ids[slot] = (uint32_t)inst;
+        uint16_t *Q = a.lp_in + (size_t)slot * 2 * KP;
+        for (int k = l; k < K; k += kWave) {
+            const uint16_t c = s_cnt[s_rk[k]];
+            Q[k] = c;
+            Q[KP + k] = s_jk[k] == 0 ? c : (uint16_t)0;
+        }
+    }
+}
+
+// One wave per listed instance: x from its staging slot into the record, then the static state row (pack_static_state).
+__global__ __launch_bounds__(kWave) void generate_finish_kernel(DevBatch b, GenArgs a, const uint32_t *ids, int count, const double *stage) {
+    __shared__ double s_v[kGenMaxK];
+    const int slot = (int)blockIdx.x, l = (int)threadIdx.x;
+    if (slot >= count) return;
+    const int inst = (int)ids[slot];
+    unsigned char *rec = b.inst + (size_t)inst * b.L.i_stride;
+    const InstHeader h = *reinterpret_cast<const InstHeader *>(rec);
+    const int K = h.K, M = h.M, MP = b.MP, KP = b.KP;
+    const double *xs = stage + (size_t)slot * KP * MP;
+    double *x = reinterpret_cast<double *>(rec + b.L.i_x);
+    for (int q = l; q < K * MP; q += kWave) x[q] = xs[q];
+    const uint16_t *p = reinterpret_cast<const uint16_t *>(rec + b.L.i_p);
+    const uint32_t *kA = reinterpret_cast<const uint32_t *>(rec + b.L.i_kA), *kB = reinterpret_cast<const uint32_t *>(rec + b.L.i_kB);
+    const uint32_t *elig = reinterpret_cast<const uint32_t *>(rec + b.L.i_elig);
+    const uint8_t *el = a.elig + (size_t)inst * (size_t)a.kmax * (size_t)MP;
+    // fluid_completed_time = max_k Q_k / rate_k, rate_k summed over machine_rj_dict in FILE order (class_FJSSP.py:276-278)
+    for (int k = l; k < K; k += kWave) {
+        const int n = __builtin_popcount(elig[k]);
+        double acc = 0.0;
+        for (int q = 0; q < n; ++q) {
+            const int m = el[(size_t)k * MP + q];
+            acc = acc + xs[(size_t)k * MP + m] * (1.0 / (double)p[(size_t)k * MP + m]);
+        }
+        s_v[k] = acc;
+    }
+    __syncthreads();
+    if (l != 0) return;
+    double *ss = reinterpret_cast<double *>(rec + b.L.i_ss);
+    double best = 0.0;
+    bool lp_ok = true;
+    for (int k = 0; k < K; ++k) {
+        if (!(s_v[k] > 0.0)) lp_ok = false;                  // a failed LP leaves x = 0: no fluid rate
+        const double v = (double)(kA[k] >> 16) / s_v[k];
+        if (k == 0 || v > best) best = v;
+    }
+    ss[7] = best;
+    if (!lp_ok) atomicMin(a.counts + 3, (uint32_t)inst);
+    if (b.variant == FJSP_VARIANT_MO_FJSSP_DISCRETES) {
+        // MO_FJSSP_discretes.py:55-64 static_state_extract; the host's pow(d, 2.0) is d * d here
+        long ns = 0, js = 0;
+        int R = 0;
+        for (int k = 0; k < K; ++k)
+            if ((kB[k] & 0xFFu) == 0u) { ns += (long)(kA[k] >> 16); js += (long)((kB[k] >> 8) & 0xFFu); ++R; }
+        const double N_ave = (double)ns / (double)R, J_ave = (double)js / (double)R;
+        double va = 0.0, vc = 0.0;
+        for (int k = 0; k < K; ++k)
+            if ((kB[k] & 0xFFu) == 0u) { const double d = (double)(kA[k] >> 16) - N_ave; va = va + d * d; }
+        for (int k = 0; k < K; ++k)
+            if ((kB[k] & 0xFFu) == 0u) { const double d = (double)((kB[k] >> 8) & 0xFFu) - J_ave; vc = vc + d * d; }
+        ss[0] = a.g.DDT; ss[1] = (double)M; ss[2] = (double)R; ss[3] = N_ave;
+        ss[4] = sqrt(va / (double)R); ss[5] = J_ave; ss[6] = sqrt(vc / (double)R);
+    }
+}
+
+// The head of the listed instances' records (everything in front of x), side by side: the host route's one read-back.
+__global__ __launch_bounds__(256) void generate_gather_kernel(DevBatch b, const uint32_t *ids, int count, uint4 *out, int words16) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)count * (size_t)words16) return;
+    const int slot = (int)(idx / (size_t)words16), w = (int)(idx % (size_t)words16);
+    out[idx] = reinterpret_cast<const uint4 *>(b.inst + (size_t)ids[slot] * b.L.i_stride)[w];
+}
+
+// Every env as a create leaves it: done, so that a step before the reset is flagged; the row kernels' per-env operation count.
+__global__ __launch_bounds__(256) void generate_mark_done_kernel(DevBatch b, uint8_t *kenv) {
+    const int env = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (env >= b.N) return;
+    env_ptr<EnvScalars>(b, env, 0)->done = 1;
+    if (kenv) kenv[env] = (uint8_t)inst_ptr<const InstHeader>(b, env % b.n_inst, 0)->K;
+}
+
+// ---------------------------------------------------------------------------------------------------- host side
+struct GenState {
+    GenArgs a{};
+    int chunk = 0;                       // staging slots of one LP launch / one host-route round
+    int head16 = 0;                      // 16-byte words of a record in front of x
+    uint8_t *d_kenv = nullptr;
+    double *d_stage = nullptr, *d_stage_host = nullptr;     // [chunk][KP][MP] x of the device route / uploaded from the host route
+    uint4 *d_head = nullptr;             // [chunk][head16]
+    uint32_t *d_lp_err = nullptr;
+    unsigned long long *d_lp_solved = nullptr;
+    // pinned
+    GenInfo *h_info = nullptr;
+    uint32_t *h_counts = nullptr, *h_host_ids = nullptr;
+    double *h_stage = nullptr;
+    uint4 *h_head = nullptr;
+    unsigned long long *h_lp = nullptr;  // [0..1] lp_device_kernel's counters, [2] its error word
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t st_dev = nullptr, st_host = nullptr;       // the two routes run side by side
+    int64_t stats[4] = {0, 0, 0, 0};     // instances, LPs on the device, LPs on the host, device pivots: of the last call
+    double ms[5] = {0, 0, 0, 0, 0};      // generate kernel, LP launches + finish, host route, tables + reset, whole call
+};
+
+void generated_release(fjsp_env *e) {
+    if (!e || !e->gen) return;
+    for (hipEvent_t ev : e->gen->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    if (e->gen->st_dev) (void)hipStreamDestroy(e->gen->st_dev);
+    if (e->gen->st_host) (void)hipStreamDestroy(e->gen->st_host);
+    delete e->gen;
+    e->gen = nullptr;
+}
+
+namespace {
+template <class T>
+bool gen_dev_alloc(fjsp_env *e, size_t bytes, T **d, const char *what) {
+    void *p = nullptr;
+    if (!hip_ok(hipMalloc(&p, std::max<size_t>(bytes, 16)), what)) return false;
+    e->dev_allocs.push_back(p);
+    *d = static_cast<T *>(p);
+    return hip_ok(hipMemset(p, 0, std::max<size_t>(bytes, 16)), "hipMemset");
+}
+template <class T>
+bool gen_host_alloc(fjsp_env *e, size_t bytes, T **h) {
+    void *p = nullptr;
+    if (!hip_ok(hipHostMalloc(&p, std::max<size_t>(bytes, 16), hipHostMallocDefault), "hipHostMalloc")) return false;
+    e->host_allocs.push_back(p);
+    *h = static_cast<T *>(p);
+    return true;
+}
+
+// the checks of generate() (fjsp_instance.cpp)
+int check_params(const fjsp_gen_params &g) {
+    if (g.M <= 0 || g.S <= 0 || g.R_min <= 0 || g.R_max < g.R_min || g.J_min <= 0 || g.J_max < g.J_min ||
+        g.p_min <= 0 || g.p_max < g.p_min || g.N_min <= 0 || g.N_max < g.N_min) {
+        set_error("generator: bad parameters"); return FJSP_E_ARG;
+    }
+    return FJSP_OK;
+}
+
+// check_instance (fjsp_env.hip) on the worst case of the parameters, sizes into sh
+int check_worst_case(const fjsp_gen_params &g, Shape &sh) {
+    const long long K = (long long)g.R_max * g.J_max, nj = (long long)g.R_max * g.N_max, ops = K * g.N_max;
+    if (K > kWave * kMaxKC) { set_error("generated instances can have more than 256 operation types (R_max x J_max)"); return FJSP_E_UNSUPPORTED; }
+    if (g.M > kMaxM) { set_error("more than 32 machines"); return FJSP_E_UNSUPPORTED; }
+    if (nj > 65535) { set_error("generated instances can have more than 65535 jobs (R_max x N_max)"); return FJSP_E_UNSUPPORTED; }
+    if (ops > 65535) { set_error("generated instances can have more than 65535 operations (R_max x J_max x N_max)"); return FJSP_E_UNSUPPORTED; }
+    if (g.J_max > 255) { set_error("more than 255 operations in a kind"); return FJSP_E_UNSUPPORTED; }
+    if (g.p_max > 65535) { set_error("processing time above 65535"); return FJSP_E_UNSUPPORTED; }
+    // the 32-bit clocks: every operation in sequence at the largest processing time; the largest delivery time is every
+    // operation type at p_max with N_max jobs, times DDT / (2 M)
+    const double due = std::fabs((double)K * (double)g.p_max * (double)g.N_max * g.DDT / (double)(g.M * 2));
+    const double clock = (double)ops * (double)g.p_max;
+    if (!(clock + due <= 2147483647.0) || !((double)g.N_max * (clock + due) <= 2147483647.0)) {
+        set_error("generated instances can be too long for the kernels' 32-bit clocks: (operations x max processing time + "
+                  "largest delivery time) x jobs per kind must stay below 2^31");
+        return FJSP_E_UNSUPPORTED;
+    }
+    sh.K = (int)K; sh.M = g.M; sh.J = (int)nj; sh.R = g.R_max; sh.S = 1;
+    sh.single_job = g.N_min == 1 && g.N_max == 1 && g.R_max <= 255;
+    return FJSP_OK;
+}
+
+uint64_t gen_hash(const fjsp_gen_params &g, int n_inst, uint64_t seed_base, int class_fjsp) {
+    uint64_t h = 1469598103934665603ULL;
+    auto mix = [&](const void *p, size_t n) {
+        const unsigned char *c = static_cast<const unsigned char *>(p);
+        for (size_t i = 0; i < n; ++i) h = (h ^ c[i]) * 1099511628211ULL;
+    };
+    // (class_fjsp: SO_DFJSP runs as variant SO_FJSSP with other due dates, so the variant alone does not tell the two apart)
+    const int32_t iv[12] = {g.R_min, g.R_max, g.J_min, g.J_max, g.M, g.p_min, g.p_max, g.N_min, g.N_max, g.S, n_inst, class_fjsp};
+    const double dv[3] = {g.DDT, g.t_si_min, g.t_si_max};
+    mix(iv, sizeof(iv)); mix(dv, sizeof(dv)); mix(&seed_base, sizeof(seed_base));
+    return h;
+}
+
+double step_bytes_mean(const fjsp_env *e) {        // step_bytes_of (fjsp_env.hip) over what the device generated
+    const DevBatch &b = e->b;
+    const GenState &G = *e->gen;
+    const double per_k = 28.0 + (b.single_job ? 1.0 : 4.0) + (b.MP > 8 ? 4.0 : 0.0) + (b.single_job ? 0.0 : 128.0);
+    const double M = (double)G.a.g.M;
+    const double gather = b.single_job ? M * 18.0 + 1.0 : M * 26.0 + 8.0;
+    double bytes = 0.0;
+    for (int i = 0; i < b.n_inst; ++i)
+        bytes += G.h_info[i].K * per_k + G.h_info[i].nj * 16.0 + M * 16.0 + 304.0 + gather + 2.0 + b.state_size * 8.0 + 9.0;
+    return bytes;
+}
+
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
+// The LPs of host_ids[first, first + n) on host threads, x into G.h_stage[slot]; 0 or the first failing slot + 1
+int solve_on_host(fjsp_env *e, int n) {
+    GenState &G = *e->gen;
+    const DevBatch &b = e->b;
+    const size_t KP = (size_t)b.KP, MP = (size_t)b.MP, head = (size_t)G.head16 * 16;
+    int n_threads = e->arr.lp_threads > 0 ? e->arr.lp_threads : std::min((int)std::thread::hardware_concurrency(), 16);
+    n_threads = std::max(1, std::min(n_threads, n));
+    std::atomic<int> next(0), fail(0);
+    auto work = [&]() {
+        std::vector<int> Jr, p, Q, now;
+        std::vector<double> x;
+        for (;;) {
+            const int s = next.fetch_add(1);
+            if (s >= n) break;
+            const unsigned char *rec = reinterpret_cast<const unsigned char *>(G.h_head) + (size_t)s * head;
+            const InstHeader h = *reinterpret_cast<const InstHeader *>(rec);
+            const uint32_t *kA = reinterpret_cast<const uint32_t *>(rec + b.L.i_kA), *kB = reinterpret_cast<const uint32_t *>(rec + b.L.i_kB);
+            const uint16_t *p16 = reinterpret_cast<const uint16_t *>(rec + b.L.i_p);
+            Jr.assign((size_t)h.R, 0); p.assign((size_t)h.K * h.M, 0); Q.assign((size_t)h.K, 0); now.assign((size_t)h.K, 0);
+            x.assign((size_t)h.K * h.M, 0.0);
+            int r = -1;
+            for (int k = 0; k < h.K; ++k) {
+                const int j = (int)(kB[k] & 0xFFu);
+                if (j == 0) { ++r; Jr[(size_t)r] = (int)((kB[k] >> 8) & 0xFFu); }
+                Q[(size_t)k] = (int)(kA[k] >> 16);
+                now[(size_t)k] = j == 0 ? Q[(size_t)k] : 0;
+                for (int m = 0; m < h.M; ++m) p[(size_t)k * h.M + m] = p16[(size_t)k * MP + m];
+            }
+            double obj = 0.0;
+            double *out = G.h_stage + (size_t)s * KP * MP;
+            std::memset(out, 0, KP * MP * 8);
+            if (solve_fluid_lp(h.R, h.M, Jr.data(), p.data(), Q.data(), now.data(), x.data(), &obj) != 0) {
+                int zero = 0;
+                fail.compare_exchange_strong(zero, s + 1);
+                continue;
+            }
+            for (int k = 0; k < h.K; ++k)
+                for (int m = 0; m < h.M; ++m) out[(size_t)k * MP + m] = x[(size_t)k * h.M + m];
+        }
+    };
+    if (n_threads == 1) work();
+    else {
+        std::vector<std::thread> th;
+        th.reserve((size_t)n_threads);
+        try {
+            for (int t = 0; t < n_threads; ++t) th.emplace_back(work);
+        } catch (const std::system_error &) {       // no more threads to be had: the calling thread takes the rest
+            work();
+        }
+        for (auto &t : th) t.join();
+    }
+    return fail.load();
+}
+
+int fail_generate(fjsp_env *e, int rc, const std::string &msg) {
+    e->gen_failed = true;
+    set_error(msg);
+    return rc;
+}
+
+// The whole refill: records, LPs, tables, reset.  Synchronous; on the handle's device.
+int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::string &call) {
+    GenState &G = *e->gen;
+    DevBatch &b = e->b;
+    const size_t N = (size_t)b.N, KP = (size_t)b.KP, MP = (size_t)b.MP, n_inst = (size_t)b.n_inst;
+    const auto t_call = Clock::now();
+    HIP_TRY(hipDeviceSynchronize());         // steps still queued on any stream read the records this call rewrites
+    e->gen_failed = true;                    // until the call has gone through
+    G.a.seed_base = seed_base;
+    b.rng_seed = rng_seed;
+    std::memset(G.stats, 0, sizeof(G.stats));
+    std::memset(G.ms, 0, sizeof(G.ms));
+    hipStream_t st = G.st_dev, sh = G.st_host;
+    HIP_TRY(hipMemsetAsync(b.inst, 0, n_inst * b.L.i_stride, st));
+    HIP_TRY(hipMemsetAsync(b.envs, 0, N * b.L.e_stride, st));       // the draw counters too: the env streams start over
+    HIP_TRY(hipMemsetAsync(G.a.counts, 0, 12, st));
+    HIP_TRY(hipMemsetAsync(G.a.counts + 3, 0xFF, 4, st));
+    HIP_TRY(hipMemsetAsync(G.d_lp_solved, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(G.d_lp_err, 0, 8, st));
+    if (e->sched.rec) HIP_TRY(hipMemsetAsync(e->sched.rec, 0, (size_t)e->sched.cap * N * sizeof(uint4), st));
+    HIP_TRY(hipEventRecord(G.ev[0], st));
+    if (launch(generate_pack_kernel, dim3((unsigned)n_inst), dim3(kWave), 0, st, b, G.a) != 0) { set_error("generate_pack_kernel launch failed"); return FJSP_E_HIP; }
+    HIP_TRY(hipEventRecord(G.ev[1], st));
+    // the call's one read-back before the LPs: status words, sizes, the two lists' lengths, the host list
+    HIP_TRY(hipMemcpyAsync(G.h_info, G.a.info, n_inst * sizeof(GenInfo), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(G.h_host_ids, G.a.host_ids, n_inst * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int M = G.a.g.M;
+    for (size_t i = 0; i < n_inst; ++i) {
+        const GenInfo &f = G.h_info[i];
+        const std::string who = "instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ")";
+        if (f.status == FJSP_E_UNSUPPORTED)
+            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
+        if (f.status != 0)
+            return fail_generate(e, f.status, call + ": " + who + ": a draw left the record's fields (internal error)");
+        if (f.ops > e->ops_max || (size_t)f.lds != lp_device_lds_bytes(f.K, M, f.nx, f.R, b.MP))
+            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": sizes disagree with the host's (internal error)");
+    }
+    const int n_fit = (int)G.h_counts[0], n_host = (int)G.h_counts[1];
+    if ((size_t)n_fit + (size_t)n_host != n_inst) return fail_generate(e, FJSP_E_HIP, call + ": the LP lists do not cover the instances (internal error)");
+    if (e->plan.lp_device_forced == 1 && n_host > 0) {
+        uint32_t i = G.h_host_ids[0];
+        for (int q = 1; q < n_host; ++q) i = std::min(i, G.h_host_ids[q]);
+        const GenInfo &f = G.h_info[i];
+        return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": FJSP_LP_IMPL=device, but the order-0 tableau of instance " + std::to_string(i) +
+                             " (seed " + std::to_string(seed_base + i) + ") does not fit: " + std::to_string(f.lds) + " bytes of LDS (limit " +
+                             std::to_string(kLpLdsLimit) + "), " + std::to_string(f.nx + 1 + (2 * f.K + M - f.R) + 1) + " columns (limit " +
+                             std::to_string(lp_device_max_columns()) + ")");
+    }
+    for (size_t i = 0; i < n_inst; ++i) e->inst_K[i] = G.h_info[i].K;
+    e->step_bytes = (int64_t)(step_bytes_mean(e) / (double)n_inst + 0.5);
+    // ---- device route: bounded chunks of staging slots, each an LP launch and the finish of its instances
+    const size_t lds = G.h_counts[2];
+    for (int c0 = 0; c0 < n_fit; c0 += G.chunk) {
+        const int n = std::min(G.chunk, n_fit - c0);
+        if (launch_lp_device(b, nullptr, n, G.a.fit_ids + c0, G.a.lp_in + (size_t)c0 * 2 * KP, G.d_stage, G.d_lp_err, G.d_lp_solved, lds, st) != 0 ||
+            launch(generate_finish_kernel, dim3((unsigned)n), dim3(kWave), 0, st, b, G.a, (const uint32_t *)(G.a.fit_ids + c0), n, (const double *)G.d_stage) != 0) {
+            set_error("lp_device_kernel / generate_finish_kernel launch failed"); return FJSP_E_HIP;
+        }
+    }
+    HIP_TRY(hipEventRecord(G.ev[2], st));
+    // ---- host route, while the device works on its list
+    const auto t_host = Clock::now();
+    for (int c0 = 0; c0 < n_host; c0 += G.chunk) {
+        const int n = std::min(G.chunk, n_host - c0);
+        const size_t words = (size_t)n * (size_t)G.head16;
+        if (launch(generate_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, sh, b, (const uint32_t *)(G.a.host_ids + c0), n, G.d_head, G.head16) != 0) {
+            set_error("generate_gather_kernel launch failed"); return FJSP_E_HIP;
+        }
+        HIP_TRY(hipMemcpyAsync(G.h_head, G.d_head, words * 16, hipMemcpyDeviceToHost, sh));
+        HIP_TRY(hipStreamSynchronize(sh));
+        const int bad = solve_on_host(e, n);
+        if (bad) {
+            const uint32_t i = G.h_host_ids[c0 + bad - 1];
+            return fail_generate(e, FJSP_E_LP, call + ": the fluid LP of instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ") failed");
+        }
+        HIP_TRY(hipMemcpyAsync(G.d_stage_host, G.h_stage, (size_t)n * KP * MP * 8, hipMemcpyHostToDevice, sh));
+        if (launch(generate_finish_kernel, dim3((unsigned)n), dim3(kWave), 0, sh, b, G.a, (const uint32_t *)(G.a.host_ids + c0), n, (const double *)G.d_stage_host) != 0) {
+            set_error("generate_finish_kernel launch failed"); return FJSP_E_HIP;
+        }
+        HIP_TRY(hipStreamSynchronize(sh));       // h_stage and h_head are reused by the next round
+    }
+    G.ms[2] = n_host ? ms_since(t_host) : 0.0;
+    // ---- the fluid tables, one reset of every env (publishes i_obs0), every env done again: as upload_batch leaves them
+    const dim3 gN((unsigned)((N + 255) / 256));
+    if (launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, G.d_kenv) != 0 || launch_fluid_tables(b, st) != 0 ||
+        launch_reset(b, nullptr, nullptr, st) != 0 || launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, (uint8_t *)nullptr) != 0) {
+        set_error("fluid_tables_kernel / reset_kernel launch failed"); return FJSP_E_HIP;
+    }
+    HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(G.h_lp, G.d_lp_solved, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(G.h_lp + 2, G.d_lp_err, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(G.ev[3], st));
+    HIP_TRY(hipDeviceSynchronize());
+    float f01 = 0.f, f12 = 0.f, f23 = 0.f;
+    (void)hipEventElapsedTime(&f23, G.ev[2], G.ev[3]);
+    (void)hipEventElapsedTime(&f01, G.ev[0], G.ev[1]);
+    (void)hipEventElapsedTime(&f12, G.ev[1], G.ev[2]);
+    G.ms[0] = f01; G.ms[1] = f12; G.ms[3] = f23;
+    if (G.h_counts[3] != 0xFFFFFFFFu || (uint32_t)G.h_lp[2] != 0u) {
+        const uint32_t i = G.h_counts[3];
+        return fail_generate(e, FJSP_E_LP, i != 0xFFFFFFFFu ? call + ": the fluid LP of instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ") failed"
+                                                            : call + ": a fluid LP failed on the device (code " + std::to_string((uint32_t)G.h_lp[2]) + ")");
+    }
+    G.stats[0] = (int64_t)n_inst; G.stats[1] = n_fit; G.stats[2] = n_host; G.stats[3] = (int64_t)G.h_lp[1];
+    e->inst_hash = gen_hash(G.a.g, b.n_inst, seed_base, G.a.class_fjsp);
+    e->gen_failed = false;
+    G.ms[4] = ms_since(t_call);
+    return FJSP_OK;
+}
+}  // namespace
+}  // namespace fjsp
+
+using namespace fjsp;
+
+extern "C" {
+int fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
+                              uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
+    if (!prm || !out || n_inst <= 0 || n_envs <= 0) { set_error("fjsp_env_create_generated: bad arguments"); return FJSP_E_ARG; }
+    if (family < -1 || family > 1) { set_error("fjsp_env_create_generated: family must be -1, 0 or 1"); return FJSP_E_ARG; }
+    const bool class_fjsp = variant == FJSP_VARIANT_SO_DFJSP;
+    if (variant == FJSP_VARIANT_MO_DFJSP) {
+        set_error("fjsp_env_create_generated: MO_DFJSP needs machine data and the per-env fluid tables; the generator has neither (use fjsp_env_create)");
+        return FJSP_E_UNSUPPORTED;
+    }
+    if (class_fjsp) variant = FJSP_VARIANT_SO_FJSSP;
+    if (variant != FJSP_VARIANT_SO_FJSSP && variant != FJSP_VARIANT_SO_SFJSP && variant != FJSP_VARIANT_MO_FJSSP_DISCRETES) {
+        set_error("fjsp_env_create_generated: unknown variant"); return FJSP_E_ARG;
+    }
+    int rc = check_params(*prm);
+    if (rc != FJSP_OK) return rc;
+    if (prm->S != 1) {
+        set_error("fjsp_env_create_generated: one order only (S == 1): order arrivals need the per-env fluid tables (use fjsp_env_create)");
+        return FJSP_E_UNSUPPORTED;
+    }
+    Shape sh;
+    if ((rc = check_worst_case(*prm, sh)) != FJSP_OK) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("no HIP device visible: the environment kernels need an MI355X (there is no CPU path)");
+        return FJSP_E_HIP;
+    }
+    if (device < 0 || device >= ndev) { set_error("fjsp_env_create_generated: device index out of range"); return FJSP_E_ARG; }
+    DeviceGuard guard(device);
+
+    std::unique_ptr<fjsp_env, void (*)(fjsp_env *)> e(new fjsp_env(), fjsp_env_destroy);
+    e->device = device; e->src = nullptr; e->first = 0;
+    DevBatch &b = e->b;
+    if ((rc = plan_batch(b, e->plan, sh, n_inst, n_envs, variant, rng_seed, family)) != FJSP_OK) return rc;
+    // src stays null: only the order-arrival services (fjsp_arrivals.hip) read it, and only multi-order batches reach them
+    if (b.mord) { set_error("fjsp_env_create_generated: internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
+    if (lp_device_max_columns() != kLpMaxColumns) { set_error("fjsp_env_create_generated: internal error (device LP width)"); return FJSP_E_UNSUPPORTED; }
+    e->inst_K.assign((size_t)n_inst, 0); e->inst_M.assign((size_t)n_inst, sh.M);
+    e->ops_max = sh.K * prm->N_max;
+
+    e->gen = new GenState();
+    GenState &G = *e->gen;
+    const size_t N = (size_t)n_envs, NI = (size_t)n_inst, KP = (size_t)b.KP, MP = (size_t)b.MP;
+    G.a.g = *prm; G.a.class_fjsp = class_fjsp ? 1 : 0; G.a.allow_device = e->plan.lp_device_forced == 0 ? 0 : 1;
+    G.a.kmax = sh.K; G.a.RP = sh.R;
+    G.chunk = (int)std::min<size_t>(NI, 1024);
+    G.head16 = (int)((b.L.i_x + 15) / 16);
+    if (!gen_dev_alloc(e.get(), NI * b.L.i_stride, &b.inst, "hipMalloc instance slab") ||
+        !gen_dev_alloc(e.get(), N * b.L.e_stride, &b.envs, "hipMalloc env slab") ||
+        !gen_dev_alloc(e.get(), N + 16, &e->d_done_scratch, "hipMalloc scratch") ||
+        !gen_dev_alloc(e.get(), NI * (size_t)sh.K * MP, &G.a.elig, "hipMalloc eligible lists") ||
+        !gen_dev_alloc(e.get(), NI * sizeof(GenInfo), &G.a.info, "hipMalloc generator status") ||
+        !gen_dev_alloc(e.get(), 16, &G.a.counts, "hipMalloc list lengths") ||
+        !gen_dev_alloc(e.get(), NI * 4, &G.a.fit_ids, "hipMalloc LP list") || !gen_dev_alloc(e.get(), NI * 4, &G.a.host_ids, "hipMalloc LP list") ||
+        !gen_dev_alloc(e.get(), NI * 2 * KP * 2, &G.a.lp_in, "hipMalloc LP inputs") ||
+        !gen_dev_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.d_stage, "hipMalloc LP solutions") ||
+        !gen_dev_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.d_stage_host, "hipMalloc LP solutions") ||
+        !gen_dev_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.d_head, "hipMalloc record heads") ||
+        !gen_dev_alloc(e.get(), 8, &G.d_lp_err, "hipMalloc LP error word") || !gen_dev_alloc(e.get(), 16, &G.d_lp_solved, "hipMalloc LP counters") ||
+        (b.grp && !gen_dev_alloc(e.get(), N, &G.d_kenv, "hipMalloc K table")) ||
+        !gen_host_alloc(e.get(), NI * sizeof(GenInfo), &G.h_info) || !gen_host_alloc(e.get(), 16, &G.h_counts) ||
+        !gen_host_alloc(e.get(), NI * 4, &G.h_host_ids) || !gen_host_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.h_stage) ||
+        !gen_host_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.h_head) || !gen_host_alloc(e.get(), 32, &G.h_lp))
+        return FJSP_E_HIP;
+    b.kenv = G.d_kenv;
+    for (hipEvent_t &ev : G.ev) HIP_TRY(hipEventCreate(&ev));
+    HIP_TRY(hipStreamCreateWithFlags(&G.st_dev, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&G.st_host, hipStreamNonBlocking));
+    if ((rc = regenerate(e.get(), seed_base, rng_seed, "fjsp_env_create_generated")) != FJSP_OK) return rc;
+    *out = e.release();
+    return FJSP_OK;
+}
+
+int fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed) {
+    if (!e) { set_error("fjsp_env_regenerate: null env"); return FJSP_E_ARG; }
+    if (!e->gen) { set_error("fjsp_env_regenerate: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    DeviceGuard guard(e->device);
+    return regenerate(e, seed_base, rng_seed, "fjsp_env_regenerate");
+}
+
+int fjsp_env_generated_stats(const fjsp_env *e, int64_t out[4]) {
+    if (!e || !out) { set_error("fjsp_env_generated_stats: null argument"); return FJSP_E_ARG; }
+    if (!e->gen) { set_error("fjsp_env_generated_stats: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    for (int q = 0; q < 4; ++q) out[q] = e->gen->stats[q];
+    return FJSP_OK;
+}
+
+int fjsp_env_generated_times(const fjsp_env *e, double out_ms[5]) {
+    if (!e || !out_ms) { set_error("fjsp_env_generated_times: null argument"); return FJSP_E_ARG; }
+    if (!e->gen) { set_error("fjsp_env_generated_times: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    for (int q = 0; q < 5; ++q) out_ms[q] = e->gen->ms[q];
+    return FJSP_OK;
+}
+
+int fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr, int32_t *p, int32_t *elig_n, int32_t *elig_list,
+                           int32_t *count, int32_t *arrive, int32_t *delivery, double *ddt, double *x) {
+    if (!e || i < 0 || i >= e->b.n_inst) { set_error("fjsp_env_instance_read: bad arguments"); return FJSP_E_ARG; }
+    if (!e->gen) { set_error("fjsp_env_instance_read: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    if (e->gen_failed) { set_error("fjsp_env_instance_read: the last fjsp_env_regenerate of this batch failed"); return FJSP_E_STATE; }
+    DeviceGuard guard(e->device);
+    const DevBatch &b = e->b;
+    const GenState &G = *e->gen;
+    const size_t MP = (size_t)b.MP;
+    std::vector<unsigned char> rec(b.L.i_stride), el((size_t)G.a.kmax * MP);
+    GenInfo f;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(rec.data(), b.inst + (size_t)i * b.L.i_stride, rec.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(el.data(), G.a.elig + (size_t)i * el.size(), el.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&f, G.a.info + i, sizeof(f), hipMemcpyDeviceToHost));
+    const InstHeader h = *reinterpret_cast<const InstHeader *>(rec.data());
+    const uint32_t *kA = reinterpret_cast<const uint32_t *>(rec.data() + b.L.i_kA), *kB = reinterpret_cast<const uint32_t *>(rec.data() + b.L.i_kB);
+    const uint32_t *em = reinterpret_cast<const uint32_t *>(rec.data() + b.L.i_elig);
+    const uint16_t *p16 = reinterpret_cast<const uint16_t *>(rec.data() + b.L.i_p);
+    const double *xr = reinterpret_cast<const double *>(rec.data() + b.L.i_x);
+    if (dims) { dims[0] = h.R; dims[1] = h.M; dims[2] = h.K; dims[3] = 1; dims[4] = h.njobs; dims[5] = h.njobs; }
+    int r = -1;
+    for (int k = 0; k < h.K; ++k) {
+        if ((kB[k] & 0xFFu) == 0u) {
+            ++r;
+            if (Jr) Jr[r] = (int32_t)((kB[k] >> 8) & 0xFFu);
+            if (count) count[r] = (int32_t)(kA[k] >> 16);
+        }
+        if (elig_n) elig_n[k] = __builtin_popcount(em[k]);
+        for (int m = 0; m < h.M; ++m) {
+            if (p) p[(size_t)k * h.M + m] = p16[(size_t)k * MP + m];
+            if (elig_list) elig_list[(size_t)k * h.M + m] = el[(size_t)k * MP + m];
+            if (x) x[(size_t)k * h.M + m] = xr[(size_t)k * MP + m];
+        }
+    }
+    if (arrive) arrive[0] = 0;
+    if (delivery) delivery[0] = f.delivery;
+    if (ddt) *ddt = G.a.g.DDT;
+    return FJSP_OK;
+}
+}  // extern "C"

@@ -51,7 +51,18 @@ class BatchedEnv(object):
 
     variant = None
 
-    def __init__(self, instance_set, n_envs=None, first=0, n_inst=None, device=0, rng_seed=0, first_env=0):
+    def __init__(self, instance_set, n_envs=None, first=0, n_inst=None, device=0, rng_seed=0, first_env=0, seed_base=0):
+        """instance_set: an InstanceSet, or the generator's parameters (instances.GenParams): the batch's instances are
+        then generated and solved on the device from seed_base (EnvBatch.generated; n_envs is needed), and
+        ``self.batch.regenerate(seed_base)`` refills them in place.  One order only; the library refuses MO_DFJSP."""
+        if isinstance(instance_set, _inst.GenParams):
+            if n_envs is None:
+                raise ValueError("n_envs is needed with generator parameters")
+            self.batch = EnvBatch.generated(instance_set, n_envs, seed_base, n_inst=n_inst, variant=self.variant, device=device,
+                                            rng_seed=rng_seed, first_env=first_env)
+            self.N, self.device = self.batch.N, self.batch.device
+            self._staging()
+            return
         n_inst = len(instance_set) - first if n_inst is None else n_inst
         n_envs = n_inst if n_envs is None else n_envs
         self.batch = EnvBatch(instance_set, n_envs, first=first, n_inst=n_inst, variant=self.variant,

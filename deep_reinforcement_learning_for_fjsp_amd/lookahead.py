@@ -91,6 +91,10 @@ def make_branch(batch, n_candidates):
     """An EnvBatch of n_candidates x N envs on the source batch's instances, variant and kernel family (asked for
     explicitly: the record layouts of the two families differ, and the snapshot fingerprint includes the family)."""
     n = check_branch_shape(batch.N, batch.n_inst, n_candidates)
+    if batch.instances is None:         # a generated source (EnvBatch.generated): the same parameters and seeds once more
+        return EnvBatch.generated(batch.gen_params, n, batch.seed_base, n_inst=batch.n_inst, variant=batch.variant,
+                                  device=batch.device_index, rng_seed=batch.rng_seed, first_env=batch.first_env,
+                                  family=batch.kernel_family)
     return EnvBatch(batch.instances, n, first=batch.first, n_inst=batch.n_inst, variant=batch.variant,
                     device=batch.device_index, rng_seed=batch.rng_seed, first_env=batch.first_env,
                     kernel_family=batch.kernel_family)
@@ -128,7 +132,7 @@ def ops_per_env(batch):
     """i64[N] device tensor: the operations of every env's instance = the steps of its episode."""
     ops = []
     for i in range(batch.n_inst):
-        a = batch.instances.arrays(batch.first + i)
+        a = batch.instance_arrays(i)
         ops.append(int((np.asarray(a.count).reshape(a.S, a.R) * np.asarray(a.Jr)[None, :]).sum()))
     ops = np.asarray(ops, np.int64)
     return torch.as_tensor(ops[np.arange(batch.N) % batch.n_inst], device=batch.device)

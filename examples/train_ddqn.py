@@ -4,6 +4,11 @@ on SO_SFJSP environments (makespan reward, 20 flat actions); every round plays o
 random instances (generated_new_environment, DDQN.py:99-104: M in [3, 8]) and one greedy test episode.
 
     python examples/train_ddqn.py --envs 1024 --rounds 5
+    python examples/train_ddqn.py --envs 1024 --rounds 5 --device-instances
+
+--device-instances generates each round's instances (and solves their fluid LPs) on the device, in place.  A generated
+env has ONE parameter set, so there a round's instances share M (3 + round % 6: one live env per M) and DDT = 1.0,
+where the default path draws both per instance.
 """
 import argparse
 import json
@@ -18,6 +23,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--device-instances", action="store_true",
+                    help="regenerate the training instances on the device every round (one M and DDT per round)")
     args = ap.parse_args()
     import torch
     from deep_reinforcement_learning_for_fjsp_amd import instances as fi
@@ -25,10 +32,19 @@ def main():
     from deep_reinforcement_learning_for_fjsp_amd.agents.DDQN.DDQN import DDQN
 
     test_env = BatchedSOSFJSP(fi.InstanceSet(64).generate_range(800000, fi.bench_10x5_params()).solve_fluid(), rng_seed=1)
-    rounds = [0]
+    rounds, live = [0], {}
 
     def make_train_env():
         rounds[0] += 1
+        if args.device_instances:
+            M = 3 + rounds[0] % 6
+            if M not in live:
+                prm = fi.GenParams(R_min=3, R_max=12, J_min=3, J_max=5, M=M, p_min=40, p_max=400, N_min=1, N_max=2, S=1, DDT=1.0,
+                                   t_si_min=100.0, t_si_max=200.0)
+                live[M] = BatchedSOSFJSP(prm, args.envs, seed_base=5_000_000 * rounds[0], rng_seed=rounds[0])
+            else:
+                live[M].batch.regenerate(5_000_000 * rounds[0], rng_seed=rounds[0])
+            return live[M]
         s = fi.InstanceSet(args.envs)
         for i in range(args.envs):
             seed = 5_000_000 * rounds[0] + i

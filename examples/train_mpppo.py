@@ -6,6 +6,7 @@ rewards of the weighted ones (:159-164), periodic evolution towards the best pol
 (:192-205).
 
     python examples/train_mpppo.py --envs 1024 --epochs 3
+    python examples/train_mpppo.py --envs 1024 --epochs 3 --device-instances    # one env, refilled on the device per epoch
 """
 import argparse
 import json
@@ -20,6 +21,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--device-instances", action="store_true",
+                    help="keep one training env and regenerate its instances (and their fluid LPs) on the device every epoch, "
+                         "instead of a new InstanceSet + env per epoch; the instances are the same")
     args = ap.parse_args()
     import torch
     from deep_reinforcement_learning_for_fjsp_amd import instances as fi
@@ -29,8 +33,16 @@ def main():
     test_env = BatchedMOFJSSP(fi.InstanceSet(64).generate_range(900000, fi.bench_10x5_params()).solve_fluid(), rng_seed=1)
     epoch = [0]
 
+    live = []
+
     def make_train_env():
         epoch[0] += 1
+        if args.device_instances:
+            if not live:
+                live.append(BatchedMOFJSSP(fi.bench_10x5_params(), args.envs, seed_base=10_000_000 * epoch[0], rng_seed=epoch[0]))
+            else:
+                live[0].batch.regenerate(10_000_000 * epoch[0], rng_seed=epoch[0])
+            return live[0]
         s = fi.InstanceSet(args.envs).generate_range(10_000_000 * epoch[0], fi.bench_10x5_params()).solve_fluid()
         return BatchedMOFJSSP(s, rng_seed=epoch[0])
 
@@ -44,7 +56,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(json.dumps({"workload": "MPPPO, 5 policies, %d MO_FJSSP_discretes 10x5 envs per epoch" % args.envs,
-                      "epochs": args.epochs, "s_per_epoch": dt / args.epochs,
+                      "epochs": args.epochs, "device_instances": bool(args.device_instances), "s_per_epoch": dt / args.epochs,
                       "test_objectives_last_epoch": {str(p): {"completion_time": c, "tardiness": t} for p, (c, t) in hist[-1].items()},
                       "completion_min": agent.completion_min, "tardiness_min": agent.tardiness_min}))
 

@@ -158,6 +158,38 @@ int  fjsp_env_create(const fjsp_instances *s, int32_t first, int32_t n_inst, int
  * not read for 0 and 1: a batch that must match another one's family (a snapshot's fingerprint) is made this way. */
 int  fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_inst, int32_t n_envs, int32_t variant,
                             int32_t device, uint64_t rng_seed, int32_t family, fjsp_env **out);
+/* A batch whose instances are generated, and their fluid LPs solved, ON THE DEVICE (csrc/fjsp_generate.hip): instance i is
+ * what fjsp_instances_generate(seed_base + i, prm) + fjsp_instances_solve_fluid + fjsp_env_create_family give, record
+ * for record (x bit for bit; DEVIATION: the two pow-derived entries of the MO_FJSSP_discretes static state are d * d on
+ * the device, as the observation's already are).  The handle owns its instance records, sized from the parameters' worst
+ * case (R_max x J_max operation types, R_max x N_max jobs), so kernel family, builds and schedule capacity never change:
+ * fjsp_env_regenerate refills the records in place from other seeds -- no host instance set, no instance upload, no device allocation --
+ * and leaves every env as a create leaves it (done; env random streams restarted from rng_seed; recorded schedule cleared).
+ * One order only: prm->S > 1 and FJSP_VARIANT_MO_DFJSP are FJSP_E_UNSUPPORTED (they need the per-env fluid tables and
+ * machine data).  Bad parameters (the checks of fjsp_instances_generate), an unknown variant, n_inst <= 0 or n_envs <= 0:
+ * FJSP_E_ARG; a worst case outside the kernels' limits: FJSP_E_UNSUPPORTED; all before the first HIP call.
+ * An LP whose tableau fits the LDS of a CU is solved by the device simplex, the others by the host's on
+ * fjsp_env_set_lp_threads threads; FJSP_LP_IMPL=host sends all to the host, =device refuses (FJSP_E_UNSUPPORTED) when one
+ * does not fit.  The two are pivot for pivot the same, so x does not depend on the route.
+ * A failing instance (SO_DFJSP: a machine without eligible operation, FJSP_E_UNSUPPORTED; an LP failure, FJSP_E_LP) is
+ * named with its seed in fjsp_last_error; after a failed fjsp_env_regenerate reset, step, rollout, the policy launches, read,
+ * schedule, snapshots, fjsp_env_fluid_tables and fjsp_env_instance_read return FJSP_E_STATE until a later one succeeds.  fjsp_env_regenerate on any other handle: FJSP_E_STATE.  Both synchronise.
+ * Snapshots: the fingerprint of such a handle is (prm, n_inst, seed_base, SO_DFJSP or not), so a snapshot taken before a regenerate onto
+ * other seeds is refused after it. */
+int  fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
+                               uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out);
+int  fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed);
+/* Of the last create_generated / regenerate: out[0] instances, [1] LPs solved on the device, [2] on the host, [3] pivots
+ * of the device simplex.  fjsp_env_generated_times: milliseconds of its parts -- the generate kernel, the LP launches with
+ * their finish kernels, the host route, fluid tables + reset -- and of the whole call.  [0], [1], [3] are HIP-event times on the device route's
+ * stream; [2] and [4] are host wall clock, and the host route runs beside the device's LPs, so [2] overlaps [1]: the parts
+ * do not add up to [4].  (Five clock readings and four event records per call; tools/time_regenerate.py reads them.) */
+int  fjsp_env_generated_stats(const fjsp_env *e, int64_t out[4]);
+int  fjsp_env_generated_times(const fjsp_env *e, double out_ms[5]);
+/* Instance i of a generated handle, read back from the device: dims as fjsp_instances_dims, the arrays as
+ * fjsp_instances_get; every output nullable.  Synchronises. */
+int  fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr, int32_t *p, int32_t *elig_n,
+                            int32_t *elig_list, int32_t *count, int32_t *arrive, int32_t *delivery, double *ddt, double *x);
 void fjsp_env_destroy(fjsp_env *e);
 int  fjsp_env_num_envs(const fjsp_env *e);
 int  fjsp_env_state_size(const fjsp_env *e);   /* 20 (SO_FJSSP) / 18 (SO_SFJSP) / 25 (MO_FJSSP_discretes) / 30 (MO_DFJSP) */

@@ -1,0 +1,368 @@
+"""GPU: batches whose instances are generated and solved on the device (EnvBatch.generated / regenerate,
+csrc/fjsp_generate.hip) against the host path -- InstanceSet.generate_range + solve_fluid + EnvBatch -- on the same
+seeds: the same instances, fluid tables and episodes, bit for bit.  Both handles then run the same kernels, so the one
+tolerance is the MO_FJSSP_discretes static state's two pow-derived entries (host pow(d, 2.0), device d * d)."""
+import numpy as np
+import pytest
+
+from tests import helpers as H
+from tests.test_generate_host import empty_machine, replay
+
+pytestmark = pytest.mark.gpu
+
+INT_KEYS = ("Jr", "p", "elig_n", "elig_list", "count", "arrive", "delivery")
+MO_STATIC_POW = (4, 6)        # N_std, J_std of static_state_extract (MO_FJSSP_discretes.py:59-63)
+
+
+@pytest.fixture(scope="module")
+def torch_gpu(built):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch
+
+
+def gp(**kw):
+    from deep_reinforcement_learning_for_fjsp_amd._capi import GenParams
+    d = dict(p_min=1, p_max=20, N_min=1, N_max=1, S=1, DDT=1.0, t_si_min=100.0, t_si_max=200.0)
+    d.update(kw)
+    return GenParams(**d)
+
+
+def bench():
+    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
+    return fi.bench_10x5_params()
+
+
+def host_set(prm, n, seed):
+    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
+    return fi.InstanceSet(n).generate_range(seed, prm).solve_fluid()
+
+
+def pair(prm, n, seed, variant=0, family=None, n_inst=None, rng_seed=5):
+    """G: generated on the device; H: the host path on the same seeds, variant, rng_seed and family."""
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    n_inst = n if n_inst is None else n_inst
+    G = EnvBatch.generated(prm, n, seed, n_inst=n_inst, variant=variant, rng_seed=rng_seed, family=-1 if family is None else family)
+    Hb = EnvBatch(host_set(prm, n_inst, seed), n, variant=variant, rng_seed=rng_seed, kernel_family=family)
+    return G, Hb
+
+
+def same_instance(a, b, what):
+    assert (a.R, a.M, a.K, a.S) == (b.R, b.M, b.K, b.S), what
+    for key in INT_KEYS:
+        assert np.array_equal(getattr(a, key), getattr(b, key)), (what, key)
+    assert a.ddt == b.ddt, what
+    assert np.array_equal(H.bits(a.x), H.bits(b.x)), (what, "x")
+
+
+def tableau_fits(a):
+    """choose_lp_service's rule on the order-0 LP of instance arrays a (lp_device_lds_bytes, lp_device_max_columns)."""
+    K, M, R, nx = a.K, a.M, a.R, int((np.asarray(a.p) > 0).sum())
+    nr = K + M + (K - R)
+    nc = nx + 1 + nr + 1
+    lds = nr * nc * 8 + nc * 8 + 2 * nr * 8 + nr * 4 + K * M * 2 + K * 2 + nr * 2 + K * M * 2 + K * 8 + 128
+    return ((lds + 15) & ~15) <= 156 * 1024 and nc <= 512
+
+
+def acts_for(torch, b, T, seed=31):
+    from deep_reinforcement_learning_for_fjsp_amd.batch import (VARIANT_MO_FJSSP_DISCRETES, VARIANT_SO_SFJSP, global_actions)
+    nt, nm = {VARIANT_SO_SFJSP: (20, 1), VARIANT_MO_FJSSP_DISCRETES: (18, 1)}.get(b.variant, (6, 5))   # 6th / 5th: random.choice
+    mo = None
+    if b.variant == VARIANT_MO_FJSSP_DISCRETES:
+        mo = torch.tensor([[0.5, 0.5, 800.0, 300.0]], dtype=torch.float64, device="cuda").repeat(b.N, 1)
+    return torch.from_numpy(global_actions(seed, b.first_env, b.N, T, nt, nm)).cuda(), mo
+
+
+def episode(torch, b, T, seed=31):
+    """reset, T per-step steps, read(): everything a caller sees."""
+    acts, mo = acts_for(torch, b, T, seed)
+    out = [H.host(b.reset())]
+    for t in range(T):
+        st, rw, dn = b.step(acts[t], mo=mo)
+        out.append((H.host(st), H.host(rw), H.host(dn)))
+    return out, H.read(b)
+
+
+def ops_of(b):
+    return max(int((np.asarray(a.count).reshape(a.S, a.R) * np.asarray(a.Jr)[None, :]).sum())
+               for a in (b.instance_arrays(i) for i in range(b.n_inst)))
+
+
+def same_episode(eg, eh, mo_static=False, what="episode"):
+    """Bit-identical; for MO_FJSSP_discretes the static columns 4 and 6 within POW_RTOL."""
+    if not mo_static:
+        H.same(eg, eh, what)
+        return
+    (sg, rg), (sh, rh) = eg, eh
+    H.same(rg, rh, what + " read()")
+    exact = [c for c in range(25) if c not in MO_STATIC_POW]
+    states_g = [sg[0]] + [x[0] for x in sg[1:]]
+    states_h = [sh[0]] + [x[0] for x in sh[1:]]
+    n_bits = sum(int((H.bits(a[:, MO_STATIC_POW]) != H.bits(b[:, MO_STATIC_POW])).sum()) for a, b in zip(states_g, states_h))
+    print("%s: static columns 4 / 6 differ in %d entries of %d" % (what, n_bits, 2 * len(states_g) * states_g[0].shape[0]))
+    for t, (a, b) in enumerate(zip(states_g, states_h)):
+        assert np.array_equal(H.bits(a[:, exact]), H.bits(b[:, exact])), (what, t)
+        np.testing.assert_allclose(a[:, MO_STATIC_POW], b[:, MO_STATIC_POW], rtol=H.POW_RTOL, atol=0.0, err_msg="%s step %d" % (what, t))
+    for t in range(1, len(sg)):
+        H.same(sg[t][1:], sh[t][1:], "%s reward / done step %d" % (what, t))
+
+
+def check_pair(torch, G, Hb, what, mo_static=False):
+    assert (G.kernel_family, G.state_size) == (Hb.kernel_family, Hb.state_size), what
+    n_fit = 0
+    for i in range(G.n_inst):
+        a = G.instance_arrays(i)
+        same_instance(a, Hb.instances.arrays(i), "%s instance %d" % (what, i))
+        n_fit += 1 if tableau_fits(a) else 0
+    for i in range(G.N):
+        H.same(G.fluid_tables(i), Hb.fluid_tables(i), "%s fluid tables of env %d" % (what, i))
+    T = ops_of(G)
+    same_episode(episode(torch, G, T), episode(torch, Hb, T), mo_static, what)
+    st = G.generated_stats()
+    assert st["instances"] == G.n_inst and st["lp_device"] + st["lp_host"] == G.n_inst, st
+    return st, n_fit
+
+
+# ---- the cases: the smallest shapes at which each code path can go wrong ---------------------------------------------------
+def test_rows_with_both_lp_routes_in_one_call(torch_gpu):
+    G, Hb = pair(bench(), 64, 7)
+    assert G.kernel_family == 1 and G.row_build() == Hb.row_build()
+    st, n_fit = check_pair(torch_gpu, G, Hb, "rows")
+    assert 0 < n_fit < 64 and (st["lp_device"], st["lp_host"]) == (n_fit, 64 - n_fit), (st, n_fit)
+    assert st["device_pivots"] > 0
+    # ... and the fused rollout
+    T = ops_of(G)
+    outs = []
+    for b in (G, Hb):
+        acts, mo = acts_for(torch_gpu, b, T, seed=32)
+        b.reset()
+        tr, rw, s = b.rollout(acts, mo=mo)
+        outs.append(((H.host(tr), H.host(rw), H.host(s)), H.read(b)))
+    H.same(outs[0], outs[1], "fused rollout")
+    assert np.all(outs[0][1]["done"] == 1)
+
+
+def test_rows_lean_build(torch_gpu):
+    """n not a multiple of 4, the large-batch build: it reads kenv, which the device writes."""
+    with H.env_var("FJSP_GROUP_EARLY", "0"):
+        G, Hb = pair(bench(), 37, 7)
+    assert G.kernel_family == 1 and G.row_build()["early"] == 0 and G.row_build() == Hb.row_build()
+    check_pair(torch_gpu, G, Hb, "lean rows")
+
+
+def test_wave_single_job(torch_gpu):
+    G, Hb = pair(bench(), 16, 7, family=0)
+    assert G.kernel_family == 0
+    check_pair(torch_gpu, G, Hb, "wave single job")
+
+
+def test_multi_job(torch_gpu):
+    prm = gp(R_min=3, R_max=5, J_min=2, J_max=3, M=6, N_min=2, N_max=4)
+    G, Hb = pair(prm, 32, 40)
+    st, n_fit = check_pair(torch_gpu, G, Hb, "multi-job")
+    assert n_fit == 32 and st["lp_device"] == 32
+    assert len({G.instance_arrays(i).R for i in range(32)}) > 1 and any(G.instance_arrays(i).count.max() > 2 for i in range(32))
+
+
+def test_more_than_eight_machines(torch_gpu):
+    G, Hb = pair(gp(R_min=4, R_max=6, J_min=3, J_max=4, M=12), 16, 40)
+    assert G.kernel_family == 0
+    assert any(int(G.instance_arrays(i).elig_n.max()) > 4 for i in range(16))       # beyond first4: the set-order path
+    check_pair(torch_gpu, G, Hb, "M = 12")
+
+
+def test_two_chunks_every_lp_on_the_host(torch_gpu):
+    G, Hb = pair(gp(R_min=16, R_max=20, J_min=4, J_max=5, M=3), 8, 40)
+    assert all(64 <= G.instance_arrays(i).K <= 100 for i in range(8))
+    st, n_fit = check_pair(torch_gpu, G, Hb, "KC = 2")
+    assert n_fit == 0 and st["lp_host"] == 8 and st["device_pivots"] == 0
+
+
+def test_degenerate_instance(torch_gpu):
+    G, Hb = pair(gp(R_min=1, R_max=1, J_min=1, J_max=1, M=1, p_max=1), 4, 40)
+    a = G.instance_arrays(0)
+    assert (a.R, a.K, a.M) == (1, 1, 1) and a.p.tolist() == [[1]]
+    check_pair(torch_gpu, G, Hb, "1 x 1 x 1")
+
+
+@pytest.mark.parametrize("name", ["SO_DFJSP", "SO_SFJSP", "MO_FJSSP_discretes"])
+def test_each_variant(torch_gpu, name):
+    from deep_reinforcement_learning_for_fjsp_amd import batch as B
+    variant = {"SO_DFJSP": B.VARIANT_SO_DFJSP, "SO_SFJSP": B.VARIANT_SO_SFJSP, "MO_FJSSP_discretes": B.VARIANT_MO_FJSSP_DISCRETES}[name]
+    G, Hb = pair(bench(), 16, 11, variant=variant)
+    check_pair(torch_gpu, G, Hb, name, mo_static=name == "MO_FJSSP_discretes")
+
+
+# ---- further properties ----------------------------------------------------------------------------------------------------
+def test_x_does_not_depend_on_the_lp_route(torch_gpu):
+    from deep_reinforcement_learning_for_fjsp_amd._capi import FJSP_E_UNSUPPORTED, FjspError
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    D = EnvBatch.generated(bench(), 64, 7)
+    with H.env_var("FJSP_LP_IMPL", "host"):
+        Ho = EnvBatch.generated(bench(), 64, 7)
+    assert Ho.generated_stats()["lp_host"] == 64 and D.generated_stats()["lp_device"] > 0
+    for i in range(64):
+        assert np.array_equal(H.bits(D.instance_arrays(i).x), H.bits(Ho.instance_arrays(i).x)), i
+    with H.env_var("FJSP_LP_IMPL", "device"), pytest.raises(FjspError) as err:
+        EnvBatch.generated(bench(), 64, 7)
+    assert err.value.code == FJSP_E_UNSUPPORTED and "does not fit" in str(err.value) and "instance" in str(err.value)
+
+
+def test_regenerate_in_place(torch_gpu):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    A, Bs, n = 7, 5000, 32
+    G = EnvBatch.generated(bench(), n, A, rng_seed=3)
+    acts, _ = acts_for(torch, G, 5)
+    G.reset()
+    for t in range(5):
+        G.step(acts[t])
+    under_a = [G.instance_arrays(i) for i in range(n)]
+    G.regenerate(Bs)
+    assert bool(G.done.all()) and np.all(H.read(G)["done"] == 1)
+    assert any(not np.array_equal(G.instance_arrays(i).p, under_a[i].p) for i in range(n))
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    G.regenerate(A)
+    for q in range(8):
+        G.regenerate(Bs + q)
+    G.regenerate(A)
+    torch.cuda.synchronize()
+    assert abs(torch.cuda.mem_get_info()[0] - free0) <= 2 << 20, "device memory moved across ten regenerates"
+    for i in range(n):
+        same_instance(G.instance_arrays(i), under_a[i], "instance %d after A, B, A" % i)
+    T = ops_of(G)
+    H.same(episode(torch, G, T), episode(torch, EnvBatch.generated(bench(), n, A, rng_seed=3), T), "episode after A, B, A")
+
+
+def test_regenerate_needs_a_generated_handle(torch_gpu):
+    from deep_reinforcement_learning_for_fjsp_amd._capi import FJSP_E_STATE, FjspError
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    b = EnvBatch(H.gen_10x5(4, 1), 4)
+    assert b._lib.fjsp_env_regenerate(b._h, 1, 2) == FJSP_E_STATE
+    with pytest.raises(FjspError):
+        b.regenerate(1)
+
+
+def test_shards_are_slices_of_the_whole_batch(torch_gpu):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    whole = EnvBatch.generated(bench(), 32, 7, rng_seed=9)
+    shards = [EnvBatch.generated(bench(), 16, 7, rng_seed=9, first_env=f) for f in (0, 16)]
+    for i in range(32):
+        same_instance(whole.instance_arrays(i), shards[i // 16].instance_arrays(i % 16), "instance %d" % i)
+    T = ops_of(whole)
+    (sw, rw), parts = episode(torch, whole, T), [episode(torch, s, T) for s in shards]
+    cat = lambda xs: np.concatenate(xs, 0)
+    H.same(sw[0], cat([p[0][0] for p in parts]), "reset state")
+    for t in range(1, T + 1):
+        H.same(list(sw[t]), [cat([p[0][t][q] for p in parts]) for q in range(3)], "step %d" % t)
+    H.same(rw, {k: cat([p[1][k] for p in parts]) for k in rw}, "read()")
+
+
+def test_instances_shared_by_envs(torch_gpu):
+    G, Hb = pair(bench(), 16, 7, n_inst=4)
+    check_pair(torch_gpu, G, Hb, "4 instances, 16 envs")
+
+
+def test_snapshot_follows_the_seeds(torch_gpu):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd._capi import FjspError
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    G, G2 = EnvBatch.generated(bench(), 16, 7, rng_seed=3), EnvBatch.generated(bench(), 16, 7, rng_seed=3)
+    acts, _ = acts_for(torch, G, 4)
+    G.reset()
+    for t in range(4):
+        G.step(acts[t])
+    snap = G.snapshot()
+    G2.restore(snap, check=True)
+    assert snap.errors() == 0
+    H.same(H.read(G), H.read(G2), "restored into a handle generated alike")
+    G2.regenerate(8)
+    with pytest.raises(FjspError) as err:
+        G2.restore(snap)
+    assert "not compatible with the snapshot" in str(err.value)
+    # SO_DFJSP runs as SO_FJSSP with other due dates: same parameters and seeds, yet another fingerprint
+    from deep_reinforcement_learning_for_fjsp_amd.batch import VARIANT_SO_DFJSP
+    D = EnvBatch.generated(bench(), 16, 7, rng_seed=3, variant=VARIANT_SO_DFJSP)
+    assert D.kernel_family == G.kernel_family
+    with pytest.raises(FjspError) as err:
+        D.restore(snap)
+    assert "not compatible with the snapshot" in str(err.value)
+
+
+def test_recording_survives_a_regenerate(torch_gpu):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import schedule as S
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    G = EnvBatch.generated(bench(), 16, 7)
+    cap = G.record_schedule()
+    assert cap == 50                      # the parameters' worst case: 10 kinds x 5 operations x 1 job
+    G.regenerate(8)
+    assert G.record_schedule() == cap
+    T = ops_of(G)
+    episode(torch, G, T)
+    table, length = [H.host(x) for x in G.schedule()]
+    for i in range(16):
+        a = G.instance_arrays(i)
+        assert length[i] == int((a.count.reshape(1, a.R) * a.Jr[None, :]).sum())
+        assert S.validate(a, table[i, :length[i]].astype(np.int64), 0) == [], i
+
+
+def test_failing_instance_is_named_and_the_handle_recovers(torch_gpu):
+    from deep_reinforcement_learning_for_fjsp_amd._capi import FJSP_E_STATE, FJSP_E_UNSUPPORTED, FjspError
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, VARIANT_SO_DFJSP
+    prm = gp(R_min=1, R_max=1, J_min=1, J_max=1, M=3)
+    # one operation type with n ~ U{1..3} eligible machines: SO_DFJSP cannot play n < 3 (a machine divides by zero)
+    bad = next(s for s in range(1000, 2000) if not empty_machine(replay(s, prm)) and empty_machine(replay(s + 1, prm)))
+    good = next(s for s in range(1000, 2000) if not any(empty_machine(replay(s + q, prm)) for q in range(2)))
+    with pytest.raises(FjspError) as err:
+        EnvBatch.generated(prm, 2, bad, variant=VARIANT_SO_DFJSP)
+    assert err.value.code == FJSP_E_UNSUPPORTED and "instance 1 (seed %d)" % (bad + 1) in str(err.value)
+    G = EnvBatch.generated(prm, 2, good, variant=VARIANT_SO_DFJSP)
+    with pytest.raises(FjspError) as err:
+        G.regenerate(bad)
+    assert err.value.code == FJSP_E_UNSUPPORTED and "seed %d" % (bad + 1) in str(err.value)
+    for refused in (G.reset, G.read, lambda: G.fluid_tables(0), lambda: G.instance_arrays(0)):
+        with pytest.raises(FjspError) as err:
+            refused()
+        assert err.value.code == FJSP_E_STATE
+    G.regenerate(good)
+    G.reset()
+    assert np.all(H.read(G)["done"] == 0)
+
+
+def test_batched_classes_take_generator_parameters(torch_gpu):
+    from deep_reinforcement_learning_for_fjsp_amd import environments as E
+    from deep_reinforcement_learning_for_fjsp_amd._capi import FJSP_E_UNSUPPORTED, FjspError
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    for cls in (E.BatchedSOFJSSP, E.BatchedSODFJSP, E.BatchedSOSFJSP, E.BatchedMOFJSSP):
+        env = cls(bench(), 8, seed_base=7, rng_seed=2)
+        twin = EnvBatch.generated(bench(), 8, 7, variant=cls.variant, rng_seed=2)
+        assert env.batch.variant == cls.variant and env.N == 8
+        H.same(H.host(env.reset()), H.host(twin.reset()), cls.__name__)
+        env.batch.regenerate(8)
+        assert not np.array_equal(env.batch.instance_arrays(0).p, twin.instance_arrays(0).p)
+    with pytest.raises(FjspError) as err:
+        E.BatchedMODFJSP(bench(), 8, seed_base=7)
+    assert err.value.code == FJSP_E_UNSUPPORTED and "MO_DFJSP needs machine data" in str(err.value)
+    with pytest.raises(ValueError):
+        E.BatchedSOFJSSP(bench())
+
+
+def test_decoders_take_a_generated_batch(torch_gpu):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import lookahead as L, policy_search as PS
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    G = EnvBatch.generated(bench(), 16, 7)
+    G.reset()
+    L.rollout_dispatch(G, H.DET_SO[:3], "makespan")
+    r = H.read(G)
+    assert np.all(r["done"] == 1) and np.all(r["status"] == 0)
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import ActorNet
+    torch.manual_seed(0)
+    actor = ActorNet(20, 128, 2, 30).cuda()
+    G.reset()
+    PS.play(G, actor)
+    r = H.read(G)
+    assert np.all(r["done"] == 1) and np.all(r["status"] == 0)

@@ -1,0 +1,78 @@
+#!/usr/bin/env python3
+"""What a training loop spends on the NEXT batch of instances: the host path against a regenerate on the device.
+
+    python tools/time_regenerate.py [--reps 5] [--out profiles/regenerate_timing.jsonl]
+
+For 4096 and 32768 bench_10x5_params instances and 4096 of reference_generator_params(1.0, 10, 1), alternately in one
+process, wall clock between device synchronisations:
+  (a) InstanceSet(N).generate_range(s, prm).solve_fluid() on 16 threads, EnvBatch(...), up to a finished reset();
+  (b) regenerate(s) + reset() on a live EnvBatch.generated handle.
+Each repetition uses seeds of its own (the same for (a) and (b)).  Prints one JSON line per (workload, path) with every
+repetition, median [min, max], and for (b) the library's own split (generated_stats()["ms"], medians) and LP routes.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def summary(xs):
+    return dict(median=statistics.median(xs), min=min(xs), max=max(xs))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
+    args = ap.parse_args()
+    import torch
+    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+
+    workloads = [("10x5", fi.bench_10x5_params(), 4096), ("10x5", fi.bench_10x5_params(), 32768),
+                 ("reference M=10", fi.reference_generator_params(1.0, 10, 1), 4096)]
+    lines = []
+    for name, prm, N in workloads:
+        live = EnvBatch.generated(prm, N, 1)
+        live.reset()
+        torch.cuda.synchronize()
+        host_ms, dev_ms, parts, routes = [], [], [], None
+        for rep in range(args.reps):
+            seed = 1_000_000 * (rep + 1)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s = fi.InstanceSet(N).generate_range(seed, prm).solve_fluid(n_threads=16)
+            b = EnvBatch(s, N)
+            b.reset()
+            torch.cuda.synchronize()
+            host_ms.append((time.perf_counter() - t0) * 1e3)
+            del b, s
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            live.regenerate(seed)
+            live.reset()
+            torch.cuda.synchronize()
+            dev_ms.append((time.perf_counter() - t0) * 1e3)
+            st = live.generated_stats()
+            parts.append(st["ms"])
+            routes = dict(lp_device=st["lp_device"], lp_host=st["lp_host"], device_pivots=st["device_pivots"])
+        split = {k: statistics.median(p[k] for p in parts) for k in parts[0]}
+        lines.append(dict(workload=name, instances=N, path="host: generate_range + solve_fluid(16 threads) + EnvBatch + reset",
+                          ms=host_ms, **summary(host_ms)))
+        lines.append(dict(workload=name, instances=N, path="device: regenerate + reset", ms=dev_ms, split_ms_median=split,
+                          **routes, **summary(dev_ms)))
+        del live
+    for ln in lines:
+        print(json.dumps(ln))
+    if args.out:
+        with open(args.out, "a") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
+if __name__ == "__main__":
+    main()
