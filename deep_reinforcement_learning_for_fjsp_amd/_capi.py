@@ -31,6 +31,12 @@ class GenParams(C.Structure):
                 ("DDT", _dbl), ("t_si_min", _dbl), ("t_si_max", _dbl)]
 
 
+class GenRanges(C.Structure):
+    """fjsp_gen_ranges: GenRanges(base, M_min, M_max, DDT_min, DDT_max) -- the machine count and the due-date tightness are
+    drawn per instance (base.M and base.DDT are not read)."""
+    _fields_ = [("base", GenParams), ("M_min", _i32), ("M_max", _i32), ("DDT_min", _dbl), ("DDT_max", _dbl)]
+
+
 class ActorParams(C.Structure):
     """fjsp_actor_params: device pointers to the f32 parameters of a state_size -> 128 -> 128 -> n_actions actor."""
     _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w3", _vp), ("b3", _vp),
@@ -45,6 +51,8 @@ SIGNATURES = {
     "fjsp_instances_count": (C.c_int, [_vp]),
     "fjsp_instances_load_csv": (C.c_int, [_vp, _i32, _cp, _cp]),
     "fjsp_instances_generate": (C.c_int, [_vp, _i32, _u64, C.POINTER(GenParams)]),
+    "fjsp_gen_draw": (C.c_int, [C.POINTER(GenRanges), _u64, C.POINTER(GenParams)]),
+    "fjsp_instances_generate_drawn": (C.c_int, [_vp, _i32, _u64, C.POINTER(GenRanges)]),
     "fjsp_instances_set_raw": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl]),
     "fjsp_instances_dims": (C.c_int, [_vp, _i32, C.POINTER(_i32 * 6)]),
     "fjsp_instances_get": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_dbl), _vp]),
@@ -57,6 +65,7 @@ SIGNATURES = {
     "fjsp_env_create": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _pp]),
     "fjsp_env_create_family": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _i32, _pp]),
     "fjsp_env_create_generated": (C.c_int, [C.POINTER(GenParams), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
+    "fjsp_env_create_generated_ranges": (C.c_int, [C.POINTER(GenRanges), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
     "fjsp_env_regenerate": (C.c_int, [_vp, _u64, _u64]),
     "fjsp_env_generated_stats": (C.c_int, [_vp, C.POINTER(_i64 * 4)]),
     "fjsp_env_generated_times": (C.c_int, [_vp, C.POINTER(_dbl * 5)]),

@@ -213,7 +213,8 @@ class EnvBatch(object):
                   family=-1):
         """A batch whose instances are generated and solved on the device (fjsp_env_create_generated): env q plays
         instance q % n_inst = what InstanceSet.generate_range(seed_base, params) + solve_fluid() make of seed
-        seed_base + first_env + q % n_inst.  first_env shifts the instance seeds and the env random streams alike, so a
+        seed_base + first_env + q % n_inst.  params: GenParams, or GenRanges (fjsp_env_create_generated_ranges: every
+        instance draws its own machine count and due-date tightness; the batch is sized for M_max).  first_env shifts the instance seeds and the env random streams alike, so a
         shard [first_env, first_env + n_envs) is a slice of the one-GPU batch.  There is no InstanceSet (`instances` is
         None; instance_arrays(i) reads an instance back); regenerate() refills the batch in place.  One order only
         (params.S == 1), not VARIANT_MO_DFJSP: FjspError(FJSP_E_UNSUPPORTED)."""
@@ -232,9 +233,10 @@ class EnvBatch(object):
         self.first_env, self.first = int(first_env), 0
         self.gen_params, self.seed_base, self.family = params, int(seed_base), int(family)
         mask = 2 ** 64 - 1
-        check(self._lib.fjsp_env_create_generated(C.byref(params), n_inst, int(n_envs), int(variant), self.device_index,
-                                                  (int(rng_seed) + self.first_env * ENV_SEED_STRIDE) & mask, int(family),
-                                                  (self.seed_base + self.first_env) & mask, C.byref(self._h)))
+        create = self._lib.fjsp_env_create_generated_ranges if isinstance(params, _capi.GenRanges) else self._lib.fjsp_env_create_generated
+        check(create(C.byref(params), n_inst, int(n_envs), int(variant), self.device_index,
+                     (int(rng_seed) + self.first_env * ENV_SEED_STRIDE) & mask, int(family),
+                     (self.seed_base + self.first_env) & mask, C.byref(self._h)))
         self._bind(n_envs, n_inst, variant, rng_seed)
         return self
 
@@ -585,7 +587,7 @@ class EnvBatch(object):
 
     def machine_time_end(self):
         if self.instances is None:
-            mp = int(self.gen_params.M)
+            mp = int(self.gen_params.M_max if isinstance(self.gen_params, _capi.GenRanges) else self.gen_params.M)
         else:
             d = self.instances.dims(self.first)
             mp = max(self.instances.dims(self.first + i)["M"] for i in range(self.n_inst)) if self.n_inst > 1 else d["M"]

@@ -42,11 +42,16 @@ struct GenInfo {
     int32_t lds;         // LDS bytes of the order-0 tableau (lp_device_lds_bytes)
     int32_t ops;         // operations (schedule slots)
     int32_t delivery;    // delivery time of the order
+    int32_t M, pad;      // machines of the instance (its own draw on a ranges handle)
+    double ddt;          // its due-date tightness
 };
-static_assert(sizeof(GenInfo) == 32, "GenInfo is eight words");
+static_assert(sizeof(GenInfo) == 48, "GenInfo is twelve words");
 
 struct GenArgs {
-    fjsp_gen_params g;
+    fjsp_gen_params g;       // ranged: g.M and g.DDT are not read
+    int32_t ranged;          // 1: M and DDT of instance `seed` are draws 0 and 1 of the stream seed ^ FJSP_GEN_AUX_STREAM (fjsp_gen_ranges)
+    int32_t M_min, M_max;
+    double DDT_min, DDT_max;
     uint64_t seed_base;
     int32_t class_fjsp;      // SO_DFJSP: the order's delivery time is every job's due date, every machine needs an operation
     int32_t allow_device;    // 0: every LP goes to the host list (FJSP_LP_IMPL=host)
@@ -74,6 +79,14 @@ __device__ inline uint64_t gen_draw(uint64_t seed, uint32_t i) {      // draw i 
 __device__ inline int gen_randint(uint64_t seed, uint32_t i, int a, int b) {
     return a + (int)(((gen_draw(seed, i) >> 32) * (uint64_t)(b - a + 1)) >> 32);
 }
+// M and DDT of instance `seed`: the handle's one pair, or draw_gen_params (fjsp_instance.cpp) restated
+__device__ inline int gen_machines(const GenArgs &a, uint64_t seed) {
+    return a.ranged ? gen_randint(seed ^ FJSP_GEN_AUX_STREAM, 0u, a.M_min, a.M_max) : a.g.M;
+}
+__device__ inline double gen_ddt(const GenArgs &a, uint64_t seed) {
+    if (!a.ranged) return a.g.DDT;
+    return a.DDT_min + (a.DDT_max - a.DDT_min) * ((double)(gen_draw(seed ^ FJSP_GEN_AUX_STREAM, 1u) >> 11) * (1.0 / 9007199254740992.0));
+}
 // lp_device_lds_bytes (fjsp_lp_device.hip) restated for the device; the host compares the two for every instance
 __device__ inline uint32_t gen_lp_lds_bytes(int K, int M, int nx, int R, int MP) {
     const size_t nr = (size_t)K + M + (K - R), nc = (size_t)nx + 1 + nr + 1;
@@ -95,13 +108,14 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     if (inst >= b.n_inst) return;
     const fjsp_gen_params &g = a.g;
     const uint64_t seed = a.seed_base + (uint64_t)inst;
-    const int M = g.M, MP = b.MP, KP = b.KP;
+    const int M = gen_machines(a, seed), MP = b.MP, KP = b.KP;
+    const double DDT = gen_ddt(a, seed);
     unsigned char *rec = b.inst + (size_t)inst * b.L.i_stride;
     const Layout &L = b.L;
 
     // ---- R, J_r, the kinds' first operation types
     const int R = gen_randint(seed, 0u, g.R_min, g.R_max);                                       // :42
-    const bool r_ok = R >= 1 && R <= a.RP && R <= kGenMaxK;
+    const bool r_ok = R >= 1 && R <= a.RP && R <= kGenMaxK && M >= 1 && M <= MP && M <= kMaxM;
     for (int r = l; r_ok && r < R; r += kWave) s_Jr[r] = (uint8_t)gen_randint(seed, 1u + (uint32_t)r, g.J_min, g.J_max);   // :46,71
     __syncthreads();
     if (l == 0) {
@@ -131,7 +145,7 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     const int K = s_hdr[1], nx = s_hdr[3];
     int status = s_hdr[2];
     if (status != 0) {
-        if (l == 0) a.info[inst] = GenInfo{status, 0, 0, 0, 0, 0, 0, 0};
+        if (l == 0) a.info[inst] = GenInfo{status, 0, 0, 0, 0, 0, 0, 0, M, 0, DDT};
         return;
     }
     // ---- per operation type: choice(M, n, replace=False) as a Fisher-Yates prefix, then the processing times
@@ -162,7 +176,7 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
         for (int r = 0; r < R; ++r) { s_jbeg[r] = (uint16_t)nj; nj += s_cnt[r]; ops += (int)s_cnt[r] * (int)s_Jr[r]; }
         s_jbeg[R] = (uint16_t)nj;
         for (int k = 0; k < K; ++k) acc = acc + s_tr[k] * (double)s_cnt[s_rk[k]];
-        const double gap = acc * g.DDT / (double)(M * 2);
+        const double gap = acc * DDT / (double)(M * 2);
         const double dl = 0.0 + gap;                                                               // :85-86 (one order: arrives at 0)
         s_hdr[5] = nj; s_hdr[6] = (int)dl; s_hdr[7] = ops;
         if (nj > b.JP || nj > 65535) s_hdr[2] = FJSP_E_FORMAT;
@@ -176,7 +190,7 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
         for (int k = 0; k < K; ++k) ops_m += s_p[k * kMaxM + l] > 0 ? 1 : 0;
     if (a.class_fjsp && __any(l < M && ops_m == 0) && status == 0) status = FJSP_E_UNSUPPORTED;
     const uint32_t lds = gen_lp_lds_bytes(K, M, nx, R, MP);
-    if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[7], delivery};
+    if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[7], delivery, M, 0, DDT};
     if (status != 0) return;
 
     // ---- the record (pack_instance, fjsp_env.hip); the slab was zeroed before the launch
@@ -299,7 +313,7 @@ __global__ __launch_bounds__(kWave) void generate_finish_kernel(DevBatch b, GenA
             if ((kB[k] & 0xFFu) == 0u) { const double d = (double)(kA[k] >> 16) - N_ave; va = va + d * d; }
         for (int k = 0; k < K; ++k)
             if ((kB[k] & 0xFFu) == 0u) { const double d = (double)((kB[k] >> 8) & 0xFFu) - J_ave; vc = vc + d * d; }
-        ss[0] = a.g.DDT; ss[1] = (double)M; ss[2] = (double)R; ss[3] = N_ave;
+        ss[0] = gen_ddt(a, a.seed_base + (uint64_t)inst); ss[1] = (double)M; ss[2] = (double)R; ss[3] = N_ave;
         ss[4] = sqrt(va / (double)R); ss[5] = J_ave; ss[6] = sqrt(vc / (double)R);
     }
 }
@@ -379,30 +393,34 @@ int check_params(const fjsp_gen_params &g) {
     return FJSP_OK;
 }
 
-// check_instance (fjsp_env.hip) on the worst case of the parameters, sizes into sh
-int check_worst_case(const fjsp_gen_params &g, Shape &sh) {
+// check_instance (fjsp_env.hip) on the worst case of the parameters, sizes into sh.  Over M in M_min..M_max and |DDT| up to
+// ddt_max: sizes from M_max, the largest delivery time from ddt_max / (2 M_min)
+int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_max, Shape &sh) {
     const long long K = (long long)g.R_max * g.J_max, nj = (long long)g.R_max * g.N_max, ops = K * g.N_max;
     if (K > kWave * kMaxKC) { set_error("generated instances can have more than 256 operation types (R_max x J_max)"); return FJSP_E_UNSUPPORTED; }
-    if (g.M > kMaxM) { set_error("more than 32 machines"); return FJSP_E_UNSUPPORTED; }
+    if (M_max > kMaxM) { set_error(M_min == M_max ? "more than 32 machines" : "more than 32 machines (M_max)"); return FJSP_E_UNSUPPORTED; }
     if (nj > 65535) { set_error("generated instances can have more than 65535 jobs (R_max x N_max)"); return FJSP_E_UNSUPPORTED; }
     if (ops > 65535) { set_error("generated instances can have more than 65535 operations (R_max x J_max x N_max)"); return FJSP_E_UNSUPPORTED; }
     if (g.J_max > 255) { set_error("more than 255 operations in a kind"); return FJSP_E_UNSUPPORTED; }
     if (g.p_max > 65535) { set_error("processing time above 65535"); return FJSP_E_UNSUPPORTED; }
     // the 32-bit clocks: every operation in sequence at the largest processing time; the largest delivery time is every
     // operation type at p_max with N_max jobs, times DDT / (2 M)
-    const double due = std::fabs((double)K * (double)g.p_max * (double)g.N_max * g.DDT / (double)(g.M * 2));
+    const double due = std::fabs((double)K * (double)g.p_max * (double)g.N_max * ddt_max / (double)(M_min * 2));
     const double clock = (double)ops * (double)g.p_max;
     if (!(clock + due <= 2147483647.0) || !((double)g.N_max * (clock + due) <= 2147483647.0)) {
         set_error("generated instances can be too long for the kernels' 32-bit clocks: (operations x max processing time + "
-                  "largest delivery time) x jobs per kind must stay below 2^31");
+                  "largest delivery time) x jobs per kind must stay below 2^31; the largest delivery time grows with DDT (DDT_max) "
+                  "and shrinks with the machine count (M_min)");
         return FJSP_E_UNSUPPORTED;
     }
-    sh.K = (int)K; sh.M = g.M; sh.J = (int)nj; sh.R = g.R_max; sh.S = 1;
+    sh.K = (int)K; sh.M = M_max; sh.J = (int)nj; sh.R = g.R_max; sh.S = 1;
     sh.single_job = g.N_min == 1 && g.N_max == 1 && g.R_max <= 255;
     return FJSP_OK;
 }
 
-uint64_t gen_hash(const fjsp_gen_params &g, int n_inst, uint64_t seed_base, int class_fjsp) {
+uint64_t gen_hash(const GenArgs &a, int n_inst, uint64_t seed_base) {
+    const fjsp_gen_params &g = a.g;
+    const int class_fjsp = a.class_fjsp;
     uint64_t h = 1469598103934665603ULL;
     auto mix = [&](const void *p, size_t n) {
         const unsigned char *c = static_cast<const unsigned char *>(p);
@@ -412,6 +430,11 @@ uint64_t gen_hash(const fjsp_gen_params &g, int n_inst, uint64_t seed_base, int 
     const int32_t iv[12] = {g.R_min, g.R_max, g.J_min, g.J_max, g.M, g.p_min, g.p_max, g.N_min, g.N_max, g.S, n_inst, class_fjsp};
     const double dv[3] = {g.DDT, g.t_si_min, g.t_si_max};
     mix(iv, sizeof(iv)); mix(dv, sizeof(dv)); mix(&seed_base, sizeof(seed_base));
+    if (a.ranged) {     // a tag and the ranges: never the fingerprint of a fixed-parameter handle (g.M, g.DDT are zeroed there)
+        const int32_t rv[3] = {0x52414E47, a.M_min, a.M_max};
+        const double rd[2] = {a.DDT_min, a.DDT_max};
+        mix(rv, sizeof(rv)); mix(rd, sizeof(rd));
+    }
     return h;
 }
 
@@ -419,11 +442,12 @@ double step_bytes_mean(const fjsp_env *e) {        // step_bytes_of (fjsp_env.hi
     const DevBatch &b = e->b;
     const GenState &G = *e->gen;
     const double per_k = 28.0 + (b.single_job ? 1.0 : 4.0) + (b.MP > 8 ? 4.0 : 0.0) + (b.single_job ? 0.0 : 128.0);
-    const double M = (double)G.a.g.M;
-    const double gather = b.single_job ? M * 18.0 + 1.0 : M * 26.0 + 8.0;
     double bytes = 0.0;
-    for (int i = 0; i < b.n_inst; ++i)
+    for (int i = 0; i < b.n_inst; ++i) {
+        const double M = (double)G.h_info[i].M;
+        const double gather = b.single_job ? M * 18.0 + 1.0 : M * 26.0 + 8.0;
         bytes += G.h_info[i].K * per_k + G.h_info[i].nj * 16.0 + M * 16.0 + 304.0 + gather + 2.0 + b.state_size * 8.0 + 9.0;
+    }
     return bytes;
 }
 
@@ -518,7 +542,6 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
     HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(G.h_host_ids, G.a.host_ids, n_inst * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const int M = G.a.g.M;
     for (size_t i = 0; i < n_inst; ++i) {
         const GenInfo &f = G.h_info[i];
         const std::string who = "instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ")";
@@ -526,7 +549,7 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
         if (f.status != 0)
             return fail_generate(e, f.status, call + ": " + who + ": a draw left the record's fields (internal error)");
-        if (f.ops > e->ops_max || (size_t)f.lds != lp_device_lds_bytes(f.K, M, f.nx, f.R, b.MP))
+        if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP || (size_t)f.lds != lp_device_lds_bytes(f.K, f.M, f.nx, f.R, b.MP))
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": sizes disagree with the host's (internal error)");
     }
     const int n_fit = (int)G.h_counts[0], n_host = (int)G.h_counts[1];
@@ -537,10 +560,10 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
         const GenInfo &f = G.h_info[i];
         return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": FJSP_LP_IMPL=device, but the order-0 tableau of instance " + std::to_string(i) +
                              " (seed " + std::to_string(seed_base + i) + ") does not fit: " + std::to_string(f.lds) + " bytes of LDS (limit " +
-                             std::to_string(kLpLdsLimit) + "), " + std::to_string(f.nx + 1 + (2 * f.K + M - f.R) + 1) + " columns (limit " +
+                             std::to_string(kLpLdsLimit) + "), " + std::to_string(f.nx + 1 + (2 * f.K + f.M - f.R) + 1) + " columns (limit " +
                              std::to_string(lp_device_max_columns()) + ")");
     }
-    for (size_t i = 0; i < n_inst; ++i) e->inst_K[i] = G.h_info[i].K;
+    for (size_t i = 0; i < n_inst; ++i) { e->inst_K[i] = G.h_info[i].K; e->inst_M[i] = G.h_info[i].M; }
     e->step_bytes = (int64_t)(step_bytes_mean(e) / (double)n_inst + 0.5);
     // ---- device route: bounded chunks of staging slots, each an LP launch and the finish of its instances
     const size_t lds = G.h_counts[2];
@@ -596,44 +619,45 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
                                                             : call + ": a fluid LP failed on the device (code " + std::to_string((uint32_t)G.h_lp[2]) + ")");
     }
     G.stats[0] = (int64_t)n_inst; G.stats[1] = n_fit; G.stats[2] = n_host; G.stats[3] = (int64_t)G.h_lp[1];
-    e->inst_hash = gen_hash(G.a.g, b.n_inst, seed_base, G.a.class_fjsp);
+    e->inst_hash = gen_hash(G.a, b.n_inst, seed_base);
     e->gen_failed = false;
     G.ms[4] = ms_since(t_call);
     return FJSP_OK;
 }
-}  // namespace
-}  // namespace fjsp
 
-using namespace fjsp;
-
-extern "C" {
-int fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
-                              uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
-    if (!prm || !out || n_inst <= 0 || n_envs <= 0) { set_error("fjsp_env_create_generated: bad arguments"); return FJSP_E_ARG; }
-    if (family < -1 || family > 1) { set_error("fjsp_env_create_generated: family must be -1, 0 or 1"); return FJSP_E_ARG; }
+// Both creates: q == nullptr is the fixed parameter set *prm; else *prm is q->base and M, DDT are drawn per instance
+int create_generated(const std::string &call, const fjsp_gen_params *prm, const fjsp_gen_ranges *q, int32_t n_inst, int32_t n_envs,
+                     int32_t variant, int32_t device, uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
+    if (!prm || !out || n_inst <= 0 || n_envs <= 0) { set_error(call + ": bad arguments"); return FJSP_E_ARG; }
+    if (family < -1 || family > 1) { set_error(call + ": family must be -1, 0 or 1"); return FJSP_E_ARG; }
     const bool class_fjsp = variant == FJSP_VARIANT_SO_DFJSP;
     if (variant == FJSP_VARIANT_MO_DFJSP) {
-        set_error("fjsp_env_create_generated: MO_DFJSP needs machine data and the per-env fluid tables; the generator has neither (use fjsp_env_create)");
+        set_error(call + ": MO_DFJSP needs machine data and the per-env fluid tables; the generator has neither (use fjsp_env_create)");
         return FJSP_E_UNSUPPORTED;
     }
     if (class_fjsp) variant = FJSP_VARIANT_SO_FJSSP;
     if (variant != FJSP_VARIANT_SO_FJSSP && variant != FJSP_VARIANT_SO_SFJSP && variant != FJSP_VARIANT_MO_FJSSP_DISCRETES) {
-        set_error("fjsp_env_create_generated: unknown variant"); return FJSP_E_ARG;
+        set_error(call + ": unknown variant"); return FJSP_E_ARG;
     }
-    int rc = check_params(*prm);
+    int rc = q ? check_gen_ranges(*q) : FJSP_OK;
     if (rc != FJSP_OK) return rc;
+    fjsp_gen_params g = *prm;
+    if (q) { g.M = q->M_min; g.DDT = 0.0; }       // base.M and base.DDT are not read
+    if ((rc = check_params(g)) != FJSP_OK) return rc;
+    const int M_min = q ? q->M_min : g.M, M_max = q ? q->M_max : g.M;
+    const double ddt_max = q ? std::max(std::fabs(q->DDT_min), std::fabs(q->DDT_max)) : g.DDT;
     if (prm->S != 1) {
-        set_error("fjsp_env_create_generated: one order only (S == 1): order arrivals need the per-env fluid tables (use fjsp_env_create)");
+        set_error(call + ": one order only (S == 1): order arrivals need the per-env fluid tables (use fjsp_env_create)");
         return FJSP_E_UNSUPPORTED;
     }
     Shape sh;
-    if ((rc = check_worst_case(*prm, sh)) != FJSP_OK) return rc;
+    if ((rc = check_worst_case(g, M_min, M_max, ddt_max, sh)) != FJSP_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device visible: the environment kernels need an MI355X (there is no CPU path)");
         return FJSP_E_HIP;
     }
-    if (device < 0 || device >= ndev) { set_error("fjsp_env_create_generated: device index out of range"); return FJSP_E_ARG; }
+    if (device < 0 || device >= ndev) { set_error(call + ": device index out of range"); return FJSP_E_ARG; }
     DeviceGuard guard(device);
 
     std::unique_ptr<fjsp_env, void (*)(fjsp_env *)> e(new fjsp_env(), fjsp_env_destroy);
@@ -641,15 +665,16 @@ int fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_
     DevBatch &b = e->b;
     if ((rc = plan_batch(b, e->plan, sh, n_inst, n_envs, variant, rng_seed, family)) != FJSP_OK) return rc;
     // src stays null: only the order-arrival services (fjsp_arrivals.hip) read it, and only multi-order batches reach them
-    if (b.mord) { set_error("fjsp_env_create_generated: internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
-    if (lp_device_max_columns() != kLpMaxColumns) { set_error("fjsp_env_create_generated: internal error (device LP width)"); return FJSP_E_UNSUPPORTED; }
+    if (b.mord) { set_error(call + ": internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
+    if (lp_device_max_columns() != kLpMaxColumns) { set_error(call + ": internal error (device LP width)"); return FJSP_E_UNSUPPORTED; }
     e->inst_K.assign((size_t)n_inst, 0); e->inst_M.assign((size_t)n_inst, sh.M);
     e->ops_max = sh.K * prm->N_max;
 
     e->gen = new GenState();
     GenState &G = *e->gen;
     const size_t N = (size_t)n_envs, NI = (size_t)n_inst, KP = (size_t)b.KP, MP = (size_t)b.MP;
-    G.a.g = *prm; G.a.class_fjsp = class_fjsp ? 1 : 0; G.a.allow_device = e->plan.lp_device_forced == 0 ? 0 : 1;
+    if (q) { g.M = 0; G.a.ranged = 1; G.a.M_min = q->M_min; G.a.M_max = q->M_max; G.a.DDT_min = q->DDT_min; G.a.DDT_max = q->DDT_max; }
+    G.a.g = g; G.a.class_fjsp = class_fjsp ? 1 : 0; G.a.allow_device = e->plan.lp_device_forced == 0 ? 0 : 1;
     G.a.kmax = sh.K; G.a.RP = sh.R;
     G.chunk = (int)std::min<size_t>(NI, 1024);
     G.head16 = (int)((b.L.i_x + 15) / 16);
@@ -674,9 +699,25 @@ int fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_
     for (hipEvent_t &ev : G.ev) HIP_TRY(hipEventCreate(&ev));
     HIP_TRY(hipStreamCreateWithFlags(&G.st_dev, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&G.st_host, hipStreamNonBlocking));
-    if ((rc = regenerate(e.get(), seed_base, rng_seed, "fjsp_env_create_generated")) != FJSP_OK) return rc;
+    if ((rc = regenerate(e.get(), seed_base, rng_seed, call)) != FJSP_OK) return rc;
     *out = e.release();
     return FJSP_OK;
+}
+}  // namespace
+}  // namespace fjsp
+
+using namespace fjsp;
+
+extern "C" {
+int fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
+                              uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
+    return create_generated("fjsp_env_create_generated", prm, nullptr, n_inst, n_envs, variant, device, rng_seed, family, seed_base, out);
+}
+
+int fjsp_env_create_generated_ranges(const fjsp_gen_ranges *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
+                                     uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
+    return create_generated("fjsp_env_create_generated_ranges", q ? &q->base : nullptr, q, n_inst, n_envs, variant, device, rng_seed, family,
+                            seed_base, out);
 }
 
 int fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed) {
@@ -737,7 +778,7 @@ int fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr,
     }
     if (arrive) arrive[0] = 0;
     if (delivery) delivery[0] = f.delivery;
-    if (ddt) *ddt = G.a.g.DDT;
+    if (ddt) *ddt = f.ddt;
     return FJSP_OK;
 }
 }  // extern "C"

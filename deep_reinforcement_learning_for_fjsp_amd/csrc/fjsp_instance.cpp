@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -295,6 +296,23 @@ static int generate(Instance &in, uint64_t seed, const fjsp_gen_params &g) {
     return finalize_instance(in);
 }
 
+// ---- M and DDT drawn per instance (fjsp_gen_ranges, include/fjsp_amd.h) ----
+int check_gen_ranges(const fjsp_gen_ranges &q) {
+    if (q.M_min <= 0) { set_error("generator ranges: M_min must be positive"); return FJSP_E_ARG; }
+    if (q.M_max < q.M_min) { set_error("generator ranges: M_max < M_min"); return FJSP_E_ARG; }
+    if (!std::isfinite(q.DDT_min)) { set_error("generator ranges: DDT_min is not finite"); return FJSP_E_ARG; }
+    if (!std::isfinite(q.DDT_max)) { set_error("generator ranges: DDT_max is not finite"); return FJSP_E_ARG; }
+    if (q.DDT_max < q.DDT_min) { set_error("generator ranges: DDT_max < DDT_min"); return FJSP_E_ARG; }
+    return FJSP_OK;
+}
+
+void draw_gen_params(const fjsp_gen_ranges &q, uint64_t seed, fjsp_gen_params &out) {
+    Rng aux(seed ^ FJSP_GEN_AUX_STREAM);
+    out = q.base;
+    out.M = aux.randint(q.M_min, q.M_max);
+    out.DDT = aux.uniform(q.DDT_min, q.DDT_max);
+}
+
 static int solve_order0(Instance &in) {
     std::vector<int> Q(in.K), now(in.K);
     for (int r = 0; r < in.R; ++r)
@@ -346,6 +364,20 @@ int fjsp_instances_generate(fjsp_instances *s, int32_t i, uint64_t seed, const f
     int rc = generate(in, seed, *prm);
     if (rc == FJSP_OK) s->v[(size_t)i] = std::move(in);
     return rc;
+}
+
+int fjsp_gen_draw(const fjsp_gen_ranges *q, uint64_t seed, fjsp_gen_params *out) {
+    if (!q || !out) { set_error("fjsp_gen_draw: null argument"); return FJSP_E_ARG; }
+    const int rc = check_gen_ranges(*q);
+    if (rc == FJSP_OK) draw_gen_params(*q, seed, *out);
+    return rc;
+}
+
+int fjsp_instances_generate_drawn(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_ranges *q) {
+    CHECK_IDX(s, i);
+    fjsp_gen_params prm;
+    const int rc = fjsp_gen_draw(q, seed, &prm);
+    return rc == FJSP_OK ? fjsp_instances_generate(s, i, seed, &prm) : rc;
 }
 
 int fjsp_instances_set_raw(fjsp_instances *s, int32_t i, int32_t R, int32_t M, int32_t S, const int32_t *Jr,

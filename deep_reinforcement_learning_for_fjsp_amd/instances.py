@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import GenParams, check
+from ._capi import GenParams, GenRanges, check
 
 
 def bench_10x5_params(ddt=1.0):
@@ -25,6 +25,27 @@ def reference_generator_params(ddt, M, S):
     """The in-env generator's own distributions (Instance_generate.py:39-66)."""
     return GenParams(R_min=3, R_max=12, J_min=3, J_max=5, M=M, p_min=40, p_max=400,
                      N_min=5, N_max=50, S=S, DDT=ddt, t_si_min=100.0, t_si_max=200.0)
+
+
+def reference_training_ranges(agent):
+    """What the reference's training loops draw a fresh shop from, one order: the generator's own kind / operation / time
+    distributions with the machine count and the due-date tightness drawn per instance.
+        "mpppo"  MPPPO.py:149-154   M = randint(10, 20), DDT = uniform(0.5, 1.5), jobs per kind U{5..50}
+        "ddqn"   DDQN.py:99-104     M = randint(3, 8),   DDT = uniform(0.5, 1.5), jobs per kind U{1..2} (examples/train_ddqn.py)"""
+    if agent not in ("mpppo", "ddqn"):
+        raise ValueError("reference_training_ranges: 'mpppo' or 'ddqn', got %r" % (agent,))
+    base = reference_generator_params(1.0, 0, 1)
+    if agent == "ddqn":
+        base.N_min, base.N_max = 1, 2
+    M_min, M_max = (10, 20) if agent == "mpppo" else (3, 8)
+    return GenRanges(base, M_min, M_max, 0.5, 1.5)
+
+
+def draw_params(ranges, seed):
+    """The GenParams that instance `seed` is generated with under `ranges` (fjsp_gen_draw)."""
+    out = GenParams()
+    check(_capi.lib().fjsp_gen_draw(C.byref(ranges), int(seed) & (2 ** 64 - 1), C.byref(out)))
+    return out
 
 
 class InstanceArrays(object):
@@ -72,7 +93,9 @@ class InstanceSet(object):
         return self
 
     def generate(self, i, seed, params):
-        check(self._lib.fjsp_instances_generate(self._h, int(i), int(seed) & (2 ** 64 - 1), C.byref(params)))
+        """params: GenParams, or GenRanges (M and DDT drawn per instance from the seed: fjsp_instances_generate_drawn)."""
+        call = self._lib.fjsp_instances_generate_drawn if isinstance(params, GenRanges) else self._lib.fjsp_instances_generate
+        check(call(self._h, int(i), int(seed) & (2 ** 64 - 1), C.byref(params)))
         return self
 
     def generate_range(self, seed_base, params, first=0, n=None):

@@ -6,9 +6,9 @@ random instances (generated_new_environment, DDQN.py:99-104: M in [3, 8]) and on
     python examples/train_ddqn.py --envs 1024 --rounds 5
     python examples/train_ddqn.py --envs 1024 --rounds 5 --device-instances
 
---device-instances generates each round's instances (and solves their fluid LPs) on the device, in place.  A generated
-env has ONE parameter set, so there a round's instances share M (3 + round % 6: one live env per M) and DDT = 1.0,
-where the default path draws both per instance.
+--device-instances generates each round's instances (and solves their fluid LPs) on the device, in place: one live
+environment built from instances.reference_training_ranges("ddqn"), regenerated per round.  Both paths draw every
+instance's M and DDT from its seed, so they train on the same instances.
 """
 import argparse
 import json
@@ -24,7 +24,7 @@ def main():
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--device-instances", action="store_true",
-                    help="regenerate the training instances on the device every round (one M and DDT per round)")
+                    help="regenerate the training instances on the device every round, in one live environment")
     args = ap.parse_args()
     import torch
     from deep_reinforcement_learning_for_fjsp_amd import instances as fi
@@ -32,25 +32,19 @@ def main():
     from deep_reinforcement_learning_for_fjsp_amd.agents.DDQN.DDQN import DDQN
 
     test_env = BatchedSOSFJSP(fi.InstanceSet(64).generate_range(800000, fi.bench_10x5_params()).solve_fluid(), rng_seed=1)
-    rounds, live = [0], {}
+    ranges = fi.reference_training_ranges("ddqn")
+    rounds, live = [0], []
 
     def make_train_env():
         rounds[0] += 1
+        seed_base = 5_000_000 * rounds[0]
         if args.device_instances:
-            M = 3 + rounds[0] % 6
-            if M not in live:
-                prm = fi.GenParams(R_min=3, R_max=12, J_min=3, J_max=5, M=M, p_min=40, p_max=400, N_min=1, N_max=2, S=1, DDT=1.0,
-                                   t_si_min=100.0, t_si_max=200.0)
-                live[M] = BatchedSOSFJSP(prm, args.envs, seed_base=5_000_000 * rounds[0], rng_seed=rounds[0])
+            if not live:
+                live.append(BatchedSOSFJSP(ranges, args.envs, seed_base=seed_base, rng_seed=rounds[0]))
             else:
-                live[M].batch.regenerate(5_000_000 * rounds[0], rng_seed=rounds[0])
-            return live[M]
-        s = fi.InstanceSet(args.envs)
-        for i in range(args.envs):
-            seed = 5_000_000 * rounds[0] + i
-            s.generate(i, seed, fi.GenParams(R_min=3, R_max=12, J_min=3, J_max=5, M=3 + seed % 6, p_min=40, p_max=400, N_min=1,
-                                             N_max=2, S=1, DDT=0.5 + (seed % 11) / 10.0, t_si_min=100.0, t_si_max=200.0))
-        return BatchedSOSFJSP(s.solve_fluid(), rng_seed=rounds[0])
+                live[0].batch.regenerate(seed_base, rng_seed=rounds[0])
+            return live[0]
+        return BatchedSOSFJSP(fi.InstanceSet(args.envs).generate_range(seed_base, ranges).solve_fluid(), rng_seed=rounds[0])
 
     torch.manual_seed(0)
     agent = DDQN(make_train_env, test_env, updates_per_round=8, hyper={"learning_rate": 1e-4})

@@ -91,6 +91,20 @@ typedef struct {
     double  t_si_min, t_si_max; /* order inter-arrival     (:58  U(100,200))          */
 } fjsp_gen_params;
 
+/* The generator's parameters with the machine count and the due-date tightness drawn PER INSTANCE, as the reference's
+ * training loops do (MPPPO.py:149-154 M = randint(10, 20), DDQN.py:99-104 M = randint(3, 8); both DDT = uniform(0.5, 1.5)).
+ * The instance of seed s under ranges q is fjsp_instances_generate(s, p), p = q.base with
+ *     p.M   = randint(M_min, M_max)       draw 0 \  of an auxiliary splitmix64 stream seeded s ^ FJSP_GEN_AUX_STREAM:
+ *     p.DDT = uniform(DDT_min, DDT_max)   draw 1 /  a + (int)(((z >> 32) * (b - a + 1)) >> 32) and a + (b - a) * ((z >> 11) * 2^-53)
+ * Both draws are always taken; the main stream of seed s is untouched, so a point range (M_min == M_max, DDT_min ==
+ * DDT_max) gives the instances of the fixed parameter set. */
+#define FJSP_GEN_AUX_STREAM 0xD1B54A32D192ED03ULL
+typedef struct {
+    fjsp_gen_params base;      /* base.M and base.DDT are not read */
+    int32_t M_min, M_max;      /* machines per instance:  U{M_min..M_max}      */
+    double  DDT_min, DDT_max;  /* due-date tightness:     U(DDT_min, DDT_max)  */
+} fjsp_gen_ranges;
+
 int  fjsp_instances_create(int32_t n, fjsp_instances **out);
 void fjsp_instances_destroy(fjsp_instances *s);
 int  fjsp_instances_count(const fjsp_instances *s);
@@ -101,6 +115,11 @@ int  fjsp_instances_count(const fjsp_instances *s);
 int fjsp_instances_load_csv(fjsp_instances *s, int32_t i, const char *path, const char *file_name);
 /* Instance(DDT, M, S): environments/Instance_generate.py:24-94, seeded. */
 int fjsp_instances_generate(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_params *prm);
+/* The parameter set that instance `seed` is generated with under ranges q (see fjsp_gen_ranges).  FJSP_E_ARG for
+ * M_min <= 0, M_max < M_min, non-finite DDT bounds or DDT_max < DDT_min; the message names the bound. */
+int fjsp_gen_draw(const fjsp_gen_ranges *q, uint64_t seed, fjsp_gen_params *out);
+/* fjsp_gen_draw, then fjsp_instances_generate with what it drew. */
+int fjsp_instances_generate_drawn(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_ranges *q);
 /* Raw arrays (same meaning as the fjsp_instances_get outputs). */
 int fjsp_instances_set_raw(fjsp_instances *s, int32_t i, int32_t R, int32_t M, int32_t S,
                            const int32_t *Jr, const int32_t *p /*[K*M] k-major, 0 = ineligible*/,
@@ -178,6 +197,18 @@ int  fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_in
  * other seeds is refused after it. */
 int  fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
                                uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out);
+/* fjsp_env_create_generated with M and DDT drawn per instance (fjsp_gen_ranges): instance i is what
+ * fjsp_instances_generate_drawn(seed_base + i, q) + fjsp_instances_solve_fluid + fjsp_env_create_family give.  The handle is
+ * sized over the ranges: sizes, kernel family (the row kernels iff M_max <= 8 and the batch fits them otherwise), builds and
+ * schedule capacity from M_max, the 32-bit clock bound from DDT_max / (2 M_min); InstHeader.M, the LP tableau and its route
+ * are the instance's own.  fjsp_env_regenerate, fjsp_env_generated_stats / _times, fjsp_env_instance_read (dims[1] and *ddt
+ * are the instance's own M and DDT), snapshots, schedule recording and the decoders work on such a handle as on a
+ * fixed-parameter one; its snapshot fingerprint mixes the ranges and a tag, so it never matches a fixed-parameter handle's.
+ * FJSP_E_ARG: M_min <= 0, M_max < M_min, non-finite DDT bounds, DDT_max < DDT_min, the checks of fjsp_env_create_generated on
+ * base; FJSP_E_UNSUPPORTED: M_max > 32, base.S > 1, MO_DFJSP, a worst case outside the kernels' limits; all before the
+ * first HIP call, the message naming the bound. */
+int  fjsp_env_create_generated_ranges(const fjsp_gen_ranges *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
+                                      uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out);
 int  fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed);
 /* Of the last create_generated / regenerate: out[0] instances, [1] LPs solved on the device, [2] on the host, [3] pivots
  * of the device simplex.  fjsp_env_generated_times: milliseconds of its parts -- the generate kernel, the LP launches with

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a training loop spends on the NEXT batch of instances: the host path against a regenerate on the device.
 
-    python tools/time_regenerate.py [--reps 5] [--out profiles/regenerate_timing.jsonl]
+    python tools/time_regenerate.py [--reps 5] [--out profiles/regenerate_timing.jsonl] [--ranges mpppo|ddqn] [--envs 4096]
 
 For 4096 and 32768 bench_10x5_params instances and 4096 of reference_generator_params(1.0, 10, 1), alternately in one
 process, wall clock between device synchronisations:
@@ -9,6 +9,8 @@ process, wall clock between device synchronisations:
   (b) regenerate(s) + reset() on a live EnvBatch.generated handle.
 Each repetition uses seeds of its own (the same for (a) and (b)).  Prints one JSON line per (workload, path) with every
 repetition, median [min, max], and for (b) the library's own split (generated_stats()["ms"], medians) and LP routes.
+--ranges NAME times instances.reference_training_ranges(NAME) instead (M and DDT drawn per instance), --envs of them;
+--envs alone times that many 10x5 instances.
 """
 import argparse
 import json
@@ -28,6 +30,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
+    ap.add_argument("--ranges", choices=("mpppo", "ddqn"), default=None, help="the reference's training distribution instead of the three workloads")
+    ap.add_argument("--envs", type=int, default=None, help="instances of the --ranges workload (4096), or of a single 10x5 workload")
     args = ap.parse_args()
     import torch
     from deep_reinforcement_learning_for_fjsp_amd import instances as fi
@@ -35,6 +39,10 @@ def main():
 
     workloads = [("10x5", fi.bench_10x5_params(), 4096), ("10x5", fi.bench_10x5_params(), 32768),
                  ("reference M=10", fi.reference_generator_params(1.0, 10, 1), 4096)]
+    if args.ranges:
+        workloads = [("ranges " + args.ranges, fi.reference_training_ranges(args.ranges), args.envs or 4096)]
+    elif args.envs:
+        workloads = [("10x5", fi.bench_10x5_params(), args.envs)]
     lines = []
     for name, prm, N in workloads:
         live = EnvBatch.generated(prm, N, 1)
