@@ -131,6 +131,7 @@ class PPOLearner(object):
         self.device = torch.device(device)
         self.fused_learn = True            # GPU batches of >= 32 k samples train through agents/fused_mlp.py
         self.mfma_learn = True             # ... with forward + loss + backward of a network in ONE launch (csrc/fjsp_mlp_train.hip)
+        self.two_chains = True             # ... and the actor's iterations on a stream of their own where _fused_trainer allows it
         self._fused = None
         gen_state = torch.random.get_rng_state()
         torch.manual_seed(seed)            # identical initial parameters on every rank
@@ -143,14 +144,11 @@ class PPOLearner(object):
         adam = dict(lr=self.hp["learning_rate"], eps=1e-4, fused=fused, capturable=fused)   # capturable: step count on the device
         self.actor_optimizer = optim.Adam(self.actor_new.parameters(), **adam)
         self.critic_optimizer = optim.Adam(self.critic.parameters(), **adam)
-        # which trainer owns the optimiser state -- "fused" (agents/fused_mlp.py, its own Adam moments) or "eager" (the torch
-        # optimisers above) -- is decided ONCE, at the first learn(), from the smallest sample count over the ranks, and
-        # never changes: a learner that switched per call would alternate between two sets of Adam moments, and ranks that
-        # decided from their own shard could take different paths and drift apart
-        self._path = None
+        self._path = None                # see `path`
         self.graph_learn = False         # replay the learning round from a HIP graph once its sample count repeats
         if self.device.type == "cuda":
             self._fused_nets()           # re-homes the parameters into flat buffers NOW: before any graph captures their addresses
+        self._actor_stream = torch.cuda.Stream(device=self.critic.layers[0].weight.device) if self.device.type == "cuda" else None
         self._learn_graph = None
         self.action_size = action_size
         self.train_critic = train_critic
@@ -169,64 +167,95 @@ class PPOLearner(object):
             action = torch.where(u <= epsilon, rnd, action)
         return action, dist.log_prob(action)
 
+    @property
+    def path(self):
+        """Which trainer owns the optimiser state: "fused" (agents/fused_mlp.py, its own Adam moments) or "eager" (the torch
+        optimisers).  Decided ONCE, at the first learn() (None until then), from the smallest sample count over the ranks:
+        a learner that switched per call would alternate between two sets of Adam moments, and ranks that decided from
+        their own shard could take different paths and drift apart."""
+        return self._path
+
     def learn(self, states, actions, old_log_prob, returns, valid):
-        """critic_actor_learn (:314-323) on flattened [T*N] samples; returns (critic_loss, actor_loss)."""
-        hp = self.hp
-        S = states.shape[-1]
-        states = states.reshape(-1, S)
+        """critic_actor_learn (:314-323) on flattened [T*N] samples; returns (critic_loss, actor_loss).  The fused round
+        takes no mask, it sees valid samples only: a learner on the fused path drops the other rows from every batch."""
+        states = states.reshape(-1, states.shape[-1])
         actions = actions.reshape(-1)
         old_log_prob = old_log_prob.reshape(-1).detach()
         returns = returns.reshape(-1).detach()
         vmask = valid.reshape(-1) > 0
-        if states.is_cuda and states.shape[0] >= (1 << 15):
+        if self._path == "fused" or (states.is_cuda and states.shape[0] >= (1 << 15)):
             # rows of finished environments carry no sample (up to a third of a [T, N] rollout): drop them once
             # per round instead of pushing them through every one of the 20 forward/backward passes
             idx = torch.nonzero(vmask).reshape(-1)
             states, actions, old_log_prob, returns = states[idx], actions[idx], old_log_prob[idx], returns[idx]
             vmask = torch.ones(idx.shape[0], dtype=torch.bool, device=states.device)
         m = vmask.to(states.dtype)
-        # big GPU batches (rows of finished environments already dropped): the fused trainer (agents/fused_mlp.py)
         if self._path is None:
             n_min = fdist.all_reduce_scalar_min(torch.tensor(float(states.shape[0]), device=states.device))
             want = self.fused_learn and states.is_cuda and self._fused_nets() is not None
             self._path = "fused" if (want and float(n_min) >= float(1 << 15)) else "eager"
-        self._use_fused = self._path == "fused"
         if self.graph_learn and states.is_cuda and not fdist.is_distributed():
-            return self._learn_graphed(states, actions, old_log_prob, returns, m)
-        count = fdist.all_reduce_scalar_sum(m.sum())          # global number of samples
-        c_loss, a_loss = self._learn_body(states, actions, old_log_prob, returns, m, count)
+            c_loss, a_loss = self._learn_graphed(states, actions, old_log_prob, returns, m)
+        else:
+            count = fdist.all_reduce_scalar_sum(m.sum())          # global number of samples
+            c_loss, a_loss = self._learn_body(states, actions, old_log_prob, returns, m, count)
         return float(c_loss), float(a_loss)
 
     def _learn_body(self, states, actions, old_log_prob, returns, m, count):
-        """The 10 critic + 10 actor iterations of critic_actor_learn (:314-323); returns the last (critic, actor) losses
-        as tensors."""
-        hp = self.hp
-        if count is None:
-            count = m.sum()                # single process: the sample count as a device scalar (no host round trip)
-        if getattr(self, "_use_fused", False):
-            return self._learn_body_fused(states, actions, old_log_prob, returns, count)
-        with torch.no_grad():
-            advantages = returns - self.critic(states).squeeze(1)                       # :263
-        c_loss = a_loss = None
-        for _ in range(hp["learning_iterations_per_round_critic"]):
-            critic_out = self.critic(states).squeeze(1)
-            c_loss = (((critic_out - returns) ** 2) * m).sum() / count                 # F.mse_loss, :318
-            if self.train_critic:
-                self.critic_bucket.zero_()           # (gradients live in the all-reduce bucket)
-                c_loss.backward()
-                self.critic_bucket.all_reduce()
-                torch.nn.utils.clip_grad_norm_(self.critic.parameters(), hp["gradient_clipping_norm"])
-                self.critic_optimizer.step()
-            new_log_prob = self.actor_new.log_prob(states, actions)
-            terms = actor_loss_terms(new_log_prob, old_log_prob, advantages, hp["clip_epsilon"])
-            a_loss = -(terms * m).sum() / count                                         # -torch.mean(...), :351
-            self.actor_bucket.zero_()
-            a_loss.backward()
-            self.actor_bucket.all_reduce()
-            torch.nn.utils.clip_grad_norm_(self.actor_new.parameters(), hp["gradient_clipping_norm"])
-            self.actor_optimizer.step()
+        """One learning round on the trainer that owns the optimiser state; returns the last (critic, actor) losses as tensors.
+        count: the global sample count as a tensor (single process: m.sum(), a device scalar without a host round trip)."""
+        trainer = self._fused_trainer if self._path == "fused" else self._autograd_trainer
+        return self._round(returns, *trainer(states, actions, old_log_prob, returns, m, count))
+
+    def _round(self, returns, critic_start, critic_iterate, actor_iterate, scalar, side=None, side_reads=()):
+        """critic_actor_learn (:314-323): advantages from the critic as it is BEFORE the round, n iterations of each network,
+        equalise_policies; returns the last two losses, each through scalar().  What an iteration launches is the trainer's
+        business.  critic_start() gives (V(s), loss): the critic's first iteration where its forward pass hands V(s) out,
+        else a forward pass alone and loss None.  Once the advantages exist the two chains share no written tensor (the actor
+        never reads the critic's new parameters inside a round), so with a stream `side` the actor's is issued there."""
+        n = self.hp["learning_iterations_per_round_critic"]
+        values, c_loss = critic_start()
+        advantages = returns - values                                                              # :263
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream(side.device))
+        with torch.cuda.stream(side):                  # (None: the current stream)
+            for _ in range(n):
+                a_loss = actor_iterate(advantages)                                                 # :325-352
+        for _ in range(n - (c_loss is not None)):
+            c_loss = critic_iterate()                                                              # F.mse_loss, :318
+        if side is not None:
+            torch.cuda.current_stream(side.device).wait_stream(side)
+            for t in (advantages,) + side_reads:
+                t.record_stream(side)
         self.equalise_policies()
-        return c_loss.detach(), a_loss.detach()
+        return scalar(c_loss), scalar(a_loss)
+
+    def _autograd_trainer(self, states, actions, old_log_prob, returns, m, count):
+        """_round's callables on autograd and the torch optimisers; `m` masks the rows that carry no sample."""
+        def update(net, bucket, optimizer, loss):
+            bucket.zero_()               # (gradients live in the all-reduce bucket)
+            loss.backward()
+            bucket.all_reduce()
+            torch.nn.utils.clip_grad_norm_(net.parameters(), self.hp["gradient_clipping_norm"])
+            optimizer.step()
+
+        def critic_start():
+            with torch.no_grad():
+                return self.critic(states).squeeze(1), None
+
+        def critic_iterate():
+            c_loss = (((self.critic(states).squeeze(1) - returns) ** 2) * m).sum() / count     # F.mse_loss, :318
+            if self.train_critic:
+                update(self.critic, self.critic_bucket, self.critic_optimizer, c_loss)
+            return c_loss
+
+        def actor_iterate(advantages):
+            terms = actor_loss_terms(self.actor_new.log_prob(states, actions), old_log_prob, advantages, self.hp["clip_epsilon"])
+            a_loss = -(terms * m).sum() / count                                                 # -torch.mean(...), :351
+            update(self.actor_new, self.actor_bucket, self.actor_optimizer, a_loss)
+            return a_loss
+
+        return critic_start, critic_iterate, actor_iterate, torch.Tensor.detach
 
     def _learn_graphed(self, states, actions, old_log_prob, returns, m):
         """A learning round is ~1 200 small launches whose host cost rivals their device time.  With a fixed set
@@ -237,19 +266,18 @@ class PPOLearner(object):
         g = self._learn_graph
         if g is None or g["n"] != n:
             self._learn_graph = {"n": n, "graph": None}
-            c, a = self._learn_body(states, actions, old_log_prob, returns, m, None)
-            return float(c), float(a)
+            return self._learn_body(states, actions, old_log_prob, returns, m, m.sum())
         if g["graph"] is None:
             g["in"] = [t.clone() for t in (states, actions, old_log_prob, returns, m)]
             torch.cuda.synchronize(self.device)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="relaxed"):
-                g["out"] = self._learn_body(*g["in"], None)
+                g["out"] = self._learn_body(*g["in"], g["in"][4].sum())
             g["graph"] = graph
         for dst, src in zip(g["in"], (states, actions, old_log_prob, returns, m)):
             dst.copy_(src)
         g["graph"].replay()
-        return float(g["out"][0]), float(g["out"][1])
+        return g["out"]
 
     def _fused_nets(self):
         """(actor trainer, critic trainer) of agents/fused_mlp.py, created on first use; None when a network has another
@@ -264,81 +292,32 @@ class PPOLearner(object):
                 self._fused = (mk(self.actor_new), mk(self.critic))
         return self._fused or None
 
-    def _learn_body_fused(self, states, actions, old_log_prob, returns, count):
-        """_learn_body on the fused trainer: same iteration structure (:314-323), the dense layers on the library GEMMs,
-        everything between them in csrc/fjsp_ppo.hip; all samples are valid here (the caller dropped the others)."""
-        hp = self.hp
+    def _fused_trainer(self, states, actions, old_log_prob, returns, m, count):
+        """_round's callables on agents/fused_mlp.py: FusedMLP.iterate chooses the launches; every sample is valid (learn() dropped
+        the others).  Where the critic's first iteration hands V(s) out and `two_chains` is set, the actor's chain gets the side
+        stream: one chain's small launches (gradient finish, clip + Adam: 0.28 ms of a round) then run under the other's pass."""
         actor, critic = self._fused_nets()
         count = count.to(torch.float32).reshape(1)
-        if fdist.is_distributed():
-            reduce = lambda g: torch.distributed.all_reduce(g, op=torch.distributed.ReduceOp.SUM)
-        else:
-            reduce = None
+        reduce = (lambda g: torch.distributed.all_reduce(g, op=torch.distributed.ReduceOp.SUM)) if fdist.is_distributed() else None
+        how = dict(reduce=reduce, one_launch=self.mfma_learn)
         actions_f = actions.to(torch.float32).contiguous()
         states, returns, old_log_prob = states.contiguous(), returns.contiguous(), old_log_prob.contiguous()
-        c_loss = a_loss = None
-        one_launch = self.mfma_learn and actor.mfma_pass_supported() and critic.mfma_pass_supported()
-        # the advantages use the critic as it is BEFORE the round's updates (:263).  The first critic iteration's forward pass
-        # computes exactly those values: it hands them out and the separate forward pass (two library GEMMs) is not needed
-        values_from_first_pass = one_launch and reduce is None and self.train_critic
-        advantages = None
-        if not values_from_first_pass:
-            advantages = (returns - critic.forward(states).squeeze(1)).contiguous()                # :263
-        if values_from_first_pass and getattr(self, "two_chains", True):
-            # The critic's iterations and the actor's are two independent chains once the advantages exist (the actor never
-            # reads the critic's new parameters inside a round, :314-323): they are issued on two streams, so the small
-            # launches of one chain (gradient finish, clip + Adam: 0.28 ms of a round in sequence) run under the other's pass.
-            n_it = hp["learning_iterations_per_round_critic"]
-            main = torch.cuda.current_stream(states.device)
-            side = self.__dict__.get("_actor_stream")
-            if side is None:
-                side = self._actor_stream = torch.cuda.Stream(device=states.device)
+        from_first_pass = critic.hands_out_values(update=self.train_critic, **how)
+
+        def critic_iterate(values_out=None):
+            return critic.iterate(1, states, returns, None, None, count, update=self.train_critic, values_out=values_out, **how)
+
+        def critic_start():
+            if not from_first_pass:
+                return critic.forward(states).squeeze(1), None
             values = torch.empty(states.shape[0], dtype=torch.float32, device=states.device)
-            c_loss = critic.train_step(1, states, returns, None, None, count, values_out=values)           # F.mse_loss, :318
-            advantages = returns - values                                                                  # :263
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                for _ in range(n_it):
-                    a_loss = actor.train_step(0, states, actions_f, old_log_prob, advantages, count, hp["clip_epsilon"])   # :325-352
-            for _ in range(n_it - 1):
-                c_loss = critic.train_step(1, states, returns, None, None, count)
-            main.wait_stream(side)
-            for t in (advantages, actions_f, states, old_log_prob, count):
-                t.record_stream(side)
-            self.equalise_policies()
-            return c_loss[0].clone(), a_loss[0].clone()
-        for it in range(hp["learning_iterations_per_round_critic"]):
-            if one_launch and reduce is None:
-                # forward, loss, backward, clip + Adam of a network in three launches (single process: no all-reduce between)
-                if self.train_critic:
-                    if it == 0:
-                        values = torch.empty(states.shape[0], dtype=torch.float32, device=states.device)
-                        c_loss = critic.train_step(1, states, returns, None, None, count, values_out=values)   # F.mse_loss, :318
-                        advantages = returns - values                                                          # :263
-                    else:
-                        c_loss = critic.train_step(1, states, returns, None, None, count)
-                else:
-                    c_loss = critic.train_pass(1, states, returns, None, None, count)
-                a_loss = actor.train_step(0, states, actions_f, old_log_prob, advantages, count, hp["clip_epsilon"])   # :325-352
-                continue
-            if one_launch:
-                c_loss = critic.train_pass(1, states, returns, None, None, count)
-            else:
-                critic.forward(states)
-                c_loss = critic.critic_loss(returns, count)
-                if self.train_critic:
-                    critic.backward()
-            if self.train_critic:
-                critic.step(reduce)
-            if one_launch:
-                a_loss = actor.train_pass(0, states, actions_f, old_log_prob, advantages, count, hp["clip_epsilon"])
-            else:
-                actor.forward(states)
-                a_loss = actor.actor_loss(actions_f, old_log_prob, advantages, hp["clip_epsilon"], count)
-                actor.backward()
-            actor.step(reduce)
-        self.equalise_policies()
-        return c_loss[0].clone(), a_loss[0].clone()
+            return values, critic_iterate(values)
+
+        def actor_iterate(advantages):
+            return actor.iterate(0, states, actions_f, old_log_prob, advantages, count, self.hp["clip_epsilon"], **how)
+
+        side = self._actor_stream if from_first_pass and self.two_chains else None
+        return critic_start, critic_iterate, actor_iterate, lambda loss: loss[0].clone(), side, (actions_f, states, old_log_prob, count)
 
     def equalise_policies(self):
         """:372-375 with the AttributeError fixed."""

@@ -10,7 +10,7 @@ clipping + Adam in one pass over ONE flat parameter buffer (which is also the si
 `train_pass()` goes one step further for the reference's shapes (128 hidden units, <= 31 state features, <= 32
 outputs): forward + loss + backward in ONE launch on the f32 matrix cores with the activations resident in LDS
 (csrc/fjsp_mlp_train.hip; 2.1x the library-GEMM pass).  forward() / *_loss() / backward() remain for other shapes and
-for the forward-only advantage pass.
+for the forward-only advantage pass; iterate() is the one entry that picks among them for a learning iteration.
 
 The parameters stay the `nn.Parameter`s of the wrapped module -- re-homed as views of the flat buffer -- so
 everything else (acting, checkpoints, equalise_policies, the in-kernel actor of the fused rollout) sees them as before.
@@ -176,22 +176,42 @@ class FusedMLP(object):
         produces the squared norm for the clip and advances the step count.  values_out (critic only): f32[n] that
         receives V(x) as this pass's forward computed it, i.e. under the parameters before the update."""
         n = x.shape[0]
-        self.train_pass_buffers(n)
-        b = self._buf[("pass", n)]
-        if values_out is not None:
-            if int(mode) != 1 or values_out.dtype != torch.float32 or values_out.numel() != n or not values_out.is_contiguous() or values_out.device != x.device:
-                raise ValueError("train_step: values_out must be a contiguous f32[n] tensor on the samples' device (critic pass only)")
-            _capi.check(self._lib.fjsp_mlp_train_step_values(
-                1, _p(self.flat), _p(x), n, self.lin[0].in_features, self.H, self.out, _p(aux0), _p(aux1), _p(aux2), _p(count), float(clip_epsilon),
-                _p(b["partial"]), b["groups"], _p(b["loss_partial"]), _p(self.grad), _p(b["loss"]), _p(self.exp_avg), _p(self.exp_avg_sq),
-                self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, _p(self.step_count), _p(b["sumsq"]), _p(values_out), _stream(self.device.index)))
-            return b["loss"]
-        _capi.check(self._lib.fjsp_mlp_train_step(int(mode), _p(self.flat), _p(x), n, self.lin[0].in_features, self.H, self.out, _p(aux0),
-                                                  _p(aux1), _p(aux2), _p(count), float(clip_epsilon), _p(b["partial"]), b["groups"],
-                                                  _p(b["loss_partial"]), _p(self.grad), _p(b["loss"]), _p(self.exp_avg), _p(self.exp_avg_sq),
-                                                  self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, _p(self.step_count),
-                                                  _p(b["sumsq"]), _stream(self.device.index)))
+        b = self.train_pass_buffers(n)
+        args = (int(mode), _p(self.flat), _p(x), n, self.lin[0].in_features, self.H, self.out, _p(aux0), _p(aux1), _p(aux2), _p(count),
+                float(clip_epsilon), _p(b["partial"]), b["groups"], _p(b["loss_partial"]), _p(self.grad), _p(b["loss"]), _p(self.exp_avg),
+                _p(self.exp_avg_sq), self.max_norm, self.lr, self.betas[0], self.betas[1], self.eps, _p(self.step_count), _p(b["sumsq"]))
+        if values_out is None:
+            _capi.check(self._lib.fjsp_mlp_train_step(*args, _stream(self.device.index)))
+        elif int(mode) != 1 or values_out.dtype != torch.float32 or values_out.numel() != n or not values_out.is_contiguous() or values_out.device != x.device:
+            raise ValueError("train_step: values_out must be a contiguous f32[n] tensor on the samples' device (critic pass only)")
+        else:
+            _capi.check(self._lib.fjsp_mlp_train_step_values(*args, _p(values_out), _stream(self.device.index)))
         return b["loss"]
+
+    # -- one learning iteration: the trainer chooses the launches ----------------------------------------------------
+    def hands_out_values(self, reduce=None, update=True, one_launch=True):
+        """Whether iterate() with these arguments runs train_step(), the one form whose forward pass can hand V(x) out."""
+        return one_launch and self.mfma_pass_supported() and update and reduce is None
+
+    @torch.no_grad()
+    def iterate(self, mode, x, aux0, aux1, aux2, count, clip_epsilon=0.0, reduce=None, update=True, values_out=None, one_launch=True):
+        """One iteration on the samples (arguments as train_pass()): returns the loss (f32[1]); with `update`, steps the parameters
+        after `reduce` (step()'s all_reduce) summed the gradient over the ranks.  Runs train_step() where hands_out_values(), else
+        train_pass() (+ step()) for the shapes it covers, else, or with one_launch=False, forward() + loss + backward() (+ step())."""
+        if self.hands_out_values(reduce, update, one_launch):
+            return self.train_step(mode, x, aux0, aux1, aux2, count, clip_epsilon, values_out=values_out)
+        if values_out is not None:
+            raise ValueError("iterate: this iteration does not run train_step (see hands_out_values), it cannot fill values_out")
+        if one_launch and self.mfma_pass_supported():
+            loss = self.train_pass(mode, x, aux0, aux1, aux2, count, clip_epsilon)
+        else:
+            self.forward(x)
+            loss = self.critic_loss(aux0, count) if int(mode) == 1 else self.actor_loss(aux0, aux1, aux2, clip_epsilon, count)
+            if update:
+                self.backward()
+        if update:
+            self.step(reduce)
+        return loss
 
     # -- optimiser step --------------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -481,7 +481,7 @@ def test_fused_ppo_learning_matches_autograd(torch_gpu):
             assert torch.equal(pr, pf)
         lr_ = ref.learn(states, actions, old_lp, returns, valid)
         lf_ = fus.learn(states, actions, old_lp, returns, valid)
-        assert fus._use_fused and not ref._use_fused
+        assert fus.path == "fused" and ref.path == "eager"
         np.testing.assert_allclose(lf_, lr_, rtol=max(rtol, 1e-4), atol=1e-5)
         for name, nr, nf in (("actor", ref.actor_new, fus.actor_new), ("critic", ref.critic, fus.critic), ("actor_old", ref.actor_old, fus.actor_old)):
             for pr, pf in zip(nr.parameters(), nf.parameters()):
@@ -491,9 +491,9 @@ def test_fused_ppo_learning_matches_autograd(torch_gpu):
     # moments), it does not wake the torch optimisers up
     small = slice(0, 2000)
     fus.learn(states[small], actions[small], old_lp[small], returns[small], valid[small])
-    assert fus._path == "fused" and fus._use_fused and len(fus.actor_optimizer.state) == 0 and len(fus.critic_optimizer.state) == 0
+    assert fus.path == "fused" and len(fus.actor_optimizer.state) == 0 and len(fus.critic_optimizer.state) == 0
     ref.learn(states, actions, old_lp, returns, valid)
-    assert ref._path == "eager" and not ref._use_fused
+    assert ref.path == "eager"
     # the parameters live in ONE flat buffer (the all-reduce bucket), the module still owns them
     actor_tr, _ = fus._fused_nets()
     assert actor_tr.flat.numel() == sum(p.numel() for p in fus.actor_new.parameters())

@@ -449,7 +449,7 @@ def test_learner_with_shapes_the_kernels_refuse_trains_eagerly(torch_gpu, hidden
         before = [p.detach().clone() for p in ln.actor_new.parameters()]
         c_loss, a_loss = ln.learn(states, actions, old_lp, returns, valid)
         assert np.isfinite(c_loss) and np.isfinite(a_loss)
-        assert ln._path == "eager"
+        assert ln.path == "eager"
         assert any(not torch.equal(b, p) for b, p in zip(before, ln.actor_new.parameters()))
         learners.append(ln)
     torch.cuda.synchronize()

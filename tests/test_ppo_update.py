@@ -117,7 +117,7 @@ def _worker(rank, world, port, tmp):
     # the trainer path (one optimiser state per learner) was agreed between the ranks at this first round: the minimum
     # sample count over the ranks decides, not the rank's own shard
     from deep_reinforcement_learning_for_fjsp_amd import distributed as fdist
-    assert L._path == "eager"
+    assert L.path == "eager"
     assert float(fdist.all_reduce_scalar_min(torch.tensor(float(100 + rank)))) == 100.0
     torch.save([p.detach() for p in list(L.actor_new.parameters()) + list(L.critic.parameters())],
                os.path.join(tmp, "params_rank%d.pt" % rank))
@@ -155,12 +155,12 @@ def test_trainer_path_is_fixed_at_the_first_round():
     from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import PPOLearner
     torch.manual_seed(3)
     L = PPOLearner(20, 30, device="cpu", seed=4)
-    assert L._path is None
+    assert L.path is None
     for n in (64, 7, 300):
         st = torch.randn(n, 20)
         a, lp = L.act(st)
         L.learn(st, a, lp, torch.randn(n), torch.ones(n))
-        assert L._path == "eager" and not L._use_fused
+        assert L.path == "eager"
     assert len(L.actor_optimizer.state) > 0
 
 
