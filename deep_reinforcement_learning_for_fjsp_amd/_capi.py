@@ -101,6 +101,7 @@ SIGNATURES = {
     "fjsp_env_step_bytes": (_i64, [_vp]),
     "fjsp_env_kernel_family": (_i32, [_vp]),
     "fjsp_env_row_build": (C.c_int, [_vp, _i32, _vp]),
+    "fjsp_env_policy_build": (C.c_int, [_vp, _i32, _vp]),
     "fjsp_env_set_lp_threads": (C.c_int, [_vp, _i32]),
     "fjsp_env_lp_solves": (_i64, [_vp]),
     "fjsp_env_lp_on_device": (_i32, [_vp]),

@@ -358,7 +358,7 @@ class FusedSampler(object):
 def fused_policy_rollout(env, learner, memory, fused, old_log_prob, exploration, T):
     """The whole rollout loop (MPPPO.py:245-252) in ONE launch of fjsp_env_rollout_policy: the actor runs inside the
     environment kernel, rows go straight into `memory`.  Returns False when the batch / network shape is not
-    supported (multi-order instances, K > 64, another network size): the caller falls back to the per-step loop."""
+    supported (multi-order instances, another network size): the caller falls back to the per-step loop."""
     from ... import _capi
     import ctypes as C
     ap = native_actor_params(learner.actor_new)
@@ -527,7 +527,9 @@ class PPO(Base_Agent):
         self.use_graph = use_graph
         self.fused_sampling = fused_sampling or fused_rollout
         # fused_rollout: the whole rollout loop in one launch with the actor inside the environment kernel
-        # (fjsp_env_rollout_policy); falls back to the per-step loop for shapes the kernel does not take
+        # (fjsp_env_rollout_policy: every single-order batch, up to 256 operation types and as many jobs as create
+        # admits); falls back to the per-step loop for an actor of another shape than S -> 128 -> 128 -> A and for
+        # batches with order arrivals
         self.fused_rollout = fused_rollout
         self.learner_graph = use_graph
         self.device = environment.device

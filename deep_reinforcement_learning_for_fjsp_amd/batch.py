@@ -307,6 +307,14 @@ class EnvBatch(object):
         check(self._lib.fjsp_env_row_build(self._h, 1 if fused else 0, out))
         return dict(early=int(out[0]), mpc=int(out[1]), resident=int(out[2]))
 
+    def policy_build(self, state_size):
+        """The workgroup the in-launch policy kernels (fjsp_env_rollout_policy, fjsp_env_play_policy) run for this batch with
+        an actor of `state_size` inputs, as their launchers decide it (fjsp_env_policy_build): dict(envs_per_workgroup=16/8/
+        4/2/1, lds_bytes=..., kc=1/2/4).  FjspError (FJSP_E_UNSUPPORTED) for a batch they refuse: order arrivals."""
+        out = (C.c_int32 * 3)()
+        check(self._lib.fjsp_env_policy_build(self._h, int(state_size), out))
+        return dict(envs_per_workgroup=int(out[0]), lds_bytes=int(out[1]), kc=int(out[2]))
+
     def env_seed(self, e):
         """random.choice stream seed of (local) env e (matches open_env() in fjsp_kernels.hip)."""
         return (self.rng_seed + (self.first_env + e) * ENV_SEED_STRIDE) & (2 ** 64 - 1)

@@ -235,7 +235,11 @@ int launch_lp_device(const DevBatch &b, const uint32_t *count_dev, int count_hos
 // policy inside the launch (fjsp_policy.h)
 struct ActorParams;
 struct PolicyRolloutIO;
-size_t policy_rollout_lds_bytes(const DevBatch &b, int S);
+size_t policy_rollout_lds_bytes(const DevBatch &b, int S, int W);     // dynamic LDS of a workgroup of W environments
+// the workgroup both policy launchers run and fjsp_env_policy_build reports, decided in one place from the batch and the
+// actor's state size (not known at create, hence not in LaunchPlan): envs 0 = not even one environment fits
+struct PolicyGeometry { int envs; size_t lds; };
+PolicyGeometry policy_geometry(const DevBatch &b, int S);
 int launch_actor_forward(const ActorParams &ap, const double *state, int n, float *probs, hipStream_t st);
 int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st,
                           const SchedRec &rec = SchedRec{});

@@ -586,6 +586,16 @@ ActorParams actor_of(const fjsp_actor_params *a) {
     p.S = a->state_size; p.H = a->hidden; p.A = a->n_actions;
     return p;
 }
+// What keeps the policy kernels from running this batch with an actor of state size S, nullptr where nothing does; *g is
+// the workgroup they run then (policy_geometry, fjsp_kernels.hip).  Both launches and fjsp_env_policy_build ask here.
+const char *policy_refusal(const fjsp_env *e, int S, PolicyGeometry *g) {
+    if (e->b.mord)
+        return "the batch has order arrivals (their LPs are served between launches): single-order batches only";
+    *g = policy_geometry(e->b, S);
+    if (g->envs <= 0)
+        return "one environment's LDS slice does not fit the 160 KB of a CU beside the actor's weights";
+    return nullptr;
+}
 }  // namespace
 
 int fjsp_actor_forward(const fjsp_actor_params *actor, const double *d_state, int32_t n, float *d_probs, void *stream) {
@@ -608,9 +618,8 @@ int fjsp_env_rollout_policy(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_par
     if (!actor_ok(actor) || actor->state_size != e->b.state_size) {
         set_error("fjsp_env_rollout_policy: the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32)"); return FJSP_E_UNSUPPORTED;
     }
-    if (e->b.mord || e->b.KC != 1 || policy_rollout_lds_bytes(e->b, actor->state_size) > 160 * 1024) {
-        set_error("fjsp_env_rollout_policy: single-order batches of at most 64 operation types only"); return FJSP_E_UNSUPPORTED;
-    }
+    PolicyGeometry geo{};
+    if (const char *why = policy_refusal(e, actor->state_size, &geo)) { set_error(std::string("fjsp_env_rollout_policy: ") + why); return FJSP_E_UNSUPPORTED; }
     DeviceGuard guard(e->device);
     PolicyRolloutIO io;
     io.state_in = d_state_in; io.epsilon = d_epsilon; io.seed = d_seed; io.pair_div = pair_div;
@@ -640,9 +649,8 @@ int fjsp_env_play_policy(fjsp_env *e, const fjsp_actor_params *actor, int32_t pa
     }
     if (n_greedy < e->b.N && !d_seed) { set_error("fjsp_env_play_policy: sampling envs need d_seed"); return FJSP_E_ARG; }
     if (!d_state_src && n_state_in < e->b.N) { set_error("fjsp_env_play_policy: d_state_in has fewer rows than the batch"); return FJSP_E_ARG; }
-    if (e->b.mord || e->b.KC != 1 || policy_rollout_lds_bytes(e->b, actor->state_size) > 160 * 1024) {
-        set_error("fjsp_env_play_policy: single-order batches of at most 64 operation types only"); return FJSP_E_UNSUPPORTED;
-    }
+    PolicyGeometry geo{};
+    if (const char *why = policy_refusal(e, actor->state_size, &geo)) { set_error(std::string("fjsp_env_play_policy: ") + why); return FJSP_E_UNSUPPORTED; }
     DeviceGuard guard(e->device);
     PolicyPlayIO io;
     io.state_in = d_state_in; io.state_src = d_state_src; io.n_state_in = n_state_in; io.seed = d_seed; io.first = d_first;
@@ -651,6 +659,15 @@ int fjsp_env_play_policy(fjsp_env *e, const fjsp_actor_params *actor, int32_t pa
     if (launch_play_policy(e->b, actor_of(actor), io, d_mo, T, (hipStream_t)stream, e->sched) != 0) {
         set_error("play_policy_kernel launch failed"); return FJSP_E_HIP;
     }
+    return FJSP_OK;
+}
+
+int fjsp_env_policy_build(const fjsp_env *e, int32_t state_size, int32_t *out3) {
+    if (!e || !out3) { set_error("fjsp_env_policy_build: null argument"); return FJSP_E_ARG; }
+    if (state_size < 1 || state_size > 32) { set_error("fjsp_env_policy_build: state_size outside 1..32"); return FJSP_E_ARG; }
+    PolicyGeometry geo{};
+    if (const char *why = policy_refusal(e, state_size, &geo)) { set_error(std::string("fjsp_env_policy_build: ") + why); return FJSP_E_UNSUPPORTED; }
+    out3[0] = geo.envs; out3[1] = (int32_t)geo.lds; out3[2] = e->b.KC;
     return FJSP_OK;
 }
 

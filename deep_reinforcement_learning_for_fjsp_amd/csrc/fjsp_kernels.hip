@@ -1644,6 +1644,24 @@ __global__ __launch_bounds__(1024) void actor_forward_kernel(ActorParams ap, con
 #define FJSP_REC 1
 #include "fjsp_kernels_dispatch.inc"
 #undef FJSP_REC
+// the kernels with the actor inside: sixteen environments per workgroup (FJSP_PW 0), then the build whose workgroup size
+// follows from LDS (FJSP_PW 1), each plain and recording
+#define FJSP_PW 0
+#define FJSP_REC 0
+#include "fjsp_kernels_policy.inc"
+#undef FJSP_REC
+#define FJSP_REC 1
+#include "fjsp_kernels_policy.inc"
+#undef FJSP_REC
+#undef FJSP_PW
+#define FJSP_PW 1
+#define FJSP_REC 0
+#include "fjsp_kernels_policy.inc"
+#undef FJSP_REC
+#define FJSP_REC 1
+#include "fjsp_kernels_policy.inc"
+#undef FJSP_REC
+#undef FJSP_PW
 
 // Multi-order: finish the step of every env parked at an order arrival.  The host service has solved the
 // fluid LP of the env's live state (class_FJSSP.py:239) and left x in the env record; this kernel runs
@@ -1802,40 +1820,64 @@ int launch_rollout(const DevBatch &b, const LaunchPlan &p, const uint8_t *action
     });
 }
 
-size_t policy_rollout_lds_bytes(const DevBatch &b, int S) {
+size_t policy_rollout_lds_bytes(const DevBatch &b, int S, int W) {
     return ((actor_lds_floats(S) * 4 + 255) & ~(size_t)255) +
-           16 * (lds_bytes_per_wave(b.JP, b.MP, b.KP, false) + (32 + kActorH + kActorAP) * 4);
+           (size_t)W * (lds_bytes_per_wave(b.JP, b.MP, b.KP, false) + (32 + kActorH + kActorAP) * 4);
+}
+// The workgroup of the policy kernels: the actor's weights once, then one LDS slice and one actor scratch per environment;
+// the most environments (one wave each) of 16, 8, 4, 2, 1 that fit the CU's 160 KB.  Sixteen is the 1024-thread build,
+// the others share the build of at most 512 threads (fjsp_kernels_policy.inc).
+PolicyGeometry policy_geometry(const DevBatch &b, int S) {
+    for (int W = 16; W >= 1; W >>= 1) {
+        const size_t lds = policy_rollout_lds_bytes(b, S, W);
+        if (lds <= 160 * 1024) return PolicyGeometry{W, lds};
+    }
+    return PolicyGeometry{0, policy_rollout_lds_bytes(b, S, 1)};
 }
 int launch_actor_forward(const ActorParams &ap, const double *state, int n, float *probs, hipStream_t st) {
     const size_t lds = actor_lds_floats(ap.S) * 4 + 16 * (32 + kActorH + kActorAP) * 4;
     return launch(&actor_forward_kernel, grid_for16(n), dim3(1024), lds, st, ap, state, n, probs);
 }
-// the policy kernels: 16 environments per workgroup; built for one chunk (K <= 64) of the single-order variants only
-int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st,
-                          const SchedRec &rec) {
-    if (b.mord || b.KC != 1) return -1;                 // order arrivals need the host LP service between steps; K <= 64
-    const size_t lds = policy_rollout_lds_bytes(b, ap.S);
+// the policy kernels: the single-order variants only (order arrivals need the LP service between steps); -1 where
+// policy_geometry() finds no workgroup -- the entry points have refused those batches already
+template <class F16, class FW>
+static int dispatch_policy(const DevBatch &b, const ActorParams &ap, F16 &&f16, FW &&fw) {
+    if (b.mord) return -1;
+    const PolicyGeometry g = policy_geometry(b, ap.S);
+    if (g.envs <= 0) return -1;
     return dispatch(b, [&](auto kc, auto v) {
         constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-        if constexpr (!is_mord_v<V> && KC == 1)
-            return launch_rec(&rollout_policy_kernel<KC, V>, &rollout_policy_rec_kernel<KC, V>, rec, grid_for16(b.N), dim3(1024), lds, st, b, ap,
-                              io, mo, T);
-        else
-            return -1;
+        if constexpr (!is_mord_v<V>) {
+            if (g.envs < 16) return fw(kc, v, grid_for_envs(b.N, g.envs), dim3(64u * (unsigned)g.envs), g.lds);
+            // (sixteen slices of two chunks or more never fit beside the actor: that build exists for one chunk only)
+            if constexpr (KC == 1) return f16(kc, v, grid_for16(b.N), dim3(1024), g.lds);
+        }
+        return -1;
     });
+}
+int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st,
+                          const SchedRec &rec) {
+    return dispatch_policy(b, ap,
+        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            return launch_rec(&rollout_policy_kernel<KC, V>, &rollout_policy_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+        },
+        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            return launch_rec(&rollout_policy_w_kernel<KC, V>, &rollout_policy_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+        });
 }
 int launch_play_policy(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, hipStream_t st,
                        const SchedRec &rec) {
-    if (b.mord || b.KC != 1) return -1;                 // as launch_rollout_policy
-    const size_t lds = policy_rollout_lds_bytes(b, ap.S);
-    return dispatch(b, [&](auto kc, auto v) {
-        constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-        if constexpr (!is_mord_v<V> && KC == 1)
-            return launch_rec(&play_policy_kernel<KC, V>, &play_policy_rec_kernel<KC, V>, rec, grid_for16(b.N), dim3(1024), lds, st, b, ap, io,
-                              mo, T);
-        else
-            return -1;
-    });
+    return dispatch_policy(b, ap,
+        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            return launch_rec(&play_policy_kernel<KC, V>, &play_policy_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+        },
+        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            return launch_rec(&play_policy_w_kernel<KC, V>, &play_policy_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+        });
 }
 
 // (only the two multi-order variants have an arrival_kernel: its own two-way choice, not dispatch())

@@ -1,8 +1,8 @@
 // The wave-family kernels that dispatch, included twice by fjsp_kernels.hip: with FJSP_REC 0 they are step_kernel /
-// rollout_kernel / rollout_policy_kernel, with FJSP_REC 1 their recording builds step_rec_kernel / rollout_rec_kernel /
-// rollout_policy_rec_kernel, which also store every dispatch in `rec` (SchedRec, fjsp_env_record_schedule).  One text for
-// both keeps the plain kernels' code exactly what it is without recording (a shared __device__ body inlined into both
-// changes the optimiser's pass order, hence the code).
+// rollout_kernel, with FJSP_REC 1 their recording builds step_rec_kernel / rollout_rec_kernel, which also store every
+// dispatch in `rec` (SchedRec, fjsp_env_record_schedule).  One text for both keeps the plain kernels' code exactly what it
+// is without recording (a shared __device__ body inlined into both changes the optimiser's pass order, hence the code).
+// The kernels with the actor inside the launch follow the same scheme in fjsp_kernels_policy.inc.
 #if FJSP_REC
 #define FJSP_K(name) name##_rec_kernel
 #define FJSP_REC_ARG , SchedRec rec
@@ -185,149 +185,6 @@ __global__ __launch_bounds__(256, (KC == 1 && V == FJSP_VARIANT_SO_FJSSP) ? 4 : 
         }
     }
     store_dynamic<KC, V>(w, true);
-}
-
-// The T-step rollout with the actor inside the launch (replaces the per-step loop MPPPO.py:245-252: policy
-// inference, sampling, env.step, buffer append): one wavefront per environment for the whole episode, sixteen
-// per workgroup sharing the actor's weights in LDS.  Per step: actor_probs on the current state, sample_action
-// by lane 0 (the counter-based stream of fjsp_policy_sample: same seed, same actions as the per-step path),
-// the environment step, the buffer row.  Finished environments idle; their rows are marked invalid.
-template <int KC, int V>
-__global__ __launch_bounds__(1024) void FJSP_K(rollout_policy)(DevBatch b, ActorParams ap, PolicyRolloutIO io, const double *mo, int T FJSP_REC_ARG) {
-    constexpr bool REC = FJSP_REC != 0;
-    FJSP_REC_LOCAL
-    float *lds = reinterpret_cast<float *>(fjsp_lds);
-    actor_lds_fill(lds, ap, (int)threadIdx.x, (int)blockDim.x);
-    __syncthreads();                                   // (the only workgroup barrier: waves may leave after it)
-    const int wave = uni((int)(threadIdx.x >> 6));
-    const int env = blockIdx.x * 16 + wave;
-    if (env >= b.N) return;
-    const uint32_t env_stride = (uint32_t)lds_bytes_per_wave(b.JP, b.MP, b.KP, false);
-    unsigned char *wave_lds = fjsp_lds + ((actor_lds_floats(ap.S) * 4 + 255) & ~(size_t)255) +
-                              (size_t)wave * (env_stride + (32 + kActorH + kActorAP) * 4);
-    float *xs = reinterpret_cast<float *>(wave_lds + env_stride);
-    float *hs = xs + 32, *ps = hs + kActorH;
-    W<KC, V> w;
-    open_env<KC, V>(w, &b, env, wave_lds, false, true);
-    if constexpr (REC) { w.rec = rec.rec; w.rec_cap = rec.cap; }
-    compute_params<KC, V>(w);
-    const int S = ap.S, A = ap.A, N = b.N;
-    if (w.lane < S) xs[w.lane] = (float)io.state_in[(size_t)env * S + w.lane];
-    const float eps = io.epsilon[0];
-    const uint64_t seed = io.seed[0];
-    const double *mo_e = mo ? mo + (size_t)env * 4 : nullptr;
-    wave_sync();
-    for (int t = 0; t < T; ++t) {
-        const size_t row = (size_t)t * N + env;
-        const bool live = !w.done && !(w.status & (FJSP_ST_BAD_TASK_RULE | FJSP_ST_BAD_MACHINE_RULE | FJSP_ST_NO_EVENT));
-        if (!live) {
-            if (w.done) w.status |= FJSP_ST_STEP_AFTER_DONE;       // what the per-step loop flags for the same launches
-            // (rows of finished environments are masked by `valid`; they still get finite contents -- the last state,
-            // like the per-step loop leaves there -- because masked arithmetic multiplies them by zero)
-            if (w.lane < S) { io.o_state[row * S + w.lane] = xs[w.lane]; io.o_next[row * S + w.lane] = xs[w.lane]; }
-            if (w.lane == 0) {
-                io.o_valid[row] = 0.0f; io.o_reward[row] = 0.0f; io.o_done[row] = 1.0f;
-                io.o_actions[row * 2] = 0.0f; io.o_actions[row * 2 + 1] = 0.0f; io.o_flat[row] = 0.0f; io.o_logp[row] = 0.0f;
-            }
-            continue;
-        }
-        if (w.lane < S) io.o_state[row * S + w.lane] = xs[w.lane];
-        actor_probs(lds, xs, hs, ps, S, A);
-        int action = 0;
-        float logp = 0.0f;
-        if (w.lane == 0) {
-            const SampledAction sa = sample_action(ps, A, eps, seed, (uint64_t)t, env);
-            action = sa.action; logp = sa.log_prob;
-        }
-        action = uni(action);
-        const int a0 = io.pair_div > 0 ? action / io.pair_div : action, a1 = io.pair_div > 0 ? action % io.pair_div : 0;
-        int k_sel, m_sel;
-        const double reward = env_step<KC, V, 2, REC>(w, &b, a0, a1, mo_e, io.state_last, &k_sel, &m_sel, true, xs);
-        if (w.lane < S) io.o_next[row * S + w.lane] = xs[w.lane];
-        if (w.lane == 0) {
-            io.o_actions[row * 2] = (float)a0; io.o_actions[row * 2 + 1] = (float)a1;
-            io.o_reward[row] = (float)reward; io.o_done[row] = (float)w.done; io.o_valid[row] = 1.0f;
-            io.o_flat[row] = (float)action; io.o_logp[row] = logp;
-        }
-    }
-    store_dynamic<KC, V>(w, false, false);
-}
-
-// Decoding a trained policy (fjsp_env_play_policy): every environment plays to the end of its episode with the actor
-// inside the launch, as rollout_policy above but without buffer rows.  One wavefront per environment, sixteen per
-// workgroup sharing the actor's weights in LDS.  Per step: actor_probs, then the action -- envs below n_greedy take the
-// first index of the largest probability (torch.argmax), the others draw from the stream of fjsp_policy_sample with
-// epsilon 0 (counter = step index of this call, env = local index) -- then the environment step.  Step 0 applies
-// io.first instead where given.  The start observation is row state_src[env] of state_in: v(t-1) of the state vector is
-// not in the env record, so a branch batch reads its source's rows through the map.  A wave leaves its loop once its env
-// is done or carries an error bit; T only bounds the loop.
-template <int KC, int V>
-__global__ __launch_bounds__(1024) void FJSP_K(play_policy)(DevBatch b, ActorParams ap, PolicyPlayIO io, const double *mo, int T FJSP_REC_ARG) {
-    constexpr bool REC = FJSP_REC != 0;
-    FJSP_REC_LOCAL
-    float *lds = reinterpret_cast<float *>(fjsp_lds);
-    actor_lds_fill(lds, ap, (int)threadIdx.x, (int)blockDim.x);
-    __syncthreads();                                   // (the only workgroup barrier: waves may leave after it)
-    const int wave = uni((int)(threadIdx.x >> 6));
-    const int env = blockIdx.x * 16 + wave;
-    if (env >= b.N) return;
-    const int S = ap.S, A = ap.A, N = b.N;
-    const int src = uni(io.state_src ? io.state_src[env] : env);
-    if (src < 0 || src >= io.n_state_in) {             // (refused by the host entry; an env given no start row stays put)
-        if (__lane_id() == 0) io.steps_out[env] = 0;
-        return;
-    }
-    const uint32_t env_stride = (uint32_t)lds_bytes_per_wave(b.JP, b.MP, b.KP, false);
-    unsigned char *wave_lds = fjsp_lds + ((actor_lds_floats(ap.S) * 4 + 255) & ~(size_t)255) +
-                              (size_t)wave * (env_stride + (32 + kActorH + kActorAP) * 4);
-    float *xs = reinterpret_cast<float *>(wave_lds + env_stride);
-    float *hs = xs + 32, *ps = hs + kActorH;
-    W<KC, V> w;
-    open_env<KC, V>(w, &b, env, wave_lds, false, true);
-    if constexpr (REC) { w.rec = rec.rec; w.rec_cap = rec.cap; }
-    compute_params<KC, V>(w);
-    const double x0 = w.lane < S ? io.state_in[(size_t)src * S + w.lane] : 0.0;
-    if (w.lane < S) xs[w.lane] = (float)x0;
-    const uint64_t seed = io.seed ? io.seed[0] : 0;
-    const bool greedy = env < io.n_greedy;
-    const double *mo_e = mo ? mo + (size_t)env * 4 : nullptr;
-    wave_sync();
-    double reward = 0.0;
-    int t = 0;
-    for (; t < T; ++t) {
-        if (w.done || (w.status & (FJSP_ST_BAD_TASK_RULE | FJSP_ST_BAD_MACHINE_RULE | FJSP_ST_NO_EVENT))) break;
-        int a0, a1;
-        if (t == 0 && io.first) {
-            a0 = uni((int)io.first[(size_t)env * 2]); a1 = uni((int)io.first[(size_t)env * 2 + 1]);
-        } else {
-            actor_probs(lds, xs, hs, ps, S, A);
-            int action = 0;
-            if (w.lane == 0) {
-                if (greedy) {
-                    float best = ps[0];
-                    for (int a = 1; a < A; ++a)
-                        if (ps[a] > best) { best = ps[a]; action = a; }
-                } else {
-                    action = sample_action(ps, A, 0.0f, seed, (uint64_t)t, env).action;
-                }
-            }
-            action = uni(action);
-            a0 = io.pair_div > 0 ? action / io.pair_div : action; a1 = io.pair_div > 0 ? action % io.pair_div : 0;
-        }
-        int k_sel, m_sel;
-        reward = env_step<KC, V, 2, REC>(w, &b, a0, a1, mo_e, io.state_last, &k_sel, &m_sel, true, xs);
-        if (io.actions_out && w.lane == 0) {
-            const size_t row = (size_t)t * N + env;
-            io.actions_out[row * 2] = (uint8_t)a0; io.actions_out[row * 2 + 1] = (uint8_t)a1;
-        }
-    }
-    if (w.lane == 0) {
-        io.steps_out[env] = t;
-        io.done_last[env] = (uint8_t)w.done;
-        if (t > 0) io.reward_last[env] = reward;
-    }
-    if (t == 0 && w.lane < S) io.state_last[(size_t)env * S + w.lane] = x0;     // (an env that took no step keeps its start row)
-    store_dynamic<KC, V>(w, false, false);
 }
 
 #undef FJSP_K

@@ -12,10 +12,12 @@ template <int I>
 using int_c = std::integral_constant<int, I>;
 
 // grids: four environments (waves of 64 lanes, or 16-lane rows of one wave) per 256 threads; 16 environments per
-// 1024-thread workgroup of the policy kernels; the row family's waves, wpb of them to a workgroup
+// 1024-thread workgroup of the policy kernels, or W of them to one of 64 W threads (policy_geometry); the row family's
+// waves, wpb of them to a workgroup
 inline unsigned waves_for(int N) { return (unsigned)((N + 3) / 4); }
 inline dim3 grid_for(int N) { return dim3(waves_for(N)); }
 inline dim3 grid_for16(int n) { return dim3((unsigned)((n + 15) / 16)); }
+inline dim3 grid_for_envs(int n, int W) { return dim3((unsigned)((n + W - 1) / W)); }
 inline dim3 grid_for_rows(int N, unsigned wpb) { return dim3((waves_for(N) + wpb - 1) / wpb); }
 
 // Launch `kernel`; 0 = launched.  Dynamic LDS beyond the 64 KB default must be allowed per kernel (up to the 160 KB of a

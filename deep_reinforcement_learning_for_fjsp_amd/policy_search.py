@@ -1,10 +1,11 @@
 """Decoding a trained dispatching policy on the device: greedy play, best-of-K sampling, and a policy rollout lookahead.
 
-All three share one launch, fjsp_env_play_policy (play_policy_kernel, csrc/fjsp_kernels_dispatch.inc): every env plays to
+All three share one launch, fjsp_env_play_policy (play_policy_kernel, csrc/fjsp_kernels_policy.inc): every env plays to
 the end of its episode with the actor evaluated inside the environment kernel and no rollout-buffer traffic.  The actor is
 an agents.MPPPO ActorNet; the kernel takes those of the in-kernel shape (state_size <= 32 -> 128 -> 128 -> n_actions
-<= 32).  Other actors (MPPPO's 200 x 5 nets), order-arrival batches and batches of more than 64 operation types run the
-same decoding as a per-step loop (actor, argmax or fjsp_policy_sample, one env step), only more slowly.
+<= 32) on every single-order batch, whatever its operation types and jobs (EnvBatch.policy_build reports the workgroup it
+runs).  Other actors (MPPPO's 200 x 5 nets) and order-arrival batches run the same decoding as a per-step loop (actor,
+argmax or fjsp_policy_sample, one env step), only more slowly.
 
 - play: every env to the end, greedy (argmax of the actor's probabilities) or sampled (epsilon 0).
 - best_of: k episodes per env in a k x N branch batch, block 0 greedy and the others sampled; each source env ends its
@@ -75,7 +76,8 @@ def play(batch, actor, greedy=True, seed=0, mo=None, max_steps=None, first=None,
     (default: the largest count of remaining operations).  first: u8[N, 2] actions in the env encoding that step 0
     applies instead of the actor's.  state_in / state_src: env i starts from row state_src[i] of state_in (f64[M, S];
     default: the batch's own state rows, row i).  record_actions: also return the applied actions.
-    fused=False, or an actor / batch the kernel refuses, runs the per-step loop instead; with an actor of the in-kernel
+    fused=False, or what the kernel refuses (an actor of another shape than state_size <= 32 -> 128 -> 128 -> n_actions
+    <= 32, a batch with order arrivals), runs the per-step loop instead; with an actor of the in-kernel
     shape it takes the probabilities from the same device code (fjsp_actor_forward), so both give the same episode bit
     for bit.
 

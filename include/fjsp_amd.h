@@ -465,8 +465,10 @@ int fjsp_actor_forward(const fjsp_actor_params *actor, const double *d_state, in
  * (as fjsp_rollout_append writes it; rows of envs that had finished are marked invalid, buf's length becomes T).
  * d_state_in f64[N][S]: the states the rollout starts from (what fjsp_env_reset returned); d_flat_actions /
  * d_log_prob f32[T][N]: the sampled action index and its log-probability; d_state_last f64[N][S] receives every
- * env's latest state.  d_mo as in fjsp_env_step.  Single-order batches of at most 64 operation types;
- * FJSP_E_UNSUPPORTED otherwise (callers fall back to the per-step loop). */
+ * env's latest state.  d_mo as in fjsp_env_step.  Every single-order batch that create admits, whatever its operation
+ * types (up to 256) and jobs: the workgroup holds as many environments as fit a CU's LDS beside the actor's weights
+ * (fjsp_env_policy_build).  FJSP_E_UNSUPPORTED for a batch with order arrivals (their LPs are served between launches) and
+ * for an actor of another shape (callers fall back to the per-step loop). */
 int fjsp_env_rollout_policy(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_params *actor, const float *d_epsilon,
                             const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
                             float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream);
@@ -485,12 +487,20 @@ int fjsp_env_rollout_policy(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_par
  * state, reward and done flag after each env's last step (an env that took none: its start row, reward untouched).
  * FJSP_E_ARG: null env or output, T <= 0, n_greedy < 0, null d_state_in, pair_div < 0 or not dividing n_actions,
  * null d_seed while an env samples, fewer than N rows without a map.  FJSP_E_UNSUPPORTED where
- * fjsp_env_rollout_policy refuses (actor not state_size <= 32 -> 128 -> 128 -> n_actions <= 32, order arrivals,
- * more than 64 operation types, LDS): callers fall back to the per-step loop.  Recording batches record the schedule. */
+ * fjsp_env_rollout_policy refuses (actor not state_size <= 32 -> 128 -> 128 -> n_actions <= 32, order arrivals):
+ * callers fall back to the per-step loop.  Recording batches record the schedule. */
 int fjsp_env_play_policy(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
                          int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
                          const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
                          double *d_reward_last, uint8_t *d_done_last, void *stream);
+
+/* The workgroup fjsp_env_rollout_policy and fjsp_env_play_policy run for this batch with an actor of `state_size` inputs
+ * (1..32): out3 = {environments per workgroup (one wavefront each: 16, 8, 4, 2 or 1 -- the most whose LDS slices fit the
+ * 160 KB of a CU beside the actor's weights), dynamic LDS bytes of the workgroup, chunks of 64 operation types}.  Decided
+ * by the function the two launches decide with.  FJSP_E_UNSUPPORTED, with the text the launches give, for a batch they
+ * refuse (order arrivals; a slice that fits no workgroup, which create's own LDS limit rules out); FJSP_E_ARG for a null
+ * argument or a state_size outside 1..32. */
+int fjsp_env_policy_build(const fjsp_env *e, int32_t state_size, int32_t *out3);
 
 /* pick_action_and_log_prob (agents/MPPPO/MPPPO.py:272-284) for one vector step in ONE launch: samples
  * Categorical(d_probs[env]) (f32[n][n_actions], the actor's softmax output), applies the epsilon-random

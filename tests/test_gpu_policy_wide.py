@@ -1,0 +1,384 @@
+"""GPU: the in-launch policy kernels (fjsp_env_play_policy, fjsp_env_rollout_policy) on the single-order batches whose sixteen
+LDS slices do not fit a workgroup beside the actor's weights: more than 64 operation types (two and four chunks) and many
+jobs.  Those run the build whose workgroup size follows from LDS (8, 4, 2 or 1 environments; EnvBatch.policy_build reports
+it).  Every comparison is bit for bit against the per-step path, which evaluates the same actor and sampler device code one
+launch at a time; a test that runs with kernel_only(True) fails if play falls back to that loop.
+
+Unless a case says otherwise: instances from the host generator with M = 3, p in 1..20, one order, 4 instances and 12
+environments (not a multiple of 8: the last workgroup is partial)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import helpers as H
+
+pytestmark = pytest.mark.gpu
+
+UNSUPPORTED = -5
+MO_ROW = [[0.5, 0.5, 800.0, 300.0]]          # (w0, w1, completion, tardiness) of the MO_FJSSP_discretes tests
+
+
+@pytest.fixture(scope="module")
+def torch_gpu(built):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch
+
+
+@pytest.fixture
+def kernel_only(monkeypatch):
+    """The kernel path must run: the per-step loop raises if play falls back to it."""
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    loop = PS._play_loop
+
+    def boom(*a, **k):
+        raise AssertionError("play fell back to the per-step loop")
+
+    def on(flag):
+        monkeypatch.setattr(PS, "_play_loop", boom if flag else loop)
+    return on
+
+
+def _actor(torch, S, A, seed):
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import ActorNet
+    torch.manual_seed(seed)
+    return ActorNet(S, 128, 2, A).cuda()
+
+
+_SETS = {}
+
+
+def _gen(n, seed, R, J, jobs=1, M=3):
+    """n generated instances of R kinds x J operations (K = R J operation types), `jobs` jobs per kind, solved; cached."""
+    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
+    key = (n, seed, R, J, jobs, M)
+    if key not in _SETS:
+        prm = fi.GenParams(R_min=R, R_max=R, J_min=J, J_max=J, M=M, p_min=1, p_max=20, N_min=jobs, N_max=jobs, S=1, DDT=1.0,
+                           t_si_min=100.0, t_si_max=200.0)
+        _SETS[key] = fi.InstanceSet(n).generate_range(seed, prm).solve_fluid()
+    return _SETS[key]
+
+
+def _fixture_set(suite, name):
+    insts, _, _ = H.load_suite(suite)
+    pick = [a for a in insts if a.name == name]
+    assert len(pick) == 1, name
+    return pick[0], H.instance_set_from(pick)
+
+
+def _both(make, actor, kernel_only, mo=None, seed=17):
+    """Greedy and sampled play, kernel against loop; the greedy outcome."""
+    g = H.kernel_vs_loop(make, actor, kernel_only, mo=mo)
+    s = H.kernel_vs_loop(make, actor, kernel_only, mo=mo, greedy=False, seed=seed)
+    assert not np.array_equal(g["actions"], s["actions"])
+    return g
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1
+@pytest.mark.parametrize("R,J,kc", [(13, 5, 2), (43, 3, 4), (64, 4, 4)])
+def test_chunk_counts_play_kernel_equals_loop(torch_gpu, kernel_only, R, J, kc):
+    """K = 65 (one operation type in the second chunk), 129 (first of the third chunk: KC jumps 2 -> 4), 256 (the limit)."""
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    s, N = _gen(4, 400 + R, R, J), 12
+    make = lambda: EnvBatch(s, N, rng_seed=4)
+    pb = make().policy_build(20)
+    assert (pb["kc"], pb["envs_per_workgroup"]) == (kc, 8), pb
+    assert 0 < pb["lds_bytes"] <= 160 * 1024
+    got = _both(make, _actor(torch_gpu, 20, 30, 1), kernel_only)
+    assert np.array_equal(got["steps"], np.full(N, R * J))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2
+@pytest.mark.parametrize("name,K,M", [("Brandimarte_Data/Mk04", 90, 8), ("Brandimarte_Data/Mk10", 240, 15)])
+def test_brandimarte_play_kernel_equals_loop(torch_gpu, kernel_only, name, K, M):
+    """Mk04 (two chunks) and Mk10 (four chunks, 15 machines: the set-order path of the random rules): steps, read(), rows and
+    the schedule recorded by the kernel's recording twin equal the loop's (kernel_vs_loop records)."""
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    a, s = _fixture_set("large", name)
+    assert (a.K, a.M, a.S) == (K, M, 1)
+    N = 8
+    make = lambda: EnvBatch(s, N, rng_seed=5)
+    assert make().policy_build(20)["envs_per_workgroup"] == 8
+    actor = _actor(torch_gpu, 20, 30, 2)
+    for kw in (dict(), dict(greedy=False, seed=17)):
+        got = H.kernel_vs_loop(make, actor, kernel_only, **kw)
+        assert np.array_equal(got["steps"], H.ops(s, 1, N))
+        assert "schedule" in got and np.array_equal(got["schedule"][1], H.ops(s, 1, N))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3
+@pytest.mark.parametrize("which", ["so_sfjsp", "mo_discretes", "so_dfjsp"])
+def test_variants_at_two_chunks(torch_gpu, kernel_only, which):
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd.batch import (EnvBatch, VARIANT_MO_FJSSP_DISCRETES, VARIANT_SO_DFJSP,
+                                                                VARIANT_SO_SFJSP)
+    variant, S, A = {"so_sfjsp": (VARIANT_SO_SFJSP, 18, 20), "mo_discretes": (VARIANT_MO_FJSSP_DISCRETES, 25, 18),
+                     "so_dfjsp": (VARIANT_SO_DFJSP, 20, 30)}[which]
+    s, N = _gen(4, 413, 13, 5), 12
+    mo = None
+    if variant == VARIANT_MO_FJSSP_DISCRETES:
+        mo = torch.tensor(MO_ROW, dtype=torch.float64, device="cuda").repeat(N, 1)
+    make = lambda: EnvBatch(s, N, variant=variant, rng_seed=6)
+    pb = make().policy_build(S)
+    assert pb["kc"] == 2 and pb["envs_per_workgroup"] == 8, pb
+    _both(make, _actor(torch, S, A, 3), kernel_only, mo=mo)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4
+def _many_jobs(case):
+    if case == "P11":
+        return _fixture_set("multijob", "DDQN/P11")[1], 1
+    if case == "P83":
+        return _fixture_set("large", "DDQN/P83")[1], 1
+    jobs, J = {"210": (70, 2), "810": (270, 1)}[case]
+    return _gen(4, 420 + jobs, 3, J, jobs=jobs), 4
+
+
+@pytest.mark.parametrize("case,jobs,envs_per_wg", [("P11", 96, 16), ("210", 210, 8), ("P83", 280, 8), ("810", 810, 4)])
+def test_many_jobs_at_one_chunk(torch_gpu, kernel_only, case, jobs, envs_per_wg):
+    """One chunk of operation types, job lists of 128, 256, 320 and 832 words: sixteen slices fit only the first (the unchanged
+    1024-thread kernel: a regression guard), then eight, eight and four environments per workgroup -- from
+    align256(actor weights at S = 20: 93 312 B) + W x (slice + 768 B) <= 163 840 B with slices of 2 880, 3 904, 4 416 and
+    8 512 B."""
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    s, n_inst = _many_jobs(case)
+    assert all(s.dims(i)["jobs"] == jobs for i in range(n_inst))
+    N = 12
+    make = lambda: EnvBatch(s, N, rng_seed=7)
+    pb = make().policy_build(20)
+    assert (pb["kc"], pb["envs_per_workgroup"]) == (1, envs_per_wg), pb
+    got = _both(make, _actor(torch_gpu, 20, 30, 4), kernel_only)
+    assert np.array_equal(got["steps"], H.ops(s, n_inst, N))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5
+@pytest.mark.parametrize("N", [3, 9])
+def test_fewer_envs_than_a_workgroup_and_a_partial_last_one(torch_gpu, kernel_only, N):
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    s = _gen(4, 413, 13, 5)
+    make = lambda: EnvBatch(s, N, rng_seed=8)
+    assert make().policy_build(20)["envs_per_workgroup"] == 8
+    got = _both(make, _actor(torch_gpu, 20, 30, 5), kernel_only)
+    assert np.array_equal(got["steps"], np.full(N, 65))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6
+@pytest.mark.parametrize("which", ["k65", "jobs210"])
+def test_training_rollout_equals_the_per_step_path(torch_gpu, which):
+    """fjsp_env_rollout_policy on a two-chunk batch and on a 210-job batch against the per-step path (the structure of
+    test_fused_policy_rollout_equals_the_per_step_path): every buffer row and the final read(), bit for bit."""
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd.environments import BatchedSOFJSSP
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO import MPPPO as M
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.Buffer import RolloutBuffer
+    insts, T = (_gen(4, 413, 13, 5), 65) if which == "k65" else (_gen(4, 490, 3, 2, jobs=70), 420)
+    N, S, A, div = 21, 20, 30, 5
+    mk = lambda: BatchedSOFJSSP(insts, n_envs=N, rng_seed=9)
+    assert mk().batch.policy_build(S)["envs_per_workgroup"] == 8
+    torch.manual_seed(11)
+    learner = M.PPOLearner(S, A, 128, 2, 2, device=torch.device("cuda", 0), seed=5)
+    out = {}
+    for mode in ("per_step", "fused"):
+        env = mk()
+        memory = RolloutBuffer(T, N, S, device=0)
+        fused = M.FusedSampler(N, T, A, div, torch.device("cuda", 0))
+        fused.rounds = 41                              # the same sampling stream for both runs
+        old_log_prob = torch.zeros(T, N, device="cuda")
+        torch.manual_seed(77)
+        if mode == "per_step":
+            fused.native_actor = True
+            fused.new_round(0.15)
+            M._rollout_body(env, learner, memory, old_log_prob, 0.15, T, lambda a: a, None, False, fused)
+        else:
+            assert M.fused_policy_rollout(env, learner, memory, fused, old_log_prob, 0.15, T)
+        assert len(memory) == T
+        torch.cuda.synchronize()
+        valid = memory.valid[:T].clone()
+        r = env.read()
+        keep = lambda x: torch.where((valid if x.dim() == 2 else valid.unsqueeze(-1)) > 0, x, torch.zeros_like(x))   # valid rows only
+        assert all(bool(torch.isfinite(x).all()) for x in (memory.states[:T], memory.next_states[:T], old_log_prob))
+        out[mode] = dict(valid=valid, flat=keep(fused.flat_actions[:T]), logp=keep(old_log_prob),
+                         states=keep(memory.states[:T]), nxt=keep(memory.next_states[:T]),
+                         rewards=keep(memory.rewards[:T]), dones=keep(memory.dones[:T]), actions=keep(memory.actions[:T]),
+                         final_state=env.batch.state.clone(), status=r["status"] & ~4,
+                         **{k: v for k, v in r.items() if k != "status"})
+    a, b = out["per_step"], out["fused"]
+    assert int(a["valid"].sum()) == int(a["step_count"].sum()) and bool((a["step_count"] == T).all())
+    for k in a:
+        if not torch.equal(a[k], b[k]):
+            bad = (a[k] != b[k]).nonzero()
+            raise AssertionError("%s differs at %d places, first %s: %r vs %r" % (
+                k, bad.shape[0], bad[0].tolist(), a[k][tuple(bad[0].tolist())].item(), b[k][tuple(bad[0].tolist())].item()))
+    assert int(a["status"].abs().sum()) == 0 and bool((a["done"] == 1).all())
+    assert len(set(a["flat"].long().flatten().tolist())) > A // 2              # the policy did sample around
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7
+def test_search_on_top_of_the_two_chunk_kernel(torch_gpu, kernel_only):
+    """Mk04, two environments, the per-step loop forbidden throughout: best_of is never worse than the greedy play and leaves
+    a valid schedule of that makespan; policy_lookahead finishes clean and its returned actions replay to its makespan."""
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    from deep_reinforcement_learning_for_fjsp_amd import schedule as sch
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    a, s = _fixture_set("large", "Brandimarte_Data/Mk04")
+    N = 2
+    actor = _actor(torch, 20, 30, 6)
+    kernel_only(True)
+    twin = EnvBatch(s, N, rng_seed=10)
+    twin.reset()
+    PS.play(twin, actor)
+    greedy = H.read(twin)["makespan"].astype(np.float64)
+    b = EnvBatch(s, N, rng_seed=10)
+    b.record_schedule()
+    b.reset()
+    res = PS.best_of(b, actor, 4, "makespan", seed=3)
+    obj = res["objective"].cpu().numpy()
+    r = H.read(b)
+    assert np.all(obj <= greedy) and np.all(r["done"] == 1) and np.all(r["status"] == 0)
+    assert np.array_equal(r["makespan"].astype(np.float64), obj)
+    table, length = [H.host(x) for x in b.schedule()]
+    for e in range(N):
+        rows = sch.rows(table, length, e)
+        assert sch.validate(s.arrays(0), rows, 0) == [], e
+        assert sch.objectives(s.arrays(0), rows, 0)["makespan"] == r["makespan"][e], e
+    c = EnvBatch(s, N, rng_seed=10)
+    c.reset()
+    res = PS.policy_lookahead(c, actor, "makespan", candidates=H.DET_SO)
+    r = H.read(c)
+    assert np.all(r["done"] == 1) and np.all(r["status"] == 0)
+    assert np.array_equal(res["steps"], H.ops(s, 1, N))
+    got = res["objective"].cpu().numpy()
+    assert np.array_equal(r["makespan"].astype(np.float64), got)
+    kernel_only(False)
+    fresh = EnvBatch(s, N, rng_seed=10)
+    fresh.reset()
+    fresh.rollout(torch.from_numpy(res["actions"]).cuda(), trace=False, rewards=False)
+    assert np.array_equal(H.read(fresh)["makespan"].astype(np.float64), got)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 8
+def test_the_learner_takes_the_fused_path_on_training_like_instances(torch_gpu, monkeypatch):
+    """Generated with R 3-4, J 2-3, 40-50 jobs per kind on 12 machines (up to 200 jobs; this set reaches more than 192, so
+    its job lists take 256 words and sixteen slices no longer fit): PPO(fused_rollout=True) gets 0 from
+    fjsp_env_rollout_policy every round, with the invariants of test_ppo_rounds_with_the_fused_policy_rollout."""
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import _capi
+    from deep_reinforcement_learning_for_fjsp_amd import instances as fi
+    from deep_reinforcement_learning_for_fjsp_amd.environments import BatchedSOFJSSP
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.MPPPO import PPO
+    N = 64
+    prm = fi.GenParams(R_min=3, R_max=4, J_min=2, J_max=3, M=12, p_min=1, p_max=20, N_min=40, N_max=50, S=1, DDT=1.0,
+                       t_si_min=100.0, t_si_max=200.0)
+    s = fi.InstanceSet(N).generate_range(2000, prm).solve_fluid()
+    assert 192 < max(s.dims(i)["jobs"] for i in range(N)) <= 200
+    ops = H.ops(s, N, N)
+    env = BatchedSOFJSSP(s, rng_seed=3)
+    assert env.batch.policy_build(20)["envs_per_workgroup"] == 8
+    lib, codes = _capi.lib(), []
+    real = lib.fjsp_env_rollout_policy
+
+    def recording(*args):
+        codes.append(real(*args))
+        return codes[-1]
+
+    monkeypatch.setattr(lib, "fjsp_env_rollout_policy", recording)
+    torch.manual_seed(0)
+    agent = PPO(env, hidden_size=128, hidden_layer=2, seed=1, max_steps=int(ops.max()), fused_rollout=True)
+    for rnd in range(2):
+        tard, mk, (c_loss, a_loss) = agent.run_one_policy_network()
+        assert np.isfinite(tard) and np.isfinite(mk) and np.isfinite(c_loss) and np.isfinite(a_loss)
+        assert codes == [0] * (rnd + 1)
+        r = env.read()
+        assert bool((r["done"] == 1).all()) and int(((r["status"] & ~4) != 0).sum()) == 0
+        assert np.array_equal(r["step_count"].cpu().numpy(), ops)
+        valid = agent.memory.valid[:len(agent.memory)]
+        assert np.array_equal(valid.sum(0).cpu().numpy().astype(np.int64), ops)
+        tot = (agent.memory.rewards[:len(agent.memory)].double() * valid.double()).sum(0)
+        assert torch.equal(-tot.long(), r["delay_time_sum"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- 9
+def test_the_largest_batch_create_admits(torch_gpu, kernel_only):
+    """Three operation types (three kinds of one operation) and as many jobs as create admits, found by bisection on
+    FJSP_E_UNSUPPORTED: the kernel still has a workgroup for it (one LDS slice of that size fits beside the actor), plays it
+    to the end, and the recorded actions replay to the same read().  No loop comparison: thousands of steps."""
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import _capi
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+
+    def admitted(jobs_per_kind):
+        try:
+            EnvBatch(_gen(1, 77, 3, 1, jobs=jobs_per_kind), 2, rng_seed=12)         # (destroyed when it goes out of scope)
+            return True
+        except _capi.FjspError as err:
+            assert err.code == UNSUPPORTED, err
+            return False
+
+    lo, hi = 256, 21845                                # 3 x 21845 = 65535 jobs: the instance format's own limit
+    assert admitted(lo) and not admitted(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if admitted(mid) else (lo, mid)
+    s = _gen(1, 77, 3, 1, jobs=lo)
+    assert s.dims(0)["jobs"] == 3 * lo and lo >= 1000
+    N = 2
+    b = EnvBatch(s, N, rng_seed=12)
+    pb = b.policy_build(20)
+    assert pb["kc"] == 1 and pb["envs_per_workgroup"] in (1, 2) and pb["lds_bytes"] <= 160 * 1024, pb
+    assert b.policy_build(32)["envs_per_workgroup"] >= 1                # the widest actor the kernel takes still fits
+    b.reset()
+    kernel_only(True)
+    res = PS.play(b, _actor(torch, 20, 30, 7), record_actions=True)
+    kernel_only(False)
+    r = H.read(b)
+    assert np.all(r["done"] == 1) and np.all(r["status"] == 0)
+    assert np.array_equal(H.host(res["steps"]), H.ops(s, 1, N)) and np.array_equal(r["step_count"], H.ops(s, 1, N))
+    fresh = EnvBatch(s, N, rng_seed=12)
+    fresh.reset()
+    fresh.rollout(res["actions"], trace=False, rewards=False)
+    H.same(H.read(fresh), r, "replay of the recorded actions")
+
+
+# --------------------------------------------------------------------------------------------------------------- 10
+def test_order_arrivals_stay_refused(torch_gpu):
+    """A multi-order batch: FJSP_E_UNSUPPORTED from both entry points and from policy_build, the text names the order
+    arrivals, and play still decodes it through the loop."""
+    torch = torch_gpu
+    from deep_reinforcement_learning_for_fjsp_amd import _capi
+    from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.Buffer import RolloutBuffer
+    from deep_reinforcement_learning_for_fjsp_amd.agents.native_actor import native_actor_params
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    lib, p = _capi.lib(), _capi.ptr
+    insts, _, _ = H.load_suite("multiorder")
+    insts = [a for a in insts if a.name.startswith("gen")]
+    assert insts and all(a.S > 1 for a in insts)
+    s = H.instance_set_from(insts)
+    N = 2 * len(insts)
+    b = EnvBatch(s, N, rng_seed=13)
+    state = b.reset()
+    actor = _actor(torch, 20, 30, 8)
+    ap = native_actor_params(actor)
+    assert ap is not None
+    steps = torch.zeros(N, dtype=torch.int32, device="cuda")
+    assert lib.fjsp_env_play_policy(b._h, C.byref(ap), 5, N, None, 10, None, b._p_state, N, None, None, None, p(steps),
+                                    b._p_state, b._p_reward, b._p_done, b._stream()) == UNSUPPORTED
+    assert b"order arrivals" in lib.fjsp_last_error() and b"64 operation types" not in lib.fjsp_last_error()
+    T = 10
+    memory = RolloutBuffer(T, N, 20, device=0)
+    eps = torch.zeros(1, dtype=torch.float32, device="cuda")
+    seed = torch.tensor([7], dtype=torch.int64, device="cuda")
+    flat, logp = torch.zeros(T, N, device="cuda"), torch.zeros(T, N, device="cuda")
+    st0 = state.clone()
+    assert lib.fjsp_env_rollout_policy(b._h, memory._h, C.byref(ap), p(eps), p(seed), 5, T, None, p(st0), p(flat), p(logp),
+                                       b._p_state, b._stream()) == UNSUPPORTED
+    assert b"order arrivals" in lib.fjsp_last_error()
+    with pytest.raises(_capi.FjspError) as err:
+        b.policy_build(20)
+    assert err.value.code == UNSUPPORTED and "order arrivals" in str(err.value)
+    res = PS.play(b, actor, record_actions=True)
+    r = H.read(b)
+    assert np.all(r["done"] == 1) and np.array_equal(H.host(res["steps"]), H.ops(s, len(insts), N))
