@@ -80,6 +80,7 @@ SIGNATURES = {
     "fjsp_env_step_async": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_env_arrivals_flush": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_env_parked": (_i64, [_vp]),
+    "fjsp_env_async_stats": (C.c_int, [_vp, C.POINTER(_i64 * 4)]),
     "fjsp_env_lp_cache_hits": (_i64, [_vp]),
     "fjsp_env_rollout": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "fjsp_env_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -422,6 +422,16 @@ class EnvBatch(object):
     def parked(self):
         return int(self._lib.fjsp_env_parked(self._h))
 
+    @property
+    def async_stats(self):
+        """fjsp_env_async_stats, host-side counters of the asynchronous arrival service: (launches whose parked envs went
+        to the LP workers, those of them with more than 64 parked envs (second copy), step_async calls that found every
+        batch of the ring in flight and waited, most envs parked by one launch).  Zeros before the first step_async
+        and on batches without order arrivals.  The ring's length is FJSP_ASYNC_RING (1 ... 32) when the batch is created."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.fjsp_env_async_stats(self._h, C.byref(out)))
+        return tuple(int(v) for v in out)
+
     def rollout(self, actions, trace=True, rewards=True, mo=None, state=True):
         """T fused steps in one launch. actions: uint8[T, N, 2]. Returns (trace_km i16[T,N,2], reward f64[T,N], state).
         state=False: no final state (the fused kernel then skips the observation)."""
@@ -581,7 +591,8 @@ class EnvBatch(object):
         return table, length
 
     def set_lp_threads(self, n_threads):
-        """Host threads of the order-arrival LP service (0 = all cores)."""
+        """Host threads of the order-arrival LP service (0 = all cores).  The asynchronous service builds its worker pool
+        at the first step_async and reads this once, there: call it before that."""
         check(self._lib.fjsp_env_set_lp_threads(self._h, int(n_threads)))
 
     @property

@@ -158,12 +158,17 @@ struct LpWorkers {
 };
 
 constexpr int kAsyncRing = 32;         // batches in flight: a parked env waits for its LP (0.05 .. 0.8 ms) while calls come every ~0.03 ms
+                                       // (LaunchPlan::async_ring, FJSP_ASYNC_RING: fewer, down to 1)
 constexpr uint32_t kAsyncHead = 64;    // parked envs whose ids + LP inputs travel with the count (more: a second copy)
 
 // The asynchronous service of one handle: its batches, the worker threads and the copy stream.
 struct AsyncRing {
     AsyncBatch batch[kAsyncRing];
+    int len = kAsyncRing;               // batches in use: [0, len) (LaunchPlan::async_ring)
     int next = 0;                       // where the search for a free batch starts (the oldest batch in flight)
+    // fjsp_env_async_stats: batches handed to the workers, those of them with a tail copy, calls that found no free
+    // batch and waited, the largest batch
+    int64_t stat_batches = 0, stat_tails = 0, stat_waits = 0, stat_max_n = 0;
     std::unique_ptr<LpWorkers> workers;
     hipStream_t copy_stream = nullptr;  // the parked envs' ids / LP inputs leave on their own stream: the next step launch does not wait for them
     hipEvent_t ev_step = nullptr;
@@ -293,7 +298,9 @@ int async_setup(fjsp_env *e) {
     const DevBatch &b = e->b;
     const size_t N = (size_t)b.N, KP = (size_t)b.KP, MP = (size_t)b.MP;
     std::unique_ptr<AsyncRing> r(new AsyncRing());
-    for (AsyncBatch &a : r->batch) {
+    r->len = e->plan.async_ring;
+    for (int i = 0; i < r->len; ++i) {
+        AsyncBatch &a = r->batch[i];
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a.d_count), (N + 1) * 4));
         HIP_TRY(hipMemset(a.d_count, 0, (N + 1) * 4));
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a.d_lp_in), N * 2 * KP * 2));
@@ -324,6 +331,8 @@ int async_setup(fjsp_env *e) {
 
 // hand a batch's LPs to the worker threads
 void async_submit(AsyncRing &r, AsyncBatch *a) {
+    ++r.stat_batches;
+    r.stat_max_n = std::max<int64_t>(r.stat_max_n, a->n);
     a->solved.store(0); a->bad.store(0); a->left.store((int)a->n);
     a->state = AsyncBatch::SOLVING;
     r.workers->submit(a);
@@ -341,8 +350,8 @@ int async_progress(fjsp_env *e, const double *d_mo, double *d_state, double *d_r
     const size_t KP = (size_t)b.KP, MP = (size_t)b.MP;
     for (;;) {
         bool busy = false;
-        for (int off = 0; off < kAsyncRing; ++off) {
-            AsyncBatch &a = r.batch[(r.next + off) % kAsyncRing];       // oldest first
+        for (int off = 0; off < r.len; ++off) {
+            AsyncBatch &a = r.batch[(r.next + off) % r.len];       // oldest first
             if (a.state == AsyncBatch::HEAD_COPY) {
                 const hipError_t q = poll(a.ev_head, block);
                 if (q == hipErrorNotReady) { busy = true; continue; }
@@ -358,6 +367,7 @@ int async_progress(fjsp_env *e, const double *d_mo, double *d_state, double *d_r
                                        (size_t)(a.n - kAsyncHead) * 2 * KP * 2, hipMemcpyDeviceToHost, r.copy_stream));
                 HIP_TRY(hipEventRecord(a.ev_tail, r.copy_stream));
                 a.state = AsyncBatch::TAIL_COPY;
+                ++r.stat_tails;
                 busy = true;
             } else if (a.state == AsyncBatch::TAIL_COPY) {
                 const hipError_t q = poll(a.ev_tail, block);
@@ -469,11 +479,12 @@ int fjsp_env_step_async(fjsp_env *e, const uint8_t *d_actions, const double *d_m
     // a free batch for whatever parks in this launch (none free: wait for the oldest ones)
     AsyncBatch *slot = nullptr;
     for (int attempt = 0; attempt < 2 && !slot; ++attempt) {
-        for (int off = 0; off < kAsyncRing; ++off) {
-            AsyncBatch &a = r.batch[(r.next + off) % kAsyncRing];
-            if (a.state == AsyncBatch::FREE) { slot = &a; r.next = (int)((&a - r.batch) + 1) % kAsyncRing; break; }
+        for (int off = 0; off < r.len; ++off) {
+            AsyncBatch &a = r.batch[(r.next + off) % r.len];
+            if (a.state == AsyncBatch::FREE) { slot = &a; r.next = (int)((&a - r.batch) + 1) % r.len; break; }
         }
         if (!slot) {
+            ++r.stat_waits;
             rc = async_progress(e, d_mo, d_state, d_reward, d_done, d_ready, st, true, true);
             if (rc != FJSP_OK) { e->failed = true; return rc; }
         }
@@ -498,6 +509,13 @@ int fjsp_env_arrivals_flush(fjsp_env *e, const double *d_mo, double *d_state, do
 }
 
 int64_t fjsp_env_parked(const fjsp_env *e) { return e ? e->arr.parked : 0; }
+int fjsp_env_async_stats(const fjsp_env *e, int64_t out[4]) {
+    if (!e || !out) { set_error("fjsp_env_async_stats: null argument"); return FJSP_E_ARG; }
+    const AsyncRing *r = e->arr.ring;
+    out[0] = r ? r->stat_batches : 0; out[1] = r ? r->stat_tails : 0;
+    out[2] = r ? r->stat_waits : 0;   out[3] = r ? r->stat_max_n : 0;
+    return FJSP_OK;
+}
 int64_t fjsp_env_lp_cache_hits(fjsp_env *e) {
     if (!e || !e->arr.cache) return 0;
     std::lock_guard<std::mutex> g(e->arr.cache->mu);

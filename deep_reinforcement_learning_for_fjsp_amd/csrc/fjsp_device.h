@@ -202,6 +202,7 @@ struct LaunchPlan {
     // values the diagnostic variables force, -1 = not set: FJSP_GROUP_EARLY, FJSP_GROUP_RESIDENT, FJSP_GROUP_WPB (1, 2 or 4),
     // FJSP_LP_IMPL (0 host, 1 device)
     int early_forced = -1, resident_forced = -1, wpb_forced = -1, lp_device_forced = -1;
+    int async_ring = 32;          // batches in flight of the asynchronous arrival service (FJSP_ASYNC_RING = 1 ... 32, else 32)
 };
 // the rules of GroupBuild, in one place (fjsp_group.hip); reads the forced values of `p`
 GroupBuild group_build(const DevBatch &b, bool fused, const LaunchPlan &p);

@@ -150,6 +150,8 @@ int plan_launch(DevBatch &b, LaunchPlan &p, const Shape &sh, int family) {
     p.wpb_forced = knob("FJSP_GROUP_WPB");
     p.lds_pad = pad ? (size_t)atol(pad) : 0;
     p.lp_device_forced = lp ? (strcmp(lp, "device") == 0 ? 1 : 0) : -1;
+    const int ring = knob("FJSP_ASYNC_RING");
+    p.async_ring = (ring >= 1 && ring <= 32) ? ring : 32;
     if (b.grp) { p.step = group_build(b, false, p); p.fused = group_build(b, true, p); }
     return FJSP_OK;
 }

@@ -276,12 +276,25 @@ int fjsp_env_step_traced(fjsp_env *e, const uint8_t *d_actions, const double *d_
  * runs a dispatcher thread and a pool of LP worker threads inside the library for as long as the batch lives.  They touch
  * only the batch's own staging buffers, never call back into the caller and are joined by fjsp_env_destroy; a caller that
  * forks must do so before the first fjsp_env_step_async.  The blocking fjsp_env_step uses host threads only inside the
- * call (and none at all when the LPs run on the device, fjsp_env_lp_on_device). */
+ * call (and none at all when the LPs run on the device, fjsp_env_lp_on_device).
+ * The worker pool is built by the first fjsp_env_step_async of a batch and reads fjsp_env_set_lp_threads once, there:
+ * call fjsp_env_set_lp_threads BEFORE the first fjsp_env_step_async for it to size the pool (later calls change only
+ * the blocking service's thread count).
+ * FJSP_ASYNC_RING=n (1 ... 32; unset or anything else: 32), read when the batch is created: how many launches' parked
+ * envs the service keeps in flight at once.  A call that finds all n batches in flight waits for the oldest ones (their
+ * LPs, upload and arrival_kernel) before it launches; trajectories do not depend on n, only the interleaving does.
+ * n = 1 makes that wait deterministic -- every call after one that parked an env waits -- and is meant for tests.
+ * fjsp_env_async_stats: host-side counters of the batch's asynchronous service since it was created (no device access,
+ * no synchronisation): out[0] = launches whose parked envs (>= 1) were handed to the workers, out[1] = those of them
+ * that parked more than 64 envs and fetched the rest with a second copy, out[2] = fjsp_env_step_async calls that found
+ * no free batch and waited, out[3] = the most envs one launch parked.  All zero before the first fjsp_env_step_async
+ * and on batches without order arrivals.  FJSP_E_ARG: a null argument. */
 int fjsp_env_step_async(fjsp_env *e, const uint8_t *d_actions, const double *d_mo, int32_t autoreset, double *d_state,
                         double *d_reward, uint8_t *d_done, uint8_t *d_ready, void *stream);
 int fjsp_env_arrivals_flush(fjsp_env *e, const double *d_mo, double *d_state, double *d_reward, uint8_t *d_done,
                             uint8_t *d_ready, void *stream);
 int64_t fjsp_env_parked(const fjsp_env *e);
+int fjsp_env_async_stats(const fjsp_env *e, int64_t out[4]);
 /* Order-arrival LPs answered from the per-batch memo of (instance, Q, n_now) -> x (a pure function: same bits as a solve). */
 int64_t fjsp_env_lp_cache_hits(fjsp_env *e);
 
