@@ -69,6 +69,7 @@ SIGNATURES = {
     "fjsp_env_regenerate": (C.c_int, [_vp, _u64, _u64]),
     "fjsp_env_generated_stats": (C.c_int, [_vp, C.POINTER(_i64 * 4)]),
     "fjsp_env_generated_times": (C.c_int, [_vp, C.POINTER(_dbl * 5)]),
+    "fjsp_env_generated_stats2": (C.c_int, [_vp, C.POINTER(_i64 * 6), C.POINTER(_dbl * 6)]),
     "fjsp_env_instance_read": (C.c_int, [_vp, _i32, C.POINTER(_i32 * 6), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_dbl), _vp]),
     "fjsp_env_destroy": (None, [_vp]),
     "fjsp_env_num_envs": (C.c_int, [_vp]),
@@ -106,6 +107,7 @@ SIGNATURES = {
     "fjsp_env_set_lp_threads": (C.c_int, [_vp, _i32]),
     "fjsp_env_lp_solves": (_i64, [_vp]),
     "fjsp_env_lp_on_device": (_i32, [_vp]),
+    "fjsp_lp_global_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "fjsp_env_lp_device_pivots": (_i64, [_vp]),
     "fjsp_env_lp_device_solve": (_i32, [_vp, _i32, _vp, _vp, _vp]),
     "fjsp_pyset_and_order": (C.c_int, [C.c_uint32, _vp, _i32, _i32, _vp]),

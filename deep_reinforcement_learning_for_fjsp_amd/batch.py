@@ -197,7 +197,9 @@ class EnvBatch(object):
         self.step_bytes = int(self._lib.fjsp_env_step_bytes(self._h))
         # 1: stepped by the 16-lane-row kernels (csrc/fjsp_group.hip), 0: one wavefront per environment
         self.kernel_family = int(self._lib.fjsp_env_kernel_family(self._h))
-        # 1: the fluid LPs of order arrivals are solved on the device (csrc/fjsp_lp_device.hip), 0: on the host
+        # 1: the fluid LPs of order arrivals are solved on the device with the tableau in LDS (csrc/fjsp_lp_device.hip),
+        # 2: on the device with the tableau in global memory (csrc/fjsp_lp_global.hip; FJSP_LP_IMPL=global at create and a
+        # tableau beyond the LDS rule but within 256 rows x 1536 columns), 0: on the host
         self.lp_on_device = int(self._lib.fjsp_env_lp_on_device(self._h))
         f64 = dict(dtype=torch.float64, device=self.device)
         self.state = torch.zeros(self.N, self.state_size, **f64)
@@ -285,13 +287,15 @@ class EnvBatch(object):
         return InstanceArrays(R, M, K, S, Jr, p, elig_n, elig_list, count, arrive, delivery, ddt.value, x)
 
     def generated_stats(self):
-        """Of the last generated() / regenerate(): dict(instances, lp_device, lp_host, device_pivots), and `ms`: the
-        milliseconds of the generate kernel, the LP launches, the host LP route, fluid tables + reset, the whole call."""
-        out, ms = (C.c_int64 * 4)(), (C.c_double * 5)()
-        check(self._lib.fjsp_env_generated_stats(self._h, C.byref(out)))
-        check(self._lib.fjsp_env_generated_times(self._h, C.byref(ms)))
+        """Of the last generated() / regenerate(): dict(instances, lp_device, lp_host, device_pivots, lp_global,
+        global_pivots), and `ms`: the milliseconds of the generate kernel, the LP launches, the host LP route, fluid
+        tables + reset, the whole call, and the launches of the global-memory simplex (FJSP_LP_IMPL=global; they run on
+        the second stream beside lp_device and lp_host).  lp_device counts the LDS simplex alone; device_pivots both."""
+        out, ms = (C.c_int64 * 6)(), (C.c_double * 6)()
+        check(self._lib.fjsp_env_generated_stats2(self._h, C.byref(out), C.byref(ms)))
         return dict(instances=int(out[0]), lp_device=int(out[1]), lp_host=int(out[2]), device_pivots=int(out[3]),
-                    ms=dict(generate=ms[0], lp_device=ms[1], lp_host=ms[2], tables_reset=ms[3], total=ms[4]))
+                    lp_global=int(out[4]), global_pivots=int(out[5]),
+                    ms=dict(generate=ms[0], lp_device=ms[1], lp_host=ms[2], tables_reset=ms[3], total=ms[4], lp_global=ms[5]))
 
     def __del__(self):
         h = getattr(self, "_h", None)

@@ -217,7 +217,8 @@ int service_arrivals_impl(fjsp_env *e, const double *d_mo, double *d_state, doub
     if (A.lp_device) {
         // the whole service on the stream: LP kernel (one workgroup per parked env, count read on the device), arrival_kernel,
         // pending list emptied -- no host round trip, fjsp_env_step stays asynchronous
-        if (launch_lp_device(b, b.pending_count, 0, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, A.d_lp_solved, A.lp_lds, st) != 0) {
+        if ((A.lp_global ? launch_lp_global(b, b.pending_count, 0, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, A.d_lp_solved, A.lp_pool, st)
+                         : launch_lp_device(b, b.pending_count, 0, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, A.d_lp_solved, A.lp_lds, st)) != 0) {
             set_error("lp_device_kernel launch failed"); return FJSP_E_HIP;
         }
         if (launch_arrival(b, d_mo, 0, b.pending_count + 1, b.lp_x, d_state, d_reward, d_done, d_trace, st, nullptr, false, b.pending_count) != 0) {
@@ -546,7 +547,8 @@ int fjsp_env_lp_device_solve(fjsp_env *e, int32_t env, const int32_t *Q, const i
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(b.lp_in, lpq.data(), lpq.size() * 2, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b.pending_count + 1, &id, 4, hipMemcpyHostToDevice));
-    if (launch_lp_device(b, nullptr, 1, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, nullptr, A.lp_lds, nullptr) != 0) {
+    if ((A.lp_global ? launch_lp_global(b, nullptr, 1, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, nullptr, A.lp_pool, nullptr)
+                     : launch_lp_device(b, nullptr, 1, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, nullptr, A.lp_lds, nullptr)) != 0) {
         set_error("lp_device_kernel launch failed"); return FJSP_E_HIP;
     }
     HIP_TRY(hipDeviceSynchronize());

@@ -200,7 +200,7 @@ struct LaunchPlan {
     GroupBuild step{}, fused{};   // row-kernel batches (DevBatch::grp): per-step launches, the fused rollout
     size_t lds_pad = 0;           // diagnostic: extra dynamic LDS of a per-step launch (FJSP_GROUP_LDS_PAD)
     // values the diagnostic variables force, -1 = not set: FJSP_GROUP_EARLY, FJSP_GROUP_RESIDENT, FJSP_GROUP_WPB (1, 2 or 4),
-    // FJSP_LP_IMPL (0 host, 1 device)
+    // FJSP_LP_IMPL (0 host, 1 device, 2 global: the device, tableaus beyond the LDS in global memory)
     int early_forced = -1, resident_forced = -1, wpb_forced = -1, lp_device_forced = -1;
     int async_ring = 32;          // batches in flight of the asynchronous arrival service (FJSP_ASYNC_RING = 1 ... 32, else 32)
 };
@@ -233,6 +233,24 @@ size_t lp_device_lds_bytes(int K, int M, int nx, int R, int MP);
 int lp_device_max_columns();      // widest tableau the device simplex takes (its objective row lives in registers)
 int launch_lp_device(const DevBatch &b, const uint32_t *count_dev, int count_host, const uint32_t *ids, const uint16_t *lp_in, double *lp_x,
                      uint32_t *err, unsigned long long *solved, size_t lds, hipStream_t st);
+// the same LPs with the tableau in global memory (fjsp_lp_global.hip): up to 256 rows x 1536 columns, one scratch slot per workgroup
+struct LpGlobalLds { uint32_t zr, rr, val, basis, col_of, prec, p, Q, kB, total; int32_t cap_K, cap_M, cap_nr, cap_nc; };   // byte offsets in LDS; the sizes they hold
+struct LpGlobalPool {
+    double *mem = nullptr;        // [slots][slot_bytes / 8]
+    size_t slot_bytes = 0;        // the handle's largest admissible tableau (fjsp_lp_global_bytes)
+    int slots = 0;                // min(LPs of a launch, 256, max(1, 512 MiB / slot_bytes)): the workgroups of a launch
+    LpGlobalLds lds{};
+};
+LpGlobalLds lp_global_lds(int K, int M, int MP, int nr, int nc);
+int lp_global_max_rows();
+int lp_global_max_columns();
+inline int lp_global_slots(size_t n, size_t slot_bytes) {
+    size_t g = slot_bytes ? ((size_t)512 << 20) / slot_bytes : 1;
+    g = g < 1 ? 1 : (g > 256 ? 256 : g);
+    return (int)(n < g ? n : g);
+}
+int launch_lp_global(const DevBatch &b, const uint32_t *count_dev, int count_host, const uint32_t *ids, const uint16_t *lp_in, double *lp_x,
+                     uint32_t *err, unsigned long long *solved, const LpGlobalPool &pool, hipStream_t st);
 // policy inside the launch (fjsp_policy.h)
 struct ActorParams;
 struct PolicyRolloutIO;

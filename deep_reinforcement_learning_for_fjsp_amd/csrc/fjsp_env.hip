@@ -149,7 +149,7 @@ int plan_launch(DevBatch &b, LaunchPlan &p, const Shape &sh, int family) {
     p.resident_forced = knob("FJSP_GROUP_RESIDENT");
     p.wpb_forced = knob("FJSP_GROUP_WPB");
     p.lds_pad = pad ? (size_t)atol(pad) : 0;
-    p.lp_device_forced = lp ? (strcmp(lp, "device") == 0 ? 1 : 0) : -1;
+    p.lp_device_forced = lp ? (strcmp(lp, "device") == 0 ? 1 : (strcmp(lp, "global") == 0 ? 2 : 0)) : -1;
     const int ring = knob("FJSP_ASYNC_RING");
     p.async_ring = (ring >= 1 && ring <= 32) ? ring : 32;
     if (b.grp) { p.step = group_build(b, false, p); p.fused = group_build(b, true, p); }
@@ -356,20 +356,37 @@ double step_bytes_of(const Instance &in, const DevBatch &b) {
 // needs ~0.05 ms) but 256 of them run at once, so the device wins when arrivals come in bursts of hundreds -- measured
 // (tools/bench_dynamic.py --instances industrial): 4096 envs 32.0 M env-steps/s against the host service's 34.9 M, 32768
 // envs 63.1 M against 54.2 M.  Default: the device from 16384 environments on; FJSP_LP_IMPL=device / host decides for
-// itself (A/B runs, and the parity test of the two).
+// itself (A/B runs, and the parity test of the two).  FJSP_LP_IMPL=global (opt-in, not measured into a default yet): as device
+// when every tableau fits the LDS rule; else, when every tableau is within 256 rows x 1536 columns, the same service with the
+// simplex whose tableau lives in a scratch pool in global memory (fjsp_lp_global.hip); else the host.
 void choose_lp_service(fjsp_env *e) {
     const DevBatch &b = e->b;
-    size_t lds_max = 0;
+    size_t lds_max = 0, slot_max = 0;
+    int K_max = 0, nr_max = 0, nc_max = 0;
+    bool in_global = true;
     for (int i = 0; i < b.n_inst; ++i) {
         const Instance &in = e->src->v[(size_t)e->first + i];
         int nx = 0;
         for (int v : in.p) nx += v > 0 ? 1 : 0;
         lds_max = std::max(lds_max, lp_device_lds_bytes(in.K, in.M, nx, in.R, b.MP));
         if (nx + 1 + (in.K + in.M + in.K - in.R) + 1 > lp_device_max_columns()) lds_max = (size_t)1 << 30;
+        const size_t slot = (size_t)fjsp_lp_global_bytes(in.K, in.M, nx, in.R);
+        in_global = in_global && slot > 0;
+        slot_max = std::max(slot_max, slot);
+        K_max = std::max(K_max, in.K);
+        nr_max = std::max(nr_max, in.K + in.M + in.K - in.R);
+        nc_max = std::max(nc_max, nx + 1 + (in.K + in.M + in.K - in.R) + 1);
     }
     const bool want_device = e->plan.lp_device_forced >= 0 ? e->plan.lp_device_forced != 0 : b.N >= 16384;
     e->arr.lp_device = lds_max <= 156 * 1024 && want_device;
     e->arr.lp_lds = e->arr.lp_device ? lds_max : 0;
+    if (!e->arr.lp_device && e->plan.lp_device_forced == 2 && in_global) {
+        LpGlobalPool &P = e->arr.lp_pool;
+        P.slot_bytes = slot_max;
+        P.slots = lp_global_slots((size_t)b.N, slot_max);
+        P.lds = lp_global_lds(K_max, b.MP, b.MP, nr_max, nc_max);
+        e->arr.lp_device = e->arr.lp_global = true;        // (the pool itself: upload_batch)
+    }
 }
 
 // Stage 7: every allocation of the batch, the two slabs uploaded, then the first launches
@@ -386,6 +403,7 @@ int upload_batch(fjsp_env *e, const std::vector<unsigned char> &islab) {
                    !host_alloc(e, (N + 1) * 4, &A.h_pending) || !host_alloc(e, N * 2 * KP * 2, &A.h_lp_in) ||
                    !host_alloc(e, N * KP * MP * 8, &A.h_lp_x)))
         return FJSP_E_HIP;
+    if (A.lp_global && !dev_alloc(e, (size_t)A.lp_pool.slots * A.lp_pool.slot_bytes, &A.lp_pool.mem, "hipMalloc LP tableau pool")) return FJSP_E_HIP;
     if (A.lp_device && (!dev_alloc(e, 8, &A.d_lp_err, "hipMalloc LP error word") || !dev_alloc(e, 16, &A.d_lp_solved, "hipMalloc LP counters")))
         return FJSP_E_HIP;
     if (b.grp) {       // operation types of every environment's instance (fjsp_group.hip: large-batch kernels)
@@ -522,7 +540,7 @@ int fjsp_env_row_build(const fjsp_env *e, int32_t fused, int32_t *out3) {
     out3[0] = g.early; out3[1] = g.mpc; out3[2] = g.resident;
     return FJSP_OK;
 }
-int fjsp_env_lp_on_device(const fjsp_env *e) { return (e && e->arr.lp_device) ? 1 : 0; }
+int fjsp_env_lp_on_device(const fjsp_env *e) { return (e && e->arr.lp_device) ? (e->arr.lp_global ? 2 : 1) : 0; }
 
 int fjsp_env_reset(fjsp_env *e, const uint8_t *d_mask, double *d_state, void *stream) {
     if (!e) { set_error("fjsp_env_reset: null env"); return FJSP_E_ARG; }

@@ -36,6 +36,10 @@ struct ArrivalService {
     // device LP service (fjsp_lp_device.hip): chosen at create time when the largest tableau of the batch fits the CU's LDS
     bool lp_device = false;
     size_t lp_lds = 0;
+    // ... or, under FJSP_LP_IMPL=global, when it does not but stays within 256 rows x 1536 columns (fjsp_lp_global.hip: the
+    // tableau in a scratch pool in global memory); lp_device is set as well: the service's launches differ in the LP kernel alone
+    bool lp_global = false;
+    LpGlobalPool lp_pool;
     uint32_t *d_lp_err = nullptr;                // [0] nonzero: an LP failed on the device (reported at the next synchronising call)
     unsigned long long *d_lp_solved = nullptr;   // LPs solved on the device so far, [1] their pivots
 };

@@ -5,9 +5,12 @@
 // allocation.  A generated handle owns its instance records and refills them in place from a seed:
 //   generate_pack_kernel    record i from (seed_base + i, parameters): byte for byte what pack_instance(generate(...)) writes,
 //                           except x and the static state row, which need the LP; the LP inputs (Q, n_now); and on which
-//                           of two lists the instance goes -- its order-0 tableau fits the LDS of a CU, or it does not
+//                           of two lists the instance goes -- its order-0 tableau fits the LDS of a CU, or it does not;
+//                           under FJSP_LP_IMPL=global of three: fits the LDS, within the limits of the global-memory simplex
+//                           (256 rows x 1536 columns), neither
 //   lp_device_kernel        (fjsp_lp_device.hip, unchanged) over the fitting list, in bounded chunks of staging slots
-//   solve_fluid_lp          (fjsp_lp.cpp) on host threads for the other list: the two solvers are pivot for pivot the same
+//   lp_global_kernel        (fjsp_lp_global.hip) over the second of the three lists, on the second stream, in bounded chunks
+//   solve_fluid_lp          (fjsp_lp.cpp) on host threads for the last list: the solvers are pivot for pivot the same
 //   generate_finish_kernel  x from the staging slot into the record, the static state row
 //   fluid_tables_kernel, reset_kernel (fjsp_kernels.hip, unchanged), every env marked done: the state a create leaves
 //
@@ -63,11 +66,17 @@ struct GenArgs {
     uint32_t *fit_ids;       // [n_inst] instances whose LP runs on the device, in arrival order
     uint32_t *host_ids;      // [n_inst] the others
     uint16_t *lp_in;         // [slot of fit_ids][2][KP] (Q, n_now), lp_device_kernel's format
+    // FJSP_LP_IMPL=global: the third list -- tableaus beyond the LDS rule and within kLpGlobalRows x kLpGlobalColumns;
+    // its length is counts[4]
+    int32_t allow_global;
+    uint32_t *glob_ids;      // [n_inst]
+    uint16_t *lp_in_glob;    // [slot of glob_ids][2][KP]
 };
 
 constexpr int kGenMaxK = kWave * kMaxKC;
 constexpr uint32_t kLpLdsLimit = 156 * 1024;
 constexpr int kLpMaxColumns = 512;          // lp_device_max_columns(), verified by the host at create
+constexpr int kLpGlobalRows = 256, kLpGlobalColumns = 1536;   // lp_global_max_rows() / _columns(), verified likewise
 
 namespace {
 __device__ inline uint64_t gen_draw(uint64_t seed, uint32_t i) {      // draw i (0-based) of Rng(seed), fjsp_instance.cpp
@@ -242,19 +251,22 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     // ---- the order-0 LP: Q[k] = count[r], n_now[k] = (j == 0 ? count[r] : 0) (solve_order0), and where it is solved
     const int nc = nx + 1 + (K + M + K - R) + 1;
     const bool fit = a.allow_device && lds <= kLpLdsLimit && nc <= kLpMaxColumns;
+    const bool glob = !fit && a.allow_global && nc - nx - 2 <= kLpGlobalRows && nc <= kLpGlobalColumns;
     if (l == 0) {
         if (fit) {
             s_hdr[0] = (int)atomicAdd(a.counts + 0, 1u);
             atomicMax(a.counts + 2, lds);
+        } else if (glob) {
+            s_hdr[0] = (int)atomicAdd(a.counts + 4, 1u);
         } else {
             a.host_ids[atomicAdd(a.counts + 1, 1u)] = (uint32_t)inst;
         }
     }
     __syncthreads();
-    if (fit) {
+    if (fit || glob) {
         const uint32_t slot = (uint32_t)s_hdr[0];
-        if (l == 0) a.fit_ids[slot] = (uint32_t)inst;
-        uint16_t *Q = a.lp_in + (size_t)slot * 2 * KP;
+        if (l == 0) (fit ? a.fit_ids : a.glob_ids)[slot] = (uint32_t)inst;
+        uint16_t *Q = (fit ? a.lp_in : a.lp_in_glob) + (size_t)slot * 2 * KP;
         for (int k = l; k < K; k += kWave) {
             const uint16_t c = s_cnt[s_rk[k]];
             Q[k] = c;
@@ -350,10 +362,16 @@ struct GenState {
     double *h_stage = nullptr;
     uint4 *h_head = nullptr;
     unsigned long long *h_lp = nullptr;  // [0..1] lp_device_kernel's counters, [2] its error word
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [4], [5]: around the global-memory LP launches; [6]: after the wait for them
     hipStream_t st_dev = nullptr, st_host = nullptr;       // the two routes run side by side
-    int64_t stats[4] = {0, 0, 0, 0};     // instances, LPs on the device, LPs on the host, device pivots: of the last call
-    double ms[5] = {0, 0, 0, 0, 0};      // generate kernel, LP launches + finish, host route, tables + reset, whole call
+    // instances, LPs on the device (LDS), LPs on the host, device pivots, LPs of the global-memory simplex, its pivots: of the last call
+    int64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    // generate kernel, LP launches + finish, host route, tables + reset, whole call, global-memory LP launches + finish
+    double ms[6] = {0, 0, 0, 0, 0, 0};
+    // FJSP_LP_IMPL=global only (nothing of it is allocated otherwise)
+    LpGlobalPool pool;
+    double *d_stage_glob = nullptr;      // [chunk][KP][MP]
+    unsigned long long *d_lp_solved_glob = nullptr;
 };
 
 void generated_release(fjsp_env *e) {
@@ -531,6 +549,8 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
     HIP_TRY(hipMemsetAsync(b.envs, 0, N * b.L.e_stride, st));       // the draw counters too: the env streams start over
     HIP_TRY(hipMemsetAsync(G.a.counts, 0, 12, st));
     HIP_TRY(hipMemsetAsync(G.a.counts + 3, 0xFF, 4, st));
+    HIP_TRY(hipMemsetAsync(G.a.counts + 4, 0, 16, st));
+    if (G.d_lp_solved_glob) HIP_TRY(hipMemsetAsync(G.d_lp_solved_glob, 0, 16, st));
     HIP_TRY(hipMemsetAsync(G.d_lp_solved, 0, 16, st));
     HIP_TRY(hipMemsetAsync(G.d_lp_err, 0, 8, st));
     if (e->sched.rec) HIP_TRY(hipMemsetAsync(e->sched.rec, 0, (size_t)e->sched.cap * N * sizeof(uint4), st));
@@ -539,7 +559,7 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
     HIP_TRY(hipEventRecord(G.ev[1], st));
     // the call's one read-back before the LPs: status words, sizes, the two lists' lengths, the host list
     HIP_TRY(hipMemcpyAsync(G.h_info, G.a.info, n_inst * sizeof(GenInfo), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, 32, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(G.h_host_ids, G.a.host_ids, n_inst * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (size_t i = 0; i < n_inst; ++i) {
@@ -552,8 +572,8 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
         if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP || (size_t)f.lds != lp_device_lds_bytes(f.K, f.M, f.nx, f.R, b.MP))
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": sizes disagree with the host's (internal error)");
     }
-    const int n_fit = (int)G.h_counts[0], n_host = (int)G.h_counts[1];
-    if ((size_t)n_fit + (size_t)n_host != n_inst) return fail_generate(e, FJSP_E_HIP, call + ": the LP lists do not cover the instances (internal error)");
+    const int n_fit = (int)G.h_counts[0], n_host = (int)G.h_counts[1], n_glob = (int)G.h_counts[4];
+    if ((size_t)n_fit + (size_t)n_host + (size_t)n_glob != n_inst || (n_glob > 0 && !G.pool.mem)) return fail_generate(e, FJSP_E_HIP, call + ": the LP lists do not cover the instances (internal error)");
     if (e->plan.lp_device_forced == 1 && n_host > 0) {
         uint32_t i = G.h_host_ids[0];
         for (int q = 1; q < n_host; ++q) i = std::min(i, G.h_host_ids[q]);
@@ -575,7 +595,21 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
         }
     }
     HIP_TRY(hipEventRecord(G.ev[2], st));
-    // ---- host route, while the device works on its list
+    // ---- the tableaus beyond the LDS (FJSP_LP_IMPL=global): the global-memory simplex on the second stream, beside the first list
+    if (n_glob > 0) {
+        HIP_TRY(hipEventRecord(G.ev[4], sh));
+        for (int c0 = 0; c0 < n_glob; c0 += G.chunk) {
+            const int n = std::min(G.chunk, n_glob - c0);
+            if (launch_lp_global(b, nullptr, n, G.a.glob_ids + c0, G.a.lp_in_glob + (size_t)c0 * 2 * KP, G.d_stage_glob, G.d_lp_err, G.d_lp_solved_glob, G.pool, sh) != 0 ||
+                launch(generate_finish_kernel, dim3((unsigned)n), dim3(kWave), 0, sh, b, G.a, (const uint32_t *)(G.a.glob_ids + c0), n, (const double *)G.d_stage_glob) != 0) {
+                set_error("lp_global_kernel / generate_finish_kernel launch failed"); return FJSP_E_HIP;
+            }
+        }
+        HIP_TRY(hipEventRecord(G.ev[5], sh));
+        HIP_TRY(hipStreamWaitEvent(st, G.ev[5], 0));     // the tables below read every x
+        HIP_TRY(hipEventRecord(G.ev[6], st));
+    }
+    // ---- host route, while the device works on its lists
     const auto t_host = Clock::now();
     for (int c0 = 0; c0 < n_host; c0 += G.chunk) {
         const int n = std::min(G.chunk, n_host - c0);
@@ -606,19 +640,22 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
     HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(G.h_lp, G.d_lp_solved, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(G.h_lp + 2, G.d_lp_err, 8, hipMemcpyDeviceToHost, st));
+    if (G.d_lp_solved_glob) HIP_TRY(hipMemcpyAsync(G.h_lp + 4, G.d_lp_solved_glob, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(G.ev[3], st));
     HIP_TRY(hipDeviceSynchronize());
     float f01 = 0.f, f12 = 0.f, f23 = 0.f;
-    (void)hipEventElapsedTime(&f23, G.ev[2], G.ev[3]);
+    (void)hipEventElapsedTime(&f23, G.ev[n_glob > 0 ? 6 : 2], G.ev[3]);
     (void)hipEventElapsedTime(&f01, G.ev[0], G.ev[1]);
     (void)hipEventElapsedTime(&f12, G.ev[1], G.ev[2]);
     G.ms[0] = f01; G.ms[1] = f12; G.ms[3] = f23;
+    if (n_glob > 0) { float f45 = 0.f; (void)hipEventElapsedTime(&f45, G.ev[4], G.ev[5]); G.ms[5] = f45; }
     if (G.h_counts[3] != 0xFFFFFFFFu || (uint32_t)G.h_lp[2] != 0u) {
         const uint32_t i = G.h_counts[3];
         return fail_generate(e, FJSP_E_LP, i != 0xFFFFFFFFu ? call + ": the fluid LP of instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ") failed"
                                                             : call + ": a fluid LP failed on the device (code " + std::to_string((uint32_t)G.h_lp[2]) + ")");
     }
     G.stats[0] = (int64_t)n_inst; G.stats[1] = n_fit; G.stats[2] = n_host; G.stats[3] = (int64_t)G.h_lp[1];
+    if (G.d_lp_solved_glob) { G.stats[4] = n_glob; G.stats[5] = (int64_t)G.h_lp[5]; G.stats[3] += G.stats[5]; }
     e->inst_hash = gen_hash(G.a, b.n_inst, seed_base);
     e->gen_failed = false;
     G.ms[4] = ms_since(t_call);
@@ -666,7 +703,9 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     if ((rc = plan_batch(b, e->plan, sh, n_inst, n_envs, variant, rng_seed, family)) != FJSP_OK) return rc;
     // src stays null: only the order-arrival services (fjsp_arrivals.hip) read it, and only multi-order batches reach them
     if (b.mord) { set_error(call + ": internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
-    if (lp_device_max_columns() != kLpMaxColumns) { set_error(call + ": internal error (device LP width)"); return FJSP_E_UNSUPPORTED; }
+    if (lp_device_max_columns() != kLpMaxColumns || lp_global_max_rows() != kLpGlobalRows || lp_global_max_columns() != kLpGlobalColumns) {
+        set_error(call + ": internal error (device LP width)"); return FJSP_E_UNSUPPORTED;
+    }
     e->inst_K.assign((size_t)n_inst, 0); e->inst_M.assign((size_t)n_inst, sh.M);
     e->ops_max = sh.K * prm->N_max;
 
@@ -675,6 +714,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     const size_t N = (size_t)n_envs, NI = (size_t)n_inst, KP = (size_t)b.KP, MP = (size_t)b.MP;
     if (q) { g.M = 0; G.a.ranged = 1; G.a.M_min = q->M_min; G.a.M_max = q->M_max; G.a.DDT_min = q->DDT_min; G.a.DDT_max = q->DDT_max; }
     G.a.g = g; G.a.class_fjsp = class_fjsp ? 1 : 0; G.a.allow_device = e->plan.lp_device_forced == 0 ? 0 : 1;
+    G.a.allow_global = e->plan.lp_device_forced == 2 ? 1 : 0;
     G.a.kmax = sh.K; G.a.RP = sh.R;
     G.chunk = (int)std::min<size_t>(NI, 1024);
     G.head16 = (int)((b.L.i_x + 15) / 16);
@@ -683,7 +723,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         !gen_dev_alloc(e.get(), N + 16, &e->d_done_scratch, "hipMalloc scratch") ||
         !gen_dev_alloc(e.get(), NI * (size_t)sh.K * MP, &G.a.elig, "hipMalloc eligible lists") ||
         !gen_dev_alloc(e.get(), NI * sizeof(GenInfo), &G.a.info, "hipMalloc generator status") ||
-        !gen_dev_alloc(e.get(), 16, &G.a.counts, "hipMalloc list lengths") ||
+        !gen_dev_alloc(e.get(), 32, &G.a.counts, "hipMalloc list lengths") ||
         !gen_dev_alloc(e.get(), NI * 4, &G.a.fit_ids, "hipMalloc LP list") || !gen_dev_alloc(e.get(), NI * 4, &G.a.host_ids, "hipMalloc LP list") ||
         !gen_dev_alloc(e.get(), NI * 2 * KP * 2, &G.a.lp_in, "hipMalloc LP inputs") ||
         !gen_dev_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.d_stage, "hipMalloc LP solutions") ||
@@ -691,10 +731,24 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         !gen_dev_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.d_head, "hipMalloc record heads") ||
         !gen_dev_alloc(e.get(), 8, &G.d_lp_err, "hipMalloc LP error word") || !gen_dev_alloc(e.get(), 16, &G.d_lp_solved, "hipMalloc LP counters") ||
         (b.grp && !gen_dev_alloc(e.get(), N, &G.d_kenv, "hipMalloc K table")) ||
-        !gen_host_alloc(e.get(), NI * sizeof(GenInfo), &G.h_info) || !gen_host_alloc(e.get(), 16, &G.h_counts) ||
+        !gen_host_alloc(e.get(), NI * sizeof(GenInfo), &G.h_info) || !gen_host_alloc(e.get(), 32, &G.h_counts) ||
         !gen_host_alloc(e.get(), NI * 4, &G.h_host_ids) || !gen_host_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.h_stage) ||
-        !gen_host_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.h_head) || !gen_host_alloc(e.get(), 32, &G.h_lp))
+        !gen_host_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.h_head) || !gen_host_alloc(e.get(), 64, &G.h_lp))
         return FJSP_E_HIP;
+    if (G.a.allow_global) {
+        // the scratch pool of the global-memory simplex, sized for the largest tableau the parameters admit within its limits:
+        // K - R <= R_max (J_max - 1) precedence rows
+        const int nr_cap = std::min(kLpGlobalRows, sh.K + sh.M + prm->R_max * (prm->J_max - 1));
+        const int nc_cap = std::min(kLpGlobalColumns, sh.K * sh.M + 1 + nr_cap + 1);
+        G.pool.slot_bytes = ((size_t)nr_cap * nc_cap * 8 + 255) & ~(size_t)255;
+        G.pool.slots = lp_global_slots((size_t)G.chunk, G.pool.slot_bytes);
+        G.pool.lds = lp_global_lds(sh.K, sh.M, (int)MP, nr_cap, nc_cap);
+        if (!gen_dev_alloc(e.get(), (size_t)G.pool.slots * G.pool.slot_bytes, &G.pool.mem, "hipMalloc LP tableau pool") ||
+            !gen_dev_alloc(e.get(), NI * 4, &G.a.glob_ids, "hipMalloc LP list") || !gen_dev_alloc(e.get(), NI * 2 * KP * 2, &G.a.lp_in_glob, "hipMalloc LP inputs") ||
+            !gen_dev_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.d_stage_glob, "hipMalloc LP solutions") ||
+            !gen_dev_alloc(e.get(), 16, &G.d_lp_solved_glob, "hipMalloc LP counters"))
+            return FJSP_E_HIP;
+    }
     b.kenv = G.d_kenv;
     for (hipEvent_t &ev : G.ev) HIP_TRY(hipEventCreate(&ev));
     HIP_TRY(hipStreamCreateWithFlags(&G.st_dev, hipStreamNonBlocking));
@@ -731,6 +785,15 @@ int fjsp_env_generated_stats(const fjsp_env *e, int64_t out[4]) {
     if (!e || !out) { set_error("fjsp_env_generated_stats: null argument"); return FJSP_E_ARG; }
     if (!e->gen) { set_error("fjsp_env_generated_stats: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
     for (int q = 0; q < 4; ++q) out[q] = e->gen->stats[q];
+    return FJSP_OK;
+}
+
+int fjsp_env_generated_stats2(const fjsp_env *e, int64_t out[6], double out_ms[6]) {
+    if (!e || !out) { set_error("fjsp_env_generated_stats2: null argument"); return FJSP_E_ARG; }
+    if (!e->gen) { set_error("fjsp_env_generated_stats2: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    for (int q = 0; q < 6; ++q) out[q] = e->gen->stats[q];
+    if (out_ms)
+        for (int q = 0; q < 6; ++q) out_ms[q] = e->gen->ms[q];
     return FJSP_OK;
 }
 

@@ -24,6 +24,7 @@
 #include "fjsp_common.h"
 #include "fjsp_device.h"
 #include "fjsp_launch.h"
+#include "fjsp_lp_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -51,22 +52,6 @@ size_t lp_device_lds_bytes(int K, int M, int nx, int R, int MP) {
 namespace {
 constexpr int kZT = 8;              // registers of a lane for the objective row / the pivot row: columns l, l + 64, ... (nc <= 512)
 
-__device__ inline double lane_f64(double v, int lane) {     // v of a wave-uniform lane
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), lane);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-}  // namespace
-
-namespace {
-template <int CTRL>
-__device__ inline double dpp_f64(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)u, (int)(unsigned)u, CTRL, 0xF, 0xF, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(u >> 32), (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, false);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 }  // namespace
 
 namespace {
@@ -86,23 +71,6 @@ int lp_device_max_columns() { return kZT * 64; }
 namespace {
 struct LpTab { double *T; int *basis; int nr, nc, nv, tcol; };
 
-__device__ inline double wave_fmin_f64(double x) {                 // the smallest x of the wave (no NaNs among them), in every lane
-    x = __builtin_fmin(x, dpp_f64<0xB1>(x));
-    x = __builtin_fmin(x, dpp_f64<0x4E>(x));
-    x = __builtin_fmin(x, dpp_f64<0x141>(x));
-    x = __builtin_fmin(x, dpp_f64<0x140>(x));
-    return __builtin_fmin(__builtin_fmin(lane_f64(x, 0), lane_f64(x, 16)), __builtin_fmin(lane_f64(x, 32), lane_f64(x, 48)));
-}
-
-__device__ inline uint32_t wave_min_u32(uint32_t x) {              // the smallest x of the wave, in every lane
-#define LP_UMIN(CTRL) { const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, 0xF, 0xF, false); x = o < x ? o : x; }
-    LP_UMIN(0xB1) LP_UMIN(0x4E) LP_UMIN(0x141) LP_UMIN(0x140)
-#undef LP_UMIN
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)x, 0), b = (uint32_t)__builtin_amdgcn_readlane((int)x, 16);
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)x, 32), d = (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
-    const uint32_t ab = a < b ? a : b, cd = c < d ? c : d;
-    return ab < cd ? ab : cd;
-}
 constexpr int kLexCols = 16;        // slack columns of a tie-break step: their signs fit one 32-bit signature
 
 // The pivots of one LP (every thread of the workgroup; returns the failure code, 0 = optimal).

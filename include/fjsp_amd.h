@@ -189,7 +189,9 @@ int  fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_in
  * FJSP_E_ARG; a worst case outside the kernels' limits: FJSP_E_UNSUPPORTED; all before the first HIP call.
  * An LP whose tableau fits the LDS of a CU is solved by the device simplex, the others by the host's on
  * fjsp_env_set_lp_threads threads; FJSP_LP_IMPL=host sends all to the host, =device refuses (FJSP_E_UNSUPPORTED) when one
- * does not fit.  The two are pivot for pivot the same, so x does not depend on the route.
+ * does not fit, =global sends those that do not fit but stay within 256 rows x 1536 columns to the device simplex with its
+ * tableau in global memory (csrc/fjsp_lp_global.hip) and only the rest to the host.  All are pivot for pivot the same, so
+ * x does not depend on the route.
  * A failing instance (SO_DFJSP: a machine without eligible operation, FJSP_E_UNSUPPORTED; an LP failure, FJSP_E_LP) is
  * named with its seed in fjsp_last_error; after a failed fjsp_env_regenerate reset, step, rollout, the policy launches, read,
  * schedule, snapshots, fjsp_env_fluid_tables and fjsp_env_instance_read return FJSP_E_STATE until a later one succeeds.  fjsp_env_regenerate on any other handle: FJSP_E_STATE.  Both synchronise.
@@ -217,6 +219,11 @@ int  fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed);
  * do not add up to [4].  (Five clock readings and four event records per call; tools/time_regenerate.py reads them.) */
 int  fjsp_env_generated_stats(const fjsp_env *e, int64_t out[4]);
 int  fjsp_env_generated_times(const fjsp_env *e, double out_ms[5]);
+/* The same with the third LP route (FJSP_LP_IMPL=global): out[0..3] as fjsp_env_generated_stats ([1] counts the LDS simplex
+ * alone), out[4] LPs solved by the global-memory simplex, out[5] its pivots ([3] holds both kernels' pivots);
+ * out_ms[0..4] as fjsp_env_generated_times, out_ms[5] the global-memory LP launches with their finish kernels (HIP-event time on
+ * their own stream: they run beside [1] and [2]).  out_ms is nullable. */
+int  fjsp_env_generated_stats2(const fjsp_env *e, int64_t out[6], double out_ms[6]);
 /* Instance i of a generated handle, read back from the device: dims as fjsp_instances_dims, the arrays as
  * fjsp_instances_get; every output nullable.  Synchronises. */
 int  fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr, int32_t *p, int32_t *elig_n,
@@ -423,8 +430,17 @@ int64_t fjsp_env_lp_solves(const fjsp_env *e);
  * fjsp_env_lp_device_solve (test hook): the device solver on one LP of env's instance -- Q[K], n_now[K] as
  * class_FJSSP.py:234-237 builds them -- x f64[K*M] (k-major) to the host; the batch must have no parked environments.
  * The device stages both as 16-bit counts: a Q[k] or n_now[k] outside 0 ... 65535 is FJSP_E_ARG (never a truncated value);
- * Q[k] = 0 is FJSP_E_LP, as the host solver refuses it, and leaves the handle usable. */
+ * Q[k] = 0 is FJSP_E_LP, as the host solver refuses it, and leaves the handle usable.
+ * FJSP_LP_IMPL=global (opt-in): as =device when every tableau fits the LDS rule; otherwise, when every tableau of the batch
+ * stays within 256 rows x 1536 columns, 2 = the same service with the simplex of csrc/fjsp_lp_global.hip, whose tableau lives
+ * in a scratch pool in global memory (min(n_envs, 256, max(1, 512 MiB / slot)) slots of fjsp_lp_global_bytes each,
+ * allocated at create by such a handle alone); otherwise the host.  The test hook, the counters and the error reporting
+ * work on such a handle as on 1.
+ * fjsp_lp_global_bytes: the slot bytes of the largest tableau an instance of K operation types, M machines, nx eligible
+ * pairs and R kinds can need -- (2K + M - R) rows x (nx + 2K + M - R + 2) columns of f64, rounded up to 256 --, or 0 when
+ * it has more than 256 rows or 1536 columns (or the arguments make no instance).  Host arithmetic, no HIP call. */
 int fjsp_env_lp_on_device(const fjsp_env *e);
+int64_t fjsp_lp_global_bytes(int32_t K, int32_t M, int32_t nx, int32_t R);
 /* Pivots the device simplex has executed so far, all LPs together (0 when the batch keeps the host service; synchronises). */
 int64_t fjsp_env_lp_device_pivots(const fjsp_env *e);
 int fjsp_env_lp_device_solve(fjsp_env *e, int32_t env, const int32_t *Q, const int32_t *n_now, double *x);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Secondary measurement (BASELINE configs[4]): MO_DFJSP_breakdown at 4096 envs on one MI355X.
 
-    python tools/bench_dynamic.py [--envs 4096] [--steps 300] [--lp-threads 0]
+    python tools/bench_dynamic.py [--envs 4096] [--steps 300] [--lp-threads 0] [--instances all|industrial|hmpsac]
+                                  [--lp-impl host|device|global] [--blocking]
 
 Workload: the reference's `data/industrial/DDT0.5_M20_S{1,3,5}` and two `data/HMPSAC` instances (K = 31..45,
 M = 10..20, 63 breakdown windows, 1-5 orders) as stored in tests/golden/mo_dfjsp.npz, replicated round-robin
@@ -27,8 +28,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--lp-threads", type=int, default=0)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--instances", choices=["all", "industrial"], default="all",
-                    help="industrial: only data/industrial (K 31, M 20) -- every order-arrival LP fits a CU's LDS and is solved on the device")
+    ap.add_argument("--instances", choices=["all", "industrial", "hmpsac"], default="all",
+                    help="industrial: only data/industrial (K 31, M 20) -- every order-arrival LP fits a CU's LDS and is solved on the device; "
+                         "hmpsac: only data/HMPSAC (tableaus of 233 and 474 KB: the host, or the global-memory simplex under --lp-impl global)")
+    ap.add_argument("--lp-impl", choices=["host", "device", "global"], default=None,
+                    help="FJSP_LP_IMPL around the create (default: not set).  The device services serve fjsp_env_step: use --blocking")
     ap.add_argument("--blocking", action="store_true", help="fjsp_env_step (every call waits for its order-arrival LPs) instead of "
                                                             "the asynchronous arrival service (parked envs wait, the others step)")
     args = ap.parse_args()
@@ -41,9 +45,21 @@ def main():
     insts = [a for a in insts if not a.name.startswith("gen")]
     if args.instances == "industrial":
         insts = [a for a in insts if a.name.startswith("industrial")]
+    if args.instances == "hmpsac":
+        insts = [a for a in insts if a.name.startswith("HMPSAC")]
     s = H.instance_set_from(insts)
     N = args.envs
-    env = EnvBatch(s, N, variant=VARIANT_MO_DFJSP, rng_seed=77)
+    old = os.environ.get("FJSP_LP_IMPL")
+    if args.lp_impl:
+        os.environ["FJSP_LP_IMPL"] = args.lp_impl
+    try:
+        env = EnvBatch(s, N, variant=VARIANT_MO_DFJSP, rng_seed=77)
+    finally:
+        if args.lp_impl:
+            if old is None:
+                del os.environ["FJSP_LP_IMPL"]
+            else:
+                os.environ["FJSP_LP_IMPL"] = old
     env.set_lp_threads(args.lp_threads)
     Tbuf = 64
     rs = np.random.RandomState(99)
@@ -107,7 +123,7 @@ def main():
                    "arrival_service": "blocking (fjsp_env_step)" if args.blocking else "asynchronous (fjsp_env_step_async)",
                    "env_steps_completed": env_steps,
                    "instances": [a.name for a in insts], "lp_threads": min(args.lp_threads or 16, os.cpu_count() or 1),
-                   "lp_on_device": int(env.lp_on_device)},
+                   "lp_impl": args.lp_impl, "lp_on_device": int(env.lp_on_device)},
         "order_arrival_lps": lps, "lps_per_step": lps / args.steps, "lp_cache_hits_total": env.lp_cache_hits, "lp_device_pivots_total": env.lp_device_pivots, "cpu_baseline": cpu}))
 
 

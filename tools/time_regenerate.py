@@ -2,6 +2,7 @@
 """What a training loop spends on the NEXT batch of instances: the host path against a regenerate on the device.
 
     python tools/time_regenerate.py [--reps 5] [--out profiles/regenerate_timing.jsonl] [--ranges mpppo|ddqn] [--envs 4096]
+                                    [--lp-impl host|device|global]
 
 For 4096 and 32768 bench_10x5_params instances and 4096 of reference_generator_params(1.0, 10, 1), alternately in one
 process, wall clock between device synchronisations:
@@ -10,9 +11,11 @@ process, wall clock between device synchronisations:
 Each repetition uses seeds of its own (the same for (a) and (b)).  Prints one JSON line per (workload, path) with every
 repetition, median [min, max], and for (b) the library's own split (generated_stats()["ms"], medians) and LP routes.
 --ranges NAME times instances.reference_training_ranges(NAME) instead (M and DDT drawn per instance), --envs of them;
---envs alone times that many 10x5 instances.
+--envs alone times that many 10x5 instances.  --lp-impl sets FJSP_LP_IMPL around the create of the live handle (the
+library reads it there and nowhere else) and is recorded in the device line.
 """
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -26,12 +29,29 @@ def summary(xs):
     return dict(median=statistics.median(xs), min=min(xs), max=max(xs))
 
 
+@contextlib.contextmanager
+def lp_impl(value):
+    """FJSP_LP_IMPL = value around a create (None: left as it is)."""
+    old = os.environ.get("FJSP_LP_IMPL")
+    if value is not None:
+        os.environ["FJSP_LP_IMPL"] = value
+    try:
+        yield
+    finally:
+        if value is not None:
+            if old is None:
+                del os.environ["FJSP_LP_IMPL"]
+            else:
+                os.environ["FJSP_LP_IMPL"] = old
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     ap.add_argument("--ranges", choices=("mpppo", "ddqn"), default=None, help="the reference's training distribution instead of the three workloads")
     ap.add_argument("--envs", type=int, default=None, help="instances of the --ranges workload (4096), or of a single 10x5 workload")
+    ap.add_argument("--lp-impl", choices=("host", "device", "global"), default=None, help="FJSP_LP_IMPL of the live handle (default: not set)")
     args = ap.parse_args()
     import torch
     from deep_reinforcement_learning_for_fjsp_amd import instances as fi
@@ -45,7 +65,8 @@ def main():
         workloads = [("10x5", fi.bench_10x5_params(), args.envs)]
     lines = []
     for name, prm, N in workloads:
-        live = EnvBatch.generated(prm, N, 1)
+        with lp_impl(args.lp_impl):
+            live = EnvBatch.generated(prm, N, 1)
         live.reset()
         torch.cuda.synchronize()
         host_ms, dev_ms, parts, routes = [], [], [], None
@@ -67,11 +88,12 @@ def main():
             dev_ms.append((time.perf_counter() - t0) * 1e3)
             st = live.generated_stats()
             parts.append(st["ms"])
-            routes = dict(lp_device=st["lp_device"], lp_host=st["lp_host"], device_pivots=st["device_pivots"])
+            routes = dict(lp_device=st["lp_device"], lp_host=st["lp_host"], lp_global=st["lp_global"], device_pivots=st["device_pivots"],
+                          global_pivots=st["global_pivots"])
         split = {k: statistics.median(p[k] for p in parts) for k in parts[0]}
         lines.append(dict(workload=name, instances=N, path="host: generate_range + solve_fluid(16 threads) + EnvBatch + reset",
                           ms=host_ms, **summary(host_ms)))
-        lines.append(dict(workload=name, instances=N, path="device: regenerate + reset", ms=dev_ms, split_ms_median=split,
+        lines.append(dict(workload=name, instances=N, path="device: regenerate + reset", lp_impl=args.lp_impl, ms=dev_ms, split_ms_median=split,
                           **routes, **summary(dev_ms)))
         del live
     for ln in lines:
