@@ -15,6 +15,14 @@
 #include "fjsp_env_impl.h"
 
 namespace fjsp {
+// The device service's LP launch over the handle's staging arrays: the parked environments of the pending list (count_dev,
+// read on the device) or the first count_host slots, by the kernel choose_lp_service picked
+static int launch_service_lps(const DevBatch &b, const ArrivalService &A, const uint32_t *count_dev, int count_host, unsigned long long *solved,
+                              hipStream_t st) {
+    return A.lp_global ? launch_lp_global(b, count_dev, count_host, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, solved, A.lp_pool, st)
+                       : launch_lp_device(b, count_dev, count_host, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, solved, A.lp_lds, st);
+}
+
 // Order-arrival LPs repeat: environments that play the same instance and reach an arrival in the same situation (the
 // same unprocessed / waiting counts per operation type -- always the case when the shop had run empty and the clock
 // jumped to the arrival, SO_FJSSP.py:228-231) pose the same LP.  The LP is a pure function of (instance, Q, n_now), so
@@ -217,8 +225,7 @@ int service_arrivals_impl(fjsp_env *e, const double *d_mo, double *d_state, doub
     if (A.lp_device) {
         // the whole service on the stream: LP kernel (one workgroup per parked env, count read on the device), arrival_kernel,
         // pending list emptied -- no host round trip, fjsp_env_step stays asynchronous
-        if ((A.lp_global ? launch_lp_global(b, b.pending_count, 0, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, A.d_lp_solved, A.lp_pool, st)
-                         : launch_lp_device(b, b.pending_count, 0, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, A.d_lp_solved, A.lp_lds, st)) != 0) {
+        if (launch_service_lps(b, A, b.pending_count, 0, A.d_lp_solved, st) != 0) {
             set_error("lp_device_kernel launch failed"); return FJSP_E_HIP;
         }
         if (launch_arrival(b, d_mo, 0, b.pending_count + 1, b.lp_x, d_state, d_reward, d_done, d_trace, st, nullptr, false, b.pending_count) != 0) {
@@ -547,8 +554,7 @@ int fjsp_env_lp_device_solve(fjsp_env *e, int32_t env, const int32_t *Q, const i
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(b.lp_in, lpq.data(), lpq.size() * 2, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b.pending_count + 1, &id, 4, hipMemcpyHostToDevice));
-    if ((A.lp_global ? launch_lp_global(b, nullptr, 1, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, nullptr, A.lp_pool, nullptr)
-                     : launch_lp_device(b, nullptr, 1, b.pending_count + 1, b.lp_in, b.lp_x, A.d_lp_err, nullptr, A.lp_lds, nullptr)) != 0) {
+    if (launch_service_lps(b, A, nullptr, 1, nullptr, nullptr) != 0) {
         set_error("lp_device_kernel launch failed"); return FJSP_E_HIP;
     }
     HIP_TRY(hipDeviceSynchronize());

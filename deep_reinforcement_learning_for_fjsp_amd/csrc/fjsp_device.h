@@ -229,8 +229,7 @@ int launch_arrival(const DevBatch &b, const double *mo, int n_pending, const uin
                    double *reward, uint8_t *done, int16_t *trace_km, hipStream_t st, uint8_t *ready = nullptr, bool mark_resumed = false,
                    const uint32_t *n_dev = nullptr);     // n_dev: read the count on the device (the grid then covers the batch)
 // the order-arrival LPs on the device (fjsp_lp_device.hip): one workgroup per parked environment, x into lp_x[slot]
-size_t lp_device_lds_bytes(int K, int M, int nx, int R, int MP);
-int lp_device_max_columns();      // widest tableau the device simplex takes (its objective row lives in registers)
+// (which tableaus it takes, and lds for them: fjsp_lp_limits.h)
 int launch_lp_device(const DevBatch &b, const uint32_t *count_dev, int count_host, const uint32_t *ids, const uint16_t *lp_in, double *lp_x,
                      uint32_t *err, unsigned long long *solved, size_t lds, hipStream_t st);
 // the same LPs with the tableau in global memory (fjsp_lp_global.hip): up to 256 rows x 1536 columns, one scratch slot per workgroup
@@ -242,8 +241,6 @@ struct LpGlobalPool {
     LpGlobalLds lds{};
 };
 LpGlobalLds lp_global_lds(int K, int M, int MP, int nr, int nc);
-int lp_global_max_rows();
-int lp_global_max_columns();
 inline int lp_global_slots(size_t n, size_t slot_bytes) {
     size_t g = slot_bytes ? ((size_t)512 << 20) / slot_bytes : 1;
     g = g < 1 ? 1 : (g > 256 ? 256 : g);

@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "fjsp_env_impl.h"
+#include "fjsp_lp_limits.h"
 #include "fjsp_pyset.h"
 #include "fjsp_policy.h"
 
@@ -368,17 +369,18 @@ void choose_lp_service(fjsp_env *e) {
         const Instance &in = e->src->v[(size_t)e->first + i];
         int nx = 0;
         for (int v : in.p) nx += v > 0 ? 1 : 0;
-        lds_max = std::max(lds_max, lp_device_lds_bytes(in.K, in.M, nx, in.R, b.MP));
-        if (nx + 1 + (in.K + in.M + in.K - in.R) + 1 > lp_device_max_columns()) lds_max = (size_t)1 << 30;
+        const int nr = lp_max_rows(in.K, in.M, in.R), nc = lp_max_columns(in.K, in.M, nx, in.R);
+        lds_max = std::max(lds_max, (size_t)lp_device_lds_bytes(in.K, in.M, nx, in.R, b.MP));
+        if (nc > kLpLdsColumns) lds_max = (size_t)1 << 30;
         const size_t slot = (size_t)fjsp_lp_global_bytes(in.K, in.M, nx, in.R);
         in_global = in_global && slot > 0;
         slot_max = std::max(slot_max, slot);
         K_max = std::max(K_max, in.K);
-        nr_max = std::max(nr_max, in.K + in.M + in.K - in.R);
-        nc_max = std::max(nc_max, nx + 1 + (in.K + in.M + in.K - in.R) + 1);
+        nr_max = std::max(nr_max, nr);
+        nc_max = std::max(nc_max, nc);
     }
     const bool want_device = e->plan.lp_device_forced >= 0 ? e->plan.lp_device_forced != 0 : b.N >= 16384;
-    e->arr.lp_device = lds_max <= 156 * 1024 && want_device;
+    e->arr.lp_device = lds_max <= kLpLdsLimit && want_device;
     e->arr.lp_lds = e->arr.lp_device ? lds_max : 0;
     if (!e->arr.lp_device && e->plan.lp_device_forced == 2 && in_global) {
         LpGlobalPool &P = e->arr.lp_pool;

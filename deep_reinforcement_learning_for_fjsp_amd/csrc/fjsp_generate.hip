@@ -32,6 +32,7 @@
 
 #include "fjsp_env_impl.h"
 #include "fjsp_launch.h"
+#include "fjsp_lp_limits.h"
 
 #pragma clang fp contract(off)
 
@@ -42,7 +43,7 @@ struct GenInfo {
     int32_t status;      // 0 or a negative FJSP_E_* code
     int32_t K, R, nj;    // operation types, kinds, jobs
     int32_t nx;          // eligible (operation type, machine) pairs
-    int32_t lds;         // LDS bytes of the order-0 tableau (lp_device_lds_bytes)
+    int32_t lds;         // LDS bytes of the order-0 tableau (lp_device_lds_bytes, fjsp_lp_limits.h)
     int32_t ops;         // operations (schedule slots)
     int32_t delivery;    // delivery time of the order
     int32_t M, pad;      // machines of the instance (its own draw on a ranges handle)
@@ -74,9 +75,6 @@ struct GenArgs {
 };
 
 constexpr int kGenMaxK = kWave * kMaxKC;
-constexpr uint32_t kLpLdsLimit = 156 * 1024;
-constexpr int kLpMaxColumns = 512;          // lp_device_max_columns(), verified by the host at create
-constexpr int kLpGlobalRows = 256, kLpGlobalColumns = 1536;   // lp_global_max_rows() / _columns(), verified likewise
 
 namespace {
 __device__ inline uint64_t gen_draw(uint64_t seed, uint32_t i) {      // draw i (0-based) of Rng(seed), fjsp_instance.cpp
@@ -95,12 +93,6 @@ __device__ inline int gen_machines(const GenArgs &a, uint64_t seed) {
 __device__ inline double gen_ddt(const GenArgs &a, uint64_t seed) {
     if (!a.ranged) return a.g.DDT;
     return a.DDT_min + (a.DDT_max - a.DDT_min) * ((double)(gen_draw(seed ^ FJSP_GEN_AUX_STREAM, 1u) >> 11) * (1.0 / 9007199254740992.0));
-}
-// lp_device_lds_bytes (fjsp_lp_device.hip) restated for the device; the host compares the two for every instance
-__device__ inline uint32_t gen_lp_lds_bytes(int K, int M, int nx, int R, int MP) {
-    const size_t nr = (size_t)K + M + (K - R), nc = (size_t)nx + 1 + nr + 1;
-    const size_t bytes = nr * nc * 8 + nc * 8 + 2 * nr * 8 + nr * 4 + (size_t)K * M * 2 + (size_t)K * 2 + nr * 2 + (size_t)K * MP * 2 + (size_t)K * 8 + 128;
-    return (uint32_t)((bytes + 15) & ~(size_t)15);
 }
 }  // namespace
 
@@ -198,7 +190,7 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     if (l < M)
         for (int k = 0; k < K; ++k) ops_m += s_p[k * kMaxM + l] > 0 ? 1 : 0;
     if (a.class_fjsp && __any(l < M && ops_m == 0) && status == 0) status = FJSP_E_UNSUPPORTED;
-    const uint32_t lds = gen_lp_lds_bytes(K, M, nx, R, MP);
+    const uint32_t lds = lp_device_lds_bytes(K, M, nx, R, MP);
     if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[7], delivery, M, 0, DDT};
     if (status != 0) return;
 
@@ -249,8 +241,9 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
         reinterpret_cast<uint32_t *>(rec + L.i_op + 2048)[l] = w;
     }
     // ---- the order-0 LP: Q[k] = count[r], n_now[k] = (j == 0 ? count[r] : 0) (solve_order0), and where it is solved
+    // (nc is lp_max_columns and nc - nx - 2 is lp_max_rows of fjsp_lp_limits.h, in the wave's own integer arithmetic)
     const int nc = nx + 1 + (K + M + K - R) + 1;
-    const bool fit = a.allow_device && lds <= kLpLdsLimit && nc <= kLpMaxColumns;
+    const bool fit = a.allow_device && lds <= kLpLdsLimit && nc <= kLpLdsColumns;
     const bool glob = !fit && a.allow_global && nc - nx - 2 <= kLpGlobalRows && nc <= kLpGlobalColumns;
     if (l == 0) {
         if (fit) {
@@ -569,7 +562,7 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
         if (f.status != 0)
             return fail_generate(e, f.status, call + ": " + who + ": a draw left the record's fields (internal error)");
-        if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP || (size_t)f.lds != lp_device_lds_bytes(f.K, f.M, f.nx, f.R, b.MP))
+        if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP)
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": sizes disagree with the host's (internal error)");
     }
     const int n_fit = (int)G.h_counts[0], n_host = (int)G.h_counts[1], n_glob = (int)G.h_counts[4];
@@ -580,8 +573,8 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
         const GenInfo &f = G.h_info[i];
         return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": FJSP_LP_IMPL=device, but the order-0 tableau of instance " + std::to_string(i) +
                              " (seed " + std::to_string(seed_base + i) + ") does not fit: " + std::to_string(f.lds) + " bytes of LDS (limit " +
-                             std::to_string(kLpLdsLimit) + "), " + std::to_string(f.nx + 1 + (2 * f.K + f.M - f.R) + 1) + " columns (limit " +
-                             std::to_string(lp_device_max_columns()) + ")");
+                             std::to_string(kLpLdsLimit) + "), " + std::to_string(lp_max_columns(f.K, f.M, f.nx, f.R)) + " columns (limit " +
+                             std::to_string(kLpLdsColumns) + ")");
     }
     for (size_t i = 0; i < n_inst; ++i) { e->inst_K[i] = G.h_info[i].K; e->inst_M[i] = G.h_info[i].M; }
     e->step_bytes = (int64_t)(step_bytes_mean(e) / (double)n_inst + 0.5);
@@ -703,9 +696,6 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     if ((rc = plan_batch(b, e->plan, sh, n_inst, n_envs, variant, rng_seed, family)) != FJSP_OK) return rc;
     // src stays null: only the order-arrival services (fjsp_arrivals.hip) read it, and only multi-order batches reach them
     if (b.mord) { set_error(call + ": internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
-    if (lp_device_max_columns() != kLpMaxColumns || lp_global_max_rows() != kLpGlobalRows || lp_global_max_columns() != kLpGlobalColumns) {
-        set_error(call + ": internal error (device LP width)"); return FJSP_E_UNSUPPORTED;
-    }
     e->inst_K.assign((size_t)n_inst, 0); e->inst_M.assign((size_t)n_inst, sh.M);
     e->ops_max = sh.K * prm->N_max;
 
@@ -740,7 +730,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         // K - R <= R_max (J_max - 1) precedence rows
         const int nr_cap = std::min(kLpGlobalRows, sh.K + sh.M + prm->R_max * (prm->J_max - 1));
         const int nc_cap = std::min(kLpGlobalColumns, sh.K * sh.M + 1 + nr_cap + 1);
-        G.pool.slot_bytes = ((size_t)nr_cap * nc_cap * 8 + 255) & ~(size_t)255;
+        G.pool.slot_bytes = lp_global_slot_bytes(nr_cap, nc_cap);
         G.pool.slots = lp_global_slots((size_t)G.chunk, G.pool.slot_bytes);
         G.pool.lds = lp_global_lds(sh.K, sh.M, (int)MP, nr_cap, nc_cap);
         if (!gen_dev_alloc(e.get(), (size_t)G.pool.slots * G.pool.slot_bytes, &G.pool.mem, "hipMalloc LP tableau pool") ||

@@ -421,7 +421,7 @@ int fjsp_env_row_build(const fjsp_env *e, int32_t fused, int32_t *out3);
  * over n_threads host threads (0 = default: min(host cores, 16)).  fjsp_env_lp_solves: LPs solved so far. */
 int fjsp_env_set_lp_threads(fjsp_env *e, int32_t n_threads);
 int64_t fjsp_env_lp_solves(const fjsp_env *e);
-/* Where the order-arrival LPs of this batch are solved: 1 = on the device (csrc/fjsp_lp_device.hip: the host simplex of
+/* Where the order-arrival LPs of this batch are solved: 1 = on the device (csrc/fjsp_lp_device.hip; csrc/fjsp_lp_simplex.h: the host simplex of
  * csrc/fjsp_lp.cpp restated pivot for pivot, one workgroup per parked environment, tableau in LDS; fjsp_env_step then never
  * synchronises), 0 = on the host.  Same x either way, bit for bit.  Chosen at create time: the device when the largest tableau
  * of the batch fits a CU's LDS (and is at most 512 columns wide) and the batch has 16384 environments or more -- a single LP is

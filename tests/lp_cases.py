@@ -33,11 +33,11 @@ tests/test_lp_reference.py asserts that the committed cases still reach each of 
 import numpy as np
 
 LDS_LIMIT = 156 * 1024           # csrc/fjsp_env.hip choose_lp_service
-MAX_COLUMNS = 512                # csrc/fjsp_lp_device.hip lp_device_max_columns: kZT * 64
+MAX_COLUMNS = 512                # csrc/fjsp_lp_limits.h kLpLdsColumns (csrc/fjsp_lp_device.hip: kZT * 64)
 
 
 def lds_bytes(K, M, nx, R, MP):
-    """csrc/fjsp_lp_device.hip lp_device_lds_bytes, restated: the LDS of the largest tableau an instance can need."""
+    """csrc/fjsp_lp_limits.h lp_device_lds_bytes, restated: the LDS of the largest tableau an instance can need."""
     nr = K + M + (K - R)
     nc = nx + 1 + nr + 1
     b = nr * nc * 8 + nc * 8 + 2 * nr * 8 + nr * 4 + K * M * 2 + K * 2 + nr * 2 + K * MP * 2 + K * 8 + 128

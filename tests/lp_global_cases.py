@@ -17,8 +17,8 @@ kinds) and l_cols1536 / l_cols1537 (46 single-operation kinds, M 32, nx 1456 / 1
 """
 from tests import lp_cases as LC
 
-MAX_ROWS = 256                   # csrc/fjsp_lp_global.hip kMaxRows
-MAX_COLUMNS = 1536               # kMaxCols
+MAX_ROWS = 256                   # csrc/fjsp_lp_limits.h kLpGlobalRows
+MAX_COLUMNS = 1536               # kLpGlobalColumns
 
 
 def global_bytes(K, M, nx, R):

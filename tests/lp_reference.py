@@ -8,29 +8,29 @@ one for the difference (numpy evaluates `a - f * b` through a temporary: no FMA)
 right-hand side and the same extraction of x.  Its x and objective must therefore equal the host solver's BIT FOR BIT
 (tests/test_lp_reference.py); it is a second, independently written statement of the solver, not a tolerance oracle.
 
-What it adds is a record per pivot that classifies the pivot the way csrc/fjsp_lp_device.hip BRANCHES on it.  The device
-file chooses the leaving row without the scan wherever it can (lp_pivots, "lexicographic ratio test"); `_device_ratio_test`
+What it adds is a record per pivot that classifies the pivot the way csrc/fjsp_lp_simplex.h BRANCHES on it.  The device
+file chooses the leaving row without the scan wherever it can (lp_leaving_row, "lexicographic ratio test"); `_device_ratio_test`
 below evaluates that choice with the device file's own expressions (the line numbers cited are those of
-csrc/fjsp_lp_device.hip) and reports
+csrc/fjsp_lp_simplex.h; lp_pivots is csrc/fjsp_lp_device.hip's) and reports
 
-    nt         chunks of 64 columns, ceil(nc / 64): which lp_pivots<NT> runs (2, 3, 4, 6 or 8; :475-478)
+    nt         chunks of 64 columns, ceil(nc / 64): which lp_pivots<NT> runs (2, 3, 4, 6 or 8; lp_device_kernel)
     nr, nc     rows and columns of the solved tableau
-    s, s_chunk the entering column and its chunk (the lane and register fz is read from, :288-291)
-    r, half    the leaving row and its half: 0 = rows 0-63 (i0, acol[0], E0), 1 = rows 64-127 (i1, acol[1], E1; :236-237)
-    n_elig     rows with a > 1e-9 (:163)
-    n_tied     rows whose ratio equals the smallest exactly (in0 / in1, :170), tied_lo / tied_hi of them per half
-    bad        some eligible row is neither exactly at the minimum nor beyond the scan's tolerance from it (:172-173):
-               the device falls back to the sequential scan (:241-277)
-    steps      16-column tie-break steps taken (:178)
+    s, s_chunk the entering column and its chunk (the lane and register fz is read from, lp_pivots)
+    r, half    the leaving row and its half: 0 = rows 0-63 (row group 0), 1 = rows 64-127 (row group 1; :351-357)
+    n_elig     rows with a > 1e-9 (:238)
+    n_tied     rows whose ratio equals the smallest exactly (k[g], :253), tied_lo / tied_hi of them per half
+    bad        some eligible row is neither exactly at the minimum nor beyond the scan's tolerance from it (:254-255):
+               the device falls back to the sequential scan (:361-395)
+    steps      16-column tie-break steps taken (:259)
     decided    how the race among the tied rows ended:
                  "single"     one row at the minimum, nothing to break
-                 "signature"  by sign signatures alone (:197-207)
+                 "signature"  by sign signatures alone (:281-303)
                  "sign"       the per-column walk ran and was settled by a lone negative entry or the zeros of a column
-                              (:216-224) without a division
-                 "magnitude"  at least one column was decided by quotients (:226-229)
+                              (:317-340) without a division
+                 "magnitude"  at least one column was decided by quotients (:342-348)
                  "scan"       bad, or more than 128 rows: no order-independent choice was made
     n_sign, n_div   columns of the per-column walk settled by signs / by a division
-    small      the underflow guard fired in some step (:193, exact_signs false)
+    small      the underflow guard fired in some step (:276, exact_signs false)
     lex_row    the row the order-independent narrowing ends on (None for "scan").  The device file's central claim is
                lex_row == r, the sequential scan's row, on every pivot with a clean split.
 """
@@ -39,7 +39,7 @@ import numpy as np
 EPS_COST = 1e-9     # csrc/fjsp_lp.cpp kEpsCost
 EPS_PIV = 1e-9      # kEpsPiv
 EPS_ZERO = 1e-11    # kEpsZero
-LEX_COLS = 16       # csrc/fjsp_lp_device.hip kLexCols
+LEX_COLS = 16       # csrc/fjsp_lp_simplex.h kLexCols
 INF = float("inf")
 
 
@@ -85,82 +85,82 @@ def _sequential_scan(T, s, nv, nr, rhs):
 
 
 def _device_ratio_test(T, s, nv, nr, rhs):
-    """The leaving row as csrc/fjsp_lp_device.hip:159-240 derives it, rows as array entries instead of lanes."""
+    """The leaving row as csrc/fjsp_lp_simplex.h:225-360 (lp_leaving_row, two row groups) derives it, rows as array entries instead of lanes."""
     out = dict(n_elig=0, n_tied=0, tied_lo=0, tied_hi=0, bad=False, steps=0, decided="scan", n_sign=0, n_div=0,
                small=False, lex_row=None)
     a = T[:, s].copy()
-    el = a > EPS_PIV                                                                  # :163
+    el = a > EPS_PIV                                                                  # :238
     out["n_elig"] = int(el.sum())
-    if nr > 128 or not el.any():                                                     # :159, :165
+    if nr > 128 or not el.any():                                                     # lp_device_kernel's refusal, :242
         return out
     v = np.zeros(nr)
-    v[el] = T[el, rhs] / a[el]                                                        # :164
-    vmin = v[el].min()                                                                # :166-168
-    tolmin = 1e-12 * (abs(vmin) if abs(vmin) > 1.0 else 1.0)                          # :169
+    v[el] = T[el, rhs] / a[el]                                                        # :239
+    vmin = v[el].min()                                                                # :243-247
+    tolmin = 1e-12 * (abs(vmin) if abs(vmin) > 1.0 else 1.0)                          # :209, :247
     hi = vmin + tolmin
-    tied = el & (v == vmin)                                                           # :170
-    tol = 1e-12 * np.where(np.abs(v) > 1.0, np.abs(v), 1.0)                           # :171
-    far = (v > hi) & (vmin < v - tol)                                                 # :172
+    tied = el & (v == vmin)                                                           # :253
+    tol = 1e-12 * np.where(np.abs(v) > 1.0, np.abs(v), 1.0)                           # :209
+    far = (v > hi) & (vmin < v - tol)                                                 # :254
     out["n_tied"], out["tied_lo"], out["tied_hi"] = int(tied.sum()), int(tied[:64].sum()), int(tied[64:].sum())
-    if (el & ~tied & ~far).any():                                                     # :173
+    if (el & ~tied & ~far).any():                                                     # :255
         out["bad"] = True
         return out
     k = tied.copy()
     cnt = int(k.sum())
     cend = nv + nr
     c = nv
-    while c < cend and cnt > 1:                                                       # :178
+    while c < cend and cnt > 1:                                                       # :259
         out["steps"] += 1
         t = np.zeros((nr, LEX_COLS))
         w = min(LEX_COLS, cend - c)
-        t[k, :w] = T[k, c:c + w]                                                      # :188-189
-        small = bool(((t != 0.0) & ~(np.abs(t) >= 1e-280)).any())                     # :193
+        t[k, :w] = T[k, c:c + w]                                                      # :272
+        small = bool(((t != 0.0) & ~(np.abs(t) >= 1e-280)).any())                     # :276
         out["small"] = out["small"] or small
-        exact_signs = not small                                                       # :197
+        exact_signs = not small                                                       # :281
         if exact_signs:
-            code = (t == 0.0).astype(np.uint64) + 2 * (t > 0.0).astype(np.uint64)     # :194-195
+            code = (t == 0.0).astype(np.uint64) + 2 * (t > 0.0).astype(np.uint64)     # :277
             sig = np.zeros(nr, np.uint64)
             for u in range(LEX_COLS):
                 sig = (sig << np.uint64(2)) | code[:, u]
-            sig[~k] = 0xFFFFFFFF                                                      # :199-200
-            smin = int(sig.min())                                                     # :201
-            d = smin ^ 0x55555555                                                     # :202
-            keep = (~((1 << (2 * ((d.bit_length() - 1) >> 1))) - 1)) & 0xFFFFFFFF if d else 0xFFFFFFFF   # :204
-            pk = k & (((sig ^ np.uint64(smin)) & np.uint64(keep)) == 0)               # :205
+            sig[~k] = 0xFFFFFFFF                                                      # :267, :279
+            smin = int(sig.min())                                                     # :283-286
+            d = smin ^ 0x55555555                                                     # :287
+            keep = (~((1 << (2 * ((d.bit_length() - 1) >> 1))) - 1)) & 0xFFFFFFFF if d else 0xFFFFFFFF   # :289
+            pk = k & (((sig ^ np.uint64(smin)) & np.uint64(keep)) == 0)               # :294
             npk = int(pk.sum())
-            if d == 0 or npk == 1:                                                    # :207
+            if d == 0 or npk == 1:                                                    # :297
                 k, cnt = pk, npk
                 c += LEX_COLS
                 continue
-        for u in range(LEX_COLS):                                                     # :211
+        for u in range(LEX_COLS):                                                     # :305
             if c + u >= cend or cnt <= 1:
                 break
             x = t[:, u]
-            sel = k.copy()                                                            # :214
+            sel = k.copy()                                                            # :312
             if exact_signs:
-                g = k & (x < 0.0)                                                     # :217
+                g = k & (x < 0.0)                                                     # :319
                 nn = int(g.sum())
-                if nn == 1:                                                           # :219
+                if nn == 1:                                                           # :320
                     k, cnt = g, 1
                     out["n_sign"] += 1
                     continue
                 if nn == 0:
-                    z = k & (x == 0.0)                                                # :221
+                    z = k & (x == 0.0)                                                # :330
                     nz = int(z.sum())
-                    if nz > 0:                                                        # :223
+                    if nz > 0:                                                        # :331
                         k, cnt = z, nz
                         out["n_sign"] += 1
                         continue
                 else:
-                    sel = g                                                           # :224
+                    sel = g                                                           # :339
             wq = np.full(nr, INF)
-            wq[sel] = x[sel] / a[sel]                                                 # :226
-            wm = wq.min()                                                             # :227
-            k = sel & (wq == wm)                                                      # :228
+            wq[sel] = x[sel] / a[sel]                                                 # :344
+            wm = wq.min()                                                             # :345
+            k = sel & (wq == wm)                                                      # :348
             cnt = int(k.sum())
             out["n_div"] += 1
         c += LEX_COLS
-    if k.any():                                                                       # :233-237: E0 before E1, lowest lane first
+    if k.any():                                                                       # :351-357: row group 0 before 1, lowest lane first
         out["lex_row"] = int(np.nonzero(k)[0][0])
         out["decided"] = ("magnitude" if out["n_div"] else "sign" if out["n_sign"] else
                           "signature" if out["steps"] else "single")

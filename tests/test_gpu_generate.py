@@ -56,7 +56,7 @@ def same_instance(a, b, what):
 
 
 def tableau_fits(a):
-    """choose_lp_service's rule on the order-0 LP of instance arrays a (lp_device_lds_bytes, lp_device_max_columns)."""
+    """choose_lp_service's rule on the order-0 LP of instance arrays a (csrc/fjsp_lp_limits.h: lp_device_lds_bytes, kLpLdsColumns)."""
     K, M, R, nx = a.K, a.M, a.R, int((np.asarray(a.p) > 0).sum())
     nr = K + M + (K - R)
     nc = nx + 1 + nr + 1

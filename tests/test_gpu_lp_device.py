@@ -75,7 +75,7 @@ def test_device_lp_service_leaves_every_trajectory_unchanged(torch_gpu):
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, VARIANT_MO_DFJSP, global_actions
     insts, _, _ = H.load_suite("mo_dfjsp")
 
-    def tableau_bytes(a):        # rows x columns of the largest tableau of the instance (csrc/fjsp_lp_device.hip lp_device_lds_bytes)
+    def tableau_bytes(a):        # rows x columns of the largest tableau of the instance (csrc/fjsp_lp_limits.h lp_device_lds_bytes)
         K, M = a.p.shape
         nr = K + M + (K - len(a.Jr))
         return nr * (int((a.p > 0).sum()) + 1 + nr + 1) * 8

@@ -1,7 +1,7 @@
 """CPU: what the device simplex with its tableau in global memory (csrc/fjsp_lp_global.hip) rests on beyond the LDS kernel.
 
-Order-independent row choice at any row count.  csrc/fjsp_lp_device.hip holds two row groups per lane and sends anything
-beyond 128 rows to the sequential scan; the global-memory kernel holds four (256 rows).  The claim that makes the choice
+Order-independent row choice at any row count.  csrc/fjsp_lp_device.hip holds two row groups per lane and refuses anything
+beyond 128 rows; the global-memory kernel holds four (256 rows).  The claim that makes the choice
 legal -- on a clean split the sequential scan ends on the first lexicographic minimum among the rows exactly at the smallest
 ratio, in row order -- does not depend on the row count.  `_ratio_test_groups` restates the classifier of
 tests/lp_reference.py (`_device_ratio_test`) without its `nr > 128` exit and counts the tied rows per group of 64; the
@@ -21,7 +21,7 @@ from tests import lp_reference as LR
 
 def _ratio_test_groups(T, s, nv, nr, rhs):
     """tests/lp_reference.py `_device_ratio_test` for up to four row groups: the same expressions, no `nr > 128` exit
-    (csrc/fjsp_lp_global.hip lpg_pivots, "lexicographic ratio test")."""
+    (csrc/fjsp_lp_simplex.h lp_leaving_row<4>, "lexicographic ratio test")."""
     out = dict(n_elig=0, n_tied=0, tied_lo=0, tied_hi=0, tied_group=[0, 0, 0, 0], bad=False, steps=0, decided="scan",
                n_sign=0, n_div=0, small=False, lex_row=None)
     assert nr <= 256

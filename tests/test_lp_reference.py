@@ -1,7 +1,7 @@
 """CPU: the instrumented f64 restatement of the fluid-LP simplex (tests/lp_reference.py) against the host solver
 (csrc/fjsp_lp.cpp through instances.fluid_lp) and against scipy/HiGHS, on every fixture instance that has an LP and on the
 generated cases of tests/lp_cases.py; the coverage of the device simplex's branches those cases must keep; and the sweep
-behind "no admissible batch reaches the rows-beyond-128 code of csrc/fjsp_lp_device.hip".  No GPU is needed: what the
+behind "no admissible batch reaches the 128-row refusal of csrc/fjsp_lp_device.hip".  No GPU is needed: what the
 device file branches on is evaluated with its own expressions on the CPU (tests/lp_reference.py cites the lines).
 
 Ratio-test classes.  A pivot of the device simplex either finds one row at the smallest ratio ("single"), breaks the tie by
@@ -54,7 +54,7 @@ def _check_against_host(label, a, states):
         assert H.bits(obj) == H.bits(want_obj), what
         assert rec and (rec[0]["nr"], rec[0]["nc"]) == LR.tableau_shape(a.Jr, a.p, now)[:2], what
         for pv in rec:
-            # csrc/fjsp_lp_device.hip:143-155: on a clean split the first lexicographic minimum among the rows exactly at the
+            # csrc/fjsp_lp_simplex.h:213-222 (lp_leaving_row): on a clean split the first lexicographic minimum among the rows exactly at the
             # smallest ratio IS the row the sequential scan ends on
             if pv["nr"] <= 128 and not pv["bad"]:
                 assert pv["lex_row"] == pv["r"], "%s pivot %d: narrowing gives row %r, the scan row %d" % (what, pv["it"], pv["lex_row"], pv["r"])
@@ -155,14 +155,14 @@ def test_generated_cases_keep_their_coverage(built):
 
 
 def test_no_admissible_device_tableau_has_more_than_128_rows():
-    """csrc/fjsp_lp_device.hip keeps code for rows beyond 128 (the `nr <= 128` guard, the elimination loop from row 128,
-    the scan's later bases).  Creation admits K <= 256 operation types, M <= 32 machines, 1 <= R <= K kinds of at most 255
+    """csrc/fjsp_lp_device.hip holds two row groups of 64 in a lane and refuses an LP of more than 128 rows (error code 5,
+    before any tableau write).  Creation admits K <= 256 operation types, M <= 32 machines, 1 <= R <= K kinds of at most 255
     operations and K <= nx <= K M eligible pairs (csrc/fjsp_env.hip check_instance, csrc/fjsp_instance.cpp), and puts the
     LPs on the device only when lp_device_lds_bytes(K, M, nx, R, MP >= M) <= 156 KB and the tableau has at most 512
     columns (choose_lp_service).  The worst-case tableau has nr = K + M + (K - R) rows.  Over every such shape: none with
-    nr > 128 is admitted, so no batch reaches that code.  (nr >= 129 needs K >= 49, hence nc >= K + nr + 2 >= 180 and
+    nr > 128 is admitted, so no batch reaches that refusal.  (nr >= 129 needs K >= 49, hence nc >= K + nr + 2 >= 180 and
     129 * 180 * 8 = 185 760 B of tableau alone.)"""
-    # lp_device_lds_bytes (csrc/fjsp_lp_device.hip:44-49) by hand for K 2, M 1, nx 2, R 1: 4 rows x 8 columns
+    # lp_device_lds_bytes (csrc/fjsp_lp_limits.h) by hand for K 2, M 1, nx 2, R 1: 4 rows x 8 columns
     assert LC.lds_bytes(2, 1, 2, 1, 1) == (4 * 8 * 8 + 8 * 8 + 2 * 4 * 8 + 4 * 4 + 2 * 1 * 2 + 2 * 2 + 4 * 2 + 2 * 1 * 2 + 2 * 8 + 128 + 15) // 16 * 16 == 576
     largest, widest, checked = 0, 0, 0
     for K in range(1, 257):
