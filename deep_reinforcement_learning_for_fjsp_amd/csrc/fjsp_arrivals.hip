@@ -13,6 +13,7 @@
 #include <unordered_map>
 
 #include "fjsp_env_impl.h"
+#include "fjsp_lp_pool.h"
 
 namespace fjsp {
 // The device service's LP launch over the handle's staging arrays: the parked environments of the pending list (count_dev,
@@ -53,58 +54,6 @@ struct LpCache {
         const size_t add = k.size() + x.size() * sizeof(double) + 64;
         if (bytes + add > kMaxBytes) return;
         if (map.emplace(k, x).second) bytes += add;
-    }
-};
-
-// Persistent worker threads of the blocking service: run(n, fn) calls fn(q) for q in [0, n) on the
-// workers and the caller, returning when all are done.
-struct LpPool {
-    std::vector<std::thread> workers;
-    std::mutex mu;
-    std::condition_variable cv_work, cv_done;
-    std::function<void(uint32_t)> fn;
-    std::atomic<uint32_t> next{0};
-    uint32_t n = 0, generation = 0;
-    int active = 0;
-    bool stop = false;
-
-    explicit LpPool(int n_workers) {
-        for (int t = 0; t < n_workers; ++t) workers.emplace_back([this] { loop(); });
-    }
-    ~LpPool() {
-        { std::lock_guard<std::mutex> g(mu); stop = true; }
-        cv_work.notify_all();
-        for (auto &t : workers) t.join();
-    }
-    void drain() {
-        for (;;) {
-            const uint32_t q = next.fetch_add(1);
-            if (q >= n) return;
-            fn(q);
-        }
-    }
-    void loop() {
-        uint32_t seen = 0;
-        std::unique_lock<std::mutex> lk(mu);
-        for (;;) {
-            cv_work.wait(lk, [&] { return stop || generation != seen; });
-            if (stop) return;
-            seen = generation;
-            lk.unlock();
-            drain();
-            lk.lock();
-            if (--active == 0) cv_done.notify_one();
-        }
-    }
-    void run(uint32_t count, std::function<void(uint32_t)> f) {
-        {
-            std::lock_guard<std::mutex> g(mu);
-            fn = std::move(f); n = count; next.store(0); active = (int)workers.size(); ++generation;
-        }
-        cv_work.notify_all();
-        drain();
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return active == 0; });
     }
 };
 
@@ -247,25 +196,10 @@ int service_arrivals_impl(fjsp_env *e, const double *d_mo, double *d_state, doub
     HIP_TRY(hipStreamSynchronize(st));
     if (!A.cache) A.cache = new LpCache();
     // one LP per parked env, independent: spread over the host cores
-    std::atomic<int> fail{0};
-    std::string err;
-    std::mutex err_mu;
-    auto solve_one = [&](uint32_t q) {
-        if (fail.load()) return;
-        if (solve_parked_lp(e, (int)A.h_pending[1 + q], A.h_lp_in + (size_t)q * 2 * KP, A.h_lp_x + (size_t)q * KP * MP)) return;
-        std::lock_guard<std::mutex> g(err_mu);
-        if (fail.fetch_add(1) == 0) err = fjsp_last_error();     // thread-local message of this worker
-    };
-    int n_threads = A.lp_threads > 0 ? A.lp_threads : std::min((int)std::thread::hardware_concurrency(), 16);
-    if (n_threads <= 0) n_threads = 1;
-    if (n_threads == 1 || n == 1) {
-        for (uint32_t q = 0; q < n; ++q) solve_one(q);
-    } else {
-        if (A.pool && (int)A.pool->workers.size() != n_threads - 1) { delete A.pool; A.pool = nullptr; }
-        if (!A.pool) A.pool = new LpPool(n_threads - 1);
-        A.pool->run(n, solve_one);
-    }
-    if (fail.load()) { set_error(err); return FJSP_E_LP; }
+    const LpFailure bad = lp_pool_of(A.pool, A.lp_threads).run(n, [&](uint32_t q) {
+        return solve_parked_lp(e, (int)A.h_pending[1 + q], A.h_lp_in + (size_t)q * 2 * KP, A.h_lp_x + (size_t)q * KP * MP);
+    }, true);
+    if (bad) { set_error(bad.msg); return FJSP_E_LP; }
     HIP_TRY(hipMemcpyAsync(b.lp_x, A.h_lp_x, (size_t)n * KP * MP * 8, hipMemcpyHostToDevice, st));
     if (launch_arrival(b, d_mo, (int)n, b.pending_count + 1, b.lp_x, d_state, d_reward, d_done, d_trace, st) != 0) { set_error("arrival_kernel launch failed"); return FJSP_E_HIP; }
     HIP_TRY(hipMemsetAsync(b.pending_count, 0, 4, st));

@@ -21,24 +21,6 @@ namespace {
 // Python round(): half to even on the correctly rounded quotient (class_FJSSP.py:214-218)
 long py_round(double v) { return (long)std::nearbyint(v); }
 
-// Zeroed device memory / pinned host memory owned by the handle: fjsp_env_destroy frees it.
-template <class T>
-bool dev_alloc(fjsp_env *e, size_t bytes, T **d, const char *what) {
-    void *p = nullptr;
-    if (!hip_ok(hipMalloc(&p, bytes), what)) return false;
-    e->dev_allocs.push_back(p);
-    *d = static_cast<T *>(p);
-    return hip_ok(hipMemset(p, 0, bytes), "hipMemset");
-}
-template <class T>
-bool host_alloc(fjsp_env *e, size_t bytes, T **h) {
-    void *p = nullptr;
-    if (!hip_ok(hipHostMalloc(&p, bytes, hipHostMallocDefault), "hipHostMalloc")) return false;
-    e->host_allocs.push_back(p);
-    *h = static_cast<T *>(p);
-    return true;
-}
-
 // ---- fjsp_env_create_family, stage by stage
 
 // Stage 1 (before any HIP call): the kernels can play `in` as `variant`; its sizes go into *sh.
@@ -345,9 +327,7 @@ void pack_instance(const Instance &in, const DevBatch &b, bool class_fjsp, unsig
 //  single-job batches: + the assigned-machine byte; the column gather has no unprocessed entries there (p u16 + {arrival,
 //  rate} f64 = 18 B per machine, one byte written) against p + unprocessed + {arrival, rate} = 26 B and 8 B written)
 double step_bytes_of(const Instance &in, const DevBatch &b) {
-    const double per_k = 28.0 + (b.single_job ? 1.0 : 4.0) + (b.MP > 8 ? 4.0 : 0.0) + (b.single_job ? 0.0 : 128.0);
-    const double gather = b.single_job ? in.M * 18.0 + 1.0 : in.M * 26.0 + 8.0;
-    double bytes = in.K * per_k + in.jobs_total() * 16.0 + in.M * 16.0 + 304.0 + gather + 2.0 + b.state_size * 8.0 + 9.0;
+    double bytes = step_bytes(b, in.K, in.jobs_total(), in.M);
     if (b.variant == FJSP_VARIANT_MO_DFJSP) bytes += in.M * 14.0 + 2.0 * sizeof(DynScalars);   // power column, idle power, last-task ends r/w, DynScalars r/w
     return bytes;
 }

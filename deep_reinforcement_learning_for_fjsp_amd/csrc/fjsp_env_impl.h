@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -12,7 +13,7 @@
 #include "fjsp_host.h"
 
 namespace fjsp {
-struct LpCache; struct LpPool; struct AsyncRing;   // fjsp_arrivals.hip
+struct LpCache; struct AsyncRing; struct LpPool;   // fjsp_arrivals.hip; fjsp_lp_pool.h
 struct GenState;                                   // fjsp_generate.hip
 
 // largest sizes over the instances of a batch
@@ -27,7 +28,7 @@ struct ArrivalService {
     uint32_t *h_pending = nullptr;
     uint16_t *h_lp_in = nullptr;
     double *h_lp_x = nullptr;
-    LpPool *pool = nullptr;
+    LpPool *pool = nullptr;     // host threads of the blocking service and of a generated handle's host LP route (lp_pool_of)
     AsyncRing *ring = nullptr;  // the asynchronous service (fjsp_env_step_async), built by its first call
     LpCache *cache = nullptr;   // solved LPs of the host services
     int lp_threads = 0;         // 0 = default (min(host cores, 16))
@@ -76,6 +77,33 @@ inline bool hip_ok(hipError_t e, const char *what) {
     do {                                               \
         if (!hip_ok((expr), #expr)) return FJSP_E_HIP; \
     } while (0)
+
+// Zeroed device memory / pinned host memory owned by the handle: fjsp_env_destroy frees it.  (At least 16 bytes: a
+// generated handle's lists can be empty.)
+template <class T>
+bool dev_alloc(fjsp_env *e, size_t bytes, T **d, const char *what) {
+    void *p = nullptr;
+    bytes = std::max<size_t>(bytes, 16);
+    if (!hip_ok(hipMalloc(&p, bytes), what)) return false;
+    e->dev_allocs.push_back(p);
+    *d = static_cast<T *>(p);
+    return hip_ok(hipMemset(p, 0, bytes), "hipMemset");
+}
+template <class T>
+bool host_alloc(fjsp_env *e, size_t bytes, T **h) {
+    void *p = nullptr;
+    if (!hip_ok(hipHostMalloc(&p, std::max<size_t>(bytes, 16), hipHostMallocDefault), "hipHostMalloc")) return false;
+    e->host_allocs.push_back(p);
+    *h = static_cast<T *>(p);
+    return true;
+}
+
+// Algorithmic HBM bytes of one env-step of an instance of K operation types, `jobs` jobs, M machines (the terms: step_bytes_of, fjsp_env.hip)
+inline double step_bytes(const DevBatch &b, int K, int jobs, int M) {
+    const double per_k = 28.0 + (b.single_job ? 1.0 : 4.0) + (b.MP > 8 ? 4.0 : 0.0) + (b.single_job ? 0.0 : 128.0);
+    const double gather = b.single_job ? M * 18.0 + 1.0 : M * 26.0 + 8.0;
+    return K * per_k + jobs * 16.0 + M * 16.0 + 304.0 + gather + 2.0 + b.state_size * 8.0 + 9.0;
+}
 
 struct DeviceGuard {
     int prev = -1;

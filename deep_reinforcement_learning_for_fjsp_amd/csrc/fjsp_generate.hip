@@ -10,7 +10,7 @@
 //                           (256 rows x 1536 columns), neither
 //   lp_device_kernel        (fjsp_lp_device.hip, unchanged) over the fitting list, in bounded chunks of staging slots
 //   lp_global_kernel        (fjsp_lp_global.hip) over the second of the three lists, on the second stream, in bounded chunks
-//   solve_fluid_lp          (fjsp_lp.cpp) on host threads for the last list: the solvers are pivot for pivot the same
+//   solve_fluid_lp          (fjsp_lp.cpp) on the handle's host threads for the last list: the solvers are pivot for pivot the same
 //   generate_finish_kernel  x from the staging slot into the record, the static state row
 //   fluid_tables_kernel, reset_kernel (fjsp_kernels.hip, unchanged), every env marked done: the state a create leaves
 //
@@ -22,16 +22,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <system_error>
-#include <thread>
 
 #include "fjsp_env_impl.h"
 #include "fjsp_launch.h"
+#include "fjsp_lp_pool.h"
 #include "fjsp_lp_limits.h"
 
 #pragma clang fp contract(off)
@@ -51,6 +49,10 @@ struct GenInfo {
 };
 static_assert(sizeof(GenInfo) == 48, "GenInfo is twelve words");
 
+// The words of GenArgs::counts, shared by the kernels and the host: the lengths of fit_ids and of host_ids, the largest fitting
+// tableau (bytes of LDS), the first instance whose LP left no rate (0xFFFFFFFF: none), the length of glob_ids
+enum GenCount : int { kCountFit, kCountHost, kCountLdsMax, kCountFailed, kCountGlob, kGenCounts };
+
 struct GenArgs {
     fjsp_gen_params g;       // ranged: g.M and g.DDT are not read
     int32_t ranged;          // 1: M and DDT of instance `seed` are draws 0 and 1 of the stream seed ^ FJSP_GEN_AUX_STREAM (fjsp_gen_ranges)
@@ -63,12 +65,12 @@ struct GenArgs {
     int32_t RP;
     uint8_t *elig;           // [n_inst][kmax][MP] machine_rj_dict in FILE order (zeros behind each list)
     GenInfo *info;           // [n_inst]
-    uint32_t *counts;        // [0] length of fit_ids, [1] of host_ids, [2] largest fitting tableau (bytes), [3] first instance whose LP left no rate
+    uint32_t *counts;        // [kGenCounts], by GenCount
     uint32_t *fit_ids;       // [n_inst] instances whose LP runs on the device, in arrival order
     uint32_t *host_ids;      // [n_inst] the others
     uint16_t *lp_in;         // [slot of fit_ids][2][KP] (Q, n_now), lp_device_kernel's format
     // FJSP_LP_IMPL=global: the third list -- tableaus beyond the LDS rule and within kLpGlobalRows x kLpGlobalColumns;
-    // its length is counts[4]
+    // its length is counts[kCountGlob]
     int32_t allow_global;
     uint32_t *glob_ids;      // [n_inst]
     uint16_t *lp_in_glob;    // [slot of glob_ids][2][KP]
@@ -247,12 +249,12 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     const bool glob = !fit && a.allow_global && nc - nx - 2 <= kLpGlobalRows && nc <= kLpGlobalColumns;
     if (l == 0) {
         if (fit) {
-            s_hdr[0] = (int)atomicAdd(a.counts + 0, 1u);
-            atomicMax(a.counts + 2, lds);
+            s_hdr[0] = (int)atomicAdd(a.counts + kCountFit, 1u);
+            atomicMax(a.counts + kCountLdsMax, lds);
         } else if (glob) {
-            s_hdr[0] = (int)atomicAdd(a.counts + 4, 1u);
+            s_hdr[0] = (int)atomicAdd(a.counts + kCountGlob, 1u);
         } else {
-            a.host_ids[atomicAdd(a.counts + 1, 1u)] = (uint32_t)inst;
+            a.host_ids[atomicAdd(a.counts + kCountHost, 1u)] = (uint32_t)inst;
         }
     }
     __syncthreads();
@@ -305,7 +307,7 @@ __global__ __launch_bounds__(kWave) void generate_finish_kernel(DevBatch b, GenA
         if (k == 0 || v > best) best = v;
     }
     ss[7] = best;
-    if (!lp_ok) atomicMin(a.counts + 3, (uint32_t)inst);
+    if (!lp_ok) atomicMin(a.counts + kCountFailed, (uint32_t)inst);
     if (b.variant == FJSP_VARIANT_MO_FJSSP_DISCRETES) {
         // MO_FJSSP_discretes.py:55-64 static_state_extract; the host's pow(d, 2.0) is d * d here
         long ns = 0, js = 0;
@@ -340,61 +342,64 @@ __global__ __launch_bounds__(256) void generate_mark_done_kernel(DevBatch b, uin
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
+struct LpCounters { unsigned long long solved, pivots; };      // what a device simplex counts (launch_lp_device's `solved`)
+
+// One way the order-0 LPs get solved.  generate_pack_kernel puts every instance on one route's list; the host runs each
+// list in chunks of GenState::chunk staging slots: its producer leaves x in d_stage, generate_finish_kernel takes it from there.
+struct LpRoute {
+    enum Producer { kLds, kGlobal, kHost } producer = kLds;     // lp_device_kernel; lp_global_kernel; gather, solve on host threads, upload
+    GenCount length = kCountFit;      // the counts word that holds the list's length
+    const char *launch_error = "";    // when a launch of the route fails
+    uint32_t *ids = nullptr;          // the list, on the device
+    uint16_t *lp_in = nullptr;        // [slot of ids][2][KP] (Q, n_now): device routes
+    double *d_stage = nullptr;        // [chunk][KP][MP] x; nullptr: the handle has no such route
+    LpCounters *d_solved = nullptr, *h_solved = nullptr;    // device routes: the kernel's counters and where the host reads them
+    hipStream_t st = nullptr;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;        // device routes: the time of their launches (the first route's begins at ev_packed)
+    bool present() const { return d_stage != nullptr; }
+};
+enum GenRoute : int { kRouteLds, kRouteGlobal, kRouteHost, kGenRoutes };      // in the order they are started
+
+// The slots of GenState::stats and ::ms (milliseconds), of the last call.  Their values ARE the positions in the arrays that
+// fjsp_env_generated_stats (the first four), _times (the first five) and _stats2 (all six) fill: the ABI's order is stated here alone.
+enum GenStat : int { kStatInstances, kStatLpLds, kStatLpHost, kStatDevicePivots, kStatLpGlobal, kStatGlobalPivots, kGenStats };
+enum GenTime : int { kMsGenerate, kMsLpLds, kMsLpHost, kMsTablesReset, kMsTotal, kMsLpGlobal, kGenTimes };
+struct LpErrWord { uint32_t code, unused; };                    // launch_lp_device's `err`: nonzero when an LP failed on the device
+struct GenReadback { LpCounters lds, glob; LpErrWord lp_err; };  // pinned: what the host reads of the device simplexes
+
 struct GenState {
     GenArgs a{};
+    LpRoute route[kGenRoutes];
     int chunk = 0;                       // staging slots of one LP launch / one host-route round
     int head16 = 0;                      // 16-byte words of a record in front of x
     uint8_t *d_kenv = nullptr;
-    double *d_stage = nullptr, *d_stage_host = nullptr;     // [chunk][KP][MP] x of the device route / uploaded from the host route
-    uint4 *d_head = nullptr;             // [chunk][head16]
     uint32_t *d_lp_err = nullptr;
-    unsigned long long *d_lp_solved = nullptr;
-    // pinned
+    uint4 *d_head = nullptr, *h_head = nullptr;      // [chunk][head16] record heads of the host route, and pinned
+    double *h_stage = nullptr;           // pinned, as all that follow: [chunk][KP][MP] x of the host route
     GenInfo *h_info = nullptr;
     uint32_t *h_counts = nullptr, *h_host_ids = nullptr;
-    double *h_stage = nullptr;
-    uint4 *h_head = nullptr;
-    unsigned long long *h_lp = nullptr;  // [0..1] lp_device_kernel's counters, [2] its error word
-    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [4], [5]: around the global-memory LP launches; [6]: after the wait for them
-    hipStream_t st_dev = nullptr, st_host = nullptr;       // the two routes run side by side
-    // instances, LPs on the device (LDS), LPs on the host, device pivots, LPs of the global-memory simplex, its pivots: of the last call
-    int64_t stats[6] = {0, 0, 0, 0, 0, 0};
-    // generate kernel, LP launches + finish, host route, tables + reset, whole call, global-memory LP launches + finish
-    double ms[6] = {0, 0, 0, 0, 0, 0};
-    // FJSP_LP_IMPL=global only (nothing of it is allocated otherwise)
-    LpGlobalPool pool;
-    double *d_stage_glob = nullptr;      // [chunk][KP][MP]
-    unsigned long long *d_lp_solved_glob = nullptr;
+    GenReadback *h_back = nullptr;
+    hipEvent_t ev_start = nullptr, ev_packed = nullptr, ev_end = nullptr;
+    hipEvent_t ev_joined = nullptr;      // a side route's x has reached the first stream
+    hipEvent_t ev_lps = nullptr;         // (not owned) the event on the first stream behind which every device route's x is there
+    hipStream_t st_dev = nullptr, st_host = nullptr;       // the first route's stream and the side routes': they run side by side
+    int64_t stats[kGenStats] = {};
+    double ms[kGenTimes] = {};
+    LpGlobalPool pool;                   // FJSP_LP_IMPL=global only (nothing of that route is allocated otherwise)
 };
 
 void generated_release(fjsp_env *e) {
     if (!e || !e->gen) return;
-    for (hipEvent_t ev : e->gen->ev)
+    GenState &G = *e->gen;
+    for (hipEvent_t ev : {G.ev_start, G.ev_packed, G.ev_end, G.ev_joined, G.route[kRouteLds].ev_end, G.route[kRouteGlobal].ev_begin, G.route[kRouteGlobal].ev_end})
         if (ev) (void)hipEventDestroy(ev);
-    if (e->gen->st_dev) (void)hipStreamDestroy(e->gen->st_dev);
-    if (e->gen->st_host) (void)hipStreamDestroy(e->gen->st_host);
+    for (hipStream_t st : {G.st_dev, G.st_host})
+        if (st) (void)hipStreamDestroy(st);
     delete e->gen;
     e->gen = nullptr;
 }
 
 namespace {
-template <class T>
-bool gen_dev_alloc(fjsp_env *e, size_t bytes, T **d, const char *what) {
-    void *p = nullptr;
-    if (!hip_ok(hipMalloc(&p, std::max<size_t>(bytes, 16)), what)) return false;
-    e->dev_allocs.push_back(p);
-    *d = static_cast<T *>(p);
-    return hip_ok(hipMemset(p, 0, std::max<size_t>(bytes, 16)), "hipMemset");
-}
-template <class T>
-bool gen_host_alloc(fjsp_env *e, size_t bytes, T **h) {
-    void *p = nullptr;
-    if (!hip_ok(hipHostMalloc(&p, std::max<size_t>(bytes, 16), hipHostMallocDefault), "hipHostMalloc")) return false;
-    e->host_allocs.push_back(p);
-    *h = static_cast<T *>(p);
-    return true;
-}
-
 // the checks of generate() (fjsp_instance.cpp)
 int check_params(const fjsp_gen_params &g) {
     if (g.M <= 0 || g.S <= 0 || g.R_min <= 0 || g.R_max < g.R_min || g.J_min <= 0 || g.J_max < g.J_min ||
@@ -449,74 +454,22 @@ uint64_t gen_hash(const GenArgs &a, int n_inst, uint64_t seed_base) {
     return h;
 }
 
-double step_bytes_mean(const fjsp_env *e) {        // step_bytes_of (fjsp_env.hip) over what the device generated
-    const DevBatch &b = e->b;
-    const GenState &G = *e->gen;
-    const double per_k = 28.0 + (b.single_job ? 1.0 : 4.0) + (b.MP > 8 ? 4.0 : 0.0) + (b.single_job ? 0.0 : 128.0);
-    double bytes = 0.0;
-    for (int i = 0; i < b.n_inst; ++i) {
-        const double M = (double)G.h_info[i].M;
-        const double gather = b.single_job ? M * 18.0 + 1.0 : M * 26.0 + 8.0;
-        bytes += G.h_info[i].K * per_k + G.h_info[i].nj * 16.0 + M * 16.0 + 304.0 + gather + 2.0 + b.state_size * 8.0 + 9.0;
-    }
-    return bytes;
-}
-
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+double ms_between(hipEvent_t a, hipEvent_t b) { float f = 0.f; (void)hipEventElapsedTime(&f, a, b); return f; }
 
-// The LPs of host_ids[first, first + n) on host threads, x into G.h_stage[slot]; 0 or the first failing slot + 1
-int solve_on_host(fjsp_env *e, int n) {
-    GenState &G = *e->gen;
-    const DevBatch &b = e->b;
-    const size_t KP = (size_t)b.KP, MP = (size_t)b.MP, head = (size_t)G.head16 * 16;
-    int n_threads = e->arr.lp_threads > 0 ? e->arr.lp_threads : std::min((int)std::thread::hardware_concurrency(), 16);
-    n_threads = std::max(1, std::min(n_threads, n));
-    std::atomic<int> next(0), fail(0);
-    auto work = [&]() {
-        std::vector<int> Jr, p, Q, now;
-        std::vector<double> x;
-        for (;;) {
-            const int s = next.fetch_add(1);
-            if (s >= n) break;
-            const unsigned char *rec = reinterpret_cast<const unsigned char *>(G.h_head) + (size_t)s * head;
-            const InstHeader h = *reinterpret_cast<const InstHeader *>(rec);
-            const uint32_t *kA = reinterpret_cast<const uint32_t *>(rec + b.L.i_kA), *kB = reinterpret_cast<const uint32_t *>(rec + b.L.i_kB);
-            const uint16_t *p16 = reinterpret_cast<const uint16_t *>(rec + b.L.i_p);
-            Jr.assign((size_t)h.R, 0); p.assign((size_t)h.K * h.M, 0); Q.assign((size_t)h.K, 0); now.assign((size_t)h.K, 0);
-            x.assign((size_t)h.K * h.M, 0.0);
-            int r = -1;
-            for (int k = 0; k < h.K; ++k) {
-                const int j = (int)(kB[k] & 0xFFu);
-                if (j == 0) { ++r; Jr[(size_t)r] = (int)((kB[k] >> 8) & 0xFFu); }
-                Q[(size_t)k] = (int)(kA[k] >> 16);
-                now[(size_t)k] = j == 0 ? Q[(size_t)k] : 0;
-                for (int m = 0; m < h.M; ++m) p[(size_t)k * h.M + m] = p16[(size_t)k * MP + m];
-            }
-            double obj = 0.0;
-            double *out = G.h_stage + (size_t)s * KP * MP;
-            std::memset(out, 0, KP * MP * 8);
-            if (solve_fluid_lp(h.R, h.M, Jr.data(), p.data(), Q.data(), now.data(), x.data(), &obj) != 0) {
-                int zero = 0;
-                fail.compare_exchange_strong(zero, s + 1);
-                continue;
-            }
-            for (int k = 0; k < h.K; ++k)
-                for (int m = 0; m < h.M; ++m) out[(size_t)k * MP + m] = x[(size_t)k * h.M + m];
-        }
-    };
-    if (n_threads == 1) work();
-    else {
-        std::vector<std::thread> th;
-        th.reserve((size_t)n_threads);
-        try {
-            for (int t = 0; t < n_threads; ++t) th.emplace_back(work);
-        } catch (const std::system_error &) {       // no more threads to be had: the calling thread takes the rest
-            work();
-        }
-        for (auto &t : th) t.join();
+// The head of a packed record (pack_instance, generate_pack_kernel: everything in front of x) back on the host
+struct RecordHead { InstHeader h{}; std::vector<int> Jr, count, p; };      // [R], [R] jobs of every kind, [K][M] unpadded
+void decode_head(const DevBatch &b, const unsigned char *rec, RecordHead &o) {
+    o.h = *reinterpret_cast<const InstHeader *>(rec);
+    const uint32_t *kA = reinterpret_cast<const uint32_t *>(rec + b.L.i_kA), *kB = reinterpret_cast<const uint32_t *>(rec + b.L.i_kB);
+    const uint16_t *p16 = reinterpret_cast<const uint16_t *>(rec + b.L.i_p);
+    const size_t K = (size_t)o.h.K, M = (size_t)o.h.M;
+    o.Jr.clear(); o.count.clear(); o.p.assign(K * M, 0);
+    for (size_t k = 0; k < K; ++k) {
+        if ((kB[k] & 0xFFu) == 0u) { o.Jr.push_back((int)((kB[k] >> 8) & 0xFFu)); o.count.push_back((int)(kA[k] >> 16)); }     // a kind's first operation type
+        for (size_t m = 0; m < M; ++m) o.p[k * M + m] = p16[k * (size_t)b.MP + m];
     }
-    return fail.load();
 }
 
 int fail_generate(fjsp_env *e, int rc, const std::string &msg) {
@@ -524,134 +477,164 @@ int fail_generate(fjsp_env *e, int rc, const std::string &msg) {
     set_error(msg);
     return rc;
 }
+std::string who(uint64_t seed_base, size_t i) { return "instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ")"; }
+int launch_failed(const char *text) { set_error(text); return FJSP_E_HIP; }
+
+// The host route's producer: the record heads of ids[c0, c0 + n) read back, their order-0 LPs (solve_order0) on the
+// handle's host threads, x uploaded into the staging slots
+int solve_on_host(fjsp_env *e, const LpRoute &r, int c0, int n, const std::string &call) {
+    GenState &G = *e->gen;
+    const DevBatch &b = e->b;
+    const size_t KP = (size_t)b.KP, MP = (size_t)b.MP, head = (size_t)G.head16 * 16, words = (size_t)n * (size_t)G.head16;
+    if (launch(generate_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r.st, b, (const uint32_t *)(r.ids + c0), n, G.d_head, G.head16) != 0)
+        return launch_failed("generate_gather_kernel launch failed");
+    HIP_TRY(hipMemcpyAsync(G.h_head, G.d_head, words * 16, hipMemcpyDeviceToHost, r.st));
+    HIP_TRY(hipStreamSynchronize(r.st));
+    const LpFailure bad = lp_pool_of(e->arr.pool, e->arr.lp_threads).run((uint32_t)n, [&](uint32_t s) {
+        static thread_local RecordHead in;        // a thread's buffers, kept across its LPs
+        static thread_local std::vector<int> Q, now;
+        static thread_local std::vector<double> x;
+        decode_head(b, reinterpret_cast<const unsigned char *>(G.h_head) + (size_t)s * head, in);
+        const int K = in.h.K, M = in.h.M;
+        Q.clear(); now.clear(); x.assign((size_t)K * M, 0.0);
+        for (int kind = 0; kind < in.h.R; ++kind)
+            for (int j = 0; j < in.Jr[(size_t)kind]; ++j) { Q.push_back(in.count[(size_t)kind]); now.push_back(j == 0 ? in.count[(size_t)kind] : 0); }
+        double obj = 0.0, *out = G.h_stage + (size_t)s * KP * MP;
+        std::memset(out, 0, KP * MP * 8);
+        if (solve_fluid_lp(in.h.R, M, in.Jr.data(), in.p.data(), Q.data(), now.data(), x.data(), &obj) != 0) return false;
+        for (int k = 0; k < K; ++k)
+            for (int m = 0; m < M; ++m) out[(size_t)k * MP + m] = x[(size_t)k * M + m];
+        return true;
+    });
+    if (bad) return fail_generate(e, FJSP_E_LP, call + ": the fluid LP of " + who(G.a.seed_base, G.h_host_ids[c0 + bad.index]) + " failed");
+    HIP_TRY(hipMemcpyAsync(r.d_stage, G.h_stage, (size_t)n * KP * MP * 8, hipMemcpyHostToDevice, r.st));
+    return FJSP_OK;
+}
+
+// The n LPs of route r, in bounded chunks of staging slots: each its producer and the finish of its instances
+int run_route(fjsp_env *e, const LpRoute &r, int n_total, const std::string &call) {
+    GenState &G = *e->gen;
+    const DevBatch &b = e->b;
+    const bool side = r.st != G.st_dev;               // on the second stream, beside the first route
+    if (side && n_total == 0) return FJSP_OK;         // (the first route always marks its end: the tables' time counts from there)
+    if (r.ev_begin) HIP_TRY(hipEventRecord(r.ev_begin, r.st));
+    for (int c0 = 0; c0 < n_total; c0 += G.chunk) {
+        const int n = std::min(G.chunk, n_total - c0);
+        const uint32_t *ids = r.ids + c0;
+        const uint16_t *lp_in = r.lp_in ? r.lp_in + (size_t)c0 * 2 * (size_t)b.KP : nullptr;
+        int rc = FJSP_OK, launched = 0;
+        if (r.producer == LpRoute::kLds) launched = launch_lp_device(b, nullptr, n, ids, lp_in, r.d_stage, G.d_lp_err, &r.d_solved->solved, G.h_counts[kCountLdsMax], r.st);
+        else if (r.producer == LpRoute::kGlobal) launched = launch_lp_global(b, nullptr, n, ids, lp_in, r.d_stage, G.d_lp_err, &r.d_solved->solved, G.pool, r.st);
+        else rc = solve_on_host(e, r, c0, n, call);
+        if (rc != FJSP_OK) return rc;
+        if (launched != 0 || launch(generate_finish_kernel, dim3((unsigned)n), dim3(kWave), 0, r.st, b, G.a, ids, n, (const double *)r.d_stage) != 0) return launch_failed(r.launch_error);
+        if (r.producer == LpRoute::kHost) HIP_TRY(hipStreamSynchronize(r.st));       // h_stage and h_head are reused by the next round
+    }
+    if (!r.ev_end) return FJSP_OK;
+    HIP_TRY(hipEventRecord(r.ev_end, r.st));
+    G.ev_lps = r.ev_end;
+    if (side) {       // the tables read every x
+        HIP_TRY(hipStreamWaitEvent(G.st_dev, r.ev_end, 0));
+        HIP_TRY(hipEventRecord(G.ev_joined, G.st_dev));
+        G.ev_lps = G.ev_joined;
+    }
+    return FJSP_OK;
+}
 
 // The whole refill: records, LPs, tables, reset.  Synchronous; on the handle's device.
 int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::string &call) {
     GenState &G = *e->gen;
     DevBatch &b = e->b;
-    const size_t N = (size_t)b.N, KP = (size_t)b.KP, MP = (size_t)b.MP, n_inst = (size_t)b.n_inst;
+    const size_t N = (size_t)b.N, n_inst = (size_t)b.n_inst;
     const auto t_call = Clock::now();
     HIP_TRY(hipDeviceSynchronize());         // steps still queued on any stream read the records this call rewrites
     e->gen_failed = true;                    // until the call has gone through
     G.a.seed_base = seed_base;
     b.rng_seed = rng_seed;
-    std::memset(G.stats, 0, sizeof(G.stats));
-    std::memset(G.ms, 0, sizeof(G.ms));
-    hipStream_t st = G.st_dev, sh = G.st_host;
+    std::fill(G.stats, G.stats + kGenStats, 0);
+    std::fill(G.ms, G.ms + kGenTimes, 0.0);
+    hipStream_t st = G.st_dev;
+    // ---- clear
     HIP_TRY(hipMemsetAsync(b.inst, 0, n_inst * b.L.i_stride, st));
     HIP_TRY(hipMemsetAsync(b.envs, 0, N * b.L.e_stride, st));       // the draw counters too: the env streams start over
-    HIP_TRY(hipMemsetAsync(G.a.counts, 0, 12, st));
-    HIP_TRY(hipMemsetAsync(G.a.counts + 3, 0xFF, 4, st));
-    HIP_TRY(hipMemsetAsync(G.a.counts + 4, 0, 16, st));
-    if (G.d_lp_solved_glob) HIP_TRY(hipMemsetAsync(G.d_lp_solved_glob, 0, 16, st));
-    HIP_TRY(hipMemsetAsync(G.d_lp_solved, 0, 16, st));
-    HIP_TRY(hipMemsetAsync(G.d_lp_err, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(G.a.counts, 0, kGenCounts * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(G.a.counts + kCountFailed, 0xFF, sizeof(uint32_t), st));
+    for (const LpRoute &r : G.route) if (r.d_solved) HIP_TRY(hipMemsetAsync(r.d_solved, 0, sizeof(LpCounters), st));
+    HIP_TRY(hipMemsetAsync(G.d_lp_err, 0, sizeof(LpErrWord), st));
     if (e->sched.rec) HIP_TRY(hipMemsetAsync(e->sched.rec, 0, (size_t)e->sched.cap * N * sizeof(uint4), st));
-    HIP_TRY(hipEventRecord(G.ev[0], st));
-    if (launch(generate_pack_kernel, dim3((unsigned)n_inst), dim3(kWave), 0, st, b, G.a) != 0) { set_error("generate_pack_kernel launch failed"); return FJSP_E_HIP; }
-    HIP_TRY(hipEventRecord(G.ev[1], st));
-    // the call's one read-back before the LPs: status words, sizes, the two lists' lengths, the host list
+    // ---- pack
+    HIP_TRY(hipEventRecord(G.ev_start, st));
+    if (launch(generate_pack_kernel, dim3((unsigned)n_inst), dim3(kWave), 0, st, b, G.a) != 0) return launch_failed("generate_pack_kernel launch failed");
+    HIP_TRY(hipEventRecord(G.ev_packed, st));
+    // ---- the call's one read-back before the LPs: status words, sizes, the lists' lengths, the host list; validate
     HIP_TRY(hipMemcpyAsync(G.h_info, G.a.info, n_inst * sizeof(GenInfo), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, 32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(G.h_host_ids, G.a.host_ids, n_inst * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, kGenCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(G.h_host_ids, G.a.host_ids, n_inst * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    double bytes = 0.0;
     for (size_t i = 0; i < n_inst; ++i) {
         const GenInfo &f = G.h_info[i];
-        const std::string who = "instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ")";
         if (f.status == FJSP_E_UNSUPPORTED)
-            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
+            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
         if (f.status != 0)
-            return fail_generate(e, f.status, call + ": " + who + ": a draw left the record's fields (internal error)");
+            return fail_generate(e, f.status, call + ": " + who(seed_base, i) + ": a draw left the record's fields (internal error)");
         if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP)
-            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who + ": sizes disagree with the host's (internal error)");
+            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": sizes disagree with the host's (internal error)");
+        bytes += step_bytes(b, f.K, f.nj, f.M);
     }
-    const int n_fit = (int)G.h_counts[0], n_host = (int)G.h_counts[1], n_glob = (int)G.h_counts[4];
-    if ((size_t)n_fit + (size_t)n_host + (size_t)n_glob != n_inst || (n_glob > 0 && !G.pool.mem)) return fail_generate(e, FJSP_E_HIP, call + ": the LP lists do not cover the instances (internal error)");
+    size_t listed = 0;
+    bool routed = true;      // no instance is on a list this handle has no route for
+    for (const LpRoute &r : G.route) { listed += G.h_counts[r.length]; routed = routed && (r.present() || G.h_counts[r.length] == 0); }
+    if (listed != n_inst || !routed) return fail_generate(e, FJSP_E_HIP, call + ": the LP lists do not cover the instances (internal error)");
+    const int n_host = (int)G.h_counts[kCountHost];
     if (e->plan.lp_device_forced == 1 && n_host > 0) {
-        uint32_t i = G.h_host_ids[0];
-        for (int q = 1; q < n_host; ++q) i = std::min(i, G.h_host_ids[q]);
+        const uint32_t i = *std::min_element(G.h_host_ids, G.h_host_ids + n_host);
         const GenInfo &f = G.h_info[i];
-        return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": FJSP_LP_IMPL=device, but the order-0 tableau of instance " + std::to_string(i) +
-                             " (seed " + std::to_string(seed_base + i) + ") does not fit: " + std::to_string(f.lds) + " bytes of LDS (limit " +
+        return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": FJSP_LP_IMPL=device, but the order-0 tableau of " + who(seed_base, i) +
+                             " does not fit: " + std::to_string(f.lds) + " bytes of LDS (limit " +
                              std::to_string(kLpLdsLimit) + "), " + std::to_string(lp_max_columns(f.K, f.M, f.nx, f.R)) + " columns (limit " +
                              std::to_string(kLpLdsColumns) + ")");
     }
     for (size_t i = 0; i < n_inst; ++i) { e->inst_K[i] = G.h_info[i].K; e->inst_M[i] = G.h_info[i].M; }
-    e->step_bytes = (int64_t)(step_bytes_mean(e) / (double)n_inst + 0.5);
-    // ---- device route: bounded chunks of staging slots, each an LP launch and the finish of its instances
-    const size_t lds = G.h_counts[2];
-    for (int c0 = 0; c0 < n_fit; c0 += G.chunk) {
-        const int n = std::min(G.chunk, n_fit - c0);
-        if (launch_lp_device(b, nullptr, n, G.a.fit_ids + c0, G.a.lp_in + (size_t)c0 * 2 * KP, G.d_stage, G.d_lp_err, G.d_lp_solved, lds, st) != 0 ||
-            launch(generate_finish_kernel, dim3((unsigned)n), dim3(kWave), 0, st, b, G.a, (const uint32_t *)(G.a.fit_ids + c0), n, (const double *)G.d_stage) != 0) {
-            set_error("lp_device_kernel / generate_finish_kernel launch failed"); return FJSP_E_HIP;
-        }
+    e->step_bytes = (int64_t)(bytes / (double)n_inst + 0.5);
+    // ---- the routes: the device's on their streams, then the host's while the device works on its lists
+    for (const LpRoute &r : G.route) {
+        if (!r.present()) continue;
+        const auto t_route = Clock::now();
+        if (const int rc = run_route(e, r, (int)G.h_counts[r.length], call)) return rc;
+        if (r.producer == LpRoute::kHost && n_host) G.ms[kMsLpHost] = ms_since(t_route);
     }
-    HIP_TRY(hipEventRecord(G.ev[2], st));
-    // ---- the tableaus beyond the LDS (FJSP_LP_IMPL=global): the global-memory simplex on the second stream, beside the first list
-    if (n_glob > 0) {
-        HIP_TRY(hipEventRecord(G.ev[4], sh));
-        for (int c0 = 0; c0 < n_glob; c0 += G.chunk) {
-            const int n = std::min(G.chunk, n_glob - c0);
-            if (launch_lp_global(b, nullptr, n, G.a.glob_ids + c0, G.a.lp_in_glob + (size_t)c0 * 2 * KP, G.d_stage_glob, G.d_lp_err, G.d_lp_solved_glob, G.pool, sh) != 0 ||
-                launch(generate_finish_kernel, dim3((unsigned)n), dim3(kWave), 0, sh, b, G.a, (const uint32_t *)(G.a.glob_ids + c0), n, (const double *)G.d_stage_glob) != 0) {
-                set_error("lp_global_kernel / generate_finish_kernel launch failed"); return FJSP_E_HIP;
-            }
-        }
-        HIP_TRY(hipEventRecord(G.ev[5], sh));
-        HIP_TRY(hipStreamWaitEvent(st, G.ev[5], 0));     // the tables below read every x
-        HIP_TRY(hipEventRecord(G.ev[6], st));
-    }
-    // ---- host route, while the device works on its lists
-    const auto t_host = Clock::now();
-    for (int c0 = 0; c0 < n_host; c0 += G.chunk) {
-        const int n = std::min(G.chunk, n_host - c0);
-        const size_t words = (size_t)n * (size_t)G.head16;
-        if (launch(generate_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, sh, b, (const uint32_t *)(G.a.host_ids + c0), n, G.d_head, G.head16) != 0) {
-            set_error("generate_gather_kernel launch failed"); return FJSP_E_HIP;
-        }
-        HIP_TRY(hipMemcpyAsync(G.h_head, G.d_head, words * 16, hipMemcpyDeviceToHost, sh));
-        HIP_TRY(hipStreamSynchronize(sh));
-        const int bad = solve_on_host(e, n);
-        if (bad) {
-            const uint32_t i = G.h_host_ids[c0 + bad - 1];
-            return fail_generate(e, FJSP_E_LP, call + ": the fluid LP of instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ") failed");
-        }
-        HIP_TRY(hipMemcpyAsync(G.d_stage_host, G.h_stage, (size_t)n * KP * MP * 8, hipMemcpyHostToDevice, sh));
-        if (launch(generate_finish_kernel, dim3((unsigned)n), dim3(kWave), 0, sh, b, G.a, (const uint32_t *)(G.a.host_ids + c0), n, (const double *)G.d_stage_host) != 0) {
-            set_error("generate_finish_kernel launch failed"); return FJSP_E_HIP;
-        }
-        HIP_TRY(hipStreamSynchronize(sh));       // h_stage and h_head are reused by the next round
-    }
-    G.ms[2] = n_host ? ms_since(t_host) : 0.0;
     // ---- the fluid tables, one reset of every env (publishes i_obs0), every env done again: as upload_batch leaves them
     const dim3 gN((unsigned)((N + 255) / 256));
     if (launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, G.d_kenv) != 0 || launch_fluid_tables(b, st) != 0 ||
-        launch_reset(b, nullptr, nullptr, st) != 0 || launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, (uint8_t *)nullptr) != 0) {
-        set_error("fluid_tables_kernel / reset_kernel launch failed"); return FJSP_E_HIP;
-    }
-    HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(G.h_lp, G.d_lp_solved, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(G.h_lp + 2, G.d_lp_err, 8, hipMemcpyDeviceToHost, st));
-    if (G.d_lp_solved_glob) HIP_TRY(hipMemcpyAsync(G.h_lp + 4, G.d_lp_solved_glob, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(G.ev[3], st));
+        launch_reset(b, nullptr, nullptr, st) != 0 || launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, (uint8_t *)nullptr) != 0)
+        return launch_failed("fluid_tables_kernel / reset_kernel launch failed");
+    // ---- the counters
+    HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, kGenCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    for (const LpRoute &r : G.route) if (r.d_solved) HIP_TRY(hipMemcpyAsync(r.h_solved, r.d_solved, sizeof(LpCounters), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&G.h_back->lp_err, G.d_lp_err, sizeof(LpErrWord), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(G.ev_end, st));
     HIP_TRY(hipDeviceSynchronize());
-    float f01 = 0.f, f12 = 0.f, f23 = 0.f;
-    (void)hipEventElapsedTime(&f23, G.ev[n_glob > 0 ? 6 : 2], G.ev[3]);
-    (void)hipEventElapsedTime(&f01, G.ev[0], G.ev[1]);
-    (void)hipEventElapsedTime(&f12, G.ev[1], G.ev[2]);
-    G.ms[0] = f01; G.ms[1] = f12; G.ms[3] = f23;
-    if (n_glob > 0) { float f45 = 0.f; (void)hipEventElapsedTime(&f45, G.ev[4], G.ev[5]); G.ms[5] = f45; }
-    if (G.h_counts[3] != 0xFFFFFFFFu || (uint32_t)G.h_lp[2] != 0u) {
-        const uint32_t i = G.h_counts[3];
-        return fail_generate(e, FJSP_E_LP, i != 0xFFFFFFFFu ? call + ": the fluid LP of instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ") failed"
-                                                            : call + ": a fluid LP failed on the device (code " + std::to_string((uint32_t)G.h_lp[2]) + ")");
+    // ---- report
+    const LpRoute &lds = G.route[kRouteLds], &glob = G.route[kRouteGlobal];
+    const int n_glob = (int)G.h_counts[kCountGlob];
+    G.ms[kMsGenerate] = ms_between(G.ev_start, G.ev_packed);
+    G.ms[kMsLpLds] = ms_between(G.ev_packed, lds.ev_end);
+    G.ms[kMsTablesReset] = ms_between(G.ev_lps, G.ev_end);
+    if (n_glob > 0) G.ms[kMsLpGlobal] = ms_between(glob.ev_begin, glob.ev_end);
+    const uint32_t failed = G.h_counts[kCountFailed], lp_err = G.h_back->lp_err.code;
+    if (failed != 0xFFFFFFFFu || lp_err != 0u)
+        return fail_generate(e, FJSP_E_LP, failed != 0xFFFFFFFFu ? call + ": the fluid LP of " + who(seed_base, failed) + " failed"
+                                                                 : call + ": a fluid LP failed on the device (code " + std::to_string(lp_err) + ")");
+    G.stats[kStatInstances] = (int64_t)n_inst; G.stats[kStatLpLds] = G.h_counts[kCountFit]; G.stats[kStatLpHost] = n_host;
+    G.stats[kStatDevicePivots] = (int64_t)lds.h_solved->pivots;
+    if (glob.present()) {
+        G.stats[kStatLpGlobal] = n_glob; G.stats[kStatGlobalPivots] = (int64_t)glob.h_solved->pivots;
+        G.stats[kStatDevicePivots] += G.stats[kStatGlobalPivots];
     }
-    G.stats[0] = (int64_t)n_inst; G.stats[1] = n_fit; G.stats[2] = n_host; G.stats[3] = (int64_t)G.h_lp[1];
-    if (G.d_lp_solved_glob) { G.stats[4] = n_glob; G.stats[5] = (int64_t)G.h_lp[5]; G.stats[3] += G.stats[5]; }
     e->inst_hash = gen_hash(G.a, b.n_inst, seed_base);
     e->gen_failed = false;
-    G.ms[4] = ms_since(t_call);
+    G.ms[kMsTotal] = ms_since(t_call);
     return FJSP_OK;
 }
 
@@ -708,22 +691,27 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     G.a.kmax = sh.K; G.a.RP = sh.R;
     G.chunk = (int)std::min<size_t>(NI, 1024);
     G.head16 = (int)((b.L.i_x + 15) / 16);
-    if (!gen_dev_alloc(e.get(), NI * b.L.i_stride, &b.inst, "hipMalloc instance slab") ||
-        !gen_dev_alloc(e.get(), N * b.L.e_stride, &b.envs, "hipMalloc env slab") ||
-        !gen_dev_alloc(e.get(), N + 16, &e->d_done_scratch, "hipMalloc scratch") ||
-        !gen_dev_alloc(e.get(), NI * (size_t)sh.K * MP, &G.a.elig, "hipMalloc eligible lists") ||
-        !gen_dev_alloc(e.get(), NI * sizeof(GenInfo), &G.a.info, "hipMalloc generator status") ||
-        !gen_dev_alloc(e.get(), 32, &G.a.counts, "hipMalloc list lengths") ||
-        !gen_dev_alloc(e.get(), NI * 4, &G.a.fit_ids, "hipMalloc LP list") || !gen_dev_alloc(e.get(), NI * 4, &G.a.host_ids, "hipMalloc LP list") ||
-        !gen_dev_alloc(e.get(), NI * 2 * KP * 2, &G.a.lp_in, "hipMalloc LP inputs") ||
-        !gen_dev_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.d_stage, "hipMalloc LP solutions") ||
-        !gen_dev_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.d_stage_host, "hipMalloc LP solutions") ||
-        !gen_dev_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.d_head, "hipMalloc record heads") ||
-        !gen_dev_alloc(e.get(), 8, &G.d_lp_err, "hipMalloc LP error word") || !gen_dev_alloc(e.get(), 16, &G.d_lp_solved, "hipMalloc LP counters") ||
-        (b.grp && !gen_dev_alloc(e.get(), N, &G.d_kenv, "hipMalloc K table")) ||
-        !gen_host_alloc(e.get(), NI * sizeof(GenInfo), &G.h_info) || !gen_host_alloc(e.get(), 32, &G.h_counts) ||
-        !gen_host_alloc(e.get(), NI * 4, &G.h_host_ids) || !gen_host_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.h_stage) ||
-        !gen_host_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.h_head) || !gen_host_alloc(e.get(), 64, &G.h_lp))
+    const size_t stage = (size_t)G.chunk * KP * MP * 8, ids = NI * sizeof(uint32_t), lp_in = NI * 2 * KP * sizeof(uint16_t);
+    LpRoute &lds = G.route[kRouteLds], &glob = G.route[kRouteGlobal], &host = G.route[kRouteHost];
+    lds.producer = LpRoute::kLds; lds.length = kCountFit; lds.launch_error = "lp_device_kernel / generate_finish_kernel launch failed";
+    glob.producer = LpRoute::kGlobal; glob.length = kCountGlob; glob.launch_error = "lp_global_kernel / generate_finish_kernel launch failed";
+    host.producer = LpRoute::kHost; host.length = kCountHost; host.launch_error = "generate_finish_kernel launch failed";
+    if (!dev_alloc(e.get(), NI * b.L.i_stride, &b.inst, "hipMalloc instance slab") ||
+        !dev_alloc(e.get(), N * b.L.e_stride, &b.envs, "hipMalloc env slab") ||
+        !dev_alloc(e.get(), N + 16, &e->d_done_scratch, "hipMalloc scratch") ||
+        !dev_alloc(e.get(), NI * (size_t)sh.K * MP, &G.a.elig, "hipMalloc eligible lists") ||
+        !dev_alloc(e.get(), NI * sizeof(GenInfo), &G.a.info, "hipMalloc generator status") ||
+        !dev_alloc(e.get(), kGenCounts * sizeof(uint32_t), &G.a.counts, "hipMalloc list lengths") ||
+        !dev_alloc(e.get(), ids, &G.a.fit_ids, "hipMalloc LP list") || !dev_alloc(e.get(), ids, &G.a.host_ids, "hipMalloc LP list") ||
+        !dev_alloc(e.get(), lp_in, &G.a.lp_in, "hipMalloc LP inputs") ||
+        !dev_alloc(e.get(), stage, &lds.d_stage, "hipMalloc LP solutions") || !dev_alloc(e.get(), stage, &host.d_stage, "hipMalloc LP solutions") ||
+        !dev_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.d_head, "hipMalloc record heads") ||
+        !dev_alloc(e.get(), sizeof(LpErrWord), &G.d_lp_err, "hipMalloc LP error word") ||
+        !dev_alloc(e.get(), sizeof(LpCounters), &lds.d_solved, "hipMalloc LP counters") ||
+        (b.grp && !dev_alloc(e.get(), N, &G.d_kenv, "hipMalloc K table")) ||
+        !host_alloc(e.get(), NI * sizeof(GenInfo), &G.h_info) || !host_alloc(e.get(), kGenCounts * sizeof(uint32_t), &G.h_counts) ||
+        !host_alloc(e.get(), ids, &G.h_host_ids) || !host_alloc(e.get(), stage, &G.h_stage) ||
+        !host_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.h_head) || !host_alloc(e.get(), sizeof(GenReadback), &G.h_back))
         return FJSP_E_HIP;
     if (G.a.allow_global) {
         // the scratch pool of the global-memory simplex, sized for the largest tableau the parameters admit within its limits:
@@ -733,16 +721,20 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         G.pool.slot_bytes = lp_global_slot_bytes(nr_cap, nc_cap);
         G.pool.slots = lp_global_slots((size_t)G.chunk, G.pool.slot_bytes);
         G.pool.lds = lp_global_lds(sh.K, sh.M, (int)MP, nr_cap, nc_cap);
-        if (!gen_dev_alloc(e.get(), (size_t)G.pool.slots * G.pool.slot_bytes, &G.pool.mem, "hipMalloc LP tableau pool") ||
-            !gen_dev_alloc(e.get(), NI * 4, &G.a.glob_ids, "hipMalloc LP list") || !gen_dev_alloc(e.get(), NI * 2 * KP * 2, &G.a.lp_in_glob, "hipMalloc LP inputs") ||
-            !gen_dev_alloc(e.get(), (size_t)G.chunk * KP * MP * 8, &G.d_stage_glob, "hipMalloc LP solutions") ||
-            !gen_dev_alloc(e.get(), 16, &G.d_lp_solved_glob, "hipMalloc LP counters"))
+        if (!dev_alloc(e.get(), (size_t)G.pool.slots * G.pool.slot_bytes, &G.pool.mem, "hipMalloc LP tableau pool") ||
+            !dev_alloc(e.get(), ids, &G.a.glob_ids, "hipMalloc LP list") || !dev_alloc(e.get(), lp_in, &G.a.lp_in_glob, "hipMalloc LP inputs") ||
+            !dev_alloc(e.get(), stage, &glob.d_stage, "hipMalloc LP solutions") ||
+            !dev_alloc(e.get(), sizeof(LpCounters), &glob.d_solved, "hipMalloc LP counters"))
             return FJSP_E_HIP;
+        for (hipEvent_t *ev : {&glob.ev_begin, &glob.ev_end}) HIP_TRY(hipEventCreate(ev));
     }
     b.kenv = G.d_kenv;
-    for (hipEvent_t &ev : G.ev) HIP_TRY(hipEventCreate(&ev));
+    for (hipEvent_t *ev : {&G.ev_start, &G.ev_packed, &G.ev_end, &G.ev_joined, &lds.ev_end}) HIP_TRY(hipEventCreate(ev));
     HIP_TRY(hipStreamCreateWithFlags(&G.st_dev, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&G.st_host, hipStreamNonBlocking));
+    lds.ids = G.a.fit_ids; lds.lp_in = G.a.lp_in; lds.h_solved = &G.h_back->lds; lds.st = G.st_dev;
+    glob.ids = G.a.glob_ids; glob.lp_in = G.a.lp_in_glob; glob.h_solved = &G.h_back->glob; glob.st = G.st_host;
+    host.ids = G.a.host_ids; host.st = G.st_host;
     if ((rc = regenerate(e.get(), seed_base, rng_seed, call)) != FJSP_OK) return rc;
     *out = e.release();
     return FJSP_OK;
@@ -771,28 +763,17 @@ int fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed) {
     return regenerate(e, seed_base, rng_seed, "fjsp_env_regenerate");
 }
 
-int fjsp_env_generated_stats(const fjsp_env *e, int64_t out[4]) {
-    if (!e || !out) { set_error("fjsp_env_generated_stats: null argument"); return FJSP_E_ARG; }
-    if (!e->gen) { set_error("fjsp_env_generated_stats: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
-    for (int q = 0; q < 4; ++q) out[q] = e->gen->stats[q];
+// The three accessors hand out prefixes of GenState::stats and ::ms; `given`: the caller passed the array the call is about
+static int copy_stats(const fjsp_env *e, const std::string &fn, bool given, int64_t *out, int n_out, double *out_ms, int n_ms) {
+    if (!e || !given) { set_error(fn + ": null argument"); return FJSP_E_ARG; }
+    if (!e->gen) { set_error(fn + ": the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    if (out) std::copy(e->gen->stats, e->gen->stats + n_out, out);
+    if (out_ms) std::copy(e->gen->ms, e->gen->ms + n_ms, out_ms);
     return FJSP_OK;
 }
-
-int fjsp_env_generated_stats2(const fjsp_env *e, int64_t out[6], double out_ms[6]) {
-    if (!e || !out) { set_error("fjsp_env_generated_stats2: null argument"); return FJSP_E_ARG; }
-    if (!e->gen) { set_error("fjsp_env_generated_stats2: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
-    for (int q = 0; q < 6; ++q) out[q] = e->gen->stats[q];
-    if (out_ms)
-        for (int q = 0; q < 6; ++q) out_ms[q] = e->gen->ms[q];
-    return FJSP_OK;
-}
-
-int fjsp_env_generated_times(const fjsp_env *e, double out_ms[5]) {
-    if (!e || !out_ms) { set_error("fjsp_env_generated_times: null argument"); return FJSP_E_ARG; }
-    if (!e->gen) { set_error("fjsp_env_generated_times: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
-    for (int q = 0; q < 5; ++q) out_ms[q] = e->gen->ms[q];
-    return FJSP_OK;
-}
+int fjsp_env_generated_stats(const fjsp_env *e, int64_t out[4]) { return copy_stats(e, "fjsp_env_generated_stats", out, out, kStatDevicePivots + 1, nullptr, 0); }
+int fjsp_env_generated_stats2(const fjsp_env *e, int64_t out[6], double out_ms[6]) { return copy_stats(e, "fjsp_env_generated_stats2", out, out, kGenStats, out_ms, kGenTimes); }
+int fjsp_env_generated_times(const fjsp_env *e, double out_ms[5]) { return copy_stats(e, "fjsp_env_generated_times", out_ms, nullptr, 0, out_ms, kMsTotal + 1); }
 
 int fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr, int32_t *p, int32_t *elig_n, int32_t *elig_list,
                            int32_t *count, int32_t *arrive, int32_t *delivery, double *ddt, double *x) {
@@ -809,22 +790,18 @@ int fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr,
     HIP_TRY(hipMemcpy(rec.data(), b.inst + (size_t)i * b.L.i_stride, rec.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(el.data(), G.a.elig + (size_t)i * el.size(), el.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&f, G.a.info + i, sizeof(f), hipMemcpyDeviceToHost));
-    const InstHeader h = *reinterpret_cast<const InstHeader *>(rec.data());
-    const uint32_t *kA = reinterpret_cast<const uint32_t *>(rec.data() + b.L.i_kA), *kB = reinterpret_cast<const uint32_t *>(rec.data() + b.L.i_kB);
+    RecordHead in;
+    decode_head(b, rec.data(), in);
+    const InstHeader &h = in.h;
     const uint32_t *em = reinterpret_cast<const uint32_t *>(rec.data() + b.L.i_elig);
-    const uint16_t *p16 = reinterpret_cast<const uint16_t *>(rec.data() + b.L.i_p);
     const double *xr = reinterpret_cast<const double *>(rec.data() + b.L.i_x);
     if (dims) { dims[0] = h.R; dims[1] = h.M; dims[2] = h.K; dims[3] = 1; dims[4] = h.njobs; dims[5] = h.njobs; }
-    int r = -1;
+    if (Jr) std::copy(in.Jr.begin(), in.Jr.end(), Jr);
+    if (count) std::copy(in.count.begin(), in.count.end(), count);
+    if (p) std::copy(in.p.begin(), in.p.end(), p);
     for (int k = 0; k < h.K; ++k) {
-        if ((kB[k] & 0xFFu) == 0u) {
-            ++r;
-            if (Jr) Jr[r] = (int32_t)((kB[k] >> 8) & 0xFFu);
-            if (count) count[r] = (int32_t)(kA[k] >> 16);
-        }
         if (elig_n) elig_n[k] = __builtin_popcount(em[k]);
         for (int m = 0; m < h.M; ++m) {
-            if (p) p[(size_t)k * h.M + m] = p16[(size_t)k * MP + m];
             if (elig_list) elig_list[(size_t)k * h.M + m] = el[(size_t)k * MP + m];
             if (x) x[(size_t)k * h.M + m] = xr[(size_t)k * MP + m];
         }

@@ -4,15 +4,14 @@
 //   - fluid LP driver        <- environments/class_FJSSP.py:246-280 (see fjsp_lp.cpp)
 #include "../../include/fjsp_amd.h"
 #include "fjsp_host.h"
+#include "fjsp_lp_pool.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <sstream>
-#include <thread>
 
 namespace fjsp {
 
@@ -470,27 +469,9 @@ int fjsp_instances_solve_fluid(fjsp_instances *s, int32_t first, int32_t n, int3
     if (!s || first < 0 || n <= 0 || (size_t)first + (size_t)n > s->v.size()) { set_error("solve_fluid: range"); return FJSP_E_ARG; }
     for (int i = first; i < first + n; ++i)
         if (!s->v[(size_t)i].valid) { set_error("solve_fluid: instance not populated"); return FJSP_E_STATE; }
-    if (n_threads <= 0) n_threads = (int)std::thread::hardware_concurrency();
-    if (n_threads <= 0) n_threads = 1;
-    if (n_threads > n) n_threads = n;
-    std::atomic<int> next(first), fail(0);
-    std::string err;
-    auto work = [&]() {
-        for (;;) {
-            int i = next.fetch_add(1);
-            if (i >= first + n) break;
-            if (solve_order0(s->v[(size_t)i]) != FJSP_OK) {
-                if (fail.fetch_add(1) == 0) err = g_err;  // thread-local message of the worker
-            }
-        }
-    };
-    if (n_threads == 1) work();
-    else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < n_threads; ++t) th.emplace_back(work);
-        for (auto &t : th) t.join();
-    }
-    if (fail.load()) { set_error(err.empty() ? "fluid LP failed" : err); return FJSP_E_LP; }
+    LpPool pool(std::min(lp_thread_count(n_threads, 1 << 30), n) - 1);     // of its own, for this call: every core unless n_threads says otherwise, the caller counted
+    const LpFailure bad = pool.run((uint32_t)n, [&](uint32_t q) { return solve_order0(s->v[(size_t)first + q]) == FJSP_OK; });
+    if (bad) { set_error(bad.msg.empty() ? "fluid LP failed" : bad.msg); return FJSP_E_LP; }
     return FJSP_OK;
 }
 

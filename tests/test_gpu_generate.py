@@ -178,6 +178,50 @@ def test_two_chunks_every_lp_on_the_host(torch_gpu):
     assert n_fit == 0 and st["lp_host"] == 8 and st["device_pivots"] == 0
 
 
+CHUNK_N = 1030                                            # one full chunk of 1024 staging slots and a second one of 6
+CHUNK_ENVS = (0, 1, 1022, 1023, 1024, 1025, 1029)         # either side of the boundary: where an offset error would land
+CHUNK_ROUTES = {                                          # route: (FJSP_LP_IMPL, parameters, seed base, the list all go on)
+    "host": ("host", bench, 7, "lp_host"),
+    "lds": (None, lambda: gp(R_min=3, R_max=5, J_min=2, J_max=3, M=6, N_min=2, N_max=4), 40, "lp_device"),
+    "global": ("global", lambda: gp(R_min=16, R_max=20, J_min=4, J_max=5, M=3), 40, "lp_global"),
+}
+
+
+@pytest.mark.parametrize("route", sorted(CHUNK_ROUTES))
+def test_second_chunk_of_staging_slots(torch_gpu, route):
+    """1030 instances, all on one LP list: the second round of that list's chunk loop, with its offsets into the ids,
+    the LP inputs and the staging slots.  Reference: the host solver on the same seeds (for the host route the host
+    path's instance set).  The bench() case runs the row kernels; the other two parameter sets have several jobs per
+    kind / more than 64 operation types and so run the wave kernels.  The episode has as many steps as the largest
+    instance the parameters admit (R_max x J_max x N_max >= ops_of): no pass over all 1030 instances."""
+    from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch
+    impl, make, seed, key = CHUNK_ROUTES[route]
+    prm = make()
+    with H.env_var("FJSP_LP_IMPL", impl):
+        G = EnvBatch.generated(prm, CHUNK_N, seed, rng_seed=5)
+    if route == "host":
+        assert G.kernel_family == 1
+        Hb = EnvBatch(host_set(prm, CHUNK_N, seed), CHUNK_N, rng_seed=5)
+        ref = Hb.instances.arrays
+    else:
+        with H.env_var("FJSP_LP_IMPL", "host"):
+            Hb = EnvBatch.generated(prm, CHUNK_N, seed, rng_seed=5)
+        assert Hb.generated_stats()["lp_host"] == CHUNK_N
+        ref = Hb.instance_arrays
+    st = G.generated_stats()
+    assert st["instances"] == CHUNK_N and st[key] == CHUNK_N, st
+    assert st["lp_device"] + st["lp_host"] + st["lp_global"] == CHUNK_N, st
+    for i in CHUNK_ENVS:
+        a = G.instance_arrays(i)
+        same_instance(a, ref(i), "%s instance %d" % (route, i))
+        assert route == "host" or tableau_fits(a) == (route == "lds"), i
+        H.same(G.fluid_tables(i), Hb.fluid_tables(i), "%s fluid tables of env %d" % (route, i))
+    T = prm.R_max * prm.J_max * prm.N_max
+    eg = episode(torch_gpu, G, T)
+    assert np.all(eg[1]["done"] == 1), route
+    same_episode(eg, episode(torch_gpu, Hb, T), what=route)
+
+
 def test_degenerate_instance(torch_gpu):
     G, Hb = pair(gp(R_min=1, R_max=1, J_min=1, J_max=1, M=1, p_max=1), 4, 40)
     a = G.instance_arrays(0)
