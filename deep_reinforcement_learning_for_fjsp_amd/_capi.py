@@ -37,6 +37,12 @@ class GenRanges(C.Structure):
     _fields_ = [("base", GenParams), ("M_min", _i32), ("M_max", _i32), ("DDT_min", _dbl), ("DDT_max", _dbl)]
 
 
+class GenOrders(C.Structure):
+    """fjsp_gen_orders: GenOrders(r, S_min, S_max) -- a GenRanges and the number of orders, drawn per instance as well
+    (r.base.S is not read)."""
+    _fields_ = [("r", GenRanges), ("S_min", _i32), ("S_max", _i32)]
+
+
 class ActorParams(C.Structure):
     """fjsp_actor_params: device pointers to the f32 parameters of a state_size -> 128 -> 128 -> n_actions actor."""
     _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w3", _vp), ("b3", _vp),
@@ -53,6 +59,8 @@ SIGNATURES = {
     "fjsp_instances_generate": (C.c_int, [_vp, _i32, _u64, C.POINTER(GenParams)]),
     "fjsp_gen_draw": (C.c_int, [C.POINTER(GenRanges), _u64, C.POINTER(GenParams)]),
     "fjsp_instances_generate_drawn": (C.c_int, [_vp, _i32, _u64, C.POINTER(GenRanges)]),
+    "fjsp_gen_draw_orders": (C.c_int, [C.POINTER(GenOrders), _u64, C.POINTER(GenParams)]),
+    "fjsp_instances_generate_orders": (C.c_int, [_vp, _i32, _u64, C.POINTER(GenOrders)]),
     "fjsp_instances_set_raw": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl]),
     "fjsp_instances_dims": (C.c_int, [_vp, _i32, C.POINTER(_i32 * 6)]),
     "fjsp_instances_get": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_dbl), _vp]),
@@ -66,6 +74,7 @@ SIGNATURES = {
     "fjsp_env_create_family": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _u64, _i32, _pp]),
     "fjsp_env_create_generated": (C.c_int, [C.POINTER(GenParams), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
     "fjsp_env_create_generated_ranges": (C.c_int, [C.POINTER(GenRanges), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
+    "fjsp_env_create_generated_orders": (C.c_int, [C.POINTER(GenOrders), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
     "fjsp_env_regenerate": (C.c_int, [_vp, _u64, _u64]),
     "fjsp_env_generated_stats": (C.c_int, [_vp, C.POINTER(_i64 * 4)]),
     "fjsp_env_generated_times": (C.c_int, [_vp, C.POINTER(_dbl * 5)]),

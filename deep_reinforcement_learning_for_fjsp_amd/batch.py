@@ -215,11 +215,13 @@ class EnvBatch(object):
                   family=-1):
         """A batch whose instances are generated and solved on the device (fjsp_env_create_generated): env q plays
         instance q % n_inst = what InstanceSet.generate_range(seed_base, params) + solve_fluid() make of seed
-        seed_base + first_env + q % n_inst.  params: GenParams, or GenRanges (fjsp_env_create_generated_ranges: every
-        instance draws its own machine count and due-date tightness; the batch is sized for M_max).  first_env shifts the instance seeds and the env random streams alike, so a
+        seed_base + first_env + q % n_inst.  params: GenParams, GenRanges (fjsp_env_create_generated_ranges: every
+        instance draws its own machine count and due-date tightness; the batch is sized for M_max) or GenOrders
+        (fjsp_env_create_generated_orders: its number of orders too; with S_max > 1 the batch plays order arrivals, their
+        LPs served as lp_on_device says).  first_env shifts the instance seeds and the env random streams alike, so a
         shard [first_env, first_env + n_envs) is a slice of the one-GPU batch.  There is no InstanceSet (`instances` is
-        None; instance_arrays(i) reads an instance back); regenerate() refills the batch in place.  One order only
-        (params.S == 1), not VARIANT_MO_DFJSP: FjspError(FJSP_E_UNSUPPORTED)."""
+        None; instance_arrays(i) reads an instance back); regenerate() refills the batch in place.  Several orders only
+        through GenOrders, and then VARIANT_SO_FJSSP / VARIANT_SO_DFJSP; never VARIANT_MO_DFJSP: FjspError(FJSP_E_UNSUPPORTED)."""
         if not torch.cuda.is_available():
             raise RuntimeError("EnvBatch needs an MI355X: the environment kernels have no CPU path")
         if family not in (-1, 0, 1):
@@ -235,7 +237,8 @@ class EnvBatch(object):
         self.first_env, self.first = int(first_env), 0
         self.gen_params, self.seed_base, self.family = params, int(seed_base), int(family)
         mask = 2 ** 64 - 1
-        create = self._lib.fjsp_env_create_generated_ranges if isinstance(params, _capi.GenRanges) else self._lib.fjsp_env_create_generated
+        create = (self._lib.fjsp_env_create_generated_orders if isinstance(params, _capi.GenOrders) else
+                  self._lib.fjsp_env_create_generated_ranges if isinstance(params, _capi.GenRanges) else self._lib.fjsp_env_create_generated)
         check(create(C.byref(params), n_inst, int(n_envs), int(variant), self.device_index,
                      (int(rng_seed) + self.first_env * ENV_SEED_STRIDE) & mask, int(family),
                      (self.seed_base + self.first_env) & mask, C.byref(self._h)))
@@ -610,7 +613,8 @@ class EnvBatch(object):
 
     def machine_time_end(self):
         if self.instances is None:
-            mp = int(self.gen_params.M_max if isinstance(self.gen_params, _capi.GenRanges) else self.gen_params.M)
+            g = self.gen_params
+            mp = int(g.r.M_max if isinstance(g, _capi.GenOrders) else g.M_max if isinstance(g, _capi.GenRanges) else g.M)
         else:
             d = self.instances.dims(self.first)
             mp = max(self.instances.dims(self.first + i)["M"] for i in range(self.n_inst)) if self.n_inst > 1 else d["M"]

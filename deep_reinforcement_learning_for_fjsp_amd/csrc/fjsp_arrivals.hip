@@ -151,14 +151,14 @@ namespace {
 bool solve_parked_lp(fjsp_env *e, int env, const uint16_t *lpq, double *x_slot) {
     const DevBatch &b = e->b;
     const size_t KP = (size_t)b.KP, MP = (size_t)b.MP;
-    const Instance &in = e->src->v[(size_t)e->first + (size_t)(env % b.n_inst)];
+    const LpShape in = lp_shape_of(e, env % b.n_inst);
     std::vector<int> Q(in.K), now(in.K);
     for (int k = 0; k < in.K; ++k) { Q[k] = lpq[(size_t)k]; now[k] = lpq[KP + (size_t)k]; }
     std::vector<double> xk((size_t)in.K * in.M, 0.0);
     double obj = 0.0;
     const std::string ck = LpCache::key(env % b.n_inst, lpq, KP, in.K);
     if (!e->arr.cache->find(ck, xk)) {
-        if (solve_fluid_lp(in.R, in.M, in.Jr.data(), in.p.data(), Q.data(), now.data(), xk.data(), &obj) != 0) return false;
+        if (solve_fluid_lp(in.R, in.M, in.Jr, in.p, Q.data(), now.data(), xk.data(), &obj) != 0) return false;
         e->arr.cache->put(ck, xk);
     }
     std::fill(x_slot, x_slot + KP * MP, 0.0);
@@ -237,6 +237,9 @@ int async_reserve(fjsp_env *e, AsyncBatch &a, uint32_t need) {
 // Builds the asynchronous service of the handle at its first call, completely or not at all (e->arr.ring stays nullptr).
 int async_setup(fjsp_env *e) {
     if (e->arr.ring) return FJSP_OK;
+    // a generated handle whose blocking service runs on the device has not gathered its records' heads yet
+    if (e->gen && e->lp_mirror.empty())
+        if (const int rc = refresh_lp_mirror(e)) return rc;
     const DevBatch &b = e->b;
     const size_t N = (size_t)b.N, KP = (size_t)b.KP, MP = (size_t)b.MP;
     std::unique_ptr<AsyncRing> r(new AsyncRing());
@@ -390,6 +393,13 @@ bool async_idle(const fjsp_env *e) {
 }
 
 void arrivals_release(ArrivalService &a) { delete a.ring; delete a.pool; delete a.cache; }
+
+void arrivals_forget(ArrivalService &a) {
+    if (!a.cache) return;
+    std::lock_guard<std::mutex> g(a.cache->mu);      // (the asynchronous workers are idle: the caller checked async_idle)
+    a.cache->map.clear();
+    a.cache->bytes = 0;
+}
 }  // namespace fjsp
 
 using namespace fjsp;
@@ -475,9 +485,10 @@ int fjsp_env_lp_device_solve(fjsp_env *e, int32_t env, const int32_t *Q, const i
     if (!A.lp_device) { set_error("fjsp_env_lp_device_solve: this batch keeps the host LP service"); return FJSP_E_UNSUPPORTED; }
     DeviceGuard guard(e->device);
     const DevBatch &b = e->b;
-    const Instance &in = e->src->v[(size_t)e->first + (size_t)(env % b.n_inst)];
+    // (the sizes alone: every handle keeps them per instance, a generated one with no host mirror of its records too)
+    const int K = e->inst_K[(size_t)(env % b.n_inst)], M = e->inst_M[(size_t)(env % b.n_inst)];
     std::vector<uint16_t> lpq((size_t)2 * b.KP, 0);
-    for (int k = 0; k < in.K; ++k) {          // the staging arrays hold 16-bit counts (a batch has at most 65535 jobs)
+    for (int k = 0; k < K; ++k) {          // the staging arrays hold 16-bit counts (a batch has at most 65535 jobs)
         if (Q[k] < 0 || Q[k] > 65535 || n_now[k] < 0 || n_now[k] > 65535) {
             set_error("fjsp_env_lp_device_solve: Q[k] and n_now[k] must lie in 0 ... 65535"); return FJSP_E_ARG;
         }
@@ -497,8 +508,8 @@ int fjsp_env_lp_device_solve(fjsp_env *e, int32_t env, const int32_t *Q, const i
     if (err) { const uint32_t z = 0; (void)hipMemcpy(A.d_lp_err, &z, 4, hipMemcpyHostToDevice); set_error("fluid LP failed on the device (code " + std::to_string(err) + ")"); return FJSP_E_LP; }
     std::vector<double> xs((size_t)b.KP * b.MP);
     HIP_TRY(hipMemcpy(xs.data(), b.lp_x, xs.size() * 8, hipMemcpyDeviceToHost));
-    for (int k = 0; k < in.K; ++k)
-        for (int m = 0; m < in.M; ++m) x[(size_t)k * in.M + m] = xs[(size_t)k * b.MP + m];
+    for (int k = 0; k < K; ++k)
+        for (int m = 0; m < M; ++m) x[(size_t)k * M + m] = xs[(size_t)k * b.MP + m];
     return FJSP_OK;
 }
 

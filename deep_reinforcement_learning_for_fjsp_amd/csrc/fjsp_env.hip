@@ -332,27 +332,28 @@ double step_bytes_of(const Instance &in, const DevBatch &b) {
     return bytes;
 }
 
-// Stage 6 (multi-order batches): the LPs of order arrivals on the device when every tableau this batch can meet fits the LDS
-// of a CU.  Which service: one LP takes the device ~0.3 ms (a 48-pivot tableau of the industrial instances; a host core
+}  // namespace
+
+namespace fjsp {
+// Stage 6 (multi-order batches): the LPs of order arrivals on the device when every tableau this batch can meet
+// (t[0, n): its instances', or the one worst case of a generated handle's parameters) fits the LDS of a CU.  Which service: one LP takes the device ~0.3 ms (a 48-pivot tableau of the industrial instances; a host core
 // needs ~0.05 ms) but 256 of them run at once, so the device wins when arrivals come in bursts of hundreds -- measured
 // (tools/bench_dynamic.py --instances industrial): 4096 envs 32.0 M env-steps/s against the host service's 34.9 M, 32768
 // envs 63.1 M against 54.2 M.  Default: the device from 16384 environments on; FJSP_LP_IMPL=device / host decides for
 // itself (A/B runs, and the parity test of the two).  FJSP_LP_IMPL=global (opt-in, not measured into a default yet): as device
 // when every tableau fits the LDS rule; else, when every tableau is within 256 rows x 1536 columns, the same service with the
 // simplex whose tableau lives in a scratch pool in global memory (fjsp_lp_global.hip); else the host.
-void choose_lp_service(fjsp_env *e) {
+void choose_lp_service(fjsp_env *e, const LpTableau *t, int n) {
     const DevBatch &b = e->b;
     size_t lds_max = 0, slot_max = 0;
     int K_max = 0, nr_max = 0, nc_max = 0;
     bool in_global = true;
-    for (int i = 0; i < b.n_inst; ++i) {
-        const Instance &in = e->src->v[(size_t)e->first + i];
-        int nx = 0;
-        for (int v : in.p) nx += v > 0 ? 1 : 0;
-        const int nr = lp_max_rows(in.K, in.M, in.R), nc = lp_max_columns(in.K, in.M, nx, in.R);
-        lds_max = std::max(lds_max, (size_t)lp_device_lds_bytes(in.K, in.M, nx, in.R, b.MP));
+    for (int i = 0; i < n; ++i) {
+        const LpTableau &in = t[i];
+        const int nr = lp_max_rows(in.K, in.M, in.R), nc = lp_max_columns(in.K, in.M, in.nx, in.R);
+        lds_max = std::max(lds_max, (size_t)lp_device_lds_bytes(in.K, in.M, in.nx, in.R, b.MP));
         if (nc > kLpLdsColumns) lds_max = (size_t)1 << 30;
-        const size_t slot = (size_t)fjsp_lp_global_bytes(in.K, in.M, nx, in.R);
+        const size_t slot = (size_t)fjsp_lp_global_bytes(in.K, in.M, in.nx, in.R);
         in_global = in_global && slot > 0;
         slot_max = std::max(slot_max, slot);
         K_max = std::max(K_max, in.K);
@@ -367,19 +368,15 @@ void choose_lp_service(fjsp_env *e) {
         P.slot_bytes = slot_max;
         P.slots = lp_global_slots((size_t)b.N, slot_max);
         P.lds = lp_global_lds(K_max, b.MP, b.MP, nr_max, nc_max);
-        e->arr.lp_device = e->arr.lp_global = true;        // (the pool itself: upload_batch)
+        e->arr.lp_device = e->arr.lp_global = true;        // (the pool itself: alloc_arrival_staging)
     }
 }
 
-// Stage 7: every allocation of the batch, the two slabs uploaded, then the first launches
-int upload_batch(fjsp_env *e, const std::vector<unsigned char> &islab) {
+// Staging of the LP services, one slot per env (worst case: every env parks in the same launch)
+int alloc_arrival_staging(fjsp_env *e) {
     DevBatch &b = e->b;
     ArrivalService &A = e->arr;
     const size_t N = (size_t)b.N, KP = (size_t)b.KP, MP = (size_t)b.MP;
-    if (!dev_alloc(e, islab.size(), &b.inst, "hipMalloc instance slab") || !dev_alloc(e, N * b.L.e_stride, &b.envs, "hipMalloc env slab") ||
-        !dev_alloc(e, N + 16, &e->d_done_scratch, "hipMalloc scratch"))
-        return FJSP_E_HIP;
-    // staging of the LP services, one slot per env (worst case: every env parks in the same launch)
     if (b.mord && (!dev_alloc(e, (N + 1) * 4, &b.pending_count, "hipMalloc pending list") ||
                    !dev_alloc(e, N * 2 * KP * 2, &b.lp_in, "hipMalloc LP inputs") || !dev_alloc(e, N * KP * MP * 8, &b.lp_x, "hipMalloc LP solutions") ||
                    !host_alloc(e, (N + 1) * 4, &A.h_pending) || !host_alloc(e, N * 2 * KP * 2, &A.h_lp_in) ||
@@ -388,6 +385,19 @@ int upload_batch(fjsp_env *e, const std::vector<unsigned char> &islab) {
     if (A.lp_global && !dev_alloc(e, (size_t)A.lp_pool.slots * A.lp_pool.slot_bytes, &A.lp_pool.mem, "hipMalloc LP tableau pool")) return FJSP_E_HIP;
     if (A.lp_device && (!dev_alloc(e, 8, &A.d_lp_err, "hipMalloc LP error word") || !dev_alloc(e, 16, &A.d_lp_solved, "hipMalloc LP counters")))
         return FJSP_E_HIP;
+    return FJSP_OK;
+}
+}  // namespace fjsp
+
+namespace {
+// Stage 7: every allocation of the batch, the two slabs uploaded, then the first launches
+int upload_batch(fjsp_env *e, const std::vector<unsigned char> &islab) {
+    DevBatch &b = e->b;
+    const size_t N = (size_t)b.N;
+    if (!dev_alloc(e, islab.size(), &b.inst, "hipMalloc instance slab") || !dev_alloc(e, N * b.L.e_stride, &b.envs, "hipMalloc env slab") ||
+        !dev_alloc(e, N + 16, &e->d_done_scratch, "hipMalloc scratch"))
+        return FJSP_E_HIP;
+    if (const int rc = alloc_arrival_staging(e)) return rc;
     if (b.grp) {       // operation types of every environment's instance (fjsp_group.hip: large-batch kernels)
         std::vector<uint8_t> kq(N);
         for (size_t q = 0; q < N; ++q) kq[q] = (uint8_t)e->inst_K[q % (size_t)b.n_inst];
@@ -491,7 +501,16 @@ int fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_ins
     for (unsigned char c : islab) h = (h ^ c) * 1099511628211ULL;
     e->inst_hash = h;
 
-    if (b.mord) choose_lp_service(e.get());
+    if (b.mord) {
+        std::vector<LpTableau> t;
+        for (int i = 0; i < n_inst; ++i) {
+            const Instance &in = s->v[(size_t)first + i];
+            int nx = 0;
+            for (int v : in.p) nx += v > 0 ? 1 : 0;
+            t.push_back(LpTableau{in.K, in.M, nx, in.R});
+        }
+        choose_lp_service(e.get(), t.data(), n_inst);
+    }
     if ((rc = upload_batch(e.get(), islab)) != FJSP_OK) return rc;
     *out = e.release();
     return FJSP_OK;

@@ -11,6 +11,7 @@
 #include "../../include/fjsp_amd.h"
 #include "fjsp_device.h"
 #include "fjsp_host.h"
+#include "fjsp_lp_limits.h"
 
 namespace fjsp {
 struct LpCache; struct AsyncRing; struct LpPool;   // fjsp_arrivals.hip; fjsp_lp_pool.h
@@ -44,6 +45,13 @@ struct ArrivalService {
     uint32_t *d_lp_err = nullptr;                // [0] nonzero: an LP failed on the device (reported at the next synchronising call)
     unsigned long long *d_lp_solved = nullptr;   // LPs solved on the device so far, [1] their pivots
 };
+
+// The LP shape of one instance of a batch, what a host arrival LP reads of it (lp_shape_of below): the host Instance's arrays,
+// or on a generated handle those of its mirror
+struct LpShape { int R = 0, M = 0, K = 0; const int *Jr = nullptr, *p = nullptr; };   // Jr[R]; p[K][M] unpadded
+// The head of a packed record (pack_instance, generate_pack_kernel) back on the host: of a generated handle's host LP route,
+// and the entries of fjsp_env::lp_mirror
+struct RecordHead { InstHeader h{}; std::vector<int> Jr, count, p; };      // h.R without the order count; [R], [R] jobs of every kind in order 0, [K][M] unpadded
 }  // namespace fjsp
 
 struct fjsp_env {
@@ -61,9 +69,10 @@ struct fjsp_env {
     int first = 0;
     bool failed = false;        // the arrival service failed mid-step: parked envs are in limbo, the handle refuses further steps
     fjsp::ArrivalService arr;
-    // handles of fjsp_env_create_generated only (fjsp_generate.hip): the device generator's buffers and parameters.  Such a
-    // handle has no host instance set (src == nullptr) and never a multi-order batch, the only reader of src.
+    // handles of fjsp_env_create_generated* only (fjsp_generate.hip): the device generator's buffers and parameters.  Such a
+    // handle has no host instance set (src == nullptr); a multi-order one keeps lp_mirror for its host arrival LPs.
     fjsp::GenState *gen = nullptr;
+    std::vector<fjsp::RecordHead> lp_mirror;   // [n_inst] the records' heads as of the last regenerate; empty: not gathered (refresh_lp_mirror)
     bool gen_failed = false;    // the last fjsp_env_regenerate failed: reset / step / rollout are refused until one succeeds
 };
 
@@ -136,4 +145,21 @@ int plan_launch(DevBatch &b, LaunchPlan &p, const Shape &sh, int family);
 int plan_layout(DevBatch &b, const Shape &sh);
 void generated_release(fjsp_env *e);        // fjsp_generate.hip: frees e->gen (its device memory is in e->dev_allocs)
 void arrivals_release(ArrivalService &a);   // joins the LP threads first; on the handle's device
+void arrivals_forget(ArrivalService &a);    // empties the memo of solved arrival LPs: the instance indices in its keys name other instances now
+// fjsp_env.hip, stage 6 of a create of a multi-order batch: which arrival service, from the n tableaus the batch can meet;
+// alloc_arrival_staging: the staging and pools of that service (device memory and pinned mirrors, owned by the handle)
+void choose_lp_service(fjsp_env *e, const LpTableau *t, int n);
+int alloc_arrival_staging(fjsp_env *e);
+// fjsp_generate.hip: a generated multi-order handle's lp_mirror from its records (one gather, synchronises)
+int refresh_lp_mirror(fjsp_env *e);
+
+// The LP shape of instance i of the batch: one source for every host reader
+inline LpShape lp_shape_of(const fjsp_env *e, int i) {
+    if (e->src) {
+        const Instance &in = e->src->v[(size_t)e->first + (size_t)i];
+        return LpShape{in.R, in.M, in.K, in.Jr.data(), in.p.data()};
+    }
+    const RecordHead &m = e->lp_mirror[(size_t)i];
+    return LpShape{m.h.R, m.h.M, m.h.K, m.Jr.data(), m.p.data()};
+}
 }  // namespace fjsp

@@ -19,6 +19,12 @@
 // where the next type's draws start, K dependent hashes -- and the lanes then run their own operation types' shuffles and
 // processing times from those offsets, and write the record's rows side by side.  (One lane per instance would leave the
 // per-type machine lists in scratch memory and the record writes uncoalesced.)
+//
+// Several orders (fjsp_env_create_generated_orders): the S x R job counts and the S - 1 arrival intervals follow the
+// processing times in the stream; lane s computes order s's gap and arrival time, lane 0 sorts the at most
+// FJSP_GEN_MAX_ORDERS delivery times.  The handle is then a multi-order one: its arrival service (fjsp_arrivals.hip) is
+// chosen at create from the parameters' worst tableau and, where it runs on the host, reads fjsp_env::lp_mirror, the
+// records' heads that refresh_lp_mirror gathers after every refill.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,9 +48,9 @@ struct GenInfo {
     int32_t K, R, nj;    // operation types, kinds, jobs
     int32_t nx;          // eligible (operation type, machine) pairs
     int32_t lds;         // LDS bytes of the order-0 tableau (lp_device_lds_bytes, fjsp_lp_limits.h)
-    int32_t ops;         // operations (schedule slots)
-    int32_t delivery;    // delivery time of the order
-    int32_t M, pad;      // machines of the instance (its own draw on a ranges handle)
+    int32_t ops;         // operations (schedule slots), of all orders as nj
+    int32_t delivery;    // delivery time of the first order due (every order's: GenArgs::deliv)
+    int32_t M, S;        // machines and orders of the instance (its own draws on a ranges / orders handle)
     double ddt;          // its due-date tightness
 };
 static_assert(sizeof(GenInfo) == 48, "GenInfo is twelve words");
@@ -58,12 +64,15 @@ struct GenArgs {
     int32_t ranged;          // 1: M and DDT of instance `seed` are draws 0 and 1 of the stream seed ^ FJSP_GEN_AUX_STREAM (fjsp_gen_ranges)
     int32_t M_min, M_max;
     double DDT_min, DDT_max;
+    int32_t orders;          // 1: S of instance `seed` is draw 2 of that stream (fjsp_gen_orders); 0: one order
+    int32_t S_min, S_max;
     uint64_t seed_base;
     int32_t class_fjsp;      // SO_DFJSP: the order's delivery time is every job's due date, every machine needs an operation
     int32_t allow_device;    // 0: every LP goes to the host list (FJSP_LP_IMPL=host)
     int32_t kmax;            // operation types of the largest possible instance: stride of the eligible-list rows
     int32_t RP;
     uint8_t *elig;           // [n_inst][kmax][MP] machine_rj_dict in FILE order (zeros behind each list)
+    int32_t *deliv;          // [n_inst][SP] delivery_s, ascending: the record keeps the jobs' due dates only
     GenInfo *info;           // [n_inst]
     uint32_t *counts;        // [kGenCounts], by GenCount
     uint32_t *fit_ids;       // [n_inst] instances whose LP runs on the device, in arrival order
@@ -96,6 +105,13 @@ __device__ inline double gen_ddt(const GenArgs &a, uint64_t seed) {
     if (!a.ranged) return a.g.DDT;
     return a.DDT_min + (a.DDT_max - a.DDT_min) * ((double)(gen_draw(seed ^ FJSP_GEN_AUX_STREAM, 1u) >> 11) * (1.0 / 9007199254740992.0));
 }
+__device__ inline int gen_orders(const GenArgs &a, uint64_t seed) {      // draw_gen_orders (fjsp_instance.cpp)
+    return a.orders ? gen_randint(seed ^ FJSP_GEN_AUX_STREAM, 2u, a.S_min, a.S_max) : 1;
+}
+__device__ inline double gen_uniform(uint64_t seed, uint32_t i, double lo, double hi) {
+    return lo + (hi - lo) * ((double)(gen_draw(seed, i) >> 11) * (1.0 / 9007199254740992.0));
+}
+constexpr int kGenMaxS = FJSP_GEN_MAX_ORDERS;
 }  // namespace
 
 // One wave per instance.
@@ -104,21 +120,25 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     __shared__ uint16_t s_p[kGenMaxK * kMaxM];       // p[k][m], 0 = ineligible
     __shared__ double s_tr[kGenMaxK];                // time_rj: mean processing time over the eligible list
     __shared__ uint32_t s_off[kGenMaxK], s_poff[kGenMaxK];   // first shuffle draw / first processing-time draw of type k
-    __shared__ uint16_t s_rk[kGenMaxK], s_koff[kGenMaxK + 1], s_jbeg[kGenMaxK + 1], s_cnt[kGenMaxK];
+    __shared__ uint16_t s_rk[kGenMaxK], s_koff[kGenMaxK + 1], s_jbeg[kGenMaxK + 1];
+    __shared__ uint16_t s_cnt[kGenMaxS * kGenMaxK];  // count[s][r] at s * kGenMaxK + r: order 0 in front
+    __shared__ uint16_t s_tot[kGenMaxK];             // jobs of kind r over all orders
     __shared__ uint8_t s_n[kGenMaxK], s_jk[kGenMaxK], s_Jr[kGenMaxK];
     __shared__ int32_t s_hdr[8];                     // R, K, status, nx, first count draw, nj, delivery, ops
+    __shared__ double s_dl[kGenMaxS];                // arrive + gap of order s, then sorted
+    __shared__ int32_t s_arr[kGenMaxS], s_del[kGenMaxS];     // time_arrive_s, delivery_s (ascending)
     const int inst = (int)blockIdx.x, l = (int)threadIdx.x;
     if (inst >= b.n_inst) return;
     const fjsp_gen_params &g = a.g;
     const uint64_t seed = a.seed_base + (uint64_t)inst;
-    const int M = gen_machines(a, seed), MP = b.MP, KP = b.KP;
+    const int M = gen_machines(a, seed), MP = b.MP, KP = b.KP, S = gen_orders(a, seed);
     const double DDT = gen_ddt(a, seed);
     unsigned char *rec = b.inst + (size_t)inst * b.L.i_stride;
     const Layout &L = b.L;
 
     // ---- R, J_r, the kinds' first operation types
     const int R = gen_randint(seed, 0u, g.R_min, g.R_max);                                       // :42
-    const bool r_ok = R >= 1 && R <= a.RP && R <= kGenMaxK && M >= 1 && M <= MP && M <= kMaxM;
+    const bool r_ok = R >= 1 && R <= a.RP && R <= kGenMaxK && M >= 1 && M <= MP && M <= kMaxM && S >= 1 && S <= b.SP && S <= kGenMaxS;
     for (int r = l; r_ok && r < R; r += kWave) s_Jr[r] = (uint8_t)gen_randint(seed, 1u + (uint32_t)r, g.J_min, g.J_max);   // :46,71
     __syncthreads();
     if (l == 0) {
@@ -148,7 +168,7 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     const int K = s_hdr[1], nx = s_hdr[3];
     int status = s_hdr[2];
     if (status != 0) {
-        if (l == 0) a.info[inst] = GenInfo{status, 0, 0, 0, 0, 0, 0, 0, M, 0, DDT};
+        if (l == 0) a.info[inst] = GenInfo{status, 0, 0, 0, 0, 0, 0, 0, M, S, DDT};
         return;
     }
     // ---- per operation type: choice(M, n, replace=False) as a Fisher-Yates prefix, then the processing times
@@ -171,17 +191,39 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
         for (int m = n; m < M; ++m) perm[m] = 0;
         s_tr[k] = (double)sum / (double)n;                                                         // :78
     }
-    for (int r = l; r < R; r += kWave) s_cnt[r] = (uint16_t)gen_randint(seed, (uint32_t)s_hdr[4] + (uint32_t)r, g.N_min, g.N_max);   // :80
+    // the S x R job counts, order-major, behind the processing times; the S - 1 arrival intervals behind them       :80, :83-84
+    for (int q = l; q < S * R; q += kWave)
+        s_cnt[(q / R) * kGenMaxK + q % R] = (uint16_t)gen_randint(seed, (uint32_t)s_hdr[4] + (uint32_t)q, g.N_min, g.N_max);
+    __syncthreads();
+    if (l < S) {
+        // order l: its gap strictly left to right over the operation types (:81-82); its arrival time the truncated running
+        // sum of the intervals, accumulated from order 0 again (:85-86; interval[0] = 0.0)
+        double acc = 0.0;
+        for (int k = 0; k < K; ++k) acc = acc + s_tr[k] * (double)s_cnt[l * kGenMaxK + s_rk[k]];
+        const double gap = acc * DDT / (double)(M * 2);
+        double t = 0.0;                              // (0.0 + interval[0] is 0.0)
+        for (int q = 1; q <= l; ++q) t = t + gen_uniform(seed, (uint32_t)s_hdr[4] + (uint32_t)(S * R) + (uint32_t)(q - 1), g.t_si_min, g.t_si_max);
+        s_arr[l] = (int)t;
+        s_dl[l] = (double)s_arr[l] + gap;
+    }
     __syncthreads();
     if (l == 0) {
         int nj = 0, ops = 0;
-        double acc = 0.0;                                                                          // :81-82, strictly left to right
-        for (int r = 0; r < R; ++r) { s_jbeg[r] = (uint16_t)nj; nj += s_cnt[r]; ops += (int)s_cnt[r] * (int)s_Jr[r]; }
+        for (int r = 0; r < R; ++r) {
+            int tot = 0;
+            for (int so = 0; so < S; ++so) tot += s_cnt[so * kGenMaxK + r];
+            s_jbeg[r] = (uint16_t)nj; s_tot[r] = (uint16_t)tot; nj += tot; ops += tot * (int)s_Jr[r];
+        }
         s_jbeg[R] = (uint16_t)nj;
-        for (int k = 0; k < K; ++k) acc = acc + s_tr[k] * (double)s_cnt[s_rk[k]];
-        const double gap = acc * DDT / (double)(M * 2);
-        const double dl = 0.0 + gap;                                                               // :85-86 (one order: arrives at 0)
-        s_hdr[5] = nj; s_hdr[6] = (int)dl; s_hdr[7] = ops;
+        // :87-88 the delivery times sorted ascending, then truncated: an insertion sort (S <= 16; equal keys are equal values)
+        for (int i = 1; i < S; ++i) {
+            const double v = s_dl[i];
+            int j = i - 1;
+            for (; j >= 0 && s_dl[j] > v; --j) s_dl[j + 1] = s_dl[j];
+            s_dl[j + 1] = v;
+        }
+        for (int so = 0; so < S; ++so) s_del[so] = (int)s_dl[so];
+        s_hdr[5] = nj; s_hdr[6] = s_del[0]; s_hdr[7] = ops;
         if (nj > b.JP || nj > 65535) s_hdr[2] = FJSP_E_FORMAT;
     }
     __syncthreads();
@@ -193,11 +235,15 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
         for (int k = 0; k < K; ++k) ops_m += s_p[k * kMaxM + l] > 0 ? 1 : 0;
     if (a.class_fjsp && __any(l < M && ops_m == 0) && status == 0) status = FJSP_E_UNSUPPORTED;
     const uint32_t lds = lp_device_lds_bytes(K, M, nx, R, MP);
-    if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[7], delivery, M, 0, DDT};
+    if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[7], delivery, M, S, DDT};
     if (status != 0) return;
 
     // ---- the record (pack_instance, fjsp_env.hip); the slab was zeroed before the launch
-    if (l == 0) *reinterpret_cast<InstHeader *>(rec) = InstHeader{K, M, R, nj};
+    if (l == 0) *reinterpret_cast<InstHeader *>(rec) = InstHeader{K, M, R | (b.mord ? S << 16 : 0), nj};
+    if (l < S) {
+        reinterpret_cast<int32_t *>(rec + L.i_oarr)[l] = s_arr[l];
+        a.deliv[(size_t)inst * (size_t)b.SP + l] = s_del[l];
+    }
     uint16_t *ocnt = reinterpret_cast<uint16_t *>(rec + L.i_ocnt);
     uint32_t *kA = reinterpret_cast<uint32_t *>(rec + L.i_kA), *kB = reinterpret_cast<uint32_t *>(rec + L.i_kB);
     uint32_t *elig = reinterpret_cast<uint32_t *>(rec + L.i_elig), *first4 = reinterpret_cast<uint32_t *>(rec + L.i_f4);
@@ -206,18 +252,24 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     uint16_t *p = reinterpret_cast<uint16_t *>(rec + L.i_p);
     uint8_t *el_out = a.elig + (size_t)inst * (size_t)a.kmax * (size_t)MP;
     for (int r = l; r < R; r += kWave) {
-        const int c = s_cnt[r], J = s_Jr[r], jb = s_jbeg[r];
-        ocnt[r] = (uint16_t)c;
-        // class_FJSSP.py:214-218 with Python's round (half to even: rint in the default rounding mode)
-        const long r_due = (long)rint((double)((long)delivery * J) / (double)c);
-        for (int n = 0; n < c; ++n) {
-            due[jb + n] = a.class_fjsp ? delivery : (int32_t)(long)rint((double)(r_due * n) / (double)c);
-            jinfo[jb + n] = (uint32_t)s_koff[r] | ((uint32_t)J << 16);
+        const int J = s_Jr[r], jb = s_jbeg[r];
+        // the jobs of kind r over all orders in arrival order; class_FJSSP.py:214-218 with Python's round (half to even: rint in
+        // the default rounding mode), the ABSOLUTE job number n and the order's own count
+        int cnt = 0;
+        for (int so = 0; so < S; ++so) {
+            const int c = s_cnt[so * kGenMaxK + r], dl = s_del[so];
+            ocnt[(size_t)so * b.RP + r] = (uint16_t)c;
+            const long r_due = (long)rint((double)((long)dl * J) / (double)c);
+            for (int n = cnt; n < cnt + c; ++n) {
+                due[jb + n] = a.class_fjsp ? dl : (int32_t)(long)rint((double)(r_due * n) / (double)c);
+                jinfo[jb + n] = (uint32_t)s_koff[r] | ((uint32_t)J << 16);
+            }
+            cnt += c;
         }
     }
     for (int k = l; k < K; k += kWave) {
         const int r = s_rk[k], j = s_jk[k], J = s_Jr[r], n = s_n[k];
-        kA[k] = (uint32_t)s_jbeg[r] | ((uint32_t)s_cnt[r] << 16);
+        kA[k] = (uint32_t)s_jbeg[r] | ((uint32_t)s_tot[r] << 16);
         kB[k] = (uint32_t)j | ((uint32_t)J << 8) | ((uint32_t)(r & 0xFF) << 16) | ((uint32_t)((j == J - 1 ? 1u : 0u) | 2u) << 24);
         uint32_t em = 0, f4 = 0;
         for (int m = 0; m < M; ++m) {
@@ -263,7 +315,7 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
         if (l == 0) (fit ? a.fit_ids : a.glob_ids)[slot] = (uint32_t)inst;
         uint16_t *Q = (fit ? a.lp_in : a.lp_in_glob) + (size_t)slot * 2 * KP;
         for (int k = l; k < K; k += kWave) {
-            const uint16_t c = s_cnt[s_rk[k]];
+            const uint16_t c = s_cnt[s_rk[k]];      // order 0's count, not the kind's total
             Q[k] = c;
             Q[KP + k] = s_jk[k] == 0 ? c : (uint16_t)0;
         }
@@ -299,11 +351,14 @@ __global__ __launch_bounds__(kWave) void generate_finish_kernel(DevBatch b, GenA
     __syncthreads();
     if (l != 0) return;
     double *ss = reinterpret_cast<double *>(rec + b.L.i_ss);
+    // (Q_k is the count of the kind in order 0 -- i_ocnt's first row; kA >> 16 is the kind's total over all orders)
+    const uint16_t *ocnt = reinterpret_cast<const uint16_t *>(rec + b.L.i_ocnt);
     double best = 0.0;
     bool lp_ok = true;
-    for (int k = 0; k < K; ++k) {
+    for (int k = 0, r = -1; k < K; ++k) {
+        if ((kB[k] & 0xFFu) == 0u) ++r;                      // a kind's first operation type
         if (!(s_v[k] > 0.0)) lp_ok = false;                  // a failed LP leaves x = 0: no fluid rate
-        const double v = (double)(kA[k] >> 16) / s_v[k];
+        const double v = (double)ocnt[r] / s_v[k];
         if (k == 0 || v > best) best = v;
     }
     ss[7] = best;
@@ -326,11 +381,14 @@ __global__ __launch_bounds__(kWave) void generate_finish_kernel(DevBatch b, GenA
 }
 
 // The head of the listed instances' records (everything in front of x), side by side: the host route's one read-back.
-__global__ __launch_bounds__(256) void generate_gather_kernel(DevBatch b, const uint32_t *ids, int count, uint4 *out, int words16) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)count * (size_t)words16) return;
-    const int slot = (int)(idx / (size_t)words16), w = (int)(idx % (size_t)words16);
-    out[idx] = reinterpret_cast<const uint4 *>(b.inst + (size_t)ids[slot] * b.L.i_stride)[w];
+// A multi-order handle's rows carry `tail` more words from word tail0 on: the orders' counts (i_oarr, i_ocnt), which lie
+// behind x.  ids == nullptr: instances 0 .. count - 1.
+__global__ __launch_bounds__(256) void generate_gather_kernel(DevBatch b, const uint32_t *ids, int count, uint4 *out, int head, int tail0, int tail) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, words16 = (size_t)(head + tail);
+    if (idx >= (size_t)count * words16) return;
+    const int slot = (int)(idx / words16), w = (int)(idx % words16);
+    const size_t inst = ids ? (size_t)ids[slot] : (size_t)slot;
+    out[idx] = reinterpret_cast<const uint4 *>(b.inst + inst * b.L.i_stride)[w < head ? w : tail0 + (w - head)];
 }
 
 // Every env as a create leaves it: done, so that a step before the reset is flagged; the row kernels' per-env operation count.
@@ -372,6 +430,7 @@ struct GenState {
     LpRoute route[kGenRoutes];
     int chunk = 0;                       // staging slots of one LP launch / one host-route round
     int head16 = 0;                      // 16-byte words of a record in front of x
+    int tail0 = 0, tail16 = 0;           // multi-order handles: the words that hold i_oarr and i_ocnt, gathered behind the head
     uint8_t *d_kenv = nullptr;
     uint32_t *d_lp_err = nullptr;
     uint4 *d_head = nullptr, *h_head = nullptr;      // [chunk][head16] record heads of the host route, and pinned
@@ -411,8 +470,13 @@ int check_params(const fjsp_gen_params &g) {
 
 // check_instance (fjsp_env.hip) on the worst case of the parameters, sizes into sh.  Over M in M_min..M_max and |DDT| up to
 // ddt_max: sizes from M_max, the largest delivery time from ddt_max / (2 M_min)
-int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_max, Shape &sh) {
-    const long long K = (long long)g.R_max * g.J_max, nj = (long long)g.R_max * g.N_max, ops = K * g.N_max;
+// With S_max > 1 orders: jobs, operations and the clock count all of them, the clock starts from the last arrival
+int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_max, int S_max, Shape &sh) {
+    const long long K = (long long)g.R_max * g.J_max, nj = (long long)g.R_max * g.N_max * S_max, ops = K * g.N_max * S_max;
+    if (S_max > 1) {
+        if (nj > 65535) { set_error("generated instances can have more than 65535 jobs (R_max x N_max x S_max)"); return FJSP_E_UNSUPPORTED; }
+        if (ops > 65535) { set_error("generated instances can have more than 65535 operations (R_max x J_max x N_max x S_max)"); return FJSP_E_UNSUPPORTED; }
+    }
     if (K > kWave * kMaxKC) { set_error("generated instances can have more than 256 operation types (R_max x J_max)"); return FJSP_E_UNSUPPORTED; }
     if (M_max > kMaxM) { set_error(M_min == M_max ? "more than 32 machines" : "more than 32 machines (M_max)"); return FJSP_E_UNSUPPORTED; }
     if (nj > 65535) { set_error("generated instances can have more than 65535 jobs (R_max x N_max)"); return FJSP_E_UNSUPPORTED; }
@@ -421,15 +485,20 @@ int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_
     if (g.p_max > 65535) { set_error("processing time above 65535"); return FJSP_E_UNSUPPORTED; }
     // the 32-bit clocks: every operation in sequence at the largest processing time; the largest delivery time is every
     // operation type at p_max with N_max jobs, times DDT / (2 M)
-    const double due = std::fabs((double)K * (double)g.p_max * (double)g.N_max * ddt_max / (double)(M_min * 2));
-    const double clock = (double)ops * (double)g.p_max;
-    if (!(clock + due <= 2147483647.0) || !((double)g.N_max * (clock + due) <= 2147483647.0)) {
-        set_error("generated instances can be too long for the kernels' 32-bit clocks: (operations x max processing time + "
-                  "largest delivery time) x jobs per kind must stay below 2^31; the largest delivery time grows with DDT (DDT_max) "
-                  "and shrinks with the machine count (M_min)");
+    // (several orders: the last one arrives at (S_max - 1) t_si_max at the latest, its delivery time lies one order's gap behind
+    // that, the work of all orders follows the last arrival, and a kind has N_max jobs in every order)
+    const double arrive = S_max > 1 ? (double)(S_max - 1) * g.t_si_max : 0.0;
+    const double due = arrive + std::fabs((double)K * (double)g.p_max * (double)g.N_max * ddt_max / (double)(M_min * 2));
+    const double clock = arrive + (double)ops * (double)g.p_max;
+    if (!(clock + due <= 2147483647.0) || !((double)g.N_max * (double)S_max * (clock + due) <= 2147483647.0)) {
+        set_error(S_max > 1 ? "generated instances can be too long for the kernels' 32-bit clocks: (last arrival (S_max - 1) x t_si_max + operations "
+                              "of all orders x max processing time + largest delivery time) x jobs per kind (N_max x S_max) must stay below 2^31"
+                            : "generated instances can be too long for the kernels' 32-bit clocks: (operations x max processing time + "
+                              "largest delivery time) x jobs per kind must stay below 2^31; the largest delivery time grows with DDT (DDT_max) "
+                              "and shrinks with the machine count (M_min)");
         return FJSP_E_UNSUPPORTED;
     }
-    sh.K = (int)K; sh.M = M_max; sh.J = (int)nj; sh.R = g.R_max; sh.S = 1;
+    sh.K = (int)K; sh.M = M_max; sh.J = (int)nj; sh.R = g.R_max; sh.S = S_max;
     sh.single_job = g.N_min == 1 && g.N_max == 1 && g.R_max <= 255;
     return FJSP_OK;
 }
@@ -451,6 +520,11 @@ uint64_t gen_hash(const GenArgs &a, int n_inst, uint64_t seed_base) {
         const double rd[2] = {a.DDT_min, a.DDT_max};
         mix(rv, sizeof(rv)); mix(rd, sizeof(rd));
     }
+    if (a.orders) {     // likewise: a tag, the order range and the interval bounds
+        const int32_t ov[3] = {0x4F524453, a.S_min, a.S_max};
+        const double od[2] = {g.t_si_min, g.t_si_max};
+        mix(ov, sizeof(ov)); mix(od, sizeof(od));
+    }
     return h;
 }
 
@@ -458,18 +532,26 @@ using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 double ms_between(hipEvent_t a, hipEvent_t b) { float f = 0.f; (void)hipEventElapsedTime(&f, a, b); return f; }
 
-// The head of a packed record (pack_instance, generate_pack_kernel: everything in front of x) back on the host
-struct RecordHead { InstHeader h{}; std::vector<int> Jr, count, p; };      // [R], [R] jobs of every kind, [K][M] unpadded
-void decode_head(const DevBatch &b, const unsigned char *rec, RecordHead &o) {
+// The head of a packed record (pack_instance, generate_pack_kernel: everything in front of x) back on the host (RecordHead,
+// fjsp_env_impl.h).  ocnt: the record's i_ocnt, whose first row is order 0; nullptr on a one-order handle, where kA >> 16 is it
+void decode_head(const DevBatch &b, const unsigned char *rec, const uint16_t *ocnt, RecordHead &o) {
     o.h = *reinterpret_cast<const InstHeader *>(rec);
+    o.h.R &= 0xFFFF;                                     // (the order count rides in the high half on a multi-order handle)
     const uint32_t *kA = reinterpret_cast<const uint32_t *>(rec + b.L.i_kA), *kB = reinterpret_cast<const uint32_t *>(rec + b.L.i_kB);
     const uint16_t *p16 = reinterpret_cast<const uint16_t *>(rec + b.L.i_p);
     const size_t K = (size_t)o.h.K, M = (size_t)o.h.M;
     o.Jr.clear(); o.count.clear(); o.p.assign(K * M, 0);
     for (size_t k = 0; k < K; ++k) {
-        if ((kB[k] & 0xFFu) == 0u) { o.Jr.push_back((int)((kB[k] >> 8) & 0xFFu)); o.count.push_back((int)(kA[k] >> 16)); }     // a kind's first operation type
+        if ((kB[k] & 0xFFu) == 0u) { o.count.push_back(ocnt ? (int)ocnt[o.Jr.size()] : (int)(kA[k] >> 16)); o.Jr.push_back((int)((kB[k] >> 8) & 0xFFu)); }     // a kind's first operation type
         for (size_t m = 0; m < M; ++m) o.p[k * M + m] = p16[k * (size_t)b.MP + m];
     }
+}
+
+// a gathered row (generate_gather_kernel): its bytes, and decode_head of it
+size_t row_bytes(const GenState &G) { return (size_t)(G.head16 + G.tail16) * 16; }
+void decode_row(const DevBatch &b, const GenState &G, const unsigned char *row, RecordHead &o) {
+    const unsigned char *tail = row + (size_t)G.head16 * 16 - (size_t)G.tail0 * 16;       // where the record's byte 0 would lie for the tail's offsets
+    decode_head(b, row, G.tail16 ? reinterpret_cast<const uint16_t *>(tail + b.L.i_ocnt) : nullptr, o);
 }
 
 int fail_generate(fjsp_env *e, int rc, const std::string &msg) {
@@ -485,8 +567,8 @@ int launch_failed(const char *text) { set_error(text); return FJSP_E_HIP; }
 int solve_on_host(fjsp_env *e, const LpRoute &r, int c0, int n, const std::string &call) {
     GenState &G = *e->gen;
     const DevBatch &b = e->b;
-    const size_t KP = (size_t)b.KP, MP = (size_t)b.MP, head = (size_t)G.head16 * 16, words = (size_t)n * (size_t)G.head16;
-    if (launch(generate_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r.st, b, (const uint32_t *)(r.ids + c0), n, G.d_head, G.head16) != 0)
+    const size_t KP = (size_t)b.KP, MP = (size_t)b.MP, head = row_bytes(G), words = (size_t)n * (head / 16);
+    if (launch(generate_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, r.st, b, (const uint32_t *)(r.ids + c0), n, G.d_head, G.head16, G.tail0, G.tail16) != 0)
         return launch_failed("generate_gather_kernel launch failed");
     HIP_TRY(hipMemcpyAsync(G.h_head, G.d_head, words * 16, hipMemcpyDeviceToHost, r.st));
     HIP_TRY(hipStreamSynchronize(r.st));
@@ -494,7 +576,7 @@ int solve_on_host(fjsp_env *e, const LpRoute &r, int c0, int n, const std::strin
         static thread_local RecordHead in;        // a thread's buffers, kept across its LPs
         static thread_local std::vector<int> Q, now;
         static thread_local std::vector<double> x;
-        decode_head(b, reinterpret_cast<const unsigned char *>(G.h_head) + (size_t)s * head, in);
+        decode_row(b, G, reinterpret_cast<const unsigned char *>(G.h_head) + (size_t)s * head, in);
         const int K = in.h.K, M = in.h.M;
         Q.clear(); now.clear(); x.assign((size_t)K * M, 0.0);
         for (int kind = 0; kind < in.h.R; ++kind)
@@ -541,6 +623,31 @@ int run_route(fjsp_env *e, const LpRoute &r, int n_total, const std::string &cal
     return FJSP_OK;
 }
 
+}  // namespace
+
+// The heads of all records into e->lp_mirror, in rounds of GenState::chunk through the host route's gather buffers.  Called
+// with no regenerate under way.
+int refresh_lp_mirror(fjsp_env *e) {
+    GenState &G = *e->gen;
+    const DevBatch &b = e->b;
+    const size_t row = row_bytes(G);
+    std::vector<RecordHead> mirror((size_t)b.n_inst);
+    for (int c0 = 0; c0 < b.n_inst; c0 += G.chunk) {
+        const int n = std::min(G.chunk, b.n_inst - c0);
+        const size_t words = (size_t)n * (row / 16);
+        DevBatch part = b;                               // instances c0 .. c0 + n - 1, by position
+        part.inst = b.inst + (size_t)c0 * b.L.i_stride;
+        if (launch(generate_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, G.st_host, part, (const uint32_t *)nullptr, n, G.d_head, G.head16, G.tail0, G.tail16) != 0)
+            return launch_failed("generate_gather_kernel launch failed");
+        HIP_TRY(hipMemcpyAsync(G.h_head, G.d_head, words * 16, hipMemcpyDeviceToHost, G.st_host));
+        HIP_TRY(hipStreamSynchronize(G.st_host));
+        for (int q = 0; q < n; ++q) decode_row(b, G, reinterpret_cast<const unsigned char *>(G.h_head) + (size_t)q * row, mirror[(size_t)(c0 + q)]);
+    }
+    e->lp_mirror.swap(mirror);
+    return FJSP_OK;
+}
+
+namespace {
 // The whole refill: records, LPs, tables, reset.  Synchronous; on the handle's device.
 int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::string &call) {
     GenState &G = *e->gen;
@@ -557,6 +664,7 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
     // ---- clear
     HIP_TRY(hipMemsetAsync(b.inst, 0, n_inst * b.L.i_stride, st));
     HIP_TRY(hipMemsetAsync(b.envs, 0, N * b.L.e_stride, st));       // the draw counters too: the env streams start over
+    if (b.mord) HIP_TRY(hipMemsetAsync(b.pending_count, 0, 4, st)); // no env is parked at an arrival
     HIP_TRY(hipMemsetAsync(G.a.counts, 0, kGenCounts * sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(G.a.counts + kCountFailed, 0xFF, sizeof(uint32_t), st));
     for (const LpRoute &r : G.route) if (r.d_solved) HIP_TRY(hipMemsetAsync(r.d_solved, 0, sizeof(LpCounters), st));
@@ -578,7 +686,7 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
         if (f.status != 0)
             return fail_generate(e, f.status, call + ": " + who(seed_base, i) + ": a draw left the record's fields (internal error)");
-        if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP)
+        if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP || f.S < 1 || f.S > b.SP)
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": sizes disagree with the host's (internal error)");
         bytes += step_bytes(b, f.K, f.nj, f.M);
     }
@@ -633,14 +741,23 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
         G.stats[kStatDevicePivots] += G.stats[kStatGlobalPivots];
     }
     e->inst_hash = gen_hash(G.a, b.n_inst, seed_base);
+    if (b.mord) {
+        // the memo of solved arrival LPs is keyed by the instance index, which names another instance now (the counters of
+        // solved LPs and pivots keep running); the host services read the new records' heads
+        arrivals_forget(e->arr);
+        e->lp_mirror.clear();
+        if (!e->arr.lp_device || e->arr.ring)
+            if (const int rc = refresh_lp_mirror(e)) return rc;
+    }
     e->gen_failed = false;
     G.ms[kMsTotal] = ms_since(t_call);
     return FJSP_OK;
 }
 
-// Both creates: q == nullptr is the fixed parameter set *prm; else *prm is q->base and M, DDT are drawn per instance
-int create_generated(const std::string &call, const fjsp_gen_params *prm, const fjsp_gen_ranges *q, int32_t n_inst, int32_t n_envs,
-                     int32_t variant, int32_t device, uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
+// The three creates: q == nullptr is the fixed parameter set *prm; else *prm is q->base and M, DDT are drawn per instance;
+// o != nullptr: q is &o->r and the number of orders is drawn as well
+int create_generated(const std::string &call, const fjsp_gen_params *prm, const fjsp_gen_ranges *q, const fjsp_gen_orders *o, int32_t n_inst,
+                     int32_t n_envs, int32_t variant, int32_t device, uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
     if (!prm || !out || n_inst <= 0 || n_envs <= 0) { set_error(call + ": bad arguments"); return FJSP_E_ARG; }
     if (family < -1 || family > 1) { set_error(call + ": family must be -1, 0 or 1"); return FJSP_E_ARG; }
     const bool class_fjsp = variant == FJSP_VARIANT_SO_DFJSP;
@@ -652,19 +769,29 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     if (variant != FJSP_VARIANT_SO_FJSSP && variant != FJSP_VARIANT_SO_SFJSP && variant != FJSP_VARIANT_MO_FJSSP_DISCRETES) {
         set_error(call + ": unknown variant"); return FJSP_E_ARG;
     }
-    int rc = q ? check_gen_ranges(*q) : FJSP_OK;
+    int rc = o ? check_gen_orders(*o) : (q ? check_gen_ranges(*q) : FJSP_OK);
     if (rc != FJSP_OK) return rc;
     fjsp_gen_params g = *prm;
     if (q) { g.M = q->M_min; g.DDT = 0.0; }       // base.M and base.DDT are not read
+    if (o) g.S = o->S_max;                        // nor is base.S
     if ((rc = check_params(g)) != FJSP_OK) return rc;
+    const int S_max = o ? o->S_max : 1;
+    if (S_max > FJSP_GEN_MAX_ORDERS) {
+        set_error(call + ": more than " + std::to_string(FJSP_GEN_MAX_ORDERS) + " orders (S_max): the generator kernel keeps the orders' counts and times in LDS");
+        return FJSP_E_UNSUPPORTED;
+    }
+    if (S_max > 1 && variant != FJSP_VARIANT_SO_FJSSP) {
+        set_error(call + ": only SO_FJSSP handles order arrivals (the subclasses are single-order, SO_SFJSP.py:20 / MO_FJSSP_discretes.py:21): S_max must be 1");
+        return FJSP_E_UNSUPPORTED;
+    }
     const int M_min = q ? q->M_min : g.M, M_max = q ? q->M_max : g.M;
     const double ddt_max = q ? std::max(std::fabs(q->DDT_min), std::fabs(q->DDT_max)) : g.DDT;
-    if (prm->S != 1) {
+    if (!o && prm->S != 1) {
         set_error(call + ": one order only (S == 1): order arrivals need the per-env fluid tables (use fjsp_env_create)");
         return FJSP_E_UNSUPPORTED;
     }
     Shape sh;
-    if ((rc = check_worst_case(g, M_min, M_max, ddt_max, sh)) != FJSP_OK) return rc;
+    if ((rc = check_worst_case(g, M_min, M_max, ddt_max, S_max, sh)) != FJSP_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device visible: the environment kernels need an MI355X (there is no CPU path)");
@@ -677,10 +804,16 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     e->device = device; e->src = nullptr; e->first = 0;
     DevBatch &b = e->b;
     if ((rc = plan_batch(b, e->plan, sh, n_inst, n_envs, variant, rng_seed, family)) != FJSP_OK) return rc;
-    // src stays null: only the order-arrival services (fjsp_arrivals.hip) read it, and only multi-order batches reach them
-    if (b.mord) { set_error(call + ": internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
+    // src stays null: the order-arrival services (fjsp_arrivals.hip) of a multi-order handle read lp_mirror in its place
+    if ((b.mord != 0) != (S_max > 1)) { set_error(call + ": internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
     e->inst_K.assign((size_t)n_inst, 0); e->inst_M.assign((size_t)n_inst, sh.M);
-    e->ops_max = sh.K * prm->N_max;
+    e->ops_max = sh.K * prm->N_max * S_max;
+    if (b.mord) {
+        // the arrival service, once: from the worst tableau of the parameters, with its staging and pools
+        const LpTableau worst = lp_worst_case(prm->R_max, prm->J_max, sh.M);
+        choose_lp_service(e.get(), &worst, 1);
+        if ((rc = alloc_arrival_staging(e.get())) != FJSP_OK) return rc;
+    }
 
     e->gen = new GenState();
     GenState &G = *e->gen;
@@ -688,9 +821,15 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     if (q) { g.M = 0; G.a.ranged = 1; G.a.M_min = q->M_min; G.a.M_max = q->M_max; G.a.DDT_min = q->DDT_min; G.a.DDT_max = q->DDT_max; }
     G.a.g = g; G.a.class_fjsp = class_fjsp ? 1 : 0; G.a.allow_device = e->plan.lp_device_forced == 0 ? 0 : 1;
     G.a.allow_global = e->plan.lp_device_forced == 2 ? 1 : 0;
+    if (o) { G.a.orders = 1; G.a.S_min = o->S_min; G.a.S_max = o->S_max; }
     G.a.kmax = sh.K; G.a.RP = sh.R;
     G.chunk = (int)std::min<size_t>(NI, 1024);
     G.head16 = (int)((b.L.i_x + 15) / 16);
+    if (b.mord) {
+        G.tail0 = (int)(b.L.i_oarr / 16);
+        G.tail16 = (int)((b.L.i_ocnt + (size_t)b.SP * b.RP * 2 + 15) / 16) - G.tail0;
+    }
+    const size_t heads = (size_t)G.chunk * row_bytes(G);
     const size_t stage = (size_t)G.chunk * KP * MP * 8, ids = NI * sizeof(uint32_t), lp_in = NI * 2 * KP * sizeof(uint16_t);
     LpRoute &lds = G.route[kRouteLds], &glob = G.route[kRouteGlobal], &host = G.route[kRouteHost];
     lds.producer = LpRoute::kLds; lds.length = kCountFit; lds.launch_error = "lp_device_kernel / generate_finish_kernel launch failed";
@@ -700,18 +839,19 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         !dev_alloc(e.get(), N * b.L.e_stride, &b.envs, "hipMalloc env slab") ||
         !dev_alloc(e.get(), N + 16, &e->d_done_scratch, "hipMalloc scratch") ||
         !dev_alloc(e.get(), NI * (size_t)sh.K * MP, &G.a.elig, "hipMalloc eligible lists") ||
+        !dev_alloc(e.get(), NI * (size_t)b.SP * sizeof(int32_t), &G.a.deliv, "hipMalloc delivery times") ||
         !dev_alloc(e.get(), NI * sizeof(GenInfo), &G.a.info, "hipMalloc generator status") ||
         !dev_alloc(e.get(), kGenCounts * sizeof(uint32_t), &G.a.counts, "hipMalloc list lengths") ||
         !dev_alloc(e.get(), ids, &G.a.fit_ids, "hipMalloc LP list") || !dev_alloc(e.get(), ids, &G.a.host_ids, "hipMalloc LP list") ||
         !dev_alloc(e.get(), lp_in, &G.a.lp_in, "hipMalloc LP inputs") ||
         !dev_alloc(e.get(), stage, &lds.d_stage, "hipMalloc LP solutions") || !dev_alloc(e.get(), stage, &host.d_stage, "hipMalloc LP solutions") ||
-        !dev_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.d_head, "hipMalloc record heads") ||
+        !dev_alloc(e.get(), heads, &G.d_head, "hipMalloc record heads") ||
         !dev_alloc(e.get(), sizeof(LpErrWord), &G.d_lp_err, "hipMalloc LP error word") ||
         !dev_alloc(e.get(), sizeof(LpCounters), &lds.d_solved, "hipMalloc LP counters") ||
         (b.grp && !dev_alloc(e.get(), N, &G.d_kenv, "hipMalloc K table")) ||
         !host_alloc(e.get(), NI * sizeof(GenInfo), &G.h_info) || !host_alloc(e.get(), kGenCounts * sizeof(uint32_t), &G.h_counts) ||
         !host_alloc(e.get(), ids, &G.h_host_ids) || !host_alloc(e.get(), stage, &G.h_stage) ||
-        !host_alloc(e.get(), (size_t)G.chunk * G.head16 * 16, &G.h_head) || !host_alloc(e.get(), sizeof(GenReadback), &G.h_back))
+        !host_alloc(e.get(), heads, &G.h_head) || !host_alloc(e.get(), sizeof(GenReadback), &G.h_back))
         return FJSP_E_HIP;
     if (G.a.allow_global) {
         // the scratch pool of the global-memory simplex, sized for the largest tableau the parameters admit within its limits:
@@ -747,18 +887,28 @@ using namespace fjsp;
 extern "C" {
 int fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
                               uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
-    return create_generated("fjsp_env_create_generated", prm, nullptr, n_inst, n_envs, variant, device, rng_seed, family, seed_base, out);
+    return create_generated("fjsp_env_create_generated", prm, nullptr, nullptr, n_inst, n_envs, variant, device, rng_seed, family, seed_base, out);
 }
 
 int fjsp_env_create_generated_ranges(const fjsp_gen_ranges *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
                                      uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
-    return create_generated("fjsp_env_create_generated_ranges", q ? &q->base : nullptr, q, n_inst, n_envs, variant, device, rng_seed, family,
+    return create_generated("fjsp_env_create_generated_ranges", q ? &q->base : nullptr, q, nullptr, n_inst, n_envs, variant, device, rng_seed, family,
                             seed_base, out);
+}
+
+int fjsp_env_create_generated_orders(const fjsp_gen_orders *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
+                                     uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
+    return create_generated("fjsp_env_create_generated_orders", q ? &q->r.base : nullptr, q ? &q->r : nullptr, q, n_inst, n_envs, variant, device,
+                            rng_seed, family, seed_base, out);
 }
 
 int fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed) {
     if (!e) { set_error("fjsp_env_regenerate: null env"); return FJSP_E_ARG; }
     if (!e->gen) { set_error("fjsp_env_regenerate: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    if (!async_idle(e)) {
+        set_error("fjsp_env_regenerate: environments are parked in the asynchronous arrival service; call fjsp_env_arrivals_flush first");
+        return FJSP_E_STATE;
+    }
     DeviceGuard guard(e->device);
     return regenerate(e, seed_base, rng_seed, "fjsp_env_regenerate");
 }
@@ -790,14 +940,23 @@ int fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr,
     HIP_TRY(hipMemcpy(rec.data(), b.inst + (size_t)i * b.L.i_stride, rec.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(el.data(), G.a.elig + (size_t)i * el.size(), el.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&f, G.a.info + i, sizeof(f), hipMemcpyDeviceToHost));
+    std::vector<int32_t> dl((size_t)b.SP);
+    HIP_TRY(hipMemcpy(dl.data(), G.a.deliv + (size_t)i * (size_t)b.SP, dl.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     RecordHead in;
-    decode_head(b, rec.data(), in);
+    const uint16_t *ocnt = reinterpret_cast<const uint16_t *>(rec.data() + b.L.i_ocnt);
+    const int32_t *oarr = reinterpret_cast<const int32_t *>(rec.data() + b.L.i_oarr);
+    decode_head(b, rec.data(), ocnt, in);
     const InstHeader &h = in.h;
+    const int S = f.S;
+    if (S < 1 || S > b.SP) { set_error("fjsp_env_instance_read: the record's order count is out of range (internal error)"); return FJSP_E_STATE; }
+    int jobs0 = 0;
+    for (int r = 0; r < h.R; ++r) jobs0 += ocnt[r];
     const uint32_t *em = reinterpret_cast<const uint32_t *>(rec.data() + b.L.i_elig);
     const double *xr = reinterpret_cast<const double *>(rec.data() + b.L.i_x);
-    if (dims) { dims[0] = h.R; dims[1] = h.M; dims[2] = h.K; dims[3] = 1; dims[4] = h.njobs; dims[5] = h.njobs; }
+    if (dims) { dims[0] = h.R; dims[1] = h.M; dims[2] = h.K; dims[3] = S; dims[4] = jobs0; dims[5] = h.njobs; }
     if (Jr) std::copy(in.Jr.begin(), in.Jr.end(), Jr);
-    if (count) std::copy(in.count.begin(), in.count.end(), count);
+    for (int so = 0; count && so < S; ++so)
+        for (int r = 0; r < h.R; ++r) count[(size_t)so * h.R + r] = ocnt[(size_t)so * b.RP + r];
     if (p) std::copy(in.p.begin(), in.p.end(), p);
     for (int k = 0; k < h.K; ++k) {
         if (elig_n) elig_n[k] = __builtin_popcount(em[k]);
@@ -806,8 +965,10 @@ int fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr,
             if (x) x[(size_t)k * h.M + m] = xr[(size_t)k * MP + m];
         }
     }
-    if (arrive) arrive[0] = 0;
-    if (delivery) delivery[0] = f.delivery;
+    for (int so = 0; so < S; ++so) {
+        if (arrive) arrive[so] = oarr[so];
+        if (delivery) delivery[so] = dl[(size_t)so];
+    }
     if (ddt) *ddt = f.ddt;
     return FJSP_OK;
 }

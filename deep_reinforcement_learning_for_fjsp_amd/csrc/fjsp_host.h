@@ -60,6 +60,8 @@ int finalize_instance(Instance &in);  // derives koff/K, validates
 // the bounds of a fjsp_gen_ranges (FJSP_E_ARG, the message names the bound); its per-instance draws of M and DDT
 int check_gen_ranges(const fjsp_gen_ranges &q);
 void draw_gen_params(const fjsp_gen_ranges &q, uint64_t seed, fjsp_gen_params &out);
+// the same of a fjsp_gen_orders: the ranges' bounds, the order count's and the arrival intervals'
+int check_gen_orders(const fjsp_gen_orders &q);
 
 }  // namespace fjsp
 

@@ -312,6 +312,26 @@ void draw_gen_params(const fjsp_gen_ranges &q, uint64_t seed, fjsp_gen_params &o
     out.DDT = aux.uniform(q.DDT_min, q.DDT_max);
 }
 
+// ---- ... and the number of orders (fjsp_gen_orders) ----
+int check_gen_orders(const fjsp_gen_orders &q) {
+    if (const int rc = check_gen_ranges(q.r)) return rc;
+    if (q.S_min < 1) { set_error("generator orders: S_min must be at least 1"); return FJSP_E_ARG; }
+    if (q.S_max < q.S_min) { set_error("generator orders: S_max < S_min"); return FJSP_E_ARG; }
+    const double lo = q.r.base.t_si_min, hi = q.r.base.t_si_max;
+    if (!std::isfinite(lo) || lo < 0.0) { set_error("generator orders: t_si_min must be finite and not negative"); return FJSP_E_ARG; }
+    if (!std::isfinite(hi) || hi < 0.0) { set_error("generator orders: t_si_max must be finite and not negative"); return FJSP_E_ARG; }
+    if (hi < lo) { set_error("generator orders: t_si_max < t_si_min"); return FJSP_E_ARG; }
+    return FJSP_OK;
+}
+
+void draw_gen_orders(const fjsp_gen_orders &q, uint64_t seed, fjsp_gen_params &out) {
+    Rng aux(seed ^ FJSP_GEN_AUX_STREAM);
+    out = q.r.base;
+    out.M = aux.randint(q.r.M_min, q.r.M_max);
+    out.DDT = aux.uniform(q.r.DDT_min, q.r.DDT_max);
+    out.S = aux.randint(q.S_min, q.S_max);
+}
+
 static int solve_order0(Instance &in) {
     std::vector<int> Q(in.K), now(in.K);
     for (int r = 0; r < in.R; ++r)
@@ -376,6 +396,20 @@ int fjsp_instances_generate_drawn(fjsp_instances *s, int32_t i, uint64_t seed, c
     CHECK_IDX(s, i);
     fjsp_gen_params prm;
     const int rc = fjsp_gen_draw(q, seed, &prm);
+    return rc == FJSP_OK ? fjsp_instances_generate(s, i, seed, &prm) : rc;
+}
+
+int fjsp_gen_draw_orders(const fjsp_gen_orders *q, uint64_t seed, fjsp_gen_params *out) {
+    if (!q || !out) { set_error("fjsp_gen_draw_orders: null argument"); return FJSP_E_ARG; }
+    const int rc = check_gen_orders(*q);
+    if (rc == FJSP_OK) draw_gen_orders(*q, seed, *out);
+    return rc;
+}
+
+int fjsp_instances_generate_orders(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_orders *q) {
+    CHECK_IDX(s, i);
+    fjsp_gen_params prm;
+    const int rc = fjsp_gen_draw_orders(q, seed, &prm);
     return rc == FJSP_OK ? fjsp_instances_generate(s, i, seed, &prm) : rc;
 }
 

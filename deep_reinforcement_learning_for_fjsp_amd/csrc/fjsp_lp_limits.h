@@ -21,6 +21,12 @@ constexpr int kLpGlobalColumns = 1536;         // ... and 24 chunks of 64 column
 __host__ __device__ inline int lp_max_rows(int K, int M, int R) { return K + M + K - R; }
 __host__ __device__ inline int lp_max_columns(int K, int M, int nx, int R) { return nx + 1 + lp_max_rows(K, M, R) + 1; }
 
+// The sizes that decide an instance's tableau.  lp_worst_case: those of the largest tableau a generator's parameters admit --
+// rows, columns and bytes all grow with K, M, nx and with K - R, so most arise at R_max kinds of J_max operations each
+// (rows R_max (2 J_max - 1) + M_max) with every (operation type, machine) pair eligible on M_max machines
+struct LpTableau { int K, M, nx, R; };
+inline LpTableau lp_worst_case(int R_max, int J_max, int M_max) { return LpTableau{R_max * J_max, M_max, R_max * J_max * M_max, R_max}; }
+
 // LDS bytes of lp_device_kernel for that tableau:
 // tableau | column values (x extraction) | (spare) | basis | ... | col_of, prec list | staged inputs: p, Q, n_now, kB (the tail)
 // (32 bits hold it: a batch has at most 256 operation types on 32 machines, 38 MB)

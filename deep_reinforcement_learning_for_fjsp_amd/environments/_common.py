@@ -52,11 +52,12 @@ class BatchedEnv(object):
     variant = None
 
     def __init__(self, instance_set, n_envs=None, first=0, n_inst=None, device=0, rng_seed=0, first_env=0, seed_base=0):
-        """instance_set: an InstanceSet, or the generator's parameters (instances.GenParams, or instances.GenRanges with
-        the machine count and the due-date tightness drawn per instance): the batch's instances are
+        """instance_set: an InstanceSet, or the generator's parameters (instances.GenParams, instances.GenRanges with
+        the machine count and the due-date tightness drawn per instance, or instances.GenOrders with the number of orders
+        drawn too -- BatchedSOFJSSP / BatchedSODFJSP then play order arrivals): the batch's instances are
         then generated and solved on the device from seed_base (EnvBatch.generated; n_envs is needed), and
-        ``self.batch.regenerate(seed_base)`` refills them in place.  One order only; the library refuses MO_DFJSP."""
-        if isinstance(instance_set, (_inst.GenParams, _inst.GenRanges)):
+        ``self.batch.regenerate(seed_base)`` refills them in place.  The library refuses MO_DFJSP."""
+        if isinstance(instance_set, (_inst.GenParams, _inst.GenRanges, _inst.GenOrders)):
             if n_envs is None:
                 raise ValueError("n_envs is needed with generator parameters")
             self.batch = EnvBatch.generated(instance_set, n_envs, seed_base, n_inst=n_inst, variant=self.variant, device=device,

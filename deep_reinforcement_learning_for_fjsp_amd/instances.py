@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import GenParams, GenRanges, check
+from ._capi import GenOrders, GenParams, GenRanges, check
 
 
 def bench_10x5_params(ddt=1.0):
@@ -41,10 +41,23 @@ def reference_training_ranges(agent):
     return GenRanges(base, M_min, M_max, 0.5, 1.5)
 
 
+def reference_order_ranges(agent):
+    """What the reference's multi-order training loops draw a fresh shop from: the generator's own distributions with the
+    machine count, the due-date tightness and the number of orders drawn per instance.
+        "da3c"    DA3C_double_actor.py:243-248   M = randint(10, 20), DDT = uniform(0.5, 1.5), S = randint(1, 5)
+        "hmpsac"  A3C_v5.1.py:245-250            the same"""
+    if agent not in ("da3c", "hmpsac"):
+        raise ValueError("reference_order_ranges: 'da3c' or 'hmpsac', got %r" % (agent,))
+    return GenOrders(GenRanges(reference_generator_params(1.0, 0, 1), 10, 20, 0.5, 1.5), 1, 5)
+
+
 def draw_params(ranges, seed):
-    """The GenParams that instance `seed` is generated with under `ranges` (fjsp_gen_draw)."""
+    """The GenParams that instance `seed` is generated with under `ranges`: a GenRanges (fjsp_gen_draw) or a GenOrders
+    (fjsp_gen_draw_orders)."""
     out = GenParams()
-    check(_capi.lib().fjsp_gen_draw(C.byref(ranges), int(seed) & (2 ** 64 - 1), C.byref(out)))
+    lib = _capi.lib()
+    draw = lib.fjsp_gen_draw_orders if isinstance(ranges, GenOrders) else lib.fjsp_gen_draw
+    check(draw(C.byref(ranges), int(seed) & (2 ** 64 - 1), C.byref(out)))
     return out
 
 
@@ -93,8 +106,10 @@ class InstanceSet(object):
         return self
 
     def generate(self, i, seed, params):
-        """params: GenParams, or GenRanges (M and DDT drawn per instance from the seed: fjsp_instances_generate_drawn)."""
-        call = self._lib.fjsp_instances_generate_drawn if isinstance(params, GenRanges) else self._lib.fjsp_instances_generate
+        """params: GenParams, GenRanges (M and DDT drawn per instance from the seed: fjsp_instances_generate_drawn) or
+        GenOrders (the number of orders too: fjsp_instances_generate_orders)."""
+        call = (self._lib.fjsp_instances_generate_orders if isinstance(params, GenOrders) else
+                self._lib.fjsp_instances_generate_drawn if isinstance(params, GenRanges) else self._lib.fjsp_instances_generate)
         check(call(self._h, int(i), int(seed) & (2 ** 64 - 1), C.byref(params)))
         return self
 

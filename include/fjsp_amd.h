@@ -105,6 +105,21 @@ typedef struct {
     double  DDT_min, DDT_max;  /* due-date tightness:     U(DDT_min, DDT_max)  */
 } fjsp_gen_ranges;
 
+/* ... and the number of orders, as the reference's DA3C / HMPSAC loops draw it (DA3C_double_actor.py:243-248,
+ * A3C_v5.1.py:245-250: S = randint(1, 5)).  The instance of seed s under q is fjsp_instances_generate(s, p), p = q.r.base
+ * with p.M and p.DDT as under q.r and
+ *     p.S   = randint(S_min, S_max)       draw 2 of the same auxiliary stream, the integer formula above
+ * THE CONTRACT: all three draws are always taken, draws 0 and 1 are those of fjsp_gen_ranges and the main stream of seed s is
+ * untouched, so a point range in all three (M_min == M_max, DDT_min == DDT_max, S_min == S_max) gives exactly the
+ * instances of fjsp_instances_generate with that fixed parameter set.
+ * FJSP_GEN_MAX_ORDERS: the most orders a batch generated on the device can draw (fjsp_env_create_generated_orders; the
+ * reference draws at most 6); it sizes the generator kernel's per-order arrays. */
+#define FJSP_GEN_MAX_ORDERS 16
+typedef struct {
+    fjsp_gen_ranges r;         /* r.base.S is not read */
+    int32_t S_min, S_max;      /* orders per instance:    U{S_min..S_max}      */
+} fjsp_gen_orders;
+
 int  fjsp_instances_create(int32_t n, fjsp_instances **out);
 void fjsp_instances_destroy(fjsp_instances *s);
 int  fjsp_instances_count(const fjsp_instances *s);
@@ -120,6 +135,12 @@ int fjsp_instances_generate(fjsp_instances *s, int32_t i, uint64_t seed, const f
 int fjsp_gen_draw(const fjsp_gen_ranges *q, uint64_t seed, fjsp_gen_params *out);
 /* fjsp_gen_draw, then fjsp_instances_generate with what it drew. */
 int fjsp_instances_generate_drawn(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_ranges *q);
+/* The same with the number of orders drawn as well (see fjsp_gen_orders).  FJSP_E_ARG for the bounds fjsp_gen_draw refuses,
+ * S_min < 1, S_max < S_min, and order intervals (r.base.t_si_min / t_si_max) that are not finite, negative or max < min; the
+ * message names the bound. */
+int fjsp_gen_draw_orders(const fjsp_gen_orders *q, uint64_t seed, fjsp_gen_params *out);
+/* fjsp_gen_draw_orders, then fjsp_instances_generate with what it drew. */
+int fjsp_instances_generate_orders(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_orders *q);
 /* Raw arrays (same meaning as the fjsp_instances_get outputs). */
 int fjsp_instances_set_raw(fjsp_instances *s, int32_t i, int32_t R, int32_t M, int32_t S,
                            const int32_t *Jr, const int32_t *p /*[K*M] k-major, 0 = ineligible*/,
@@ -184,8 +205,8 @@ int  fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_in
  * case (R_max x J_max operation types, R_max x N_max jobs), so kernel family, builds and schedule capacity never change:
  * fjsp_env_regenerate refills the records in place from other seeds -- no host instance set, no instance upload, no device allocation --
  * and leaves every env as a create leaves it (done; env random streams restarted from rng_seed; recorded schedule cleared).
- * One order only: prm->S > 1 and FJSP_VARIANT_MO_DFJSP are FJSP_E_UNSUPPORTED (they need the per-env fluid tables and
- * machine data).  Bad parameters (the checks of fjsp_instances_generate), an unknown variant, n_inst <= 0 or n_envs <= 0:
+ * One order only: prm->S > 1 and FJSP_VARIANT_MO_DFJSP are FJSP_E_UNSUPPORTED here (several orders:
+ * fjsp_env_create_generated_orders below; MO_DFJSP needs machine data, which the generator does not draw).  Bad parameters (the checks of fjsp_instances_generate), an unknown variant, n_inst <= 0 or n_envs <= 0:
  * FJSP_E_ARG; a worst case outside the kernels' limits: FJSP_E_UNSUPPORTED; all before the first HIP call.
  * An LP whose tableau fits the LDS of a CU is solved by the device simplex, the others by the host's on
  * fjsp_env_set_lp_threads threads; FJSP_LP_IMPL=host sends all to the host, =device refuses (FJSP_E_UNSUPPORTED) when one
@@ -210,6 +231,27 @@ int  fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32
  * base; FJSP_E_UNSUPPORTED: M_max > 32, base.S > 1, MO_DFJSP, a worst case outside the kernels' limits; all before the
  * first HIP call, the message naming the bound. */
 int  fjsp_env_create_generated_ranges(const fjsp_gen_ranges *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
+                                      uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out);
+/* ... and with the number of orders drawn per instance (fjsp_gen_orders): instance i is what
+ * fjsp_instances_generate_orders(seed_base + i, q) + fjsp_instances_solve_fluid + fjsp_env_create_family give, record for
+ * record, x bit for bit.  The generator kernel restates the host generator for S orders: the S x R job counts order-major,
+ * then the S - 1 arrival intervals, arrival times as truncated running sums, delivery times arrive + gap sorted ascending.
+ * The handle is sized for S_max, M_max and the worst case (R_max N_max S_max jobs, R_max J_max N_max S_max operations); it
+ * is a multi-order handle -- per-env fluid tables, order-arrival LPs -- iff S_max > 1, and an instance that drew S = 1 plays
+ * on it as a one-order instance.  The arrival service (device simplex in LDS, in global memory, or the host) is chosen
+ * once, at create, from the parameters' worst tableau (R_max kinds of J_max operations, every pair eligible on M_max
+ * machines) by the rule of fjsp_env_create and FJSP_LP_IMPL; a host or asynchronous service reads a host mirror of the
+ * records' heads that every fjsp_env_regenerate refills.  fjsp_env_regenerate on such a handle is FJSP_E_STATE while envs
+ * are parked in the asynchronous service; it empties the memo of solved arrival LPs and leaves fjsp_env_lp_solves and the
+ * device pivot counters running.  fjsp_env_instance_read gives dims[3] = the instance's own S, count[S * R], arrive[S],
+ * delivery[S]; fjsp_env_generated_stats*, snapshots (the fingerprint also mixes a tag, S_min, S_max and the interval
+ * bounds) and schedule recording work as on the other generated handles; the policy launches refuse a multi-order handle.
+ * FJSP_VARIANT_SO_FJSSP and _SO_DFJSP for any S_max; _SO_SFJSP and _MO_FJSSP_DISCRETES only with S_max == 1 (then as
+ * fjsp_env_create_generated_ranges), else FJSP_E_UNSUPPORTED; _MO_DFJSP: FJSP_E_UNSUPPORTED.  FJSP_E_ARG: the bounds
+ * fjsp_gen_draw_orders refuses and those of fjsp_env_create_generated_ranges; FJSP_E_UNSUPPORTED: S_max >
+ * FJSP_GEN_MAX_ORDERS, a worst case outside the kernels' limits (the 32-bit clock bound counts the last arrival,
+ * (S_max - 1) t_si_max, and the work of all orders); all before the first HIP call, the message naming the bound. */
+int  fjsp_env_create_generated_orders(const fjsp_gen_orders *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
                                       uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out);
 int  fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed);
 /* Of the last create_generated / regenerate: out[0] instances, [1] LPs solved on the device, [2] on the host, [3] pivots

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """What a training loop spends on the NEXT batch of instances: the host path against a regenerate on the device.
 
-    python tools/time_regenerate.py [--reps 5] [--out profiles/regenerate_timing.jsonl] [--ranges mpppo|ddqn] [--envs 4096]
-                                    [--lp-impl host|device|global]
+    python tools/time_regenerate.py [--reps 5] [--out profiles/regenerate_timing.jsonl] [--ranges mpppo|ddqn] [--orders da3c|hmpsac]
+                                    [--envs 4096] [--lp-impl host|device|global]
 
 For 4096 and 32768 bench_10x5_params instances and 4096 of reference_generator_params(1.0, 10, 1), alternately in one
 process, wall clock between device synchronisations:
@@ -11,7 +11,8 @@ process, wall clock between device synchronisations:
 Each repetition uses seeds of its own (the same for (a) and (b)).  Prints one JSON line per (workload, path) with every
 repetition, median [min, max], and for (b) the library's own split (generated_stats()["ms"], medians) and LP routes.
 --ranges NAME times instances.reference_training_ranges(NAME) instead (M and DDT drawn per instance), --envs of them;
---envs alone times that many 10x5 instances.  --lp-impl sets FJSP_LP_IMPL around the create of the live handle (the
+--orders NAME times instances.reference_order_ranges(NAME) (the number of orders drawn too: a multi-order handle; the
+reset alone plays no order arrival, so the arrival service is not in the figure); --envs alone times that many 10x5 instances.  --lp-impl sets FJSP_LP_IMPL around the create of the live handle (the
 library reads it there and nowhere else) and is recorded in the device line.
 """
 import argparse
@@ -50,7 +51,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     ap.add_argument("--ranges", choices=("mpppo", "ddqn"), default=None, help="the reference's training distribution instead of the three workloads")
-    ap.add_argument("--envs", type=int, default=None, help="instances of the --ranges workload (4096), or of a single 10x5 workload")
+    ap.add_argument("--orders", choices=("da3c", "hmpsac"), default=None, help="the reference's multi-order training distribution instead")
+    ap.add_argument("--envs", type=int, default=None, help="instances of the --ranges / --orders workload (4096), or of a single 10x5 workload")
     ap.add_argument("--lp-impl", choices=("host", "device", "global"), default=None, help="FJSP_LP_IMPL of the live handle (default: not set)")
     args = ap.parse_args()
     import torch
@@ -59,7 +61,11 @@ def main():
 
     workloads = [("10x5", fi.bench_10x5_params(), 4096), ("10x5", fi.bench_10x5_params(), 32768),
                  ("reference M=10", fi.reference_generator_params(1.0, 10, 1), 4096)]
-    if args.ranges:
+    if args.ranges and args.orders:
+        ap.error("--ranges and --orders are two workloads: give one")
+    if args.orders:
+        workloads = [("orders " + args.orders, fi.reference_order_ranges(args.orders), args.envs or 4096)]
+    elif args.ranges:
         workloads = [("ranges " + args.ranges, fi.reference_training_ranges(args.ranges), args.envs or 4096)]
     elif args.envs:
         workloads = [("10x5", fi.bench_10x5_params(), args.envs)]
