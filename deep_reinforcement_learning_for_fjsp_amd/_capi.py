@@ -43,6 +43,22 @@ class GenOrders(C.Structure):
     _fields_ = [("r", GenRanges), ("S_min", _i32), ("S_max", _i32)]
 
 
+class GenMachine(C.Structure):
+    """fjsp_gen_machine: the machine data of an MO_DFJSP shop -- processing power per eligible pair, idle power per machine,
+    up to W_max breakdown windows per machine, each a gap of working time and a length."""
+    _fields_ = [("pw_min", _i32), ("pw_max", _i32), ("idle_min", _i32), ("idle_max", _i32), ("W_max", _i32),
+                ("gap_min", _i32), ("gap_max", _i32), ("len_min", _i32), ("len_max", _i32)]
+
+
+class GenDynamic(C.Structure):
+    """fjsp_gen_dynamic: GenDynamic(o, m, redraws) -- a GenOrders, a GenMachine and the number of further attempts for an
+    instance with a machine that no operation is eligible on (0 ... FJSP_GEN_MAX_REDRAWS)."""
+    _fields_ = [("o", GenOrders), ("m", GenMachine), ("redraws", _i32)]
+
+
+FJSP_GEN_MAX_WINDOWS, FJSP_GEN_MAX_REDRAWS = 2047, 16
+
+
 class ActorParams(C.Structure):
     """fjsp_actor_params: device pointers to the f32 parameters of a state_size -> 128 -> 128 -> n_actions actor."""
     _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w3", _vp), ("b3", _vp),
@@ -61,6 +77,9 @@ SIGNATURES = {
     "fjsp_instances_generate_drawn": (C.c_int, [_vp, _i32, _u64, C.POINTER(GenRanges)]),
     "fjsp_gen_draw_orders": (C.c_int, [C.POINTER(GenOrders), _u64, C.POINTER(GenParams)]),
     "fjsp_instances_generate_orders": (C.c_int, [_vp, _i32, _u64, C.POINTER(GenOrders)]),
+    "fjsp_gen_dynamic_seed": (C.c_int, [C.POINTER(GenDynamic), _u64, C.POINTER(_u64)]),
+    "fjsp_gen_draw_dynamic": (C.c_int, [C.POINTER(GenDynamic), _u64, C.POINTER(GenParams)]),
+    "fjsp_instances_generate_dynamic": (C.c_int, [_vp, _i32, _u64, C.POINTER(GenDynamic)]),
     "fjsp_instances_set_raw": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl]),
     "fjsp_instances_dims": (C.c_int, [_vp, _i32, C.POINTER(_i32 * 6)]),
     "fjsp_instances_get": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_dbl), _vp]),
@@ -75,6 +94,8 @@ SIGNATURES = {
     "fjsp_env_create_generated": (C.c_int, [C.POINTER(GenParams), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
     "fjsp_env_create_generated_ranges": (C.c_int, [C.POINTER(GenRanges), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
     "fjsp_env_create_generated_orders": (C.c_int, [C.POINTER(GenOrders), _i32, _i32, _i32, _i32, _u64, _i32, _u64, _pp]),
+    "fjsp_env_create_generated_dynamic": (C.c_int, [C.POINTER(GenDynamic), _i32, _i32, _i32, _u64, _u64, _pp]),
+    "fjsp_env_instance_read_dynamic": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_i32 * 2)]),
     "fjsp_env_regenerate": (C.c_int, [_vp, _u64, _u64]),
     "fjsp_env_generated_stats": (C.c_int, [_vp, C.POINTER(_i64 * 4)]),
     "fjsp_env_generated_times": (C.c_int, [_vp, C.POINTER(_dbl * 5)]),

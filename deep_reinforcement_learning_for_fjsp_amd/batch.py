@@ -221,7 +221,10 @@ class EnvBatch(object):
         LPs served as lp_on_device says).  first_env shifts the instance seeds and the env random streams alike, so a
         shard [first_env, first_env + n_envs) is a slice of the one-GPU batch.  There is no InstanceSet (`instances` is
         None; instance_arrays(i) reads an instance back); regenerate() refills the batch in place.  Several orders only
-        through GenOrders, and then VARIANT_SO_FJSSP / VARIANT_SO_DFJSP; never VARIANT_MO_DFJSP: FjspError(FJSP_E_UNSUPPORTED)."""
+        through GenOrders, and then VARIANT_SO_FJSSP / VARIANT_SO_DFJSP.  VARIANT_MO_DFJSP only with a GenDynamic
+        (fjsp_env_create_generated_dynamic: the machine data are generated too, an unplayable instance is drawn again;
+        instance_arrays(i) then carries power, idle_power, bk_n, bk and seed_used) and a GenDynamic only with it; with any
+        other parameters FjspError(FJSP_E_UNSUPPORTED)."""
         if not torch.cuda.is_available():
             raise RuntimeError("EnvBatch needs an MI355X: the environment kernels have no CPU path")
         if family not in (-1, 0, 1):
@@ -237,11 +240,19 @@ class EnvBatch(object):
         self.first_env, self.first = int(first_env), 0
         self.gen_params, self.seed_base, self.family = params, int(seed_base), int(family)
         mask = 2 ** 64 - 1
+        lib_seed, lib_base = (int(rng_seed) + self.first_env * ENV_SEED_STRIDE) & mask, (self.seed_base + self.first_env) & mask
+        if isinstance(params, _capi.GenDynamic):
+            if int(variant) != VARIANT_MO_DFJSP:
+                raise _capi.FjspError(_capi.FJSP_E_UNSUPPORTED, "EnvBatch.generated: a GenDynamic makes VARIANT_MO_DFJSP batches only")
+            if family == 1:
+                raise _capi.FjspError(_capi.FJSP_E_UNSUPPORTED, "EnvBatch.generated: the row kernels do not play MO_DFJSP")
+            check(self._lib.fjsp_env_create_generated_dynamic(C.byref(params), n_inst, int(n_envs), self.device_index, lib_seed, lib_base,
+                                                              C.byref(self._h)))
+            self._bind(n_envs, n_inst, variant, rng_seed)
+            return self
         create = (self._lib.fjsp_env_create_generated_orders if isinstance(params, _capi.GenOrders) else
                   self._lib.fjsp_env_create_generated_ranges if isinstance(params, _capi.GenRanges) else self._lib.fjsp_env_create_generated)
-        check(create(C.byref(params), n_inst, int(n_envs), int(variant), self.device_index,
-                     (int(rng_seed) + self.first_env * ENV_SEED_STRIDE) & mask, int(family),
-                     (self.seed_base + self.first_env) & mask, C.byref(self._h)))
+        check(create(C.byref(params), n_inst, int(n_envs), int(variant), self.device_index, lib_seed, int(family), lib_base, C.byref(self._h)))
         self._bind(n_envs, n_inst, variant, rng_seed)
         return self
 
@@ -287,7 +298,16 @@ class EnvBatch(object):
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)
         check(self._lib.fjsp_env_instance_read(self._h, int(i), None, ptr(Jr), ptr(p), ptr(elig_n), ptr(elig_list), ptr(count),
                                                ptr(arrive), ptr(delivery), C.byref(ddt), ptr(x)))
-        return InstanceArrays(R, M, K, S, Jr, p, elig_n, elig_list, count, arrive, delivery, ddt.value, x)
+        out = InstanceArrays(R, M, K, S, Jr, p, elig_n, elig_list, count, arrive, delivery, ddt.value, x)
+        if isinstance(self.gen_params, _capi.GenDynamic):       # the machine data and the seed the instance was made of
+            dd, used = (C.c_int32 * 2)(), C.c_uint64()
+            check(self._lib.fjsp_env_instance_read_dynamic(self._h, int(i), None, None, None, None, None, C.byref(dd)))
+            out.power, out.idle_power, out.bk_n = np.zeros((K, M), np.int32), np.zeros(M, np.int32), np.zeros(M, np.int32)
+            out.bk = np.zeros((max(dd[1], 1), 2), np.int32)
+            check(self._lib.fjsp_env_instance_read_dynamic(self._h, int(i), ptr(out.power), ptr(out.idle_power), ptr(out.bk_n), ptr(out.bk),
+                                                           C.byref(used), None))
+            out.bk, out.seed_used = out.bk[:dd[1]], int(used.value)
+        return out
 
     def generated_stats(self):
         """Of the last generated() / regenerate(): dict(instances, lp_device, lp_host, device_pivots, lp_global,
@@ -614,7 +634,8 @@ class EnvBatch(object):
     def machine_time_end(self):
         if self.instances is None:
             g = self.gen_params
-            mp = int(g.r.M_max if isinstance(g, _capi.GenOrders) else g.M_max if isinstance(g, _capi.GenRanges) else g.M)
+            mp = int(g.o.r.M_max if isinstance(g, _capi.GenDynamic) else g.r.M_max if isinstance(g, _capi.GenOrders) else
+                     g.M_max if isinstance(g, _capi.GenRanges) else g.M)
         else:
             d = self.instances.dims(self.first)
             mp = max(self.instances.dims(self.first + i)["M"] for i in range(self.n_inst)) if self.n_inst > 1 else d["M"]

@@ -25,6 +25,12 @@
 // FJSP_GEN_MAX_ORDERS delivery times.  The handle is then a multi-order one: its arrival service (fjsp_arrivals.hip) is
 // chosen at create from the parameters' worst tableau and, where it runs on the host, reads fjsp_env::lp_mirror, the
 // records' heads that refresh_lp_mirror gathers after every refill.
+//
+// MO_DFJSP (fjsp_env_create_generated_dynamic): the same kernel built with its redraw loop -- an attempt whose shop leaves a
+// machine without an eligible operation is drawn again from the next seed of the instance's redraw stream, at most
+// GenDynArgs::redraws times -- and generate_machine_kernel behind it: the powers, idle powers and breakdown windows of the
+// seed the instance was made of, every draw at a position that is a function of its indices (fjsp_gen_machine), so the
+// lanes need no chain but the running end of a machine's own windows.  The other handles launch neither.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -85,6 +91,15 @@ struct GenArgs {
     uint16_t *lp_in_glob;    // [slot of glob_ids][2][KP]
 };
 
+// What a dynamic handle's kernels take beside GenArgs (whose class_fjsp is 1 there: MO_DFJSP shares SO_DFJSP's due dates and
+// its need of an operation on every machine)
+struct GenDynArgs {
+    fjsp_gen_machine mc;
+    int32_t redraws;         // further attempts for an instance with an idle machine, at most FJSP_GEN_MAX_REDRAWS
+    int32_t windows;         // window pairs a record's i_bk holds (Shape::B = M_max x W_max)
+    uint64_t *seed_used;     // [n_inst] the seed the instance was made of
+};
+
 constexpr int kGenMaxK = kWave * kMaxKC;
 
 namespace {
@@ -114,8 +129,10 @@ __device__ inline double gen_uniform(uint64_t seed, uint32_t i, double lo, doubl
 constexpr int kGenMaxS = FJSP_GEN_MAX_ORDERS;
 }  // namespace
 
-// One wave per instance.
-__global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArgs a) {
+// One wave per instance.  DYN (a dynamic handle, d given): the shop is drawn again, from the next seed of the instance's
+// redraw stream, while it leaves a machine idle and attempts remain; without DYN there is one attempt and no loop is compiled.
+template <bool DYN>
+__device__ __forceinline__ void generate_pack(const DevBatch &b, const GenArgs &a, const GenDynArgs *d) {
     __shared__ uint8_t s_el[kGenMaxK * kMaxM];       // the shuffle of operation type k, then its eligible list
     __shared__ uint16_t s_p[kGenMaxK * kMaxM];       // p[k][m], 0 = ineligible
     __shared__ double s_tr[kGenMaxK];                // time_rj: mean processing time over the eligible list
@@ -130,110 +147,121 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
     const int inst = (int)blockIdx.x, l = (int)threadIdx.x;
     if (inst >= b.n_inst) return;
     const fjsp_gen_params &g = a.g;
-    const uint64_t seed = a.seed_base + (uint64_t)inst;
-    const int M = gen_machines(a, seed), MP = b.MP, KP = b.KP, S = gen_orders(a, seed);
-    const double DDT = gen_ddt(a, seed);
+    const uint64_t seed0 = a.seed_base + (uint64_t)inst;
+    const int MP = b.MP, KP = b.KP;
     unsigned char *rec = b.inst + (size_t)inst * b.L.i_stride;
     const Layout &L = b.L;
-
-    // ---- R, J_r, the kinds' first operation types
-    const int R = gen_randint(seed, 0u, g.R_min, g.R_max);                                       // :42
-    const bool r_ok = R >= 1 && R <= a.RP && R <= kGenMaxK && M >= 1 && M <= MP && M <= kMaxM && S >= 1 && S <= b.SP && S <= kGenMaxS;
-    for (int r = l; r_ok && r < R; r += kWave) s_Jr[r] = (uint8_t)gen_randint(seed, 1u + (uint32_t)r, g.J_min, g.J_max);   // :46,71
-    __syncthreads();
-    if (l == 0) {
-        int K = 0, st = r_ok ? 0 : FJSP_E_FORMAT;
-        for (int r = 0; st == 0 && r < R; ++r) {
-            const int J = s_Jr[r];
-            if (J < 1 || K + J > KP || K + J > a.kmax) { st = FJSP_E_FORMAT; break; }
-            s_koff[r] = (uint16_t)K;
-            for (int j = 0; j < J; ++j) { s_rk[K + j] = (uint16_t)r; s_jk[K + j] = (uint8_t)j; }
-            K += J;
+    const int redraws = DYN ? (d->redraws < FJSP_GEN_MAX_REDRAWS ? d->redraws : FJSP_GEN_MAX_REDRAWS) : 0;     // the loop's hard bound
+    uint64_t seed = seed0;
+    int M, S, R, K, nx, status, nj, delivery, ops_m;
+    double DDT;
+    for (int attempt = 0;; ++attempt) {
+        if (DYN && attempt > 0) {
+            seed = gen_draw(seed0 ^ FJSP_GEN_REDRAW_STREAM, (uint32_t)(attempt - 1));
+            __syncthreads();                         // the lanes have read the last attempt's shop
         }
-        if (st == 0) s_koff[R] = (uint16_t)K;
-        // the one serial chain: n of type k decides where type k + 1's draws start                 :73
-        uint32_t pos = 1u + (uint32_t)R, nx = 0;
-        for (int k = 0; st == 0 && k < K; ++k) {
-            const int n = gen_randint(seed, pos, 1, M);
-            if (n < 1 || n > M) { st = FJSP_E_FORMAT; break; }
-            s_n[k] = (uint8_t)n; s_off[k] = pos + 1u;
-            pos += 1u + (uint32_t)n;
-            nx += (uint32_t)n;
+        M = gen_machines(a, seed); S = gen_orders(a, seed); DDT = gen_ddt(a, seed);
+        // ---- R, J_r, the kinds' first operation types
+        R = gen_randint(seed, 0u, g.R_min, g.R_max);                                                 // :42
+        const bool r_ok = R >= 1 && R <= a.RP && R <= kGenMaxK && M >= 1 && M <= MP && M <= kMaxM && S >= 1 && S <= b.SP && S <= kGenMaxS;
+        for (int r = l; r_ok && r < R; r += kWave) s_Jr[r] = (uint8_t)gen_randint(seed, 1u + (uint32_t)r, g.J_min, g.J_max);   // :46,71
+        __syncthreads();
+        if (l == 0) {
+            int K = 0, st = r_ok ? 0 : FJSP_E_FORMAT;
+            for (int r = 0; st == 0 && r < R; ++r) {
+                const int J = s_Jr[r];
+                if (J < 1 || K + J > KP || K + J > a.kmax) { st = FJSP_E_FORMAT; break; }
+                s_koff[r] = (uint16_t)K;
+                for (int j = 0; j < J; ++j) { s_rk[K + j] = (uint16_t)r; s_jk[K + j] = (uint8_t)j; }
+                K += J;
+            }
+            if (st == 0) s_koff[R] = (uint16_t)K;
+            // the one serial chain: n of type k decides where type k + 1's draws start                 :73
+            uint32_t pos = 1u + (uint32_t)R, nx = 0;
+            for (int k = 0; st == 0 && k < K; ++k) {
+                const int n = gen_randint(seed, pos, 1, M);
+                if (n < 1 || n > M) { st = FJSP_E_FORMAT; break; }
+                s_n[k] = (uint8_t)n; s_off[k] = pos + 1u;
+                pos += 1u + (uint32_t)n;
+                nx += (uint32_t)n;
+            }
+            uint32_t q = pos;                                                                          // :74 draws follow all shuffles
+            for (int k = 0; st == 0 && k < K; ++k) { s_poff[k] = q; q += s_n[k]; }
+            s_hdr[0] = R; s_hdr[1] = K; s_hdr[2] = st; s_hdr[3] = (int)nx; s_hdr[4] = (int)q;
         }
-        uint32_t q = pos;                                                                          // :74 draws follow all shuffles
-        for (int k = 0; st == 0 && k < K; ++k) { s_poff[k] = q; q += s_n[k]; }
-        s_hdr[0] = R; s_hdr[1] = K; s_hdr[2] = st; s_hdr[3] = (int)nx; s_hdr[4] = (int)q;
+        __syncthreads();
+        K = s_hdr[1]; nx = s_hdr[3];
+        status = s_hdr[2];
+        if (status != 0) {
+            if (l == 0) a.info[inst] = GenInfo{status, 0, 0, 0, 0, 0, 0, 0, M, S, DDT};
+            return;
+        }
+        // ---- per operation type: choice(M, n, replace=False) as a Fisher-Yates prefix, then the processing times
+        for (int k = l; k < K; k += kWave) {
+            uint8_t *perm = s_el + k * kMaxM;
+            uint16_t *pk = s_p + k * kMaxM;
+            const int n = s_n[k];
+            for (int m = 0; m < M; ++m) { perm[m] = (uint8_t)m; pk[m] = 0; }
+            for (int i = 0; i < n; ++i) {
+                int j = gen_randint(seed, s_off[k] + (uint32_t)i, i, M - 1);
+                j = j < i ? i : (j > M - 1 ? M - 1 : j);
+                const uint8_t t = perm[i]; perm[i] = perm[j]; perm[j] = t;
+            }
+            long sum = 0;
+            for (int i = 0; i < n; ++i) {
+                const int pv = gen_randint(seed, s_poff[k] + (uint32_t)i, g.p_min, g.p_max);
+                pk[perm[i]] = (uint16_t)pv;
+                sum += pv;
+            }
+            for (int m = n; m < M; ++m) perm[m] = 0;
+            s_tr[k] = (double)sum / (double)n;                                                         // :78
+        }
+        // the S x R job counts, order-major, behind the processing times; the S - 1 arrival intervals behind them       :80, :83-84
+        for (int q = l; q < S * R; q += kWave)
+            s_cnt[(q / R) * kGenMaxK + q % R] = (uint16_t)gen_randint(seed, (uint32_t)s_hdr[4] + (uint32_t)q, g.N_min, g.N_max);
+        __syncthreads();
+        if (l < S) {
+            // order l: its gap strictly left to right over the operation types (:81-82); its arrival time the truncated running
+            // sum of the intervals, accumulated from order 0 again (:85-86; interval[0] = 0.0)
+            double acc = 0.0;
+            for (int k = 0; k < K; ++k) acc = acc + s_tr[k] * (double)s_cnt[l * kGenMaxK + s_rk[k]];
+            const double gap = acc * DDT / (double)(M * 2);
+            double t = 0.0;                              // (0.0 + interval[0] is 0.0)
+            for (int q = 1; q <= l; ++q) t = t + gen_uniform(seed, (uint32_t)s_hdr[4] + (uint32_t)(S * R) + (uint32_t)(q - 1), g.t_si_min, g.t_si_max);
+            s_arr[l] = (int)t;
+            s_dl[l] = (double)s_arr[l] + gap;
+        }
+        __syncthreads();
+        if (l == 0) {
+            int nj = 0, ops = 0;
+            for (int r = 0; r < R; ++r) {
+                int tot = 0;
+                for (int so = 0; so < S; ++so) tot += s_cnt[so * kGenMaxK + r];
+                s_jbeg[r] = (uint16_t)nj; s_tot[r] = (uint16_t)tot; nj += tot; ops += tot * (int)s_Jr[r];
+            }
+            s_jbeg[R] = (uint16_t)nj;
+            // :87-88 the delivery times sorted ascending, then truncated: an insertion sort (S <= 16; equal keys are equal values)
+            for (int i = 1; i < S; ++i) {
+                const double v = s_dl[i];
+                int j = i - 1;
+                for (; j >= 0 && s_dl[j] > v; --j) s_dl[j + 1] = s_dl[j];
+                s_dl[j + 1] = v;
+            }
+            for (int so = 0; so < S; ++so) s_del[so] = (int)s_dl[so];
+            s_hdr[5] = nj; s_hdr[6] = s_del[0]; s_hdr[7] = ops;
+            if (nj > b.JP || nj > 65535) s_hdr[2] = FJSP_E_FORMAT;
+        }
+        __syncthreads();
+        nj = s_hdr[5]; delivery = s_hdr[6];
+        status = s_hdr[2];
+        // SO_DFJSP and MO_DFJSP divide by the number of operation types of every machine (check_instance, fjsp_env.hip)
+        ops_m = 0;
+        if (l < M)
+            for (int k = 0; k < K; ++k) ops_m += s_p[k * kMaxM + l] > 0 ? 1 : 0;
+        if (a.class_fjsp && __any(l < M && ops_m == 0) && status == 0) status = FJSP_E_UNSUPPORTED;
+        if (!DYN || status != FJSP_E_UNSUPPORTED || attempt >= redraws) break;
     }
-    __syncthreads();
-    const int K = s_hdr[1], nx = s_hdr[3];
-    int status = s_hdr[2];
-    if (status != 0) {
-        if (l == 0) a.info[inst] = GenInfo{status, 0, 0, 0, 0, 0, 0, 0, M, S, DDT};
-        return;
-    }
-    // ---- per operation type: choice(M, n, replace=False) as a Fisher-Yates prefix, then the processing times
-    for (int k = l; k < K; k += kWave) {
-        uint8_t *perm = s_el + k * kMaxM;
-        uint16_t *pk = s_p + k * kMaxM;
-        const int n = s_n[k];
-        for (int m = 0; m < M; ++m) { perm[m] = (uint8_t)m; pk[m] = 0; }
-        for (int i = 0; i < n; ++i) {
-            int j = gen_randint(seed, s_off[k] + (uint32_t)i, i, M - 1);
-            j = j < i ? i : (j > M - 1 ? M - 1 : j);
-            const uint8_t t = perm[i]; perm[i] = perm[j]; perm[j] = t;
-        }
-        long sum = 0;
-        for (int i = 0; i < n; ++i) {
-            const int pv = gen_randint(seed, s_poff[k] + (uint32_t)i, g.p_min, g.p_max);
-            pk[perm[i]] = (uint16_t)pv;
-            sum += pv;
-        }
-        for (int m = n; m < M; ++m) perm[m] = 0;
-        s_tr[k] = (double)sum / (double)n;                                                         // :78
-    }
-    // the S x R job counts, order-major, behind the processing times; the S - 1 arrival intervals behind them       :80, :83-84
-    for (int q = l; q < S * R; q += kWave)
-        s_cnt[(q / R) * kGenMaxK + q % R] = (uint16_t)gen_randint(seed, (uint32_t)s_hdr[4] + (uint32_t)q, g.N_min, g.N_max);
-    __syncthreads();
-    if (l < S) {
-        // order l: its gap strictly left to right over the operation types (:81-82); its arrival time the truncated running
-        // sum of the intervals, accumulated from order 0 again (:85-86; interval[0] = 0.0)
-        double acc = 0.0;
-        for (int k = 0; k < K; ++k) acc = acc + s_tr[k] * (double)s_cnt[l * kGenMaxK + s_rk[k]];
-        const double gap = acc * DDT / (double)(M * 2);
-        double t = 0.0;                              // (0.0 + interval[0] is 0.0)
-        for (int q = 1; q <= l; ++q) t = t + gen_uniform(seed, (uint32_t)s_hdr[4] + (uint32_t)(S * R) + (uint32_t)(q - 1), g.t_si_min, g.t_si_max);
-        s_arr[l] = (int)t;
-        s_dl[l] = (double)s_arr[l] + gap;
-    }
-    __syncthreads();
-    if (l == 0) {
-        int nj = 0, ops = 0;
-        for (int r = 0; r < R; ++r) {
-            int tot = 0;
-            for (int so = 0; so < S; ++so) tot += s_cnt[so * kGenMaxK + r];
-            s_jbeg[r] = (uint16_t)nj; s_tot[r] = (uint16_t)tot; nj += tot; ops += tot * (int)s_Jr[r];
-        }
-        s_jbeg[R] = (uint16_t)nj;
-        // :87-88 the delivery times sorted ascending, then truncated: an insertion sort (S <= 16; equal keys are equal values)
-        for (int i = 1; i < S; ++i) {
-            const double v = s_dl[i];
-            int j = i - 1;
-            for (; j >= 0 && s_dl[j] > v; --j) s_dl[j + 1] = s_dl[j];
-            s_dl[j + 1] = v;
-        }
-        for (int so = 0; so < S; ++so) s_del[so] = (int)s_dl[so];
-        s_hdr[5] = nj; s_hdr[6] = s_del[0]; s_hdr[7] = ops;
-        if (nj > b.JP || nj > 65535) s_hdr[2] = FJSP_E_FORMAT;
-    }
-    __syncthreads();
-    const int nj = s_hdr[5], delivery = s_hdr[6];
-    status = s_hdr[2];
-    // SO_DFJSP divides by the number of operation types of every machine (check_instance, fjsp_env.hip)
-    int ops_m = 0;
-    if (l < M)
-        for (int k = 0; k < K; ++k) ops_m += s_p[k * kMaxM + l] > 0 ? 1 : 0;
-    if (a.class_fjsp && __any(l < M && ops_m == 0) && status == 0) status = FJSP_E_UNSUPPORTED;
+    if (DYN && l == 0) d->seed_used[inst] = seed;
     const uint32_t lds = lp_device_lds_bytes(K, M, nx, R, MP);
     if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[7], delivery, M, S, DDT};
     if (status != 0) return;
@@ -320,6 +348,52 @@ __global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArg
             Q[KP + k] = s_jk[k] == 0 ? c : (uint16_t)0;
         }
     }
+}
+
+__global__ __launch_bounds__(kWave) void generate_pack_kernel(DevBatch b, GenArgs a) { generate_pack<false>(b, a, nullptr); }
+__global__ __launch_bounds__(kWave) void generate_pack_dynamic_kernel(DevBatch b, GenArgs a, GenDynArgs d) { generate_pack<true>(b, a, &d); }
+
+// One wave per instance of a dynamic handle, behind generate_pack_dynamic_kernel: the machine data of the seed the instance was
+// made of into the record, as pack_instance writes them (i_pw, i_ipw, i_bkoff, i_bk; the due-date tightness in front of
+// the static state row).  K, M and the eligible pairs are the record's.
+__global__ __launch_bounds__(kWave) void generate_machine_kernel(DevBatch b, GenArgs a, GenDynArgs d) {
+    __shared__ uint16_t s_w[kMaxM];                  // windows of machine m
+    const int inst = (int)blockIdx.x, l = (int)threadIdx.x;
+    if (inst >= b.n_inst || a.info[inst].status != 0) return;
+    unsigned char *rec = b.inst + (size_t)inst * b.L.i_stride;
+    const InstHeader h = *reinterpret_cast<const InstHeader *>(rec);
+    const int K = h.K, M = h.M, MP = b.MP, W = d.mc.W_max;
+    if (K < 1 || K > b.KP || M < 1 || M > MP || MP > kMaxM || W < 0 || M * W > d.windows) return;     // (generate_pack's own checks; the size of i_bk)
+    const uint64_t ms = d.seed_used[inst] ^ FJSP_GEN_MACHINE_STREAM;
+    const uint16_t *p = reinterpret_cast<const uint16_t *>(rec + b.L.i_p);
+    uint16_t *pw = reinterpret_cast<uint16_t *>(rec + b.L.i_pw);
+    for (int q = l; q < K * M; q += kWave) {
+        const size_t at = (size_t)(q / M) * MP + q % M;
+        pw[at] = p[at] > 0 ? (uint16_t)gen_randint(ms, (uint32_t)(2 * M + q), d.mc.pw_min, d.mc.pw_max) : (uint16_t)0;
+    }
+    if (l < M) {
+        reinterpret_cast<int32_t *>(rec + b.L.i_ipw)[l] = gen_randint(ms, (uint32_t)l, d.mc.idle_min, d.mc.idle_max);
+        const int n = gen_randint(ms, (uint32_t)(M + l), 0, W);
+        s_w[l] = (uint16_t)(n < 0 ? 0 : (n > W ? W : n));
+    }
+    __syncthreads();
+    if (l <= MP) {
+        // the first window of machine l: the windows of the machines in front of it (i_bkoff[MP] = all of them)
+        int off = 0;
+        for (int m = 0; m < l && m < M; ++m) off += s_w[m];
+        reinterpret_cast<uint16_t *>(rec + b.L.i_bkoff)[l] = (uint16_t)off;
+        if (l < M) {
+            int32_t *bk = reinterpret_cast<int32_t *>(rec + b.L.i_bk) + 2 * off;
+            int t = 0;
+            for (int w = 0; w < (int)s_w[l]; ++w) {
+                const uint32_t pos = (uint32_t)(2 * M + K * M + 2 * (l * W + w));
+                const int st = t + gen_randint(ms, pos, d.mc.gap_min, d.mc.gap_max);
+                t = st + gen_randint(ms, pos + 1u, d.mc.len_min, d.mc.len_max);
+                bk[2 * w] = st; bk[2 * w + 1] = t;
+            }
+        }
+    }
+    if (l == 0) reinterpret_cast<double *>(rec + b.L.i_ss)[0] = a.info[inst].ddt;      // observation[0] = self.DDT
 }
 
 // One wave per listed instance: x from its staging slot into the record, then the static state row (pack_static_state).
@@ -427,6 +501,9 @@ struct GenReadback { LpCounters lds, glob; LpErrWord lp_err; };  // pinned: what
 
 struct GenState {
     GenArgs a{};
+    bool dynamic = false;                // made by fjsp_env_create_generated_dynamic: d is in use
+    GenDynArgs d{};
+    uint64_t *h_seed_used = nullptr;     // pinned [n_inst], dynamic handles
     LpRoute route[kGenRoutes];
     int chunk = 0;                       // staging slots of one LP launch / one host-route round
     int head16 = 0;                      // 16-byte words of a record in front of x
@@ -471,7 +548,8 @@ int check_params(const fjsp_gen_params &g) {
 // check_instance (fjsp_env.hip) on the worst case of the parameters, sizes into sh.  Over M in M_min..M_max and |DDT| up to
 // ddt_max: sizes from M_max, the largest delivery time from ddt_max / (2 M_min)
 // With S_max > 1 orders: jobs, operations and the clock count all of them, the clock starts from the last arrival
-int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_max, int S_max, Shape &sh) {
+// mc != nullptr (MO_DFJSP): every breakdown window stretches the clock (the bk_total term of check_instance)
+int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_max, int S_max, const fjsp_gen_machine *mc, Shape &sh) {
     const long long K = (long long)g.R_max * g.J_max, nj = (long long)g.R_max * g.N_max * S_max, ops = K * g.N_max * S_max;
     if (S_max > 1) {
         if (nj > 65535) { set_error("generated instances can have more than 65535 jobs (R_max x N_max x S_max)"); return FJSP_E_UNSUPPORTED; }
@@ -489,9 +567,13 @@ int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_
     // that, the work of all orders follows the last arrival, and a kind has N_max jobs in every order)
     const double arrive = S_max > 1 ? (double)(S_max - 1) * g.t_si_max : 0.0;
     const double due = arrive + std::fabs((double)K * (double)g.p_max * (double)g.N_max * ddt_max / (double)(M_min * 2));
-    const double clock = arrive + (double)ops * (double)g.p_max;
+    const double windows = mc ? (double)M_max * (double)mc->W_max * (double)mc->len_max : 0.0;
+    const double clock = arrive + (double)ops * (double)g.p_max + windows;
     if (!(clock + due <= 2147483647.0) || !((double)g.N_max * (double)S_max * (clock + due) <= 2147483647.0)) {
-        set_error(S_max > 1 ? "generated instances can be too long for the kernels' 32-bit clocks: (last arrival (S_max - 1) x t_si_max + operations "
+        set_error(mc ? "generated instances can be too long for the kernels' 32-bit clocks: (last arrival (S_max - 1) x t_si_max + operations "
+                       "of all orders x max processing time + every breakdown window M_max x W_max x len_max + largest delivery time) x jobs "
+                       "per kind (N_max x S_max) must stay below 2^31"
+                  : S_max > 1 ? "generated instances can be too long for the kernels' 32-bit clocks: (last arrival (S_max - 1) x t_si_max + operations "
                               "of all orders x max processing time + largest delivery time) x jobs per kind (N_max x S_max) must stay below 2^31"
                             : "generated instances can be too long for the kernels' 32-bit clocks: (operations x max processing time + "
                               "largest delivery time) x jobs per kind must stay below 2^31; the largest delivery time grows with DDT (DDT_max) "
@@ -499,11 +581,15 @@ int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_
         return FJSP_E_UNSUPPORTED;
     }
     sh.K = (int)K; sh.M = M_max; sh.J = (int)nj; sh.R = g.R_max; sh.S = S_max;
+    if (mc) {
+        if ((long long)M_max * mc->W_max > 65535) { set_error("generated instances can have more than 65535 breakdown windows (M_max x W_max)"); return FJSP_E_UNSUPPORTED; }
+        sh.B = std::max(1, M_max * mc->W_max);
+    }
     sh.single_job = g.N_min == 1 && g.N_max == 1 && g.R_max <= 255;
     return FJSP_OK;
 }
 
-uint64_t gen_hash(const GenArgs &a, int n_inst, uint64_t seed_base) {
+uint64_t gen_hash(const GenArgs &a, const GenDynArgs *d, int n_inst, uint64_t seed_base) {
     const fjsp_gen_params &g = a.g;
     const int class_fjsp = a.class_fjsp;
     uint64_t h = 1469598103934665603ULL;
@@ -524,6 +610,10 @@ uint64_t gen_hash(const GenArgs &a, int n_inst, uint64_t seed_base) {
         const int32_t ov[3] = {0x4F524453, a.S_min, a.S_max};
         const double od[2] = {g.t_si_min, g.t_si_max};
         mix(ov, sizeof(ov)); mix(od, sizeof(od));
+    }
+    if (d) {            // likewise: a tag, the machine ranges and the redraw bound
+        const int32_t tag = 0x44594E4D;
+        mix(&tag, sizeof(tag)); mix(&d->mc, sizeof(d->mc)); mix(&d->redraws, sizeof(d->redraws));
     }
     return h;
 }
@@ -672,16 +762,24 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
     if (e->sched.rec) HIP_TRY(hipMemsetAsync(e->sched.rec, 0, (size_t)e->sched.cap * N * sizeof(uint4), st));
     // ---- pack
     HIP_TRY(hipEventRecord(G.ev_start, st));
-    if (launch(generate_pack_kernel, dim3((unsigned)n_inst), dim3(kWave), 0, st, b, G.a) != 0) return launch_failed("generate_pack_kernel launch failed");
+    if (G.dynamic) {
+        if (launch(generate_pack_dynamic_kernel, dim3((unsigned)n_inst), dim3(kWave), 0, st, b, G.a, G.d) != 0 ||
+            launch(generate_machine_kernel, dim3((unsigned)n_inst), dim3(kWave), 0, st, b, G.a, G.d) != 0)
+            return launch_failed("generate_pack_dynamic_kernel / generate_machine_kernel launch failed");
+    } else if (launch(generate_pack_kernel, dim3((unsigned)n_inst), dim3(kWave), 0, st, b, G.a) != 0) return launch_failed("generate_pack_kernel launch failed");
     HIP_TRY(hipEventRecord(G.ev_packed, st));
     // ---- the call's one read-back before the LPs: status words, sizes, the lists' lengths, the host list; validate
     HIP_TRY(hipMemcpyAsync(G.h_info, G.a.info, n_inst * sizeof(GenInfo), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, kGenCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(G.h_host_ids, G.a.host_ids, n_inst * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (G.dynamic) HIP_TRY(hipMemcpyAsync(G.h_seed_used, G.d.seed_used, n_inst * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     double bytes = 0.0;
     for (size_t i = 0; i < n_inst; ++i) {
         const GenInfo &f = G.h_info[i];
+        if (f.status == FJSP_E_UNSUPPORTED && G.dynamic)
+            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": MO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference) in each of " +
+                                 std::to_string(G.d.redraws + 1) + " attempts (redraws = " + std::to_string(G.d.redraws) + ")");
         if (f.status == FJSP_E_UNSUPPORTED)
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
         if (f.status != 0)
@@ -689,6 +787,7 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
         if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP || f.S < 1 || f.S > b.SP)
             return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": sizes disagree with the host's (internal error)");
         bytes += step_bytes(b, f.K, f.nj, f.M);
+        if (G.dynamic) bytes += f.M * 14.0 + 2.0 * sizeof(DynScalars);      // step_bytes_of (fjsp_env.hip)
     }
     size_t listed = 0;
     bool routed = true;      // no instance is on a list this handle has no route for
@@ -740,7 +839,7 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
         G.stats[kStatLpGlobal] = n_glob; G.stats[kStatGlobalPivots] = (int64_t)glob.h_solved->pivots;
         G.stats[kStatDevicePivots] += G.stats[kStatGlobalPivots];
     }
-    e->inst_hash = gen_hash(G.a, b.n_inst, seed_base);
+    e->inst_hash = gen_hash(G.a, G.dynamic ? &G.d : nullptr, b.n_inst, seed_base);
     if (b.mord) {
         // the memo of solved arrival LPs is keyed by the instance index, which names another instance now (the counters of
         // solved LPs and pivots keep running); the host services read the new records' heads
@@ -755,21 +854,23 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
 }
 
 // The three creates: q == nullptr is the fixed parameter set *prm; else *prm is q->base and M, DDT are drawn per instance;
-// o != nullptr: q is &o->r and the number of orders is drawn as well
-int create_generated(const std::string &call, const fjsp_gen_params *prm, const fjsp_gen_ranges *q, const fjsp_gen_orders *o, int32_t n_inst,
-                     int32_t n_envs, int32_t variant, int32_t device, uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
+// o != nullptr: q is &o->r and the number of orders is drawn as well; dq != nullptr (fjsp_env_create_generated_dynamic): o is
+// &dq->o, the variant is MO_DFJSP and the machine data are drawn too
+int create_generated(const std::string &call, const fjsp_gen_params *prm, const fjsp_gen_ranges *q, const fjsp_gen_orders *o, const fjsp_gen_dynamic *dq,
+                     int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device, uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
     if (!prm || !out || n_inst <= 0 || n_envs <= 0) { set_error(call + ": bad arguments"); return FJSP_E_ARG; }
     if (family < -1 || family > 1) { set_error(call + ": family must be -1, 0 or 1"); return FJSP_E_ARG; }
-    const bool class_fjsp = variant == FJSP_VARIANT_SO_DFJSP;
-    if (variant == FJSP_VARIANT_MO_DFJSP) {
-        set_error(call + ": MO_DFJSP needs machine data and the per-env fluid tables; the generator has neither (use fjsp_env_create)");
+    // (MO_DFJSP shares SO_DFJSP's due dates -- the order's delivery time -- and its need of an operation on every machine)
+    const bool class_fjsp = variant == FJSP_VARIANT_SO_DFJSP || dq;
+    if (variant == FJSP_VARIANT_MO_DFJSP && !dq) {
+        set_error(call + ": MO_DFJSP needs machine data: use fjsp_env_create_generated_dynamic (or fjsp_env_create)");
         return FJSP_E_UNSUPPORTED;
     }
-    if (class_fjsp) variant = FJSP_VARIANT_SO_FJSSP;
-    if (variant != FJSP_VARIANT_SO_FJSSP && variant != FJSP_VARIANT_SO_SFJSP && variant != FJSP_VARIANT_MO_FJSSP_DISCRETES) {
+    if (variant == FJSP_VARIANT_SO_DFJSP) variant = FJSP_VARIANT_SO_FJSSP;
+    if (variant != FJSP_VARIANT_SO_FJSSP && variant != FJSP_VARIANT_SO_SFJSP && variant != FJSP_VARIANT_MO_FJSSP_DISCRETES && !dq) {
         set_error(call + ": unknown variant"); return FJSP_E_ARG;
     }
-    int rc = o ? check_gen_orders(*o) : (q ? check_gen_ranges(*q) : FJSP_OK);
+    int rc = dq ? check_gen_dynamic(*dq) : (o ? check_gen_orders(*o) : (q ? check_gen_ranges(*q) : FJSP_OK));
     if (rc != FJSP_OK) return rc;
     fjsp_gen_params g = *prm;
     if (q) { g.M = q->M_min; g.DDT = 0.0; }       // base.M and base.DDT are not read
@@ -780,7 +881,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         set_error(call + ": more than " + std::to_string(FJSP_GEN_MAX_ORDERS) + " orders (S_max): the generator kernel keeps the orders' counts and times in LDS");
         return FJSP_E_UNSUPPORTED;
     }
-    if (S_max > 1 && variant != FJSP_VARIANT_SO_FJSSP) {
+    if (S_max > 1 && variant != FJSP_VARIANT_SO_FJSSP && !dq) {
         set_error(call + ": only SO_FJSSP handles order arrivals (the subclasses are single-order, SO_SFJSP.py:20 / MO_FJSSP_discretes.py:21): S_max must be 1");
         return FJSP_E_UNSUPPORTED;
     }
@@ -791,7 +892,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         return FJSP_E_UNSUPPORTED;
     }
     Shape sh;
-    if ((rc = check_worst_case(g, M_min, M_max, ddt_max, S_max, sh)) != FJSP_OK) return rc;
+    if ((rc = check_worst_case(g, M_min, M_max, ddt_max, S_max, dq ? &dq->m : nullptr, sh)) != FJSP_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device visible: the environment kernels need an MI355X (there is no CPU path)");
@@ -805,7 +906,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     DevBatch &b = e->b;
     if ((rc = plan_batch(b, e->plan, sh, n_inst, n_envs, variant, rng_seed, family)) != FJSP_OK) return rc;
     // src stays null: the order-arrival services (fjsp_arrivals.hip) of a multi-order handle read lp_mirror in its place
-    if ((b.mord != 0) != (S_max > 1)) { set_error(call + ": internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
+    if ((b.mord != 0) != (S_max > 1 || dq)) { set_error(call + ": internal error (multi-order layout)"); return FJSP_E_UNSUPPORTED; }
     e->inst_K.assign((size_t)n_inst, 0); e->inst_M.assign((size_t)n_inst, sh.M);
     e->ops_max = sh.K * prm->N_max * S_max;
     if (b.mord) {
@@ -822,6 +923,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     G.a.g = g; G.a.class_fjsp = class_fjsp ? 1 : 0; G.a.allow_device = e->plan.lp_device_forced == 0 ? 0 : 1;
     G.a.allow_global = e->plan.lp_device_forced == 2 ? 1 : 0;
     if (o) { G.a.orders = 1; G.a.S_min = o->S_min; G.a.S_max = o->S_max; }
+    if (dq) { G.dynamic = true; G.d.mc = dq->m; G.d.redraws = dq->redraws; G.d.windows = sh.B; }
     G.a.kmax = sh.K; G.a.RP = sh.R;
     G.chunk = (int)std::min<size_t>(NI, 1024);
     G.head16 = (int)((b.L.i_x + 15) / 16);
@@ -849,6 +951,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         !dev_alloc(e.get(), sizeof(LpErrWord), &G.d_lp_err, "hipMalloc LP error word") ||
         !dev_alloc(e.get(), sizeof(LpCounters), &lds.d_solved, "hipMalloc LP counters") ||
         (b.grp && !dev_alloc(e.get(), N, &G.d_kenv, "hipMalloc K table")) ||
+        (dq && (!dev_alloc(e.get(), NI * sizeof(uint64_t), &G.d.seed_used, "hipMalloc instance seeds") || !host_alloc(e.get(), NI * sizeof(uint64_t), &G.h_seed_used))) ||
         !host_alloc(e.get(), NI * sizeof(GenInfo), &G.h_info) || !host_alloc(e.get(), kGenCounts * sizeof(uint32_t), &G.h_counts) ||
         !host_alloc(e.get(), ids, &G.h_host_ids) || !host_alloc(e.get(), stage, &G.h_stage) ||
         !host_alloc(e.get(), heads, &G.h_head) || !host_alloc(e.get(), sizeof(GenReadback), &G.h_back))
@@ -887,19 +990,25 @@ using namespace fjsp;
 extern "C" {
 int fjsp_env_create_generated(const fjsp_gen_params *prm, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
                               uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
-    return create_generated("fjsp_env_create_generated", prm, nullptr, nullptr, n_inst, n_envs, variant, device, rng_seed, family, seed_base, out);
+    return create_generated("fjsp_env_create_generated", prm, nullptr, nullptr, nullptr, n_inst, n_envs, variant, device, rng_seed, family, seed_base, out);
 }
 
 int fjsp_env_create_generated_ranges(const fjsp_gen_ranges *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
                                      uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
-    return create_generated("fjsp_env_create_generated_ranges", q ? &q->base : nullptr, q, nullptr, n_inst, n_envs, variant, device, rng_seed, family,
-                            seed_base, out);
+    return create_generated("fjsp_env_create_generated_ranges", q ? &q->base : nullptr, q, nullptr, nullptr, n_inst, n_envs, variant, device, rng_seed,
+                            family, seed_base, out);
 }
 
 int fjsp_env_create_generated_orders(const fjsp_gen_orders *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
                                      uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out) {
-    return create_generated("fjsp_env_create_generated_orders", q ? &q->r.base : nullptr, q ? &q->r : nullptr, q, n_inst, n_envs, variant, device,
-                            rng_seed, family, seed_base, out);
+    return create_generated("fjsp_env_create_generated_orders", q ? &q->r.base : nullptr, q ? &q->r : nullptr, q, nullptr, n_inst, n_envs, variant,
+                            device, rng_seed, family, seed_base, out);
+}
+
+int fjsp_env_create_generated_dynamic(const fjsp_gen_dynamic *q, int32_t n_inst, int32_t n_envs, int32_t device, uint64_t rng_seed, uint64_t seed_base,
+                                      fjsp_env **out) {
+    return create_generated("fjsp_env_create_generated_dynamic", q ? &q->o.r.base : nullptr, q ? &q->o.r : nullptr, q ? &q->o : nullptr, q, n_inst, n_envs,
+                            FJSP_VARIANT_MO_DFJSP, device, rng_seed, 0, seed_base, out);
 }
 
 int fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed) {
@@ -970,6 +1079,38 @@ int fjsp_env_instance_read(fjsp_env *e, int32_t i, int32_t dims[6], int32_t *Jr,
         if (delivery) delivery[so] = dl[(size_t)so];
     }
     if (ddt) *ddt = f.ddt;
+    return FJSP_OK;
+}
+
+int fjsp_env_instance_read_dynamic(fjsp_env *e, int32_t i, int32_t *power, int32_t *idle_power, int32_t *bk_n, int32_t *bk, uint64_t *seed_used,
+                                   int32_t dims[2]) {
+    if (!e || i < 0 || i >= e->b.n_inst) { set_error("fjsp_env_instance_read_dynamic: bad arguments"); return FJSP_E_ARG; }
+    if (!e->gen || !e->gen->dynamic) { set_error("fjsp_env_instance_read_dynamic: the batch was not made by fjsp_env_create_generated_dynamic"); return FJSP_E_STATE; }
+    if (e->gen_failed) { set_error("fjsp_env_instance_read_dynamic: the last fjsp_env_regenerate of this batch failed"); return FJSP_E_STATE; }
+    DeviceGuard guard(e->device);
+    const DevBatch &b = e->b;
+    const size_t MP = (size_t)b.MP;
+    std::vector<unsigned char> rec(b.L.i_stride);
+    uint64_t used = 0;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(rec.data(), b.inst + (size_t)i * b.L.i_stride, rec.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&used, e->gen->d.seed_used + i, sizeof(used), hipMemcpyDeviceToHost));
+    const InstHeader h = *reinterpret_cast<const InstHeader *>(rec.data());
+    const uint16_t *pw = reinterpret_cast<const uint16_t *>(rec.data() + b.L.i_pw), *bko = reinterpret_cast<const uint16_t *>(rec.data() + b.L.i_bkoff);
+    const int32_t *ipw = reinterpret_cast<const int32_t *>(rec.data() + b.L.i_ipw), *win = reinterpret_cast<const int32_t *>(rec.data() + b.L.i_bk);
+    const int total = bko[MP];
+    if (h.K < 1 || h.K > b.KP || h.M < 1 || h.M > b.MP || total > e->gen->d.windows) {
+        set_error("fjsp_env_instance_read_dynamic: the record's sizes are out of range (internal error)"); return FJSP_E_STATE;
+    }
+    for (int k = 0; power && k < h.K; ++k)
+        for (int m = 0; m < h.M; ++m) power[(size_t)k * h.M + m] = pw[(size_t)k * MP + m];
+    for (int m = 0; m < h.M; ++m) {
+        if (idle_power) idle_power[m] = ipw[m];
+        if (bk_n) bk_n[m] = (int)bko[m + 1] - (int)bko[m];
+    }
+    if (bk) std::copy(win, win + 2 * (size_t)total, bk);
+    if (seed_used) *seed_used = used;
+    if (dims) { dims[0] = 1; dims[1] = total; }
     return FJSP_OK;
 }
 }  // extern "C"

@@ -62,6 +62,8 @@ int check_gen_ranges(const fjsp_gen_ranges &q);
 void draw_gen_params(const fjsp_gen_ranges &q, uint64_t seed, fjsp_gen_params &out);
 // the same of a fjsp_gen_orders: the ranges' bounds, the order count's and the arrival intervals'
 int check_gen_orders(const fjsp_gen_orders &q);
+// ... and of a fjsp_gen_dynamic: those, the machine ranges (FJSP_E_ARG) and what the record's fields cannot hold (FJSP_E_UNSUPPORTED)
+int check_gen_dynamic(const fjsp_gen_dynamic &q);
 
 }  // namespace fjsp
 

@@ -332,6 +332,79 @@ void draw_gen_orders(const fjsp_gen_orders &q, uint64_t seed, fjsp_gen_params &o
     out.S = aux.randint(q.S_min, q.S_max);
 }
 
+// ---- ... and the machine data of an MO_DFJSP shop (fjsp_gen_dynamic) ----
+int check_gen_dynamic(const fjsp_gen_dynamic &q) {
+    if (const int rc = check_gen_orders(q.o)) return rc;
+    const fjsp_gen_machine &m = q.m;
+    auto bad = [](const char *msg, int rc) { set_error(std::string("generator machine data: ") + msg); return rc; };
+    if (m.pw_min < 1) return bad("pw_min must be at least 1", FJSP_E_ARG);
+    if (m.pw_max < m.pw_min) return bad("pw_max < pw_min", FJSP_E_ARG);
+    if (m.idle_min < 0) return bad("idle_min must not be negative", FJSP_E_ARG);
+    if (m.idle_max < m.idle_min) return bad("idle_max < idle_min", FJSP_E_ARG);
+    if (m.W_max < 0) return bad("W_max must not be negative", FJSP_E_ARG);
+    if (m.gap_min < 1) return bad("gap_min must be at least 1 (windows stay disjoint)", FJSP_E_ARG);
+    if (m.gap_max < m.gap_min) return bad("gap_max < gap_min", FJSP_E_ARG);
+    if (m.len_min < 1) return bad("len_min must be at least 1 (windows stay non-empty)", FJSP_E_ARG);
+    if (m.len_max < m.len_min) return bad("len_max < len_min", FJSP_E_ARG);
+    if (q.redraws < 0) return bad("redraws must not be negative", FJSP_E_ARG);
+    if (q.redraws > FJSP_GEN_MAX_REDRAWS) return bad(("redraws above " + std::to_string(FJSP_GEN_MAX_REDRAWS) + " (FJSP_GEN_MAX_REDRAWS)").c_str(), FJSP_E_UNSUPPORTED);
+    if (m.W_max > FJSP_GEN_MAX_WINDOWS) return bad(("W_max above " + std::to_string(FJSP_GEN_MAX_WINDOWS) + " (FJSP_GEN_MAX_WINDOWS)").c_str(), FJSP_E_UNSUPPORTED);
+    if (m.pw_max > 65535) return bad("pw_max above 65535", FJSP_E_UNSUPPORTED);
+    if ((long long)m.pw_max * (long long)q.o.r.base.p_max > 0x7fffffffLL) return bad("pw_max x p_max above 2^31 - 1 (the energy of one operation)", FJSP_E_UNSUPPORTED);
+    if ((long long)m.W_max * ((long long)m.gap_max + (long long)m.len_max) > 0x7fffffffLL)
+        return bad("W_max x (gap_max + len_max) above 2^31 - 1 (the end of a machine's last window)", FJSP_E_UNSUPPORTED);
+    return FJSP_OK;
+}
+
+// draw i (0-based) of Rng(seed): the stream advances by a constant, so a position needs no chain
+static Rng rng_at(uint64_t seed, uint32_t i) { return Rng(seed + (uint64_t)i * 0x9E3779B97F4A7C15ULL); }
+static int randint_at(uint64_t seed, uint32_t i, int a, int b) { return rng_at(seed, i).randint(a, b); }
+
+static bool machine_without_operation(const Instance &in) {
+    for (int m = 0; m < in.M; ++m) {
+        int ops_m = 0;
+        for (int k = 0; k < in.K; ++k) ops_m += in.p[(size_t)k * in.M + m] > 0 ? 1 : 0;
+        if (ops_m == 0) return true;
+    }
+    return false;
+}
+
+// The first playable attempt of instance `seed` (fjsp_gen_dynamic, include/fjsp_amd.h): its shop into `in`, its seed into used
+static int generate_playable(Instance &in, uint64_t seed, const fjsp_gen_dynamic &q, uint64_t &used) {
+    for (int j = 0; j <= q.redraws; ++j) {
+        used = j == 0 ? seed : rng_at(seed ^ FJSP_GEN_REDRAW_STREAM, (uint32_t)(j - 1)).next();
+        fjsp_gen_params prm;
+        draw_gen_orders(q.o, used, prm);
+        if (const int rc = generate(in, used, prm)) return rc;
+        if (!machine_without_operation(in)) return FJSP_OK;
+    }
+    set_error("MO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference) in each of " +
+              std::to_string(q.redraws + 1) + " attempts (redraws = " + std::to_string(q.redraws) + ")");
+    return FJSP_E_UNSUPPORTED;
+}
+
+static void generate_machine_data(Instance &in, uint64_t seed, const fjsp_gen_machine &g) {
+    const uint64_t ms = seed ^ FJSP_GEN_MACHINE_STREAM;
+    const uint32_t M = (uint32_t)in.M, K = (uint32_t)in.K, W = (uint32_t)g.W_max;
+    in.power.assign((size_t)K * M, 0); in.idle_power.assign(M, 0); in.bk_n.assign(M, 0); in.bk.clear();
+    for (uint32_t m = 0; m < M; ++m) {
+        in.idle_power[m] = randint_at(ms, m, g.idle_min, g.idle_max);
+        in.bk_n[m] = randint_at(ms, M + m, 0, g.W_max);
+    }
+    for (uint32_t q = 0; q < K * M; ++q)
+        if (in.p[q] > 0) in.power[q] = randint_at(ms, 2u * M + q, g.pw_min, g.pw_max);
+    for (uint32_t m = 0; m < M; ++m) {
+        int t = 0;
+        for (uint32_t w = 0; w < (uint32_t)in.bk_n[m]; ++w) {
+            const uint32_t pos = 2u * M + K * M + 2u * (m * W + w);
+            const int st = t + randint_at(ms, pos, g.gap_min, g.gap_max), en = st + randint_at(ms, pos + 1u, g.len_min, g.len_max);
+            in.bk.push_back(st); in.bk.push_back(en);
+            t = en;
+        }
+    }
+    in.has_dynamic = true;
+}
+
 static int solve_order0(Instance &in) {
     std::vector<int> Q(in.K), now(in.K);
     for (int r = 0; r < in.R; ++r)
@@ -411,6 +484,38 @@ int fjsp_instances_generate_orders(fjsp_instances *s, int32_t i, uint64_t seed, 
     fjsp_gen_params prm;
     const int rc = fjsp_gen_draw_orders(q, seed, &prm);
     return rc == FJSP_OK ? fjsp_instances_generate(s, i, seed, &prm) : rc;
+}
+
+int fjsp_gen_dynamic_seed(const fjsp_gen_dynamic *q, uint64_t seed, uint64_t *used) {
+    if (!q || !used) { set_error("fjsp_gen_dynamic_seed: null argument"); return FJSP_E_ARG; }
+    if (const int rc = check_gen_dynamic(*q)) return rc;
+    Instance in;
+    const int rc = generate_playable(in, seed, *q, *used);
+    if (rc == FJSP_E_UNSUPPORTED) set_error("seed " + std::to_string(seed) + ": " + g_err);
+    return rc;
+}
+
+int fjsp_gen_draw_dynamic(const fjsp_gen_dynamic *q, uint64_t seed, fjsp_gen_params *out) {
+    if (!q || !out) { set_error("fjsp_gen_draw_dynamic: null argument"); return FJSP_E_ARG; }
+    uint64_t used = 0;
+    const int rc = fjsp_gen_dynamic_seed(q, seed, &used);
+    if (rc == FJSP_OK) draw_gen_orders(q->o, used, *out);
+    return rc;
+}
+
+int fjsp_instances_generate_dynamic(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_dynamic *q) {
+    CHECK_IDX(s, i);
+    if (!q) { set_error("fjsp_instances_generate_dynamic: null argument"); return FJSP_E_ARG; }
+    if (const int rc = check_gen_dynamic(*q)) return rc;
+    Instance in;
+    uint64_t used = 0;
+    if (const int rc = generate_playable(in, seed, *q, used)) {
+        if (rc == FJSP_E_UNSUPPORTED) set_error("instance " + std::to_string(i) + " (seed " + std::to_string(seed) + "): " + g_err);
+        return rc;
+    }
+    generate_machine_data(in, used, q->m);
+    s->v[(size_t)i] = std::move(in);
+    return FJSP_OK;
 }
 
 int fjsp_instances_set_raw(fjsp_instances *s, int32_t i, int32_t R, int32_t M, int32_t S, const int32_t *Jr,

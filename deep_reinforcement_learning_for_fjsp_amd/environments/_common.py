@@ -56,8 +56,9 @@ class BatchedEnv(object):
         the machine count and the due-date tightness drawn per instance, or instances.GenOrders with the number of orders
         drawn too -- BatchedSOFJSSP / BatchedSODFJSP then play order arrivals): the batch's instances are
         then generated and solved on the device from seed_base (EnvBatch.generated; n_envs is needed), and
-        ``self.batch.regenerate(seed_base)`` refills them in place.  The library refuses MO_DFJSP."""
-        if isinstance(instance_set, (_inst.GenParams, _inst.GenRanges, _inst.GenOrders)):
+        ``self.batch.regenerate(seed_base)`` refills them in place.  BatchedMODFJSP takes an instances.GenDynamic -- the shop of a
+        GenOrders with its machine data -- and only that; the other classes refuse one."""
+        if isinstance(instance_set, (_inst.GenParams, _inst.GenRanges, _inst.GenOrders, _inst.GenDynamic)):
             if n_envs is None:
                 raise ValueError("n_envs is needed with generator parameters")
             self.batch = EnvBatch.generated(instance_set, n_envs, seed_base, n_inst=n_inst, variant=self.variant, device=device,

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import GenOrders, GenParams, GenRanges, check
+from ._capi import GenDynamic, GenMachine, GenOrders, GenParams, GenRanges, check
 
 
 def bench_10x5_params(ddt=1.0):
@@ -51,14 +51,39 @@ def reference_order_ranges(agent):
     return GenOrders(GenRanges(reference_generator_params(1.0, 0, 1), 10, 20, 0.5, 1.5), 1, 5)
 
 
+def reference_machine_params(max_windows=0, window_gap=(50, 400), window_len=(5, 60)):
+    """The machine data the reference's generator draws -- processing power U{10..200} per eligible pair, idle power
+    U{1..9} per machine (Instance_generate.py:61-66) -- and, as an extension of ours, up to max_windows breakdown windows per
+    machine (the reference's generator has none: its windows exist only in CSV folders)."""
+    return GenMachine(10, 200, 1, 9, int(max_windows), int(window_gap[0]), int(window_gap[1]), int(window_len[0]), int(window_len[1]))
+
+
+def reference_dynamic_ranges(agent, redraws=8, **windows):
+    """What HMPSAC's lower policies draw a fresh MO_DFJSP shop from (A3C_v5.1.py:245-253): reference_order_ranges(agent) plus
+    reference_machine_params(**windows); an instance with a machine that no operation is eligible on is drawn again, at most
+    `redraws` times."""
+    if agent != "hmpsac":
+        raise ValueError("reference_dynamic_ranges: 'hmpsac', got %r" % (agent,))
+    return GenDynamic(reference_order_ranges(agent), reference_machine_params(**windows), int(redraws))
+
+
 def draw_params(ranges, seed):
-    """The GenParams that instance `seed` is generated with under `ranges`: a GenRanges (fjsp_gen_draw) or a GenOrders
-    (fjsp_gen_draw_orders)."""
+    """The GenParams that instance `seed` is generated with under `ranges`: a GenRanges (fjsp_gen_draw), a GenOrders
+    (fjsp_gen_draw_orders) or a GenDynamic (fjsp_gen_draw_dynamic: those of the seed the instance is made of, dynamic_seed)."""
     out = GenParams()
     lib = _capi.lib()
-    draw = lib.fjsp_gen_draw_orders if isinstance(ranges, GenOrders) else lib.fjsp_gen_draw
+    draw = (lib.fjsp_gen_draw_dynamic if isinstance(ranges, GenDynamic) else
+            lib.fjsp_gen_draw_orders if isinstance(ranges, GenOrders) else lib.fjsp_gen_draw)
     check(draw(C.byref(ranges), int(seed) & (2 ** 64 - 1), C.byref(out)))
     return out
+
+
+def dynamic_seed(params, seed):
+    """The seed the MO_DFJSP instance `seed` is made of under the GenDynamic `params` (fjsp_gen_dynamic_seed): `seed` itself
+    unless its shop leaves a machine without an eligible operation and is drawn again."""
+    used = C.c_uint64()
+    check(_capi.lib().fjsp_gen_dynamic_seed(C.byref(params), int(seed) & (2 ** 64 - 1), C.byref(used)))
+    return int(used.value)
 
 
 class InstanceArrays(object):
@@ -107,8 +132,10 @@ class InstanceSet(object):
 
     def generate(self, i, seed, params):
         """params: GenParams, GenRanges (M and DDT drawn per instance from the seed: fjsp_instances_generate_drawn) or
-        GenOrders (the number of orders too: fjsp_instances_generate_orders)."""
-        call = (self._lib.fjsp_instances_generate_orders if isinstance(params, GenOrders) else
+        GenOrders (the number of orders too: fjsp_instances_generate_orders) or GenDynamic (an MO_DFJSP shop with its machine
+        data, drawn again while a machine is left without an eligible operation: fjsp_instances_generate_dynamic)."""
+        call = (self._lib.fjsp_instances_generate_dynamic if isinstance(params, GenDynamic) else
+                self._lib.fjsp_instances_generate_orders if isinstance(params, GenOrders) else
                 self._lib.fjsp_instances_generate_drawn if isinstance(params, GenRanges) else self._lib.fjsp_instances_generate)
         check(call(self._h, int(i), int(seed) & (2 ** 64 - 1), C.byref(params)))
         return self
@@ -194,7 +221,10 @@ class InstanceSet(object):
         """Machine data for a generated instance, drawn like the reference's generator: processing power
         U{10..200} per eligible pair, idle power U{1..9} per machine (Instance_generate.py:61-66,90-91).  The
         generator has no breakdowns (that data only exists in CSV folders, MO_DFJSP_instance_read.py:56-73);
-        max_windows > 0 adds up to that many sorted, disjoint windows per machine for synthetic batches."""
+        max_windows > 0 adds up to that many sorted, disjoint windows per machine for synthetic batches.
+        These are draws of a NumPy RandomState on this side of the C ABI.  generate(i, seed, GenDynamic) draws machine data
+        of the same distributions from the library's own counter-based stream, which the device generator restates
+        (EnvBatch.generated with a GenDynamic): the two produce DIFFERENT data for the same seed."""
         a = self.arrays(i)
         rs = np.random.RandomState(int(seed) & 0x7FFFFFFF)
         power = np.where(a.p > 0, rs.randint(10, 201, a.p.shape), 0)

@@ -8,7 +8,11 @@ breakdowns + energy), everything batched on one MI355X:
      the reference's industrial instances (data/industrial/DDT0.5_M20_S{1,3,5} + two data/HMPSAC folders as
      stored in tests/golden/mo_dfjsp.npz, replicated round-robin, different random streams per env).
 
-    python examples/train_hmpsac.py --envs 4096 --lower-rounds 2 --epochs 2
+    python examples/train_hmpsac.py --envs 4096 --lower-rounds 2 --epochs 2 [--generated]
+
+--generated: every lower policy trains on one MO_DFJSP batch generated on the device (instances.GenDynamic: the same shop
+and window ranges, machine count, tightness and order count drawn by the library's generator) and refilled in place for every
+round, instead of a batch rebuilt on the host.  Off by default: the instances differ, and so do the figures.
 
 Prints one JSON line: env-steps/s of the controller loop (policy inference + HIP env + host LP service at
 order arrivals + SAC updates) and the objectives of the last epoch."""
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--lower-envs", type=int, default=512)
     ap.add_argument("--lower-rounds", type=int, default=2)
     ap.add_argument("--epochs", type=int, default=2)
+    ap.add_argument("--generated", action="store_true", help="lower-policy training batches generated and refilled on the device")
     args = ap.parse_args()
     import torch
     from tests import helpers as H
@@ -56,11 +61,25 @@ def main():
             s.generate_machine_data(i, seed, max_windows=3, window_gap=(200, 3000), window_len=(20, 300))
         return BatchedMODFJSP(s.solve_fluid(), rng_seed=rounds[0])
 
+    def make_generated_env():  # the same ranges through the device generator: one handle, refilled for every round
+        q = fi.reference_dynamic_ranges("hmpsac", max_windows=3, window_gap=(200, 3000), window_len=(20, 300))
+        q.o.r.base.R_max, q.o.r.base.N_min, q.o.r.base.N_max = 8, 2, 8
+        live = []
+
+        def make():
+            rounds[0] += 1
+            if live:
+                live[0].batch.regenerate(100000 * rounds[0], rng_seed=rounds[0])
+            else:
+                live.append(BatchedMODFJSP(q, n_envs=args.lower_envs, seed_base=100000 * rounds[0], rng_seed=rounds[0]))
+            return live[0]
+        return make
+
     torch.manual_seed(0)
     lower, t0 = {}, time.perf_counter()
     lower_obj = {}
     for policy in (0, 1, 2):
-        tr = DA3C(make_train_env, test_env, reward_policy=policy, seed=policy, max_steps=4096)
+        tr = DA3C(make_generated_env() if args.generated else make_train_env, test_env, reward_policy=policy, seed=policy, max_steps=4096)
         lower_obj[policy] = [tr.run_one_round() for _ in range(args.lower_rounds)]
         lower[policy] = (tr.actor_task_model, tr.actor_machine_model)
     t_lower = time.perf_counter() - t0
@@ -86,6 +105,7 @@ def main():
         "controller_transitions": ctrl_steps, "order_arrival_lps": env.batch.lp_solves - lp0,
         "learn_sessions": sac.learn_sessions, "losses": sac.last_losses, "alpha": float(sac.alpha.detach()),
         "last_epoch_mean_objectives": {"completion_time": out[0], "delay_time_sum": out[1], "energy_consumption": out[2]},
+        "lower_policy_batches": "generated on the device" if args.generated else "rebuilt on the host",
         "lower_policy_training_s": t_lower, "lower_policy_test_objectives": lower_obj}))
 
 

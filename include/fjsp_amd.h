@@ -120,6 +120,44 @@ typedef struct {
     int32_t S_min, S_max;      /* orders per instance:    U{S_min..S_max}      */
 } fjsp_gen_orders;
 
+/* ... and the machine data of a dynamic multi-objective shop (FJSP_VARIANT_MO_DFJSP): processing power per eligible pair,
+ * idle power per machine, breakdown windows per machine.  The reference's generator draws powers U{10..200}, idle powers
+ * U{1..9} and no windows (Instance_generate.py:61-66; its Python stream is pinned nowhere, so this stream is the library's
+ * own).  The machine data of instance s (M machines, K operation types) are draws of the splitmix64 stream seeded
+ * s ^ FJSP_GEN_MACHINE_STREAM, each at a position that is a pure function of its indices (the integer formula above):
+ *     idle power of machine m         U{idle_min..idle_max}   draw m
+ *     window count of machine m       U{0..W_max}             draw M + m
+ *     power of pair (k, m)            U{pw_min..pw_max}       draw 2M + k*M + m   (reserved for an ineligible pair too: its power is 0)
+ *     gap of window w of machine m    U{gap_min..gap_max}     draw 2M + K*M + 2*(m*W_max + w)
+ *     length of that window           U{len_min..len_max}     the draw behind its gap
+ * Window w starts at the end of window w - 1 (0 for the first) plus its gap and ends at its start plus its length, so the
+ * windows of a machine are sorted, disjoint and non-empty; powers and idle powers do not depend on W_max.  All draws of an
+ * instance are always reserved; the main and the auxiliary stream of s are untouched.
+ * FJSP_GEN_MAX_WINDOWS: the largest W_max (32 machines x 2047 windows index the record's u16 window offsets). */
+#define FJSP_GEN_MACHINE_STREAM 0xA0761D6478BD642FULL
+#define FJSP_GEN_MAX_WINDOWS 2047
+typedef struct {
+    int32_t pw_min, pw_max;     /* processing power of an eligible pair */
+    int32_t idle_min, idle_max; /* idle power of a machine */
+    int32_t W_max;              /* most breakdown windows of a machine, 0 = none */
+    int32_t gap_min, gap_max;   /* working time in front of a window */
+    int32_t len_min, len_max;   /* length of a window */
+} fjsp_gen_machine;
+
+/* An MO_DFJSP instance: the shop of a fjsp_gen_orders and its machine data.  MO_DFJSP cannot play an instance with a machine
+ * that no operation is eligible on (Machine.gap_ave divides by zero in the reference), so such an instance is drawn again:
+ * attempt j of instance s is the WHOLE instance (M, DDT, S, the shop, the machine data) of seed s_j, with s_0 = s and, for
+ * j > 0, s_j = draw j - 1 of the splitmix64 stream seeded s ^ FJSP_GEN_REDRAW_STREAM (never s + j, which is a neighbour's
+ * seed).  The instance is the first attempt in which every machine has an eligible operation; after `redraws` further
+ * attempts (0 ... FJSP_GEN_MAX_REDRAWS) the instance fails with FJSP_E_UNSUPPORTED. */
+#define FJSP_GEN_REDRAW_STREAM 0xE7037ED1A0B428DBULL
+#define FJSP_GEN_MAX_REDRAWS 16
+typedef struct {
+    fjsp_gen_orders o;
+    fjsp_gen_machine m;
+    int32_t redraws;
+} fjsp_gen_dynamic;
+
 int  fjsp_instances_create(int32_t n, fjsp_instances **out);
 void fjsp_instances_destroy(fjsp_instances *s);
 int  fjsp_instances_count(const fjsp_instances *s);
@@ -141,6 +179,18 @@ int fjsp_instances_generate_drawn(fjsp_instances *s, int32_t i, uint64_t seed, c
 int fjsp_gen_draw_orders(const fjsp_gen_orders *q, uint64_t seed, fjsp_gen_params *out);
 /* fjsp_gen_draw_orders, then fjsp_instances_generate with what it drew. */
 int fjsp_instances_generate_orders(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_orders *q);
+/* The MO_DFJSP instance of `seed` under q (see fjsp_gen_dynamic).  fjsp_gen_dynamic_seed: the seed of the first attempt in
+ * which every machine has an eligible operation, in *used (== seed where attempt 0 is playable); FJSP_E_UNSUPPORTED, the
+ * message naming the seed, when none of the 1 + q->redraws attempts is.  fjsp_gen_draw_dynamic: the parameter set of that
+ * seed (fjsp_gen_draw_orders of it).  fjsp_instances_generate_dynamic: fjsp_instances_generate_orders of that seed plus the
+ * machine data of the stream above (fjsp_instances_get_dynamic reads them); its failure names the instance as well.
+ * FJSP_E_ARG, the message naming the field: the bounds fjsp_gen_draw_orders refuses, a machine range with max < min,
+ * pw_min < 1, idle_min < 0, W_max < 0, gap_min < 1, len_min < 1, redraws < 0.  FJSP_E_UNSUPPORTED, likewise: W_max >
+ * FJSP_GEN_MAX_WINDOWS, redraws > FJSP_GEN_MAX_REDRAWS, pw_max > 65535, pw_max x p_max > 2^31 - 1 (the energy of one
+ * operation), W_max x (gap_max + len_max) > 2^31 - 1 (the end of a machine's last window). */
+int fjsp_gen_dynamic_seed(const fjsp_gen_dynamic *q, uint64_t seed, uint64_t *used);
+int fjsp_gen_draw_dynamic(const fjsp_gen_dynamic *q, uint64_t seed, fjsp_gen_params *out);
+int fjsp_instances_generate_dynamic(fjsp_instances *s, int32_t i, uint64_t seed, const fjsp_gen_dynamic *q);
 /* Raw arrays (same meaning as the fjsp_instances_get outputs). */
 int fjsp_instances_set_raw(fjsp_instances *s, int32_t i, int32_t R, int32_t M, int32_t S,
                            const int32_t *Jr, const int32_t *p /*[K*M] k-major, 0 = ineligible*/,
@@ -206,7 +256,7 @@ int  fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_in
  * fjsp_env_regenerate refills the records in place from other seeds -- no host instance set, no instance upload, no device allocation --
  * and leaves every env as a create leaves it (done; env random streams restarted from rng_seed; recorded schedule cleared).
  * One order only: prm->S > 1 and FJSP_VARIANT_MO_DFJSP are FJSP_E_UNSUPPORTED here (several orders:
- * fjsp_env_create_generated_orders below; MO_DFJSP needs machine data, which the generator does not draw).  Bad parameters (the checks of fjsp_instances_generate), an unknown variant, n_inst <= 0 or n_envs <= 0:
+ * fjsp_env_create_generated_orders below; MO_DFJSP needs machine data: fjsp_env_create_generated_dynamic below).  Bad parameters (the checks of fjsp_instances_generate), an unknown variant, n_inst <= 0 or n_envs <= 0:
  * FJSP_E_ARG; a worst case outside the kernels' limits: FJSP_E_UNSUPPORTED; all before the first HIP call.
  * An LP whose tableau fits the LDS of a CU is solved by the device simplex, the others by the host's on
  * fjsp_env_set_lp_threads threads; FJSP_LP_IMPL=host sends all to the host, =device refuses (FJSP_E_UNSUPPORTED) when one
@@ -253,6 +303,26 @@ int  fjsp_env_create_generated_ranges(const fjsp_gen_ranges *q, int32_t n_inst, 
  * (S_max - 1) t_si_max, and the work of all orders); all before the first HIP call, the message naming the bound. */
 int  fjsp_env_create_generated_orders(const fjsp_gen_orders *q, int32_t n_inst, int32_t n_envs, int32_t variant, int32_t device,
                                       uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out);
+/* A FJSP_VARIANT_MO_DFJSP batch generated on the device (fjsp_gen_dynamic): instance i is what
+ * fjsp_instances_generate_dynamic(seed_base + i, q) + fjsp_instances_solve_fluid + fjsp_env_create give -- the shop, the
+ * machine data (generate_machine_kernel: the record's powers, idle powers and breakdown windows are byte for byte what the
+ * host packs), x bit for bit, and so the episodes.  The redraw loop runs in the generator kernel, bounded by q->redraws;
+ * an instance without a playable attempt fails the call as it fails on the host (FJSP_E_UNSUPPORTED, named with its seed).
+ * One wave per environment (the row kernels do not play MO_DFJSP); always a multi-order handle, sized as
+ * fjsp_env_create_generated_orders sizes its own plus M_max x W_max breakdown windows per record; the arrival service is chosen and
+ * behaves as there (fjsp_env_regenerate, the host mirror, the refusal while envs are parked).  The snapshot fingerprint
+ * mixes a tag, the machine ranges and redraws.  Refusals: those of fjsp_instances_generate_dynamic and of
+ * fjsp_env_create_generated_orders; FJSP_E_UNSUPPORTED when the 32-bit clock bound fails once it counts every breakdown
+ * window (M_max x W_max x len_max); all before the first HIP call, the message naming the bound.
+ * fjsp_env_create_generated, _ranges and _orders keep refusing FJSP_VARIANT_MO_DFJSP and name this entry point.
+ * fjsp_env_instance_read_dynamic: the machine data of instance i read back from the device, the twin of
+ * fjsp_instances_dynamic_dims / _get_dynamic (dims[0] = 1, dims[1] = windows of the instance; bk holds dims[1] (start, end)
+ * pairs), and the seed the instance was made of (seed_base + i unless it was drawn again); every output nullable;
+ * FJSP_E_STATE on any other handle.  Synchronises. */
+int  fjsp_env_create_generated_dynamic(const fjsp_gen_dynamic *q, int32_t n_inst, int32_t n_envs, int32_t device, uint64_t rng_seed,
+                                       uint64_t seed_base, fjsp_env **out);
+int  fjsp_env_instance_read_dynamic(fjsp_env *e, int32_t i, int32_t *power, int32_t *idle_power, int32_t *bk_n, int32_t *bk,
+                                    uint64_t *seed_used, int32_t dims[2]);
 int  fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed);
 /* Of the last create_generated / regenerate: out[0] instances, [1] LPs solved on the device, [2] on the host, [3] pivots
  * of the device simplex.  fjsp_env_generated_times: milliseconds of its parts -- the generate kernel, the LP launches with
