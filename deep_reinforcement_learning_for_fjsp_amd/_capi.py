@@ -97,6 +97,8 @@ SIGNATURES = {
     "fjsp_env_create_generated_dynamic": (C.c_int, [C.POINTER(GenDynamic), _i32, _i32, _i32, _u64, _u64, _pp]),
     "fjsp_env_instance_read_dynamic": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_i32 * 2)]),
     "fjsp_env_regenerate": (C.c_int, [_vp, _u64, _u64]),
+    "fjsp_env_regenerate_masked": (C.c_int, [_vp, _vp, _u64, _vp]),
+    "fjsp_env_instance_seed": (C.c_int, [_vp, _i32, C.POINTER(_u64)]),
     "fjsp_env_generated_stats": (C.c_int, [_vp, C.POINTER(_i64 * 4)]),
     "fjsp_env_generated_times": (C.c_int, [_vp, C.POINTER(_dbl * 5)]),
     "fjsp_env_generated_stats2": (C.c_int, [_vp, C.POINTER(_i64 * 6), C.POINTER(_dbl * 6)]),

@@ -275,6 +275,40 @@ class EnvBatch(object):
         self.step_bytes = int(self._lib.fjsp_env_step_bytes(self._h))
         return self
 
+    def regenerate_masked(self, seed_base, mask=None):
+        """New instances in place for part of the batch (fjsp_env_regenerate_masked): instance i with mask[i] != 0 (a bool /
+        uint8 tensor [n_inst] on the batch's device) becomes that of seed seed_base + first_env + i, and the envs that play it
+        are left done with their random streams started over (call reset(mask_of_those_envs)); every other env plays on
+        undisturbed.  mask=None: the finished ones -- instance i iff every env q with q % n_inst == i is done.  Returns the
+        applied mask, a uint8 device tensor [n_inst].  Synchronises.  After a failure (FjspError names the instance and its
+        seed) the batch refuses every call until a regenerate succeeds; the next regenerate_masked makes the failed call's
+        instances too."""
+        if self.gen_params is None:
+            raise _capi.FjspError(_capi.FJSP_E_STATE, "regenerate_masked(): the batch was not made by EnvBatch.generated")
+        p_mask = None
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.n_inst,) \
+                    or mask.device != self.device:
+                raise ValueError("regenerate_masked(): mask must be a bool / uint8 tensor [%d] on %s" % (self.n_inst, self.device))
+            mask = mask.to(torch.uint8).contiguous()
+            p_mask = _ptr(mask)
+        applied = torch.zeros(self.n_inst, dtype=torch.uint8, device=self.device)
+        # (the call synchronises the device first, so the mask and the zeros above are there when its own stream reads them)
+        rc = self._lib.fjsp_env_regenerate_masked(self._h, p_mask, (int(seed_base) + self.first_env) & (2 ** 64 - 1), _ptr(applied))
+        # the cached rows of the refreshed envs are those of the old instances, whatever the outcome
+        envs = applied.to(torch.bool).repeat((self.N + self.n_inst - 1) // self.n_inst)[:self.N]
+        self.state[envs] = 0.0; self.reward[envs] = 0.0; self.done[envs] = 1
+        check(rc)
+        self.step_bytes = int(self._lib.fjsp_env_step_bytes(self._h))
+        return applied
+
+    def instance_seed(self, i):
+        """The seed instance i of a generated batch was made of last (fjsp_env_instance_seed), without the first_env shift:
+        seed_base + i of the generated() / regenerate() / regenerate_masked() that made it."""
+        out = C.c_uint64()
+        check(self._lib.fjsp_env_instance_seed(self._h, int(i), C.byref(out)))
+        return (int(out.value) - self.first_env) & (2 ** 64 - 1)
+
     def instance_dims(self, i):
         """dict(R, M, K, S, jobs0, jobs) of instance i, from the InstanceSet or, for a generated batch, the device."""
         if self.instances is not None:

@@ -208,7 +208,8 @@ struct LaunchPlan {
 GroupBuild group_build(const DevBatch &b, bool fused, const LaunchPlan &p);
 
 // kernel launchers (fjsp_kernels.hip); all asynchronous on `st`, 0 = launched
-int launch_fluid_tables(const DevBatch &b, hipStream_t st);
+// ids != nullptr: the tables of the `count` listed instances alone
+int launch_fluid_tables(const DevBatch &b, hipStream_t st, const uint32_t *ids = nullptr, int count = 0);
 int launch_reset(const DevBatch &b, const uint8_t *mask, double *state, hipStream_t st);
 // row-kernel batches go to launch_step_group unless `ready` is given
 // ready (nullable, multi-order batches): asynchronous arrival service, see fjsp_env_step_async

@@ -72,8 +72,8 @@ struct fjsp_env {
     // handles of fjsp_env_create_generated* only (fjsp_generate.hip): the device generator's buffers and parameters.  Such a
     // handle has no host instance set (src == nullptr); a multi-order one keeps lp_mirror for its host arrival LPs.
     fjsp::GenState *gen = nullptr;
-    std::vector<fjsp::RecordHead> lp_mirror;   // [n_inst] the records' heads as of the last regenerate; empty: not gathered (refresh_lp_mirror)
-    bool gen_failed = false;    // the last fjsp_env_regenerate failed: reset / step / rollout are refused until one succeeds
+    std::vector<fjsp::RecordHead> lp_mirror;   // [n_inst] the records' heads as of the last regenerate (a masked one regathers its own); empty: not gathered (refresh_lp_mirror)
+    bool gen_failed = false;    // the last fjsp_env_regenerate / _regenerate_masked failed: reset / step / rollout are refused until one succeeds
 };
 
 namespace fjsp {

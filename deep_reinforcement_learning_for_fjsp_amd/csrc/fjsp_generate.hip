@@ -31,6 +31,11 @@
 // GenDynArgs::redraws times -- and generate_machine_kernel behind it: the powers, idle powers and breakdown windows of the
 // seed the instance was made of, every draw at a position that is a function of its indices (fjsp_gen_machine), so the
 // lanes need no chain but the running end of a machine's own windows.  The other handles launch neither.
+//
+// Part of a batch (fjsp_env_regenerate_masked): generate_list_kernel compacts a mask over the instances -- or the envs' done
+// flags -- into an ascending list, generate_clear_kernel zeroes the listed records and their envs' in place of the whole
+// refill's memsets, and the kernels above run over the list: every other record keeps its bytes and its envs play on.  Every
+// instance is made of its own seed (GenArgs::seeds), which the snapshot fingerprint follows (gen_hash).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,8 +67,9 @@ struct GenInfo {
 static_assert(sizeof(GenInfo) == 48, "GenInfo is twelve words");
 
 // The words of GenArgs::counts, shared by the kernels and the host: the lengths of fit_ids and of host_ids, the largest fitting
-// tableau (bytes of LDS), the first instance whose LP left no rate (0xFFFFFFFF: none), the length of glob_ids
-enum GenCount : int { kCountFit, kCountHost, kCountLdsMax, kCountFailed, kCountGlob, kGenCounts };
+// tableau (bytes of LDS), the first instance whose LP left no rate (0xFFFFFFFF: none), the length of glob_ids, the length of
+// GenArgs::list (a masked refill: generate_list_kernel)
+enum GenCount : int { kCountFit, kCountHost, kCountLdsMax, kCountFailed, kCountGlob, kCountListed, kGenCounts };
 
 struct GenArgs {
     fjsp_gen_params g;       // ranged: g.M and g.DDT are not read
@@ -89,6 +95,11 @@ struct GenArgs {
     int32_t allow_global;
     uint32_t *glob_ids;      // [n_inst]
     uint16_t *lp_in_glob;    // [slot of glob_ids][2][KP]
+    // every instance is made of its own seed: seed_base + i of the call that made it last
+    uint64_t *seeds;         // [n_inst]
+    // a masked refill (fjsp_env_regenerate_masked): the instances it makes, ascending, counts[kCountListed] of them; the
+    // generator kernels then run one wave per listed instance.  nullptr: every instance
+    const uint32_t *list;
 };
 
 // What a dynamic handle's kernels take beside GenArgs (whose class_fjsp is 1 there: MO_DFJSP shares SO_DFJSP's due dates and
@@ -127,6 +138,14 @@ __device__ inline double gen_uniform(uint64_t seed, uint32_t i, double lo, doubl
     return lo + (hi - lo) * ((double)(gen_draw(seed, i) >> 11) * (1.0 / 9007199254740992.0));
 }
 constexpr int kGenMaxS = FJSP_GEN_MAX_ORDERS;
+// The instance of workgroup blockIdx.x of a generator kernel: its own number, or on a masked refill the entry of the list;
+// -1: none (the grid covers every instance, the list's length stays on the device until the call's one read-back)
+__device__ inline int gen_listed(const DevBatch &b, const GenArgs &a) {
+    const uint32_t slot = blockIdx.x;
+    if (slot >= (uint32_t)b.n_inst || (a.list && slot >= a.counts[kCountListed])) return -1;
+    const uint32_t inst = a.list ? a.list[slot] : slot;
+    return inst < (uint32_t)b.n_inst ? (int)inst : -1;
+}
 }  // namespace
 
 // One wave per instance.  DYN (a dynamic handle, d given): the shop is drawn again, from the next seed of the instance's
@@ -144,10 +163,10 @@ __device__ __forceinline__ void generate_pack(const DevBatch &b, const GenArgs &
     __shared__ int32_t s_hdr[8];                     // R, K, status, nx, first count draw, nj, delivery, ops
     __shared__ double s_dl[kGenMaxS];                // arrive + gap of order s, then sorted
     __shared__ int32_t s_arr[kGenMaxS], s_del[kGenMaxS];     // time_arrive_s, delivery_s (ascending)
-    const int inst = (int)blockIdx.x, l = (int)threadIdx.x;
-    if (inst >= b.n_inst) return;
+    const int l = (int)threadIdx.x, inst = gen_listed(b, a);
+    if (inst < 0) return;
     const fjsp_gen_params &g = a.g;
-    const uint64_t seed0 = a.seed_base + (uint64_t)inst;
+    const uint64_t seed0 = a.seeds[inst];
     const int MP = b.MP, KP = b.KP;
     unsigned char *rec = b.inst + (size_t)inst * b.L.i_stride;
     const Layout &L = b.L;
@@ -358,8 +377,8 @@ __global__ __launch_bounds__(kWave) void generate_pack_dynamic_kernel(DevBatch b
 // the static state row).  K, M and the eligible pairs are the record's.
 __global__ __launch_bounds__(kWave) void generate_machine_kernel(DevBatch b, GenArgs a, GenDynArgs d) {
     __shared__ uint16_t s_w[kMaxM];                  // windows of machine m
-    const int inst = (int)blockIdx.x, l = (int)threadIdx.x;
-    if (inst >= b.n_inst || a.info[inst].status != 0) return;
+    const int l = (int)threadIdx.x, inst = gen_listed(b, a);
+    if (inst < 0 || a.info[inst].status != 0) return;
     unsigned char *rec = b.inst + (size_t)inst * b.L.i_stride;
     const InstHeader h = *reinterpret_cast<const InstHeader *>(rec);
     const int K = h.K, M = h.M, MP = b.MP, W = d.mc.W_max;
@@ -449,7 +468,7 @@ __global__ __launch_bounds__(kWave) void generate_finish_kernel(DevBatch b, GenA
             if ((kB[k] & 0xFFu) == 0u) { const double d = (double)(kA[k] >> 16) - N_ave; va = va + d * d; }
         for (int k = 0; k < K; ++k)
             if ((kB[k] & 0xFFu) == 0u) { const double d = (double)((kB[k] >> 8) & 0xFFu) - J_ave; vc = vc + d * d; }
-        ss[0] = gen_ddt(a, a.seed_base + (uint64_t)inst); ss[1] = (double)M; ss[2] = (double)R; ss[3] = N_ave;
+        ss[0] = gen_ddt(a, a.seeds[inst]); ss[1] = (double)M; ss[2] = (double)R; ss[3] = N_ave;
         ss[4] = sqrt(va / (double)R); ss[5] = J_ave; ss[6] = sqrt(vc / (double)R);
     }
 }
@@ -466,11 +485,75 @@ __global__ __launch_bounds__(256) void generate_gather_kernel(DevBatch b, const 
 }
 
 // Every env as a create leaves it: done, so that a step before the reset is flagged; the row kernels' per-env operation count.
-__global__ __launch_bounds__(256) void generate_mark_done_kernel(DevBatch b, uint8_t *kenv) {
+// env_mask != nullptr (a masked refill): the envs it marks alone.
+__global__ __launch_bounds__(256) void generate_mark_done_kernel(DevBatch b, uint8_t *kenv, const uint8_t *env_mask) {
     const int env = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (env >= b.N) return;
+    if (env >= b.N || (env_mask && env_mask[env] == 0)) return;
     env_ptr<EnvScalars>(b, env, 0)->done = 1;
     if (kenv) kenv[env] = (uint8_t)inst_ptr<const InstHeader>(b, env % b.n_inst, 0)->K;
+}
+
+// Every instance's seed of a whole refill.
+__global__ __launch_bounds__(256) void generate_seeds_kernel(DevBatch b, GenArgs a) {
+    const int inst = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (inst < b.n_inst) a.seeds[inst] = a.seed_base + (uint64_t)inst;
+}
+
+// A masked refill's list, by one workgroup of sixteen waves over tiles of 1024 instances: instance i is on iff mask[i] != 0 --
+// mask == nullptr: iff every env that plays it is done -- or pending[i] != 0 (the instances a failed call left half made).
+// A wave's ballot gives a lane its place among the wave's, the waves' counts in LDS its wave's place in the tile, the
+// running sum the tile's: the list is ascending and takes no atomics.  Also the seeds of the listed instances, the mask that
+// was applied (refreshed, u8[n_inst], nullable), the same per env (env_mask, u8[N]: launch_reset's mask) and the list's
+// length.
+__global__ __launch_bounds__(1024) void generate_list_kernel(DevBatch b, GenArgs a, const uint8_t *mask, const uint8_t *pending, uint32_t *list,
+                                                            uint8_t *refreshed, uint8_t *env_mask) {
+    __shared__ uint32_t s_wave[16];
+    const int t = (int)threadIdx.x, lane = t & (kWave - 1), wv = t >> 6;
+    uint32_t base = 0;
+    for (int i0 = 0; i0 < b.n_inst; i0 += 1024) {
+        const int i = i0 + t;
+        bool on = false;
+        if (i < b.n_inst) {
+            if (mask) on = mask[i] != 0;
+            else {
+                on = true;
+                for (int q = i; q < b.N; q += b.n_inst) on = on && env_ptr<const EnvScalars>(b, q, 0)->done != 0;
+            }
+            if (pending && pending[i] != 0) on = true;
+        }
+        const unsigned long long bal = __ballot(on);
+        if (lane == 0) s_wave[wv] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (int w = 0; w < 16; ++w) { const uint32_t c = s_wave[w]; before += w < wv ? c : 0u; total += c; }
+        if (i < b.n_inst) {
+            if (on) {
+                list[base + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)i;
+                a.seeds[i] = a.seed_base + (uint64_t)i;
+            }
+            if (refreshed) refreshed[i] = on ? 1 : 0;
+            for (int q = i; q < b.N; q += b.n_inst) env_mask[q] = on ? 1 : 0;
+        }
+        base += total;
+        __syncthreads();          // s_wave is written again
+    }
+    if (t == 0) a.counts[kCountListed] = base;
+}
+
+// One workgroup per listed instance of a masked refill: its record, the records of the envs that play it and their dispatch
+// records to zero -- what the whole refill's memsets do to the slabs.
+__global__ __launch_bounds__(256) void generate_clear_kernel(DevBatch b, GenArgs a, SchedRec rec) {
+    const int t = (int)threadIdx.x, inst = gen_listed(b, a);
+    if (inst < 0) return;
+    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+    uint4 *ir = reinterpret_cast<uint4 *>(b.inst + (size_t)inst * b.L.i_stride);
+    for (uint32_t w = (uint32_t)t; w < b.L.i_stride / 16u; w += 256u) ir[w] = zero;
+    for (int q = inst; q < b.N; q += b.n_inst) {
+        uint4 *er = reinterpret_cast<uint4 *>(b.envs + (size_t)q * b.L.e_stride);
+        for (uint32_t w = (uint32_t)t; w < b.L.e_stride / 16u; w += 256u) er[w] = zero;
+        if (rec.rec)
+            for (int s = t; s < rec.cap; s += 256) rec.rec[(size_t)s * (size_t)b.N + (size_t)q] = zero;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
@@ -522,7 +605,16 @@ struct GenState {
     int64_t stats[kGenStats] = {};
     double ms[kGenTimes] = {};
     LpGlobalPool pool;                   // FJSP_LP_IMPL=global only (nothing of that route is allocated otherwise)
+    // per instance: the seed it was made of last (GenArgs::seeds on the host), and whether a failed call left it half made --
+    // the next masked refill takes those too, a whole one takes every instance anyway
+    std::vector<uint64_t> seeds;
+    std::vector<uint8_t> unfinished;
+    // a masked refill (generate_list_kernel): the list and pinned, the applied mask per env, the upload of `unfinished`
+    uint32_t *d_list = nullptr, *h_list = nullptr;
+    uint8_t *d_env_mask = nullptr, *d_pending = nullptr, *h_pending = nullptr;
 };
+// What fjsp_env_regenerate_masked passes to the refill; nullptr there: the whole batch
+struct MaskedCall { const uint8_t *d_mask; uint8_t *d_refreshed; };
 
 void generated_release(fjsp_env *e) {
     if (!e || !e->gen) return;
@@ -589,7 +681,9 @@ int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_
     return FJSP_OK;
 }
 
-uint64_t gen_hash(const GenArgs &a, const GenDynArgs *d, int n_inst, uint64_t seed_base) {
+// The fingerprint of a generated handle's instances: its parameters and its seeds.  Seeds s + i for one s (a create, a whole
+// refill, a masked one of every instance) mix s alone; any other seeds a tag and all of them.
+uint64_t gen_hash(const GenArgs &a, const GenDynArgs *d, int n_inst, const std::vector<uint64_t> &seeds) {
     const fjsp_gen_params &g = a.g;
     const int class_fjsp = a.class_fjsp;
     uint64_t h = 1469598103934665603ULL;
@@ -600,7 +694,14 @@ uint64_t gen_hash(const GenArgs &a, const GenDynArgs *d, int n_inst, uint64_t se
     // (class_fjsp: SO_DFJSP runs as variant SO_FJSSP with other due dates, so the variant alone does not tell the two apart)
     const int32_t iv[12] = {g.R_min, g.R_max, g.J_min, g.J_max, g.M, g.p_min, g.p_max, g.N_min, g.N_max, g.S, n_inst, class_fjsp};
     const double dv[3] = {g.DDT, g.t_si_min, g.t_si_max};
-    mix(iv, sizeof(iv)); mix(dv, sizeof(dv)); mix(&seed_base, sizeof(seed_base));
+    mix(iv, sizeof(iv)); mix(dv, sizeof(dv));
+    bool affine = true;
+    for (size_t i = 0; i < seeds.size(); ++i) affine = affine && seeds[i] == seeds[0] + (uint64_t)i;
+    if (affine) mix(&seeds[0], sizeof(uint64_t));
+    else {
+        const int32_t tag = 0x53454544;
+        mix(&tag, sizeof(tag)); mix(seeds.data(), seeds.size() * sizeof(uint64_t));
+    }
     if (a.ranged) {     // a tag and the ranges: never the fingerprint of a fixed-parameter handle (g.M, g.DDT are zeroed there)
         const int32_t rv[3] = {0x52414E47, a.M_min, a.M_max};
         const double rd[2] = {a.DDT_min, a.DDT_max};
@@ -649,7 +750,7 @@ int fail_generate(fjsp_env *e, int rc, const std::string &msg) {
     set_error(msg);
     return rc;
 }
-std::string who(uint64_t seed_base, size_t i) { return "instance " + std::to_string(i) + " (seed " + std::to_string(seed_base + i) + ")"; }
+std::string who(const GenState &G, size_t i) { return "instance " + std::to_string(i) + " (seed " + std::to_string(G.seeds[i]) + ")"; }
 int launch_failed(const char *text) { set_error(text); return FJSP_E_HIP; }
 
 // The host route's producer: the record heads of ids[c0, c0 + n) read back, their order-0 LPs (solve_order0) on the
@@ -678,7 +779,7 @@ int solve_on_host(fjsp_env *e, const LpRoute &r, int c0, int n, const std::strin
             for (int m = 0; m < M; ++m) out[(size_t)k * MP + m] = x[(size_t)k * M + m];
         return true;
     });
-    if (bad) return fail_generate(e, FJSP_E_LP, call + ": the fluid LP of " + who(G.a.seed_base, G.h_host_ids[c0 + bad.index]) + " failed");
+    if (bad) return fail_generate(e, FJSP_E_LP, call + ": the fluid LP of " + who(G, G.h_host_ids[c0 + bad.index]) + " failed");
     HIP_TRY(hipMemcpyAsync(r.d_stage, G.h_stage, (size_t)n * KP * MP * 8, hipMemcpyHostToDevice, r.st));
     return FJSP_OK;
 }
@@ -715,51 +816,78 @@ int run_route(fjsp_env *e, const LpRoute &r, int n_total, const std::string &cal
 
 }  // namespace
 
-// The heads of all records into e->lp_mirror, in rounds of GenState::chunk through the host route's gather buffers.  Called
-// with no regenerate under way.
-int refresh_lp_mirror(fjsp_env *e) {
+// The heads of records into mirror, in rounds of GenState::chunk through the host route's gather buffers: of all records, or
+// of the `listed` first entries of a masked refill's list (mirror then holds every instance already).
+static int gather_heads(fjsp_env *e, std::vector<RecordHead> &mirror, int count, bool listed) {
     GenState &G = *e->gen;
     const DevBatch &b = e->b;
     const size_t row = row_bytes(G);
-    std::vector<RecordHead> mirror((size_t)b.n_inst);
-    for (int c0 = 0; c0 < b.n_inst; c0 += G.chunk) {
-        const int n = std::min(G.chunk, b.n_inst - c0);
+    for (int c0 = 0; c0 < count; c0 += G.chunk) {
+        const int n = std::min(G.chunk, count - c0);
         const size_t words = (size_t)n * (row / 16);
-        DevBatch part = b;                               // instances c0 .. c0 + n - 1, by position
-        part.inst = b.inst + (size_t)c0 * b.L.i_stride;
-        if (launch(generate_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, G.st_host, part, (const uint32_t *)nullptr, n, G.d_head, G.head16, G.tail0, G.tail16) != 0)
+        DevBatch part = b;                               // not listed: instances c0 .. c0 + n - 1, by position
+        if (!listed) part.inst = b.inst + (size_t)c0 * b.L.i_stride;
+        if (launch(generate_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, G.st_host, part, listed ? (const uint32_t *)(G.d_list + c0) : (const uint32_t *)nullptr, n,
+                   G.d_head, G.head16, G.tail0, G.tail16) != 0)
             return launch_failed("generate_gather_kernel launch failed");
         HIP_TRY(hipMemcpyAsync(G.h_head, G.d_head, words * 16, hipMemcpyDeviceToHost, G.st_host));
         HIP_TRY(hipStreamSynchronize(G.st_host));
-        for (int q = 0; q < n; ++q) decode_row(b, G, reinterpret_cast<const unsigned char *>(G.h_head) + (size_t)q * row, mirror[(size_t)(c0 + q)]);
+        for (int q = 0; q < n; ++q)
+            decode_row(b, G, reinterpret_cast<const unsigned char *>(G.h_head) + (size_t)q * row, mirror[listed ? (size_t)G.h_list[c0 + q] : (size_t)(c0 + q)]);
     }
+    return FJSP_OK;
+}
+
+// The heads of all records into e->lp_mirror.  Called with no regenerate under way.
+int refresh_lp_mirror(fjsp_env *e) {
+    std::vector<RecordHead> mirror((size_t)e->b.n_inst);
+    if (const int rc = gather_heads(e, mirror, e->b.n_inst, false)) return rc;
     e->lp_mirror.swap(mirror);
     return FJSP_OK;
 }
 
 namespace {
-// The whole refill: records, LPs, tables, reset.  Synchronous; on the handle's device.
-int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::string &call) {
+// The refill: records, LPs, tables, reset -- of every instance and env (mc == nullptr: fjsp_env_regenerate, the creates), or
+// of the instances a masked call lists and the envs that play them (fjsp_env_regenerate_masked; rng_seed is not read: those
+// envs' streams start over from the handle's).  Synchronous; on the handle's device.
+int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::string &call, const MaskedCall *mc) {
     GenState &G = *e->gen;
     DevBatch &b = e->b;
     const size_t N = (size_t)b.N, n_inst = (size_t)b.n_inst;
     const auto t_call = Clock::now();
     HIP_TRY(hipDeviceSynchronize());         // steps still queued on any stream read the records this call rewrites
+    const bool was_failed = e->gen_failed;
     e->gen_failed = true;                    // until the call has gone through
     G.a.seed_base = seed_base;
-    b.rng_seed = rng_seed;
+    G.a.list = mc ? G.d_list : nullptr;
+    if (!mc) b.rng_seed = rng_seed;
     std::fill(G.stats, G.stats + kGenStats, 0);
     std::fill(G.ms, G.ms + kGenTimes, 0.0);
     hipStream_t st = G.st_dev;
     // ---- clear
-    HIP_TRY(hipMemsetAsync(b.inst, 0, n_inst * b.L.i_stride, st));
-    HIP_TRY(hipMemsetAsync(b.envs, 0, N * b.L.e_stride, st));       // the draw counters too: the env streams start over
-    if (b.mord) HIP_TRY(hipMemsetAsync(b.pending_count, 0, 4, st)); // no env is parked at an arrival
     HIP_TRY(hipMemsetAsync(G.a.counts, 0, kGenCounts * sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(G.a.counts + kCountFailed, 0xFF, sizeof(uint32_t), st));
     for (const LpRoute &r : G.route) if (r.d_solved) HIP_TRY(hipMemsetAsync(r.d_solved, 0, sizeof(LpCounters), st));
     HIP_TRY(hipMemsetAsync(G.d_lp_err, 0, sizeof(LpErrWord), st));
-    if (e->sched.rec) HIP_TRY(hipMemsetAsync(e->sched.rec, 0, (size_t)e->sched.cap * N * sizeof(uint4), st));
+    if (!mc) {
+        std::fill(G.unfinished.begin(), G.unfinished.end(), (uint8_t)1);
+        HIP_TRY(hipMemsetAsync(b.inst, 0, n_inst * b.L.i_stride, st));
+        HIP_TRY(hipMemsetAsync(b.envs, 0, N * b.L.e_stride, st));       // the draw counters too: the env streams start over
+        if (b.mord) HIP_TRY(hipMemsetAsync(b.pending_count, 0, 4, st)); // no env is parked at an arrival
+        if (e->sched.rec) HIP_TRY(hipMemsetAsync(e->sched.rec, 0, (size_t)e->sched.cap * N * sizeof(uint4), st));
+        if (launch(generate_seeds_kernel, dim3((unsigned)((n_inst + 255) / 256)), dim3(256), 0, st, b, G.a) != 0) return launch_failed("generate_seeds_kernel launch failed");
+    } else {
+        // the list (with what a failed call left half made), then the listed records and their envs' to zero
+        const bool pending = std::find(G.unfinished.begin(), G.unfinished.end(), (uint8_t)1) != G.unfinished.end();
+        if (pending) {
+            std::copy(G.unfinished.begin(), G.unfinished.end(), G.h_pending);
+            HIP_TRY(hipMemcpyAsync(G.d_pending, G.h_pending, n_inst, hipMemcpyHostToDevice, st));
+        }
+        if (launch(generate_list_kernel, dim3(1), dim3(1024), 0, st, b, G.a, mc->d_mask, pending ? (const uint8_t *)G.d_pending : (const uint8_t *)nullptr, G.d_list,
+                   mc->d_refreshed, G.d_env_mask) != 0 ||
+            launch(generate_clear_kernel, dim3((unsigned)n_inst), dim3(256), 0, st, b, G.a, e->sched) != 0)
+            return launch_failed("generate_list_kernel / generate_clear_kernel launch failed");
+    }
     // ---- pack
     HIP_TRY(hipEventRecord(G.ev_start, st));
     if (G.dynamic) {
@@ -768,41 +896,54 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
             return launch_failed("generate_pack_dynamic_kernel / generate_machine_kernel launch failed");
     } else if (launch(generate_pack_kernel, dim3((unsigned)n_inst), dim3(kWave), 0, st, b, G.a) != 0) return launch_failed("generate_pack_kernel launch failed");
     HIP_TRY(hipEventRecord(G.ev_packed, st));
-    // ---- the call's one read-back before the LPs: status words, sizes, the lists' lengths, the host list; validate
+    // ---- the call's one read-back before the LPs: status words, sizes, the lists' lengths, the host list, a masked call's list; validate
     HIP_TRY(hipMemcpyAsync(G.h_info, G.a.info, n_inst * sizeof(GenInfo), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, kGenCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(G.h_host_ids, G.a.host_ids, n_inst * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (G.dynamic) HIP_TRY(hipMemcpyAsync(G.h_seed_used, G.d.seed_used, n_inst * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (mc) HIP_TRY(hipMemcpyAsync(G.h_list, G.d_list, n_inst * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    double bytes = 0.0;
-    for (size_t i = 0; i < n_inst; ++i) {
+    const size_t n_made = mc ? std::min<size_t>(G.h_counts[kCountListed], n_inst) : n_inst;
+    const auto made = [&](size_t s) { return mc ? (size_t)G.h_list[s] : s; };      // the s-th instance of this call, ascending
+    if (n_made == 0) {                       // an empty mask: nothing was written but the (all zero) applied masks
+        e->gen_failed = was_failed;
+        G.ms[kMsTotal] = ms_since(t_call);
+        return FJSP_OK;
+    }
+    for (size_t s = 0; s < n_made; ++s) { G.seeds[made(s)] = seed_base + made(s); G.unfinished[made(s)] = 1; }
+    for (size_t s = 0; s < n_made; ++s) {
+        const size_t i = made(s);
         const GenInfo &f = G.h_info[i];
         if (f.status == FJSP_E_UNSUPPORTED && G.dynamic)
-            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": MO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference) in each of " +
+            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(G, i) + ": MO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference) in each of " +
                                  std::to_string(G.d.redraws + 1) + " attempts (redraws = " + std::to_string(G.d.redraws) + ")");
         if (f.status == FJSP_E_UNSUPPORTED)
-            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
+            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(G, i) + ": SO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference)");
         if (f.status != 0)
-            return fail_generate(e, f.status, call + ": " + who(seed_base, i) + ": a draw left the record's fields (internal error)");
+            return fail_generate(e, f.status, call + ": " + who(G, i) + ": a draw left the record's fields (internal error)");
         if (f.ops > e->ops_max || f.M < 1 || f.M > b.MP || f.S < 1 || f.S > b.SP)
-            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(seed_base, i) + ": sizes disagree with the host's (internal error)");
+            return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": " + who(G, i) + ": sizes disagree with the host's (internal error)");
+    }
+    double bytes = 0.0;                      // the mean over all instances, those this call left alone too
+    for (size_t i = 0; i < n_inst; ++i) {
+        const GenInfo &f = G.h_info[i];
         bytes += step_bytes(b, f.K, f.nj, f.M);
         if (G.dynamic) bytes += f.M * 14.0 + 2.0 * sizeof(DynScalars);      // step_bytes_of (fjsp_env.hip)
     }
     size_t listed = 0;
     bool routed = true;      // no instance is on a list this handle has no route for
     for (const LpRoute &r : G.route) { listed += G.h_counts[r.length]; routed = routed && (r.present() || G.h_counts[r.length] == 0); }
-    if (listed != n_inst || !routed) return fail_generate(e, FJSP_E_HIP, call + ": the LP lists do not cover the instances (internal error)");
+    if (listed != n_made || !routed) return fail_generate(e, FJSP_E_HIP, call + ": the LP lists do not cover the instances (internal error)");
     const int n_host = (int)G.h_counts[kCountHost];
     if (e->plan.lp_device_forced == 1 && n_host > 0) {
         const uint32_t i = *std::min_element(G.h_host_ids, G.h_host_ids + n_host);
         const GenInfo &f = G.h_info[i];
-        return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": FJSP_LP_IMPL=device, but the order-0 tableau of " + who(seed_base, i) +
+        return fail_generate(e, FJSP_E_UNSUPPORTED, call + ": FJSP_LP_IMPL=device, but the order-0 tableau of " + who(G, i) +
                              " does not fit: " + std::to_string(f.lds) + " bytes of LDS (limit " +
                              std::to_string(kLpLdsLimit) + "), " + std::to_string(lp_max_columns(f.K, f.M, f.nx, f.R)) + " columns (limit " +
                              std::to_string(kLpLdsColumns) + ")");
     }
-    for (size_t i = 0; i < n_inst; ++i) { e->inst_K[i] = G.h_info[i].K; e->inst_M[i] = G.h_info[i].M; }
+    for (size_t s = 0; s < n_made; ++s) { const size_t i = made(s); e->inst_K[i] = G.h_info[i].K; e->inst_M[i] = G.h_info[i].M; }
     e->step_bytes = (int64_t)(bytes / (double)n_inst + 0.5);
     // ---- the routes: the device's on their streams, then the host's while the device works on its lists
     for (const LpRoute &r : G.route) {
@@ -811,10 +952,12 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
         if (const int rc = run_route(e, r, (int)G.h_counts[r.length], call)) return rc;
         if (r.producer == LpRoute::kHost && n_host) G.ms[kMsLpHost] = ms_since(t_route);
     }
-    // ---- the fluid tables, one reset of every env (publishes i_obs0), every env done again: as upload_batch leaves them
+    // ---- the fluid tables, one reset of every env made (publishes i_obs0), those envs done again: as upload_batch leaves them
     const dim3 gN((unsigned)((N + 255) / 256));
-    if (launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, G.d_kenv) != 0 || launch_fluid_tables(b, st) != 0 ||
-        launch_reset(b, nullptr, nullptr, st) != 0 || launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, (uint8_t *)nullptr) != 0)
+    const uint8_t *envs = mc ? G.d_env_mask : nullptr;
+    if (launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, G.d_kenv, envs) != 0 ||
+        launch_fluid_tables(b, st, mc ? G.d_list : nullptr, (int)n_made) != 0 ||
+        launch_reset(b, envs, nullptr, st) != 0 || launch(generate_mark_done_kernel, gN, dim3(256), 0, st, b, (uint8_t *)nullptr, envs) != 0)
         return launch_failed("fluid_tables_kernel / reset_kernel launch failed");
     // ---- the counters
     HIP_TRY(hipMemcpyAsync(G.h_counts, G.a.counts, kGenCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -831,23 +974,29 @@ int regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed, const std::st
     if (n_glob > 0) G.ms[kMsLpGlobal] = ms_between(glob.ev_begin, glob.ev_end);
     const uint32_t failed = G.h_counts[kCountFailed], lp_err = G.h_back->lp_err.code;
     if (failed != 0xFFFFFFFFu || lp_err != 0u)
-        return fail_generate(e, FJSP_E_LP, failed != 0xFFFFFFFFu ? call + ": the fluid LP of " + who(seed_base, failed) + " failed"
+        return fail_generate(e, FJSP_E_LP, failed != 0xFFFFFFFFu ? call + ": the fluid LP of " + who(G, failed) + " failed"
                                                                  : call + ": a fluid LP failed on the device (code " + std::to_string(lp_err) + ")");
-    G.stats[kStatInstances] = (int64_t)n_inst; G.stats[kStatLpLds] = G.h_counts[kCountFit]; G.stats[kStatLpHost] = n_host;
+    G.stats[kStatInstances] = (int64_t)n_made; G.stats[kStatLpLds] = G.h_counts[kCountFit]; G.stats[kStatLpHost] = n_host;
     G.stats[kStatDevicePivots] = (int64_t)lds.h_solved->pivots;
     if (glob.present()) {
         G.stats[kStatLpGlobal] = n_glob; G.stats[kStatGlobalPivots] = (int64_t)glob.h_solved->pivots;
         G.stats[kStatDevicePivots] += G.stats[kStatGlobalPivots];
     }
-    e->inst_hash = gen_hash(G.a, G.dynamic ? &G.d : nullptr, b.n_inst, seed_base);
+    e->inst_hash = gen_hash(G.a, G.dynamic ? &G.d : nullptr, b.n_inst, G.seeds);
     if (b.mord) {
         // the memo of solved arrival LPs is keyed by the instance index, which names another instance now (the counters of
         // solved LPs and pivots keep running); the host services read the new records' heads
         arrivals_forget(e->arr);
-        e->lp_mirror.clear();
-        if (!e->arr.lp_device || e->arr.ring)
-            if (const int rc = refresh_lp_mirror(e)) return rc;
+        const bool mirrored = !e->arr.lp_device || e->arr.ring;
+        if (mc && mirrored && e->lp_mirror.size() == n_inst) {
+            if (const int rc = gather_heads(e, e->lp_mirror, (int)n_made, true)) return rc;
+        } else {
+            e->lp_mirror.clear();
+            if (mirrored)
+                if (const int rc = refresh_lp_mirror(e)) return rc;
+        }
     }
+    std::fill(G.unfinished.begin(), G.unfinished.end(), (uint8_t)0);
     e->gen_failed = false;
     G.ms[kMsTotal] = ms_since(t_call);
     return FJSP_OK;
@@ -950,6 +1099,9 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
         !dev_alloc(e.get(), heads, &G.d_head, "hipMalloc record heads") ||
         !dev_alloc(e.get(), sizeof(LpErrWord), &G.d_lp_err, "hipMalloc LP error word") ||
         !dev_alloc(e.get(), sizeof(LpCounters), &lds.d_solved, "hipMalloc LP counters") ||
+        !dev_alloc(e.get(), NI * sizeof(uint64_t), &G.a.seeds, "hipMalloc instance seeds") || !dev_alloc(e.get(), ids, &G.d_list, "hipMalloc refill list") ||
+        !dev_alloc(e.get(), N, &G.d_env_mask, "hipMalloc refill mask") ||
+        !dev_alloc(e.get(), NI, &G.d_pending, "hipMalloc refill mask") || !host_alloc(e.get(), ids, &G.h_list) || !host_alloc(e.get(), NI, &G.h_pending) ||
         (b.grp && !dev_alloc(e.get(), N, &G.d_kenv, "hipMalloc K table")) ||
         (dq && (!dev_alloc(e.get(), NI * sizeof(uint64_t), &G.d.seed_used, "hipMalloc instance seeds") || !host_alloc(e.get(), NI * sizeof(uint64_t), &G.h_seed_used))) ||
         !host_alloc(e.get(), NI * sizeof(GenInfo), &G.h_info) || !host_alloc(e.get(), kGenCounts * sizeof(uint32_t), &G.h_counts) ||
@@ -971,6 +1123,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
             return FJSP_E_HIP;
         for (hipEvent_t *ev : {&glob.ev_begin, &glob.ev_end}) HIP_TRY(hipEventCreate(ev));
     }
+    G.seeds.assign(NI, 0); G.unfinished.assign(NI, 0);
     b.kenv = G.d_kenv;
     for (hipEvent_t *ev : {&G.ev_start, &G.ev_packed, &G.ev_end, &G.ev_joined, &lds.ev_end}) HIP_TRY(hipEventCreate(ev));
     HIP_TRY(hipStreamCreateWithFlags(&G.st_dev, hipStreamNonBlocking));
@@ -978,7 +1131,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     lds.ids = G.a.fit_ids; lds.lp_in = G.a.lp_in; lds.h_solved = &G.h_back->lds; lds.st = G.st_dev;
     glob.ids = G.a.glob_ids; glob.lp_in = G.a.lp_in_glob; glob.h_solved = &G.h_back->glob; glob.st = G.st_host;
     host.ids = G.a.host_ids; host.st = G.st_host;
-    if ((rc = regenerate(e.get(), seed_base, rng_seed, call)) != FJSP_OK) return rc;
+    if ((rc = regenerate(e.get(), seed_base, rng_seed, call, nullptr)) != FJSP_OK) return rc;
     *out = e.release();
     return FJSP_OK;
 }
@@ -1019,7 +1172,27 @@ int fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed) {
         return FJSP_E_STATE;
     }
     DeviceGuard guard(e->device);
-    return regenerate(e, seed_base, rng_seed, "fjsp_env_regenerate");
+    return regenerate(e, seed_base, rng_seed, "fjsp_env_regenerate", nullptr);
+}
+
+int fjsp_env_regenerate_masked(fjsp_env *e, const uint8_t *d_mask, uint64_t seed_base, uint8_t *d_refreshed) {
+    if (!e) { set_error("fjsp_env_regenerate_masked: null env"); return FJSP_E_ARG; }
+    if (!e->gen) { set_error("fjsp_env_regenerate_masked: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    if (!async_idle(e)) {
+        set_error("fjsp_env_regenerate_masked: environments are parked in the asynchronous arrival service; call fjsp_env_arrivals_flush first");
+        return FJSP_E_STATE;
+    }
+    DeviceGuard guard(e->device);
+    const MaskedCall mc{d_mask, d_refreshed};
+    return regenerate(e, seed_base, 0, "fjsp_env_regenerate_masked", &mc);
+}
+
+int fjsp_env_instance_seed(const fjsp_env *e, int32_t i, uint64_t *seed) {
+    if (!e || !seed) { set_error("fjsp_env_instance_seed: null argument"); return FJSP_E_ARG; }
+    if (!e->gen) { set_error("fjsp_env_instance_seed: the batch was not made by fjsp_env_create_generated"); return FJSP_E_STATE; }
+    if (i < 0 || i >= e->b.n_inst) { set_error("fjsp_env_instance_seed: instance index out of range"); return FJSP_E_ARG; }
+    *seed = e->gen->seeds[(size_t)i];
+    return FJSP_OK;
 }
 
 // The three accessors hand out prefixes of GenState::stats and ::ms; `given`: the caller passed the array the call is about

@@ -1553,11 +1553,12 @@ __device__ __forceinline__ double env_step(W<KC, V> &w, const DevBatch *b, int a
 }
 
 // ------------------------------------------------------------------------ kernels
-// update_fluid_parameter (class_FJSSP.py:282-306): one thread per (instance, k).
-__global__ void fluid_tables_kernel(DevBatch b) {
+// update_fluid_parameter (class_FJSSP.py:282-306): one thread per (instance, k).  ids != nullptr: of the `count` instances it
+// lists alone (a generated batch's masked refill).
+__global__ void fluid_tables_kernel(DevBatch b, const uint32_t *ids, int count) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= b.n_inst * b.KP) return;
-    const int inst = idx / b.KP, k = idx % b.KP;
+    if (idx >= (ids ? count : b.n_inst) * b.KP) return;
+    const int inst = ids ? (int)ids[idx / b.KP] : idx / b.KP, k = idx % b.KP;
     const InstHeader h = *inst_ptr<const InstHeader>(b, inst, 0);
     const int MP = b.MP;
     const uint16_t *p = inst_ptr<const uint16_t>(b, inst, b.L.i_p) + (size_t)k * MP;
@@ -1753,9 +1754,9 @@ __global__ void read_kernel(DevBatch b, int64_t *delay, int32_t *makespan, int32
 // dispatchers below pick from the batch -- the argument list is named once, the recording twin gets `rec` appended.
 size_t step_lds_bytes(const DevBatch &b) { return 4 * lds_bytes_per_wave(b.JP, b.MP, b.KP, false); }
 
-int launch_fluid_tables(const DevBatch &b, hipStream_t st) {
-    const int n = b.n_inst * b.KP;
-    return launch(fluid_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b);
+int launch_fluid_tables(const DevBatch &b, hipStream_t st, const uint32_t *ids, int count) {
+    const int n = (ids ? count : b.n_inst) * b.KP;
+    return launch(fluid_tables_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b, ids, count);
 }
 
 // one instantiation per (chunk count, environment variant): the variant is a compile-time

@@ -324,7 +324,27 @@ int  fjsp_env_create_generated_dynamic(const fjsp_gen_dynamic *q, int32_t n_inst
 int  fjsp_env_instance_read_dynamic(fjsp_env *e, int32_t i, int32_t *power, int32_t *idle_power, int32_t *bk_n, int32_t *bk,
                                     uint64_t *seed_used, int32_t dims[2]);
 int  fjsp_env_regenerate(fjsp_env *e, uint64_t seed_base, uint64_t rng_seed);
-/* Of the last create_generated / regenerate: out[0] instances, [1] LPs solved on the device, [2] on the host, [3] pivots
+/* fjsp_env_regenerate for some instances of any generated handle: instance i with d_mask[i] != 0 (u8[n_inst], device)
+ * becomes the instance of seed seed_base + i, and the envs q with q % n_inst == i are left as fjsp_env_regenerate leaves
+ * them -- record zeroed, random stream started over from the handle's rng_seed, recorded dispatches cleared, done.
+ * d_mask == NULL: the finished ones -- instance i iff every env that plays it is done, decided on the device.  d_refreshed
+ * (u8[n_inst], device, nullable) receives the mask that was applied.  Every other instance record, env record and recorded
+ * dispatch keeps its bytes: those envs play on, mid-episode or between order arrivals, as if the call had not happened.
+ * An empty mask is FJSP_OK and changes nothing; a full one leaves what fjsp_env_regenerate(e, seed_base, the handle's
+ * rng_seed) leaves.  Synchronises; FJSP_E_STATE while envs are parked in the asynchronous service; empties the memo of
+ * solved arrival LPs, refills the host mirror's refreshed heads.  fjsp_env_generated_stats* / _times describe the last call
+ * of either kind ([0]: instances refreshed); fjsp_env_step_bytes stays the mean over all instances.
+ * The handle keeps one seed per instance (fjsp_env_instance_seed: seed_base + i of the call that made it last; every
+ * message that names an instance takes its seed from there).  The snapshot fingerprint is a function of these seeds: while
+ * they are s + i for one s it is that of fjsp_env_regenerate(s), otherwise it mixes a tag and all of them, so a snapshot
+ * taken before a call that changed a seed is refused after it.
+ * A failing instance fails the call as it fails fjsp_env_regenerate (same codes, same refusals afterwards).  The instances
+ * the failed call was making are remembered: the next fjsp_env_regenerate_masked makes them as well, from its own
+ * seed_base and whatever its mask says, and reports them in d_refreshed; a whole fjsp_env_regenerate makes all anyway.
+ * A null handle: FJSP_E_ARG; a handle not made by a generated create: FJSP_E_STATE; both before the first HIP call. */
+int  fjsp_env_regenerate_masked(fjsp_env *e, const uint8_t *d_mask, uint64_t seed_base, uint8_t *d_refreshed);
+int  fjsp_env_instance_seed(const fjsp_env *e, int32_t i, uint64_t *seed);
+/* Of the last create_generated / regenerate / regenerate_masked: out[0] instances, [1] LPs solved on the device, [2] on the host, [3] pivots
  * of the device simplex.  fjsp_env_generated_times: milliseconds of its parts -- the generate kernel, the LP launches with
  * their finish kernels, the host route, fluid tables + reset -- and of the whole call.  [0], [1], [3] are HIP-event times on the device route's
  * stream; [2] and [4] are host wall clock, and the host route runs beside the device's LPs, so [2] overlaps [1]: the parts

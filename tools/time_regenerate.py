@@ -2,7 +2,7 @@
 """What a training loop spends on the NEXT batch of instances: the host path against a regenerate on the device.
 
     python tools/time_regenerate.py [--reps 5] [--out profiles/regenerate_timing.jsonl] [--ranges mpppo|ddqn] [--orders da3c|hmpsac]
-                                    [--dynamic] [--envs 4096] [--lp-impl host|device|global]
+                                    [--dynamic] [--envs 4096] [--lp-impl host|device|global] [--masked FRACTION]
 
 For 4096 and 32768 bench_10x5_params instances and 4096 of reference_generator_params(1.0, 10, 1), alternately in one
 process, wall clock between device synchronisations:
@@ -16,7 +16,9 @@ reset alone plays no order arrival, so the arrival service is not in the figure)
 instances.reference_dynamic_ranges("hmpsac") (machine data generated too), and its host path (a) is the route
 examples/train_hmpsac.py's make_train_env runs without --generated: a Python loop per instance with its redraw loop, NumPy
 machine data, solve_fluid, a new BatchedMODFJSP; --envs alone times that many 10x5 instances.  --lp-impl sets FJSP_LP_IMPL around the create of the live handle (the
-library reads it there and nowhere else) and is recorded in the device line.
+library reads it there and nowhere else) and is recorded in the device line.  --masked FRACTION times (b) as
+regenerate_masked(s, mask) + reset(mask) instead, over that share of the instances -- round(FRACTION x N) of them at a fixed
+stride -- with the same split; the host path (a) has no such call and is not run.
 """
 import argparse
 import contextlib
@@ -73,7 +75,10 @@ def main():
     ap.add_argument("--dynamic", action="store_true", help="MO_DFJSP batches of reference_dynamic_ranges('hmpsac') against make_train_env's host route")
     ap.add_argument("--envs", type=int, default=None, help="instances of the --ranges / --orders workload (4096), or of a single 10x5 workload")
     ap.add_argument("--lp-impl", choices=("host", "device", "global"), default=None, help="FJSP_LP_IMPL of the live handle (default: not set)")
+    ap.add_argument("--masked", type=float, default=None, metavar="FRACTION", help="time regenerate_masked + reset(mask) over this share of the instances (0 < FRACTION <= 1)")
     args = ap.parse_args()
+    if args.masked is not None and not 0.0 < args.masked <= 1.0:
+        ap.error("--masked takes a share of the instances in (0, 1]")
     import torch
     from deep_reinforcement_learning_for_fjsp_amd import instances as fi
     from deep_reinforcement_learning_for_fjsp_amd.batch import EnvBatch, VARIANT_MO_DFJSP, VARIANT_SO_FJSSP
@@ -97,9 +102,26 @@ def main():
         live.reset()
         torch.cuda.synchronize()
         host_ms, dev_ms, parts, routes = [], [], [], None
+        mask = None
+        if args.masked is not None:
+            k = max(1, int(round(args.masked * N)))
+            mask = torch.zeros(N, dtype=torch.uint8, device=live.device)
+            mask[torch.div(torch.arange(k, device=live.device) * N, k, rounding_mode="floor")] = 1
         for rep in range(args.reps):
             seed = 1_000_000 * (rep + 1)
             torch.cuda.synchronize()
+            if mask is not None:
+                t0 = time.perf_counter()
+                live.regenerate_masked(seed, mask)
+                live.reset(mask)
+                torch.cuda.synchronize()
+                dev_ms.append((time.perf_counter() - t0) * 1e3)
+                st = live.generated_stats()
+                assert st["instances"] == int(mask.sum()), st
+                parts.append(st["ms"])
+                routes = dict(refreshed=st["instances"], lp_device=st["lp_device"], lp_host=st["lp_host"], lp_global=st["lp_global"],
+                              device_pivots=st["device_pivots"], global_pivots=st["global_pivots"])
+                continue
             t0 = time.perf_counter()
             if args.dynamic:
                 s, b = None, hmpsac_host_route(fi, prm, N, seed)
@@ -121,6 +143,11 @@ def main():
             routes = dict(lp_device=st["lp_device"], lp_host=st["lp_host"], lp_global=st["lp_global"], device_pivots=st["device_pivots"],
                           global_pivots=st["global_pivots"])
         split = {k: statistics.median(p[k] for p in parts) for k in parts[0]}
+        if mask is not None:
+            lines.append(dict(workload=name, instances=N, path="device: regenerate_masked + reset(mask)", masked=args.masked, lp_impl=args.lp_impl,
+                              ms=dev_ms, split_ms_median=split, **routes, **summary(dev_ms)))
+            del live
+            continue
         lines.append(dict(workload=name, instances=N, path="host: make_train_env's loop (generate, redraw, NumPy machine data) + solve_fluid(16 threads) + BatchedMODFJSP + reset"
                           if args.dynamic else "host: generate_range + solve_fluid(16 threads) + EnvBatch + reset",
                           ms=host_ms, **summary(host_ms)))
