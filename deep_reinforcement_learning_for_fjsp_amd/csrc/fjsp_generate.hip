@@ -1,8 +1,8 @@
 // Training instances generated ON THE DEVICE: fjsp_env_create_generated / fjsp_env_regenerate (include/fjsp_amd.h).
 //
-// The host path of a fresh batch is fjsp_instances_generate (one splitmix64 stream per instance, fjsp_instance.cpp),
-// fjsp_instances_solve_fluid (the order-0 fluid LP, fjsp_lp.cpp), pack_instance (fjsp_env.hip), two uploads and a new
-// allocation.  A generated handle owns its instance records and refills them in place from a seed:
+// The host path of a fresh batch is fjsp_instances_generate (fjsp_instance.cpp), fjsp_instances_solve_fluid (the order-0
+// fluid LP, fjsp_lp.cpp), pack_instance (fjsp_env.hip), two uploads and a new allocation.  A generated handle owns its
+// instance records and refills them in place from a seed:
 //   generate_pack_kernel    record i from (seed_base + i, parameters): byte for byte what pack_instance(generate(...)) writes,
 //                           except x and the static state row, which need the LP; the LP inputs (Q, n_now); and on which
 //                           of two lists the instance goes -- its order-0 tableau fits the LDS of a CU, or it does not;
@@ -14,23 +14,22 @@
 //   generate_finish_kernel  x from the staging slot into the record, the static state row
 //   fluid_tables_kernel, reset_kernel (fjsp_kernels.hip, unchanged), every env marked done: the state a create leaves
 //
-// The generator's stream advances by a constant per draw, so draw i is a pure function of (seed, i).  One wave per
-// instance: lane 0 walks the one serial chain there is -- the number of eligible machines of every operation type decides
-// where the next type's draws start, K dependent hashes -- and the lanes then run their own operation types' shuffles and
-// processing times from those offsets, and write the record's rows side by side.  (One lane per instance would leave the
-// per-type machine lists in scratch memory and the record writes uncoalesced.)
+// The generator itself -- the stream, the position of every draw, the arithmetic that makes a shop of the draws -- is
+// fjsp_gen_stream.h, which fjsp_instance.cpp compiles too; the kernels here spread its element functions over a wave, one
+// wave per instance.  Draw i is a pure function of (seed, i): lane 0 walks the one serial chain there is (K dependent
+// hashes), the lanes then take their own operation types from the chain's offsets and write the record's rows side by side.
+// (One lane per instance would leave the per-type machine lists in scratch memory and the record writes uncoalesced.)
 //
-// Several orders (fjsp_env_create_generated_orders): the S x R job counts and the S - 1 arrival intervals follow the
-// processing times in the stream; lane s computes order s's gap and arrival time, lane 0 sorts the at most
-// FJSP_GEN_MAX_ORDERS delivery times.  The handle is then a multi-order one: its arrival service (fjsp_arrivals.hip) is
-// chosen at create from the parameters' worst tableau and, where it runs on the host, reads fjsp_env::lp_mirror, the
-// records' heads that refresh_lp_mirror gathers after every refill.
+// Several orders (fjsp_env_create_generated_orders): lane s computes order s, lane 0 sorts the at most FJSP_GEN_MAX_ORDERS
+// delivery times.  The handle is then a multi-order one: its arrival service (fjsp_arrivals.hip) is chosen at create from
+// the parameters' worst tableau and, where it runs on the host, reads fjsp_env::lp_mirror, the records' heads that
+// refresh_lp_mirror gathers after every refill.
 //
 // MO_DFJSP (fjsp_env_create_generated_dynamic): the same kernel built with its redraw loop -- an attempt whose shop leaves a
 // machine without an eligible operation is drawn again from the next seed of the instance's redraw stream, at most
-// GenDynArgs::redraws times -- and generate_machine_kernel behind it: the powers, idle powers and breakdown windows of the
-// seed the instance was made of, every draw at a position that is a function of its indices (fjsp_gen_machine), so the
-// lanes need no chain but the running end of a machine's own windows.  The other handles launch neither.
+// GenDynArgs::redraws times -- and generate_machine_kernel behind it: the machine data of the seed the instance was made of,
+// every draw at a position of its own, so the lanes need no chain but the running end of a machine's own windows.  The other
+// handles launch neither.
 //
 // Part of a batch (fjsp_env_regenerate_masked): generate_list_kernel compacts a mask over the instances -- or the envs' done
 // flags -- into an ascending list, generate_clear_kernel zeroes the listed records and their envs' in place of the whole
@@ -45,6 +44,7 @@
 #include <memory>
 
 #include "fjsp_env_impl.h"
+#include "fjsp_gen_stream.h"
 #include "fjsp_launch.h"
 #include "fjsp_lp_pool.h"
 #include "fjsp_lp_limits.h"
@@ -114,30 +114,14 @@ struct GenDynArgs {
 constexpr int kGenMaxK = kWave * kMaxKC;
 
 namespace {
-__device__ inline uint64_t gen_draw(uint64_t seed, uint32_t i) {      // draw i (0-based) of Rng(seed), fjsp_instance.cpp
-    uint64_t z = seed + (uint64_t)(i + 1u) * 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-__device__ inline int gen_randint(uint64_t seed, uint32_t i, int a, int b) {
-    return a + (int)(((gen_draw(seed, i) >> 32) * (uint64_t)(b - a + 1)) >> 32);
-}
-// M and DDT of instance `seed`: the handle's one pair, or draw_gen_params (fjsp_instance.cpp) restated
-__device__ inline int gen_machines(const GenArgs &a, uint64_t seed) {
-    return a.ranged ? gen_randint(seed ^ FJSP_GEN_AUX_STREAM, 0u, a.M_min, a.M_max) : a.g.M;
-}
-__device__ inline double gen_ddt(const GenArgs &a, uint64_t seed) {
-    if (!a.ranged) return a.g.DDT;
-    return a.DDT_min + (a.DDT_max - a.DDT_min) * ((double)(gen_draw(seed ^ FJSP_GEN_AUX_STREAM, 1u) >> 11) * (1.0 / 9007199254740992.0));
-}
-__device__ inline int gen_orders(const GenArgs &a, uint64_t seed) {      // draw_gen_orders (fjsp_instance.cpp)
-    return a.orders ? gen_randint(seed ^ FJSP_GEN_AUX_STREAM, 2u, a.S_min, a.S_max) : 1;
-}
-__device__ inline double gen_uniform(uint64_t seed, uint32_t i, double lo, double hi) {
-    return lo + (hi - lo) * ((double)(gen_draw(seed, i) >> 11) * (1.0 / 9007199254740992.0));
-}
+// M, DDT and S of instance `seed`: the handle's own, or the instance's draws of the auxiliary stream
+__device__ inline int gen_machines(const GenArgs &a, uint64_t seed) { return a.ranged ? gen::aux_machines(seed, a.M_min, a.M_max) : a.g.M; }
+__device__ inline double gen_ddt(const GenArgs &a, uint64_t seed) { return a.ranged ? gen::aux_ddt(seed, a.DDT_min, a.DDT_max) : a.g.DDT; }
+__device__ inline int gen_orders(const GenArgs &a, uint64_t seed) { return a.orders ? gen::aux_orders(seed, a.S_min, a.S_max) : 1; }
 constexpr int kGenMaxS = FJSP_GEN_MAX_ORDERS;
+// The words of generate_pack's s_hdr: what lane 0 leaves for the wave (the first draw behind the chain, where the job counts
+// start; jobs and operations of all orders; the delivery time of the first order due), and the slot the instance got on its LP list
+enum GenHdr : int { kHdrSlot, kHdrK, kHdrStatus, kHdrNx, kHdrChainEnd, kHdrJobs, kHdrDelivery, kHdrOps, kGenHdrWords };
 // The instance of workgroup blockIdx.x of a generator kernel: its own number, or on a masked refill the entry of the list;
 // -1: none (the grid covers every instance, the list's length stays on the device until the call's one read-back)
 __device__ inline int gen_listed(const DevBatch &b, const GenArgs &a) {
@@ -160,7 +144,7 @@ __device__ __forceinline__ void generate_pack(const DevBatch &b, const GenArgs &
     __shared__ uint16_t s_cnt[kGenMaxS * kGenMaxK];  // count[s][r] at s * kGenMaxK + r: order 0 in front
     __shared__ uint16_t s_tot[kGenMaxK];             // jobs of kind r over all orders
     __shared__ uint8_t s_n[kGenMaxK], s_jk[kGenMaxK], s_Jr[kGenMaxK];
-    __shared__ int32_t s_hdr[8];                     // R, K, status, nx, first count draw, nj, delivery, ops
+    __shared__ int32_t s_hdr[kGenHdrWords];          // by GenHdr
     __shared__ double s_dl[kGenMaxS];                // arrive + gap of order s, then sorted
     __shared__ int32_t s_arr[kGenMaxS], s_del[kGenMaxS];     // time_arrive_s, delivery_s (ascending)
     const int l = (int)threadIdx.x, inst = gen_listed(b, a);
@@ -176,14 +160,14 @@ __device__ __forceinline__ void generate_pack(const DevBatch &b, const GenArgs &
     double DDT;
     for (int attempt = 0;; ++attempt) {
         if (DYN && attempt > 0) {
-            seed = gen_draw(seed0 ^ FJSP_GEN_REDRAW_STREAM, (uint32_t)(attempt - 1));
+            seed = gen::attempt_seed(seed0, attempt);
             __syncthreads();                         // the lanes have read the last attempt's shop
         }
         M = gen_machines(a, seed); S = gen_orders(a, seed); DDT = gen_ddt(a, seed);
         // ---- R, J_r, the kinds' first operation types
-        R = gen_randint(seed, 0u, g.R_min, g.R_max);                                                 // :42
+        R = gen::randint(seed, gen::pos_kinds(), g.R_min, g.R_max);
         const bool r_ok = R >= 1 && R <= a.RP && R <= kGenMaxK && M >= 1 && M <= MP && M <= kMaxM && S >= 1 && S <= b.SP && S <= kGenMaxS;
-        for (int r = l; r_ok && r < R; r += kWave) s_Jr[r] = (uint8_t)gen_randint(seed, 1u + (uint32_t)r, g.J_min, g.J_max);   // :46,71
+        for (int r = l; r_ok && r < R; r += kWave) s_Jr[r] = (uint8_t)gen::randint(seed, gen::pos_operations(r), g.J_min, g.J_max);
         __syncthreads();
         if (l == 0) {
             int K = 0, st = r_ok ? 0 : FJSP_E_FORMAT;
@@ -194,62 +178,24 @@ __device__ __forceinline__ void generate_pack(const DevBatch &b, const GenArgs &
                 for (int j = 0; j < J; ++j) { s_rk[K + j] = (uint16_t)r; s_jk[K + j] = (uint8_t)j; }
                 K += J;
             }
+            uint32_t nx = 0, end = 0;
             if (st == 0) s_koff[R] = (uint16_t)K;
-            // the one serial chain: n of type k decides where type k + 1's draws start                 :73
-            uint32_t pos = 1u + (uint32_t)R, nx = 0;
-            for (int k = 0; st == 0 && k < K; ++k) {
-                const int n = gen_randint(seed, pos, 1, M);
-                if (n < 1 || n > M) { st = FJSP_E_FORMAT; break; }
-                s_n[k] = (uint8_t)n; s_off[k] = pos + 1u;
-                pos += 1u + (uint32_t)n;
-                nx += (uint32_t)n;
-            }
-            uint32_t q = pos;                                                                          // :74 draws follow all shuffles
-            for (int k = 0; st == 0 && k < K; ++k) { s_poff[k] = q; q += s_n[k]; }
-            s_hdr[0] = R; s_hdr[1] = K; s_hdr[2] = st; s_hdr[3] = (int)nx; s_hdr[4] = (int)q;
+            if (st == 0) st = gen::chain(seed, R, K, M, s_n, s_off, s_poff, nx, end);      // the one serial chain
+            s_hdr[kHdrK] = K; s_hdr[kHdrStatus] = st; s_hdr[kHdrNx] = (int)nx; s_hdr[kHdrChainEnd] = (int)end;
         }
         __syncthreads();
-        K = s_hdr[1]; nx = s_hdr[3];
-        status = s_hdr[2];
+        K = s_hdr[kHdrK]; nx = s_hdr[kHdrNx]; status = s_hdr[kHdrStatus];
+        const uint32_t chain_end = (uint32_t)s_hdr[kHdrChainEnd];
         if (status != 0) {
             if (l == 0) a.info[inst] = GenInfo{status, 0, 0, 0, 0, 0, 0, 0, M, S, DDT};
             return;
         }
-        // ---- per operation type: choice(M, n, replace=False) as a Fisher-Yates prefix, then the processing times
-        for (int k = l; k < K; k += kWave) {
-            uint8_t *perm = s_el + k * kMaxM;
-            uint16_t *pk = s_p + k * kMaxM;
-            const int n = s_n[k];
-            for (int m = 0; m < M; ++m) { perm[m] = (uint8_t)m; pk[m] = 0; }
-            for (int i = 0; i < n; ++i) {
-                int j = gen_randint(seed, s_off[k] + (uint32_t)i, i, M - 1);
-                j = j < i ? i : (j > M - 1 ? M - 1 : j);
-                const uint8_t t = perm[i]; perm[i] = perm[j]; perm[j] = t;
-            }
-            long sum = 0;
-            for (int i = 0; i < n; ++i) {
-                const int pv = gen_randint(seed, s_poff[k] + (uint32_t)i, g.p_min, g.p_max);
-                pk[perm[i]] = (uint16_t)pv;
-                sum += pv;
-            }
-            for (int m = n; m < M; ++m) perm[m] = 0;
-            s_tr[k] = (double)sum / (double)n;                                                         // :78
-        }
-        // the S x R job counts, order-major, behind the processing times; the S - 1 arrival intervals behind them       :80, :83-84
-        for (int q = l; q < S * R; q += kWave)
-            s_cnt[(q / R) * kGenMaxK + q % R] = (uint16_t)gen_randint(seed, (uint32_t)s_hdr[4] + (uint32_t)q, g.N_min, g.N_max);
+        for (int k = l; k < K; k += kWave)          // per operation type: its eligible list, its processing times
+            s_tr[k] = gen::operation_type(seed, M, s_n[k], s_off[k], s_poff[k], g.p_min, g.p_max, s_el + k * kMaxM, s_p + k * kMaxM);
+        for (int q = l; q < S * R; q += kWave)      // the S x R job counts, order-major
+            s_cnt[(q / R) * kGenMaxK + q % R] = (uint16_t)gen::randint(seed, gen::pos_count(chain_end, q), g.N_min, g.N_max);
         __syncthreads();
-        if (l < S) {
-            // order l: its gap strictly left to right over the operation types (:81-82); its arrival time the truncated running
-            // sum of the intervals, accumulated from order 0 again (:85-86; interval[0] = 0.0)
-            double acc = 0.0;
-            for (int k = 0; k < K; ++k) acc = acc + s_tr[k] * (double)s_cnt[l * kGenMaxK + s_rk[k]];
-            const double gap = acc * DDT / (double)(M * 2);
-            double t = 0.0;                              // (0.0 + interval[0] is 0.0)
-            for (int q = 1; q <= l; ++q) t = t + gen_uniform(seed, (uint32_t)s_hdr[4] + (uint32_t)(S * R) + (uint32_t)(q - 1), g.t_si_min, g.t_si_max);
-            s_arr[l] = (int)t;
-            s_dl[l] = (double)s_arr[l] + gap;
-        }
+        if (l < S) s_dl[l] = gen::order(seed, l, S, R, K, M, DDT, chain_end, g.t_si_min, g.t_si_max, s_tr, s_cnt + l * kGenMaxK, s_rk, s_arr[l]);
         __syncthreads();
         if (l == 0) {
             int nj = 0, ops = 0;
@@ -259,30 +205,20 @@ __device__ __forceinline__ void generate_pack(const DevBatch &b, const GenArgs &
                 s_jbeg[r] = (uint16_t)nj; s_tot[r] = (uint16_t)tot; nj += tot; ops += tot * (int)s_Jr[r];
             }
             s_jbeg[R] = (uint16_t)nj;
-            // :87-88 the delivery times sorted ascending, then truncated: an insertion sort (S <= 16; equal keys are equal values)
-            for (int i = 1; i < S; ++i) {
-                const double v = s_dl[i];
-                int j = i - 1;
-                for (; j >= 0 && s_dl[j] > v; --j) s_dl[j + 1] = s_dl[j];
-                s_dl[j + 1] = v;
-            }
-            for (int so = 0; so < S; ++so) s_del[so] = (int)s_dl[so];
-            s_hdr[5] = nj; s_hdr[6] = s_del[0]; s_hdr[7] = ops;
-            if (nj > b.JP || nj > 65535) s_hdr[2] = FJSP_E_FORMAT;
+            gen::sort_deliveries(s_dl, S, s_del);
+            s_hdr[kHdrJobs] = nj; s_hdr[kHdrDelivery] = s_del[0]; s_hdr[kHdrOps] = ops;
+            if (nj > b.JP || nj > 65535) s_hdr[kHdrStatus] = FJSP_E_FORMAT;
         }
         __syncthreads();
-        nj = s_hdr[5]; delivery = s_hdr[6];
-        status = s_hdr[2];
+        nj = s_hdr[kHdrJobs]; delivery = s_hdr[kHdrDelivery]; status = s_hdr[kHdrStatus];
         // SO_DFJSP and MO_DFJSP divide by the number of operation types of every machine (check_instance, fjsp_env.hip)
-        ops_m = 0;
-        if (l < M)
-            for (int k = 0; k < K; ++k) ops_m += s_p[k * kMaxM + l] > 0 ? 1 : 0;
+        ops_m = l < M ? gen::operations_on_machine(s_p, kMaxM, K, l) : 0;
         if (a.class_fjsp && __any(l < M && ops_m == 0) && status == 0) status = FJSP_E_UNSUPPORTED;
         if (!DYN || status != FJSP_E_UNSUPPORTED || attempt >= redraws) break;
     }
     if (DYN && l == 0) d->seed_used[inst] = seed;
     const uint32_t lds = lp_device_lds_bytes(K, M, nx, R, MP);
-    if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[7], delivery, M, S, DDT};
+    if (l == 0) a.info[inst] = GenInfo{status, K, R, nj, nx, (int32_t)lds, s_hdr[kHdrOps], delivery, M, S, DDT};
     if (status != 0) return;
 
     // ---- the record (pack_instance, fjsp_env.hip); the slab was zeroed before the launch
@@ -348,17 +284,17 @@ __device__ __forceinline__ void generate_pack(const DevBatch &b, const GenArgs &
     const bool glob = !fit && a.allow_global && nc - nx - 2 <= kLpGlobalRows && nc <= kLpGlobalColumns;
     if (l == 0) {
         if (fit) {
-            s_hdr[0] = (int)atomicAdd(a.counts + kCountFit, 1u);
+            s_hdr[kHdrSlot] = (int)atomicAdd(a.counts + kCountFit, 1u);
             atomicMax(a.counts + kCountLdsMax, lds);
         } else if (glob) {
-            s_hdr[0] = (int)atomicAdd(a.counts + kCountGlob, 1u);
+            s_hdr[kHdrSlot] = (int)atomicAdd(a.counts + kCountGlob, 1u);
         } else {
             a.host_ids[atomicAdd(a.counts + kCountHost, 1u)] = (uint32_t)inst;
         }
     }
     __syncthreads();
     if (fit || glob) {
-        const uint32_t slot = (uint32_t)s_hdr[0];
+        const uint32_t slot = (uint32_t)s_hdr[kHdrSlot];
         if (l == 0) (fit ? a.fit_ids : a.glob_ids)[slot] = (uint32_t)inst;
         uint16_t *Q = (fit ? a.lp_in : a.lp_in_glob) + (size_t)slot * 2 * KP;
         for (int k = l; k < K; k += kWave) {
@@ -383,17 +319,16 @@ __global__ __launch_bounds__(kWave) void generate_machine_kernel(DevBatch b, Gen
     const InstHeader h = *reinterpret_cast<const InstHeader *>(rec);
     const int K = h.K, M = h.M, MP = b.MP, W = d.mc.W_max;
     if (K < 1 || K > b.KP || M < 1 || M > MP || MP > kMaxM || W < 0 || M * W > d.windows) return;     // (generate_pack's own checks; the size of i_bk)
-    const uint64_t ms = d.seed_used[inst] ^ FJSP_GEN_MACHINE_STREAM;
+    const uint64_t ms = gen::machine_stream(d.seed_used[inst]);
     const uint16_t *p = reinterpret_cast<const uint16_t *>(rec + b.L.i_p);
     uint16_t *pw = reinterpret_cast<uint16_t *>(rec + b.L.i_pw);
     for (int q = l; q < K * M; q += kWave) {
         const size_t at = (size_t)(q / M) * MP + q % M;
-        pw[at] = p[at] > 0 ? (uint16_t)gen_randint(ms, (uint32_t)(2 * M + q), d.mc.pw_min, d.mc.pw_max) : (uint16_t)0;
+        pw[at] = p[at] > 0 ? (uint16_t)gen::power(ms, M, q, d.mc) : (uint16_t)0;
     }
     if (l < M) {
-        reinterpret_cast<int32_t *>(rec + b.L.i_ipw)[l] = gen_randint(ms, (uint32_t)l, d.mc.idle_min, d.mc.idle_max);
-        const int n = gen_randint(ms, (uint32_t)(M + l), 0, W);
-        s_w[l] = (uint16_t)(n < 0 ? 0 : (n > W ? W : n));
+        reinterpret_cast<int32_t *>(rec + b.L.i_ipw)[l] = gen::idle_power(ms, l, d.mc);
+        s_w[l] = (uint16_t)gen::window_count(ms, M, l, d.mc);
     }
     __syncthreads();
     if (l <= MP) {
@@ -403,12 +338,9 @@ __global__ __launch_bounds__(kWave) void generate_machine_kernel(DevBatch b, Gen
         reinterpret_cast<uint16_t *>(rec + b.L.i_bkoff)[l] = (uint16_t)off;
         if (l < M) {
             int32_t *bk = reinterpret_cast<int32_t *>(rec + b.L.i_bk) + 2 * off;
-            int t = 0;
-            for (int w = 0; w < (int)s_w[l]; ++w) {
-                const uint32_t pos = (uint32_t)(2 * M + K * M + 2 * (l * W + w));
-                const int st = t + gen_randint(ms, pos, d.mc.gap_min, d.mc.gap_max);
-                t = st + gen_randint(ms, pos + 1u, d.mc.len_min, d.mc.len_max);
-                bk[2 * w] = st; bk[2 * w + 1] = t;
+            for (int w = 0, end = 0; w < (int)s_w[l]; ++w) {
+                bk[2 * w] = gen::window(ms, M, K, l, w, d.mc, end);
+                bk[2 * w + 1] = end;
             }
         }
     }
@@ -628,15 +560,6 @@ void generated_release(fjsp_env *e) {
 }
 
 namespace {
-// the checks of generate() (fjsp_instance.cpp)
-int check_params(const fjsp_gen_params &g) {
-    if (g.M <= 0 || g.S <= 0 || g.R_min <= 0 || g.R_max < g.R_min || g.J_min <= 0 || g.J_max < g.J_min ||
-        g.p_min <= 0 || g.p_max < g.p_min || g.N_min <= 0 || g.N_max < g.N_min) {
-        set_error("generator: bad parameters"); return FJSP_E_ARG;
-    }
-    return FJSP_OK;
-}
-
 // check_instance (fjsp_env.hip) on the worst case of the parameters, sizes into sh.  Over M in M_min..M_max and |DDT| up to
 // ddt_max: sizes from M_max, the largest delivery time from ddt_max / (2 M_min)
 // With S_max > 1 orders: jobs, operations and the clock count all of them, the clock starts from the last arrival
@@ -1024,7 +947,7 @@ int create_generated(const std::string &call, const fjsp_gen_params *prm, const 
     fjsp_gen_params g = *prm;
     if (q) { g.M = q->M_min; g.DDT = 0.0; }       // base.M and base.DDT are not read
     if (o) g.S = o->S_max;                        // nor is base.S
-    if ((rc = check_params(g)) != FJSP_OK) return rc;
+    if ((rc = check_gen_params(g)) != FJSP_OK) return rc;
     const int S_max = o ? o->S_max : 1;
     if (S_max > FJSP_GEN_MAX_ORDERS) {
         set_error(call + ": more than " + std::to_string(FJSP_GEN_MAX_ORDERS) + " orders (S_max): the generator kernel keeps the orders' counts and times in LDS");

@@ -57,6 +57,8 @@ int solve_fluid_lp(int R, int M, const int *Jr, const int *p, const int *Q, cons
 
 // fjsp_instance.cpp
 int finalize_instance(Instance &in);  // derives koff/K, validates
+// the bounds of a fjsp_gen_params (FJSP_E_ARG): what fjsp_instances_generate and the generated creates refuse alike
+int check_gen_params(const fjsp_gen_params &g);
 // the bounds of a fjsp_gen_ranges (FJSP_E_ARG, the message names the bound); its per-instance draws of M and DDT
 int check_gen_ranges(const fjsp_gen_ranges &q);
 void draw_gen_params(const fjsp_gen_ranges &q, uint64_t seed, fjsp_gen_params &out);

@@ -3,6 +3,7 @@
 //   - seeded random generator<- environments/Instance_generate.py:19-94
 //   - fluid LP driver        <- environments/class_FJSSP.py:246-280 (see fjsp_lp.cpp)
 #include "../../include/fjsp_amd.h"
+#include "fjsp_gen_stream.h"
 #include "fjsp_host.h"
 #include "fjsp_lp_pool.h"
 
@@ -221,77 +222,38 @@ static int load_csv(Instance &in, const std::string &dir) {
     }
 }
 
-// ---- counter-based generator ----------------------------------------------
-struct Rng {
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed) {}
-    uint64_t next() {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-        return z ^ (z >> 31);
-    }
-    int randint(int a, int b) { return a + (int)(((next() >> 32) * (uint64_t)(b - a + 1)) >> 32); }
-    double uniform(double a, double b) { return a + (b - a) * ((double)(next() >> 11) * (1.0 / 9007199254740992.0)); }
-};
-
-static int generate(Instance &in, uint64_t seed, const fjsp_gen_params &g) {
+// ---- counter-based generator: the stream and the shop are fjsp_gen_stream.h's, shared with the device generator ----
+int check_gen_params(const fjsp_gen_params &g) {
     if (g.M <= 0 || g.S <= 0 || g.R_min <= 0 || g.R_max < g.R_min || g.J_min <= 0 || g.J_max < g.J_min ||
         g.p_min <= 0 || g.p_max < g.p_min || g.N_min <= 0 || g.N_max < g.N_min) {
         set_error("generator: bad parameters"); return FJSP_E_ARG;
     }
-    Rng rng(seed);
-    in = Instance();
-    in.ddt = g.DDT; in.M = g.M; in.S = g.S;
-    in.R = rng.randint(g.R_min, g.R_max);                                    // :42
-    in.Jr.resize(in.R);
-    for (int r = 0; r < in.R; ++r) in.Jr[r] = rng.randint(g.J_min, g.J_max); // :46,71
-    in.koff.assign(in.R + 1, 0);
-    for (int r = 0; r < in.R; ++r) in.koff[r + 1] = in.koff[r] + in.Jr[r];
-    in.K = in.koff[in.R];
-    size_t km = (size_t)in.K * in.M;
-    in.p.assign(km, 0); in.elig_list.assign(km, 0); in.elig_n.assign(in.K, 0);
-    std::vector<int> perm(in.M);
-    for (int k = 0; k < in.K; ++k) {                                         // :73 choice(M, U{1..M}, replace=False)
-        int n = rng.randint(1, in.M);
-        for (int m = 0; m < in.M; ++m) perm[m] = m;
-        for (int i = 0; i < n; ++i) {
-            int j = rng.randint(i, in.M - 1);
-            std::swap(perm[i], perm[j]);
-            in.elig_list[(size_t)k * in.M + i] = perm[i];
-        }
-        in.elig_n[k] = n;
-    }
-    for (int k = 0; k < in.K; ++k)                                           // :74
-        for (int i = 0; i < in.elig_n[k]; ++i)
-            in.p[(size_t)k * in.M + in.elig_list[(size_t)k * in.M + i]] = rng.randint(g.p_min, g.p_max);
-    std::vector<double> time_rj(in.K);                                       // :78 mean over machine_rj_dict order
-    for (int k = 0; k < in.K; ++k) {
-        long s = 0;
-        for (int i = 0; i < in.elig_n[k]; ++i) s += in.p[(size_t)k * in.M + in.elig_list[(size_t)k * in.M + i]];
-        time_rj[k] = (double)s / (double)in.elig_n[k];
-    }
-    in.count.assign((size_t)in.S * in.R, 0);
-    for (int s = 0; s < in.S; ++s)
-        for (int r = 0; r < in.R; ++r) in.count[(size_t)s * in.R + r] = rng.randint(g.N_min, g.N_max); // :80
-    std::vector<double> gap(in.S), interval(in.S, 0.0);
-    for (int s = 0; s < in.S; ++s) {                                         // :81-82
-        double acc = 0.0;
-        for (int r = 0; r < in.R; ++r)
-            for (int j = 0; j < in.Jr[r]; ++j) acc = acc + time_rj[in.koff[r] + j] * (double)in.count[(size_t)s * in.R + r];
-        gap[s] = acc * g.DDT / (double)(in.M * 2);
-    }
-    for (int s = 1; s < in.S; ++s) interval[s] = rng.uniform(g.t_si_min, g.t_si_max); // :83-84
-    in.arrive.assign(in.S, 0); in.delivery.assign(in.S, 0);
-    std::vector<double> dl(in.S);
-    for (int s = 0; s < in.S; ++s) {                                         // :85-86
-        double acc = 0.0;
-        for (int q = 0; q <= s; ++q) acc = acc + interval[q];
-        in.arrive[s] = (int)acc;
-        dl[s] = (double)in.arrive[s] + gap[s];
-    }
-    std::sort(dl.begin(), dl.end());                                         // :87
-    for (int s = 0; s < in.S; ++s) in.delivery[s] = (int)dl[s];              // :88
+    return FJSP_OK;
+}
+
+static int generate(Instance &in, uint64_t seed, const fjsp_gen_params &g) {
+    if (const int rc = check_gen_params(g)) return rc;
+    in = Instance(); in.ddt = g.DDT; in.M = g.M; in.S = g.S;
+    const int M = g.M, S = g.S, R = in.R = gen::randint(seed, gen::pos_kinds(), g.R_min, g.R_max);
+    in.Jr.resize(R);
+    for (int r = 0; r < R; ++r) in.Jr[r] = gen::randint(seed, gen::pos_operations(r), g.J_min, g.J_max);
+    in.koff.assign(R + 1, 0);
+    for (int r = 0; r < R; ++r) in.koff[r + 1] = in.koff[r] + in.Jr[r];
+    const int K = in.K = in.koff[R];
+    std::vector<int> kind_of(K);
+    for (int r = 0; r < R; ++r) std::fill(kind_of.begin() + in.koff[r], kind_of.begin() + in.koff[r + 1], r);
+    in.p.assign((size_t)K * M, 0); in.elig_list = in.p; in.elig_n.assign(K, 0);
+    std::vector<uint32_t> off(K), poff(K);
+    uint32_t nx = 0, end = 0;
+    if (const int rc = gen::chain(seed, R, K, M, in.elig_n.data(), off.data(), poff.data(), nx, end)) { set_error("generator: eligible machine count out of range"); return rc; }
+    std::vector<double> time_rj(K), dl(S);
+    for (int k = 0; k < K; ++k)
+        time_rj[k] = gen::operation_type(seed, M, in.elig_n[k], off[k], poff[k], g.p_min, g.p_max, &in.elig_list[(size_t)k * M], &in.p[(size_t)k * M]);
+    in.count.assign((size_t)S * R, 0); in.arrive.assign(S, 0); in.delivery.assign(S, 0);
+    for (int q = 0; q < S * R; ++q) in.count[q] = gen::randint(seed, gen::pos_count(end, q), g.N_min, g.N_max);
+    for (int s = 0; s < S; ++s)
+        dl[s] = gen::order(seed, s, S, R, K, M, g.DDT, end, g.t_si_min, g.t_si_max, time_rj.data(), &in.count[(size_t)s * R], kind_of.data(), in.arrive[s]);
+    gen::sort_deliveries(dl.data(), S, in.delivery.data());
     return finalize_instance(in);
 }
 
@@ -306,10 +268,9 @@ int check_gen_ranges(const fjsp_gen_ranges &q) {
 }
 
 void draw_gen_params(const fjsp_gen_ranges &q, uint64_t seed, fjsp_gen_params &out) {
-    Rng aux(seed ^ FJSP_GEN_AUX_STREAM);
     out = q.base;
-    out.M = aux.randint(q.M_min, q.M_max);
-    out.DDT = aux.uniform(q.DDT_min, q.DDT_max);
+    out.M = gen::aux_machines(seed, q.M_min, q.M_max);
+    out.DDT = gen::aux_ddt(seed, q.DDT_min, q.DDT_max);
 }
 
 // ---- ... and the number of orders (fjsp_gen_orders) ----
@@ -325,11 +286,8 @@ int check_gen_orders(const fjsp_gen_orders &q) {
 }
 
 void draw_gen_orders(const fjsp_gen_orders &q, uint64_t seed, fjsp_gen_params &out) {
-    Rng aux(seed ^ FJSP_GEN_AUX_STREAM);
-    out = q.r.base;
-    out.M = aux.randint(q.r.M_min, q.r.M_max);
-    out.DDT = aux.uniform(q.r.DDT_min, q.r.DDT_max);
-    out.S = aux.randint(q.S_min, q.S_max);
+    draw_gen_params(q.r, seed, out);
+    out.S = gen::aux_orders(seed, q.S_min, q.S_max);
 }
 
 // ---- ... and the machine data of an MO_DFJSP shop (fjsp_gen_dynamic) ----
@@ -356,27 +314,16 @@ int check_gen_dynamic(const fjsp_gen_dynamic &q) {
     return FJSP_OK;
 }
 
-// draw i (0-based) of Rng(seed): the stream advances by a constant, so a position needs no chain
-static Rng rng_at(uint64_t seed, uint32_t i) { return Rng(seed + (uint64_t)i * 0x9E3779B97F4A7C15ULL); }
-static int randint_at(uint64_t seed, uint32_t i, int a, int b) { return rng_at(seed, i).randint(a, b); }
-
-static bool machine_without_operation(const Instance &in) {
-    for (int m = 0; m < in.M; ++m) {
-        int ops_m = 0;
-        for (int k = 0; k < in.K; ++k) ops_m += in.p[(size_t)k * in.M + m] > 0 ? 1 : 0;
-        if (ops_m == 0) return true;
-    }
-    return false;
-}
-
 // The first playable attempt of instance `seed` (fjsp_gen_dynamic, include/fjsp_amd.h): its shop into `in`, its seed into used
 static int generate_playable(Instance &in, uint64_t seed, const fjsp_gen_dynamic &q, uint64_t &used) {
     for (int j = 0; j <= q.redraws; ++j) {
-        used = j == 0 ? seed : rng_at(seed ^ FJSP_GEN_REDRAW_STREAM, (uint32_t)(j - 1)).next();
+        used = gen::attempt_seed(seed, j);
         fjsp_gen_params prm;
         draw_gen_orders(q.o, used, prm);
         if (const int rc = generate(in, used, prm)) return rc;
-        if (!machine_without_operation(in)) return FJSP_OK;
+        int m = 0;
+        while (m < in.M && gen::operations_on_machine(in.p.data(), in.M, in.K, m) > 0) ++m;
+        if (m == in.M) return FJSP_OK;       // no machine without an eligible operation
     }
     set_error("MO_DFJSP: a machine with no eligible operation (ZeroDivisionError in the reference) in each of " +
               std::to_string(q.redraws + 1) + " attempts (redraws = " + std::to_string(q.redraws) + ")");
@@ -384,22 +331,16 @@ static int generate_playable(Instance &in, uint64_t seed, const fjsp_gen_dynamic
 }
 
 static void generate_machine_data(Instance &in, uint64_t seed, const fjsp_gen_machine &g) {
-    const uint64_t ms = seed ^ FJSP_GEN_MACHINE_STREAM;
-    const uint32_t M = (uint32_t)in.M, K = (uint32_t)in.K, W = (uint32_t)g.W_max;
+    const uint64_t ms = gen::machine_stream(seed);
+    const int M = in.M, K = in.K;
     in.power.assign((size_t)K * M, 0); in.idle_power.assign(M, 0); in.bk_n.assign(M, 0); in.bk.clear();
-    for (uint32_t m = 0; m < M; ++m) {
-        in.idle_power[m] = randint_at(ms, m, g.idle_min, g.idle_max);
-        in.bk_n[m] = randint_at(ms, M + m, 0, g.W_max);
-    }
-    for (uint32_t q = 0; q < K * M; ++q)
-        if (in.p[q] > 0) in.power[q] = randint_at(ms, 2u * M + q, g.pw_min, g.pw_max);
-    for (uint32_t m = 0; m < M; ++m) {
-        int t = 0;
-        for (uint32_t w = 0; w < (uint32_t)in.bk_n[m]; ++w) {
-            const uint32_t pos = 2u * M + K * M + 2u * (m * W + w);
-            const int st = t + randint_at(ms, pos, g.gap_min, g.gap_max), en = st + randint_at(ms, pos + 1u, g.len_min, g.len_max);
-            in.bk.push_back(st); in.bk.push_back(en);
-            t = en;
+    for (int q = 0; q < K * M; ++q) in.power[q] = in.p[q] > 0 ? gen::power(ms, M, q, g) : 0;
+    for (int m = 0; m < M; ++m) {
+        in.idle_power[m] = gen::idle_power(ms, m, g);
+        in.bk_n[m] = gen::window_count(ms, M, m, g);
+        for (int w = 0, end = 0; w < in.bk_n[m]; ++w) {
+            in.bk.push_back(gen::window(ms, M, K, m, w, g, end));
+            in.bk.push_back(end);
         }
     }
     in.has_dynamic = true;

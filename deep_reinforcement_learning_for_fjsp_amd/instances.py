@@ -223,8 +223,8 @@ class InstanceSet(object):
         generator has no breakdowns (that data only exists in CSV folders, MO_DFJSP_instance_read.py:56-73);
         max_windows > 0 adds up to that many sorted, disjoint windows per machine for synthetic batches.
         These are draws of a NumPy RandomState on this side of the C ABI.  generate(i, seed, GenDynamic) draws machine data
-        of the same distributions from the library's own counter-based stream, which the device generator restates
-        (EnvBatch.generated with a GenDynamic): the two produce DIFFERENT data for the same seed."""
+        of the same distributions from the library's own counter-based stream, which the device generator shares
+        (csrc/fjsp_gen_stream.h; EnvBatch.generated with a GenDynamic): the two produce DIFFERENT data for the same seed."""
         a = self.arrays(i)
         rs = np.random.RandomState(int(seed) & 0x7FFFFFFF)
         power = np.where(a.p > 0, rs.randint(10, 201, a.p.shape), 0)

@@ -284,7 +284,7 @@ int  fjsp_env_create_generated_ranges(const fjsp_gen_ranges *q, int32_t n_inst, 
                                       uint64_t rng_seed, int32_t family, uint64_t seed_base, fjsp_env **out);
 /* ... and with the number of orders drawn per instance (fjsp_gen_orders): instance i is what
  * fjsp_instances_generate_orders(seed_base + i, q) + fjsp_instances_solve_fluid + fjsp_env_create_family give, record for
- * record, x bit for bit.  The generator kernel restates the host generator for S orders: the S x R job counts order-major,
+ * record, x bit for bit.  The generator kernel and the host generator compile one text (csrc/fjsp_gen_stream.h): the S x R job counts order-major,
  * then the S - 1 arrival intervals, arrival times as truncated running sums, delivery times arrive + gap sorted ascending.
  * The handle is sized for S_max, M_max and the worst case (R_max N_max S_max jobs, R_max J_max N_max S_max operations); it
  * is a multi-order handle -- per-env fluid tables, order-arrival LPs -- iff S_max > 1, and an instance that drew S = 1 plays

@@ -1,7 +1,8 @@
 """Function-by-function comparison of two device builds of the kernel sources: instruction text (branch labels
 normalised) and the resource usage the compiler reports.  Used to check that a change leaves existing kernels' code alone.
 
-    for f in fjsp_kernels fjsp_group fjsp_lp_device fjsp_snapshot fjsp_rollout_buffer fjsp_ppo fjsp_mlp_train fjsp_policy_mlp; do
+    for f in fjsp_kernels fjsp_group fjsp_lp_device fjsp_lp_global fjsp_env fjsp_arrivals fjsp_snapshot fjsp_rollout_buffer fjsp_ppo \\
+             fjsp_mlp_train fjsp_policy_mlp fjsp_generate; do
       # (every .hip with kernels) once in a checkout of the parent (-> DIR_A), once in this tree (-> DIR_B)
       hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -I include \\
             -I deep_reinforcement_learning_for_fjsp_amd/csrc --cuda-device-only -S \\
