@@ -468,9 +468,21 @@ int fjsp_env_create_family(const fjsp_instances *s, int32_t first, int32_t n_ins
         set_error("fjsp_env_create: unknown variant"); return FJSP_E_ARG;
     }
     Shape sh;
+    int stages_max = 0;
     for (int i = 0; i < n_inst; ++i) {
-        const int rc = check_instance(s->v[(size_t)first + i], variant, class_fjsp, sh);
+        const Instance &in = s->v[(size_t)first + i];
+        const int rc = check_instance(in, variant, class_fjsp, sh);
         if (rc != FJSP_OK) return rc;
+        for (int r = 0; r < in.R; ++r) stages_max = std::max(stages_max, in.Jr[r]);
+    }
+    // A batch with order arrivals (an instance of several orders, or MO_DFJSP: plan_batch's mord) marks the jobs of orders
+    // still to come with 0xFF in the byte of a job's state word that otherwise holds its next stage (kAbsent,
+    // fjsp_kernels.hip), and a finished job of a kind of 255 stages carries 255 there: compute_params would count it as not
+    // arrived and finish_rate would divide by too few jobs, by none once all of the kind are finished.
+    if ((sh.S > 1 || dyn) && stages_max > 254) {
+        set_error("more than 254 operations in a kind of a batch with order arrivals (several orders, MO_DFJSP); 255 in a "
+                  "batch of single-order instances");
+        return FJSP_E_UNSUPPORTED;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {

@@ -575,6 +575,11 @@ int check_worst_case(const fjsp_gen_params &g, int M_min, int M_max, double ddt_
     if (nj > 65535) { set_error("generated instances can have more than 65535 jobs (R_max x N_max)"); return FJSP_E_UNSUPPORTED; }
     if (ops > 65535) { set_error("generated instances can have more than 65535 operations (R_max x J_max x N_max)"); return FJSP_E_UNSUPPORTED; }
     if (g.J_max > 255) { set_error("more than 255 operations in a kind"); return FJSP_E_UNSUPPORTED; }
+    // (a handle with order arrivals keeps 255 in a job's next-stage byte for orders still to come: fjsp_env_create_family)
+    if (g.J_max > 254 && (S_max > 1 || mc)) {
+        set_error("more than 254 operations in a kind (J_max) of a handle with order arrivals (S_max > 1, MO_DFJSP)");
+        return FJSP_E_UNSUPPORTED;
+    }
     if (g.p_max > 65535) { set_error("processing time above 65535"); return FJSP_E_UNSUPPORTED; }
     // the 32-bit clocks: every operation in sequence at the largest processing time; the largest delivery time is every
     // operation type at p_max with N_max jobs, times DDT / (2 M)

@@ -157,7 +157,8 @@ def test_generated_cases_keep_their_coverage(built):
 def test_no_admissible_device_tableau_has_more_than_128_rows():
     """csrc/fjsp_lp_device.hip holds two row groups of 64 in a lane and refuses an LP of more than 128 rows (error code 5,
     before any tableau write).  Creation admits K <= 256 operation types, M <= 32 machines, 1 <= R <= K kinds of at most 255
-    operations and K <= nx <= K M eligible pairs (csrc/fjsp_env.hip check_instance, csrc/fjsp_instance.cpp), and puts the
+    operations (254 in a batch with order arrivals, the only batches that pose LPs on the device; the sweep below keeps the
+    wider 255) and K <= nx <= K M eligible pairs (csrc/fjsp_env.hip check_instance, csrc/fjsp_instance.cpp), and puts the
     LPs on the device only when lp_device_lds_bytes(K, M, nx, R, MP >= M) <= 156 KB and the tableau has at most 512
     columns (choose_lp_service).  The worst-case tableau has nr = K + M + (K - R) rows.  Over every such shape: none with
     nr > 128 is admitted, so no batch reaches that refusal.  (nr >= 129 needs K >= 49, hence nc >= K + nr + 2 >= 180 and
