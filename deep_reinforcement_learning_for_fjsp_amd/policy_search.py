@@ -1,6 +1,7 @@
-"""Decoding a trained dispatching policy on the device: greedy play, best-of-K sampling, and a policy rollout lookahead.
+"""Decoding a trained dispatching policy on the device: greedy play, best-of-K sampling, a policy rollout lookahead, and
+beam search.
 
-All three share one launch, fjsp_env_play_policy (play_policy_kernel, csrc/fjsp_kernels_policy.inc): every env plays to
+The first three share one launch, fjsp_env_play_policy (play_policy_kernel, csrc/fjsp_kernels_policy.inc): every env plays to
 the end of its episode with the actor evaluated inside the environment kernel and no rollout-buffer traffic.  The actor is
 an agents.MPPPO ActorNet; the kernel takes those of the in-kernel shape (state_size <= 32 -> 128 -> 128 -> n_actions
 <= 32) on every single-order batch, whatever its operation types and jobs (EnvBatch.policy_build reports the workgroup it
@@ -13,6 +14,13 @@ argmax or fjsp_policy_sample, one env step), only more slowly.
 - policy_lookahead: the rollout algorithm of lookahead.rollout_dispatch with the greedy actor as base policy: the same
   decision loop (lookahead.decide_by_rollouts), in which branch block p applies candidate p and plays greedily to the
   end, all in one launch.
+- beam_search: `width` partial schedules per env in a width x N beam batch.  At every decision each beam is scored under
+  every action (score="logp": the cumulative -log probability of the actor, one forward pass; score="rollout": the
+  objective of the episode that applies the action and follows the greedy actor to the end, policy_lookahead's
+  evaluation in a width x P x N expansion batch), fjsp_beam_select (csrc/fjsp_beam.hip) keeps the `width` best of an
+  env's width x A candidates under a stated total order (cost, then parent beam, then action), the beam batch is
+  gathered through a snapshot pair and takes one step.  The search is reproducible bit for bit; width 1 is greedy play
+  (logp) or policy_lookahead (rollout).
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -26,8 +34,8 @@ from . import _capi
 from ._capi import ptr as _ptr
 from .agents.native_actor import native_actor_forward, native_actor_params
 from .batch import ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT
-from .lookahead import (ACTION_RANGES, OBJECTIVES, branch_for, candidate_pairs, check_status, decide_by_rollouts, mo_rows,
-                        objective_values, ops_per_env)
+from .lookahead import (ACTION_RANGES, OBJECTIVES, Clock, branch_for, candidate_pairs, check_branch_shape, check_status,
+                        decide_by_rollouts, mo_rows, objective_values, ops_per_env)
 
 # the status bits at which an env stops playing (the kernel's and fjsp_env_rollout's `live` test)
 _STOP_BITS = ST_BAD_TASK_RULE | ST_BAD_MACHINE_RULE | ST_NO_EVENT
@@ -51,6 +59,12 @@ def action_encoding(actor, batch):
         raise ValueError("the actor maps %d inputs to %d actions; this batch has states of %d and %d actions"
                          % (lin[0].in_features, lin[-1].out_features, batch.state_size, n_actions))
     return n_actions, pair_div
+
+
+def _every_action(variant):
+    """Every action of the variant as candidates (lookahead.candidate_pairs): pairs, or flat actions."""
+    rng = ACTION_RANGES[variant]
+    return [(a, m) for a in range(rng[0]) for m in range(rng[1])] if len(rng) == 2 else list(range(rng[0]))
 
 
 def _check_objective(objective):
@@ -213,10 +227,7 @@ def policy_lookahead(batch, actor, objective, candidates=None, mo=None, branch=N
     batch, mo = _unwrap(batch, mo)
     _check_objective(objective)
     _, pair_div = action_encoding(actor, batch)
-    if candidates is None:
-        rng = ACTION_RANGES[batch.variant]
-        candidates = [(a, m) for a in range(rng[0]) for m in range(rng[1])] if len(rng) == 2 else list(range(rng[0]))
-    pairs = candidate_pairs(candidates, batch.variant)
+    pairs = candidate_pairs(_every_action(batch.variant) if candidates is None else candidates, batch.variant)
     P, N = len(pairs), batch.N
     first = torch.as_tensor(pairs, device=batch.device)[:, None, :].expand(P, N, 2).reshape(P * N, 2).contiguous()   # candidate p in block p
 
@@ -231,3 +242,185 @@ def policy_lookahead(batch, actor, objective, candidates=None, mo=None, branch=N
 
     # (the source step returns a state: the next decision's actor input)
     return decide_by_rollouts(batch, pairs, objective, mo, branch, timings, "policy_lookahead", True, play_branch)
+
+
+BEAM_SCORES = ("logp", "rollout")
+BEAM_TIMINGS = ("forward", "select", "snapshot", "restore", "rollout", "step")
+
+
+def beam_select(cost, done=None, width_out=None):
+    """fjsp_beam_select (include/fjsp_amd.h) on the current stream: cost f64[W, N, A] on the device (beam-major: entry
+    (b, i, a) = the cost of action a in beam b of source env i, NaN / +inf = no candidate), done u8[W, N] or None,
+    width_out (default W) -> (parent i32, action i32, cost f64), each [width_out, N]: source env i's candidates in
+    ascending (cost, parent, action), ranks past the last candidate (-1, -1, +inf)."""
+    if not torch.is_tensor(cost) or cost.dim() != 3 or cost.dtype != torch.float64 or cost.device.type != "cuda":
+        raise ValueError("beam_select: cost must be an f64[W, N, A] device tensor")
+    W, N, A = cost.shape
+    width_out = W if width_out is None else int(width_out)
+    dev = cost.device
+    cost = cost.contiguous()
+    if done is not None:
+        done = torch.as_tensor(done, device=dev).to(torch.uint8).reshape(W, N).contiguous()
+    shape = (max(width_out, 0), N)
+    parent = torch.empty(shape, dtype=torch.int32, device=dev)
+    action = torch.empty(shape, dtype=torch.int32, device=dev)
+    out = torch.empty(shape, dtype=torch.float64, device=dev)
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    _capi.check(_capi.lib().fjsp_beam_select(_ptr(cost), _ptr(done), N, W, A, width_out, _ptr(parent), _ptr(action), _ptr(out),
+                                             _capi.stream(index)))
+    return parent, action, out
+
+
+def beam_search(batch, actor, width, objective=None, score="logp", candidates=None, mo=None, beams=None, expand=None, timings=None):
+    """Play every env of `batch` (reset or mid-episode) to the end by beam search: `width` partial schedules per env,
+    each expanded by every candidate action at every decision, the `width` best kept (fjsp_beam_select: ascending cost,
+    equal costs by lower parent beam, then lower action -- the same result in every run).
+
+    score="logp": a candidate's cost is its beam's cumulative cost minus the log (taken in f64) of the actor's
+    probability of the action, so rank 0 ends as the most likely sequence the beam has kept and width 1 is greedy play.
+    score="rollout": the cost is the `objective` (required) of the episode that applies the action in the beam and
+    follows the greedy actor to the end, policy_lookahead's evaluation; width 1 is policy_lookahead.
+    candidates: as policy_lookahead; None = every action of the variant; the others are never applied.
+    beams: an EnvBatch of width x N envs (lookahead.make_branch), reused across calls, or None; it records its schedule
+    iff the source does.  expand (rollout mode): one of width x P x N envs for the P candidates, or None.
+    timings: a dict that receives the synchronised seconds per part: forward (the actor, logp mode), rollout (the
+    expansion's play to the end, rollout mode), select, snapshot, restore, step.
+
+    Beam 0 starts from the source's state with cost 0 and the others with cost +inf, so the first selection fans out
+    from one beam.  A rank with no candidate left (fewer than `width` candidates) copies rank 0 and keeps cost +inf: it
+    is never chosen.  When every beam has finished, each source env takes the first rank with the lowest objective
+    (objective=None in logp mode: rank 0) with its rows and, when recording, its schedule.  Beams change slots at every
+    decision, so, as restore() states, random-rule actions continue on another slot's random stream: with them the
+    returned actions need not replay to the same episode; with deterministic rules they do, bit for bit.
+
+    Returns dict(objective=tensor[N] of the source's finished episodes or None, best=i64[N] the winning rank, cost=
+    f64[width, N] the ranks' final costs, actions=uint8[T, N, 2] numpy, the winner's action at each decision (zero past an
+    env's end), steps=int[N] numpy decisions each env took, beams=the beam batch, expand=the expansion batch or None)."""
+    who = "beam_search"
+    W = int(width)
+    if not 1 <= W <= 64:
+        raise ValueError("beam_search: width must be 1..64, got %d" % W)
+    if score not in BEAM_SCORES:
+        raise ValueError("beam_search: score must be one of %s, got %r" % (BEAM_SCORES, score))
+    if objective is None and score == "rollout":
+        raise ValueError("beam_search: score='rollout' needs an objective")
+    if objective is not None:
+        _check_objective(objective)
+    batch, mo = _unwrap(batch, mo)
+    A, pair_div = action_encoding(actor, batch)
+    pairs = candidate_pairs(_every_action(batch.variant) if candidates is None else candidates, batch.variant)
+    P, N, dev = len(pairs), batch.N, batch.device
+    check_branch_shape(N, batch.n_inst, W, who)
+    beams = branch_for(batch, W, beams, who)
+    expand = branch_for(batch, W * P, expand, who) if score == "rollout" else expand
+    if _recording(beams) != _recording(batch):
+        beams.record_schedule(_recording(batch))
+    inf = float("inf")
+    flat = torch.arange(A, device=dev)
+    table = torch.stack([flat // pair_div, flat % pair_div] if pair_div else [flat, torch.zeros_like(flat)], 1).to(torch.uint8)   # action -> pair
+    pairs_dev = torch.as_tensor(pairs, device=dev)
+    cand = pairs_dev[:, 0].long() * pair_div + pairs_dev[:, 1].long() if pair_div else pairs_dev[:, 0].long()       # i64[P]
+    allowed = torch.zeros(A, dtype=torch.bool, device=dev)
+    allowed[cand] = True
+    ar = torch.arange(N, device=dev)
+    mo_beams = mo_rows(mo, N, dev, W)
+    ops = ops_per_env(beams)
+    beams.restore(batch.snapshot(), np.tile(np.arange(N, dtype=np.int64), W), rows=True)
+    cum = torch.full((W, N), inf, dtype=torch.float64, device=dev)
+    cum[0] = 0.0
+    clock = Clock(timings, dev)
+    if timings is not None:
+        for part in BEAM_TIMINGS:
+            timings.setdefault(part, 0.0)
+
+    if score == "logp":
+        native = native_actor_params(actor) is not None
+
+        def costs(T, snap):
+            with torch.no_grad():
+                probs = native_actor_forward(actor, beams.state) if native else actor(beams.state.float())
+            c = cum[:, :, None] - torch.log(probs.double()).reshape(W, N, A)
+            c = torch.where(allowed, c, torch.full_like(c, inf))
+            clock.lap("forward")
+            return c
+    else:
+        src_h = (np.arange(W)[:, None, None] * N + np.zeros((1, P, 1), np.int64) + np.arange(N)[None, None, :]).reshape(-1)
+        src_dev = torch.as_tensor(src_h.astype(np.int32), device=dev)        # expansion env (b * P + p) * N + i <- beam env b * N + i
+        first = pairs_dev[None, :, None, :].expand(W, P, N, 2).reshape(W * P * N, 2).contiguous()          # ... applies candidate p
+        mo_expand = mo_rows(mo, N, dev, W * P)
+        restored = []
+
+        def costs(T, snap):
+            expand.restore(snap, src_dev if restored else src_h, rows=False)       # (the host map is validated once)
+            restored.append(True)
+            clock.lap("restore")
+            _play(expand, actor, pair_div, W * P * N, 0, mo_expand, T, first, src_dev, beams.state, False, True)
+            clock.lap("rollout")
+            re = expand.read()
+            check_status(re, "expansion", who)
+            if not bool((re["done"] != 0).all()):
+                raise RuntimeError("beam_search: an expansion env did not finish its episode")
+            c = torch.full((W, N, A), inf, dtype=torch.float64, device=dev)
+            c[:, :, cand] = objective_values(expand, objective, re).reshape(W, P, N).permute(0, 2, 1)
+            return c
+
+    snap, back_parent, back_action = None, [], []
+    prev_live, prev_count = None, None
+    r = beams.read()
+    while True:
+        check_status(r, "beam", who)
+        live = r["done"] == 0
+        count = r["step_count"].long()
+        if prev_live is not None and bool((prev_live & live & (count <= prev_count)).any()):
+            raise RuntimeError("beam_search: a beam env did not advance in its step")
+        if not bool(live.any()):
+            break
+        T = int(torch.where(live, ops - count, torch.zeros_like(ops)).max().item())
+        clock.start()
+        snap = beams.snapshot(out=snap)
+        clock.lap("snapshot")
+        cost = costs(T, snap)
+        done = r["done"].reshape(W, N)
+        cost = torch.where((cum < inf)[:, :, None], cost, torch.full_like(cost, inf))     # a rank without a beam expands nothing
+        cost[:, :, 0] = torch.where(done != 0, cum, cost[:, :, 0])                        # a finished beam stays, at its cost
+        parent, action, cum = beam_select(cost, done, W)
+        none = parent < 0
+        if bool((none[0] & live[:N]).any()):
+            raise RuntimeError("beam_search: a source env has no candidate left (every candidate's cost is +inf or NaN)")
+        parent, action = torch.where(none, parent[:1], parent), torch.where(none, action[:1], action)
+        clock.lap("select")
+        beams.restore(snap, (parent.long() * N + ar).reshape(-1), rows=True)
+        clock.lap("restore")
+        live = torch.gather(live.reshape(W, N), 0, parent.long()).reshape(-1)
+        count = torch.gather(count.reshape(W, N), 0, parent.long()).reshape(-1)
+        act = table[action.clamp(min=0).long().reshape(-1)]
+        _, rw, _ = beams.rollout(act[None].contiguous(), trace=False, rewards=True, mo=mo_beams, state=True)
+        beams.reward.copy_(torch.where(live, rw[0], beams.reward))
+        clock.lap("step")
+        back_parent.append(parent)
+        back_action.append(action)
+        prev_live, prev_count = live, count
+        r = beams.read()
+    beams.done.copy_(r["done"])
+
+    if objective is None:
+        best = torch.zeros(N, dtype=torch.int64, device=dev)
+    else:
+        final = objective_values(beams, objective, r).reshape(W, N)
+        best = torch.argmin(torch.where(cum < inf, final, torch.full_like(final, inf)), dim=0)          # first minimum
+    batch.restore(beams.snapshot(best * N + ar), rows=True)
+
+    # the winner's actions: follow the back-pointers from its final rank to the first decision
+    D = len(back_parent)
+    actions, steps = np.zeros((D, N, 2), np.uint8), np.zeros(N, np.int64)
+    if D:
+        bp, ba, tab = torch.stack(back_parent).cpu().numpy(), torch.stack(back_action).cpu().numpy(), table.cpu().numpy()
+        rank, cols = best.cpu().numpy(), np.arange(N)
+        for t in range(D - 1, -1, -1):
+            a = ba[t, rank, cols]
+            took = a >= 0                        # (-1: the env had finished before this decision)
+            actions[t, took] = tab[a[took]]
+            steps += took
+            rank = bp[t, rank, cols]
+    return dict(objective=None if objective is None else objective_values(batch, objective), best=best, cost=cum, actions=actions,
+                steps=steps, beams=beams, expand=expand)

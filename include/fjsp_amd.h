@@ -673,6 +673,20 @@ int fjsp_policy_sample(const float *d_probs, int32_t n, int32_t n_actions, int32
                        const uint64_t *d_seed, uint64_t counter, uint8_t *d_pair, float *d_action, float *d_log_prob,
                        void *stream);
 
+/* The selection step of a beam search (policy_search.beam_search; csrc/fjsp_beam.hip) for n_src source envs in ONE
+ * launch, one wavefront per source env.  d_cost f64[width_in][n_src][n_actions], beam-major like every branch batch
+ * (beam b of source env i is branch env b * n_src + i): entry (b, i, a) is the cost of applying action a in beam b of
+ * source env i, lower is better; a NaN or +inf entry is not a candidate.  d_done u8[width_in][n_src] (nullable:
+ * nothing done): a done beam has exactly one candidate, (b, action -1) with cost d_cost[b][i][0]; its other entries
+ * are ignored whatever they hold.  Outputs, all [width_out][n_src]: d_parent / d_action i32 and d_cost_out f64 = the parent beam, the
+ * action and the cost (the input's bits) of source env i's k-th candidate in ascending cost, equal costs by lower
+ * parent, then lower action; -0.0 and 0.0 are equal.  Ranks beyond the number of candidates: parent -1, action -1,
+ * cost +inf.  The costs are compared and never computed with: the result is a function of the input bits.
+ * Stream-ordered, no host synchronisation, capturable.  FJSP_E_ARG before any device call: a null d_cost or output,
+ * n_src < 1, width_in or width_out outside 1..64, n_actions outside 1..128 (MO_DFJSP has 120 actions). */
+int fjsp_beam_select(const double *d_cost, const uint8_t *d_done, int32_t n_src, int32_t width_in, int32_t n_actions,
+                     int32_t width_out, int32_t *d_parent, int32_t *d_action, double *d_cost_out, void *stream);
+
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
  *
