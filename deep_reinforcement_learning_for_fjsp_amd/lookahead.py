@@ -14,12 +14,16 @@ chosen candidate from the next state reproduces its branch's objective: the obje
 above the best fixed candidate's.  Random-rule candidates (SO_FJSSP task rule 6 / machine rule 5 style
 random.choice rules) are allowed, but a branch continues on its own slot's random stream, so the bound does not hold
 for them.  Out of scope: truncated horizons.
+
+rule_front does not decide step by step: it plays every candidate from the current state to the end once and returns,
+per env, the Pareto front of the finished episodes over several objectives (pareto.select).
 """
 import time
 
 import numpy as np
 import torch
 
+from . import pareto
 from .batch import (EnvBatch, ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT, ST_SCHEDULE_OVERFLOW, VARIANT_MO_DFJSP,
                     VARIANT_MO_FJSSP_DISCRETES, VARIANT_SO_DFJSP, VARIANT_SO_FJSSP, VARIANT_SO_SFJSP)
 
@@ -209,6 +213,24 @@ def decide_by_rollouts(batch, pairs, objective, mo, branch, timings, who, state,
     return dict(actions=actions, steps=steps.cpu().numpy(), objective=objective_values(batch, objective), branch=branch)
 
 
+def play_rules(branch, acts, mo_branch, who, lap=None):
+    """Play the restored branch batch to the end with the given actions, acts u8[T, P x N, 2] (the fused rule rollout; T
+    bounds the steps any env has left), and return its read().  lap() is called between the launch and the read."""
+    branch.rollout(acts, trace=False, rewards=False, mo=mo_branch, state=False)
+    if lap is not None:
+        lap()
+    rb = branch.read()
+    check_status(rb, "branch", who)
+    while not bool((rb["done"] != 0).all()):       # (a step dispatches one operation: not expected to run; T still bounds it)
+        before = rb["step_count"].long()
+        branch.rollout(acts, trace=False, rewards=False, mo=mo_branch, state=False)
+        rb = branch.read()
+        check_status(rb, "branch", who)
+        if not bool(((rb["done"] != 0) | (rb["step_count"].long() > before)).all()):
+            raise RuntimeError("%s: a branch env neither finished nor advanced" % who)
+    return rb
+
+
 def rollout_dispatch(batch, candidates, objective, mo=None, branch=None, timings=None):
     """Play every env of `batch` (an EnvBatch or a Batched* wrapper, reset and not yet stepped, or mid-episode) to the end,
     choosing at every decision the candidate whose rollout to the end gives the lowest objective.
@@ -232,17 +254,45 @@ def rollout_dispatch(batch, candidates, objective, mo=None, branch=None, timings
     def play_branch(branch, T, mo_branch, src_dev, clock):
         if not act_buf or act_buf[0].shape[0] < T:
             act_buf[:] = [branch_act[None].expand(T, P * N, 2).contiguous()]
-        branch.rollout(act_buf[0][:T], trace=False, rewards=False, mo=mo_branch, state=False)
-        clock.lap("rollout")
-        rb = branch.read()
-        check_status(rb, "branch", "rollout_dispatch")
-        while not bool((rb["done"] != 0).all()):       # (a step dispatches one operation: not expected to run; T still bounds it)
-            before = rb["step_count"].long()
-            branch.rollout(act_buf[0][:T], trace=False, rewards=False, mo=mo_branch, state=False)
-            rb = branch.read()
-            check_status(rb, "branch", "rollout_dispatch")
-            if not bool(((rb["done"] != 0) | (rb["step_count"].long() > before)).all()):
-                raise RuntimeError("rollout_dispatch: a branch env neither finished nor advanced")
-        return rb
+        return play_rules(branch, act_buf[0][:T], mo_branch, "rollout_dispatch", lambda: clock.lap("rollout"))
 
     return decide_by_rollouts(batch, pairs, objective, mo, branch, timings, "rollout_dispatch", False, play_branch)
+
+
+def objective_vectors(branch, objectives, r, blocks):
+    """f64[blocks, N, D]: the `objectives` (each as objective_values takes it) of a finished blocks x N branch batch."""
+    if len(objectives) < 1:
+        raise ValueError("at least one objective is needed")
+    return torch.stack([objective_values(branch, o, r) for o in objectives], dim=1).reshape(blocks, branch.N // blocks, len(objectives))
+
+
+def rule_front(batch, candidates, objectives=("makespan", "tardiness"), mo=None, branch=None, cap=None):
+    """The Pareto front, per env, of P fixed candidates each played from the env's current state to the end of its
+    episode: branch block p plays candidate p (one fused rule rollout of the P x N branch batch), the finished
+    episodes' objective vectors go through one pareto.select.
+
+    candidates, mo, branch: as rollout_dispatch (P at most 1024).  objectives: 1..4 of "makespan", "tardiness", "energy"
+    (MO_DFJSP) or callables on read(), lower is better.  cap: the front members kept per env (default P).
+    The source batch is only read: its state rows, read() and schedule stay as they were.
+
+    Returns dict(objectives=f64[P, N, D], index=i32[N, cap] the front's candidates in ascending lexicographic order of
+    their vectors (-1 past the front), count=i32[N], mask=u8[P, N], front=f64[N, cap, D] (NaN past the front),
+    branch=the branch batch, holding the finished episodes)."""
+    who = "rule_front"
+    batch = getattr(batch, "batch", batch)
+    pairs = candidate_pairs(candidates, batch.variant)
+    P, N, dev = len(pairs), batch.N, batch.device
+    if P > pareto.MAX_CANDIDATES:
+        raise ValueError("%s: at most %d candidates, got %d" % (who, pareto.MAX_CANDIDATES, P))
+    check_branch_shape(N, batch.n_inst, P, who)
+    branch = branch_for(batch, P, branch, who)
+    r = batch.read()
+    check_status(r, "source", who)
+    left = torch.where(r["done"] == 0, ops_per_env(batch) - r["step_count"].long(), torch.zeros(N, dtype=torch.int64, device=dev))
+    T = max(int(left.max().item()), 1)
+    branch.restore(batch.snapshot(), np.tile(np.arange(N, dtype=np.int64), P), rows=False)
+    acts = torch.as_tensor(pairs, device=dev)[None, :, None, :].expand(T, P, N, 2).reshape(T, P * N, 2).contiguous()   # candidate p in block p
+    rb = play_rules(branch, acts, mo_rows(mo, N, dev, P), who)
+    obj = objective_vectors(branch, objectives, rb, P)
+    index, count, mask = pareto.select(obj, cap=cap)
+    return dict(objectives=obj, index=index, count=count, mask=mask, front=pareto.front_points(obj, index), branch=branch)

@@ -1,5 +1,5 @@
-"""Decoding a trained dispatching policy on the device: greedy play, best-of-K sampling, a policy rollout lookahead, and
-beam search.
+"""Decoding a trained dispatching policy on the device: greedy play, best-of-K sampling, a policy rollout lookahead,
+beam search, and the Pareto front of several policies' sampled episodes.
 
 The first three share one launch, fjsp_env_play_policy (play_policy_kernel, csrc/fjsp_kernels_policy.inc): every env plays to
 the end of its episode with the actor evaluated inside the environment kernel and no rollout-buffer traffic.  The actor is
@@ -21,6 +21,8 @@ argmax or fjsp_policy_sample, one env step), only more slowly.
   env's width x A candidates under a stated total order (cost, then parent beam, then action), the beam batch is
   gathered through a snapshot pair and takes one step.  The search is reproducible bit for bit; width 1 is greedy play
   (logp) or policy_lookahead (rollout).
+- pareto_front: P actors x k episodes per env, played as best_of plays them, and the non-dominated set of their
+  objective vectors per env (pareto.select, fjsp_pareto_select, csrc/fjsp_pareto.hip) instead of one minimum.
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -30,12 +32,12 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, pareto
 from ._capi import ptr as _ptr
 from .agents.native_actor import native_actor_forward, native_actor_params
 from .batch import ST_BAD_MACHINE_RULE, ST_BAD_TASK_RULE, ST_NO_EVENT
 from .lookahead import (ACTION_RANGES, OBJECTIVES, Clock, branch_for, candidate_pairs, check_branch_shape, check_status,
-                        decide_by_rollouts, mo_rows, objective_values, ops_per_env)
+                        decide_by_rollouts, mo_rows, objective_values, objective_vectors, ops_per_env)
 
 # the status bits at which an env stops playing (the kernel's and fjsp_env_rollout's `live` test)
 _STOP_BITS = ST_BAD_TASK_RULE | ST_BAD_MACHINE_RULE | ST_NO_EVENT
@@ -212,6 +214,79 @@ def best_of(batch, actor, k, objective, seed=0, mo=None, branch=None):
     win = branch.snapshot(best * N + torch.arange(N, device=dev))
     batch.restore(win, rows=True)
     return dict(objective=objective_values(batch, objective), best=best, branch=branch)
+
+
+def pareto_front(batch, actors, k, objectives=("makespan", "tardiness"), seed=0, mos=None, branch=None, keep_branches=False, cap=None,
+                 timings=None):
+    """The Pareto front, per env, of the P x k episodes that P actors decode: actor p plays a k x N branch exactly as
+    best_of does (block 0 greedy in the source's own slots, blocks 1..k-1 sampled with `seed`), so candidate p * k + j is
+    the episode best_of(batch, actors[p], k, ..., seed) plays in its block j; the finished episodes' objective vectors go
+    through one pareto.select (P x k at most 1024).
+
+    actors: one actor or a list of P (MPPPO's five policies along a weight vector).  objectives: 1..4 of "makespan",
+    "tardiness", "energy" (MO_DFJSP) or callables on read(), lower is better.  mos: None (a wrapper's own `mo`), one
+    f64[N, 4] for every actor, or a list of P of them.  branch: an EnvBatch of k x N envs (lookahead.make_branch) that
+    every actor plays in turn, or None; with keep_branches=True each actor gets its own (branch: a list of P, or None)
+    and they are returned still holding their finished episodes, recording iff the source records: a front member's
+    schedule is branches[p].schedule() of env j * N + i.  cap: the front members kept per env (default P x k).
+    timings: a dict that receives the synchronised seconds of the parts "play" and "select".
+    The source batch is only read: its state rows, read() and schedule stay as they were.
+
+    Returns dict(objectives=f64[P x k, N, D], index=i32[N, cap] the front's candidates in ascending lexicographic order
+    of their vectors (-1 past the front), count=i32[N], mask=u8[P x k, N], front=f64[N, cap, D] (NaN past the front),
+    policy=index // k and block=index % k (i32[N, cap], -1 past the front), branch=the branch batch or, with
+    keep_branches, branches=the list of P)."""
+    who = "pareto_front"
+    batch, mo_own = _unwrap(batch, None)
+    actors = list(actors) if isinstance(actors, (list, tuple)) else [actors]
+    P, k = len(actors), int(k)
+    if P < 1 or k < 1 or P * k > pareto.MAX_CANDIDATES:
+        raise ValueError("%s: needs at least one actor, k >= 1 and at most %d episodes per env, got %d x %d" % (who, pareto.MAX_CANDIDATES, P, k))
+    for o in objectives:
+        _check_objective(o)
+    if isinstance(mos, (list, tuple)):
+        if len(mos) != P:
+            raise ValueError("%s: mos must be None, one mo or one per actor (%d), got %d" % (who, P, len(mos)))
+    else:
+        mos = [mo_own if mos is None else mos] * P
+    if keep_branches:
+        branches = list(branch) if branch is not None else [None] * P
+        if len(branches) != P:
+            raise ValueError("%s: with keep_branches, branch must be None or one branch per actor (%d)" % (who, P))
+    else:
+        branches = [branch_for(batch, k, branch, who)] * P
+    N, dev = batch.N, batch.device
+    src = np.tile(np.arange(N, dtype=np.int64), k)
+    src_dev = torch.as_tensor(src, device=dev)
+    snap = batch.snapshot()
+    clock = Clock(timings, dev)
+    clock.start()
+    obj = []
+    for p, actor in enumerate(actors):
+        _, pair_div = action_encoding(actor, batch)
+        br = branches[p] = branch_for(batch, k, branches[p], who)
+        if _recording(br) != _recording(batch):
+            br.record_schedule(_recording(batch))
+        br.restore(snap, src, rows=False)
+        _play(br, actor, pair_div, N, seed, mo_rows(mos[p], N, dev, k), None, None, src_dev, batch.state, False, True)
+        rb = br.read()
+        check_status(rb, "branch", who)
+        if not bool((rb["done"] != 0).all()):
+            raise RuntimeError("%s: a branch env did not finish its episode" % who)
+        obj.append(objective_vectors(br, objectives, rb, k))
+    obj = torch.cat(obj, dim=0)
+    clock.lap("play")
+    index, count, mask = pareto.select(obj, cap=cap)
+    clock.lap("select")
+    on = index >= 0
+    none = torch.full_like(index, -1)
+    out = dict(objectives=obj, index=index, count=count, mask=mask, front=pareto.front_points(obj, index),
+               policy=torch.where(on, index // k, none), block=torch.where(on, index % k, none))
+    if keep_branches:
+        out["branches"] = branches
+    else:
+        out["branch"] = branches[0]
+    return out
 
 
 def policy_lookahead(batch, actor, objective, candidates=None, mo=None, branch=None, timings=None):

@@ -687,6 +687,23 @@ int fjsp_policy_sample(const float *d_probs, int32_t n, int32_t n_actions, int32
 int fjsp_beam_select(const double *d_cost, const uint8_t *d_done, int32_t n_src, int32_t width_in, int32_t n_actions,
                      int32_t width_out, int32_t *d_parent, int32_t *d_action, double *d_cost_out, void *stream);
 
+/* The Pareto front of every source env's candidates (pareto.select; csrc/fjsp_pareto.hip; the reference's
+ * filter_pareto_front, utilities/Utility_Class.py:132-146) for n_src source envs in ONE launch.  d_obj
+ * f64[n_cand][n_src][n_obj], candidate-major like every branch batch (candidate c of source env i is branch env
+ * c * n_src + i); lower is better in every objective.  d_valid u8[n_cand][n_src] (nullable: every candidate valid).  A
+ * candidate with valid == 0 or with a NaN in any objective is not a candidate; the infinities are ordinary values under
+ * IEEE comparison; -0.0 and 0.0 are equal.  Candidate c is on the front iff no candidate j has obj[j] <= obj[c] in
+ * every objective and < in at least one, and no candidate j < c has the same objective vector (of equal points the
+ * lowest index survives).  Outputs: d_index i32[n_src][cap] = the front members' candidate indices in ascending
+ * lexicographic order of their objective vectors, objective 0 most significant (np.unique(axis=0)'s order), -1 past
+ * the front; d_count i32[n_src] = the true front size, which may exceed cap (d_index then holds the first cap
+ * members); d_mask u8[n_cand][n_src] (nullable) = 1 on the front.  The values are compared and never computed with;
+ * no atomics: the result is a function of the input bits.  Stream-ordered, no host synchronisation, capturable.
+ * FJSP_E_ARG before any device call: a null d_obj, d_index or d_count, n_src < 1, n_cand outside 1..1024, n_obj
+ * outside 1..4, cap outside 1..n_cand. */
+int fjsp_pareto_select(const double *d_obj, const uint8_t *d_valid, int32_t n_src, int32_t n_cand, int32_t n_obj,
+                       int32_t cap, int32_t *d_index, int32_t *d_count, uint8_t *d_mask, void *stream);
+
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
  *
