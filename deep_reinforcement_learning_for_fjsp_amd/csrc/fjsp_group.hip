@@ -766,6 +766,7 @@ GDEV void g_open(GE<V> &e, const DevBatch &b, int wave_id, unsigned char *lds, i
     uint32_t asgw, jwl = 0;
     int tend = 0, mjob = -1;
     long long sc, sc2 = 0;
+    [[maybe_unused]] uint4 scw[4];       // early build: EnvScalars words 0..7, the same in every lane of the row
     if constexpr (EARLY) {
         // straight-line: a lane without an operation type (or job, or machine) reads the LAST entry its row reads anyway (a line
         // the row fetches: no byte more, never an address outside the instance's or the environment's record) and drops the
@@ -786,7 +787,11 @@ GDEV void g_open(GE<V> &e, const DevBatch &b, int wave_id, unsigned char *lds, i
         const int ml = min(e.l, MP - 1);
         tend = reinterpret_cast<const int32_t *>(er + FO::e_tend())[ml];
         mjob = reinterpret_cast<const int32_t *>(er + FO::e_mjob((uint32_t)MP))[ml];
-        sc = reinterpret_cast<const long long *>(er)[e.l];                        // EnvScalars words 0..15
+        // EnvScalars words 0..7 are row-uniform: four 16-byte loads from the row's one address hand them to all 16 lanes (the
+        // line the per-lane load asked for; no DPP fan-out behind the wait, see "consume").  Words 8..17, obs_prev, stay per lane.
+#pragma unroll
+        for (int q = 0; q < 4; ++q) scw[q] = reinterpret_cast<const uint4 *>(er)[q];
+        sc = reinterpret_cast<const long long *>(er)[max(e.l, 8)];                // obs_prev[0..7]
         sc2 = reinterpret_cast<const long long *>(er)[16 + min(e.l, 1)];          // obs_prev[8], [9]
         // ---- mask: exactly the values of the predicated form
 #pragma unroll
@@ -846,14 +851,24 @@ GDEV void g_open(GE<V> &e, const DevBatch &b, int wave_id, unsigned char *lds, i
     e.duej = duej;
     e.asgw = asgw; e.jwl = e.l < e.njobs ? jwl : 0xFFFFFFFFu;
     e.tend = e.l < e.M ? tend : 0; e.mjob = e.l < e.M ? mjob : -1;
-    const int lo = (int)sc, hi = (int)(sc >> 32);
-    e.t = bc<0>(lo); e.step_count = bc<0>(hi);
-    e.done = bc<1>(lo); e.n_un = bc<1>(hi);
-    e.status = bcu<2>((uint32_t)lo); e.seq_ctr = bcu<2>((uint32_t)hi);
-    e.rng_calls = bcu<3>((uint32_t)lo); e.busy = bcu<3>((uint32_t)hi);
-    e.completion = bc<4>(lo); e.completion_last = bc<4>(hi);
-    e.tard_done = bcl<5>(sc); e.delay_sum = bcl<6>(sc);
-    e.t_arr = bc<7>(lo); e.misc = bcu<7>((uint32_t)hi);
+    if constexpr (EARLY) {
+        // (every lane holds the eight words: no broadcast out of the lane that loaded them)
+        e.t = (int)scw[0].x; e.step_count = (int)scw[0].y; e.done = (int)scw[0].z; e.n_un = (int)scw[0].w;
+        e.status = scw[1].x; e.seq_ctr = scw[1].y; e.rng_calls = scw[1].z; e.busy = scw[1].w;
+        e.completion = (int)scw[2].x; e.completion_last = (int)scw[2].y;
+        e.tard_done = (long long)(((uint64_t)scw[2].w << 32) | scw[2].z);
+        e.delay_sum = (long long)(((uint64_t)scw[3].y << 32) | scw[3].x);
+        e.t_arr = (int)scw[3].z; e.misc = scw[3].w;
+    } else {
+        const int lo = (int)sc, hi = (int)(sc >> 32);
+        e.t = bc<0>(lo); e.step_count = bc<0>(hi);
+        e.done = bc<1>(lo); e.n_un = bc<1>(hi);
+        e.status = bcu<2>((uint32_t)lo); e.seq_ctr = bcu<2>((uint32_t)hi);
+        e.rng_calls = bcu<3>((uint32_t)lo); e.busy = bcu<3>((uint32_t)hi);
+        e.completion = bc<4>(lo); e.completion_last = bc<4>(hi);
+        e.tard_done = bcl<5>(sc); e.delay_sum = bcl<6>(sc);
+        e.t_arr = bc<7>(lo); e.misc = bcu<7>((uint32_t)hi);
+    }
     e.obs_prev = __longlong_as_double(e.l >= 8 ? sc : sc2);
     e.obs_re = 0.0; e.re_on = false;
     if constexpr (EARLY) {
@@ -863,6 +878,9 @@ GDEV void g_open(GE<V> &e, const DevBatch &b, int wave_id, unsigned char *lds, i
 #pragma unroll
         for (int s = 0; s < GS; ++s) asm volatile("" : "+v"(e.kB[s]), "+v"(e.em[s]), "+v"(e.rsum[s]), "+v"(e.tsum[s]));
         asm volatile("" : "+v"(e.asgw), "+v"(e.jwl), "+v"(e.tend), "+v"(e.mjob), "+v"(e.obs_prev), "+v"(e.duej), "+v"(e.jinfo));
+        // (the row-uniform words no longer pass through a DPP move, which was their use: they are taken here as well)
+        asm volatile("" : "+v"(e.t), "+v"(e.step_count), "+v"(e.done), "+v"(e.n_un), "+v"(e.status), "+v"(e.seq_ctr), "+v"(e.rng_calls), "+v"(e.busy));
+        asm volatile("" : "+v"(e.completion), "+v"(e.completion_last), "+v"(e.tard_done), "+v"(e.delay_sum), "+v"(e.t_arr), "+v"(e.misc));
     }
     e.env_seed = b.rng_seed + (uint64_t)e.env * 1000003ULL;
 }
