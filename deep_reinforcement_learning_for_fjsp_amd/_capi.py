@@ -136,6 +136,7 @@ SIGNATURES = {
     "fjsp_env_kernel_family": (_i32, [_vp]),
     "fjsp_env_row_build": (C.c_int, [_vp, _i32, _vp]),
     "fjsp_env_policy_build": (C.c_int, [_vp, _i32, _vp]),
+    "fjsp_env_policy_orders_build": (C.c_int, [_vp, _i32, _vp]),
     "fjsp_env_set_lp_threads": (C.c_int, [_vp, _i32]),
     "fjsp_env_lp_solves": (_i64, [_vp]),
     "fjsp_env_lp_on_device": (_i32, [_vp]),
@@ -155,6 +156,9 @@ SIGNATURES = {
     "fjsp_env_rollout_policy": (C.c_int, [_vp, _vp, C.POINTER(ActorParams), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_env_play_policy": (C.c_int, [_vp, C.POINTER(ActorParams), _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp]),
+    "fjsp_env_rollout_policy_orders": (C.c_int, [_vp, _vp, C.POINTER(ActorParams), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fjsp_env_play_policy_orders": (C.c_int, [_vp, C.POINTER(ActorParams), _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp]),
     "fjsp_ppo_partials": (C.c_int, [_i32]),
     "fjsp_ppo_actor_loss": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_ppo_critic_loss": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),

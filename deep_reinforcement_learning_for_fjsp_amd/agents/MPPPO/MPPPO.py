@@ -357,8 +357,9 @@ class FusedSampler(object):
 
 def fused_policy_rollout(env, learner, memory, fused, old_log_prob, exploration, T):
     """The whole rollout loop (MPPPO.py:245-252) in ONE launch of fjsp_env_rollout_policy: the actor runs inside the
-    environment kernel, rows go straight into `memory`.  Returns False when the batch / network shape is not
-    supported (multi-order instances, another network size): the caller falls back to the per-step loop."""
+    environment kernel, rows go straight into `memory`.  A batch with order arrivals takes fjsp_env_rollout_policy_orders:
+    one such launch per segment of the episode, the arrival service between them.  Returns False when the batch / network
+    shape is not supported (MO_DFJSP, another network size): the caller falls back to the per-step loop."""
     from ... import _capi
     import ctypes as C
     ap = native_actor_params(learner.actor_new)
@@ -370,9 +371,11 @@ def fused_policy_rollout(env, learner, memory, fused, old_log_prob, exploration,
     memory.clear()
     state = env.reset()
     fused.new_round(exploration)
-    rc = _capi.lib().fjsp_env_rollout_policy(batch._h, memory._h, C.byref(ap), p(fused.eps), p(fused.seed), fused.div, int(T), p(mo),
-                                            p(state), p(fused.flat_actions), p(old_log_prob), p(batch.state),
-                                            _capi.stream(batch.device_index))
+    args = (batch._h, memory._h, C.byref(ap), p(fused.eps), p(fused.seed), fused.div, int(T), p(mo), p(state), p(fused.flat_actions),
+            p(old_log_prob), p(batch.state), _capi.stream(batch.device_index))
+    rc = _capi.lib().fjsp_env_rollout_policy(*args)
+    if rc == _capi.FJSP_E_UNSUPPORTED:
+        rc = _capi.lib().fjsp_env_rollout_policy_orders(*args)
     if rc == _capi.FJSP_E_UNSUPPORTED:
         return False
     _capi.check(rc)
@@ -528,8 +531,8 @@ class PPO(Base_Agent):
         self.fused_sampling = fused_sampling or fused_rollout
         # fused_rollout: the whole rollout loop in one launch with the actor inside the environment kernel
         # (fjsp_env_rollout_policy: every single-order batch, up to 256 operation types and as many jobs as create
-        # admits); falls back to the per-step loop for an actor of another shape than S -> 128 -> 128 -> A and for
-        # batches with order arrivals
+        # admits; batches with order arrivals through fjsp_env_rollout_policy_orders, one launch per segment between
+        # arrival services); falls back to the per-step loop for an actor of another shape than S -> 128 -> 128 -> A
         self.fused_rollout = fused_rollout
         self.learner_graph = use_graph
         self.device = environment.device

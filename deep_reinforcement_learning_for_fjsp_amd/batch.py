@@ -376,6 +376,15 @@ class EnvBatch(object):
         check(self._lib.fjsp_env_policy_build(self._h, int(state_size), out))
         return dict(envs_per_workgroup=int(out[0]), lds_bytes=int(out[1]), kc=int(out[2]))
 
+    def policy_orders_build(self, state_size):
+        """policy_build for a batch with order arrivals, which the segmented entries play (fjsp_env_play_policy_orders,
+        fjsp_env_rollout_policy_orders; fjsp_env_policy_orders_build): dict(envs_per_workgroup, lds_bytes, kc, segments = the
+        policy launches of one call at most, the largest order count of the batch).  FjspError (FJSP_E_UNSUPPORTED) for a batch
+        they refuse: no order arrivals, MO_DFJSP."""
+        out = (C.c_int32 * 4)()
+        check(self._lib.fjsp_env_policy_orders_build(self._h, int(state_size), out))
+        return dict(envs_per_workgroup=int(out[0]), lds_bytes=int(out[1]), kc=int(out[2]), segments=int(out[3]))
+
     def env_seed(self, e):
         """random.choice stream seed of (local) env e (matches open_env() in fjsp_kernels.hip)."""
         return (self.rng_seed + (self.first_env + e) * ENV_SEED_STRIDE) & (2 ** 64 - 1)

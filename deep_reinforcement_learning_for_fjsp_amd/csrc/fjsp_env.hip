@@ -704,6 +704,128 @@ int fjsp_env_policy_build(const fjsp_env *e, int32_t state_size, int32_t *out3) 
     return FJSP_OK;
 }
 
+// ---- the same on batches with order arrivals: one policy launch per segment, the arrival service between them
+namespace {
+const char kOrdersActor[] = "the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32)";
+// What keeps the segmented policy kernels from running this batch (the batch alone: asked before the actor's shape)
+const char *policy_orders_batch_refusal(const fjsp_env *e) {
+    if (e->b.variant == FJSP_VARIANT_MO_DFJSP)
+        return "MO_DFJSP batches are not played inside the launch (their 12 x 10 actions do not fit the in-kernel actor)";
+    if (!e->b.mord)
+        return "the batch has no order arrivals: fjsp_env_play_policy / fjsp_env_rollout_policy run it in one launch";
+    return nullptr;
+}
+const char *policy_orders_geometry_refusal(const fjsp_env *e, int S, PolicyGeometry *g) {
+    *g = policy_geometry(e->b, S);
+    return g->envs > 0 ? nullptr : "one environment's LDS slice does not fit the 160 KB of a CU beside the actor's weights";
+}
+// Between two segments: the LPs of the envs the last launch parked, then arrival_kernel into the rows given.  *more = false
+// where the service knows that nothing parked (the host route fetches the count anyway): every env has finished or reached T.
+int serve_segment(fjsp_env *e, const double *d_mo, double *d_state, double *d_reward, uint8_t *d_done, hipStream_t st, bool *more) {
+    const int rc = service_arrivals(e, d_mo, d_state, d_reward, d_done, nullptr, st);
+    *more = rc == FJSP_OK && (e->arr.lp_device || e->arr.h_pending[0] != 0);
+    return rc;
+}
+// The rollout's per-env progress between segments: next_t i32[N], the arrival's reward f64[N], parked u8[N]; owned by the
+// handle, allocated by the first segmented rollout
+int segment_scratch(fjsp_env *e) {
+    if (e->d_seg_reward) return FJSP_OK;
+    const size_t N = (size_t)e->b.N;
+    double *p = nullptr;
+    if (!dev_alloc(e, N * 8 + N * 4 + N, &p, "hipMalloc (segment scratch)")) return FJSP_E_HIP;
+    e->d_seg_reward = p;
+    return FJSP_OK;
+}
+}  // namespace
+
+int fjsp_env_rollout_policy_orders(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_params *actor, const float *d_epsilon,
+                                   const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
+                                   float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream) {
+    const char *who = "fjsp_env_rollout_policy_orders";
+    if (!e || !buf || !d_epsilon || !d_seed || !d_state_in || !d_flat_actions || !d_log_prob || !d_state_last || T <= 0 || pair_div < 0) {
+        set_error(std::string(who) + ": bad arguments"); return FJSP_E_ARG;
+    }
+    if (const int rc = usable(e, who, kIntact | kIdle)) return rc;
+    if (buf->N != e->b.N || buf->S != e->b.state_size || buf->T < T || buf->device != e->device) {
+        set_error(std::string(who) + ": the rollout buffer does not match the batch (N, state_size, T, device)"); return FJSP_E_ARG;
+    }
+    if (const char *why = policy_orders_batch_refusal(e)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+    if (!actor_ok(actor) || actor->state_size != e->b.state_size) { set_error(std::string(who) + ": " + kOrdersActor); return FJSP_E_UNSUPPORTED; }
+    PolicyGeometry geo{};
+    if (const char *why = policy_orders_geometry_refusal(e, actor->state_size, &geo)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+    DeviceGuard guard(e->device);
+    if (const int rc = segment_scratch(e)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t N = (size_t)e->b.N;
+    PolicyRolloutIO io;
+    io.state_in = d_state_in; io.epsilon = d_epsilon; io.seed = d_seed; io.pair_div = pair_div;
+    io.o_state = buf->states; io.o_actions = buf->actions; io.o_reward = buf->rewards; io.o_next = buf->next_states;
+    io.o_done = buf->dones; io.o_valid = buf->valid; io.o_flat = d_flat_actions; io.o_logp = d_log_prob; io.state_last = d_state_last;
+    PolicySegment sg;
+    sg.next_t = reinterpret_cast<int32_t *>(e->d_seg_reward + N); sg.parked = reinterpret_cast<uint8_t *>(sg.next_t + N);
+    sg.reward = e->d_seg_reward; sg.done = e->d_done_scratch;
+    const ActorParams ap = actor_of(actor);
+    for (int seg = 0; seg < e->b.SP; ++seg) {
+        sg.seg = seg;
+        if (launch_rollout_policy_orders(e->b, ap, io, sg, d_mo, T, st, e->sched) != 0) {
+            set_error("rollout_policy_orders_kernel launch failed"); return FJSP_E_HIP;
+        }
+        if (seg + 1 == e->b.SP) break;           // (an env of S orders parks S - 1 times at most: nothing parked in the last launch)
+        bool more = false;
+        if (const int rc = serve_segment(e, d_mo, d_state_last, e->d_seg_reward, e->d_done_scratch, st, &more)) return rc;
+        if (!more) break;
+    }
+    buf->len = T;
+    return FJSP_OK;
+}
+
+int fjsp_env_play_policy_orders(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
+                                int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
+                                const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
+                                double *d_reward_last, uint8_t *d_done_last, void *stream) {
+    const char *who = "fjsp_env_play_policy_orders";
+    if (!e || T <= 0 || n_greedy < 0 || pair_div < 0 || !d_state_in || n_state_in <= 0 || !d_steps_out || !d_state_last ||
+        !d_reward_last || !d_done_last) {
+        set_error(std::string(who) + ": bad arguments"); return FJSP_E_ARG;
+    }
+    if (const int rc = usable(e, who, kIntact | kIdle)) return rc;
+    if (const char *why = policy_orders_batch_refusal(e)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+    if (!actor_ok(actor) || actor->state_size != e->b.state_size) { set_error(std::string(who) + ": " + kOrdersActor); return FJSP_E_UNSUPPORTED; }
+    if (pair_div > 0 && actor->n_actions % pair_div != 0) { set_error(std::string(who) + ": pair_div does not divide n_actions"); return FJSP_E_ARG; }
+    if (n_greedy < e->b.N && !d_seed) { set_error(std::string(who) + ": sampling envs need d_seed"); return FJSP_E_ARG; }
+    if (!d_state_src && n_state_in < e->b.N) { set_error(std::string(who) + ": d_state_in has fewer rows than the batch"); return FJSP_E_ARG; }
+    PolicyGeometry geo{};
+    if (const char *why = policy_orders_geometry_refusal(e, actor->state_size, &geo)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+    DeviceGuard guard(e->device);
+    hipStream_t st = (hipStream_t)stream;
+    PolicyPlayIO io;
+    io.state_in = d_state_in; io.state_src = d_state_src; io.n_state_in = n_state_in; io.seed = d_seed; io.first = d_first;
+    io.pair_div = pair_div; io.n_greedy = n_greedy; io.actions_out = d_actions_out; io.steps_out = d_steps_out;
+    io.state_last = d_state_last; io.reward_last = d_reward_last; io.done_last = d_done_last;
+    const ActorParams ap = actor_of(actor);
+    for (int seg = 0; seg < e->b.SP; ++seg) {
+        if (launch_play_policy_orders(e->b, ap, io, d_mo, T, seg, st, e->sched) != 0) {
+            set_error("play_policy_orders_kernel launch failed"); return FJSP_E_HIP;
+        }
+        if (seg + 1 == e->b.SP) break;           // (an env of S orders parks S - 1 times at most: nothing parked in the last launch)
+        bool more = false;
+        if (const int rc = serve_segment(e, d_mo, d_state_last, d_reward_last, d_done_last, st, &more)) return rc;
+        if (!more) break;
+    }
+    return FJSP_OK;
+}
+
+int fjsp_env_policy_orders_build(const fjsp_env *e, int32_t state_size, int32_t *out4) {
+    const char *who = "fjsp_env_policy_orders_build";
+    if (!e || !out4) { set_error(std::string(who) + ": null argument"); return FJSP_E_ARG; }
+    if (state_size < 1 || state_size > 32) { set_error(std::string(who) + ": state_size outside 1..32"); return FJSP_E_ARG; }
+    if (const char *why = policy_orders_batch_refusal(e)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+    PolicyGeometry geo{};
+    if (const char *why = policy_orders_geometry_refusal(e, state_size, &geo)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+    out4[0] = geo.envs; out4[1] = (int32_t)geo.lds; out4[2] = e->b.KC; out4[3] = e->b.SP;
+    return FJSP_OK;
+}
+
 int fjsp_env_read(fjsp_env *e, int64_t *d_delay_time_sum, int32_t *d_makespan, int32_t *d_completion,
                   int32_t *d_step_time, int32_t *d_step_count, uint8_t *d_done, uint32_t *d_status, void *stream) {
     if (!e) { set_error("fjsp_env_read: null env"); return FJSP_E_ARG; }

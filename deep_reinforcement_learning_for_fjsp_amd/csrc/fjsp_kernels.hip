@@ -1639,6 +1639,26 @@ __global__ __launch_bounds__(1024) void actor_forward_kernel(ActorParams ap, con
     if (lane < ap.A) probs[(size_t)row * ap.A + lane] = ps[lane];
 }
 
+// Park an env whose step met an order arrival (w.pending after env_step), as step_kernel parks it
+// (fjsp_kernels_dispatch.inc; that text stays its own: the step kernels' code is pinned): stash (k, m) for arrival_kernel's
+// trace, take a slot of the service's pending list, leave the LP inputs there, store the env.  The policy kernels of
+// multi-order batches leave their segment through here.
+template <int KC, int V>
+__device__ __forceinline__ void park_env(W<KC, V> &w, const DevBatch &b, int env, int k_sel, int m_sel) {
+    if (w.lane == 0) {
+        int16_t *stash = reinterpret_cast<int16_t *>(w.er + b.L.e_lpq) + 2 * b.KP;
+        stash[0] = (int16_t)k_sel; stash[1] = (int16_t)m_sel;
+    }
+    uint32_t slot = 0;
+    if (w.lane == 0) { slot = atomicAdd(b.pending_count, 1u); if (slot < (uint32_t)b.N) b.pending_count[1 + slot] = (uint32_t)env; }
+    slot = min(uniu(slot), (uint32_t)b.N - 1u);     // (N slots: an env parks at most once per service)
+    wave_sync_global();
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(w.er + b.L.e_lpq);     // u16[2][KP] as KP words
+    uint32_t *dst = reinterpret_cast<uint32_t *>(b.lp_in + (size_t)slot * 2 * b.KP);
+    for (int i = w.lane; i < b.KP; i += kWave) dst[i] = src[i];
+    store_dynamic<KC, V>(w, false, false);          // (statistics are stale until arrival_kernel finishes the step)
+}
+
 #define FJSP_REC 0
 #include "fjsp_kernels_dispatch.inc"
 #undef FJSP_REC
@@ -1878,6 +1898,43 @@ int launch_play_policy(const DevBatch &b, const ActorParams &ap, const PolicyPla
         [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
             constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
             return launch_rec(&play_policy_w_kernel<KC, V>, &play_policy_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+        });
+}
+// ... and their segment builds for multi-order SO_FJSSP batches (kMord), in the same two geometries; -1 for every other batch
+template <class F16, class FW>
+static int dispatch_policy_orders(const DevBatch &b, const ActorParams &ap, F16 &&f16, FW &&fw) {
+    if (!b.mord || b.variant == FJSP_VARIANT_MO_DFJSP) return -1;
+    const PolicyGeometry g = policy_geometry(b, ap.S);
+    if (g.envs <= 0) return -1;
+    return dispatch_kc<kMord>(b.KC, [&](auto kc, auto v) {
+        constexpr int KC = decltype(kc)::value;
+        if (g.envs < 16) return fw(kc, v, grid_for_envs(b.N, g.envs), dim3(64u * (unsigned)g.envs), g.lds);
+        if constexpr (KC == 1) return f16(kc, v, grid_for16(b.N), dim3(1024), g.lds);
+        return -1;
+    });
+}
+int launch_rollout_policy_orders(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const PolicySegment &sg, const double *mo,
+                                 int T, hipStream_t st, const SchedRec &rec) {
+    return dispatch_policy_orders(b, ap,
+        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            return launch_rec(&rollout_policy_orders_kernel<KC, V>, &rollout_policy_orders_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, sg, mo, T);
+        },
+        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            return launch_rec(&rollout_policy_orders_w_kernel<KC, V>, &rollout_policy_orders_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, sg, mo, T);
+        });
+}
+int launch_play_policy_orders(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, int seg, hipStream_t st,
+                              const SchedRec &rec) {
+    return dispatch_policy_orders(b, ap,
+        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            return launch_rec(&play_policy_orders_kernel<KC, V>, &play_policy_orders_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T, seg);
+        },
+        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
+            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+            return launch_rec(&play_policy_orders_w_kernel<KC, V>, &play_policy_orders_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T, seg);
         });
 }
 

@@ -125,6 +125,18 @@ struct PolicyPlayIO {
     uint8_t *done_last;          // [N]
 };
 
+// One launch ("segment") of the policy kernels of a multi-order batch (fjsp_env_play_policy_orders, _rollout_policy_orders):
+// a wave leaves its segment when its env parks at an order arrival, the arrival service runs between the launches, the
+// next segment goes on where arrival_kernel left the env.  The play keeps its per-env progress in PolicyPlayIO::steps_out;
+// the rollout keeps it here, in device scratch owned by the handle.
+struct PolicySegment {
+    int seg;                     // index of this launch within the call; 0 starts from state_in
+    int32_t *next_t;             // [N] rollout: the step index a parked env goes on at (its parked step is row next_t - 1)
+    uint8_t *parked;             // [N] rollout: the env left the previous segment parked (0: its rows are all written)
+    const double *reward;        // [N] rollout: what arrival_kernel wrote for the parked step of every env it finished
+    const uint8_t *done;         // [N]
+};
+
 // LDS-only hand-off between the lanes of one wave (see wave_sync() in fjsp_kernels.hip)
 __device__ __forceinline__ void actor_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");

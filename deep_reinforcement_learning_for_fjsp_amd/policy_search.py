@@ -5,8 +5,11 @@ The first three share one launch, fjsp_env_play_policy (play_policy_kernel, csrc
 the end of its episode with the actor evaluated inside the environment kernel and no rollout-buffer traffic.  The actor is
 an agents.MPPPO ActorNet; the kernel takes those of the in-kernel shape (state_size <= 32 -> 128 -> 128 -> n_actions
 <= 32) on every single-order batch, whatever its operation types and jobs (EnvBatch.policy_build reports the workgroup it
-runs).  Other actors (MPPPO's 200 x 5 nets) and order-arrival batches run the same decoding as a per-step loop (actor,
-argmax or fjsp_policy_sample, one env step), only more slowly.
+runs).  A batch with order arrivals (SO_FJSSP / SO_DFJSP instances of several orders) takes fjsp_env_play_policy_orders: the
+same kernel once per segment of the episode, the arrival service (fluid LPs, arrival_kernel) between the launches -- at most
+as many launches as the batch's largest order count (EnvBatch.policy_orders_build).  Other actors (MPPPO's 200 x 5 nets) and
+MO_DFJSP batches run the same decoding as a per-step loop (actor, argmax or fjsp_policy_sample, one env step), only more
+slowly.
 
 - play: every env to the end, greedy (argmax of the actor's probabilities) or sampled (epsilon 0).
 - best_of: k episodes per env in a k x N branch batch, block 0 greedy and the others sampled; each source env ends its
@@ -92,10 +95,12 @@ def play(batch, actor, greedy=True, seed=0, mo=None, max_steps=None, first=None,
     (default: the largest count of remaining operations).  first: u8[N, 2] actions in the env encoding that step 0
     applies instead of the actor's.  state_in / state_src: env i starts from row state_src[i] of state_in (f64[M, S];
     default: the batch's own state rows, row i).  record_actions: also return the applied actions.
-    fused=False, or what the kernel refuses (an actor of another shape than state_size <= 32 -> 128 -> 128 -> n_actions
-    <= 32, a batch with order arrivals), runs the per-step loop instead; with an actor of the in-kernel
-    shape it takes the probabilities from the same device code (fjsp_actor_forward), so both give the same episode bit
-    for bit.
+    A batch with order arrivals is played in segments (fjsp_env_play_policy_orders) -- but through the loop, unless
+    fused="segments", where the segments measured no gain: host arrival LPs and fewer than four envs per workgroup
+    (EnvBatch.policy_orders_build; _segments_pay).  fused=False, or what the kernels
+    refuse (an actor of another shape than state_size <= 32 -> 128 -> 128 -> n_actions <= 32, a MO_DFJSP batch), runs the
+    per-step loop instead; with an actor of the in-kernel shape it takes the probabilities from the same device code
+    (fjsp_actor_forward), so both give the same episode bit for bit.
 
     The batch's state / reward / done rows end as a step leaves them after each env's last step.  Returns
     dict(actions=u8[T, N, 2] device tensor or None -- the action applied at each step, zero past an env's end --,
@@ -133,14 +138,29 @@ def _play(b, actor, pair_div, n_greedy, seed, mo, T, first, src, state_in, recor
     seed_t = _seed_tensor(seed, dev)
     ap = native_actor_params(actor) if fused else None
     if ap is not None:
-        rc = b._lib.fjsp_env_play_policy(b._h, C.byref(ap), int(pair_div), int(n_greedy), _ptr(seed_t), T, _ptr(mo), _ptr(state_in),
-                                         int(state_in.shape[0]), _ptr(src), _ptr(first), _ptr(acts), _ptr(steps), b._p_state,
-                                         b._p_reward, b._p_done, b._stream())
+        args = (b._h, C.byref(ap), int(pair_div), int(n_greedy), _ptr(seed_t), T, _ptr(mo), _ptr(state_in), int(state_in.shape[0]),
+                _ptr(src), _ptr(first), _ptr(acts), _ptr(steps), b._p_state, b._p_reward, b._p_done, b._stream())
+        rc = b._lib.fjsp_env_play_policy(*args)
+        if rc == _capi.FJSP_E_UNSUPPORTED and (fused == "segments" or _segments_pay(b)):
+            rc = b._lib.fjsp_env_play_policy_orders(*args)     # order arrivals: one launch per segment, the arrival service between them
         if rc != _capi.FJSP_E_UNSUPPORTED:
             _capi.check(rc)
             return dict(actions=acts, steps=steps)
     _play_loop(b, actor, pair_div, n_greedy, seed_t, T, mo, state_in, src, first, acts, steps)
     return dict(actions=acts, steps=steps)
+
+
+def _segments_pay(b):
+    """Whether play takes fjsp_env_play_policy_orders by default for a batch the one-launch entry refused.  Not where it
+    measured no gain over the per-step loop ("Order arrivals between policy launches"): arrival LPs on the
+    host and shops so large that fewer than four envs fit a workgroup -- two waves per CU then play 4096 DA3C shops no faster
+    than the loop's full-occupancy step kernel.  fused="segments" plays the segments there all the same."""
+    if b.lp_on_device:
+        return True
+    out = (C.c_int32 * 4)()
+    if b._lib.fjsp_env_policy_orders_build(b._h, int(b.state_size), out) != 0:
+        return True                               # (not a batch the segments play: their entry says so itself)
+    return out[0] >= 4
 
 
 def _play_loop(b, actor, pair_div, n_greedy, seed_t, T, mo, state_in, src, first, acts, steps):

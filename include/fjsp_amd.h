@@ -663,6 +663,29 @@ int fjsp_env_play_policy(fjsp_env *e, const fjsp_actor_params *actor, int32_t pa
  * argument or a state_size outside 1..32. */
 int fjsp_env_policy_build(const fjsp_env *e, int32_t state_size, int32_t *out3);
 
+/* The two calls above on a batch WITH order arrivals (SO_FJSSP / SO_DFJSP instances of more than one order), which the
+ * one-launch entries refuse: same arguments, same outputs, same actions as the per-step path bit for bit.  The episode
+ * is played in segments: a policy launch runs every env until it finishes, reaches T or meets an order arrival; the
+ * arrival service (the one fjsp_env_step runs: LP on the device or on the host, then arrival_kernel) finishes the steps
+ * that met one, and the next launch goes on from there -- at most S_max launches and S_max - 1 services for a batch whose
+ * instances have up to S_max orders, all on `stream`.  With the LPs on the device nothing synchronises; the host LP
+ * service synchronises as it does in fjsp_env_step, and the call stops at the first launch in which no env parked.
+ * Between segments the play's progress is d_steps_out, the rollout's is scratch owned by the handle.  A failed service
+ * marks the handle failed, as in fjsp_env_step.
+ * FJSP_E_UNSUPPORTED, fjsp_last_error() saying why: a batch without order arrivals (use the one-launch entry), a
+ * FJSP_VARIANT_MO_DFJSP batch (its 12 x 10 actions do not fit the in-kernel actor), an actor of another shape than
+ * state_size <= 32 -> 128 -> 128 -> n_actions <= 32, a slice that fits no workgroup.  FJSP_E_ARG as the one-launch entries. */
+int fjsp_env_rollout_policy_orders(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_params *actor, const float *d_epsilon,
+                                   const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
+                                   float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream);
+int fjsp_env_play_policy_orders(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
+                                int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
+                                const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
+                                double *d_reward_last, uint8_t *d_done_last, void *stream);
+/* fjsp_env_policy_build for the two: out4 = {environments per workgroup, dynamic LDS bytes, chunks of 64 operation types,
+ * segments = the largest order count of the batch's instances (a generated handle: of its generator's range)}. */
+int fjsp_env_policy_orders_build(const fjsp_env *e, int32_t state_size, int32_t *out4);
+
 /* pick_action_and_log_prob (agents/MPPPO/MPPPO.py:272-284) for one vector step in ONE launch: samples
  * Categorical(d_probs[env]) (f32[n][n_actions], the actor's softmax output), applies the epsilon-random
  * override (*d_epsilon, device scalar so that captured graphs can change it), and writes the flat action

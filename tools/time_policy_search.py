@@ -14,8 +14,16 @@ on the host (play with its default step bound, the per-step loop, best_of, polic
 clock.  policy_lookahead plays one whole episode with the 20 deterministic pairs and reports the mean seconds per
 decision, split into its parts.  One JSON line per measurement, also written to --out.
 
+--orders NAME times play alone, on a generated order-arrival batch (instances.reference_order_ranges(NAME), or NAME =
+compact: small shops that fit sixteen to a workgroup) whose arrival LPs take the route FJSP_LP_IMPL names (unset, device,
+global; exit status 3 where the handle does not admit the route): greedy and sampled, bounded at --steps, through the
+segments of fjsp_env_play_policy_orders and with fused=False, --runs wall-clock times each, appended to --out.  --tree DIR
+imports the package from another checkout -- the parent commit's, whose play is the per-step loop -- so that both trees
+are timed alternately by one script; --tag names the tree in the lines.
+
     python tools/time_policy_search.py [--envs 4096] [--reps 20] [--suite NAME[:INSTANCE]] [--lookahead-envs N]
                                        [--out profiles/policy_search_timing.jsonl]
+    python tools/time_policy_search.py --orders da3c [--steps 128] [--runs 5] [--tree PARENT --tag parent] --out FILE
 """
 import argparse
 import ctypes as C
@@ -27,7 +35,22 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=4096)
+ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--loop-reps", type=int, default=3)
+ap.add_argument("--suite", default=None, help="NAME[:INSTANCE] of tests/golden instead of the generated 10x5 set")
+ap.add_argument("--lookahead-envs", type=int, default=None, help="envs of the lookahead episode (default: --envs)")
+ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                              "policy_search_timing.jsonl"))
+ap.add_argument("--orders", default=None, help="NAME: time play on a generated order-arrival batch of instances.reference_order_ranges(NAME), or of the small shops of NAME = compact")
+ap.add_argument("--steps", type=int, default=128, help="--orders: the step bound of every timed play")
+ap.add_argument("--runs", type=int, default=5, help="--orders: timed runs of every play")
+ap.add_argument("--tag", default="head", help="--orders: what the lines call this tree (parent / head)")
+ap.add_argument("--tree", default=None, help="import the package from this checkout (the parent commit's) instead of the tool's own")
+args = ap.parse_args()
+
+sys.path.insert(0, os.path.abspath(args.tree) if args.tree else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deep_reinforcement_learning_for_fjsp_amd import _capi  # noqa: E402
 from deep_reinforcement_learning_for_fjsp_amd import instances as fi  # noqa: E402
 from deep_reinforcement_learning_for_fjsp_amd import policy_search as PS  # noqa: E402
@@ -38,15 +61,6 @@ from deep_reinforcement_learning_for_fjsp_amd.lookahead import ACTION_RANGES, op
 
 DET_SO = [(a, b) for a in range(5) for b in range(4)]
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--envs", type=int, default=4096)
-ap.add_argument("--reps", type=int, default=20)
-ap.add_argument("--loop-reps", type=int, default=3)
-ap.add_argument("--suite", default=None, help="NAME[:INSTANCE] of tests/golden instead of the generated 10x5 set")
-ap.add_argument("--lookahead-envs", type=int, default=None, help="envs of the lookahead episode (default: --envs)")
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                              "policy_search_timing.jsonl"))
-args = ap.parse_args()
 N = args.envs
 lines = []
 
@@ -82,6 +96,52 @@ def wall_timed(prep, fn, reps):
         ts.append(time.perf_counter() - t0)
     return float(np.median(ts)), float(np.min(ts)), float(np.max(ts)), out
 
+
+if args.orders:
+    # An order-arrival batch, generated on the device; FJSP_LP_IMPL (unset / device / global) picks the LP route of its
+    # arrival service at create.  play bounded at --steps steps from reset, greedy and sampled: as policy_search.play runs it
+    # in the tree imported (the segments of fjsp_env_play_policy_orders; the per-step loop in a tree without them) and, where
+    # that was not the loop already, with fused=False.  One line per play with the --runs wall-clock seconds, APPENDED to
+    # --out: run it alternately with and without --tree PARENT_CHECKOUT.
+    if args.orders == "compact":      # small shops that fit sixteen to a workgroup: 3 kinds x 2..3 stages x 2..3 jobs, 3..6 machines, 1..3 orders
+        from deep_reinforcement_learning_for_fjsp_amd._capi import GenOrders, GenParams, GenRanges  # noqa: E402
+        prm = GenParams(R_min=3, R_max=3, J_min=2, J_max=3, M=0, p_min=5, p_max=30, N_min=2, N_max=3, S=0, DDT=0.0, t_si_min=100.0,
+                        t_si_max=200.0)
+        ranges = GenOrders(GenRanges(prm, 3, 6, 0.5, 1.5), 1, 3)
+    else:
+        ranges = fi.reference_order_ranges(args.orders)
+    b = EnvBatch.generated(ranges, N, 1000, rng_seed=1)
+    torch.manual_seed(0)
+    actor = ActorNet(b.state_size, 128, 2, 30).cuda()
+    calls, _loop = [0], PS._play_loop
+
+    def _counted(*a, **k):
+        calls[0] += 1
+        return _loop(*a, **k)
+
+    PS._play_loop = _counted
+    info = dict(orders=args.orders, tree=args.tag, lp_impl=os.environ.get("FJSP_LP_IMPL", ""), lp_on_device=b.lp_on_device, steps=args.steps)
+    if hasattr(b, "policy_orders_build"):
+        info["policy_orders_build"] = b.policy_orders_build(b.state_size)
+    if info["lp_impl"] in ("device", "global") and not b.lp_on_device:
+        emit(what="route_not_admitted", **info)               # (the handle keeps the host service: nothing new to time)
+        sys.exit(3)
+    for fused in ("segments", False):                          # (warm-up of both paths: library handles, the host service's LP memo)
+        b.reset(); PS.play(b, actor, max_steps=args.steps, fused=fused)
+    for what, kw in (("play_greedy", {}), ("play_sampled", dict(greedy=False, seed=3))):
+        for fused in ("segments", False):                      # ("segments": also where play's default keeps the loop)
+            mark, secs = calls[0], []
+            for _ in range(args.runs):
+                secs.append(wall_timed(b.reset, lambda: PS.play(b, actor, max_steps=args.steps, fused=fused, **kw), 1)[0])
+            was_loop = calls[0] > mark
+            emit(what=what, fused=bool(fused), path="loop" if was_loop else "segments", seconds=secs, mean_steps=float(b.read()["step_count"].double().mean()), **info)
+            if was_loop:
+                break
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "a") as f:
+        for kw in lines:
+            f.write(json.dumps(kw) + "\n")
+    sys.exit(0)
 
 variant, mo = fb.VARIANT_SO_FJSSP, None
 if args.suite:
