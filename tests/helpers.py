@@ -235,3 +235,51 @@ def kernel_vs_loop(make, actor, kernel_only, mo=None, **kw):
     assert np.all(got["read"]["done"] == 1) and np.all(got["read"]["status"] == 0)
     assert np.array_equal(got["steps"], got["read"]["step_count"])
     return got
+
+
+def rollouts(torch, mk_env, learner, T, record=False):
+    """The T-step rollout per step (_rollout_body with the native actor) and through the segments: what each left in the
+    buffer (valid rows only), the sampler, the batch -- compared bit for bit here.  mk_env() makes a fresh Batched* wrapper
+    of a batch with order arrivals; record: both record their schedule, compared as well.  Returns (what the per-step run
+    left, its action pairs u8[T, N, 2])."""
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO import MPPPO as M
+    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.Buffer import RolloutBuffer
+    out = {}
+    for mode in ("per_step", "fused"):
+        env = mk_env()
+        N = env.N
+        if record:
+            env.batch.record_schedule()
+        memory = RolloutBuffer(T, N, 20, device=0)
+        fused = M.FusedSampler(N, T, 30, 5, torch.device("cuda", 0))
+        fused.rounds = 41                              # the same sampling stream for both runs
+        old_log_prob = torch.zeros(T, N, device="cuda")
+        torch.manual_seed(77)
+        if mode == "per_step":
+            fused.native_actor = True
+            fused.new_round(0.15)
+            M._rollout_body(env, learner, memory, old_log_prob, 0.15, T, lambda a: a, None, False, fused)
+        else:
+            assert M.fused_policy_rollout(env, learner, memory, fused, old_log_prob, 0.15, T)
+        assert len(memory) == T
+        torch.cuda.synchronize()
+        valid = memory.valid[:T].clone()
+        r = env.read()
+        keep = lambda x: torch.where((valid if x.dim() == 2 else valid.unsqueeze(-1)) > 0, x, torch.zeros_like(x))   # valid rows only
+        assert all(bool(torch.isfinite(x).all()) for x in (memory.states[:T], memory.next_states[:T], old_log_prob))
+        out[mode] = dict(valid=valid, flat=keep(fused.flat_actions[:T]), logp=keep(old_log_prob),
+                         states=keep(memory.states[:T]), nxt=keep(memory.next_states[:T]),
+                         rewards=keep(memory.rewards[:T]), dones=keep(memory.dones[:T]), actions=keep(memory.actions[:T]),
+                         final_state=env.batch.state.clone(), delay=r["delay_time_sum"], makespan=r["makespan"], steps=r["step_count"],
+                         done=r["done"], status=r["status"] & ~4, completion=r["completion_time"], step_time=r["step_time"])
+        if record:
+            out[mode]["schedule"], out[mode]["schedule_length"] = [x.clone() for x in env.batch.schedule()]
+        out[mode + "_pairs"] = memory.actions[:T].to(torch.uint8)
+    a, b = out["per_step"], out["fused"]
+    for k in a:
+        if not torch.equal(a[k], b[k]):
+            bad = (a[k] != b[k]).nonzero()
+            raise AssertionError("T = %d: %s differs at %d places, first %s: %r vs %r" % (
+                T, k, bad.shape[0], bad[0].tolist(), a[k][tuple(bad[0].tolist())].item(), b[k][tuple(bad[0].tolist())].item()))
+    assert int(a["valid"].sum()) == int(a["steps"].sum()) and int(a["status"].abs().sum()) == 0
+    return a, out["per_step_pairs"]

@@ -190,48 +190,6 @@ def test_park_in_step_0_of_the_call(torch_gpu, kernel_only, forced):
     assert np.all(H.host(res["steps"]) == 1) and np.all(H.read(b)["step_count"] == p + 1)
 
 
-def _rollouts(torch, mk_env, learner, T):
-    """The T-step rollout per step (_rollout_body with the native actor) and through the segments: what each left in the
-    buffer (valid rows only), the sampler, the batch."""
-    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO import MPPPO as M
-    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.Buffer import RolloutBuffer
-    out = {}
-    for mode in ("per_step", "fused"):
-        env = mk_env()
-        N = env.N
-        memory = RolloutBuffer(T, N, 20, device=0)
-        fused = M.FusedSampler(N, T, 30, 5, torch.device("cuda", 0))
-        fused.rounds = 41                              # the same sampling stream for both runs
-        old_log_prob = torch.zeros(T, N, device="cuda")
-        torch.manual_seed(77)
-        if mode == "per_step":
-            fused.native_actor = True
-            fused.new_round(0.15)
-            M._rollout_body(env, learner, memory, old_log_prob, 0.15, T, lambda a: a, None, False, fused)
-        else:
-            assert M.fused_policy_rollout(env, learner, memory, fused, old_log_prob, 0.15, T)
-        assert len(memory) == T
-        torch.cuda.synchronize()
-        valid = memory.valid[:T].clone()
-        r = env.read()
-        keep = lambda x: torch.where((valid if x.dim() == 2 else valid.unsqueeze(-1)) > 0, x, torch.zeros_like(x))   # valid rows only
-        assert all(bool(torch.isfinite(x).all()) for x in (memory.states[:T], memory.next_states[:T], old_log_prob))
-        out[mode] = dict(valid=valid, flat=keep(fused.flat_actions[:T]), logp=keep(old_log_prob),
-                         states=keep(memory.states[:T]), nxt=keep(memory.next_states[:T]),
-                         rewards=keep(memory.rewards[:T]), dones=keep(memory.dones[:T]), actions=keep(memory.actions[:T]),
-                         final_state=env.batch.state.clone(), delay=r["delay_time_sum"], makespan=r["makespan"], steps=r["step_count"],
-                         done=r["done"], status=r["status"] & ~4)
-        out[mode + "_pairs"] = memory.actions[:T].to(torch.uint8)
-    a, b = out["per_step"], out["fused"]
-    for k in a:
-        if not torch.equal(a[k], b[k]):
-            bad = (a[k] != b[k]).nonzero()
-            raise AssertionError("T = %d: %s differs at %d places, first %s: %r vs %r" % (
-                T, k, bad.shape[0], bad[0].tolist(), a[k][tuple(bad[0].tolist())].item(), b[k][tuple(bad[0].tolist())].item()))
-    assert int(a["valid"].sum()) == int(a["steps"].sum()) and int(a["status"].abs().sum()) == 0
-    return a, out["per_step_pairs"]
-
-
 @pytest.mark.parametrize("lp", sorted(ROUTES))
 @pytest.mark.parametrize("suite", sorted(SUITES))
 def test_rollout_rows_equal_the_per_step_path(torch_gpu, suite, lp):
@@ -254,7 +212,7 @@ def test_rollout_rows_equal_the_per_step_path(torch_gpu, suite, lp):
     learner = M.PPOLearner(20, 30, 128, 2, 2, device=torch.device("cuda", 0), seed=5)
     ops = H.ops(s, len(insts), 8 * len(insts))
     T = int(ops.max())
-    full, pairs = _rollouts(torch, mk_env, learner, T)
+    full, pairs = H.rollouts(torch, mk_env, learner, T)
     assert np.array_equal(full["steps"].cpu().numpy(), ops) and bool((full["done"] == 1).all())
     assert len(set(full["flat"].long().flatten().tolist())) > 15              # the policy did sample around
     # the first arrival under those actions: replay them step by step on the host route and watch the solve counter
@@ -268,7 +226,7 @@ def test_rollout_rows_equal_the_per_step_path(torch_gpu, suite, lp):
             p = t
             break
     assert p is not None and p + 1 < T
-    short, _ = _rollouts(torch, mk_env, learner, p + 1)
+    short, _ = H.rollouts(torch, mk_env, learner, p + 1)
     assert np.array_equal(short["steps"].cpu().numpy(), np.minimum(ops, p + 1))
     assert np.array_equal(short["valid"][p].cpu().numpy() == 1, ops > p) and np.any(ops > p)
     for k in ("valid", "flat", "logp", "states", "nxt", "rewards", "dones", "actions"):

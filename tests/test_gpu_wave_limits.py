@@ -3,7 +3,8 @@ of 64 operation types) against the C oracle at their size limits.
 
 The cases are tests/wave_limit_cases.py's (tests/test_wave_limit_cases_host.py proves on the CPU that each reaches the
 condition it exists for): K = 64 | 65, 128 | 129, 255 | 256; R = 255 | 256 kinds; a kind of 254 | 255 stages; M = 8 | 9,
-31 | 32; job tables of 16 | 17, 64 | 65, 128 | 129 and 131 jobs; 64 orders; tardiness next to 2^31.  Every batch is created
+31 | 32; job tables of 16 | 17, 64 | 65, 128 | 129 and 131 jobs; 64 orders; tardiness next to 2^31; K = 65, 128 | 129 with
+three orders (the two- and four-chunk builds of the kernels with order arrivals).  Every batch is created
 with kernel_family=0 (the wave kernels also where the row kernels would fit), instances at offset 2, 6 environments.
 
 Per case: per-step launches against the oracle's replay of every environment -- chosen (operation type, machine),

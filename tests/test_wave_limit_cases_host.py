@@ -3,6 +3,7 @@ tests/wave_limit_cases.py to its end and the case reaches the condition it exist
 cannot silently lose the edge; and the create-time limits on both sides, through fjsp_env_create, which refuses before
 any device is touched."""
 import ctypes as C
+import hashlib
 
 import numpy as np
 import pytest
@@ -10,6 +11,8 @@ import pytest
 from tests import wave_limit_cases as WC
 
 E_UNSUPPORTED = -5
+# _digest of the 63 cases that were there before the chunk_orders family, computed before it was added
+LEGACY_DIGEST = "b426acf99dd8cac207988a416b56caf05e81209febbaf9d83eea3d8f7e1ba771"
 
 
 @pytest.fixture(scope="module")
@@ -21,10 +24,32 @@ def oracle(built):
 
 def test_case_list_covers_every_family_and_variant():
     ids = WC.case_ids()
-    assert len(ids) == len(set(ids)) == 63
-    assert {c[0] for c in ids} == {"chunks", "kinds", "stages", "machines", "jobs", "orders", "late"}
+    assert len(ids) == len(set(ids)) == 69
+    assert {c[0] for c in ids} == {"chunks", "kinds", "stages", "machines", "jobs", "orders", "late", "chunk_orders"}
     assert {c[2] for c in ids} == {0, 1, 2, 4, 5}
+    # families added after the first 63 cases go last: actions() seeds a case by its position
+    assert [c[0] for c in ids[63:]] == ["chunk_orders"] * 6 and "chunk_orders" not in {c[0] for c in ids[:63]}
     assert WC.N_ENVS % 4 != 0 and WC.FIRST == 2
+
+
+def _digest(cids):
+    """sha256 over the instance arrays (the arguments of set_raw) and the actions of the cases."""
+    h = hashlib.sha256()
+    for cid in cids:
+        c = WC.case(cid)
+        for a in c.arrs:
+            for key in ("Jr", "p", "elig_n", "elig_list", "count", "arrive", "delivery"):
+                x = np.ascontiguousarray(getattr(a, key))
+                h.update(("%s %s %s|" % (key, x.dtype, x.shape)).encode())
+                h.update(x.tobytes())
+        h.update(WC.actions(c).tobytes())
+    return h.hexdigest()
+
+
+def test_a_new_family_leaves_the_older_cases_where_they_were():
+    """_build seeds a case by the sorted position of its (family, shape) among the first 63 and actions() by its position in
+    case_ids(): a family added in the wrong place would silently re-draw every older case."""
+    assert _digest(WC.case_ids()[:63]) == LEGACY_DIGEST
 
 
 @pytest.mark.parametrize("cid", WC.case_ids(), ids=WC.case_name)
@@ -76,6 +101,10 @@ def test_case_shapes_sit_on_the_limits(oracle):
         elif c.family == "late":
             a = edge[0]
             assert a.R == 256 and int(a.p.max()) == 5 and int(a.delivery[0]) == -(2 ** 31 - 1 - 256 * 5)
+        elif c.family == "chunk_orders":
+            assert [(a.K, a.S) for a in c.arrs] == [(1, 1), (64, 2), (int(c.shape), 3)]
+            assert all(1 <= j <= 16 for a in c.arrs for j in a.Jr) and all((a.count == 1).all() for a in c.arrs[1:])
+            assert c.record == (c.shape == "128")
     # MO_DFJSP machines cases: windows on the highest machine, at most four per machine
     for M in WC.MACHINE_M:
         a = WC.set_arrays(WC.case(("machines", str(M), 4)))[0]

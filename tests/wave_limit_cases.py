@@ -35,6 +35,12 @@ oracle's replay of environment e that the edge instances must satisfy.
     late      R = 256 kinds of one job, order delivery at the most negative value check_instance admits, SO_DFJSP (due
               date = order delivery): every tardiness is close to 2^31, their total close to 2^39.  Condition:
               delay_time_sum > 2^38.
+    chunk_orders  the chunks family with order arrivals: largest K = 65 | 128 | 129 (two, two and four chunks), kinds of
+              1..16 stages, three orders (at 0, 25, 50) of one job per kind; fillers with K = 1 (one order: an environment
+              that never waits for an arrival) and K = 64 (two orders), so the batch runs the kernels with order arrivals
+              and a 2- or 4-chunk build also opens records whose upper chunks are empty.  SO_FJSSP, SO_DFJSP.  Condition:
+              S - 1 arrivals happen and an operation type of the last chunk is dispatched after the first of them.
+              Appended to case_ids() with a seed base of its own: the older cases keep their instances and actions.
 """
 import numpy as np
 
@@ -51,6 +57,9 @@ STATE_KW = {0: {}, 1: dict(sf=True), 2: dict(mo=True), 4: dict(dyn=True), 5: {}}
 MAX_STEPS = 520
 
 CHUNK_K = (64, 65, 128, 129, 255, 256)
+CHUNK_ORDERS_K = (65, 128, 129)
+CHUNK_ORDERS_ARRIVE = (0, 25, 50)
+CHUNK_ORDERS_SEED = 20000        # the family's own seed base (the older families: 7000 + 131 x their sorted index)
 MACHINE_M = (8, 9, 31, 32)
 JOB_TOTALS = {"16": (8, 8), "17": (9, 8), "64": (32, 32), "65": (33, 32), "128": (65, 63), "129": (65, 64), "131": (129, 1, 1)}
 ORDERS_S = 64
@@ -69,6 +78,8 @@ def case_ids():
     out += [("jobs", n, v) for n in JOB_TOTALS for v in (0, 1)]
     out += [("orders", pat, v) for pat in ("gap7", "burst") for v in (0, 4)]
     out += [("late", "256", 5)]
+    # families added later go last (actions() seeds by position) and bring their own seed base (_build)
+    out += [("chunk_orders", str(K), v) for K in CHUNK_ORDERS_K for v in (0, 5)]
     return out
 
 
@@ -162,7 +173,17 @@ def case(cid):
 def _build(cid):
     family, shape, v = cid
     tag = case_name(cid)
-    seed = 7000 + 131 * sorted(set(c[:2] for c in case_ids())).index(cid[:2]) + v
+    if family == "chunk_orders":
+        K, M = int(shape), 6
+        seed = CHUNK_ORDERS_SEED + 131 * CHUNK_ORDERS_K.index(K) + v
+        rs = np.random.RandomState(seed)
+        fill = _kinds(rs, 64)
+        big = _kinds(rs, K)
+        arrs = [make(tag + "/k1", seed + 1, [1], M, [2], full_ops=(0,)),
+                make(tag + "/k64", seed + 2, fill, M, np.ones((2, len(fill))), arrive=CHUNK_ORDERS_ARRIVE[:2]),
+                make(tag + "/edge", seed + 3, big, M, np.ones((3, len(big))), arrive=CHUNK_ORDERS_ARRIVE)]
+        return Case(cid, arrs, edge=[2], record=K == 128)
+    seed = 7000 + 131 * sorted(set(c[:2] for c in case_ids() if c[0] != "chunk_orders")).index(cid[:2]) + v
     rs = np.random.RandomState(seed)
     if family == "chunks":
         K, M = int(shape), 6
@@ -390,4 +411,10 @@ def condition(c, e, a, rec, acts_e):
         return most >= 2 and len(steps) == a.S - 1 == ORDERS_S - 1, "up to %d arrivals in one step" % most
     if c.family == "late":
         return rec["delay_time_sum"] > 2 ** 38, "delay_time_sum %d" % rec["delay_time_sum"]
+    if c.family == "chunk_orders":
+        steps = sorted(arrival_steps(c, a, acts_e, e))
+        last = (a.K - 1) // 64
+        n = int((rec["k"][steps[0] + 1:] // 64 == last).sum()) if steps else 0
+        ok = len(steps) == a.S - 1 == 2 and n > 0 and a.K == int(c.shape) and last == (1 if a.K <= 128 else 2)
+        return ok, "arrivals in steps %s, %d dispatches in chunk %d after the first" % (steps, n, last)
     raise KeyError(c.family)
