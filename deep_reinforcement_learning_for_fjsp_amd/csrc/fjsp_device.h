@@ -258,17 +258,14 @@ size_t policy_rollout_lds_bytes(const DevBatch &b, int S, int W);     // dynamic
 struct PolicyGeometry { int envs; size_t lds; };
 PolicyGeometry policy_geometry(const DevBatch &b, int S);
 int launch_actor_forward(const ActorParams &ap, const double *state, int n, float *probs, hipStream_t st);
-int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st,
-                          const SchedRec &rec = SchedRec{});
-struct PolicyPlayIO;
-int launch_play_policy(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, hipStream_t st,
-                       const SchedRec &rec = SchedRec{});
-// one segment of the same two on a multi-order SO_FJSSP batch (fjsp_kernels_policy.inc); -1 for every other batch
+// the whole rollout / play of a single-order batch (sg nullptr, seg 0), one segment of it on a multi-order SO_FJSSP batch
+// (fjsp_kernels_policy.inc); -1 for a MO_DFJSP batch
 struct PolicySegment;
-int launch_rollout_policy_orders(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const PolicySegment &sg, const double *mo,
-                                 int T, hipStream_t st, const SchedRec &rec = SchedRec{});
-int launch_play_policy_orders(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, int seg, hipStream_t st,
-                              const SchedRec &rec = SchedRec{});
+int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const PolicySegment *sg, const double *mo, int T,
+                          hipStream_t st, const SchedRec &rec = SchedRec{});
+struct PolicyPlayIO;
+int launch_play_policy(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, int seg, hipStream_t st,
+                       const SchedRec &rec = SchedRec{});
 // the recorded schedule as the public table (fjsp_env_schedule): i32[N][cap][6] = (r, j, n, m, begin, end), -1 past len[i]
 int launch_schedule_unpack(const DevBatch &b, const SchedRec &rec, int32_t *table, int32_t *len, hipStream_t st);
 // saved env states (fjsp_snapshot.hip; buffer layout there): n entries of e_stride bytes, their headers, [cap][n]

@@ -609,6 +609,7 @@ int fjsp_env_rollout(fjsp_env *e, const uint8_t *d_actions, const double *d_mo, 
 }
 
 namespace {
+const char kActorShape[] = "the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32)";
 bool actor_ok(const fjsp_actor_params *a) {
     return a && a->w1 && a->b1 && a->w2 && a->b2 && a->w3 && a->b3 && a->hidden == kActorH && a->state_size > 0 &&
            a->state_size <= 32 && a->n_actions > 0 && a->n_actions <= kActorAP;
@@ -619,105 +620,34 @@ ActorParams actor_of(const fjsp_actor_params *a) {
     p.S = a->state_size; p.H = a->hidden; p.A = a->n_actions;
     return p;
 }
-// What keeps the policy kernels from running this batch with an actor of state size S, nullptr where nothing does; *g is
-// the workgroup they run then (policy_geometry, fjsp_kernels.hip).  Both launches and fjsp_env_policy_build ask here.
-const char *policy_refusal(const fjsp_env *e, int S, PolicyGeometry *g) {
-    if (e->b.mord)
+int refuse(const char *who, const char *why, int rc) { set_error(std::string(who) + ": " + why); return rc; }
+
+// The two routes of the policy kernels through an episode.  kOneLaunch (fjsp_env_rollout_policy, fjsp_env_play_policy,
+// fjsp_env_policy_build): a single-order batch, the whole call in one launch.  kSegments (their _orders twins): a batch with
+// order arrivals, one launch per segment, the arrival service between the launches.
+enum PolicyRoute { kOneLaunch, kSegments };
+// What keeps the policy kernels from running this batch on `route`, nullptr where nothing does.  g == nullptr asks about the
+// kind of batch alone; otherwise also whether a workgroup exists for an actor of state size S, and *g is the workgroup the
+// kernels run then (policy_geometry, fjsp_kernels.hip).
+const char *policy_refusal(const fjsp_env *e, PolicyRoute route, int S = 0, PolicyGeometry *g = nullptr) {
+    if (route == kOneLaunch && e->b.mord)
         return "the batch has order arrivals (their LPs are served between launches): single-order batches only";
-    *g = policy_geometry(e->b, S);
-    if (g->envs <= 0)
-        return "one environment's LDS slice does not fit the 160 KB of a CU beside the actor's weights";
-    return nullptr;
-}
-}  // namespace
-
-int fjsp_actor_forward(const fjsp_actor_params *actor, const double *d_state, int32_t n, float *d_probs, void *stream) {
-    if (!d_state || !d_probs || n <= 0) { set_error("fjsp_actor_forward: bad arguments"); return FJSP_E_ARG; }
-    if (!actor_ok(actor)) { set_error("fjsp_actor_forward: the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32)"); return FJSP_E_UNSUPPORTED; }
-    if (launch_actor_forward(actor_of(actor), d_state, n, d_probs, (hipStream_t)stream) != 0) { set_error("actor_forward_kernel launch failed"); return FJSP_E_HIP; }
-    return FJSP_OK;
-}
-
-int fjsp_env_rollout_policy(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_params *actor, const float *d_epsilon,
-                            const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
-                            float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream) {
-    if (!e || !buf || !d_epsilon || !d_seed || !d_state_in || !d_flat_actions || !d_log_prob || !d_state_last || T <= 0 || pair_div < 0) {
-        set_error("fjsp_env_rollout_policy: bad arguments"); return FJSP_E_ARG;
-    }
-    if (const int rc = usable(e, "fjsp_env_rollout_policy", kIntact)) return rc;
-    if (buf->N != e->b.N || buf->S != e->b.state_size || buf->T < T || buf->device != e->device) {
-        set_error("fjsp_env_rollout_policy: the rollout buffer does not match the batch (N, state_size, T, device)"); return FJSP_E_ARG;
-    }
-    if (!actor_ok(actor) || actor->state_size != e->b.state_size) {
-        set_error("fjsp_env_rollout_policy: the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32)"); return FJSP_E_UNSUPPORTED;
-    }
-    PolicyGeometry geo{};
-    if (const char *why = policy_refusal(e, actor->state_size, &geo)) { set_error(std::string("fjsp_env_rollout_policy: ") + why); return FJSP_E_UNSUPPORTED; }
-    DeviceGuard guard(e->device);
-    PolicyRolloutIO io;
-    io.state_in = d_state_in; io.epsilon = d_epsilon; io.seed = d_seed; io.pair_div = pair_div;
-    io.o_state = buf->states; io.o_actions = buf->actions; io.o_reward = buf->rewards; io.o_next = buf->next_states;
-    io.o_done = buf->dones; io.o_valid = buf->valid; io.o_flat = d_flat_actions; io.o_logp = d_log_prob; io.state_last = d_state_last;
-    if (launch_rollout_policy(e->b, actor_of(actor), io, d_mo, T, (hipStream_t)stream, e->sched) != 0) {
-        set_error("rollout_policy_kernel launch failed"); return FJSP_E_HIP;
-    }
-    buf->len = T;
-    return FJSP_OK;
-}
-
-int fjsp_env_play_policy(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
-                         int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
-                         const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
-                         double *d_reward_last, uint8_t *d_done_last, void *stream) {
-    if (!e || T <= 0 || n_greedy < 0 || pair_div < 0 || !d_state_in || n_state_in <= 0 || !d_steps_out || !d_state_last ||
-        !d_reward_last || !d_done_last) {
-        set_error("fjsp_env_play_policy: bad arguments"); return FJSP_E_ARG;
-    }
-    if (const int rc = usable(e, "fjsp_env_play_policy", kIntact)) return rc;
-    if (!actor_ok(actor) || actor->state_size != e->b.state_size) {
-        set_error("fjsp_env_play_policy: the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32)"); return FJSP_E_UNSUPPORTED;
-    }
-    if (pair_div > 0 && actor->n_actions % pair_div != 0) {
-        set_error("fjsp_env_play_policy: pair_div does not divide n_actions"); return FJSP_E_ARG;
-    }
-    if (n_greedy < e->b.N && !d_seed) { set_error("fjsp_env_play_policy: sampling envs need d_seed"); return FJSP_E_ARG; }
-    if (!d_state_src && n_state_in < e->b.N) { set_error("fjsp_env_play_policy: d_state_in has fewer rows than the batch"); return FJSP_E_ARG; }
-    PolicyGeometry geo{};
-    if (const char *why = policy_refusal(e, actor->state_size, &geo)) { set_error(std::string("fjsp_env_play_policy: ") + why); return FJSP_E_UNSUPPORTED; }
-    DeviceGuard guard(e->device);
-    PolicyPlayIO io;
-    io.state_in = d_state_in; io.state_src = d_state_src; io.n_state_in = n_state_in; io.seed = d_seed; io.first = d_first;
-    io.pair_div = pair_div; io.n_greedy = n_greedy; io.actions_out = d_actions_out; io.steps_out = d_steps_out;
-    io.state_last = d_state_last; io.reward_last = d_reward_last; io.done_last = d_done_last;
-    if (launch_play_policy(e->b, actor_of(actor), io, d_mo, T, (hipStream_t)stream, e->sched) != 0) {
-        set_error("play_policy_kernel launch failed"); return FJSP_E_HIP;
-    }
-    return FJSP_OK;
-}
-
-int fjsp_env_policy_build(const fjsp_env *e, int32_t state_size, int32_t *out3) {
-    if (!e || !out3) { set_error("fjsp_env_policy_build: null argument"); return FJSP_E_ARG; }
-    if (state_size < 1 || state_size > 32) { set_error("fjsp_env_policy_build: state_size outside 1..32"); return FJSP_E_ARG; }
-    PolicyGeometry geo{};
-    if (const char *why = policy_refusal(e, state_size, &geo)) { set_error(std::string("fjsp_env_policy_build: ") + why); return FJSP_E_UNSUPPORTED; }
-    out3[0] = geo.envs; out3[1] = (int32_t)geo.lds; out3[2] = e->b.KC;
-    return FJSP_OK;
-}
-
-// ---- the same on batches with order arrivals: one policy launch per segment, the arrival service between them
-namespace {
-const char kOrdersActor[] = "the in-kernel actor is state_size (<= 32) -> 128 -> 128 -> n_actions (<= 32)";
-// What keeps the segmented policy kernels from running this batch (the batch alone: asked before the actor's shape)
-const char *policy_orders_batch_refusal(const fjsp_env *e) {
-    if (e->b.variant == FJSP_VARIANT_MO_DFJSP)
+    if (route == kSegments && e->b.variant == FJSP_VARIANT_MO_DFJSP)
         return "MO_DFJSP batches are not played inside the launch (their 12 x 10 actions do not fit the in-kernel actor)";
-    if (!e->b.mord)
+    if (route == kSegments && !e->b.mord)
         return "the batch has no order arrivals: fjsp_env_play_policy / fjsp_env_rollout_policy run it in one launch";
-    return nullptr;
-}
-const char *policy_orders_geometry_refusal(const fjsp_env *e, int S, PolicyGeometry *g) {
+    if (!g) return nullptr;
     *g = policy_geometry(e->b, S);
     return g->envs > 0 ? nullptr : "one environment's LDS slice does not fit the 160 KB of a CU beside the actor's weights";
+}
+// The first checks the launching entries share once their own arguments are in order.  Their order decides the text when
+// two things are wrong at once: the segmented entries ask about the kind of batch before the actor's shape, the one-launch
+// entries after everything else (policy_refusal with the workgroup, which every entry asks last).
+int actor_refusal(const fjsp_env *e, const char *who, PolicyRoute route, const fjsp_actor_params *actor) {
+    if (route == kSegments)
+        if (const char *why = policy_refusal(e, route)) return refuse(who, why, FJSP_E_UNSUPPORTED);
+    if (!actor_ok(actor) || actor->state_size != e->b.state_size) return refuse(who, kActorShape, FJSP_E_UNSUPPORTED);
+    return FJSP_OK;
 }
 // Between two segments: the LPs of the envs the last launch parked, then arrival_kernel into the rows given.  *more = false
 // where the service knows that nothing parked (the host route fetches the count anyway): every env has finished or reached T.
@@ -736,41 +666,39 @@ int segment_scratch(fjsp_env *e) {
     e->d_seg_reward = p;
     return FJSP_OK;
 }
-}  // namespace
 
-int fjsp_env_rollout_policy_orders(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_params *actor, const float *d_epsilon,
-                                   const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
-                                   float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream) {
-    const char *who = "fjsp_env_rollout_policy_orders";
-    if (!e || !buf || !d_epsilon || !d_seed || !d_state_in || !d_flat_actions || !d_log_prob || !d_state_last || T <= 0 || pair_div < 0) {
-        set_error(std::string(who) + ": bad arguments"); return FJSP_E_ARG;
-    }
-    if (const int rc = usable(e, who, kIntact | kIdle)) return rc;
-    if (buf->N != e->b.N || buf->S != e->b.state_size || buf->T < T || buf->device != e->device) {
-        set_error(std::string(who) + ": the rollout buffer does not match the batch (N, state_size, T, device)"); return FJSP_E_ARG;
-    }
-    if (const char *why = policy_orders_batch_refusal(e)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
-    if (!actor_ok(actor) || actor->state_size != e->b.state_size) { set_error(std::string(who) + ": " + kOrdersActor); return FJSP_E_UNSUPPORTED; }
+int rollout_policy(const char *who, PolicyRoute route, fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_params *actor, const float *d_epsilon,
+                   const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
+                   float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream) {
+    if (!e || !buf || !d_epsilon || !d_seed || !d_state_in || !d_flat_actions || !d_log_prob || !d_state_last || T <= 0 || pair_div < 0)
+        return refuse(who, "bad arguments", FJSP_E_ARG);
+    if (const int rc = usable(e, who, route == kSegments ? kIntact | kIdle : kIntact)) return rc;
+    if (buf->N != e->b.N || buf->S != e->b.state_size || buf->T < T || buf->device != e->device)
+        return refuse(who, "the rollout buffer does not match the batch (N, state_size, T, device)", FJSP_E_ARG);
+    if (const int rc = actor_refusal(e, who, route, actor)) return rc;
     PolicyGeometry geo{};
-    if (const char *why = policy_orders_geometry_refusal(e, actor->state_size, &geo)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+    if (const char *why = policy_refusal(e, route, actor->state_size, &geo)) return refuse(who, why, FJSP_E_UNSUPPORTED);
     DeviceGuard guard(e->device);
-    if (const int rc = segment_scratch(e)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const size_t N = (size_t)e->b.N;
     PolicyRolloutIO io;
     io.state_in = d_state_in; io.epsilon = d_epsilon; io.seed = d_seed; io.pair_div = pair_div;
     io.o_state = buf->states; io.o_actions = buf->actions; io.o_reward = buf->rewards; io.o_next = buf->next_states;
     io.o_done = buf->dones; io.o_valid = buf->valid; io.o_flat = d_flat_actions; io.o_logp = d_log_prob; io.state_last = d_state_last;
-    PolicySegment sg;
-    sg.next_t = reinterpret_cast<int32_t *>(e->d_seg_reward + N); sg.parked = reinterpret_cast<uint8_t *>(sg.next_t + N);
-    sg.reward = e->d_seg_reward; sg.done = e->d_done_scratch;
+    PolicySegment sg{};
+    if (route == kSegments) {
+        if (const int rc = segment_scratch(e)) return rc;
+        const size_t N = (size_t)e->b.N;
+        sg.next_t = reinterpret_cast<int32_t *>(e->d_seg_reward + N); sg.parked = reinterpret_cast<uint8_t *>(sg.next_t + N);
+        sg.reward = e->d_seg_reward; sg.done = e->d_done_scratch;
+    }
     const ActorParams ap = actor_of(actor);
-    for (int seg = 0; seg < e->b.SP; ++seg) {
+    const int segments = route == kSegments ? e->b.SP : 1;      // (the one-launch route: one segment, no service)
+    for (int seg = 0; seg < segments; ++seg) {
         sg.seg = seg;
-        if (launch_rollout_policy_orders(e->b, ap, io, sg, d_mo, T, st, e->sched) != 0) {
-            set_error("rollout_policy_orders_kernel launch failed"); return FJSP_E_HIP;
+        if (launch_rollout_policy(e->b, ap, io, route == kSegments ? &sg : nullptr, d_mo, T, st, e->sched) != 0) {
+            set_error(route == kSegments ? "rollout_policy_orders_kernel launch failed" : "rollout_policy_kernel launch failed"); return FJSP_E_HIP;
         }
-        if (seg + 1 == e->b.SP) break;           // (an env of S orders parks S - 1 times at most: nothing parked in the last launch)
+        if (seg + 1 == segments) break;          // (an env of S orders parks S - 1 times at most: nothing parked in the last launch)
         bool more = false;
         if (const int rc = serve_segment(e, d_mo, d_state_last, e->d_seg_reward, e->d_done_scratch, st, &more)) return rc;
         if (!more) break;
@@ -779,23 +707,20 @@ int fjsp_env_rollout_policy_orders(fjsp_env *e, fjsp_rollout *buf, const fjsp_ac
     return FJSP_OK;
 }
 
-int fjsp_env_play_policy_orders(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
-                                int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
-                                const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
-                                double *d_reward_last, uint8_t *d_done_last, void *stream) {
-    const char *who = "fjsp_env_play_policy_orders";
+int play_policy(const char *who, PolicyRoute route, fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy,
+                const uint64_t *d_seed, int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
+                const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last, double *d_reward_last,
+                uint8_t *d_done_last, void *stream) {
     if (!e || T <= 0 || n_greedy < 0 || pair_div < 0 || !d_state_in || n_state_in <= 0 || !d_steps_out || !d_state_last ||
-        !d_reward_last || !d_done_last) {
-        set_error(std::string(who) + ": bad arguments"); return FJSP_E_ARG;
-    }
-    if (const int rc = usable(e, who, kIntact | kIdle)) return rc;
-    if (const char *why = policy_orders_batch_refusal(e)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
-    if (!actor_ok(actor) || actor->state_size != e->b.state_size) { set_error(std::string(who) + ": " + kOrdersActor); return FJSP_E_UNSUPPORTED; }
-    if (pair_div > 0 && actor->n_actions % pair_div != 0) { set_error(std::string(who) + ": pair_div does not divide n_actions"); return FJSP_E_ARG; }
-    if (n_greedy < e->b.N && !d_seed) { set_error(std::string(who) + ": sampling envs need d_seed"); return FJSP_E_ARG; }
-    if (!d_state_src && n_state_in < e->b.N) { set_error(std::string(who) + ": d_state_in has fewer rows than the batch"); return FJSP_E_ARG; }
+        !d_reward_last || !d_done_last)
+        return refuse(who, "bad arguments", FJSP_E_ARG);
+    if (const int rc = usable(e, who, route == kSegments ? kIntact | kIdle : kIntact)) return rc;
+    if (const int rc = actor_refusal(e, who, route, actor)) return rc;
+    if (pair_div > 0 && actor->n_actions % pair_div != 0) return refuse(who, "pair_div does not divide n_actions", FJSP_E_ARG);
+    if (n_greedy < e->b.N && !d_seed) return refuse(who, "sampling envs need d_seed", FJSP_E_ARG);
+    if (!d_state_src && n_state_in < e->b.N) return refuse(who, "d_state_in has fewer rows than the batch", FJSP_E_ARG);
     PolicyGeometry geo{};
-    if (const char *why = policy_orders_geometry_refusal(e, actor->state_size, &geo)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+    if (const char *why = policy_refusal(e, route, actor->state_size, &geo)) return refuse(who, why, FJSP_E_UNSUPPORTED);
     DeviceGuard guard(e->device);
     hipStream_t st = (hipStream_t)stream;
     PolicyPlayIO io;
@@ -803,11 +728,12 @@ int fjsp_env_play_policy_orders(fjsp_env *e, const fjsp_actor_params *actor, int
     io.pair_div = pair_div; io.n_greedy = n_greedy; io.actions_out = d_actions_out; io.steps_out = d_steps_out;
     io.state_last = d_state_last; io.reward_last = d_reward_last; io.done_last = d_done_last;
     const ActorParams ap = actor_of(actor);
-    for (int seg = 0; seg < e->b.SP; ++seg) {
-        if (launch_play_policy_orders(e->b, ap, io, d_mo, T, seg, st, e->sched) != 0) {
-            set_error("play_policy_orders_kernel launch failed"); return FJSP_E_HIP;
+    const int segments = route == kSegments ? e->b.SP : 1;      // (the one-launch route: one segment, no service)
+    for (int seg = 0; seg < segments; ++seg) {
+        if (launch_play_policy(e->b, ap, io, d_mo, T, seg, st, e->sched) != 0) {
+            set_error(route == kSegments ? "play_policy_orders_kernel launch failed" : "play_policy_kernel launch failed"); return FJSP_E_HIP;
         }
-        if (seg + 1 == e->b.SP) break;           // (an env of S orders parks S - 1 times at most: nothing parked in the last launch)
+        if (seg + 1 == segments) break;          // (an env of S orders parks S - 1 times at most: nothing parked in the last launch)
         bool more = false;
         if (const int rc = serve_segment(e, d_mo, d_state_last, d_reward_last, d_done_last, st, &more)) return rc;
         if (!more) break;
@@ -815,15 +741,58 @@ int fjsp_env_play_policy_orders(fjsp_env *e, const fjsp_actor_params *actor, int
     return FJSP_OK;
 }
 
-int fjsp_env_policy_orders_build(const fjsp_env *e, int32_t state_size, int32_t *out4) {
-    const char *who = "fjsp_env_policy_orders_build";
-    if (!e || !out4) { set_error(std::string(who) + ": null argument"); return FJSP_E_ARG; }
-    if (state_size < 1 || state_size > 32) { set_error(std::string(who) + ": state_size outside 1..32"); return FJSP_E_ARG; }
-    if (const char *why = policy_orders_batch_refusal(e)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
+// out: envs per workgroup, its LDS bytes, KC; the segmented route adds the policy launches of one call at most
+int policy_build(const char *who, PolicyRoute route, const fjsp_env *e, int32_t state_size, int32_t *out) {
+    if (!e || !out) return refuse(who, "null argument", FJSP_E_ARG);
+    if (state_size < 1 || state_size > 32) return refuse(who, "state_size outside 1..32", FJSP_E_ARG);
     PolicyGeometry geo{};
-    if (const char *why = policy_orders_geometry_refusal(e, state_size, &geo)) { set_error(std::string(who) + ": " + why); return FJSP_E_UNSUPPORTED; }
-    out4[0] = geo.envs; out4[1] = (int32_t)geo.lds; out4[2] = e->b.KC; out4[3] = e->b.SP;
+    if (const char *why = policy_refusal(e, route, state_size, &geo)) return refuse(who, why, FJSP_E_UNSUPPORTED);
+    out[0] = geo.envs; out[1] = (int32_t)geo.lds; out[2] = e->b.KC;
+    if (route == kSegments) out[3] = e->b.SP;
     return FJSP_OK;
+}
+}  // namespace
+
+int fjsp_actor_forward(const fjsp_actor_params *actor, const double *d_state, int32_t n, float *d_probs, void *stream) {
+    if (!d_state || !d_probs || n <= 0) { set_error("fjsp_actor_forward: bad arguments"); return FJSP_E_ARG; }
+    if (!actor_ok(actor)) return refuse("fjsp_actor_forward", kActorShape, FJSP_E_UNSUPPORTED);
+    if (launch_actor_forward(actor_of(actor), d_state, n, d_probs, (hipStream_t)stream) != 0) { set_error("actor_forward_kernel launch failed"); return FJSP_E_HIP; }
+    return FJSP_OK;
+}
+
+int fjsp_env_rollout_policy(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_params *actor, const float *d_epsilon,
+                            const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
+                            float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream) {
+    return rollout_policy("fjsp_env_rollout_policy", kOneLaunch, e, buf, actor, d_epsilon, d_seed, pair_div, T, d_mo, d_state_in, d_flat_actions,
+                          d_log_prob, d_state_last, stream);
+}
+int fjsp_env_play_policy(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
+                         int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
+                         const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
+                         double *d_reward_last, uint8_t *d_done_last, void *stream) {
+    return play_policy("fjsp_env_play_policy", kOneLaunch, e, actor, pair_div, n_greedy, d_seed, T, d_mo, d_state_in, n_state_in, d_state_src,
+                       d_first, d_actions_out, d_steps_out, d_state_last, d_reward_last, d_done_last, stream);
+}
+int fjsp_env_policy_build(const fjsp_env *e, int32_t state_size, int32_t *out3) {
+    return policy_build("fjsp_env_policy_build", kOneLaunch, e, state_size, out3);
+}
+
+// ---- the same on batches with order arrivals: one policy launch per segment, the arrival service between them
+int fjsp_env_rollout_policy_orders(fjsp_env *e, fjsp_rollout *buf, const fjsp_actor_params *actor, const float *d_epsilon,
+                                   const uint64_t *d_seed, int32_t pair_div, int32_t T, const double *d_mo, const double *d_state_in,
+                                   float *d_flat_actions, float *d_log_prob, double *d_state_last, void *stream) {
+    return rollout_policy("fjsp_env_rollout_policy_orders", kSegments, e, buf, actor, d_epsilon, d_seed, pair_div, T, d_mo, d_state_in,
+                          d_flat_actions, d_log_prob, d_state_last, stream);
+}
+int fjsp_env_play_policy_orders(fjsp_env *e, const fjsp_actor_params *actor, int32_t pair_div, int32_t n_greedy, const uint64_t *d_seed,
+                                int32_t T, const double *d_mo, const double *d_state_in, int32_t n_state_in, const int32_t *d_state_src,
+                                const uint8_t *d_first, uint8_t *d_actions_out, int32_t *d_steps_out, double *d_state_last,
+                                double *d_reward_last, uint8_t *d_done_last, void *stream) {
+    return play_policy("fjsp_env_play_policy_orders", kSegments, e, actor, pair_div, n_greedy, d_seed, T, d_mo, d_state_in, n_state_in,
+                       d_state_src, d_first, d_actions_out, d_steps_out, d_state_last, d_reward_last, d_done_last, stream);
+}
+int fjsp_env_policy_orders_build(const fjsp_env *e, int32_t state_size, int32_t *out4) {
+    return policy_build("fjsp_env_policy_orders_build", kSegments, e, state_size, out4);
 }
 
 int fjsp_env_read(fjsp_env *e, int64_t *d_delay_time_sum, int32_t *d_makespan, int32_t *d_completion,

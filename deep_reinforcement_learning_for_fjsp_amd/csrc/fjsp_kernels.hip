@@ -1666,22 +1666,43 @@ __device__ __forceinline__ void park_env(W<KC, V> &w, const DevBatch &b, int env
 #include "fjsp_kernels_dispatch.inc"
 #undef FJSP_REC
 // the kernels with the actor inside: sixteen environments per workgroup (FJSP_PW 0), then the build whose workgroup size
-// follows from LDS (FJSP_PW 1), each plain and recording
+// follows from LDS (FJSP_PW 1); each for the whole episode (FJSP_ORD 0) and for one segment of it between order arrivals
+// (FJSP_ORD 1); each of those plain and recording
 #define FJSP_PW 0
+#define FJSP_ORD 0
 #define FJSP_REC 0
 #include "fjsp_kernels_policy.inc"
 #undef FJSP_REC
 #define FJSP_REC 1
 #include "fjsp_kernels_policy.inc"
 #undef FJSP_REC
+#undef FJSP_ORD
+#define FJSP_ORD 1
+#define FJSP_REC 0
+#include "fjsp_kernels_policy.inc"
+#undef FJSP_REC
+#define FJSP_REC 1
+#include "fjsp_kernels_policy.inc"
+#undef FJSP_REC
+#undef FJSP_ORD
 #undef FJSP_PW
 #define FJSP_PW 1
+#define FJSP_ORD 0
 #define FJSP_REC 0
 #include "fjsp_kernels_policy.inc"
 #undef FJSP_REC
 #define FJSP_REC 1
 #include "fjsp_kernels_policy.inc"
 #undef FJSP_REC
+#undef FJSP_ORD
+#define FJSP_ORD 1
+#define FJSP_REC 0
+#include "fjsp_kernels_policy.inc"
+#undef FJSP_REC
+#define FJSP_REC 1
+#include "fjsp_kernels_policy.inc"
+#undef FJSP_REC
+#undef FJSP_ORD
 #undef FJSP_PW
 
 // Multi-order: finish the step of every env parked at an order arrival.  The host service has solved the
@@ -1859,83 +1880,54 @@ int launch_actor_forward(const ActorParams &ap, const double *state, int n, floa
     const size_t lds = actor_lds_floats(ap.S) * 4 + 16 * (32 + kActorH + kActorAP) * 4;
     return launch(&actor_forward_kernel, grid_for16(n), dim3(1024), lds, st, ap, state, n, probs);
 }
-// the policy kernels: the single-order variants only (order arrivals need the LP service between steps); -1 where
-// policy_geometry() finds no workgroup -- the entry points have refused those batches already
-template <class F16, class FW>
-static int dispatch_policy(const DevBatch &b, const ActorParams &ap, F16 &&f16, FW &&fw) {
-    if (b.mord) return -1;
+// the policy kernels, f(kc, v, wide, grid, block, lds) with wide = the FJSP_PW 1 build; -1 where there is no instantiation:
+// a MO_DFJSP batch (not played inside the launch), or policy_geometry() finds no workgroup -- the entry points have refused
+// those batches already.  A multi-order batch comes with v = kMord: the launchers run a segment of it (the _orders kernels,
+// fjsp_kernels_policy.inc) and the entry serves the arrivals between the launches.
+template <class F>
+static int dispatch_policy(const DevBatch &b, const ActorParams &ap, F &&f) {
     const PolicyGeometry g = policy_geometry(b, ap.S);
     if (g.envs <= 0) return -1;
     return dispatch(b, [&](auto kc, auto v) {
         constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-        if constexpr (!is_mord_v<V>) {
-            if (g.envs < 16) return fw(kc, v, grid_for_envs(b.N, g.envs), dim3(64u * (unsigned)g.envs), g.lds);
+        if constexpr (V != kDyn) {
+            if (g.envs < 16) return f(kc, v, std::true_type{}, grid_for_envs(b.N, g.envs), dim3(64u * (unsigned)g.envs), g.lds);
             // (sixteen slices of two chunks or more never fit beside the actor: that build exists for one chunk only)
-            if constexpr (KC == 1) return f16(kc, v, grid_for16(b.N), dim3(1024), g.lds);
+            if constexpr (KC == 1) return f(kc, v, std::false_type{}, grid_for16(b.N), dim3(1024), g.lds);
         }
         return -1;
     });
 }
-int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const double *mo, int T, hipStream_t st,
-                          const SchedRec &rec) {
-    return dispatch_policy(b, ap,
-        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            return launch_rec(&rollout_policy_kernel<KC, V>, &rollout_policy_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
-        },
-        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            return launch_rec(&rollout_policy_w_kernel<KC, V>, &rollout_policy_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
-        });
-}
-int launch_play_policy(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, hipStream_t st,
-                       const SchedRec &rec) {
-    return dispatch_policy(b, ap,
-        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            return launch_rec(&play_policy_kernel<KC, V>, &play_policy_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
-        },
-        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            return launch_rec(&play_policy_w_kernel<KC, V>, &play_policy_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
-        });
-}
-// ... and their segment builds for multi-order SO_FJSSP batches (kMord), in the same two geometries; -1 for every other batch
-template <class F16, class FW>
-static int dispatch_policy_orders(const DevBatch &b, const ActorParams &ap, F16 &&f16, FW &&fw) {
-    if (!b.mord || b.variant == FJSP_VARIANT_MO_DFJSP) return -1;
-    const PolicyGeometry g = policy_geometry(b, ap.S);
-    if (g.envs <= 0) return -1;
-    return dispatch_kc<kMord>(b.KC, [&](auto kc, auto v) {
-        constexpr int KC = decltype(kc)::value;
-        if (g.envs < 16) return fw(kc, v, grid_for_envs(b.N, g.envs), dim3(64u * (unsigned)g.envs), g.lds);
-        if constexpr (KC == 1) return f16(kc, v, grid_for16(b.N), dim3(1024), g.lds);
-        return -1;
+// sg: the segment of a multi-order batch's rollout (nullptr on every other batch, whose one launch is the whole rollout)
+int launch_rollout_policy(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const PolicySegment *sg, const double *mo, int T,
+                          hipStream_t st, const SchedRec &rec) {
+    return dispatch_policy(b, ap, [&](auto kc, auto v, auto wide, dim3 grid, dim3 block, size_t lds) {
+        constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+        constexpr bool PW = decltype(wide)::value;
+        if constexpr (V == kMord) {
+            if (!sg) return -1;
+            if constexpr (PW) return launch_rec(&rollout_policy_orders_w_kernel<KC, V>, &rollout_policy_orders_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, *sg, mo, T);
+            else return launch_rec(&rollout_policy_orders_kernel<KC, V>, &rollout_policy_orders_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, *sg, mo, T);
+        } else {
+            if constexpr (PW) return launch_rec(&rollout_policy_w_kernel<KC, V>, &rollout_policy_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+            else return launch_rec(&rollout_policy_kernel<KC, V>, &rollout_policy_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+        }
     });
 }
-int launch_rollout_policy_orders(const DevBatch &b, const ActorParams &ap, const PolicyRolloutIO &io, const PolicySegment &sg, const double *mo,
-                                 int T, hipStream_t st, const SchedRec &rec) {
-    return dispatch_policy_orders(b, ap,
-        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            return launch_rec(&rollout_policy_orders_kernel<KC, V>, &rollout_policy_orders_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, sg, mo, T);
-        },
-        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            return launch_rec(&rollout_policy_orders_w_kernel<KC, V>, &rollout_policy_orders_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, sg, mo, T);
-        });
-}
-int launch_play_policy_orders(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, int seg, hipStream_t st,
-                              const SchedRec &rec) {
-    return dispatch_policy_orders(b, ap,
-        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            return launch_rec(&play_policy_orders_kernel<KC, V>, &play_policy_orders_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T, seg);
-        },
-        [&](auto kc, auto v, dim3 grid, dim3 block, size_t lds) {
-            constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
-            return launch_rec(&play_policy_orders_w_kernel<KC, V>, &play_policy_orders_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T, seg);
-        });
+// seg: the index of the segment of a multi-order batch's play (0 on every other batch)
+int launch_play_policy(const DevBatch &b, const ActorParams &ap, const PolicyPlayIO &io, const double *mo, int T, int seg, hipStream_t st,
+                       const SchedRec &rec) {
+    return dispatch_policy(b, ap, [&](auto kc, auto v, auto wide, dim3 grid, dim3 block, size_t lds) {
+        constexpr int KC = decltype(kc)::value, V = decltype(v)::value;
+        constexpr bool PW = decltype(wide)::value;
+        if constexpr (V == kMord) {
+            if constexpr (PW) return launch_rec(&play_policy_orders_w_kernel<KC, V>, &play_policy_orders_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T, seg);
+            else return launch_rec(&play_policy_orders_kernel<KC, V>, &play_policy_orders_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T, seg);
+        } else {
+            if constexpr (PW) return launch_rec(&play_policy_w_kernel<KC, V>, &play_policy_w_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+            else return launch_rec(&play_policy_kernel<KC, V>, &play_policy_rec_kernel<KC, V>, rec, grid, block, lds, st, b, ap, io, mo, T);
+        }
+    });
 }
 
 // (only the two multi-order variants have an arrival_kernel: its own two-way choice, not dispatch())
