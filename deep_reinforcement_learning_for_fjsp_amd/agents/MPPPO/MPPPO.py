@@ -25,15 +25,18 @@ Kept as the reference has them (tests/test_ppo_update.py pins both):
                                                         policy's weight vector and moves towards the policy at
                                                         the arg-min index (see MPPPO.multi_policy_update)
 """
+import ctypes as C
 import random
 import torch
 import torch.nn.functional as F
 from torch import nn, optim
 from torch.distributions import Categorical
 
+from .Buffer import RolloutBuffer
 from ..Base_Agent import Base_Agent
 from ..linear import run_layers
 from ..native_actor import native_actor_forward, native_actor_params
+from ... import _capi
 from ... import distributed as fdist
 
 HYPER = {   # utilities/data_structures/Config.py "MP_PPO"
@@ -332,7 +335,6 @@ class FusedSampler(object):
     pair_div = size of the machine-rule axis for pair-action environments ([6, 5] -> 5), 0 for flat actions."""
 
     def __init__(self, N, T, n_actions, pair_div, device):
-        from ... import _capi
         self._lib, self._check, self._ptr, self._stream = _capi.lib(), _capi.check, _capi.ptr, _capi.stream
         self.N, self.A, self.div = int(N), int(n_actions), int(pair_div)
         self.eps = torch.zeros((), dtype=torch.float32, device=device)
@@ -360,8 +362,6 @@ def fused_policy_rollout(env, learner, memory, fused, old_log_prob, exploration,
     environment kernel, rows go straight into `memory`.  A batch with order arrivals takes fjsp_env_rollout_policy_orders:
     one such launch per segment of the episode, the arrival service between them.  Returns False when the batch / network
     shape is not supported (MO_DFJSP, another network size): the caller falls back to the per-step loop."""
-    from ... import _capi
-    import ctypes as C
     ap = native_actor_params(learner.actor_new)
     if ap is None or ap.state_size != env.state_size:
         return False
@@ -383,132 +383,148 @@ def fused_policy_rollout(env, learner, memory, fused, old_log_prob, exploration,
     return True
 
 
-def _rollout_body(env, learner, memory, old_log_prob, exploration, T, encode_action, pair, check_done, fused=None):
-    """T vector steps: policy inference, epsilon override, HIP env step, rollout-buffer append (MPPPO.py:245-252).
-    `exploration` is a float (eager) or a 0-dim device tensor (graph capture: no host branch on its value);
-    with a FusedSampler the sampling chain is one library launch and the exploration rate lives in the sampler."""
+def _rollout_steps(env, memory, T, choose, early_exit):
+    """T vector steps (MPPPO.py:245-252): action choice, HIP env step, rollout-buffer append.  choose(t, state) gives the
+    step's action pair u8[N, 2] in the environment's encoding, the pair the buffer row stores, and the flat action index
+    to write over the row's column 0 (None: the stored pair holds it).  early_exit: stop once every env is done, looked
+    at every 8 steps (a host read, so not under graph capture)."""
     memory.clear()
-    state64 = env.reset().clone()
+    state = env.reset().clone()
     done = torch.zeros(env.N, dtype=torch.uint8, device=env.device)
-    t = 0
-    while t < T:
+    mo = getattr(env, "mo", None)
+    for t in range(T):
         active = (done == 0).to(torch.uint8)
-        if fused is not None:
-            if getattr(fused, "native_actor", False):
-                probs = native_actor_forward(learner.actor_new, state64)      # the fused rollout's arithmetic, step by step
-            else:
-                with torch.no_grad():
-                    probs = learner.actor_new(state64.float())
-            act_pair = fused.sample(probs, t, old_log_prob[t])
-            nxt, rew, dn = env.batch.step(act_pair, mo=getattr(env, "mo", None))
-            memory.add_experience(state64, act_pair, rew, nxt, dn, active)
-            state64, done = nxt.clone(), dn.clone()
-            t += 1
-            if check_done and t % 8 == 0 and bool((done != 0).all()):
-                break
-            continue
-        a, lp = learner.act(state64.float(), exploration)
-        old_log_prob[t] = lp
-        nxt, rew, dn = env.step(encode_action(a))
-        memory.add_experience(state64, pair, rew, nxt, dn, active)
-        memory.actions[t, :, 0] = a.float()          # the flat action index is what the policy is trained on
-        state64 = nxt.clone()
-        done = dn.clone()
-        t += 1
-        if check_done and t % 8 == 0 and bool((done != 0).all()):
+        pair, stored, flat = choose(t, state)
+        nxt, rew, dn = env.batch.step(pair, mo=mo)
+        memory.add_experience(state, stored, rew, nxt, dn, active)
+        if flat is not None:
+            memory.actions[t, :, 0] = flat.float()
+        state, done = nxt.clone(), dn.clone()
+        if early_exit and t % 8 == 7 and bool((done != 0).all()):
             break
 
 
-class GraphedRollout(object):
-    """The whole T-step rollout of one (environment batch, learner) pair captured ONCE into a HIP graph and
-    replayed every round: a vector step is a chain of ~20 small launches (MLP, sampling, env kernel, buffer
-    append), and replaying the chain from a graph removes the per-launch host cost that dominates the eager
-    loop (rocprofv3: 31 ms of a 82 ms PPO round at 4096 envs).  The exploration rate lives in a device scalar
-    so that it can change between replays; there is no early exit, every replay plays T steps (finished
-    environments idle, their rows are masked by `valid`)."""
+def _sampled_choice(learner, sampler, old_log_prob, native_actor):
+    """choose() of _rollout_steps: the actor's forward pass, then the sampler's one launch (pair, flat action and
+    log-probability of step t).  native_actor: the actor as fjsp_env_rollout_policy evaluates it, not torch's."""
+    def choose(t, state):
+        if native_actor:
+            probs = native_actor_forward(learner.actor_new, state)
+        else:
+            with torch.no_grad():
+                probs = learner.actor_new(state.float())
+        pair = sampler.sample(probs, t, old_log_prob[t])
+        return pair, pair, None
+    return choose
 
-    def __init__(self, env, learner, memory, T, encode_action, fused=None):
-        self.env, self.learner, self.memory, self.T, self.fused = env, learner, memory, T, fused
-        dev = env.device
-        self.eps = torch.zeros((), device=dev)
-        self.old_log_prob = torch.zeros(T, env.N, device=dev)
-        self.pair = torch.zeros(env.N, 2, dtype=torch.uint8, device=dev)
-        body = lambda: _rollout_body(env, learner, memory, self.old_log_prob, self.eps, T, encode_action, self.pair, False,
-                                     fused)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
+
+def per_step_rollout(env, learner, memory, sampler, old_log_prob, exploration, T, native_actor=False):
+    """What fused_policy_rollout computes, one launch at a time: actor, fjsp_policy_sample, fjsp_env_step and
+    fjsp_rollout_append per step, all T steps.  With native_actor=True the actor is fjsp_actor_forward, the in-launch
+    kernels' arithmetic, and the two agree bit for bit: the reference path of those kernels' tests.  With
+    native_actor=False it is the rollout a PPO agent with fused_sampling and no fused_rollout collects."""
+    sampler.new_round(exploration)
+    _rollout_steps(env, memory, T, _sampled_choice(learner, sampler, old_log_prob, native_actor), early_exit=False)
+
+
+class RolloutCollector(object):
+    """The rollout half of a PPO round (MPPPO.py:230-270) and what it keeps from round to round: the rollout buffer
+    `memory`, the `sampler` (with fused_sampling), the log-probabilities `old_log_prob` [T, N] and, with use_graph, the
+    captured `graph` of the T-step loop.  remake() says what is made anew when.  A round collects in one of three ways:
+    in one launch (in_launch, where fused_policy_rollout takes the batch and the actor), by replaying the graph
+    (use_graph), or step by step with an early exit.  pair_div: the size of the machine-rule axis of a pair-action
+    environment ([6, 5] -> 5), 0 for flat actions."""
+
+    def __init__(self, pair_div, fused_sampling=False, use_graph=False, in_launch=False):
+        self.pair_div, self.use_graph, self.in_launch = int(pair_div), use_graph, in_launch
+        self.fused_sampling = fused_sampling or in_launch
+        self.memory = self.sampler = self.old_log_prob = None
+        self.pair = self.blank = None                    # torch's sampling: see remake()
+        self.graph = self.graph_of = self.eps = None     # use_graph: the graph, what it was captured for, its exploration rate
+
+    def remake(self, env, learner, T):
+        """The buffer when T grows or N or the state size changes; the sampler with the buffer, or when N, the action
+        count, pair_div or T no longer fit; old_log_prob (and the pairs of torch's sampling) when the shape no longer
+        fits; the graph when the env, the learner, the buffer, the sampler or T is another than at its capture."""
+        N, device = env.N, env.device
+        memory, sampler = self.memory, self.sampler
+        if memory is None or memory.T < T or memory.N != N or memory.S != env.state_size:
+            self.memory, sampler = RolloutBuffer(T, N, env.state_size, device=device.index or 0), None
+        if self.fused_sampling and (sampler is None or sampler.N != N or sampler.A != learner.action_size
+                                    or sampler.div != self.pair_div or sampler.flat_actions.shape[0] < T):
+            sampler = FusedSampler(N, T, learner.action_size, self.pair_div, device)
+        self.sampler = sampler
+        if self.old_log_prob is None or self.old_log_prob.shape != (T, N):
+            self.old_log_prob = torch.zeros(T, N, device=device)
+            if not self.fused_sampling:    # the step's pair, and the zero pair the buffer rows store under the flat action
+                self.pair, self.blank = torch.zeros(2, N, 2, dtype=torch.uint8, device=device)
+        now = (env, learner, self.memory, sampler)
+        if self.graph is not None and not (self.graph_of[4] == T and all(a is b for a, b in zip(self.graph_of, now))):
+            self.graph = None
+
+    def _choice(self, learner, exploration):
+        """choose() of _rollout_steps: the sampler's, or learner.act on torch's generator with `exploration`, a float
+        or (under graph capture: no host branch on its value) a 0-dim device tensor."""
+        if self.sampler is not None:
+            return _sampled_choice(learner, self.sampler, self.old_log_prob, native_actor=False)
+        pair, blank, div, old_log_prob = self.pair, self.blank, self.pair_div, self.old_log_prob
+
+        def choose(t, state):
+            a, lp = learner.act(state.float(), exploration)
+            old_log_prob[t] = lp
+            if div:
+                pair[:, 0] = (a // div).to(torch.uint8)
+                pair[:, 1] = (a % div).to(torch.uint8)
+            else:
+                pair[:, 0] = a.to(torch.uint8)
+            return pair, blank, a          # the flat action index is what the policy is trained on
+        return choose
+
+    def _capture(self, env, learner, T):
+        """The whole T-step rollout captured ONCE into a HIP graph and replayed every round: a vector step is a chain
+        of ~20 small launches (MLP, sampling, env kernel, buffer append), and replaying the chain from a graph removes
+        the per-launch host cost that dominates the eager loop (rocprofv3: 31 ms of a 82 ms PPO round at 4096 envs).
+        The exploration rate lives in a device scalar so that it can change between replays; there is no early exit,
+        every replay plays T steps (finished environments idle, their rows are masked by `valid`)."""
+        device = env.device
+        self.eps = torch.zeros((), device=device)
+        choose = self._choice(learner, self.eps)
+        body = lambda: _rollout_steps(env, self.memory, T, choose, early_exit=False)
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(side):               # warm-up outside the capture (library handles, allocator)
             body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
+        torch.cuda.current_stream(device).wait_stream(side)
+        torch.cuda.synchronize(device)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="relaxed"):
             body()
+        self.graph_of = (env, learner, self.memory, self.sampler, T)
 
-    def run(self, exploration):
-        self.eps.fill_(float(exploration))
-        if self.fused is not None:
-            self.fused.new_round(exploration)
-        self.graph.replay()
-        return self.memory, self.old_log_prob
+    def collect(self, env, learner, exploration, T):
+        """One batched episode of `learner`'s policy on `env` into self.memory and self.old_log_prob."""
+        self.remake(env, learner, T)
+        sampler = self.sampler
+        if self.in_launch and fused_policy_rollout(env, learner, self.memory, sampler, self.old_log_prob, exploration, T):
+            return
+        if self.use_graph and self.graph is None:
+            self._capture(env, learner, T)
+        if sampler is not None:
+            sampler.new_round(exploration)
+        if self.use_graph:
+            self.eps.fill_(float(exploration))
+            self.graph.replay()
+        else:
+            _rollout_steps(env, self.memory, T, self._choice(learner, exploration), early_exit=True)
 
-
-def collect_and_learn(env, learner, memory_holder, exploration, max_steps, encode_action, use_graph=False, pair_div=None,
-                      fused_rollout=False):
-    """One batched episode on `env` with `learner`'s policy + one learning round (MPPPO.py:230-270).
-
-    env.step(action_tensor) must accept what encode_action(flat_action) returns.  Returns
-    (memory, losses): the RolloutBuffer used and (critic_loss, actor_loss)."""
-    from .Buffer import RolloutBuffer
-    hp = learner.hp
-    N, device = env.N, env.device
-    T = max_steps
-    memory = memory_holder.get("memory")
-    if memory is None or memory.T < T or memory.N != N or memory.S != env.state_size:
-        memory = RolloutBuffer(T, N, env.state_size, device=device.index or 0)
-        memory_holder["memory"] = memory
-        memory_holder.pop("graph", None)
-        memory_holder.pop("fused", None)
-    fused = None
-    if pair_div is not None and device.type == "cuda":       # one-launch sampling (library kernel)
-        fused = memory_holder.get("fused")
-        if fused is None or fused.N != N or fused.flat_actions.shape[0] < T or fused.A != learner.action_size or fused.div != pair_div:
-            fused = FusedSampler(N, T, learner.action_size, pair_div, device)
-            memory_holder["fused"] = fused
-            memory_holder.pop("graph", None)
-    done_in_kernel = False
-    if fused_rollout and fused is not None:
-        old_log_prob = memory_holder.get("old_log_prob")
-        if old_log_prob is None or old_log_prob.shape != (T, N):
-            old_log_prob = torch.zeros(T, N, device=device)
-            memory_holder["old_log_prob"] = old_log_prob
-        done_in_kernel = fused_policy_rollout(env, learner, memory, fused, old_log_prob, exploration, T)
-    if done_in_kernel:
-        pass
-    elif use_graph:
-        g = memory_holder.get("graph")
-        if g is None or g.env is not env or g.learner is not learner or g.memory is not memory or g.T != T or g.fused is not fused:
-            g = GraphedRollout(env, learner, memory, T, encode_action, fused)
-            memory_holder["graph"] = g
-        _, old_log_prob = g.run(exploration)
-    else:
-        old_log_prob = torch.zeros(T, N, device=device)
-        pair = torch.zeros(N, 2, dtype=torch.uint8, device=device)
-        if fused is not None:
-            fused.new_round(exploration)
-        _rollout_body(env, learner, memory, old_log_prob, exploration, T, encode_action, pair, True, fused)
-    n = len(memory)
-    states, actions, _, _, _ = memory.sample()
-    if fused is not None:
-        actions = fused.flat_actions[:n].unsqueeze(-1)
-    valid = memory.valid[:n]
-    if hasattr(memory, "normalised_returns"):        # device rollout buffer: scan + normalisation in one launch
+    def collect_and_learn(self, env, learner, exploration, T):
+        """collect() + one learning round (MPPPO.py:230-270).  Returns (critic_loss, actor_loss)."""
+        self.collect(env, learner, exploration, T)
+        hp, memory = learner.hp, self.memory
+        n = len(memory)
+        flat = self.sampler.flat_actions[:n] if self.sampler is not None else memory.actions[:n, :, 0]
         G = memory.normalised_returns(hp["discount_rate"], hp["normalized_rewards"], hp["standardized_rewards"])
-    else:
-        G = memory.compute_returns(hp["discount_rate"])
-        G = normalise_returns(G, valid, hp["normalized_rewards"], hp["standardized_rewards"])
-    losses = learner.learn(states, actions[..., 0].long(), old_log_prob[:n], G, valid)
-    return memory, losses
+        return learner.learn(memory.states[:n], flat.long(), self.old_log_prob[:n], G, memory.valid[:n])
 
 
 def jittered_exploration(episode_number, denominator, rng):
@@ -527,14 +543,11 @@ class PPO(Base_Agent):
                  fused_sampling=False, fused_rollout=False):
         super().__init__()
         self.environment = environment
-        self.use_graph = use_graph
-        self.fused_sampling = fused_sampling or fused_rollout
         # fused_rollout: the whole rollout loop in one launch with the actor inside the environment kernel
         # (fjsp_env_rollout_policy: every single-order batch, up to 256 operation types and as many jobs as create
         # admits; batches with order arrivals through fjsp_env_rollout_policy_orders, one launch per segment between
         # arrival services); falls back to the per-step loop for an actor of another shape than S -> 128 -> 128 -> A
-        self.fused_rollout = fused_rollout
-        self.learner_graph = use_graph
+        self.rollout = RolloutCollector(environment.actions_size[1], fused_sampling, use_graph, in_launch=fused_rollout)
         self.device = environment.device
         self.state_size = environment.state_size
         self.action_size = environment.actions_size[0] * environment.actions_size[1]
@@ -543,30 +556,20 @@ class PPO(Base_Agent):
         self.learner.graph_learn = bool(use_graph)
         self.hyper_parameters = self.learner.hp
         self.max_steps = max_steps
-        self._holder = {}
         self.global_step_number = 0
         self._rng = random.Random(seed)
-        self._pair = torch.zeros(environment.N, 2, dtype=torch.uint8, device=self.device)
 
     @property
     def memory(self):
-        return self._holder.get("memory")
-
-    def _encode(self, a):
-        n1 = self.environment.actions_size[1]
-        self._pair[:, 0] = (a // n1).to(torch.uint8)
-        self._pair[:, 1] = (a % n1).to(torch.uint8)
-        return self._pair
+        return self.rollout.memory
 
     def run_one_policy_network(self, exploration=None):
         """One batched episode + one learning round. Returns (mean delay_time_sum, mean makespan, losses)."""
         hp = self.hyper_parameters
         if exploration is None:                                                         # :240-241
             exploration = jittered_exploration(self.episode_number, hp["epsilon_decay_rate_denominator"], self._rng)
-        memory, losses = collect_and_learn(self.environment, self.learner, self._holder, exploration,
-                                           self.max_steps or 64, self._encode, use_graph=self.use_graph,
-                                           pair_div=self.environment.actions_size[1] if self.fused_sampling else None,
-                                           fused_rollout=self.fused_rollout)
+        losses = self.rollout.collect_and_learn(self.environment, self.learner, exploration, self.max_steps or 64)
+        memory = self.memory
         self.global_step_number += int(memory.valid[:len(memory)].sum().item())
         self.episode_number += 1
         r = self.environment.read()
@@ -591,7 +594,7 @@ class MPPPO(Base_Agent):
                  seed=0, hyper=None, max_steps=64, evolve_every=30, fused_sampling=True):
         super().__init__()
         self.make_train_env, self.test_env = make_train_env, test_env
-        self.fused_sampling = fused_sampling
+        self.rollout = RolloutCollector(0, fused_sampling)        # one buffer and one sampler serve every policy
         self.device = test_env.device
         self.actor_number = actor_number
         self.policy_tuple = tuple(range(actor_number))
@@ -605,7 +608,6 @@ class MPPPO(Base_Agent):
         self.max_steps, self.evolve_every = max_steps, evolve_every
         self.completion_min = float("inf")
         self.tardiness_min = float("inf")
-        self._holder = {}
         self._rng = random.Random(seed)
 
     def run_one_policy_network(self, environment, policy_number, completion=None, tardiness=None):
@@ -613,8 +615,7 @@ class MPPPO(Base_Agent):
         hp = self.hyper_parameters
         eps = jittered_exploration(self.episode_number, hp["epsilon_decay_rate_denominator"], self._rng)   # :240-241
         environment.set_objective(self.weight_vector_dict[policy_number], completion, tardiness)
-        collect_and_learn(environment, self.learners[policy_number], self._holder, eps, self.max_steps, lambda a: a,
-                          pair_div=0 if self.fused_sampling else None)
+        self.rollout.collect_and_learn(environment, self.learners[policy_number], eps, self.max_steps)
         r = environment.read()
         return r["delay_time_sum"].double(), r["completion_time"].double()
 

@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from tests import helpers as H
+
 pytestmark = pytest.mark.gpu
 
 
@@ -98,7 +100,7 @@ def test_policy_sample_kernel(torch_gpu):
 @pytest.mark.parametrize("use_graph,fused", [(False, False), (True, False), (False, True), (True, True)])
 def test_batched_ppo_rounds_run_on_the_hip_environment(torch_gpu, use_graph, fused):
     """BASELINE config 3 in miniature: 256 envs, actor/critic 2x128, three learning rounds; eager rollout and the
-    rollout replayed from a captured HIP graph (policy + env kernel + buffer append, MPPPO.GraphedRollout)."""
+    rollout replayed from a captured HIP graph (policy + env kernel + buffer append, RolloutCollector._capture)."""
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd import instances as fi
     from deep_reinforcement_learning_for_fjsp_amd.environments import BatchedSOFJSSP
@@ -383,7 +385,6 @@ def test_fused_policy_rollout_equals_the_per_step_path(torch_gpu, which):
     from deep_reinforcement_learning_for_fjsp_amd import instances as fi
     from deep_reinforcement_learning_for_fjsp_amd.environments import BatchedMOFJSSP, BatchedSOFJSSP
     from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO import MPPPO as M
-    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.Buffer import RolloutBuffer
     N, T = 150, 56                                    # (not a multiple of 16: the last workgroup is partial)
     insts = fi.InstanceSet(N).generate_range(3000, fi.bench_10x5_params()).solve_fluid()
     if which == "so_fjssp":
@@ -397,39 +398,8 @@ def test_fused_policy_rollout_equals_the_per_step_path(torch_gpu, which):
         S, A, div = 25, 18, 0
     torch.manual_seed(11)
     learner = M.PPOLearner(S, A, 128, 2, 2, device=torch.device("cuda", 0), seed=5)
-    out = {}
-    for mode in ("per_step", "fused"):
-        env = mk()
-        memory = RolloutBuffer(T, N, S, device=0)
-        fused = M.FusedSampler(N, T, A, div, torch.device("cuda", 0))
-        fused.rounds = 41                              # the same sampling stream for both runs
-        old_log_prob = torch.zeros(T, N, device="cuda")
-        torch.manual_seed(77)
-        if mode == "per_step":
-            fused.native_actor = True
-            fused.new_round(0.15)
-            M._rollout_body(env, learner, memory, old_log_prob, 0.15, T, lambda a: a, None, False, fused)
-        else:
-            assert M.fused_policy_rollout(env, learner, memory, fused, old_log_prob, 0.15, T)
-        assert len(memory) == T
-        torch.cuda.synchronize()
-        valid = memory.valid[:T].clone()
-        r = env.read()
-        keep = lambda x: torch.where((valid if x.dim() == 2 else valid.unsqueeze(-1)) > 0, x, torch.zeros_like(x))   # valid rows only
-        assert all(bool(torch.isfinite(x).all()) for x in (memory.states[:T], memory.next_states[:T], old_log_prob))
-        out[mode] = dict(valid=valid, flat=keep(fused.flat_actions[:T]), logp=keep(old_log_prob),
-                         states=keep(memory.states[:T]), nxt=keep(memory.next_states[:T]),
-                         rewards=keep(memory.rewards[:T]), dones=keep(memory.dones[:T]), actions=keep(memory.actions[:T]),
-                         final_state=env.batch.state.clone(), delay=r["delay_time_sum"], makespan=r["makespan"], steps=r["step_count"],
-                         status=r["status"] & ~4)
-    a, b = out["per_step"], out["fused"]
-    assert int(a["valid"].sum()) == int(a["steps"].sum()) and bool((a["steps"] > 0).all())
-    for k in a:
-        if not torch.equal(a[k], b[k]):
-            bad = (a[k] != b[k]).nonzero()
-            raise AssertionError("%s differs at %d places, first %s: %r vs %r" % (
-                k, bad.shape[0], bad[0].tolist(), a[k][tuple(bad[0].tolist())].item(), b[k][tuple(bad[0].tolist())].item()))
-    assert int(a["status"].abs().sum()) == 0
+    a, _ = H.rollouts(torch, mk, learner, T, S, A, div)
+    assert bool((a["steps"] > 0).all())
     assert len(set(a["flat"].long().flatten().tolist())) > A // 2              # the policy did sample around
 
 

@@ -1,6 +1,6 @@
 """GPU: the in-launch policy kernels on batches with order arrivals (fjsp_env_play_policy_orders,
 fjsp_env_rollout_policy_orders: one policy launch per segment of the episode, the arrival service between the launches)
-against the per-step paths they replace -- policy_search._play_loop and MPPPO._rollout_body with the native actor.  Every
+against the per-step paths they replace -- policy_search._play_loop and MPPPO.per_step_rollout with the native actor.  Every
 comparison is bit for bit (H.same / torch.equal): both sides run the same device arithmetic, so no tolerance applies.
 
 Shapes: the generated instances of the `multiorder` suite (gen777: S = 3, 72 operations; gen778: S = 4, 143) and of the
@@ -193,7 +193,7 @@ def test_park_in_step_0_of_the_call(torch_gpu, kernel_only, forced):
 @pytest.mark.parametrize("lp", sorted(ROUTES))
 @pytest.mark.parametrize("suite", sorted(SUITES))
 def test_rollout_rows_equal_the_per_step_path(torch_gpu, suite, lp):
-    """fjsp_env_rollout_policy_orders against _rollout_body: states, actions, rewards, next states, dones, valid, flat
+    """fjsp_env_rollout_policy_orders against per_step_rollout: states, actions, rewards, next states, dones, valid, flat
     actions, log-probabilities of every valid row and the last state.  T = the longest episode, and T = p + 1 with p the
     step of the first arrival under the sampled actions: an env parks in the last admitted step, and the next segment
     still completes its row."""
@@ -412,8 +412,8 @@ def test_ppo_round_through_the_segments(torch_gpu, monkeypatch):
 
     def boom(*a, **k):
         raise AssertionError("the rollout fell back to the per-step loop")
-    monkeypatch.setattr(M, "_rollout_body", boom)
-    monkeypatch.setattr(M, "GraphedRollout", boom)
+    monkeypatch.setattr(M, "_rollout_steps", boom)
+    monkeypatch.setattr(M.RolloutCollector, "_capture", boom)
     torch.manual_seed(0)
     agent = M.PPO(env, hidden_size=128, hidden_layer=2, seed=1, max_steps=81, fused_rollout=True)      # 81 = 3 x 3 x 3 x 3 operations at most
     before = [q.detach().clone() for q in agent.learner.actor_new.parameters()]

@@ -6,7 +6,7 @@ rollout only in the sixteen-env build.
 The batches are tests/policy_orders_wide_cases.py's (tests/test_policy_orders_wide_cases_host.py proves on the CPU that the
 oracle plays each through its arrivals into its last chunk, and that the table's builds follow from the size rules).
 Every comparison is bit for bit: the kernels against the per-step paths they replace (policy_search._play_loop,
-MPPPO._rollout_body with the native actor: the same device arithmetic one launch at a time), and the played episodes --
+MPPPO.per_step_rollout with the native actor: the same device arithmetic one launch at a time), and the played episodes --
 their returned actions replayed on the C oracle -- against the oracle's totals and dispatches, which is what fails if the
 environment step inside the policy build and inside the loop are wrong together.  A test that runs with kernel_only(True)
 fails if play falls back to the loop; policy_orders_build says which build ran."""
@@ -248,7 +248,7 @@ def _learner(torch):
 @pytest.mark.parametrize("name,lp,record", [("narrow", "host", False), ("narrow", "device", True), ("k65", "global", True),
                                             ("k129", "global", True), ("k129x2", "host", False)])
 def test_rollout_rows_equal_the_per_step_path(torch_gpu, name, lp, record):
-    """fjsp_env_rollout_policy_orders in the build of fewer than sixteen envs against _rollout_body, T = the longest
+    """fjsp_env_rollout_policy_orders in the build of fewer than sixteen envs against per_step_rollout, T = the longest
     episode: valid, flat actions, log-probabilities, states, next states, rewards, dones, actions of every valid row, the
     final state and read().  `record`: both sides record their schedule (the recording twin), compared too -- with
     test_rollout_parks_in_its_last_admitted_step (k65, host, not recording) both twins run at one, two and four chunks."""

@@ -171,46 +171,14 @@ def test_training_rollout_equals_the_per_step_path(torch_gpu, which):
     torch = torch_gpu
     from deep_reinforcement_learning_for_fjsp_amd.environments import BatchedSOFJSSP
     from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO import MPPPO as M
-    from deep_reinforcement_learning_for_fjsp_amd.agents.MPPPO.Buffer import RolloutBuffer
     insts, T = (_gen(4, 413, 13, 5), 65) if which == "k65" else (_gen(4, 490, 3, 2, jobs=70), 420)
     N, S, A, div = 21, 20, 30, 5
     mk = lambda: BatchedSOFJSSP(insts, n_envs=N, rng_seed=9)
     assert mk().batch.policy_build(S)["envs_per_workgroup"] == 8
     torch.manual_seed(11)
     learner = M.PPOLearner(S, A, 128, 2, 2, device=torch.device("cuda", 0), seed=5)
-    out = {}
-    for mode in ("per_step", "fused"):
-        env = mk()
-        memory = RolloutBuffer(T, N, S, device=0)
-        fused = M.FusedSampler(N, T, A, div, torch.device("cuda", 0))
-        fused.rounds = 41                              # the same sampling stream for both runs
-        old_log_prob = torch.zeros(T, N, device="cuda")
-        torch.manual_seed(77)
-        if mode == "per_step":
-            fused.native_actor = True
-            fused.new_round(0.15)
-            M._rollout_body(env, learner, memory, old_log_prob, 0.15, T, lambda a: a, None, False, fused)
-        else:
-            assert M.fused_policy_rollout(env, learner, memory, fused, old_log_prob, 0.15, T)
-        assert len(memory) == T
-        torch.cuda.synchronize()
-        valid = memory.valid[:T].clone()
-        r = env.read()
-        keep = lambda x: torch.where((valid if x.dim() == 2 else valid.unsqueeze(-1)) > 0, x, torch.zeros_like(x))   # valid rows only
-        assert all(bool(torch.isfinite(x).all()) for x in (memory.states[:T], memory.next_states[:T], old_log_prob))
-        out[mode] = dict(valid=valid, flat=keep(fused.flat_actions[:T]), logp=keep(old_log_prob),
-                         states=keep(memory.states[:T]), nxt=keep(memory.next_states[:T]),
-                         rewards=keep(memory.rewards[:T]), dones=keep(memory.dones[:T]), actions=keep(memory.actions[:T]),
-                         final_state=env.batch.state.clone(), status=r["status"] & ~4,
-                         **{k: v for k, v in r.items() if k != "status"})
-    a, b = out["per_step"], out["fused"]
-    assert int(a["valid"].sum()) == int(a["step_count"].sum()) and bool((a["step_count"] == T).all())
-    for k in a:
-        if not torch.equal(a[k], b[k]):
-            bad = (a[k] != b[k]).nonzero()
-            raise AssertionError("%s differs at %d places, first %s: %r vs %r" % (
-                k, bad.shape[0], bad[0].tolist(), a[k][tuple(bad[0].tolist())].item(), b[k][tuple(bad[0].tolist())].item()))
-    assert int(a["status"].abs().sum()) == 0 and bool((a["done"] == 1).all())
+    a, _ = H.rollouts(torch, mk, learner, T, S, A, div)
+    assert bool((a["steps"] == T).all()) and bool((a["done"] == 1).all())
     assert len(set(a["flat"].long().flatten().tolist())) > A // 2              # the policy did sample around
 
 
