@@ -235,6 +235,7 @@ REFUSED = [
     ("32-bit clock with every window", dyn(mc=machine(2047, len_max=170000)), UNS, "M_max x W_max x len_max", False),
     ("S_max = 17", dyn(S_max=17), UNS, "16 orders (S_max)", False),
     ("more than 32 machines", dyn(M_max=33), UNS, "32 machines", False),
+    ("J_max = 255", dyn(R_min=1, R_max=1, J_min=255, J_max=255), UNS, "more than 254 operations in a kind (J_max)", False),
 ]
 
 

@@ -137,6 +137,10 @@ REFUSED = [
     # 50 kinds x 5 operations x 200 jobs = 50 000 operations of up to 60 000: the clock can pass 2^31
     ("32-bit clock", dict(prm=params(R_min=50, R_max=50, J_max=5, N_max=200, p_max=60000)), _capi.FJSP_E_UNSUPPORTED,
      "32-bit clocks"),
+    # one step past the limits of the record's fields (their accepted twins: tests/test_generator_limit_cases_host.py)
+    ("M = 33", dict(prm=params(M=33)), _capi.FJSP_E_UNSUPPORTED, "more than 32 machines"),
+    ("p_max = 65536", dict(prm=params(p_max=65536)), _capi.FJSP_E_UNSUPPORTED, "processing time above 65535"),
+    ("J_max = 256", dict(prm=params(R_min=1, R_max=1, J_min=256, J_max=256)), _capi.FJSP_E_UNSUPPORTED, "more than 255 operations in a kind"),
 ]
 
 

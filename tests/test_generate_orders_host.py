@@ -142,6 +142,9 @@ REFUSED = [
     # 16 operation types x 4 jobs of up to 65 535: 4.2e6 x 4 jobs per kind with one order, 6.7e7 x 64 > 2^31 with 16
     ("32-bit clock: the work of all orders", dict(q=orders(S_max=16, R_min=4, R_max=4, J_min=4, J_max=4, N_max=4, p_max=65535)),
      _capi.FJSP_E_UNSUPPORTED, "operations of all orders"),
+    # a job's next-stage byte keeps 255 for an order still to come (the twin with 254: tests/test_generator_limit_cases_host.py)
+    ("J_max = 255 with S_max = 2", dict(q=orders(S_max=2, R_min=1, R_max=1, J_min=255, J_max=255)), _capi.FJSP_E_UNSUPPORTED,
+     "more than 254 operations in a kind (J_max)"),
 ]
 
 
