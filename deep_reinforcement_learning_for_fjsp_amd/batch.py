@@ -660,6 +660,20 @@ class EnvBatch(object):
         check(self._lib.fjsp_env_schedule(self._h, _ptr(table), _ptr(length), self._stream()))
         return table, length
 
+    def decode_capacity(self):
+        """Rows of a plan of schedule.decode: the operations of the batch's largest instance (fjsp_schedule_decode_capacity;
+        record_schedule()'s capacity, recording on or off)."""
+        return int(self._lib.fjsp_schedule_decode_capacity(self._h))
+
+    def decode_group(self):
+        """Candidates one workgroup of the decode kernel takes (fjsp_schedule_decode_group); 0: the batch is not decoded."""
+        return int(self._lib.fjsp_schedule_decode_group(self._h))
+
+    def decode(self, plan, moves=None, n_cand=1, want_table=False):
+        """schedule.decode on this batch's instances: explicit schedules -> objectives, status, tables, lengths."""
+        from . import schedule
+        return schedule.decode(self, plan, moves, n_cand, want_table)
+
     def set_lp_threads(self, n_threads):
         """Host threads of the order-arrival LP service (0 = all cores).  The asynchronous service builds its worker pool
         at the first step_async and reads this once, there: call it before that."""

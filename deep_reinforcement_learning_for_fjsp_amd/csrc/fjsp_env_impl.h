@@ -65,6 +65,7 @@ struct fjsp_env {
     uint64_t inst_hash = 0;            // FNV-1a of the packed instance slab as uploaded (snapshot compatibility, fjsp_snapshot_*)
     int64_t step_bytes = 0;
     uint8_t *d_done_scratch = nullptr; // scratch for the non-fused rollout fallback
+    uint2 *d_decode_kinds = nullptr;   // fjsp_schedule_decode's kind table, [n_inst][KP + 1] (first use; refilled by every call)
     double *d_seg_reward = nullptr;    // fjsp_env_rollout_policy_orders between its segments: reward f64[N] | next_t i32[N] | parked u8[N] (first use)
     const fjsp_instances *src = nullptr;   // the instances [first, first + n_inst) the batch plays (the host LPs read them)
     int first = 0;

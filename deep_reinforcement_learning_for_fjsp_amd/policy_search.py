@@ -26,6 +26,9 @@ slowly.
   (logp) or policy_lookahead (rollout).
 - pareto_front: P actors x k episodes per env, played as best_of plays them, and the non-dominated set of their
   objective vectors per env (pareto.select, fjsp_pareto_select, csrc/fjsp_pareto.hip) instead of one minimum.
+- improve: no policy at all -- hill climbing on explicit schedules (an operation sequence and a machine per operation, for
+  instance a recorded table's): every round decodes `neighbours` random moves of each env's plan in one launch
+  (schedule.decode, fjsp_schedule_decode, csrc/fjsp_decode.hip) and keeps the best if it is no worse.
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -519,3 +522,84 @@ def beam_search(batch, actor, width, objective=None, score="logp", candidates=No
             rank = bp[t, rank, cols]
     return dict(objective=None if objective is None else objective_values(batch, objective), best=best, cost=cum, actions=actions,
                 steps=steps, beams=beams, expand=expand)
+
+
+IMPROVE_OBJECTIVES = ("makespan", "tardiness")
+
+
+def _machine_tables(b):
+    """(koff int64[n_inst, R_max] first operation type of a kind, elig bool[n_inst, K_max, M_max] p > 0) on the device,
+    from the batch's instance arrays (read back from the device for a generated batch)."""
+    arrs = [b.instance_arrays(i) for i in range(b.n_inst)]
+    R, K, M = max(len(a.Jr) for a in arrs), max(np.asarray(a.p).shape[0] for a in arrs), max(np.asarray(a.p).shape[1] for a in arrs)
+    koff, elig = np.zeros((b.n_inst, R), np.int64), np.zeros((b.n_inst, K, M), bool)
+    for i, a in enumerate(arrs):
+        p = np.asarray(a.p)
+        koff[i, :len(a.Jr)] = np.concatenate(([0], np.cumsum(np.asarray(a.Jr, np.int64))))[:-1]
+        elig[i, :p.shape[0], :p.shape[1]] = p > 0
+    return torch.from_numpy(koff).to(b.device), torch.from_numpy(elig).to(b.device)
+
+
+def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, sideways=True):
+    """Hill climbing on explicit schedules (schedule.decode, fjsp_schedule_decode): from one plan per env, `rounds` rounds
+    of `neighbours` random neighbours per env, all N x neighbours of a round decoded by one launch.
+
+    plan: int32[N, cap, 3] rows (r, n, m), e.g. schedule.plan_of(batch.schedule()[0]); every plan must decode.  A round
+    draws on the device, from a torch.Generator seeded with `seed`: candidate q even -- a uniform row runs on a machine
+    drawn uniformly from its operation's eligible ones (MOVE_MACHINE); q odd -- a uniform row changes places with its
+    successor (MOVE_SWAP).  Of the candidates that decode (status 0) the env takes the one of least `objective`
+    ("makespan" or "tardiness"), the lowest q among equals, if it is better than its plan, or as good with sideways=True,
+    and applies that move to its plan (schedule.apply_moves).  Nothing synchronises with the host inside the loop.
+    Returns dict(plan=int32[N, cap, 3], objective=int64[N, 2] (makespan, tardiness) of it, history=int64[rounds + 1, N] the
+    chosen objective of the input plan and after every round, accepted=int64[N] moves taken, table=int32[N, cap, 6] and
+    length=int32[N] of the final plans); rounds=0 returns the input plan."""
+    from . import schedule as sch
+    b, _ = _unwrap(batch, None)
+    if objective not in IMPROVE_OBJECTIVES:
+        raise ValueError("objective must be one of %s" % (IMPROVE_OBJECTIVES,))
+    rounds, Q = int(rounds), int(neighbours)
+    if rounds < 0 or Q < 1:
+        raise ValueError("improve needs rounds >= 0 and neighbours >= 1")
+    col = IMPROVE_OBJECTIVES.index(objective)
+    dev, N = b.device, b.N
+    first = sch.decode(b, plan, want_table=True)
+    if bool((first["status"] != 0).any()):
+        raise ValueError("improve: a plan does not decode (status %s)" % sorted(set(first["status"].flatten().tolist()) - {0}))
+    koff, elig = _machine_tables(b)
+    inst = torch.arange(N, device=dev) % b.n_inst
+    tab = first["table"][:, 0].to(torch.int64)
+    L = first["length"][:, 0].to(torch.int64)
+    # rows (r, n, m, k): the operation type travels with its row (neither move changes a row's stage)
+    k = torch.where(tab[..., 0] >= 0, koff[inst[:, None], tab[..., 0].clamp(min=0)] + tab[..., 1], torch.full_like(tab[..., 0], -1))
+    rows = torch.cat([sch.plan_of(tab), k[..., None]], -1).to(torch.int32)
+    cur = first["objective"][:, 0, col].clone()
+    history = torch.empty(rounds + 1, N, dtype=torch.int64, device=dev)
+    history[0] = cur
+    accepted = torch.zeros(N, dtype=torch.int64, device=dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    odd = (torch.arange(Q, device=dev) % 2 == 1)[None, :]
+    worst = torch.iinfo(torch.int64).max
+    env = torch.arange(N, device=dev)
+    for t in range(rounds):
+        draw = torch.rand(2, N, Q, generator=gen, device=dev, dtype=torch.float64)
+        span = torch.where(odd, (L - 1)[:, None], L[:, None]).clamp(min=1)
+        u = torch.minimum((draw[0] * span).to(torch.int64), span - 1)
+        e = elig[inst[:, None], rows[env[:, None], u, 3].to(torch.int64).clamp(min=0)]               # [N, Q, M]
+        pick = torch.minimum((draw[1] * e.sum(-1)).to(torch.int64), e.sum(-1) - 1).clamp(min=0)
+        m_new = ((e.cumsum(-1) == (pick + 1)[..., None]) & e).to(torch.int8).argmax(-1)
+        moves = torch.stack([torch.where(odd, sch.MOVE_SWAP, sch.MOVE_MACHINE).expand(N, Q), u, m_new], -1).to(torch.int32)
+        res = sch.decode(b, rows[..., :3].contiguous(), moves, Q)
+        obj = torch.where(res["status"] == 0, res["objective"][..., col], torch.full((), worst, dtype=torch.int64, device=dev))
+        best, q = obj.min(1)
+        q = (obj == best[:, None]).to(torch.int8).argmax(1)                                             # the lowest q among equals
+        take = (best != worst) & ((best < cur) | ((best == cur) & bool(sideways)))
+        chosen = moves[env, q].clone()
+        chosen[~take, 0] = sch.MOVE_NONE
+        rows = sch.apply_moves(rows, chosen[:, None])[:, 0]
+        cur = torch.where(take, best, cur)
+        accepted += take
+        history[t + 1] = cur
+    last = sch.decode(b, rows[..., :3].contiguous(), want_table=True)
+    return dict(plan=rows[..., :3].contiguous(), objective=last["objective"][:, 0], history=history, accepted=accepted,
+                table=last["table"][:, 0], length=last["length"][:, 0])

@@ -1,4 +1,5 @@
-"""Host-side use of a recorded schedule (EnvBatch.schedule / fjsp_env_schedule).  Pure numpy.
+"""Host-side use of a recorded schedule (EnvBatch.schedule / fjsp_env_schedule), pure numpy, and the way back:
+explicit schedules decoded on the device (plan_of / decode / apply_moves, fjsp_schedule_decode).
 
 A table row is one dispatched operation, (r, j, n, m, time_begin, time_end): kind r, stage j, job number n within
 kind r (counted over all orders, class_FJSSP.py:212-216), machine m and the task's start and end as the reference's
@@ -7,6 +8,9 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     rows(table, length, i)                      one env's rows, grouped per machine in start order (machine.task_list)
     validate(inst, rows, variant, breakdowns)   feasibility check; returns the list of violations (empty: feasible)
     objectives(inst, rows, variant)             makespan / completion time and total tardiness (delay_time_sum)
+    plan_of(table)                              the (r, n, m) columns of a table: the explicit schedule it records
+    decode(batch, plan, moves, n_cand)          times and objectives of explicit schedules, on the device
+    apply_moves(plan, moves)                    the plans that decode's moves stand for, materialised
 
 `inst` is anything with the instance arrays of instances.InstanceArrays: Jr[R], p[K][M] (0 = ineligible),
 count[S][R], arrive[S], delivery[S] (and bk_n[M], bk[W][2] for MO_DFJSP breakdown windows).
@@ -190,3 +194,92 @@ def from_trace(inst, k, m, job_n, step_time_after, t0=0):
     begin = np.concatenate(([t0], np.asarray(step_time_after, np.int64)[:-1]))
     end = begin + p[k, np.asarray(m, np.int64)]
     return np.stack([r, j, np.asarray(job_n, np.int64), np.asarray(m, np.int64), begin, end], 1)
+
+
+# ---- explicit schedules on the device (fjsp_schedule_decode, csrc/fjsp_decode.hip)
+MOVE_NONE, MOVE_MACHINE, MOVE_SWAP = 0, 1, 2
+DECODE_OK, DECODE_NO_JOB, DECODE_STAGES, DECODE_MACHINE, DECODE_BAD_MOVE = range(5)
+
+
+def plan_of(table):
+    """The explicit schedule a table records: its (r, n, m) columns, rows in dispatch order, -1 rows past the end.  A
+    slice of `table` (device tensor or numpy array) of shape [..., cap, 3]; the stage column is implied by the order."""
+    return table[..., [R_, N_, M_]]
+
+
+def _plan_length(plan):
+    """Rows in front of the first row of three -1, per plan: int64[...]."""
+    import torch
+    end = (plan == -1).all(-1)
+    cap = plan.shape[-2]
+    pos = torch.arange(cap, device=plan.device).expand(end.shape)
+    return torch.where(end, pos, torch.full_like(pos, cap)).amin(-1)
+
+
+def apply_moves(plan, moves):
+    """The plans decode(batch, plan, moves) decodes, materialised with tensor indexing.  plan: int32[N, cap, 3] (one
+    parent per env) or [N, Q, cap, 3]; moves: int32[N, Q, 3] = (kind, u, m_new).  Returns int32[N, Q, cap, 3].  Kind 1
+    sets row u's machine, kind 2 exchanges rows u and u + 1 unless they are rows of one job; a move decode refuses (status
+    4: unknown kind, u outside the plan) leaves its plan as it is.  Rows may carry further columns behind the three
+    (improve keeps each row's operation type there): they move with their rows."""
+    import torch
+    moves = torch.as_tensor(moves, device=plan.device).to(torch.int64)
+    N, Q = moves.shape[0], moves.shape[1]
+    out = (plan[:, None].expand(N, Q, *plan.shape[1:]) if plan.dim() == 3 else plan).clone()
+    if out.dim() != 4 or tuple(out.shape[:2]) != (N, Q) or out.shape[3] < 3:
+        raise ValueError("plan must be [N, cap, 3] or [N, Q, cap, 3] with moves [N, Q, 3]")
+    L = _plan_length(out[..., :3])
+    kind, u, m_new = moves[..., 0], moves[..., 1], moves[..., 2]
+    i, q = torch.meshgrid(torch.arange(N, device=out.device), torch.arange(Q, device=out.device), indexing="ij")
+    ok1 = (kind == MOVE_MACHINE) & (u >= 0) & (u < L)
+    out[i[ok1], q[ok1], u[ok1], 2] = m_new[ok1].to(out.dtype)
+    ok2 = (kind == MOVE_SWAP) & (u >= 0) & (u + 1 < L)
+    i2, q2, u2 = i[ok2], q[ok2], u[ok2]
+    a, b = out[i2, q2, u2], out[i2, q2, u2 + 1]
+    other = ~((a[:, 0] == b[:, 0]) & (a[:, 1] == b[:, 1]))
+    i2, q2, u2, a, b = i2[other], q2[other], u2[other], a[other], b[other]
+    out[i2, q2, u2] = b
+    out[i2, q2, u2 + 1] = a
+    return out
+
+
+def decode(batch, plan, moves=None, n_cand=1, want_table=False):
+    """Times and objectives of explicit schedules on the device (fjsp_schedule_decode): n_cand candidates per env of
+    `batch` (an EnvBatch or a Batched* wrapper), each decoded on its env's instance; the envs' episodes are not touched.
+
+    plan: int32[N, cap, 3] -- one parent plan per env, shared by its candidates -- or [N, n_cand, cap, 3]; rows (r, n, m)
+    in sequence order, -1 rows past the end, cap = batch.decode_capacity().  moves: None or int32[N, n_cand, 3] = (kind,
+    u, m_new), applied while the plan is read (MOVE_NONE, MOVE_MACHINE, MOVE_SWAP).
+    Returns dict(objective=int64[N, n_cand, 2] (makespan, total tardiness), status=int32[N, n_cand] (DECODE_*),
+    table=int32[N, n_cand, cap, 6] or None, length=int32[N, n_cand]), device tensors; a failed candidate has objective -1,
+    length 0 and a table of -1.  ValueError for shapes that do not fit; FjspError where the library refuses (MO_DFJSP,
+    an instance whose per-candidate state exceeds the limit of include/fjsp_amd.h)."""
+    import torch
+    from ._capi import check, ptr
+    b = getattr(batch, "batch", batch)
+    n_cand = int(n_cand)
+    if n_cand < 1:
+        raise ValueError("n_cand must be at least 1")
+    cap = int(b._lib.fjsp_schedule_decode_capacity(b._h))
+    if not torch.is_tensor(plan):
+        plan = torch.as_tensor(np.asarray(plan))
+    if plan.dim() == 3 and tuple(plan.shape) == (b.N, cap, 3):
+        q_plans = 1
+    elif plan.dim() == 4 and tuple(plan.shape) == (b.N, n_cand, cap, 3):
+        q_plans = n_cand
+    else:
+        raise ValueError("plan must have shape %s or %s, got %s" % ((b.N, cap, 3), (b.N, n_cand, cap, 3), tuple(plan.shape)))
+    plan = plan.to(device=b.device, dtype=torch.int32).contiguous()
+    if moves is not None:
+        if not torch.is_tensor(moves):
+            moves = torch.as_tensor(np.asarray(moves))
+        if tuple(moves.shape) != (b.N, n_cand, 3):
+            raise ValueError("moves must have shape %s, got %s" % ((b.N, n_cand, 3), tuple(moves.shape)))
+        moves = moves.to(device=b.device, dtype=torch.int32).contiguous()
+    objective = torch.empty(b.N, n_cand, 2, dtype=torch.int64, device=b.device)
+    status = torch.empty(b.N, n_cand, dtype=torch.int32, device=b.device)
+    length = torch.empty(b.N, n_cand, dtype=torch.int32, device=b.device)
+    table = torch.empty(b.N, n_cand, cap, 6, dtype=torch.int32, device=b.device) if want_table else None
+    check(b._lib.fjsp_schedule_decode(b._h, ptr(plan), q_plans, ptr(moves), n_cand, ptr(objective), ptr(status), ptr(table),
+                                      ptr(length), b._stream()))
+    return dict(objective=objective, status=status, table=table, length=length)

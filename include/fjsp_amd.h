@@ -727,6 +727,45 @@ int fjsp_beam_select(const double *d_cost, const uint8_t *d_done, int32_t n_src,
 int fjsp_pareto_select(const double *d_obj, const uint8_t *d_valid, int32_t n_src, int32_t n_cand, int32_t n_obj,
                        int32_t cap, int32_t *d_index, int32_t *d_count, uint8_t *d_mask, void *stream);
 
+/* Explicit schedules decoded on the device (schedule.decode, policy_search.improve; csrc/fjsp_decode.hip): an operation
+ * sequence with a machine per operation -> its times and objectives, n_cand candidates per env in ONE decode launch.
+ * Candidate (i, q), i < N, q < n_cand, is decoded on the instance of env i (instance i % n_inst, as resident on the
+ * device: operation counts, processing times, order counts and arrivals, due dates); no env's episode state is read or
+ * changed.  Stream-ordered, no host synchronisation (a handle's first call allocates its 8 (KP + 1) bytes per instance).
+ *
+ * d_plan i32[N][q_plans][cap][3]: rows (r, n, m) -- kind, job number within the kind counted over all orders
+ * (class_FJSSP.py:212-216), machine -- in sequence order, the plan ends at its first row of three -1 (or at cap); q_plans
+ * is 1 (the env's candidates share one parent plan) or n_cand.  The stage of a row is implied: the t-th row of job (r, n) is
+ * its stage t.  d_moves (nullable) i32[N][n_cand][3] = (kind, u, m_new), applied while the plan is read: 0 nothing; 1 row
+ * u runs on machine m_new; 2 rows u and u + 1 change places (nothing if they are rows of one job).
+ *
+ * Decoding (SO_FJSSP.py:176-196 without the event clock): a job is ready at its order's arrival
+ * (class_FJSSP.py:212-218 numbers the jobs of a kind across the orders), a machine is free at 0; row by row time_begin =
+ * max(ready, free), time_end = time_begin + p[k][m], and both become time_end.  32-bit integers, exact.
+ *
+ * d_objective i64[N][n_cand][2] = (latest time_end, total tardiness of the last stages against the due dates the env
+ * uses, class_FJSSP.py:214-218 / the order's delivery time for SO_DFJSP); d_status i32[N][n_cand]; d_table (nullable)
+ * i32[N][n_cand][cap][6] in fjsp_env_schedule's format, -1 past d_len; d_len (nullable) i32[N][n_cand].
+ * Status per candidate: 0 decoded; 1 a row names no job of the instance; 2 a job has more rows than stages, or the plan
+ * ends with operations missing; 3 machine out of range or not eligible (p = 0); 4 bad move (unknown kind, or u -- for a
+ * swap u + 1 -- outside the plan).  4 outranks the others, else the first failing row in sequence order decides, a row's
+ * checks in the order 1, 2, 3.  A failed candidate has objective -1, length 0 and a table of -1; every check is an
+ * ordinary bounds-checked path and the other candidates are not affected.
+ *
+ * Limit: a candidate's state is 5 bytes per job of the batch's largest instance (jobs rounded up to 16) + 4 per machine
+ * (of the largest), and 32 candidates must fit the 160 KB of a CU's LDS: at most 5120 bytes per candidate.  That admits the
+ * reference's training distribution (12 kinds x 50 jobs, 20 machines: 3120 bytes) and every instance the environments take
+ * up to about 1000 jobs.  fjsp_schedule_decode_group: the candidates one workgroup decodes (256, 128, 64 or 32), 0 where
+ * the state does not fit or the batch is MO_DFJSP.
+ * FJSP_E_ARG: a null e, d_plan, d_objective or d_status, n_cand < 1, q_plans neither 1 nor n_cand, N * n_cand >= 2^31.
+ * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP (breakdown shifts and energy are not decoded), a state beyond the limit.
+ * FJSP_E_STATE: a generated handle whose last regenerate failed. */
+int fjsp_schedule_decode(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
+                         int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream);
+/* rows per plan = fjsp_env_schedule_capacity's cap (operations of the batch's largest instance), recording on or off */
+int fjsp_schedule_decode_capacity(const fjsp_env *e);
+int fjsp_schedule_decode_group(const fjsp_env *e);
+
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
  *
