@@ -176,6 +176,7 @@ SIGNATURES = {
     "fjsp_schedule_decode": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_schedule_decode_capacity": (C.c_int, [_vp]),
     "fjsp_schedule_decode_group": (C.c_int, [_vp]),
+    "fjsp_schedule_critical": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_policy_pair_sample": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 

@@ -674,6 +674,11 @@ class EnvBatch(object):
         from . import schedule
         return schedule.decode(self, plan, moves, n_cand, want_table)
 
+    def critical(self, table, n_cand=1, max_moves=0):
+        """schedule.critical on this batch's instances: tables -> tails, critical flags, one critical path and its moves."""
+        from . import schedule
+        return schedule.critical(self, table, n_cand, max_moves)
+
     def set_lp_threads(self, n_threads):
         """Host threads of the order-arrival LP service (0 = all cores).  The asynchronous service builds its worker pool
         at the first step_async and reads this once, there: call it before that."""

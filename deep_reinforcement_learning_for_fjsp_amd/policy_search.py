@@ -28,7 +28,9 @@ slowly.
   objective vectors per env (pareto.select, fjsp_pareto_select, csrc/fjsp_pareto.hip) instead of one minimum.
 - improve: no policy at all -- hill climbing on explicit schedules (an operation sequence and a machine per operation, for
   instance a recorded table's): every round decodes `neighbours` random moves of each env's plan in one launch
-  (schedule.decode, fjsp_schedule_decode, csrc/fjsp_decode.hip) and keeps the best if it is no worse.
+  (schedule.decode, fjsp_schedule_decode, csrc/fjsp_decode.hip) and keeps the best if it is no worse; the moves are uniform
+  reassignments and adjacent swaps, or drawn from the neighbourhood of the plan's critical path (schedule.critical,
+  fjsp_schedule_critical).
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -540,7 +542,24 @@ def _machine_tables(b):
     return torch.from_numpy(koff).to(b.device), torch.from_numpy(elig).to(b.device)
 
 
-def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, sideways=True):
+IMPROVE_NEIGHBOURHOODS = ("uniform", "critical", "mixed")
+CRITICAL_MOVES = 128          # moves of a critical path that improve draws from (schedule.critical's max_moves)
+
+
+def _uniform_moves(sch, draw, L, k, elig, inst, odd):
+    """int32[N, Q, 3] from draw f64[2, N, Q]: candidate q even -- a uniform row on a machine drawn uniformly from its
+    operation's eligible ones; q odd -- a uniform row exchanged with its successor.  k int[N, cap]: the rows' operation types."""
+    N, Q = draw.shape[1], draw.shape[2]
+    env = torch.arange(N, device=draw.device)
+    span = torch.where(odd, (L - 1)[:, None], L[:, None]).clamp(min=1)
+    u = torch.minimum((draw[0] * span).to(torch.int64), span - 1)
+    e = elig[inst[:, None], k[env[:, None], u].to(torch.int64).clamp(min=0)]                       # [N, Q, M]
+    pick = torch.minimum((draw[1] * e.sum(-1)).to(torch.int64), e.sum(-1) - 1).clamp(min=0)
+    m_new = ((e.cumsum(-1) == (pick + 1)[..., None]) & e).to(torch.int8).argmax(-1)
+    return torch.stack([torch.where(odd, sch.MOVE_SWAP, sch.MOVE_MACHINE).expand(N, Q), u, m_new], -1).to(torch.int32)
+
+
+def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, sideways=True, neighbourhood="uniform"):
     """Hill climbing on explicit schedules (schedule.decode, fjsp_schedule_decode): from one plan per env, `rounds` rounds
     of `neighbours` random neighbours per env, all N x neighbours of a round decoded by one launch.
 
@@ -550,6 +569,14 @@ def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, si
     successor (MOVE_SWAP).  Of the candidates that decode (status 0) the env takes the one of least `objective`
     ("makespan" or "tardiness"), the lowest q among equals, if it is better than its plan, or as good with sideways=True,
     and applies that move to its plan (schedule.apply_moves).  Nothing synchronises with the host inside the loop.
+
+    neighbourhood: "uniform" -- the draws above; "critical" (objective "makespan" only) -- every round puts the plan and
+    its table into begin order (schedule.begin_order), takes the moves of its critical path (schedule.critical, the first
+    CRITICAL_MOVES of them: the exchange of two operations that follow each other on a machine of the path, then the path's
+    operations on their other machines) and draws every candidate uniformly from that list; an env whose list is empty
+    has no candidates in the round; "mixed" -- candidates q < neighbours // 2 from the critical list, the others as
+    "uniform" draws them.  Both decode the accepted plans once more per round, for the next round's table.
+
     Returns dict(plan=int32[N, cap, 3], objective=int64[N, 2] (makespan, tardiness) of it, history=int64[rounds + 1, N] the
     chosen objective of the input plan and after every round, accepted=int64[N] moves taken, table=int32[N, cap, 6] and
     length=int32[N] of the final plans); rounds=0 returns the input plan."""
@@ -557,6 +584,10 @@ def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, si
     b, _ = _unwrap(batch, None)
     if objective not in IMPROVE_OBJECTIVES:
         raise ValueError("objective must be one of %s" % (IMPROVE_OBJECTIVES,))
+    if neighbourhood not in IMPROVE_NEIGHBOURHOODS:
+        raise ValueError("neighbourhood must be one of %s" % (IMPROVE_NEIGHBOURHOODS,))
+    if neighbourhood != "uniform" and objective != "makespan":
+        raise ValueError("neighbourhood %r follows the critical path of the makespan: objective must be 'makespan'" % (neighbourhood,))
     rounds, Q = int(rounds), int(neighbours)
     if rounds < 0 or Q < 1:
         raise ValueError("improve needs rounds >= 0 and neighbours >= 1")
@@ -569,9 +600,8 @@ def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, si
     inst = torch.arange(N, device=dev) % b.n_inst
     tab = first["table"][:, 0].to(torch.int64)
     L = first["length"][:, 0].to(torch.int64)
-    # rows (r, n, m, k): the operation type travels with its row (neither move changes a row's stage)
-    k = torch.where(tab[..., 0] >= 0, koff[inst[:, None], tab[..., 0].clamp(min=0)] + tab[..., 1], torch.full_like(tab[..., 0], -1))
-    rows = torch.cat([sch.plan_of(tab), k[..., None]], -1).to(torch.int32)
+    # the operation type of a table's rows
+    op_types = lambda tab: torch.where(tab[..., 0] >= 0, koff[inst[:, None], tab[..., 0].clamp(min=0)] + tab[..., 1], torch.full_like(tab[..., 0], -1))
     cur = first["objective"][:, 0, col].clone()
     history = torch.empty(rounds + 1, N, dtype=torch.int64, device=dev)
     history[0] = cur
@@ -581,25 +611,53 @@ def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, si
     odd = (torch.arange(Q, device=dev) % 2 == 1)[None, :]
     worst = torch.iinfo(torch.int64).max
     env = torch.arange(N, device=dev)
-    for t in range(rounds):
-        draw = torch.rand(2, N, Q, generator=gen, device=dev, dtype=torch.float64)
-        span = torch.where(odd, (L - 1)[:, None], L[:, None]).clamp(min=1)
-        u = torch.minimum((draw[0] * span).to(torch.int64), span - 1)
-        e = elig[inst[:, None], rows[env[:, None], u, 3].to(torch.int64).clamp(min=0)]               # [N, Q, M]
-        pick = torch.minimum((draw[1] * e.sum(-1)).to(torch.int64), e.sum(-1) - 1).clamp(min=0)
-        m_new = ((e.cumsum(-1) == (pick + 1)[..., None]) & e).to(torch.int8).argmax(-1)
-        moves = torch.stack([torch.where(odd, sch.MOVE_SWAP, sch.MOVE_MACHINE).expand(N, Q), u, m_new], -1).to(torch.int32)
-        res = sch.decode(b, rows[..., :3].contiguous(), moves, Q)
-        obj = torch.where(res["status"] == 0, res["objective"][..., col], torch.full((), worst, dtype=torch.int64, device=dev))
+
+    def select(moves, res, masked=None):
+        """(chosen int32[N, 3], take bool[N], best int64[N]): the round's winner per env, MOVE_NONE where none is taken."""
+        ok = res["status"] == 0 if masked is None else (res["status"] == 0) & ~masked
+        obj = torch.where(ok, res["objective"][..., col], torch.full((), worst, dtype=torch.int64, device=dev))
         best, q = obj.min(1)
         q = (obj == best[:, None]).to(torch.int8).argmax(1)                                             # the lowest q among equals
         take = (best != worst) & ((best < cur) | ((best == cur) & bool(sideways)))
         chosen = moves[env, q].clone()
         chosen[~take, 0] = sch.MOVE_NONE
-        rows = sch.apply_moves(rows, chosen[:, None])[:, 0]
+        return chosen, take, best
+
+    if neighbourhood == "uniform":
+        # rows (r, n, m, k): the operation type travels with its row (neither move changes a row's stage)
+        rows = torch.cat([sch.plan_of(tab), op_types(tab)[..., None]], -1).to(torch.int32)
+        for t in range(rounds):
+            draw = torch.rand(2, N, Q, generator=gen, device=dev, dtype=torch.float64)
+            moves = _uniform_moves(sch, draw, L, rows[..., 3], elig, inst, odd)
+            res = sch.decode(b, rows[..., :3].contiguous(), moves, Q)
+            chosen, take, best = select(moves, res)
+            rows = sch.apply_moves(rows, chosen[:, None])[:, 0]
+            cur = torch.where(take, best, cur)
+            accepted += take
+            history[t + 1] = cur
+        last = sch.decode(b, rows[..., :3].contiguous(), want_table=True)
+        return dict(plan=rows[..., :3].contiguous(), objective=last["objective"][:, 0], history=history, accepted=accepted,
+                    table=last["table"][:, 0], length=last["length"][:, 0])
+
+    last, out_plan = first, None
+    from_path = (torch.arange(Q, device=dev) < (Q if neighbourhood == "critical" else Q // 2))[None, :].expand(N, Q)
+    for t in range(rounds):
+        pl, tab = sch.begin_order(last["table"][:, 0])
+        crit = sch.critical(b, tab, 1, CRITICAL_MOVES)
+        listed = crit["n_moves"][:, 0].to(torch.int64).clamp(max=CRITICAL_MOVES)[:, None]              # [N, 1]
+        draw = torch.rand(3, N, Q, generator=gen, device=dev, dtype=torch.float64)
+        slot = torch.minimum((draw[2] * listed).to(torch.int64), listed - 1).clamp(min=0)
+        moves = crit["moves"][:, 0][env[:, None], slot]
+        if neighbourhood == "mixed":
+            moves = torch.where(from_path[..., None], moves, _uniform_moves(sch, draw[:2], L, op_types(tab.to(torch.int64)), elig, inst, odd))
+        res = sch.decode(b, pl.contiguous(), moves, Q)
+        chosen, take, best = select(moves, res, from_path & (listed == 0))
+        out_plan = sch.apply_moves(pl, chosen[:, None])[:, 0].contiguous()
+        last = sch.decode(b, out_plan, want_table=True)
         cur = torch.where(take, best, cur)
         accepted += take
         history[t + 1] = cur
-    last = sch.decode(b, rows[..., :3].contiguous(), want_table=True)
-    return dict(plan=rows[..., :3].contiguous(), objective=last["objective"][:, 0], history=history, accepted=accepted,
+    if out_plan is None:
+        out_plan = torch.as_tensor(plan, device=dev).to(torch.int32).contiguous()
+    return dict(plan=out_plan, objective=last["objective"][:, 0], history=history, accepted=accepted,
                 table=last["table"][:, 0], length=last["length"][:, 0])

@@ -1,5 +1,6 @@
 """Host-side use of a recorded schedule (EnvBatch.schedule / fjsp_env_schedule), pure numpy, and the way back:
-explicit schedules decoded on the device (plan_of / decode / apply_moves, fjsp_schedule_decode).
+explicit schedules decoded on the device (plan_of / decode / apply_moves, fjsp_schedule_decode) and their critical paths
+(critical / begin_order, fjsp_schedule_critical).
 
 A table row is one dispatched operation, (r, j, n, m, time_begin, time_end): kind r, stage j, job number n within
 kind r (counted over all orders, class_FJSSP.py:212-216), machine m and the task's start and end as the reference's
@@ -11,6 +12,9 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     plan_of(table)                              the (r, n, m) columns of a table: the explicit schedule it records
     decode(batch, plan, moves, n_cand)          times and objectives of explicit schedules, on the device
     apply_moves(plan, moves)                    the plans that decode's moves stand for, materialised
+    pair_move(u, v, w)                          the MOVE_PAIR that puts rows u and v, v first, behind row w
+    critical(batch, table, n_cand, max_moves)   tails, critical flags, one critical path and its moves, on the device
+    begin_order(table)                          the same schedule with its rows sorted by begin: (plan, table)
 
 `inst` is anything with the instance arrays of instances.InstanceArrays: Jr[R], p[K][M] (0 = ineligible),
 count[S][R], arrive[S], delivery[S] (and bk_n[M], bk[W][2] for MO_DFJSP breakdown windows).
@@ -198,6 +202,7 @@ def from_trace(inst, k, m, job_n, step_time_after, t0=0):
 
 # ---- explicit schedules on the device (fjsp_schedule_decode, csrc/fjsp_decode.hip)
 MOVE_NONE, MOVE_MACHINE, MOVE_SWAP = 0, 1, 2
+MOVE_PAIR = 4                                   # (3 is no kind: decode refuses it)
 DECODE_OK, DECODE_NO_JOB, DECODE_STAGES, DECODE_MACHINE, DECODE_BAD_MOVE = range(5)
 
 
@@ -219,9 +224,10 @@ def _plan_length(plan):
 def apply_moves(plan, moves):
     """The plans decode(batch, plan, moves) decodes, materialised with tensor indexing.  plan: int32[N, cap, 3] (one
     parent per env) or [N, Q, cap, 3]; moves: int32[N, Q, 3] = (kind, u, m_new).  Returns int32[N, Q, cap, 3].  Kind 1
-    sets row u's machine, kind 2 exchanges rows u and u + 1 unless they are rows of one job; a move decode refuses (status
-    4: unknown kind, u outside the plan) leaves its plan as it is.  Rows may carry further columns behind the three
-    (improve keeps each row's operation type there): they move with their rows."""
+    sets row u's machine, kind 2 exchanges rows u and u + 1 unless they are rows of one job, kind 4 (pair_move) puts rows
+    u and v, v first, behind row w; a move decode refuses (status 4: unknown kind, u or v outside the plan, a third field
+    that is no dv | dw << 16 with 1 <= dv, 0 <= dw < dv) leaves its plan as it is.  Rows may carry further columns
+    behind the three (improve keeps each row's operation type there): they move with their rows."""
     import torch
     moves = torch.as_tensor(moves, device=plan.device).to(torch.int64)
     N, Q = moves.shape[0], moves.shape[1]
@@ -240,7 +246,29 @@ def apply_moves(plan, moves):
     i2, q2, u2, a, b = i2[other], q2[other], u2[other], a[other], b[other]
     out[i2, q2, u2] = b
     out[i2, q2, u2 + 1] = a
-    return out
+    dv, dw = m_new & 0xFFFF, m_new >> 16
+    ok4 = (kind == MOVE_PAIR) & (m_new >= 0) & (dv >= 1) & (dw < dv) & (u >= 0) & (u + dv < L)
+    pu, pw, pv = u[..., None], (u + dw)[..., None], (u + dv)[..., None]
+    t = torch.arange(out.shape[2], device=out.device).expand(N, Q, -1)
+    src = torch.where(t < pw, t + 1, torch.where(t == pw, pv, torch.where(t == pw + 1, pu, t - 1)))
+    src = torch.where(ok4[..., None] & (t >= pu) & (t <= pv), src, t)           # position t of the moved plan is old row src
+    return torch.gather(out, 2, src[..., None].expand(-1, -1, -1, out.shape[3]))
+
+
+def pair_move(u, v, w):
+    """The MOVE_PAIR (4, u, dv | dw << 16) that takes rows u and v = u + dv out of the plan and puts them, v first,
+    directly behind old row w = u + dw, u <= w < v (w = u: v in front of u; w = v - 1: u behind v).  Integers give a tuple,
+    tensors / arrays a stacked [..., 3] of their kind.  ValueError unless u <= w < v <= u + 65535 (integers only)."""
+    if all(isinstance(x, (int, np.integer)) for x in (u, v, w)):
+        u, v, w = int(u), int(v), int(w)
+        if not (0 <= u <= w < v <= u + 65535):
+            raise ValueError("pair_move needs 0 <= u <= w < v <= u + 65535, got %r" % ((u, v, w),))
+        return (MOVE_PAIR, u, (v - u) | ((w - u) << 16))
+    third = (v - u) | ((w - u) << 16)
+    if hasattr(third, "new_full"):
+        import torch
+        return torch.stack([torch.full_like(third, MOVE_PAIR), u + 0 * third, third], -1)
+    return np.stack([np.full_like(third, MOVE_PAIR), u + 0 * third, third], -1)
 
 
 def decode(batch, plan, moves=None, n_cand=1, want_table=False):
@@ -283,3 +311,65 @@ def decode(batch, plan, moves=None, n_cand=1, want_table=False):
     check(b._lib.fjsp_schedule_decode(b._h, ptr(plan), q_plans, ptr(moves), n_cand, ptr(objective), ptr(status), ptr(table),
                                       ptr(length), b._stream()))
     return dict(objective=objective, status=status, table=table, length=length)
+
+
+CRITICAL_OK, CRITICAL_BAD_ROW, CRITICAL_EMPTY = range(3)
+FLAG_CRITICAL, FLAG_PATH, FLAG_MACHINE_ARC = 1, 2, 4
+
+
+def critical(batch, table, n_cand=1, max_moves=0):
+    """Critical paths of decoded schedules on the device (fjsp_schedule_critical): n_cand tables per env of `batch`, one
+    lane per table; the envs' episodes are not touched.
+
+    table: int32[N, cap, 6] (n_cand = 1) or [N, n_cand, cap, 6], rows (r, stage, n, m, begin, end) as decode(...,
+    want_table=True) and EnvBatch.schedule() write them, -1 rows past the end.  The arcs are those of the table's own
+    order: a row's job (machine) predecessor is the latest row in front of it of the same job (on the same machine).
+    Returns a dict of device tensors, [N, n_cand] in front of every shape:
+      makespan int32 -- C, the largest end;  status int32 -- CRITICAL_OK, CRITICAL_BAD_ROW (a row fails a range check),
+      CRITICAL_EMPTY; with the latter two tail, path and makespan are -1 and everything else is 0;
+      tail int32[cap] -- the work that must follow a row: max over its job and its machine successor of their tail + their
+      duration, 0 without a successor, -1 past the table;  flags uint8[cap] -- FLAG_CRITICAL (end + tail = C) |
+      FLAG_PATH | FLAG_MACHINE_ARC (joined to its path successor by a machine arc);
+      path int32[cap], path_len int32 -- row indices from the first row that ends at C backwards, each step to the tight
+      predecessor (end = begin) that stands later in the table, a row that is both predecessors as a job arc;
+      moves int32[max_moves, 3], n_moves, skipped int32 -- the path's neighbourhood for decode: a MOVE_PAIR per machine arc
+      of the path that exchanges its two operations on their machine, then a MOVE_MACHINE per path operation and other
+      eligible machine; n_moves counts them all, the first max_moves are written, MOVE_NONE behind them; skipped counts
+      the machine arcs that no pair move expresses (see begin_order).
+    ValueError for shapes that do not fit; FjspError where the library refuses, as decode."""
+    import torch
+    from ._capi import check, ptr
+    b = getattr(batch, "batch", batch)
+    n_cand, max_moves = int(n_cand), int(max_moves)
+    if n_cand < 1 or max_moves < 0:
+        raise ValueError("critical needs n_cand >= 1 and max_moves >= 0")
+    cap = int(b._lib.fjsp_schedule_decode_capacity(b._h))
+    if not torch.is_tensor(table):
+        table = torch.as_tensor(np.asarray(table))
+    if tuple(table.shape) not in ((b.N, n_cand, cap, 6),) + (((b.N, cap, 6),) if n_cand == 1 else ()):
+        raise ValueError("table must have shape %s, got %s" % ((b.N, n_cand, cap, 6), tuple(table.shape)))
+    table = table.to(device=b.device, dtype=torch.int32).contiguous()
+    new = lambda *shape, dtype=torch.int32: torch.empty((b.N, n_cand) + shape, dtype=dtype, device=b.device)
+    out = dict(tail=new(cap), flags=new(cap, dtype=torch.uint8), path=new(cap), path_len=new(), moves=new(max_moves, 3),
+               n_moves=new(), skipped=new(), status=new(), makespan=new())
+    check(b._lib.fjsp_schedule_critical(b._h, ptr(table), n_cand, ptr(out["tail"]), ptr(out["flags"]), ptr(out["path"]),
+                                        ptr(out["path_len"]), ptr(out["moves"]) if max_moves else None, max_moves, ptr(out["n_moves"]),
+                                        ptr(out["skipped"]), ptr(out["status"]), ptr(out["makespan"]), b._stream()))
+    return out
+
+
+def begin_order(table):
+    """(plan, table) with the rows of every table stably sorted by begin, -1 rows left at the end; table: int32[..., cap,
+    6], a device tensor or an array, as decode writes it.  Two facts make this the form to search from.  It is the same
+    schedule: along every job arc and every machine arc begin increases strictly, because p > 0, so the sorted plan
+    keeps every job's and every machine's sequence and decodes to the same times.  And in this order critical() skips no
+    machine arc a -> b: the last row of b's job between them begins before b does, the first row of a's job between them
+    begins no earlier than b, so the former stands in front of the latter and the pair move exists."""
+    import torch
+    if not torch.is_tensor(table):
+        table = torch.as_tensor(np.asarray(table))
+    end = (table == -1).all(-1)
+    key = torch.where(end, torch.full_like(table[..., B_], torch.iinfo(table.dtype).max), table[..., B_])
+    order = torch.sort(key, dim=-1, stable=True).indices
+    table = torch.gather(table, -2, order[..., None].expand(table.shape))
+    return plan_of(table), table

@@ -737,7 +737,10 @@ int fjsp_pareto_select(const double *d_obj, const uint8_t *d_valid, int32_t n_sr
  * (class_FJSSP.py:212-216), machine -- in sequence order, the plan ends at its first row of three -1 (or at cap); q_plans
  * is 1 (the env's candidates share one parent plan) or n_cand.  The stage of a row is implied: the t-th row of job (r, n) is
  * its stage t.  d_moves (nullable) i32[N][n_cand][3] = (kind, u, m_new), applied while the plan is read: 0 nothing; 1 row
- * u runs on machine m_new; 2 rows u and u + 1 change places (nothing if they are rows of one job).
+ * u runs on machine m_new; 2 rows u and u + 1 change places (nothing if they are rows of one job); 4, with the third
+ * field dv | dw << 16, v = u + dv, w = u + dw, 1 <= dv, 0 <= dw < dv: rows u and v leave their places and stand, v first,
+ * directly behind old row w -- old rows 0 .. u-1, u+1 .. w, v, u, w+1 .. v-1, v+1 .. (dw = 0 puts v in front of u,
+ * dw = dv - 1 puts u behind v; no same-job exception).  3 is no kind.
  *
  * Decoding (SO_FJSSP.py:176-196 without the event clock): a job is ready at its order's arrival
  * (class_FJSSP.py:212-218 numbers the jobs of a kind across the orders), a machine is free at 0; row by row time_begin =
@@ -748,7 +751,7 @@ int fjsp_pareto_select(const double *d_obj, const uint8_t *d_valid, int32_t n_sr
  * i32[N][n_cand][cap][6] in fjsp_env_schedule's format, -1 past d_len; d_len (nullable) i32[N][n_cand].
  * Status per candidate: 0 decoded; 1 a row names no job of the instance; 2 a job has more rows than stages, or the plan
  * ends with operations missing; 3 machine out of range or not eligible (p = 0); 4 bad move (unknown kind, or u -- for a
- * swap u + 1 -- outside the plan).  4 outranks the others, else the first failing row in sequence order decides, a row's
+ * swap u + 1, for kind 4 v -- outside the plan, or a third field of kind 4 that is negative or has dv < 1 or dw >= dv).  4 outranks the others, else the first failing row in sequence order decides, a row's
  * checks in the order 1, 2, 3.  A failed candidate has objective -1, length 0 and a table of -1; every check is an
  * ordinary bounds-checked path and the other candidates are not affected.
  *
@@ -765,6 +768,44 @@ int fjsp_schedule_decode(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, co
 /* rows per plan = fjsp_env_schedule_capacity's cap (operations of the batch's largest instance), recording on or off */
 int fjsp_schedule_decode_capacity(const fjsp_env *e);
 int fjsp_schedule_decode_group(const fjsp_env *e);
+
+/* Critical paths of decoded schedules (schedule.critical, policy_search.improve(neighbourhood=...); csrc/fjsp_decode.hip):
+ * tails, critical flags, one critical path and that path's neighbourhood as moves fjsp_schedule_decode takes, n_cand
+ * tables per env in ONE launch, one lane per table, grouped as fjsp_schedule_decode groups its candidates.  Table (i, q)
+ * is read against the instance of env i; no env's episode state is read or changed.  Stream-ordered, no host
+ * synchronisation, no atomics.
+ *
+ * d_table i32[N][n_cand][cap][6]: rows (r, stage, n, m, begin, end) as fjsp_schedule_decode writes them; a table ends at
+ * its first row of six -1 (or at cap).  Only the table's own order defines the arcs: the job (machine) predecessor of
+ * row t is the latest row in front of it with the same (r, n) (the same m), its successor the first such row behind it;
+ * a row's duration is end - begin.  For a table that fjsp_schedule_decode wrote these are the arcs of the schedule.
+ *
+ * Per table: C = the largest end (d_makespan), e0 = the first row with end = C.
+ *   d_tail i32[..][cap]: the larger of (tail + duration) of the job successor and of the machine successor, 0 without a
+ *     successor: the work that must follow the row (32-bit, exact for every table a decode wrote); -1 past the table.
+ *   d_flags u8[..][cap]: bit 1 end + tail = C (critical); bit 2 on the path; bit 4 joined to its path successor by a
+ *     machine arc; 0 past the table.
+ *   d_path i32[..][cap], d_path_len: row indices from e0 backwards, -1 past path_len.  From the path's current row the
+ *     next is, of its job predecessor and its machine predecessor, a tight one (end = the current row's begin), the one
+ *     later in the table if both are; a row that is both predecessors is a job arc; with no tight predecessor the
+ *     path ends (begin 0, an order's arrival, idle time in a foreign table).
+ *   d_moves i32[..][max_moves][3] (may be null with max_moves = 0), d_n_moves, d_skipped: first, per machine arc of the
+ *     path in path order (a in row u -> b in row v), the move (4, u, (v - u) | (w - u) << 16) with w = the last row of
+ *     b's job in (u, v), or u without one -- it exchanges a and b on their machine --, if w stands in front of the first
+ *     row of a's job in (u, v) and v - u <= 65535; an arc that does not is counted in d_skipped instead (none in a
+ *     table whose rows are in begin order).  Then, per path row in path order, (1, row, m) for every other machine m with
+ *     p > 0 for the row's operation, ascending.  d_n_moves counts all of them; the first max_moves are written, the
+ *     rest of the array is (0, 0, 0).
+ * d_status i32[N][n_cand]: 0; 1 a row fails a range check (r, n, m, stage against the instance, 0 <= begin < end), checked
+ * before the value addresses anything; 2 the table is empty.  With 1 or 2: tail, path and makespan -1, the rest 0.
+ *
+ * Limits and refusals are fjsp_schedule_decode's (the state here, 4 bytes per job word and per machine, fits in its).
+ * FJSP_E_ARG: a null e, d_table or output pointer (d_moves only with max_moves > 0), n_cand < 1, max_moves < 0,
+ * N * n_cand >= 2^31.  FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP, a state beyond the limit.  FJSP_E_STATE: a generated
+ * handle whose last regenerate failed. */
+int fjsp_schedule_critical(fjsp_env *e, const int32_t *d_table, int32_t n_cand, int32_t *d_tail, uint8_t *d_flags, int32_t *d_path,
+                           int32_t *d_path_len, int32_t *d_moves, int32_t max_moves, int32_t *d_n_moves, int32_t *d_skipped,
+                           int32_t *d_status, int32_t *d_makespan, void *stream);
 
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
