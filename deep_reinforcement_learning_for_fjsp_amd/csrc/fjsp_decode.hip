@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256) void schedule_critical_kernel(DevBatch b, Crit
                 if (w == u && r == rb && n == nb) w = t;
                 if (r == ra && n == na) first = t;
             }
-            if (w < first && v - u <= 65535) emit(4, u, (v - u) | ((w - u) << 16));
+            if (w < first && w - u <= 32767) emit(4, u, (v - u) | ((w - u) << 16));    // (the field stays a non-negative int)
             else ++skipped;
         }
         for (int i = 0; i < plen; ++i) {

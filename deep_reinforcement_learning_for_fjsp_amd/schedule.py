@@ -203,6 +203,7 @@ def from_trace(inst, k, m, job_n, step_time_after, t0=0):
 # ---- explicit schedules on the device (fjsp_schedule_decode, csrc/fjsp_decode.hip)
 MOVE_NONE, MOVE_MACHINE, MOVE_SWAP = 0, 1, 2
 MOVE_PAIR = 4                                   # (3 is no kind: decode refuses it)
+PAIR_DW_MAX = 32767                             # dw of a MOVE_PAIR's dv | dw << 16: the field is a non-negative int32
 DECODE_OK, DECODE_NO_JOB, DECODE_STAGES, DECODE_MACHINE, DECODE_BAD_MOVE = range(5)
 
 
@@ -226,7 +227,8 @@ def apply_moves(plan, moves):
     parent per env) or [N, Q, cap, 3]; moves: int32[N, Q, 3] = (kind, u, m_new).  Returns int32[N, Q, cap, 3].  Kind 1
     sets row u's machine, kind 2 exchanges rows u and u + 1 unless they are rows of one job, kind 4 (pair_move) puts rows
     u and v, v first, behind row w; a move decode refuses (status 4: unknown kind, u or v outside the plan, a third field
-    that is no dv | dw << 16 with 1 <= dv, 0 <= dw < dv) leaves its plan as it is.  Rows may carry further columns
+    that is no dv | dw << 16 with 1 <= dv, 0 <= dw < dv -- a negative field, which is what dw > 32767 makes of an int32,
+    included) leaves its plan as it is.  Rows may carry further columns
     behind the three (improve keeps each row's operation type there): they move with their rows."""
     import torch
     moves = torch.as_tensor(moves, device=plan.device).to(torch.int64)
@@ -258,15 +260,29 @@ def apply_moves(plan, moves):
 def pair_move(u, v, w):
     """The MOVE_PAIR (4, u, dv | dw << 16) that takes rows u and v = u + dv out of the plan and puts them, v first,
     directly behind old row w = u + dw, u <= w < v (w = u: v in front of u; w = v - 1: u behind v).  Integers give a tuple,
-    tensors / arrays a stacked [..., 3] of their kind.  ValueError unless u <= w < v <= u + 65535 (integers only)."""
+    tensors / arrays a stacked [..., 3] of their kind.  The third field is a non-negative int32, so w <= u + PAIR_DW_MAX
+    (32767) besides v <= u + 65535: ValueError unless 0 <= u <= w < v <= u + 65535 and w - u <= 32767, for integers and
+    for every element of a tensor / array (checking a device tensor synchronises)."""
     if all(isinstance(x, (int, np.integer)) for x in (u, v, w)):
         u, v, w = int(u), int(v), int(w)
-        if not (0 <= u <= w < v <= u + 65535):
-            raise ValueError("pair_move needs 0 <= u <= w < v <= u + 65535, got %r" % ((u, v, w),))
+        if not (0 <= u <= w < v <= u + 65535 and w - u <= PAIR_DW_MAX):
+            raise ValueError("pair_move needs 0 <= u <= w < v <= u + 65535 and w - u <= %d, got %r" % (PAIR_DW_MAX, (u, v, w)))
         return (MOVE_PAIR, u, (v - u) | ((w - u) << 16))
-    third = (v - u) | ((w - u) << 16)
-    if hasattr(third, "new_full"):
+    ref = next((x for x in (u, v, w) if hasattr(x, "new_full")), None)
+    if ref is not None:                                          # (a scalar among tensors takes their dtype and device)
         import torch
+        u, v, w = torch.broadcast_tensors(*(x if hasattr(x, "new_full") else torch.as_tensor(x, dtype=ref.dtype, device=ref.device)
+                                            for x in (u, v, w)))
+        dv, dw = v.to(torch.int64) - u, w.to(torch.int64) - u
+    else:
+        ref = next((x for x in (u, v, w) if isinstance(x, np.ndarray)), None)
+        u, v, w = np.broadcast_arrays(*(x if isinstance(x, np.ndarray) else np.asarray(x, None if ref is None else ref.dtype)
+                                        for x in (u, v, w)))
+        dv, dw = v.astype(np.int64) - u, w.astype(np.int64) - u
+    if not bool(((u >= 0) & (dw >= 0) & (dw < dv) & (dv <= 65535) & (dw <= PAIR_DW_MAX)).all()):
+        raise ValueError("pair_move needs 0 <= u <= w < v <= u + 65535 and w - u <= %d in every element" % PAIR_DW_MAX)
+    third = (dv | (dw << 16)).to(u.dtype) if hasattr(dv, "new_full") else (dv | (dw << 16)).astype(u.dtype)
+    if hasattr(third, "new_full"):
         return torch.stack([torch.full_like(third, MOVE_PAIR), u + 0 * third, third], -1)
     return np.stack([np.full_like(third, MOVE_PAIR), u + 0 * third, third], -1)
 
@@ -277,7 +293,8 @@ def decode(batch, plan, moves=None, n_cand=1, want_table=False):
 
     plan: int32[N, cap, 3] -- one parent plan per env, shared by its candidates -- or [N, n_cand, cap, 3]; rows (r, n, m)
     in sequence order, -1 rows past the end, cap = batch.decode_capacity().  moves: None or int32[N, n_cand, 3] = (kind,
-    u, m_new), applied while the plan is read (MOVE_NONE, MOVE_MACHINE, MOVE_SWAP).
+    u, m_new), applied while the plan is read (MOVE_NONE, MOVE_MACHINE, MOVE_SWAP, MOVE_PAIR with m_new = dv | dw << 16,
+    dw <= 32767: a negative third field is refused, status 4).
     Returns dict(objective=int64[N, n_cand, 2] (makespan, total tardiness), status=int32[N, n_cand] (DECODE_*),
     table=int32[N, n_cand, cap, 6] or None, length=int32[N, n_cand]), device tensors; a failed candidate has objective -1,
     length 0 and a table of -1.  ValueError for shapes that do not fit; FjspError where the library refuses (MO_DFJSP,
@@ -335,7 +352,8 @@ def critical(batch, table, n_cand=1, max_moves=0):
       moves int32[max_moves, 3], n_moves, skipped int32 -- the path's neighbourhood for decode: a MOVE_PAIR per machine arc
       of the path that exchanges its two operations on their machine, then a MOVE_MACHINE per path operation and other
       eligible machine; n_moves counts them all, the first max_moves are written, MOVE_NONE behind them; skipped counts
-      the machine arcs that no pair move expresses (see begin_order).
+      the machine arcs that no pair move expresses: w not in front of the first row of a's job in (u, v), or w - u >
+      32767, which the move's third field cannot carry (see begin_order: neither happens in a begin-ordered table).
     ValueError for shapes that do not fit; FjspError where the library refuses, as decode."""
     import torch
     from ._capi import check, ptr
@@ -364,7 +382,9 @@ def begin_order(table):
     schedule: along every job arc and every machine arc begin increases strictly, because p > 0, so the sorted plan
     keeps every job's and every machine's sequence and decodes to the same times.  And in this order critical() skips no
     machine arc a -> b: the last row of b's job between them begins before b does, the first row of a's job between them
-    begins no earlier than b, so the former stands in front of the latter and the pair move exists."""
+    begins no earlier than b, so the former stands in front of the latter and the pair move exists.  Its dw fits: the rows
+    between a and b all begin within a's duration, at most p_a + 1 of them per machine, and create's clock rule keeps p
+    at 508 at most on any instance of more than 32 768 operations (MOVE_PAIR), so v - u <= 32 x 509 = 16 288."""
     import torch
     if not torch.is_tensor(table):
         table = torch.as_tensor(np.asarray(table))

@@ -738,7 +738,8 @@ int fjsp_pareto_select(const double *d_obj, const uint8_t *d_valid, int32_t n_sr
  * is 1 (the env's candidates share one parent plan) or n_cand.  The stage of a row is implied: the t-th row of job (r, n) is
  * its stage t.  d_moves (nullable) i32[N][n_cand][3] = (kind, u, m_new), applied while the plan is read: 0 nothing; 1 row
  * u runs on machine m_new; 2 rows u and u + 1 change places (nothing if they are rows of one job); 4, with the third
- * field dv | dw << 16, v = u + dv, w = u + dw, 1 <= dv, 0 <= dw < dv: rows u and v leave their places and stand, v first,
+ * field dv | dw << 16, v = u + dv, w = u + dw, 1 <= dv <= 65535, 0 <= dw < dv, dw <= 32767 (the field is a non-negative
+ * int32; a plan has at most 65535 rows, so dv always fits): rows u and v leave their places and stand, v first,
  * directly behind old row w -- old rows 0 .. u-1, u+1 .. w, v, u, w+1 .. v-1, v+1 .. (dw = 0 puts v in front of u,
  * dw = dv - 1 puts u behind v; no same-job exception).  3 is no kind.
  *
@@ -792,10 +793,10 @@ int fjsp_schedule_decode_group(const fjsp_env *e);
  *   d_moves i32[..][max_moves][3] (may be null with max_moves = 0), d_n_moves, d_skipped: first, per machine arc of the
  *     path in path order (a in row u -> b in row v), the move (4, u, (v - u) | (w - u) << 16) with w = the last row of
  *     b's job in (u, v), or u without one -- it exchanges a and b on their machine --, if w stands in front of the first
- *     row of a's job in (u, v) and v - u <= 65535; an arc that does not is counted in d_skipped instead (none in a
- *     table whose rows are in begin order).  Then, per path row in path order, (1, row, m) for every other machine m with
- *     p > 0 for the row's operation, ascending.  d_n_moves counts all of them; the first max_moves are written, the
- *     rest of the array is (0, 0, 0).
+ *     row of a's job in (u, v) and w - u <= 32767 (the decoder's limit on dw); an arc that does not is counted in
+ *     d_skipped instead (none in a table whose rows are in begin order).  Then, per path row in path order, (1, row, m)
+ *     for every other machine m with p > 0 for the row's operation, ascending.  d_n_moves counts all of them; the first
+ *     max_moves are written, the rest of the array is (0, 0, 0).
  * d_status i32[N][n_cand]: 0; 1 a row fails a range check (r, n, m, stage against the instance, 0 <= begin < end), checked
  * before the value addresses anything; 2 the table is empty.  With 1 or 2: tail, path and makespan -1, the rest 0.
  *

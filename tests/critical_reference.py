@@ -82,7 +82,7 @@ def critical_one(inst, table, max_moves=0, cap=None):
         of_b = [t for t in range(u + 1, v) if job(t) == job(v)]
         of_a = [t for t in range(u + 1, v) if job(t) == job(u)]
         w = of_b[-1] if of_b else u
-        if (not of_a or w < of_a[0]) and v - u <= 65535:
+        if (not of_a or w < of_a[0]) and w - u <= 32767:            # (dv | dw << 16 stays a non-negative int32)
             moves.append((MOVE_PAIR, u, (v - u) | ((w - u) << 16)))
         else:
             skipped += 1
