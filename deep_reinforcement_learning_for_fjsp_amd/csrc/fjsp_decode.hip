@@ -19,7 +19,7 @@
 // record in front of every decode, stream-ordered, so a regenerated handle needs no bookkeeping.
 //
 // A move is applied while the plan is read: a reassignment is a select, a swap and a pair move (kind 4: rows u and v stand,
-// v first, behind row w, u <= w < v; the swap is the pair u, u + 1, u) are one index map, position -> row, in src().
+// v first, behind row w, u <= w < v; the swap is the pair u, u + 1, u) are one index map, position -> row, in move_src().
 //
 // fjsp_schedule_critical is the decode run backwards, on the tables decode writes: one lane per table, the same grouping,
 // the same banked words -- per job and per machine "tail + duration of the latest row seen", as decode keeps ready / free.
@@ -31,12 +31,17 @@
 // Nothing is left to fault: every index a plan or a move supplies is range-checked before it is used, a candidate that
 // fails a check keeps reading rows only to find the plan's end (a move outside the plan outranks the other codes) and
 // its outputs are -1.  No atomics, no barriers; the outputs are a function of the inputs alone.
+//
+// fjsp_schedule_search runs hill climbing and tabu search over those two: one wavefront per env, all rounds in one launch,
+// built from the same device functions (its own head comment is at schedule_search_kernel; its barriers are those of a
+// one-wave workgroup around its LDS plan).
 #include <hip/hip_runtime.h>
 
 #include <string>
 
 #include "../../include/fjsp_amd.h"
 #include "fjsp_env_impl.h"
+#include "fjsp_gen_stream.h"
 #include "fjsp_launch.h"
 
 namespace {
@@ -86,118 +91,168 @@ __device__ __forceinline__ Row row_at(const int32_t *pl, int idx) { return Row{p
 
 extern __shared__ __attribute__((aligned(16))) uint32_t decode_lds[];
 
+// ---- the texts that schedule_decode_kernel, schedule_critical_kernel and schedule_search_kernel share: the instance as
+// they read it, a candidate's banked state, the index map of a move, the decode of a plan row by row, the forward and the
+// backward scan of a table with the move list.  Plans and tables come through accessors (index -> row), so that the same
+// text reads them from global memory (the first two kernels) and from LDS (the search); every function inlines, and the
+// pointers keep their address space.
+struct Shop {
+    const unsigned char *ir;
+    const uint2 *kinds;      // the instance's kind table
+    const uint16_t *p;
+    const int32_t *due;
+    int R, ops, M, MP, KP, JW, S;
+};
+__device__ __forceinline__ Shop shop_of(const DevBatch &b, const uint2 *kind_table, int inst, int JW) {
+    Shop sh;
+    sh.ir = b.inst + (size_t)inst * b.L.i_stride;
+    const InstHeader h = *reinterpret_cast<const InstHeader *>(sh.ir);
+    sh.MP = b.MP; sh.KP = b.KP; sh.JW = JW;
+    sh.M = h.M < b.MP ? h.M : b.MP;
+    sh.S = b.mord ? min(h.R >> 16, b.SP) : 1;
+    sh.kinds = kind_table + (size_t)inst * (size_t)(b.KP + 1);
+    sh.R = (int)sh.kinds[0].x; sh.ops = (int)sh.kinds[0].y;
+    sh.p = reinterpret_cast<const uint16_t *>(sh.ir + b.L.i_p);
+    sh.due = reinterpret_cast<const int32_t *>(sh.ir + b.L.i_due);
+    return sh;
+}
+
+// slot s of a workgroup of G candidates: ready[j] at ready[j * G], stage[j] at stage[(j >> 2) * 4 G + (j & 3)] (its words
+// at words[w * G]), free[m] at mfree[m * G]
+struct State { uint32_t *ready, *words, *mfree; uint8_t *stage; int G; };
+__device__ __forceinline__ State state_at(uint32_t *lds, int s, int G, int JW) {
+    return State{lds + s, lds + (size_t)JW * G + s, lds + (size_t)(JW + JW / 4) * G + s, reinterpret_cast<uint8_t *>(lds + (size_t)JW * G + s), G};
+}
+
+// A move checked against its plan (row: index -> Row, an end row past the plan).  kind drops to 0 for a swap within a job,
+// asked keeps it; rows pu and pv stand, pv first, behind row pw (a swap: pw = pu, pv = pu + 1).
+struct Move { int kind, asked, u, m_new, pu, pw, pv; bool bad; };
+__device__ __forceinline__ Move no_move() { return Move{0, 0, 0, 0, 0x7fffffff, 0, 0, false}; }
+template <class RowAt>
+__device__ __forceinline__ Move move_of(int kind, int u, int m_new, int cap, RowAt row) {
+    Move mv{kind, kind, u, m_new, 0x7fffffff, 0, 0, false};
+    if (kind == 1) {
+        mv.bad = u < 0 || u >= cap || is_end(row(u));
+    } else if (kind == 2) {
+        mv.bad = u < 0 || u >= cap - 1;
+        if (!mv.bad) {
+            const Row x = row(u), y = row(u + 1);
+            mv.bad = is_end(x) || is_end(y);
+            if (!mv.bad && x.r == y.r && x.n == y.n) mv.kind = 0;        // two rows of one job: nothing changes
+            if (!mv.bad && mv.kind == 2) { mv.pu = mv.pw = u; mv.pv = u + 1; }
+        }
+    } else if (kind == 4) {
+        const int dv = m_new & 0xFFFF, dw = m_new >> 16;
+        mv.bad = m_new < 0 || dv < 1 || dw >= dv || u < 0 || u >= cap - dv;
+        if (!mv.bad) mv.bad = is_end(row(u)) || is_end(row(u + dv));
+        if (!mv.bad) { mv.pu = u; mv.pw = u + dw; mv.pv = u + dv; }
+    } else if (kind != 0) {
+        mv.bad = true;
+    }
+    return mv;
+}
+// position t of the moved plan is row move_src(mv, t) of the plan
+__device__ __forceinline__ int move_src(const Move &mv, int t) {
+    return (t < mv.pu || t > mv.pv) ? t : (t < mv.pw ? t + 1 : (t == mv.pw ? mv.pv : (t == mv.pw + 1 ? mv.pu : t - 1)));
+}
+// a plan with rows behind its first -1 row can have let a move past the checks of move_of: L is the plan's length
+__device__ __forceinline__ bool move_past(const Move &mv, int L) {
+    return (mv.asked == 1 && mv.u >= L) || (mv.asked == 2 && mv.u + 1 >= L) || (mv.asked == 4 && mv.pv >= L);
+}
+
+// What a decoded row adds to its table: stage, operation type, times
+struct Step { int stg, k, begin, end; };
+
+// The decode of one plan under one move on the state `st`: jobs released at their order's arrival, machines free at 0,
+// then row by row.  Returns the status of the rows (0, 1, 2, 3), L = the plan's length whatever the status (a candidate
+// that fails a check keeps reading rows only to find the plan's end); sink(t, row, step) sees every decoded row.
+template <class RowAt, class Sink>
+__device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, const State &st, RowAt row, int cap, const Move &mv, Sink sink,
+                                           int &L, long long &makespan, long long &tard) {
+    const int G = st.G, JW = sh.JW, MP = sh.MP;
+    const int32_t *oarr = reinterpret_cast<const int32_t *>(sh.ir + b.L.i_oarr);
+    const uint16_t *ocnt = reinterpret_cast<const uint16_t *>(sh.ir + b.L.i_ocnt);
+    for (int w = 0; w < JW / 4; ++w) st.words[(size_t)w * G] = 0u;
+    for (int m = 0; m < MP; ++m) st.mfree[(size_t)m * G] = 0u;
+    for (int r = 0; r < sh.R; ++r) {
+        const uint32_t ka = sh.kinds[1 + r].x;
+        const int jbeg = (int)(ka & 0xFFFFu), cnt = (int)(ka >> 16);
+        int n = 0;
+        for (int so = 0; so < sh.S; ++so) {
+            const int arr = oarr[so];
+            for (int c = (int)ocnt[(size_t)so * b.RP + r]; c > 0 && n < cnt && jbeg + n < JW; --c, ++n) st.ready[(size_t)(jbeg + n) * G] = (uint32_t)arr;
+        }
+    }
+    int err = 0;
+    L = 0; makespan = 0; tard = 0;
+    Row nxt = row(move_src(mv, 0));
+    for (int t = 0; t < cap; ++t) {
+        Row x = nxt;
+        if (is_end(x)) break;
+        if (t + 1 < cap) nxt = row(move_src(mv, t + 1));                 // (the next row is requested before this one is worked on)
+        L = t + 1;
+        if (err) continue;                                               // only the plan's end is still of interest
+        if (mv.kind == 1 && t == mv.u) x.m = mv.m_new;
+        if (x.r < 0 || x.r >= sh.R) { err = 1; continue; }
+        const uint2 kd = sh.kinds[1 + x.r];
+        const int jbeg = (int)(kd.x & 0xFFFFu), cnt = (int)(kd.x >> 16), koff = (int)(kd.y & 0xFFFFu), Jr = (int)(kd.y >> 16);
+        if (x.n < 0 || x.n >= cnt || jbeg + x.n >= JW) { err = 1; continue; }
+        const int j = jbeg + x.n;
+        uint8_t *sj = st.stage + (size_t)(j >> 2) * 4 * G + (j & 3);
+        const int stg = (int)*sj;
+        if (stg >= Jr || koff + stg >= sh.KP) { err = 2; continue; }
+        if (x.m < 0 || x.m >= sh.M) { err = 3; continue; }
+        const int pv = (int)sh.p[(size_t)(koff + stg) * MP + x.m];
+        if (pv == 0) { err = 3; continue; }
+        const int begin = max((int)st.ready[(size_t)j * G], (int)st.mfree[(size_t)x.m * G]), end = begin + pv;
+        st.ready[(size_t)j * G] = (uint32_t)end;
+        st.mfree[(size_t)x.m * G] = (uint32_t)end;
+        *sj = (uint8_t)(stg + 1);
+        makespan = max(makespan, (long long)end);
+        if (stg == Jr - 1) tard += max(0LL, (long long)end - (long long)sh.due[j]);
+        sink(t, x, Step{stg, koff + stg, begin, end});
+    }
+    if (!err && L != sh.ops) err = 2;                                    // operations missing
+    return err;
+}
+
 __global__ __launch_bounds__(256) void schedule_decode_kernel(DevBatch b, DecodeArgs a) {
     const int s = (int)threadIdx.x;
     const long long g = (long long)blockIdx.x * a.G + s;
     if (s >= a.G || g >= a.total) return;
     const int env = (int)(g / a.n_cand), q = (int)(g - (long long)env * a.n_cand), inst = env % b.n_inst;
-    const int G = a.G, JW = a.JW, MP = b.MP, cap = a.cap;
-
-    const unsigned char *ir = b.inst + (size_t)inst * b.L.i_stride;
-    const InstHeader h = *reinterpret_cast<const InstHeader *>(ir);
-    const int M = h.M < MP ? h.M : MP;
-    const int S = b.mord ? min(h.R >> 16, b.SP) : 1;
-    const uint2 *kinds = a.kinds + (size_t)inst * (size_t)(b.KP + 1);
-    const int R = (int)kinds[0].x, ops = (int)kinds[0].y;
-    const uint16_t *p = reinterpret_cast<const uint16_t *>(ir + b.L.i_p);
-    const int32_t *due = reinterpret_cast<const int32_t *>(ir + b.L.i_due);
-
-    uint32_t *ready = decode_lds + s;                                    // ready[j]  at ready[j * G]
-    uint8_t *stage = reinterpret_cast<uint8_t *>(decode_lds + (size_t)JW * G + s);   // stage[j] at stage[(j >> 2) * 4 G + (j & 3)]
-    uint32_t *mfree = decode_lds + (size_t)(JW + JW / 4) * G + s;        // free[m]   at mfree[m * G]
+    const int cap = a.cap;
+    const Shop sh = shop_of(b, a.kinds, inst, a.JW);
+    const State st = state_at(decode_lds, s, a.G, a.JW);
 
     // ---- the move, checked against the plan before anything is decoded
     const int32_t *pl = a.plan + ((size_t)env * a.q_plans + (a.q_plans == 1 ? 0 : q)) * (size_t)cap * 3;
-    int kind = 0, asked = 0, u = 0, m_new = 0;     // asked: the move's kind as given (kind drops to 0 for a swap within a job)
-    int pu = 0x7fffffff, pw = 0, pv = 0;           // rows pu and pv stand, pv first, behind row pw (a swap: pw = pu, pv = pu + 1)
-    bool bad_move = false;
+    auto row = [&](int idx) { return row_at(pl, idx); };
+    Move mv = no_move();
     if (a.moves) {
-        const int32_t *mv = a.moves + (size_t)g * 3;
-        kind = asked = mv[0]; u = mv[1]; m_new = mv[2];
-        if (kind == 1) {
-            bad_move = u < 0 || u >= cap || is_end(row_at(pl, u));
-        } else if (kind == 2) {
-            bad_move = u < 0 || u >= cap - 1;
-            if (!bad_move) {
-                const Row x = row_at(pl, u), y = row_at(pl, u + 1);
-                bad_move = is_end(x) || is_end(y);
-                if (!bad_move && x.r == y.r && x.n == y.n) kind = 0;     // two rows of one job: nothing changes
-                if (!bad_move && kind == 2) { pu = pw = u; pv = u + 1; }
-            }
-        } else if (kind == 4) {
-            const int dv = m_new & 0xFFFF, dw = m_new >> 16;
-            bad_move = m_new < 0 || dv < 1 || dw >= dv || u < 0 || u >= cap - dv;
-            if (!bad_move) bad_move = is_end(row_at(pl, u)) || is_end(row_at(pl, u + dv));
-            if (!bad_move) { pu = u; pw = u + dw; pv = u + dv; }
-        } else if (kind != 0) {
-            bad_move = true;
-        }
+        const int32_t *m3 = a.moves + (size_t)g * 3;
+        mv = move_of(m3[0], m3[1], m3[2], cap, row);
     }
 
     int err = 0, L = 0;
     long long makespan = 0, tard = 0;
     int32_t *tab = a.table ? a.table + (size_t)g * (size_t)cap * 6 : nullptr;
-    if (!bad_move) {
-        // ---- the candidate's state: jobs released at their order's arrival, machines free at 0
-        const int32_t *oarr = reinterpret_cast<const int32_t *>(ir + b.L.i_oarr);
-        const uint16_t *ocnt = reinterpret_cast<const uint16_t *>(ir + b.L.i_ocnt);
-        for (int w = 0; w < JW / 4; ++w) decode_lds[(size_t)(JW + w) * G + s] = 0u;
-        for (int m = 0; m < MP; ++m) mfree[(size_t)m * G] = 0u;
-        for (int r = 0; r < R; ++r) {
-            const uint32_t ka = kinds[1 + r].x;
-            const int jbeg = (int)(ka & 0xFFFFu), cnt = (int)(ka >> 16);
-            int n = 0;
-            for (int so = 0; so < S; ++so) {
-                const int arr = oarr[so];
-                for (int c = (int)ocnt[(size_t)so * b.RP + r]; c > 0 && n < cnt && jbeg + n < JW; --c, ++n) ready[(size_t)(jbeg + n) * G] = (uint32_t)arr;
-            }
-        }
-
-        // ---- row by row; position t of the moved plan is row src(t) of the plan
-        auto src = [&](int t) { return (t < pu || t > pv) ? t : (t < pw ? t + 1 : (t == pw ? pv : (t == pw + 1 ? pu : t - 1))); };
-        Row nxt = row_at(pl, src(0));
-        for (int t = 0; t < cap; ++t) {
-            Row x = nxt;
-            if (is_end(x)) break;
-            if (t + 1 < cap) nxt = row_at(pl, src(t + 1));
-            L = t + 1;
-            if (err) continue;                                           // only the plan's end is still of interest
-            if (kind == 1 && t == u) x.m = m_new;
-            if (x.r < 0 || x.r >= R) { err = 1; continue; }
-            const uint2 kd = kinds[1 + x.r];
-            const int jbeg = (int)(kd.x & 0xFFFFu), cnt = (int)(kd.x >> 16), koff = (int)(kd.y & 0xFFFFu), Jr = (int)(kd.y >> 16);
-            if (x.n < 0 || x.n >= cnt || jbeg + x.n >= JW) { err = 1; continue; }
-            const int j = jbeg + x.n;
-            uint8_t *sj = stage + (size_t)(j >> 2) * 4 * G + (j & 3);
-            const int stg = (int)*sj;
-            if (stg >= Jr || koff + stg >= b.KP) { err = 2; continue; }
-            if (x.m < 0 || x.m >= M) { err = 3; continue; }
-            const int pv = (int)p[(size_t)(koff + stg) * MP + x.m];
-            if (pv == 0) { err = 3; continue; }
-            const int begin = max((int)ready[(size_t)j * G], (int)mfree[(size_t)x.m * G]), end = begin + pv;
-            ready[(size_t)j * G] = (uint32_t)end;
-            mfree[(size_t)x.m * G] = (uint32_t)end;
-            *sj = (uint8_t)(stg + 1);
-            makespan = max(makespan, (long long)end);
-            if (stg == Jr - 1) tard += max(0LL, (long long)end - (long long)due[j]);
+    if (!mv.bad) {
+        err = decode_plan(b, sh, st, row, cap, mv, [&](int t, const Row &x, const Step &d) {
             if (tab) {
                 int32_t *o = tab + (size_t)t * 6;
-                o[0] = x.r; o[1] = stg; o[2] = x.n; o[3] = x.m; o[4] = begin; o[5] = end;
+                o[0] = x.r; o[1] = d.stg; o[2] = x.n; o[3] = x.m; o[4] = d.begin; o[5] = d.end;
             }
-        }
-        if (!err && L != ops) err = 2;                                   // operations missing
-        // a plan with rows behind its first -1 row can have let a move past the checks above
-        if (asked == 1 && u >= L) bad_move = true;
-        if (asked == 2 && u + 1 >= L) bad_move = true;
-        if (asked == 4 && pv >= L) bad_move = true;
+        }, L, makespan, tard);
+        if (move_past(mv, L)) mv.bad = true;
     }
-    const int st = bad_move ? 4 : err;
-    a.status[g] = st;
-    a.objective[2 * g] = st ? -1 : makespan;
-    a.objective[2 * g + 1] = st ? -1 : tard;
-    if (a.len) a.len[g] = st ? 0 : L;
+    const int stt = mv.bad ? 4 : err;
+    a.status[g] = stt;
+    a.objective[2 * g] = stt ? -1 : makespan;
+    a.objective[2 * g + 1] = stt ? -1 : tard;
+    if (a.len) a.len[g] = stt ? 0 : L;
     if (tab) {
-        for (int t = st ? 0 : L; t < cap; ++t) {
+        for (int t = stt ? 0 : L; t < cap; ++t) {
             int32_t *o = tab + (size_t)t * 6;
             o[0] = -1; o[1] = -1; o[2] = -1; o[3] = -1; o[4] = -1; o[5] = -1;
         }
@@ -224,102 +279,118 @@ __device__ __forceinline__ TRow trow_at(const int32_t *tb, int t) {
     const int32_t *o = tb + (size_t)t * 6;
     return TRow{o[0], o[1], o[2], o[3], o[4], o[5]};
 }
+__device__ __forceinline__ TRow trow_at7(const int32_t *tb, int t) {       // the search's rows of seven words, the identity last
+    const int32_t *o = tb + (size_t)t * 7;
+    return TRow{o[0], o[1], o[2], o[3], o[4], o[5]};
+}
+
+// forward over a table (trow: index -> TRow): its end L, every index it supplies checked, the makespan C and the first row
+// e0 that ends there.  Returns the status (0, 1 a row fails a check, 2 the table is empty).
+template <class TRowAt>
+__device__ __forceinline__ int critical_forward(const Shop &sh, TRowAt trow, int cap, int &L, int &C, int &e0) {
+    int st = 0;
+    L = 0; C = 0; e0 = -1;
+    TRow nxt = trow(0);                                                  // (the next row is requested before this one is worked on)
+    for (int t = 0; t < cap; ++t) {
+        const TRow x = nxt;
+        if ((x.r & x.stage & x.n & x.m & x.begin & x.end) == -1) break;
+        if (t + 1 < cap) nxt = trow(t + 1);
+        L = t + 1;
+        bool ok = x.r >= 0 && x.r < sh.R;
+        if (ok) {
+            const uint2 kd = sh.kinds[1 + x.r];
+            const int jbeg = (int)(kd.x & 0xFFFFu), cnt = (int)(kd.x >> 16), koff = (int)(kd.y & 0xFFFFu), Jr = (int)(kd.y >> 16);
+            ok = x.n >= 0 && x.n < cnt && jbeg + x.n < sh.JW && x.m >= 0 && x.m < sh.M && x.stage >= 0 && x.stage < Jr &&
+                 koff + x.stage < sh.KP && x.begin >= 0 && x.begin < x.end;
+        }
+        if (!ok) { st = 1; break; }
+        if (x.end > C) { C = x.end; e0 = t; }
+    }
+    if (!st && L == 0) st = 2;
+    return st;
+}
+
+// What the backward scan writes: tail[L] (nullable), flags[L], path[<= L], mv[max_moves][3] (null with max_moves = 0)
+struct CritOut { int32_t *tail; uint8_t *flags; int32_t *path, *mv; int max_moves; };
+
+// backward over a checked table: tail + duration of the latest row seen, per job (jtail[j * G]) and per machine (mtail[m * G]),
+// as decode keeps ready / free; tails, flags and one critical path in the same pass; then the path's neighbourhood, its
+// machine arcs as pair moves and its operations on their other machines.
+template <class TRowAt>
+__device__ __forceinline__ void critical_backward(const Shop &sh, TRowAt trow, int L, int C, int e0, uint32_t *jtail, uint32_t *mtail, int G,
+                                                  const CritOut o, int &plen_out, int &n_moves_out, int &skipped_out) {
+    int plen = 0, n_moves = 0, skipped = 0;
+    for (int j = 0; j < sh.JW; ++j) jtail[(size_t)j * G] = 0u;
+    for (int m = 0; m < sh.MP; ++m) mtail[(size_t)m * G] = 0u;
+    int curj = 0, curm = 0, curb = 0;                                    // the path's current row: job word, machine, begin
+    bool needj = false, needm = false;                                   // its job / machine predecessor is still to come
+    TRow nxt = trow(L - 1);
+    for (int t = L - 1; t >= 0; --t) {
+        const TRow x = nxt;
+        if (t > 0) nxt = trow(t - 1);
+        const int j = (int)(sh.kinds[1 + x.r].x & 0xFFFFu) + x.n;
+        const uint32_t tj = jtail[(size_t)j * G], tm = mtail[(size_t)x.m * G], tl = tj > tm ? tj : tm;
+        jtail[(size_t)j * G] = mtail[(size_t)x.m * G] = tl + (uint32_t)(x.end - x.begin);
+        uint32_t f = ((uint32_t)x.end + tl == (uint32_t)C) ? 1u : 0u;
+        bool on = t == e0;
+        if (!on && (needj || needm)) {
+            const bool isj = needj && j == curj, ism = needm && x.m == curm;
+            if (isj || ism) {
+                if (x.end == curb) { on = true; if (!isj) f |= 4u; }
+                else { if (isj) needj = false; if (ism) needm = false; }
+            }
+        }
+        if (on) { f |= 2u; o.path[plen++] = t; curj = j; curm = x.m; curb = x.begin; needj = needm = true; }
+        if (o.tail) o.tail[t] = (int32_t)tl;
+        o.flags[t] = (uint8_t)f;
+    }
+
+    auto emit = [&](int kind, int u, int third) {
+        if (n_moves < o.max_moves) { int32_t *e = o.mv + (size_t)n_moves * 3; e[0] = kind; e[1] = u; e[2] = third; }
+        ++n_moves;
+    };
+    for (int i = 0; i + 1 < plen; ++i) {
+        const int u = o.path[i + 1], v = o.path[i];
+        if (!(o.flags[u] & 4u)) continue;
+        const TRow a = trow(u), bb = trow(v);
+        int w = u, first = v;                                            // last row of b's job, first row of a's job in (u, v)
+        for (int t = v - 1; t > u; --t) {
+            const TRow x = trow(t);
+            if (w == u && x.r == bb.r && x.n == bb.n) w = t;
+            if (x.r == a.r && x.n == a.n) first = t;
+        }
+        if (w < first && w - u <= 32767) emit(4, u, (v - u) | ((w - u) << 16));    // (the field stays a non-negative int)
+        else ++skipped;
+    }
+    for (int i = 0; i < plen; ++i) {
+        const int t = o.path[i];
+        const TRow x = trow(t);
+        const uint16_t *pk = sh.p + (size_t)((int)(sh.kinds[1 + x.r].y & 0xFFFFu) + x.stage) * sh.MP;
+        for (int m = 0; m < sh.M; ++m)
+            if (m != x.m && pk[m] != 0) emit(1, t, m);
+    }
+    plen_out = plen; n_moves_out = n_moves; skipped_out = skipped;
+}
 
 __global__ __launch_bounds__(256) void schedule_critical_kernel(DevBatch b, CriticalArgs a) {
     const int s = (int)threadIdx.x;
     const long long g = (long long)blockIdx.x * a.G + s;
     if (s >= a.G || g >= a.total) return;
     const int env = (int)(g / a.n_cand), inst = env % b.n_inst;
-    const int G = a.G, JW = a.JW, MP = b.MP, cap = a.cap;
-
-    const unsigned char *ir = b.inst + (size_t)inst * b.L.i_stride;
-    const InstHeader h = *reinterpret_cast<const InstHeader *>(ir);
-    const int M = h.M < MP ? h.M : MP;
-    const uint2 *kinds = a.kinds + (size_t)inst * (size_t)(b.KP + 1);
-    const int R = (int)kinds[0].x;
-    const uint16_t *p = reinterpret_cast<const uint16_t *>(ir + b.L.i_p);
+    const int G = a.G, cap = a.cap;
+    const Shop sh = shop_of(b, a.kinds, inst, a.JW);
 
     const int32_t *tb = a.table + (size_t)g * (size_t)cap * 6;
+    auto trow = [&](int t) { return trow_at(tb, t); };
     int32_t *tail = a.tail + (size_t)g * cap, *path = a.path + (size_t)g * cap;
     uint8_t *flags = a.flags + (size_t)g * cap;
     int32_t *mv = a.moves ? a.moves + (size_t)g * (size_t)a.max_moves * 3 : nullptr;
 
-    // ---- forward: the table's end, every index it supplies checked, the makespan and the first row that ends there
-    int st = 0, L = 0, C = 0, e0 = -1;
-    TRow nxt = trow_at(tb, 0);                                           // (the next row is requested before this one is worked on)
-    for (int t = 0; t < cap; ++t) {
-        const TRow x = nxt;
-        if ((x.r & x.stage & x.n & x.m & x.begin & x.end) == -1) break;
-        if (t + 1 < cap) nxt = trow_at(tb, t + 1);
-        L = t + 1;
-        bool ok = x.r >= 0 && x.r < R;
-        if (ok) {
-            const uint2 kd = kinds[1 + x.r];
-            const int jbeg = (int)(kd.x & 0xFFFFu), cnt = (int)(kd.x >> 16), koff = (int)(kd.y & 0xFFFFu), Jr = (int)(kd.y >> 16);
-            ok = x.n >= 0 && x.n < cnt && jbeg + x.n < JW && x.m >= 0 && x.m < M && x.stage >= 0 && x.stage < Jr &&
-                 koff + x.stage < b.KP && x.begin >= 0 && x.begin < x.end;
-        }
-        if (!ok) { st = 1; break; }
-        if (x.end > C) { C = x.end; e0 = t; }
-    }
-    if (!st && L == 0) st = 2;
-
-    int plen = 0, n_moves = 0, skipped = 0;
-    if (!st) {
-        // ---- backward: tail + duration of the latest row seen, per job and per machine, as decode keeps ready / free
-        uint32_t *jtail = decode_lds + s;                                // of job j     at jtail[j * G]
-        uint32_t *mtail = decode_lds + (size_t)JW * G + s;               // of machine m at mtail[m * G]
-        for (int j = 0; j < JW; ++j) jtail[(size_t)j * G] = 0u;
-        for (int m = 0; m < MP; ++m) mtail[(size_t)m * G] = 0u;
-        int curj = 0, curm = 0, curb = 0;                                // the path's current row: job word, machine, begin
-        bool needj = false, needm = false;                               // its job / machine predecessor is still to come
-        nxt = trow_at(tb, L - 1);
-        for (int t = L - 1; t >= 0; --t) {
-            const TRow x = nxt;
-            if (t > 0) nxt = trow_at(tb, t - 1);
-            const int j = (int)(kinds[1 + x.r].x & 0xFFFFu) + x.n;
-            const uint32_t tj = jtail[(size_t)j * G], tm = mtail[(size_t)x.m * G], tl = tj > tm ? tj : tm;
-            jtail[(size_t)j * G] = mtail[(size_t)x.m * G] = tl + (uint32_t)(x.end - x.begin);
-            uint32_t f = ((uint32_t)x.end + tl == (uint32_t)C) ? 1u : 0u;
-            bool on = t == e0;
-            if (!on && (needj || needm)) {
-                const bool isj = needj && j == curj, ism = needm && x.m == curm;
-                if (isj || ism) {
-                    if (x.end == curb) { on = true; if (!isj) f |= 4u; }
-                    else { if (isj) needj = false; if (ism) needm = false; }
-                }
-            }
-            if (on) { f |= 2u; path[plen++] = t; curj = j; curm = x.m; curb = x.begin; needj = needm = true; }
-            tail[t] = (int32_t)tl;
-            flags[t] = (uint8_t)f;
-        }
-
-        // ---- the path's neighbourhood: its machine arcs as pair moves, then its operations on their other machines
-        auto emit = [&](int kind, int u, int third) {
-            if (n_moves < a.max_moves) { int32_t *o = mv + (size_t)n_moves * 3; o[0] = kind; o[1] = u; o[2] = third; }
-            ++n_moves;
-        };
-        for (int i = 0; i + 1 < plen; ++i) {
-            const int u = path[i + 1], v = path[i];
-            if (!(flags[u] & 4u)) continue;
-            const int ra = tb[(size_t)u * 6], na = tb[(size_t)u * 6 + 2], rb = tb[(size_t)v * 6], nb = tb[(size_t)v * 6 + 2];
-            int w = u, first = v;                                        // last row of b's job, first row of a's job in (u, v)
-            for (int t = v - 1; t > u; --t) {
-                const int r = tb[(size_t)t * 6], n = tb[(size_t)t * 6 + 2];
-                if (w == u && r == rb && n == nb) w = t;
-                if (r == ra && n == na) first = t;
-            }
-            if (w < first && w - u <= 32767) emit(4, u, (v - u) | ((w - u) << 16));    // (the field stays a non-negative int)
-            else ++skipped;
-        }
-        for (int i = 0; i < plen; ++i) {
-            const int t = path[i];
-            const TRow x = trow_at(tb, t);
-            const uint16_t *pk = p + (size_t)((int)(kinds[1 + x.r].y & 0xFFFFu) + x.stage) * MP;
-            for (int m = 0; m < M; ++m)
-                if (m != x.m && pk[m] != 0) emit(1, t, m);
-        }
-    }
+    int L = 0, C = 0, e0 = -1, plen = 0, n_moves = 0, skipped = 0;
+    const int st = critical_forward(sh, trow, cap, L, C, e0);
+    if (!st)
+        critical_backward(sh, trow, L, C, e0, decode_lds + s, decode_lds + (size_t)a.JW * G + s, G, CritOut{tail, flags, path, mv, a.max_moves},
+                          plen, n_moves, skipped);
     for (int t = st ? 0 : L; t < cap; ++t) { tail[t] = -1; flags[t] = 0; }
     for (int t = plen; t < cap; ++t) path[t] = -1;
     for (int i = n_moves < a.max_moves ? n_moves : a.max_moves; i < a.max_moves; ++i) { mv[(size_t)i * 3] = 0; mv[(size_t)i * 3 + 1] = 0; mv[(size_t)i * 3 + 2] = 0; }
@@ -329,6 +400,217 @@ __global__ __launch_bounds__(256) void schedule_critical_kernel(DevBatch b, Crit
     a.n_moves[g] = n_moves;
     a.skipped[g] = skipped;
 }
+
+// ---- fjsp_schedule_search: hill climbing and tabu search, every round of every env in ONE launch.  One 64-lane workgroup
+// owns one env, lane q decodes candidate q of a round on its own banked state (G = 64, the decoder's layout and text).
+// Beside the states the env keeps in LDS: its plan rows (r, n, m, operation type, identity), the tabu list until[identity]
+// and, for the critical neighbourhoods, the current plan's table with the identity as a seventh word, the permutation
+// inv[] that puts it into begin order (the table itself is not moved: the scans read row inv[t]), the path, its flags and
+// the move list.  A round touches global memory for the instance's tables (kind table, p, due) and its own outputs only.
+//   critical modes, per round: every lane decodes the current plan (lane 0 keeps the table); rank by (begin, index) across
+//   the lanes -> inv; the rows are rebuilt in begin order from the table; lane 0 runs critical_forward / critical_backward.
+//   every mode: the lanes draw their moves (splitmix64 of the global env id, include/fjsp_amd.h), decode them with the move
+//   applied while reading, a butterfly over the wave finds the least (objective, q), and the wave applies the move taken: a
+//   reassignment is one store, a swap and a pair move rotate the window [pu, pv] of rows, 64 rows to a step.
+struct SearchArgs {
+    const int32_t *plan;     // i32[N][cap][3]
+    int32_t *plan_out;       // i32[N][cap][3]
+    int64_t *objective;      // i64[N][2]
+    int64_t *history;        // i64[rounds + 1][N]
+    int32_t *accepted, *status;   // i32[N]
+    int32_t *trace;          // i32[rounds][N][3], nullable
+    const uint2 *kinds;      // [n_inst][KP + 1]
+    unsigned long long seed; // of the search stream (the caller's seed ^ FJSP_SEARCH_STREAM)
+    long long first_env;
+    int rounds, n_cand, col, nbh, accept, tenure, cap, JW;
+};
+
+constexpr int kSearchMoves = 128;                                        // entries of the critical move list a round draws from
+// words of LDS behind the 64 states: rows 5, until 1, table 7, inv 1, path 1 per plan row, the flag bytes, the move list
+__host__ __device__ inline size_t search_words(int JW, int MP, int cap) {
+    return (size_t)state_words(JW, MP) * 64 + (size_t)cap * 15 + (size_t)(cap + 3) / 4 + (size_t)kSearchMoves * 3 + 4;
+}
+
+__device__ __forceinline__ uint32_t search_pick(uint64_t d, uint32_t n) { return (uint32_t)(((d >> 32) * (uint64_t)n) >> 32); }
+
+__global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchArgs a) {
+    const int q = (int)threadIdx.x, env = (int)blockIdx.x, inst = env % b.n_inst;
+    const int cap = a.cap, Q = a.n_cand, N = b.N;
+    const Shop sh = shop_of(b, a.kinds, inst, a.JW);
+    const State st = state_at(decode_lds, q, 64, a.JW);
+    int32_t *rows = reinterpret_cast<int32_t *>(decode_lds + (size_t)state_words(a.JW, b.MP) * 64);     // [cap][5]
+    int32_t *until = rows + (size_t)cap * 5, *tab = until + cap, *inv = tab + (size_t)cap * 7, *path = inv + cap;
+    int32_t *mvl = path + cap, *shared = mvl + kSearchMoves * 3;
+    uint8_t *flags = reinterpret_cast<uint8_t *>(shared + 4);
+    const int32_t *pl = a.plan + (size_t)env * cap * 3;
+    int32_t *po = a.plan_out + (size_t)env * cap * 3;
+
+    // ---- the input plan: copied through, decoded by every lane (one address to the wave), kept by lane 0
+    for (int i = q; i < cap * 3; i += 64) po[i] = pl[i];
+    int L = 0;
+    long long cur_mk = 0, cur_td = 0;
+    const int st0 = decode_plan(b, sh, st, [&](int idx) { return row_at(pl, idx); }, cap, no_move(), [&](int t, const Row &x, const Step &d) {
+        if (q == 0) { int32_t *o = rows + (size_t)t * 5; o[0] = x.r; o[1] = x.n; o[2] = x.m; o[3] = d.k; o[4] = t; until[t] = 0; }
+    }, L, cur_mk, cur_td);
+    if (st0 != 0) {                                                      // (the same in every lane)
+        if (q == 0) { a.status[env] = st0; a.accepted[env] = 0; a.objective[2 * (size_t)env] = -1; a.objective[2 * (size_t)env + 1] = -1; }
+        for (int t = q; t <= a.rounds; t += 64) a.history[(size_t)t * N + env] = -1;
+        if (a.trace)
+            for (int i = q; i < a.rounds * 3; i += 64) a.trace[((size_t)(i / 3) * N + env) * 3 + i % 3] = 0;
+        return;
+    }
+    __syncthreads();
+    long long best_mk = cur_mk, best_td = cur_td;                        // of the plan in plan_out (tabu)
+    int taken = 0, n_list = 0;
+    if (q == 0) a.history[env] = a.col ? cur_td : cur_mk;
+    const uint64_t sg = gen::draw(a.seed, (uint32_t)(a.first_env + env));
+    auto lrow = [&](int idx) { const int32_t *o = rows + (size_t)idx * 5; return idx < L ? Row{o[0], o[1], o[2]} : Row{-1, -1, -1}; };
+    auto write_out = [&]() {                                             // the current plan -> plan_out
+        for (int t = q; t < cap; t += 64) {
+            const Row x = lrow(t);
+            po[3 * t] = x.r; po[3 * t + 1] = x.n; po[3 * t + 2] = x.m;
+        }
+    };
+
+    for (int t = 0; t < a.rounds; ++t) {
+        if (a.nbh != 0) {
+            // ---- the current plan's table, put into begin order, and the moves of its critical path
+            long long mk, td;
+            int len;
+            decode_plan(b, sh, st, lrow, cap, no_move(), [&](int i, const Row &x, const Step &d) {
+                if (q == 0) { int32_t *o = tab + (size_t)i * 7; o[0] = x.r; o[1] = d.stg; o[2] = x.n; o[3] = x.m; o[4] = d.begin; o[5] = d.end; o[6] = rows[(size_t)i * 5 + 4]; }
+            }, len, mk, td);
+            __syncthreads();
+            for (int s = q; s < L; s += 64) {
+                const int bs = tab[(size_t)s * 7 + 4];
+                int rank = 0;
+                for (int i = 0; i < L; ++i) { const int bi = tab[(size_t)i * 7 + 4]; rank += (bi < bs || (bi == bs && i < s)) ? 1 : 0; }
+                inv[rank] = s;
+            }
+            __syncthreads();
+            for (int s = q; s < L; s += 64) {
+                const int32_t *x = tab + (size_t)inv[s] * 7;
+                int32_t *o = rows + (size_t)s * 5;
+                o[0] = x[0]; o[1] = x[2]; o[2] = x[3]; o[3] = (int)(sh.kinds[1 + x[0]].y & 0xFFFFu) + x[1]; o[4] = x[6];
+            }
+            if (q == 0) {
+                auto trow = [&](int i) { return i < L ? trow_at7(tab, inv[i]) : TRow{-1, -1, -1, -1, -1, -1}; };
+                int Lt = 0, C = 0, e0 = -1, plen = 0, n_moves = 0, skipped = 0;
+                if (critical_forward(sh, trow, cap, Lt, C, e0) == 0)
+                    critical_backward(sh, trow, Lt, C, e0, decode_lds, decode_lds + (size_t)a.JW * 64, 64, CritOut{nullptr, flags, path, mvl, kSearchMoves},
+                                      plen, n_moves, skipped);
+                shared[0] = n_moves < kSearchMoves ? n_moves : kSearchMoves;
+            }
+            __syncthreads();
+            n_list = shared[0];
+        }
+
+        // ---- candidate q of the round: its draws, its move, its decode
+        const uint32_t d0 = 3u * ((uint32_t)t * (uint32_t)Q + (uint32_t)q);
+        const bool from_list = a.nbh == 1 || (a.nbh == 2 && q < Q / 2);
+        bool masked = q >= Q || L == 0;
+        int kind = 0, u = 0, third = 0;
+        if (!masked) {
+            if (from_list) {
+                if (n_list == 0) masked = true;
+                else { const int32_t *e = mvl + 3 * (size_t)search_pick(gen::draw(sg, d0 + 2u), (uint32_t)n_list); kind = e[0]; u = e[1]; third = e[2]; }
+            } else if ((q & 1) == 0) {
+                kind = 1; u = (int)search_pick(gen::draw(sg, d0), (uint32_t)L);
+                const uint16_t *pk = sh.p + (size_t)rows[(size_t)u * 5 + 3] * sh.MP;
+                int n_e = 0;
+                for (int m = 0; m < sh.M; ++m) n_e += pk[m] != 0 ? 1 : 0;
+                if (n_e == 0) masked = true;
+                else {
+                    int left = (int)search_pick(gen::draw(sg, d0 + 1u), (uint32_t)n_e);
+                    for (int m = 0; m < sh.M; ++m)
+                        if (pk[m] != 0 && left-- == 0) { third = m; break; }
+                }
+            } else {
+                kind = 2; u = (int)search_pick(gen::draw(sg, d0), (uint32_t)(L > 1 ? L - 1 : 1));
+            }
+        }
+        long long mk = 0, td = 0, key = 0x7fffffffffffffffLL;
+        Move mv = no_move();
+        int id_a = 0, id_b = -1;                                         // identities of the rows the move moves
+        if (!masked) {
+            mv = move_of(kind, u, third, cap, lrow);
+            int len = 0;
+            int err = 4;
+            if (!mv.bad) {
+                err = decode_plan(b, sh, st, lrow, cap, mv, [](int, const Row &, const Step &) {}, len, mk, td);
+                if (move_past(mv, len)) err = 4;
+            }
+            bool ok = err == 0;
+            if (ok && a.accept == 2) {
+                id_a = rows[(size_t)u * 5 + 4];
+                if (kind != 1) id_b = rows[(size_t)(kind == 2 ? u + 1 : mv.pv) * 5 + 4];
+                const bool same = kind == 1 ? third == rows[(size_t)u * 5 + 2] : mv.kind == 0;
+                const bool tabu = until[id_a] > t || (id_b >= 0 && until[id_b] > t);
+                ok = !same && (!tabu || (a.col ? td : mk) < (a.col ? best_td : best_mk));
+            }
+            if (ok) key = a.col ? td : mk;
+        }
+        // ---- the least (objective, q) of the wave
+        int wq = q;
+        for (int off = 32; off > 0; off >>= 1) {
+            const long long ok2 = __shfl_xor(key, off);
+            const int oq = __shfl_xor(wq, off);
+            if (ok2 < key || (ok2 == key && oq < wq)) { key = ok2; wq = oq; }
+        }
+        const long long cur = a.col ? cur_td : cur_mk;
+        const bool take = key != 0x7fffffffffffffffLL && (a.accept == 2 || key < cur || (key == cur && a.accept == 1));
+        int t_kind = 0, t_u = 0, t_third = 0;
+        if (take) {                                                      // (the same in every lane)
+            t_kind = __shfl(kind, wq); t_u = __shfl(u, wq); t_third = __shfl(third, wq);
+            const int e_kind = __shfl(mv.kind, wq), pu = __shfl(mv.pu, wq), pw = __shfl(mv.pw, wq), pv = __shfl(mv.pv, wq);
+            cur_mk = __shfl(mk, wq); cur_td = __shfl(td, wq);
+            const int w_a = __shfl(id_a, wq), w_b = __shfl(id_b, wq);
+            __syncthreads();                                             // every lane has read the rows of its candidate
+            if (a.accept == 2 && q == 0) {
+                const long long rel = (long long)t + 1 + a.tenure;
+                const int32_t v = (int32_t)(rel < 0x7fffffffLL ? rel : 0x7fffffffLL);
+                until[w_a] = v;
+                if (w_b >= 0) until[w_b] = v;
+            }
+            if (e_kind == 1) {
+                if (q == 0) rows[(size_t)t_u * 5 + 2] = t_third;
+            } else if (e_kind != 0) {
+                // rows pu + 1 .. pw one place down, rows pw + 1 .. pv - 1 one place up, old rows pv and pu between them
+                int ra[5], rb[5], x[5];
+                for (int c = 0; c < 5; ++c) { ra[c] = rows[(size_t)pu * 5 + c]; rb[c] = rows[(size_t)pv * 5 + c]; }
+                __syncthreads();
+                for (int base = pu; base < pw; base += 64) {
+                    const int i = base + q;
+                    if (i < pw) for (int c = 0; c < 5; ++c) x[c] = rows[(size_t)(i + 1) * 5 + c];
+                    __syncthreads();
+                    if (i < pw) for (int c = 0; c < 5; ++c) rows[(size_t)i * 5 + c] = x[c];
+                    __syncthreads();
+                }
+                for (int top = pv; top >= pw + 2; top -= 64) {
+                    const int i = top - q;
+                    if (i >= pw + 2) for (int c = 0; c < 5; ++c) x[c] = rows[(size_t)(i - 1) * 5 + c];
+                    __syncthreads();
+                    if (i >= pw + 2) for (int c = 0; c < 5; ++c) rows[(size_t)i * 5 + c] = x[c];
+                    __syncthreads();
+                }
+                if (q == 0) for (int c = 0; c < 5; ++c) { rows[(size_t)pw * 5 + c] = rb[c]; rows[(size_t)(pw + 1) * 5 + c] = ra[c]; }
+            }
+            ++taken;
+            __syncthreads();
+            if (a.accept == 2 && (a.col ? cur_td < best_td : cur_mk < best_mk)) { best_mk = cur_mk; best_td = cur_td; write_out(); }
+        }
+        if (q == 0) {
+            a.history[(size_t)(t + 1) * N + env] = a.col ? cur_td : cur_mk;
+            if (a.trace) { int32_t *o = a.trace + ((size_t)t * N + env) * 3; o[0] = t_kind; o[1] = t_u; o[2] = t_third; }
+        }
+    }
+    if (a.accept != 2) {
+        best_mk = cur_mk; best_td = cur_td;
+        if (a.rounds > 0) write_out();
+    }
+    if (q == 0) { a.status[env] = 0; a.accepted[env] = taken; a.objective[2 * (size_t)env] = best_mk; a.objective[2 * (size_t)env + 1] = best_td; }
+}
+
 
 // candidates per workgroup, 0 = the state of 32 candidates does not fit the LDS of a CU
 int decode_group(const DevBatch &b) {
@@ -408,6 +690,59 @@ extern "C" int fjsp_schedule_critical(fjsp_env *e, const int32_t *d_table, int32
     const size_t lds = (size_t)(b.jcap + b.MP) * 4 * (size_t)G;
     if (launch(schedule_critical_kernel, dim3((unsigned)((total + G - 1) / G)), dim3((unsigned)(G < 64 ? 64 : G)), lds, st, b, a) != 0) {
         set_error("schedule_critical_kernel launch failed"); return FJSP_E_HIP;
+    }
+    return FJSP_OK;
+}
+
+extern "C" int fjsp_schedule_search_lds(const fjsp_env *e) {
+    if (!e || e->b.variant == FJSP_VARIANT_MO_DFJSP || e->ops_max <= 0) return 0;
+    const size_t bytes = search_words(e->b.jcap, e->b.MP, e->ops_max) * 4;
+    return bytes <= kLdsCu ? (int)bytes : 0;
+}
+
+extern "C" int fjsp_search_draws(uint64_t seed, int64_t env, uint32_t first, int32_t n, uint64_t *h_out) {
+    if (n < 0 || (n > 0 && !h_out)) { set_error("fjsp_search_draws: needs n >= 0 and an output array"); return FJSP_E_ARG; }
+    const uint64_t sg = gen::draw(seed ^ FJSP_SEARCH_STREAM, (uint32_t)env);
+    for (int32_t i = 0; i < n; ++i) h_out[i] = gen::draw(sg, first + (uint32_t)i);
+    return FJSP_OK;
+}
+
+extern "C" int fjsp_schedule_search(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, int32_t objective, int32_t neighbourhood,
+                                    int32_t accept, int32_t tenure, uint64_t seed, int64_t first_env, int32_t *d_plan_out, int64_t *d_objective,
+                                    int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream) {
+    if (!e || !d_plan || !d_plan_out || !d_objective || !d_history || !d_accepted || !d_status) {
+        set_error("fjsp_schedule_search: null env, plan or output pointer"); return FJSP_E_ARG;
+    }
+    if (e->b.variant == FJSP_VARIANT_MO_DFJSP) {
+        set_error("fjsp_schedule_search: MO_DFJSP batches are not decoded (breakdown shifts and energy)"); return FJSP_E_UNSUPPORTED;
+    }
+    if (e->gen_failed) { set_error("fjsp_schedule_search: the last regenerate of this handle failed"); return FJSP_E_STATE; }
+    if (n_cand < 1 || n_cand > 64 || rounds < 0 || tenure < 0) { set_error("fjsp_schedule_search: needs n_cand in 1..64, rounds >= 0 and tenure >= 0"); return FJSP_E_ARG; }
+    if (objective < 0 || objective > 1 || neighbourhood < 0 || neighbourhood > 2 || accept < 0 || accept > 2) {
+        set_error("fjsp_schedule_search: objective is 0 or 1, neighbourhood and accept are 0, 1 or 2"); return FJSP_E_ARG;
+    }
+    if (neighbourhood != 0 && objective != 0) { set_error("fjsp_schedule_search: the critical neighbourhoods follow the makespan: objective must be 0"); return FJSP_E_ARG; }
+    if (3ULL * (unsigned long long)rounds * (unsigned long long)n_cand > 0xFFFFFFFFULL) {
+        set_error("fjsp_schedule_search: 3 x rounds x n_cand draws per env exceed 2^32 - 1"); return FJSP_E_ARG;
+    }
+    const DevBatch &b = e->b;
+    if (e->ops_max <= 0) { set_error("fjsp_schedule_search: no operations"); return FJSP_E_ARG; }
+    const size_t lds = search_words(b.jcap, b.MP, e->ops_max) * 4;
+    if (lds > kLdsCu) {
+        set_error("fjsp_schedule_search: an env's working set (64 candidate states of " + std::to_string(state_words(b.jcap, b.MP) * 4) +
+                  " bytes and 61 bytes per operation: " + std::to_string(lds) + " bytes) exceeds the " + std::to_string(kLdsCu) + " bytes of a CU's LDS");
+        return FJSP_E_UNSUPPORTED;
+    }
+    DeviceGuard guard(e->device);
+    if (!e->d_decode_kinds && !dev_alloc(e, (size_t)b.n_inst * (size_t)(b.KP + 1) * sizeof(uint2), &e->d_decode_kinds, "hipMalloc (decode kind table)")) return FJSP_E_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch(decode_kinds_kernel, dim3((unsigned)((b.n_inst + 63) / 64)), dim3(64), 0, st, b, e->d_decode_kinds) != 0) {
+        set_error("decode_kinds_kernel launch failed"); return FJSP_E_HIP;
+    }
+    const SearchArgs a{d_plan, d_plan_out, d_objective, d_history, d_accepted, d_status, d_trace, e->d_decode_kinds, seed ^ FJSP_SEARCH_STREAM,
+                       (long long)first_env, (int)rounds, (int)n_cand, (int)objective, (int)neighbourhood, (int)accept, (int)tenure, e->ops_max, b.jcap};
+    if (launch(schedule_search_kernel, dim3((unsigned)b.N), dim3(64), lds, st, b, a) != 0) {
+        set_error("schedule_search_kernel launch failed"); return FJSP_E_HIP;
     }
     return FJSP_OK;
 }

@@ -31,6 +31,8 @@ slowly.
   (schedule.decode, fjsp_schedule_decode, csrc/fjsp_decode.hip) and keeps the best if it is no worse; the moves are uniform
   reassignments and adjacent swaps, or drawn from the neighbourhood of the plan's critical path (schedule.critical,
   fjsp_schedule_critical).
+- local_search: improve's search, descent or tabu, as one launch for all its rounds (schedule.search, fjsp_schedule_search):
+  a wavefront per env, a lane per neighbour, the plan in LDS, on a counter-based draw stream that shards reproduce.
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -661,3 +663,48 @@ def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, si
         out_plan = torch.as_tensor(plan, device=dev).to(torch.int32).contiguous()
     return dict(plan=out_plan, objective=last["objective"][:, 0], history=history, accepted=accepted,
                 table=last["table"][:, 0], length=last["length"][:, 0])
+
+
+def local_search(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, accept="sideways", tenure=8, neighbourhood="uniform",
+                 trace=False):
+    """improve's search as ONE launch for all its rounds (schedule.search, fjsp_schedule_search, csrc/fjsp_decode.hip): one
+    wavefront owns an env, each lane decodes one neighbour, the round's winner is a reduction over the wave and the plan
+    stays on the CU.  The moves, the neighbourhoods and the selection are improve's; the draws are not -- a counter-based
+    splitmix64 stream of (seed, global env id, round, candidate) that include/fjsp_amd.h states and schedule.search_draws
+    returns, so a shard of a batch (EnvBatch first_env) searches exactly as those envs of the whole batch do.
+
+    plan: int32[N, cap, 3], every plan must decode.  neighbours: 1..64.  accept: "strict" -- the round's best neighbour is
+    taken if it is better than the plan; "sideways" -- or as good (improve's sideways=True); "tabu" -- the best neighbour
+    that is not tabu is taken, better or worse: a move makes the rows it moved tabu for `tenure` further rounds, a tabu
+    move is admissible only where it beats the best plan seen (aspiration), moves that change nothing are not candidates,
+    and the best plan seen is returned.  neighbourhood: as improve; "critical" and "mixed" need objective "makespan".
+
+    Returns improve's dict -- plan=int32[N, cap, 3], objective=int64[N, 2] of it, history=int64[rounds + 1, N] the chosen
+    objective of the input plan and of the current plan after every round, accepted=int64[N], table=int32[N, cap, 6] and
+    length=int32[N] of the returned plans (one schedule.decode) -- and status=int32[N] (zeros), with trace=True also trace=
+    int32[rounds, N, 3], the move each round took ((0, 0, 0): none; indices into the plan the round started from).
+    ValueError for arguments improve refuses, neighbours > 64, tenure < 0 and a plan that does not decode; FjspError
+    where the library refuses (MO_DFJSP, an env's working set beyond a CU's LDS: EnvBatch.search_lds)."""
+    from . import schedule as sch
+    b, _ = _unwrap(batch, None)
+    if objective not in sch.SEARCH_OBJECTIVES:
+        raise ValueError("objective must be one of %s" % (sch.SEARCH_OBJECTIVES,))
+    if neighbourhood not in sch.SEARCH_NEIGHBOURHOODS:
+        raise ValueError("neighbourhood must be one of %s" % (sch.SEARCH_NEIGHBOURHOODS,))
+    if accept not in sch.SEARCH_ACCEPT:
+        raise ValueError("accept must be one of %s" % (sch.SEARCH_ACCEPT,))
+    if neighbourhood != "uniform" and objective != "makespan":
+        raise ValueError("neighbourhood %r follows the critical path of the makespan: objective must be 'makespan'" % (neighbourhood,))
+    rounds, Q, tenure = int(rounds), int(neighbours), int(tenure)
+    if rounds < 0 or not 1 <= Q <= sch.SEARCH_MAX_NEIGHBOURS or tenure < 0:
+        raise ValueError("local_search needs rounds >= 0, neighbours in 1..%d and tenure >= 0" % sch.SEARCH_MAX_NEIGHBOURS)
+    res = sch.search(b, plan, rounds, Q, sch.SEARCH_OBJECTIVES.index(objective), sch.SEARCH_NEIGHBOURHOODS.index(neighbourhood),
+                     sch.SEARCH_ACCEPT.index(accept), tenure, seed, trace)
+    if bool((res["status"] != 0).any()):
+        raise ValueError("local_search: a plan does not decode (status %s)" % sorted(set(res["status"].tolist()) - {0}))
+    last = sch.decode(b, res["plan"], want_table=True)
+    out = dict(plan=res["plan"], objective=res["objective"], history=res["history"], accepted=res["accepted"].to(torch.int64),
+               table=last["table"][:, 0], length=last["length"][:, 0], status=res["status"])
+    if trace:
+        out["trace"] = res["trace"]
+    return out

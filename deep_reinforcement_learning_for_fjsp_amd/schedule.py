@@ -15,6 +15,8 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     pair_move(u, v, w)                          the MOVE_PAIR that puts rows u and v, v first, behind row w
     critical(batch, table, n_cand, max_moves)   tails, critical flags, one critical path and its moves, on the device
     begin_order(table)                          the same schedule with its rows sorted by begin: (plan, table)
+    search(batch, plan, rounds, n_cand, ...)    hill climbing / tabu search, all rounds in one launch (fjsp_schedule_search)
+    search_draws(seed, env, first, n)           the draw stream of that search, on the host
 
 `inst` is anything with the instance arrays of instances.InstanceArrays: Jr[R], p[K][M] (0 = ineligible),
 count[S][R], arrive[S], delivery[S] (and bk_n[M], bk[W][2] for MO_DFJSP breakdown windows).
@@ -393,3 +395,48 @@ def begin_order(table):
     order = torch.sort(key, dim=-1, stable=True).indices
     table = torch.gather(table, -2, order[..., None].expand(table.shape))
     return plan_of(table), table
+
+
+SEARCH_OBJECTIVES = ("makespan", "tardiness")
+SEARCH_NEIGHBOURHOODS = ("uniform", "critical", "mixed")
+SEARCH_ACCEPT = ("strict", "sideways", "tabu")
+SEARCH_MAX_NEIGHBOURS = 64
+
+
+def search_draws(seed, env, first, n):
+    """Draws first .. first + n - 1 of the search stream of the env with global id `env` (fjsp_search_draws, host only):
+    uint64[n].  Candidate q of round t of a search with n_cand neighbours owns draws 3 (t n_cand + q) + 0, 1, 2."""
+    import ctypes as C
+    from ._capi import check, lib
+    n = int(n)
+    if n < 0:
+        raise ValueError("search_draws needs n >= 0")
+    out = np.zeros(n, np.uint64)
+    check(lib().fjsp_search_draws(int(seed) & (2 ** 64 - 1), int(env), int(first) & 0xFFFFFFFF, n, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return out
+
+
+def search(batch, plan, rounds, n_cand, objective=0, neighbourhood=0, accept=1, tenure=0, seed=0, trace=False):
+    """fjsp_schedule_search on the current stream: the whole hill climb or tabu search of every env in one launch (the
+    contract is in include/fjsp_amd.h; policy_search.local_search is the checked form).  plan: int32[N, cap, 3]; the codes
+    are the indices of SEARCH_OBJECTIVES, SEARCH_NEIGHBOURHOODS and SEARCH_ACCEPT.  Passes batch.first_env.  Returns dict(plan=
+    int32[N, cap, 3], objective=int64[N, 2], history=int64[rounds + 1, N], accepted=int32[N], status=int32[N], trace=
+    int32[rounds, N, 3] or None), device tensors.  ValueError for a plan of another shape; FjspError where the library refuses."""
+    import torch
+    from ._capi import check, ptr
+    b = getattr(batch, "batch", batch)
+    cap = int(b._lib.fjsp_schedule_decode_capacity(b._h))
+    if not torch.is_tensor(plan):
+        plan = torch.as_tensor(np.asarray(plan))
+    if tuple(plan.shape) != (b.N, cap, 3):
+        raise ValueError("plan must have shape %s, got %s" % ((b.N, cap, 3), tuple(plan.shape)))
+    plan = plan.to(device=b.device, dtype=torch.int32).contiguous()
+    rows = max(int(rounds), 0)
+    out = dict(plan=torch.empty_like(plan), objective=torch.empty(b.N, 2, dtype=torch.int64, device=b.device),
+               history=torch.empty(rows + 1, b.N, dtype=torch.int64, device=b.device),
+               accepted=torch.empty(b.N, dtype=torch.int32, device=b.device), status=torch.empty(b.N, dtype=torch.int32, device=b.device),
+               trace=torch.empty(rows, b.N, 3, dtype=torch.int32, device=b.device) if trace else None)
+    check(b._lib.fjsp_schedule_search(b._h, ptr(plan), int(rounds), int(n_cand), int(objective), int(neighbourhood), int(accept), int(tenure),
+                                      int(seed) & (2 ** 64 - 1), int(b.first_env), ptr(out["plan"]), ptr(out["objective"]), ptr(out["history"]),
+                                      ptr(out["accepted"]), ptr(out["status"]), ptr(out["trace"]), b._stream()))
+    return out

@@ -808,6 +808,58 @@ int fjsp_schedule_critical(fjsp_env *e, const int32_t *d_table, int32_t n_cand, 
                            int32_t *d_path_len, int32_t *d_moves, int32_t max_moves, int32_t *d_n_moves, int32_t *d_skipped,
                            int32_t *d_status, int32_t *d_makespan, void *stream);
 
+/* Hill climbing and tabu search on explicit schedules, every round of every env in ONE launch (policy_search.local_search;
+ * csrc/fjsp_decode.hip, schedule_search_kernel): one 64-lane workgroup per env, lane q decodes candidate q of a round, the
+ * round's selection is a reduction over the wave and the plan stays in LDS from the first round to the last.  The result
+ * is a function of the arguments alone; tests/search_reference.py restates it in numpy, bit for bit.
+ *
+ * Draws: splitmix64 (csrc/fjsp_gen_stream.h, draw(seed, i)).  The env with global id g = first_env + e has the stream
+ * s_g = draw(seed ^ FJSP_SEARCH_STREAM, (uint32_t)g); candidate q of round t owns draw(s_g, 3 (t n_cand + q) + c), c = 0, 1, 2
+ * (c0, c1, c2).  pick(d, n) = ((d >> 32) * n) >> 32.  The stream depends on g alone: a shard [k, k + n) of a batch
+ * reproduces those envs of the whole batch.  fjsp_search_draws (host only) returns draws first .. first + n - 1 of an env's
+ * stream, the index wrapping at 2^32.
+ *
+ * A round t of an env whose current plan has L rows (the input plan at t = 0):
+ *   neighbourhood 1, 2: the current plan is decoded and put into begin order (a stable sort of the rows by begin; the same
+ *     schedule), and the round's move list is what fjsp_schedule_critical writes for that table with max_moves = 128.
+ *     neighbourhood 0 never reorders the plan.
+ *   candidate q < n_cand: from the list (neighbourhood 1; 2 for q < n_cand / 2) entry pick(c2, min(n_moves, 128)), masked
+ *     when the list is empty; else, q even, (1, u, m) with u = pick(c0, L) and m the pick(c1, n_e)-th of the n_e eligible
+ *     machines of row u's operation, ascending (it may be the row's machine); q odd, (2, u, 0) with u = pick(c0, max(L - 1,
+ *     1)).  Every candidate is decoded as fjsp_schedule_decode decodes the move on the current plan.
+ *   selection: of the unmasked candidates with status 0 the least objective, the lowest q among equals.
+ *   accept 0 (strict): taken if below the current plan's objective; 1 (sideways): if not above it.
+ *   accept 2 (tabu): every row carries its index in the input plan as identity, through moves and sorting; until[id] = 0
+ *     at the start.  A candidate that changes nothing (a reassignment to the row's machine, a swap of two rows of one
+ *     job) is masked; one that moves a row with until[id] > t (rows u; u, u + 1; u, v of kinds 1; 2; 4) is tabu and
+ *     admissible only if its objective is below the best seen so far.  The winner of the admissible candidates is taken,
+ *     better or worse, and its moved rows get until = t + 1 + tenure (saturating at 2^31 - 1).
+ *   The move taken is applied to the current plan (as schedule.apply_moves applies it).
+ *
+ * d_plan i32[N][cap][3] as fjsp_schedule_decode takes it, one plan per env.  d_status i32[N]: the decode status of the
+ * input plan; an env whose plan does not decode gets its plan copied through, history and objective -1, accepted 0 and
+ * a trace of zeros, and the others are not affected.  d_plan_out i32[N][cap][3]: the best plan seen, replaced only on
+ * strict improvement -- with accept 0 and 1 the current plan after the last round; with rounds = 0 the input plan as it
+ * came --, -1 rows past its end; d_objective i64[N][2] its (makespan, total tardiness).  d_history i64[rounds + 1][N]: the
+ * chosen objective of the input plan, then of the CURRENT plan after every round.  d_accepted i32[N]: moves taken.
+ * d_trace (nullable) i32[rounds][N][3]: the move taken in round t, (0, 0, 0) for none; its indices refer to the plan the
+ * round started from (in begin order with neighbourhood 1, 2).
+ *
+ * Stream-ordered, no host synchronisation, two launches for any number of rounds (the kind table, then the search).
+ * Limit: 64 candidate states (fjsp_schedule_decode's, 5 bytes per job rounded up to 16 jobs + 4 per machine) and 61
+ * bytes per row of the longest plan, 1552 bytes more, must fit the 160 KB of a CU's LDS; fjsp_schedule_search_lds is that
+ * sum in bytes, 0 where it does not fit or the batch is MO_DFJSP.
+ * FJSP_E_ARG: a null e, d_plan or output other than d_trace, n_cand outside 1..64, rounds < 0, tenure < 0, an objective
+ * outside 0..1, a neighbourhood or accept outside 0..2, neighbourhood != 0 with objective != 0, 3 x rounds x n_cand > 2^32 - 1.
+ * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP, a working set beyond the limit (the message gives the bytes).  FJSP_E_STATE: a
+ * generated handle whose last regenerate failed. */
+#define FJSP_SEARCH_STREAM 0x8CB92BA72F3D8DD7ULL
+int fjsp_schedule_search(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, int32_t objective, int32_t neighbourhood,
+                         int32_t accept, int32_t tenure, uint64_t seed, int64_t first_env, int32_t *d_plan_out, int64_t *d_objective,
+                         int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream);
+int fjsp_schedule_search_lds(const fjsp_env *e);
+int fjsp_search_draws(uint64_t seed, int64_t env, uint32_t first, int32_t n, uint64_t *h_out);
+
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
  *
