@@ -674,6 +674,17 @@ class EnvBatch(object):
         from . import schedule
         return schedule.decode(self, plan, moves, n_cand, want_table)
 
+    def decode_dyn_group(self):
+        """Candidates one workgroup of the MO_DFJSP decode kernel takes (fjsp_schedule_decode_dyn_group); 0: the batch is
+        not MO_DFJSP, or a candidate's state exceeds the limit."""
+        return int(self._lib.fjsp_schedule_decode_dyn_group(self._h))
+
+    def decode_dyn(self, plan, moves=None, n_cand=1, want_table=False):
+        """schedule.decode_dyn on this MO_DFJSP batch's instances: explicit schedules -> (makespan, tardiness, energy),
+        status, tables, lengths."""
+        from . import schedule
+        return schedule.decode_dyn(self, plan, moves, n_cand, want_table)
+
     def critical(self, table, n_cand=1, max_moves=0):
         """schedule.critical on this batch's instances: tables -> tails, critical flags, one critical path and its moves."""
         from . import schedule

@@ -21,6 +21,11 @@
 // A move is applied while the plan is read: a reassignment is a select, a swap and a pair move (kind 4: rows u and v stand,
 // v first, behind row w, u <= w < v; the swap is the pair u, u + 1, u) are one index map, position -> row, in move_src().
 //
+// fjsp_schedule_decode_dyn is the same kernel text compiled with DYN for MO_DFJSP handles (schedule_decode_dyn_kernel): per
+// row the lane also gathers the machine's window range and walks its windows, power[k][m] and the machine's idle power, and
+// keeps one more banked word per machine, the end of its last task; free[m] is the machine's end there and the objective
+// has a third entry, energy.  The three kernels without DYN compile to what they compiled to before the switch.
+//
 // fjsp_schedule_critical is the decode run backwards, on the tables decode writes: one lane per table, the same grouping,
 // the same banked words -- per job and per machine "tail + duration of the latest row seen", as decode keeps ready / free.
 // A forward scan finds the table's end, checks every index it supplies, and the first row that ends at the makespan; the
@@ -163,17 +168,41 @@ __device__ __forceinline__ bool move_past(const Move &mv, int L) {
 // What a decoded row adds to its table: stage, operation type, times
 struct Step { int stg, k, begin, end; };
 
+// What the MO_DFJSP decode (fjsp_schedule_decode_dyn) reads and keeps beside Shop and State: power and idle power, the
+// machines' breakdown windows (machine m's are windows bkoff[m] .. bkoff[m + 1] - 1, file order; BW = the windows a record
+// has room for) and, behind free[MP] in the banked state, the end of every machine's last task (-1: none, as e_dyn keeps it)
+struct DynShop {
+    const uint16_t *pw, *bkoff;
+    const int32_t *ipw;
+    const int2 *bk;
+    uint32_t *mlast;
+    int BW;
+};
+__device__ __forceinline__ DynShop dyn_shop_of(const DevBatch &b, const Shop &sh, const State &st, int BW) {
+    return DynShop{reinterpret_cast<const uint16_t *>(sh.ir + b.L.i_pw), reinterpret_cast<const uint16_t *>(sh.ir + b.L.i_bkoff),
+                   reinterpret_cast<const int32_t *>(sh.ir + b.L.i_ipw), reinterpret_cast<const int2 *>(sh.ir + b.L.i_bk),
+                   st.mfree + (size_t)sh.MP * st.G, BW};
+}
+
 // The decode of one plan under one move on the state `st`: jobs released at their order's arrival, machines free at 0,
 // then row by row.  Returns the status of the rows (0, 1, 2, 3), L = the plan's length whatever the status (a candidate
 // that fails a check keeps reading rows only to find the plan's end); sink(t, row, step) sees every decoded row.
-template <class RowAt, class Sink>
+// DYN (MO_DFJSP_breakdown.py:203-256 without the event clock; the contract is at fjsp_schedule_decode_dyn): the dispatch
+// time t0 = max(ready, free) is shifted by the machine's windows, walked from the first in file order at every row as the
+// reference walks them; free[m] and ready[job] become the MACHINE's end, which a window that starts exactly at the task's
+// end moves on its own; *energy gathers power x duration and idle power x the gap from the last task's end to t0.
+template <bool DYN = false, class RowAt, class Sink>
 __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, const State &st, RowAt row, int cap, const Move &mv, Sink sink,
-                                           int &L, long long &makespan, long long &tard) {
+                                           int &L, long long &makespan, long long &tard, const DynShop *dy = nullptr, long long *energy = nullptr) {
     const int G = st.G, JW = sh.JW, MP = sh.MP;
     const int32_t *oarr = reinterpret_cast<const int32_t *>(sh.ir + b.L.i_oarr);
     const uint16_t *ocnt = reinterpret_cast<const uint16_t *>(sh.ir + b.L.i_ocnt);
     for (int w = 0; w < JW / 4; ++w) st.words[(size_t)w * G] = 0u;
     for (int m = 0; m < MP; ++m) st.mfree[(size_t)m * G] = 0u;
+    if constexpr (DYN) {
+        for (int m = 0; m < MP; ++m) dy->mlast[(size_t)m * G] = 0xFFFFFFFFu;
+        *energy = 0;
+    }
     for (int r = 0; r < sh.R; ++r) {
         const uint32_t ka = sh.kinds[1 + r].x;
         const int jbeg = (int)(ka & 0xFFFFu), cnt = (int)(ka >> 16);
@@ -204,9 +233,28 @@ __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, co
         if (x.m < 0 || x.m >= sh.M) { err = 3; continue; }
         const int pv = (int)sh.p[(size_t)(koff + stg) * MP + x.m];
         if (pv == 0) { err = 3; continue; }
-        const int begin = max((int)st.ready[(size_t)j * G], (int)st.mfree[(size_t)x.m * G]), end = begin + pv;
-        st.ready[(size_t)j * G] = (uint32_t)end;
-        st.mfree[(size_t)x.m * G] = (uint32_t)end;
+        int begin = max((int)st.ready[(size_t)j * G], (int)st.mfree[(size_t)x.m * G]), end = begin + pv;
+        if constexpr (DYN) {
+            const int t0 = begin;
+            int mend = end;
+            const int q1 = min((int)dy->bkoff[x.m + 1], dy->BW);                  // (x.m + 1 <= MP; no window index past the record)
+            for (int q = (int)dy->bkoff[x.m]; q < q1; ++q) {
+                const int2 w = dy->bk[q];
+                if (w.x <= t0 && t0 < w.y) { begin += w.y - t0; end += w.y - t0; mend = end; }
+                else if (t0 < w.x && w.x < end) { end += w.y - w.x; mend = end; }
+                else if (w.x == end) mend += w.y - w.x;
+                else if (w.x > end) break;
+            }
+            *energy += (long long)dy->pw[(size_t)(koff + stg) * MP + x.m] * (long long)pv;
+            const int last = (int)dy->mlast[(size_t)x.m * G];
+            if (last >= 0) *energy += (long long)(t0 - last) * (long long)dy->ipw[x.m];
+            dy->mlast[(size_t)x.m * G] = (uint32_t)end;
+            st.ready[(size_t)j * G] = (uint32_t)mend;
+            st.mfree[(size_t)x.m * G] = (uint32_t)mend;
+        } else {
+            st.ready[(size_t)j * G] = (uint32_t)end;
+            st.mfree[(size_t)x.m * G] = (uint32_t)end;
+        }
         *sj = (uint8_t)(stg + 1);
         makespan = max(makespan, (long long)end);
         if (stg == Jr - 1) tard += max(0LL, (long long)end - (long long)sh.due[j]);
@@ -216,7 +264,11 @@ __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, co
     return err;
 }
 
-__global__ __launch_bounds__(256) void schedule_decode_kernel(DevBatch b, DecodeArgs a) {
+// One candidate of schedule_decode_kernel (objective i64[2]) and of schedule_decode_dyn_kernel (DYN: MO_DFJSP, objective
+// i64[3] with the energy, the state a word per machine longer)
+template <bool DYN>
+__device__ __forceinline__ void decode_candidate(const DevBatch &b, const DecodeArgs &a, int BW) {
+    constexpr int NO = DYN ? 3 : 2;
     const int s = (int)threadIdx.x;
     const long long g = (long long)blockIdx.x * a.G + s;
     if (s >= a.G || g >= a.total) return;
@@ -235,21 +287,24 @@ __global__ __launch_bounds__(256) void schedule_decode_kernel(DevBatch b, Decode
     }
 
     int err = 0, L = 0;
-    long long makespan = 0, tard = 0;
+    long long makespan = 0, tard = 0, energy = 0;
+    DynShop dy{};
+    if constexpr (DYN) dy = dyn_shop_of(b, sh, st, BW);
     int32_t *tab = a.table ? a.table + (size_t)g * (size_t)cap * 6 : nullptr;
     if (!mv.bad) {
-        err = decode_plan(b, sh, st, row, cap, mv, [&](int t, const Row &x, const Step &d) {
+        err = decode_plan<DYN>(b, sh, st, row, cap, mv, [&](int t, const Row &x, const Step &d) {
             if (tab) {
                 int32_t *o = tab + (size_t)t * 6;
                 o[0] = x.r; o[1] = d.stg; o[2] = x.n; o[3] = x.m; o[4] = d.begin; o[5] = d.end;
             }
-        }, L, makespan, tard);
+        }, L, makespan, tard, &dy, &energy);
         if (move_past(mv, L)) mv.bad = true;
     }
     const int stt = mv.bad ? 4 : err;
     a.status[g] = stt;
-    a.objective[2 * g] = stt ? -1 : makespan;
-    a.objective[2 * g + 1] = stt ? -1 : tard;
+    a.objective[NO * g] = stt ? -1 : makespan;
+    a.objective[NO * g + 1] = stt ? -1 : tard;
+    if constexpr (DYN) a.objective[NO * g + 2] = stt ? -1 : energy;
     if (a.len) a.len[g] = stt ? 0 : L;
     if (tab) {
         for (int t = stt ? 0 : L; t < cap; ++t) {
@@ -258,6 +313,9 @@ __global__ __launch_bounds__(256) void schedule_decode_kernel(DevBatch b, Decode
         }
     }
 }
+
+__global__ __launch_bounds__(256) void schedule_decode_kernel(DevBatch b, DecodeArgs a) { decode_candidate<false>(b, a, 0); }
+__global__ __launch_bounds__(256) void schedule_decode_dyn_kernel(DevBatch b, DecodeArgs a, int BW) { decode_candidate<true>(b, a, BW); }
 
 // ---- fjsp_schedule_critical: the decode run backwards, one lane per table, the same grouping and banked layout
 struct CriticalArgs {
@@ -613,13 +671,15 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
 
 
 // candidates per workgroup, 0 = the state of 32 candidates does not fit the LDS of a CU
-int decode_group(const DevBatch &b) {
-    const size_t bytes = (size_t)state_words(b.jcap, b.MP) * 4;
+int decode_group(size_t bytes) {
     for (int G = 256; G >= 64; G >>= 1)
         if (G * bytes <= kLdsTwo) return G;
     if (64 * bytes <= kLdsCu) return 64;
     return 32 * bytes <= kLdsCu ? 32 : 0;
 }
+int decode_group(const DevBatch &b) { return decode_group((size_t)state_words(b.jcap, b.MP) * 4); }
+// the MO_DFJSP decode keeps one more word per machine (the end of its last task)
+size_t dyn_state_bytes(const DevBatch &b) { return (size_t)(state_words(b.jcap, b.MP) + b.MP) * 4; }
 
 }  // namespace
 
@@ -629,23 +689,28 @@ extern "C" int fjsp_schedule_decode_group(const fjsp_env *e) {
     return (e && e->b.variant != FJSP_VARIANT_MO_DFJSP) ? decode_group(e->b) : 0;
 }
 
-extern "C" int fjsp_schedule_decode(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
-                                    int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream) {
-    if (!e || !d_plan || !d_objective || !d_status) { set_error("fjsp_schedule_decode: null env, plan, objective or status pointer"); return FJSP_E_ARG; }
-    if (n_cand < 1 || (q_plans != 1 && q_plans != n_cand)) { set_error("fjsp_schedule_decode: needs n_cand >= 1 and q_plans = 1 or n_cand"); return FJSP_E_ARG; }
-    if (e->b.variant == FJSP_VARIANT_MO_DFJSP) {
-        set_error("fjsp_schedule_decode: MO_DFJSP batches are not decoded (breakdown shifts and energy)"); return FJSP_E_UNSUPPORTED;
+// fjsp_schedule_decode (dyn false) and fjsp_schedule_decode_dyn (dyn true): each takes the handles the other refuses
+static int schedule_decode(bool dyn, fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
+                           int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream) {
+    const std::string fn = dyn ? "fjsp_schedule_decode_dyn" : "fjsp_schedule_decode";
+    if (!e || !d_plan || !d_objective || !d_status) { set_error(fn + ": null env, plan, objective or status pointer"); return FJSP_E_ARG; }
+    if (n_cand < 1 || (q_plans != 1 && q_plans != n_cand)) { set_error(fn + ": needs n_cand >= 1 and q_plans = 1 or n_cand"); return FJSP_E_ARG; }
+    if ((e->b.variant == FJSP_VARIANT_MO_DFJSP) != dyn) {
+        set_error(dyn ? fn + ": decodes MO_DFJSP batches only (breakdown shifts and energy): fjsp_schedule_decode decodes the others"
+                      : fn + ": MO_DFJSP batches are not decoded here (breakdown shifts and energy): fjsp_schedule_decode_dyn decodes them");
+        return FJSP_E_UNSUPPORTED;
     }
-    if (e->gen_failed) { set_error("fjsp_schedule_decode: the last regenerate of this handle failed"); return FJSP_E_STATE; }
+    if (e->gen_failed) { set_error(fn + ": the last regenerate of this handle failed"); return FJSP_E_STATE; }
     const DevBatch &b = e->b;
-    const int G = decode_group(b);
+    const size_t bytes = dyn ? dyn_state_bytes(b) : (size_t)state_words(b.jcap, b.MP) * 4;
+    const int G = decode_group(bytes);
     if (G == 0) {
-        set_error("fjsp_schedule_decode: a candidate's state (5 bytes per job of the largest instance, rounded up to 16 jobs, + 4 per machine: " +
-                  std::to_string(state_words(b.jcap, b.MP) * 4) + " bytes) exceeds 5120 bytes");
+        set_error(fn + ": a candidate's state (5 bytes per job of the largest instance, rounded up to 16 jobs, + " + (dyn ? "8" : "4") +
+                  " per machine: " + std::to_string(bytes) + " bytes) exceeds 5120 bytes");
         return FJSP_E_UNSUPPORTED;
     }
     const long long total = (long long)b.N * (long long)n_cand;
-    if (e->ops_max <= 0 || total > 0x7fffffffLL) { set_error("fjsp_schedule_decode: no operations, or more than 2^31 - 1 candidates"); return FJSP_E_ARG; }
+    if (e->ops_max <= 0 || total > 0x7fffffffLL) { set_error(fn + ": no operations, or more than 2^31 - 1 candidates"); return FJSP_E_ARG; }
     DeviceGuard guard(e->device);
     if (!e->d_decode_kinds && !dev_alloc(e, (size_t)b.n_inst * (size_t)(b.KP + 1) * sizeof(uint2), &e->d_decode_kinds, "hipMalloc (decode kind table)")) return FJSP_E_HIP;
     hipStream_t st = (hipStream_t)stream;
@@ -653,11 +718,26 @@ extern "C" int fjsp_schedule_decode(fjsp_env *e, const int32_t *d_plan, int32_t 
         set_error("decode_kinds_kernel launch failed"); return FJSP_E_HIP;
     }
     const DecodeArgs a{d_plan, d_moves, d_objective, d_status, d_table, d_len, e->d_decode_kinds, total, (int)n_cand, (int)q_plans, e->ops_max, G, b.jcap};
-    const size_t lds = (size_t)state_words(b.jcap, b.MP) * 4 * (size_t)G;
-    if (launch(schedule_decode_kernel, dim3((unsigned)((total + G - 1) / G)), dim3((unsigned)(G < 64 ? 64 : G)), lds, st, b, a) != 0) {
-        set_error("schedule_decode_kernel launch failed"); return FJSP_E_HIP;
-    }
+    const dim3 grid((unsigned)((total + G - 1) / G)), block((unsigned)(G < 64 ? 64 : G));
+    // dyn: the windows from i_bk to the record's end -- no window index reaches past the record, whatever i_bkoff holds
+    const int rc = dyn ? launch(schedule_decode_dyn_kernel, grid, block, bytes * (size_t)G, st, b, a, (int)((b.L.i_stride - b.L.i_bk) / 8))
+                       : launch(schedule_decode_kernel, grid, block, bytes * (size_t)G, st, b, a);
+    if (rc != 0) { set_error(std::string(dyn ? "schedule_decode_dyn_kernel" : "schedule_decode_kernel") + " launch failed"); return FJSP_E_HIP; }
     return FJSP_OK;
+}
+
+extern "C" int fjsp_schedule_decode(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
+                                    int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream) {
+    return schedule_decode(false, e, d_plan, q_plans, d_moves, n_cand, d_objective, d_status, d_table, d_len, stream);
+}
+
+extern "C" int fjsp_schedule_decode_dyn_group(const fjsp_env *e) {
+    return (e && e->b.variant == FJSP_VARIANT_MO_DFJSP) ? decode_group(dyn_state_bytes(e->b)) : 0;
+}
+
+extern "C" int fjsp_schedule_decode_dyn(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
+                                        int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream) {
+    return schedule_decode(true, e, d_plan, q_plans, d_moves, n_cand, d_objective, d_status, d_table, d_len, stream);
 }
 
 extern "C" int fjsp_schedule_critical(fjsp_env *e, const int32_t *d_table, int32_t n_cand, int32_t *d_tail, uint8_t *d_flags, int32_t *d_path,

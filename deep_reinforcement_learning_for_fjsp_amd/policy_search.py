@@ -30,7 +30,8 @@ slowly.
   instance a recorded table's): every round decodes `neighbours` random moves of each env's plan in one launch
   (schedule.decode, fjsp_schedule_decode, csrc/fjsp_decode.hip) and keeps the best if it is no worse; the moves are uniform
   reassignments and adjacent swaps, or drawn from the neighbourhood of the plan's critical path (schedule.critical,
-  fjsp_schedule_critical).
+  fjsp_schedule_critical).  A MO_DFJSP batch is decoded with its breakdown windows and energy (schedule.decode_dyn,
+  fjsp_schedule_decode_dyn): "energy" is an objective there, and the moves are the uniform ones.
 - local_search: improve's search, descent or tabu, as one launch for all its rounds (schedule.search, fjsp_schedule_search):
   a wavefront per env, a lane per neighbour, the plan in LDS, on a counter-based draw stream that shards reproduce.
 
@@ -579,23 +580,33 @@ def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, si
     has no candidates in the round; "mixed" -- candidates q < neighbours // 2 from the critical list, the others as
     "uniform" draws them.  Both decode the accepted plans once more per round, for the next round's table.
 
+    A MO_DFJSP batch decodes through schedule.decode_dyn (fjsp_schedule_decode_dyn): objective may also be "energy", the
+    returned objective has that third column, and neighbourhood must be "uniform" -- the critical-path analysis adds
+    durations along a path, and the shift a breakdown window gives an operation depends on when it is dispatched.
+
     Returns dict(plan=int32[N, cap, 3], objective=int64[N, 2] (makespan, tardiness) of it, history=int64[rounds + 1, N] the
     chosen objective of the input plan and after every round, accepted=int64[N] moves taken, table=int32[N, cap, 6] and
     length=int32[N] of the final plans); rounds=0 returns the input plan."""
     from . import schedule as sch
     b, _ = _unwrap(batch, None)
-    if objective not in IMPROVE_OBJECTIVES:
-        raise ValueError("objective must be one of %s" % (IMPROVE_OBJECTIVES,))
+    dyn = b.variant == sch.VARIANT_MO_DFJSP
+    objectives = IMPROVE_OBJECTIVES + (("energy",) if dyn else ())
+    decode = sch.decode_dyn if dyn else sch.decode
+    if objective not in objectives:
+        raise ValueError("objective must be one of %s" % (objectives,))
     if neighbourhood not in IMPROVE_NEIGHBOURHOODS:
         raise ValueError("neighbourhood must be one of %s" % (IMPROVE_NEIGHBOURHOODS,))
+    if dyn and neighbourhood != "uniform":
+        raise ValueError("neighbourhood %r: critical paths are not analysed on MO_DFJSP (breakdown shifts are not additive in the "
+                         "durations): neighbourhood must be 'uniform'" % (neighbourhood,))
     if neighbourhood != "uniform" and objective != "makespan":
         raise ValueError("neighbourhood %r follows the critical path of the makespan: objective must be 'makespan'" % (neighbourhood,))
     rounds, Q = int(rounds), int(neighbours)
     if rounds < 0 or Q < 1:
         raise ValueError("improve needs rounds >= 0 and neighbours >= 1")
-    col = IMPROVE_OBJECTIVES.index(objective)
+    col = objectives.index(objective)
     dev, N = b.device, b.N
-    first = sch.decode(b, plan, want_table=True)
+    first = decode(b, plan, want_table=True)
     if bool((first["status"] != 0).any()):
         raise ValueError("improve: a plan does not decode (status %s)" % sorted(set(first["status"].flatten().tolist()) - {0}))
     koff, elig = _machine_tables(b)
@@ -631,13 +642,13 @@ def improve(batch, plan, rounds, neighbours=64, objective="makespan", seed=0, si
         for t in range(rounds):
             draw = torch.rand(2, N, Q, generator=gen, device=dev, dtype=torch.float64)
             moves = _uniform_moves(sch, draw, L, rows[..., 3], elig, inst, odd)
-            res = sch.decode(b, rows[..., :3].contiguous(), moves, Q)
+            res = decode(b, rows[..., :3].contiguous(), moves, Q)
             chosen, take, best = select(moves, res)
             rows = sch.apply_moves(rows, chosen[:, None])[:, 0]
             cur = torch.where(take, best, cur)
             accepted += take
             history[t + 1] = cur
-        last = sch.decode(b, rows[..., :3].contiguous(), want_table=True)
+        last = decode(b, rows[..., :3].contiguous(), want_table=True)
         return dict(plan=rows[..., :3].contiguous(), objective=last["objective"][:, 0], history=history, accepted=accepted,
                     table=last["table"][:, 0], length=last["length"][:, 0])
 

@@ -11,6 +11,7 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     objectives(inst, rows, variant)             makespan / completion time and total tardiness (delay_time_sum)
     plan_of(table)                              the (r, n, m) columns of a table: the explicit schedule it records
     decode(batch, plan, moves, n_cand)          times and objectives of explicit schedules, on the device
+    decode_dyn(batch, plan, moves, n_cand)      the same on MO_DFJSP: breakdown shifts, and energy as a third objective
     apply_moves(plan, moves)                    the plans that decode's moves stand for, materialised
     pair_move(u, v, w)                          the MOVE_PAIR that puts rows u and v, v first, behind row w
     critical(batch, table, n_cand, max_moves)   tails, critical flags, one critical path and its moves, on the device
@@ -299,8 +300,22 @@ def decode(batch, plan, moves=None, n_cand=1, want_table=False):
     dw <= 32767: a negative third field is refused, status 4).
     Returns dict(objective=int64[N, n_cand, 2] (makespan, total tardiness), status=int32[N, n_cand] (DECODE_*),
     table=int32[N, n_cand, cap, 6] or None, length=int32[N, n_cand]), device tensors; a failed candidate has objective -1,
-    length 0 and a table of -1.  ValueError for shapes that do not fit; FjspError where the library refuses (MO_DFJSP,
-    an instance whose per-candidate state exceeds the limit of include/fjsp_amd.h)."""
+    length 0 and a table of -1.  ValueError for shapes that do not fit; FjspError where the library refuses (MO_DFJSP, which
+    decode_dyn decodes; an instance whose per-candidate state exceeds the limit of include/fjsp_amd.h)."""
+    return _decode(batch, plan, moves, n_cand, want_table, "fjsp_schedule_decode", 2)
+
+
+def decode_dyn(batch, plan, moves=None, n_cand=1, want_table=False):
+    """decode on a MO_DFJSP batch (fjsp_schedule_decode_dyn): the same arguments, checks, status codes and results, the
+    times shifted by the machines' breakdown windows as MO_DFJSP_breakdown.py:203-247 shifts them, and objective=int64[N,
+    n_cand, 3] = (makespan, total tardiness, energy), -1 on failure.  Every operation is dispatched at max(its job's
+    release, its machine's end); the contract is in include/fjsp_amd.h.  FjspError on a batch that is not MO_DFJSP.
+    Energy is an objective of the decode only: objectives() cannot compute it from a table, because a dispatch that a
+    window swallows leaves its dispatch time, which the idle energy is measured to, in no row."""
+    return _decode(batch, plan, moves, n_cand, want_table, "fjsp_schedule_decode_dyn", 3)
+
+
+def _decode(batch, plan, moves, n_cand, want_table, entry, n_obj):
     import torch
     from ._capi import check, ptr
     b = getattr(batch, "batch", batch)
@@ -323,12 +338,11 @@ def decode(batch, plan, moves=None, n_cand=1, want_table=False):
         if tuple(moves.shape) != (b.N, n_cand, 3):
             raise ValueError("moves must have shape %s, got %s" % ((b.N, n_cand, 3), tuple(moves.shape)))
         moves = moves.to(device=b.device, dtype=torch.int32).contiguous()
-    objective = torch.empty(b.N, n_cand, 2, dtype=torch.int64, device=b.device)
+    objective = torch.empty(b.N, n_cand, n_obj, dtype=torch.int64, device=b.device)
     status = torch.empty(b.N, n_cand, dtype=torch.int32, device=b.device)
     length = torch.empty(b.N, n_cand, dtype=torch.int32, device=b.device)
     table = torch.empty(b.N, n_cand, cap, 6, dtype=torch.int32, device=b.device) if want_table else None
-    check(b._lib.fjsp_schedule_decode(b._h, ptr(plan), q_plans, ptr(moves), n_cand, ptr(objective), ptr(status), ptr(table),
-                                      ptr(length), b._stream()))
+    check(getattr(b._lib, entry)(b._h, ptr(plan), q_plans, ptr(moves), n_cand, ptr(objective), ptr(status), ptr(table), ptr(length), b._stream()))
     return dict(objective=objective, status=status, table=table, length=length)
 
 

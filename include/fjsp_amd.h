@@ -762,13 +762,59 @@ int fjsp_pareto_select(const double *d_obj, const uint8_t *d_valid, int32_t n_sr
  * up to about 1000 jobs.  fjsp_schedule_decode_group: the candidates one workgroup decodes (256, 128, 64 or 32), 0 where
  * the state does not fit or the batch is MO_DFJSP.
  * FJSP_E_ARG: a null e, d_plan, d_objective or d_status, n_cand < 1, q_plans neither 1 nor n_cand, N * n_cand >= 2^31.
- * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP (breakdown shifts and energy are not decoded), a state beyond the limit.
+ * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP (breakdown shifts and energy: fjsp_schedule_decode_dyn decodes those), a
+ * state beyond the limit.
  * FJSP_E_STATE: a generated handle whose last regenerate failed. */
 int fjsp_schedule_decode(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
                          int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream);
 /* rows per plan = fjsp_env_schedule_capacity's cap (operations of the batch's largest instance), recording on or off */
 int fjsp_schedule_decode_capacity(const fjsp_env *e);
 int fjsp_schedule_decode_group(const fjsp_env *e);
+
+/* Explicit schedules of MO_DFJSP decoded on the device (schedule.decode_dyn, policy_search.improve on such a batch;
+ * csrc/fjsp_decode.hip): fjsp_schedule_decode with the machines' breakdown windows and the third objective, energy.
+ * Arguments, plans, moves, the checks, the status codes 0 to 4, d_table, d_len and the handling of a failed candidate are
+ * fjsp_schedule_decode's, unchanged; d_objective is i64[N][n_cand][3] = (latest time_end, total tardiness, energy), all
+ * -1 on failure.  Plan capacity: fjsp_schedule_decode_capacity.
+ *
+ * Decoding (MO_DFJSP_breakdown.py:203-256 without the event clock).  Jobs are ready at their order's arrival, machines
+ * are free at 0 and have no last task.  Then per plan row (r, n, m), with stage the job's next stage and k its operation
+ * type:
+ *   d = p[k][m], t = max(ready[job], free[m]); begin = t, end = machine_end = t + d.
+ *   Machine m's windows (bs, be) are walked in file order from the first, t fixed, end as it stands at that window:
+ *     bs <= t < be        begin += be - t, end += be - t, machine_end = end   (dispatched inside the window)
+ *     else t < bs < end   end += be - bs, machine_end = end                   (the window interrupts the operation)
+ *     else bs == end      machine_end += be - bs                              (the table's end does not move)
+ *     else bs > end       the walk stops.
+ *   energy += power[k][m] * d; if the machine had a task before, energy += (t - last_end[m]) * idle_power[m] -- the gap
+ *   is measured to the dispatch time t, not to the shifted begin; then last_end[m] = end.
+ *   ready[job] = free[m] = machine_end: the job's next stage waits for the machine's end too (the reference re-queues the
+ *   job when machine.time_end is reached).
+ *   makespan = max(makespan, end); at a job's last stage tardiness += max(0, end - due), due = the order's delivery time
+ *   (class_MODFJSP.py:224).  The table row is (r, stage, n, m, begin, end).
+ * This is the schedule the environment dispatches when every operation is dispatched at max(ready, free): it returns a
+ * recorded single-order episode's table, its energy_consumption, completion time and tardiness.  With several orders it is
+ * tighter than the environment where an order arrives between two events: the environment releases the order's jobs at
+ * the first event time at or after the arrival, the decode at the arrival.
+ *
+ * 32-bit clocks, exact, for windows with 0 <= bs < be (what the reference's files hold).  No clock can overflow: a window
+ * stretches a task on its machine at most once per candidate, because a window that moved anything leaves free[m] >= be,
+ * every later t on that machine is then >= be > bs, and none of its three cases can hold again; so every time is at most
+ * last arrival + sum of p + sum of the window lengths, which fjsp_env_create bounds below 2^31 (the sum over EVERY
+ * operation at the largest p and EVERY window).  Energy is int64: at most 65535 terms power x d, each below 2^31 by
+ * create's rule, and per machine idle power x (its gaps, which add up to at most the clock bound): below 2^63 on 32
+ * machines for idle powers below 2^26 (the reference's are below 100).
+ *
+ * Limit: a candidate's state is 5 bytes per job (jobs of the largest instance rounded up to 16) + 8 per machine (free and
+ * last_end), at most 5120 bytes, grouped by fjsp_schedule_decode's rule on that figure; fjsp_schedule_decode_dyn_group:
+ * the candidates one workgroup decodes, 0 where the state does not fit or the batch is not MO_DFJSP.
+ * FJSP_E_ARG, FJSP_E_STATE: as fjsp_schedule_decode.  FJSP_E_UNSUPPORTED: a handle that is not FJSP_VARIANT_MO_DFJSP
+ * (fjsp_schedule_decode decodes those), a state beyond the limit.
+ * Not decoded for MO_DFJSP: fjsp_schedule_critical and fjsp_schedule_search keep refusing it -- the critical-path
+ * analysis is additive in durations and window shifts are not. */
+int fjsp_schedule_decode_dyn(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
+                             int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream);
+int fjsp_schedule_decode_dyn_group(const fjsp_env *e);
 
 /* Critical paths of decoded schedules (schedule.critical, policy_search.improve(neighbourhood=...); csrc/fjsp_decode.hip):
  * tails, critical flags, one critical path and that path's neighbourhood as moves fjsp_schedule_decode takes, n_cand
