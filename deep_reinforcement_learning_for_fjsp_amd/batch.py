@@ -695,6 +695,11 @@ class EnvBatch(object):
         is not searched (MO_DFJSP, or a working set beyond a CU's LDS)."""
         return int(self._lib.fjsp_schedule_search_lds(self._h))
 
+    def search_dyn_lds(self):
+        """LDS bytes a workgroup of policy_search.local_search takes on this MO_DFJSP batch (fjsp_schedule_search_dyn_lds);
+        0: the batch is not MO_DFJSP, or an env's working set exceeds a CU's LDS."""
+        return int(self._lib.fjsp_schedule_search_dyn_lds(self._h))
+
     def set_lp_threads(self, n_threads):
         """Host threads of the order-arrival LP service (0 = all cores).  The asynchronous service builds its worker pool
         at the first step_async and reads this once, there: call it before that."""

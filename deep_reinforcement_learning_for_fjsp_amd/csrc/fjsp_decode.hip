@@ -39,7 +39,8 @@
 //
 // fjsp_schedule_search runs hill climbing and tabu search over those two: one wavefront per env, all rounds in one launch,
 // built from the same device functions (its own head comment is at schedule_search_kernel; its barriers are those of a
-// one-wave workgroup around its LDS plan).
+// one-wave workgroup around its LDS plan).  fjsp_schedule_search_dyn is that kernel text compiled with DYN for MO_DFJSP
+// handles (schedule_search_kernel<true>): the uniform neighbourhood only, every decode decode_plan<true>, three objectives.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -67,8 +68,14 @@ struct DecodeArgs {
     int G, JW;               // candidates per workgroup; job words of a candidate (DevBatch::jcap)
 };
 
+// BW of the MO_DFJSP kernels: the windows from i_bk to the record's end -- no window index reaches past the record, whatever
+// i_bkoff holds
+__host__ __device__ inline int dyn_windows(const DevBatch &b) { return (int)((b.L.i_stride - b.L.i_bk) / 8); }
+
 // words of one candidate's state: ready[JW], the stage bytes of four jobs to a word, free[MP]
 __host__ __device__ inline int state_words(int JW, int MP) { return JW + JW / 4 + MP; }
+// the MO_DFJSP decode keeps one more word per machine behind them (the end of its last task)
+__host__ __device__ inline int dyn_state_words(int JW, int MP) { return state_words(JW, MP) + MP; }
 
 // entry 0: (kinds, operations of the instance); entry 1 + r: (first job | jobs << 16, first operation type | stages << 16)
 __global__ __launch_bounds__(64) void decode_kinds_kernel(DevBatch b, uint2 *kinds) {
@@ -473,7 +480,7 @@ __global__ __launch_bounds__(256) void schedule_critical_kernel(DevBatch b, Crit
 struct SearchArgs {
     const int32_t *plan;     // i32[N][cap][3]
     int32_t *plan_out;       // i32[N][cap][3]
-    int64_t *objective;      // i64[N][2]
+    int64_t *objective;      // i64[N][2], DYN: i64[N][3]
     int64_t *history;        // i64[rounds + 1][N]
     int32_t *accepted, *status;   // i32[N]
     int32_t *trace;          // i32[rounds][N][3], nullable
@@ -489,14 +496,28 @@ __host__ __device__ inline size_t search_words(int JW, int MP, int cap) {
     return (size_t)state_words(JW, MP) * 64 + (size_t)cap * 15 + (size_t)(cap + 3) / 4 + (size_t)kSearchMoves * 3 + 4;
 }
 
+// fjsp_schedule_search_dyn: the states a word per machine longer; rows 5 and until 1 per plan row are all that the uniform
+// neighbourhood keeps behind them (no table, inv, path, flag bytes or move list, and so no shared word for the list's length)
+__host__ __device__ inline size_t search_dyn_words(int JW, int MP, int cap) { return (size_t)dyn_state_words(JW, MP) * 64 + (size_t)cap * 6; }
+
 __device__ __forceinline__ uint32_t search_pick(uint64_t d, uint32_t n) { return (uint32_t)(((d >> 32) * (uint64_t)n) >> 32); }
 
+// DYN (fjsp_schedule_search_dyn, MO_DFJSP): every decode is decode_plan<true> on a state a word per machine longer, the
+// objective has the energy as a third entry carried beside the other two, and the neighbourhood is the uniform one: nbh is
+// 0 at compile time, so the critical block and its arrays are not in that kernel.  The template sits on the kernel itself:
+// behind a __device__ wrapper the compiler allocated the plain kernel's registers differently and its uniform round ran
+// 1.5 % slower; in this form it compiles to the instructions it had before the switch, but for a few reordered ones
+// (which is also why the best plan's update below compares first and selects the column after).
+template <bool DYN>
 __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchArgs a) {
+    constexpr int NO = DYN ? 3 : 2;
     const int q = (int)threadIdx.x, env = (int)blockIdx.x, inst = env % b.n_inst;
-    const int cap = a.cap, Q = a.n_cand, N = b.N;
+    const int cap = a.cap, Q = a.n_cand, N = b.N, nbh = DYN ? 0 : a.nbh;
     const Shop sh = shop_of(b, a.kinds, inst, a.JW);
     const State st = state_at(decode_lds, q, 64, a.JW);
-    int32_t *rows = reinterpret_cast<int32_t *>(decode_lds + (size_t)state_words(a.JW, b.MP) * 64);     // [cap][5]
+    DynShop dy{};
+    if constexpr (DYN) dy = dyn_shop_of(b, sh, st, dyn_windows(b));
+    int32_t *rows = reinterpret_cast<int32_t *>(decode_lds + (size_t)(DYN ? dyn_state_words(a.JW, b.MP) : state_words(a.JW, b.MP)) * 64);     // [cap][5]
     int32_t *until = rows + (size_t)cap * 5, *tab = until + cap, *inv = tab + (size_t)cap * 7, *path = inv + cap;
     int32_t *mvl = path + cap, *shared = mvl + kSearchMoves * 3;
     uint8_t *flags = reinterpret_cast<uint8_t *>(shared + 4);
@@ -506,21 +527,26 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
     // ---- the input plan: copied through, decoded by every lane (one address to the wave), kept by lane 0
     for (int i = q; i < cap * 3; i += 64) po[i] = pl[i];
     int L = 0;
-    long long cur_mk = 0, cur_td = 0;
-    const int st0 = decode_plan(b, sh, st, [&](int idx) { return row_at(pl, idx); }, cap, no_move(), [&](int t, const Row &x, const Step &d) {
+    long long cur_mk = 0, cur_td = 0, cur_en = 0;
+    // the chosen objective of (makespan, tardiness, energy)
+    auto chosen = [&](long long mk, long long td, long long en) { return DYN && a.col == 2 ? en : (a.col ? td : mk); };
+    const int st0 = decode_plan<DYN>(b, sh, st, [&](int idx) { return row_at(pl, idx); }, cap, no_move(), [&](int t, const Row &x, const Step &d) {
         if (q == 0) { int32_t *o = rows + (size_t)t * 5; o[0] = x.r; o[1] = x.n; o[2] = x.m; o[3] = d.k; o[4] = t; until[t] = 0; }
-    }, L, cur_mk, cur_td);
+    }, L, cur_mk, cur_td, &dy, &cur_en);
     if (st0 != 0) {                                                      // (the same in every lane)
-        if (q == 0) { a.status[env] = st0; a.accepted[env] = 0; a.objective[2 * (size_t)env] = -1; a.objective[2 * (size_t)env + 1] = -1; }
+        if (q == 0) {
+            a.status[env] = st0; a.accepted[env] = 0;
+            for (int c = 0; c < NO; ++c) a.objective[NO * (size_t)env + c] = -1;
+        }
         for (int t = q; t <= a.rounds; t += 64) a.history[(size_t)t * N + env] = -1;
         if (a.trace)
             for (int i = q; i < a.rounds * 3; i += 64) a.trace[((size_t)(i / 3) * N + env) * 3 + i % 3] = 0;
         return;
     }
     __syncthreads();
-    long long best_mk = cur_mk, best_td = cur_td;                        // of the plan in plan_out (tabu)
+    long long best_mk = cur_mk, best_td = cur_td, best_en = cur_en;      // of the plan in plan_out (tabu)
     int taken = 0, n_list = 0;
-    if (q == 0) a.history[env] = a.col ? cur_td : cur_mk;
+    if (q == 0) a.history[env] = chosen(cur_mk, cur_td, cur_en);
     const uint64_t sg = gen::draw(a.seed, (uint32_t)(a.first_env + env));
     auto lrow = [&](int idx) { const int32_t *o = rows + (size_t)idx * 5; return idx < L ? Row{o[0], o[1], o[2]} : Row{-1, -1, -1}; };
     auto write_out = [&]() {                                             // the current plan -> plan_out
@@ -531,7 +557,7 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
     };
 
     for (int t = 0; t < a.rounds; ++t) {
-        if (a.nbh != 0) {
+        if (nbh != 0) {
             // ---- the current plan's table, put into begin order, and the moves of its critical path
             long long mk, td;
             int len;
@@ -565,7 +591,7 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
 
         // ---- candidate q of the round: its draws, its move, its decode
         const uint32_t d0 = 3u * ((uint32_t)t * (uint32_t)Q + (uint32_t)q);
-        const bool from_list = a.nbh == 1 || (a.nbh == 2 && q < Q / 2);
+        const bool from_list = nbh == 1 || (nbh == 2 && q < Q / 2);
         bool masked = q >= Q || L == 0;
         int kind = 0, u = 0, third = 0;
         if (!masked) {
@@ -587,7 +613,7 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
                 kind = 2; u = (int)search_pick(gen::draw(sg, d0), (uint32_t)(L > 1 ? L - 1 : 1));
             }
         }
-        long long mk = 0, td = 0, key = 0x7fffffffffffffffLL;
+        long long mk = 0, td = 0, en = 0, key = 0x7fffffffffffffffLL;
         Move mv = no_move();
         int id_a = 0, id_b = -1;                                         // identities of the rows the move moves
         if (!masked) {
@@ -595,7 +621,7 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
             int len = 0;
             int err = 4;
             if (!mv.bad) {
-                err = decode_plan(b, sh, st, lrow, cap, mv, [](int, const Row &, const Step &) {}, len, mk, td);
+                err = decode_plan<DYN>(b, sh, st, lrow, cap, mv, [](int, const Row &, const Step &) {}, len, mk, td, &dy, &en);
                 if (move_past(mv, len)) err = 4;
             }
             bool ok = err == 0;
@@ -604,9 +630,9 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
                 if (kind != 1) id_b = rows[(size_t)(kind == 2 ? u + 1 : mv.pv) * 5 + 4];
                 const bool same = kind == 1 ? third == rows[(size_t)u * 5 + 2] : mv.kind == 0;
                 const bool tabu = until[id_a] > t || (id_b >= 0 && until[id_b] > t);
-                ok = !same && (!tabu || (a.col ? td : mk) < (a.col ? best_td : best_mk));
+                ok = !same && (!tabu || chosen(mk, td, en) < chosen(best_mk, best_td, best_en));
             }
-            if (ok) key = a.col ? td : mk;
+            if (ok) key = chosen(mk, td, en);
         }
         // ---- the least (objective, q) of the wave
         int wq = q;
@@ -615,13 +641,14 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
             const int oq = __shfl_xor(wq, off);
             if (ok2 < key || (ok2 == key && oq < wq)) { key = ok2; wq = oq; }
         }
-        const long long cur = a.col ? cur_td : cur_mk;
+        const long long cur = chosen(cur_mk, cur_td, cur_en);
         const bool take = key != 0x7fffffffffffffffLL && (a.accept == 2 || key < cur || (key == cur && a.accept == 1));
         int t_kind = 0, t_u = 0, t_third = 0;
         if (take) {                                                      // (the same in every lane)
             t_kind = __shfl(kind, wq); t_u = __shfl(u, wq); t_third = __shfl(third, wq);
             const int e_kind = __shfl(mv.kind, wq), pu = __shfl(mv.pu, wq), pw = __shfl(mv.pw, wq), pv = __shfl(mv.pv, wq);
             cur_mk = __shfl(mk, wq); cur_td = __shfl(td, wq);
+            if constexpr (DYN) cur_en = __shfl(en, wq);
             const int w_a = __shfl(id_a, wq), w_b = __shfl(id_b, wq);
             __syncthreads();                                             // every lane has read the rows of its candidate
             if (a.accept == 2 && q == 0) {
@@ -655,18 +682,21 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
             }
             ++taken;
             __syncthreads();
-            if (a.accept == 2 && (a.col ? cur_td < best_td : cur_mk < best_mk)) { best_mk = cur_mk; best_td = cur_td; write_out(); }
+            if (a.accept == 2 && (DYN && a.col == 2 ? cur_en < best_en : (a.col ? cur_td < best_td : cur_mk < best_mk))) { best_mk = cur_mk; best_td = cur_td; best_en = cur_en; write_out(); }
         }
         if (q == 0) {
-            a.history[(size_t)(t + 1) * N + env] = a.col ? cur_td : cur_mk;
+            a.history[(size_t)(t + 1) * N + env] = chosen(cur_mk, cur_td, cur_en);
             if (a.trace) { int32_t *o = a.trace + ((size_t)t * N + env) * 3; o[0] = t_kind; o[1] = t_u; o[2] = t_third; }
         }
     }
     if (a.accept != 2) {
-        best_mk = cur_mk; best_td = cur_td;
+        best_mk = cur_mk; best_td = cur_td; best_en = cur_en;
         if (a.rounds > 0) write_out();
     }
-    if (q == 0) { a.status[env] = 0; a.accepted[env] = taken; a.objective[2 * (size_t)env] = best_mk; a.objective[2 * (size_t)env + 1] = best_td; }
+    if (q == 0) {
+        a.status[env] = 0; a.accepted[env] = taken; a.objective[NO * (size_t)env] = best_mk; a.objective[NO * (size_t)env + 1] = best_td;
+        if constexpr (DYN) a.objective[NO * (size_t)env + 2] = best_en;
+    }
 }
 
 
@@ -678,8 +708,9 @@ int decode_group(size_t bytes) {
     return 32 * bytes <= kLdsCu ? 32 : 0;
 }
 int decode_group(const DevBatch &b) { return decode_group((size_t)state_words(b.jcap, b.MP) * 4); }
-// the MO_DFJSP decode keeps one more word per machine (the end of its last task)
-size_t dyn_state_bytes(const DevBatch &b) { return (size_t)(state_words(b.jcap, b.MP) + b.MP) * 4; }
+size_t dyn_state_bytes(const DevBatch &b) { return (size_t)dyn_state_words(b.jcap, b.MP) * 4; }
+// BW of the MO_DFJSP kernels: the windows from i_bk to the record's end -- no window index reaches past the record, whatever
+// i_bkoff holds
 
 }  // namespace
 
@@ -719,8 +750,7 @@ static int schedule_decode(bool dyn, fjsp_env *e, const int32_t *d_plan, int32_t
     }
     const DecodeArgs a{d_plan, d_moves, d_objective, d_status, d_table, d_len, e->d_decode_kinds, total, (int)n_cand, (int)q_plans, e->ops_max, G, b.jcap};
     const dim3 grid((unsigned)((total + G - 1) / G)), block((unsigned)(G < 64 ? 64 : G));
-    // dyn: the windows from i_bk to the record's end -- no window index reaches past the record, whatever i_bkoff holds
-    const int rc = dyn ? launch(schedule_decode_dyn_kernel, grid, block, bytes * (size_t)G, st, b, a, (int)((b.L.i_stride - b.L.i_bk) / 8))
+    const int rc = dyn ? launch(schedule_decode_dyn_kernel, grid, block, bytes * (size_t)G, st, b, a, dyn_windows(b))
                        : launch(schedule_decode_kernel, grid, block, bytes * (size_t)G, st, b, a);
     if (rc != 0) { set_error(std::string(dyn ? "schedule_decode_dyn_kernel" : "schedule_decode_kernel") + " launch failed"); return FJSP_E_HIP; }
     return FJSP_OK;
@@ -780,6 +810,12 @@ extern "C" int fjsp_schedule_search_lds(const fjsp_env *e) {
     return bytes <= kLdsCu ? (int)bytes : 0;
 }
 
+extern "C" int fjsp_schedule_search_dyn_lds(const fjsp_env *e) {
+    if (!e || e->b.variant != FJSP_VARIANT_MO_DFJSP || e->ops_max <= 0) return 0;
+    const size_t bytes = search_dyn_words(e->b.jcap, e->b.MP, e->ops_max) * 4;
+    return bytes <= kLdsCu ? (int)bytes : 0;
+}
+
 extern "C" int fjsp_search_draws(uint64_t seed, int64_t env, uint32_t first, int32_t n, uint64_t *h_out) {
     if (n < 0 || (n > 0 && !h_out)) { set_error("fjsp_search_draws: needs n >= 0 and an output array"); return FJSP_E_ARG; }
     const uint64_t sg = gen::draw(seed ^ FJSP_SEARCH_STREAM, (uint32_t)env);
@@ -787,30 +823,37 @@ extern "C" int fjsp_search_draws(uint64_t seed, int64_t env, uint32_t first, int
     return FJSP_OK;
 }
 
-extern "C" int fjsp_schedule_search(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, int32_t objective, int32_t neighbourhood,
-                                    int32_t accept, int32_t tenure, uint64_t seed, int64_t first_env, int32_t *d_plan_out, int64_t *d_objective,
-                                    int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream) {
+// fjsp_schedule_search (dyn false) and fjsp_schedule_search_dyn (dyn true, neighbourhood 0): each takes the handles the
+// other refuses
+static int schedule_search(bool dyn, fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, int32_t objective, int32_t neighbourhood,
+                           int32_t accept, int32_t tenure, uint64_t seed, int64_t first_env, int32_t *d_plan_out, int64_t *d_objective,
+                           int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream) {
+    const std::string fn = dyn ? "fjsp_schedule_search_dyn" : "fjsp_schedule_search";
     if (!e || !d_plan || !d_plan_out || !d_objective || !d_history || !d_accepted || !d_status) {
-        set_error("fjsp_schedule_search: null env, plan or output pointer"); return FJSP_E_ARG;
+        set_error(fn + ": null env, plan or output pointer"); return FJSP_E_ARG;
     }
-    if (e->b.variant == FJSP_VARIANT_MO_DFJSP) {
-        set_error("fjsp_schedule_search: MO_DFJSP batches are not decoded (breakdown shifts and energy)"); return FJSP_E_UNSUPPORTED;
+    if ((e->b.variant == FJSP_VARIANT_MO_DFJSP) != dyn) {
+        set_error(dyn ? fn + ": searches MO_DFJSP batches only (breakdown shifts and energy): fjsp_schedule_search searches the others"
+                      : fn + ": MO_DFJSP batches are not searched here (breakdown shifts and energy): fjsp_schedule_search_dyn searches them");
+        return FJSP_E_UNSUPPORTED;
     }
-    if (e->gen_failed) { set_error("fjsp_schedule_search: the last regenerate of this handle failed"); return FJSP_E_STATE; }
-    if (n_cand < 1 || n_cand > 64 || rounds < 0 || tenure < 0) { set_error("fjsp_schedule_search: needs n_cand in 1..64, rounds >= 0 and tenure >= 0"); return FJSP_E_ARG; }
-    if (objective < 0 || objective > 1 || neighbourhood < 0 || neighbourhood > 2 || accept < 0 || accept > 2) {
-        set_error("fjsp_schedule_search: objective is 0 or 1, neighbourhood and accept are 0, 1 or 2"); return FJSP_E_ARG;
+    if (e->gen_failed) { set_error(fn + ": the last regenerate of this handle failed"); return FJSP_E_STATE; }
+    if (n_cand < 1 || n_cand > 64 || rounds < 0 || tenure < 0) { set_error(fn + ": needs n_cand in 1..64, rounds >= 0 and tenure >= 0"); return FJSP_E_ARG; }
+    if (objective < 0 || objective > (dyn ? 2 : 1) || neighbourhood < 0 || neighbourhood > 2 || accept < 0 || accept > 2) {
+        set_error(dyn ? fn + ": objective and accept are 0, 1 or 2" : fn + ": objective is 0 or 1, neighbourhood and accept are 0, 1 or 2");
+        return FJSP_E_ARG;
     }
-    if (neighbourhood != 0 && objective != 0) { set_error("fjsp_schedule_search: the critical neighbourhoods follow the makespan: objective must be 0"); return FJSP_E_ARG; }
+    if (neighbourhood != 0 && objective != 0) { set_error(fn + ": the critical neighbourhoods follow the makespan: objective must be 0"); return FJSP_E_ARG; }
     if (3ULL * (unsigned long long)rounds * (unsigned long long)n_cand > 0xFFFFFFFFULL) {
-        set_error("fjsp_schedule_search: 3 x rounds x n_cand draws per env exceed 2^32 - 1"); return FJSP_E_ARG;
+        set_error(fn + ": 3 x rounds x n_cand draws per env exceed 2^32 - 1"); return FJSP_E_ARG;
     }
     const DevBatch &b = e->b;
-    if (e->ops_max <= 0) { set_error("fjsp_schedule_search: no operations"); return FJSP_E_ARG; }
-    const size_t lds = search_words(b.jcap, b.MP, e->ops_max) * 4;
+    if (e->ops_max <= 0) { set_error(fn + ": no operations"); return FJSP_E_ARG; }
+    const size_t lds = (dyn ? search_dyn_words(b.jcap, b.MP, e->ops_max) : search_words(b.jcap, b.MP, e->ops_max)) * 4;
     if (lds > kLdsCu) {
-        set_error("fjsp_schedule_search: an env's working set (64 candidate states of " + std::to_string(state_words(b.jcap, b.MP) * 4) +
-                  " bytes and 61 bytes per operation: " + std::to_string(lds) + " bytes) exceeds the " + std::to_string(kLdsCu) + " bytes of a CU's LDS");
+        set_error(fn + ": an env's working set (64 candidate states of " + std::to_string((dyn ? dyn_state_words(b.jcap, b.MP) : state_words(b.jcap, b.MP)) * 4) +
+                  " bytes and " + (dyn ? "24" : "61") + " bytes per operation: " + std::to_string(lds) + " bytes) exceeds the " + std::to_string(kLdsCu) +
+                  " bytes of a CU's LDS");
         return FJSP_E_UNSUPPORTED;
     }
     DeviceGuard guard(e->device);
@@ -821,8 +864,22 @@ extern "C" int fjsp_schedule_search(fjsp_env *e, const int32_t *d_plan, int32_t 
     }
     const SearchArgs a{d_plan, d_plan_out, d_objective, d_history, d_accepted, d_status, d_trace, e->d_decode_kinds, seed ^ FJSP_SEARCH_STREAM,
                        (long long)first_env, (int)rounds, (int)n_cand, (int)objective, (int)neighbourhood, (int)accept, (int)tenure, e->ops_max, b.jcap};
-    if (launch(schedule_search_kernel, dim3((unsigned)b.N), dim3(64), lds, st, b, a) != 0) {
-        set_error("schedule_search_kernel launch failed"); return FJSP_E_HIP;
-    }
+    const int rc = dyn ? launch(schedule_search_kernel<true>, dim3((unsigned)b.N), dim3(64), lds, st, b, a)
+                       : launch(schedule_search_kernel<false>, dim3((unsigned)b.N), dim3(64), lds, st, b, a);
+    if (rc != 0) { set_error(std::string(dyn ? "schedule_search_kernel<true>" : "schedule_search_kernel<false>") + " launch failed"); return FJSP_E_HIP; }
     return FJSP_OK;
+}
+
+extern "C" int fjsp_schedule_search(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, int32_t objective, int32_t neighbourhood,
+                                    int32_t accept, int32_t tenure, uint64_t seed, int64_t first_env, int32_t *d_plan_out, int64_t *d_objective,
+                                    int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream) {
+    return schedule_search(false, e, d_plan, rounds, n_cand, objective, neighbourhood, accept, tenure, seed, first_env, d_plan_out, d_objective,
+                           d_history, d_accepted, d_status, d_trace, stream);
+}
+
+extern "C" int fjsp_schedule_search_dyn(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, int32_t objective, int32_t accept,
+                                        int32_t tenure, uint64_t seed, int64_t first_env, int32_t *d_plan_out, int64_t *d_objective,
+                                        int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream) {
+    return schedule_search(true, e, d_plan, rounds, n_cand, objective, 0, accept, tenure, seed, first_env, d_plan_out, d_objective, d_history,
+                           d_accepted, d_status, d_trace, stream);
 }

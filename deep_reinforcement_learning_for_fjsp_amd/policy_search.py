@@ -32,7 +32,8 @@ slowly.
   reassignments and adjacent swaps, or drawn from the neighbourhood of the plan's critical path (schedule.critical,
   fjsp_schedule_critical).  A MO_DFJSP batch is decoded with its breakdown windows and energy (schedule.decode_dyn,
   fjsp_schedule_decode_dyn): "energy" is an objective there, and the moves are the uniform ones.
-- local_search: improve's search, descent or tabu, as one launch for all its rounds (schedule.search, fjsp_schedule_search):
+- local_search: improve's search, descent or tabu, as one launch for all its rounds (schedule.search, fjsp_schedule_search;
+  on a MO_DFJSP batch schedule.search_dyn, fjsp_schedule_search_dyn: uniform neighbourhood, "energy" an objective):
   a wavefront per env, a lane per neighbour, the plan in LDS, on a counter-based draw stream that shards reproduce.
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
@@ -690,30 +691,43 @@ def local_search(batch, plan, rounds, neighbours=64, objective="makespan", seed=
     move is admissible only where it beats the best plan seen (aspiration), moves that change nothing are not candidates,
     and the best plan seen is returned.  neighbourhood: as improve; "critical" and "mixed" need objective "makespan".
 
-    Returns improve's dict -- plan=int32[N, cap, 3], objective=int64[N, 2] of it, history=int64[rounds + 1, N] the chosen
-    objective of the input plan and of the current plan after every round, accepted=int64[N], table=int32[N, cap, 6] and
-    length=int32[N] of the returned plans (one schedule.decode) -- and status=int32[N] (zeros), with trace=True also trace=
-    int32[rounds, N, 3], the move each round took ((0, 0, 0): none; indices into the plan the round started from).
+    A MO_DFJSP batch is searched by schedule.search_dyn (fjsp_schedule_search_dyn) and decoded by schedule.decode_dyn:
+    objective may also be "energy", the returned objective has that third column, and neighbourhood must be "uniform", as
+    in improve.
+
+    Returns improve's dict -- plan=int32[N, cap, 3], objective=int64[N, 2] of it ([N, 3] on MO_DFJSP), history=int64[rounds
+    + 1, N] the chosen objective of the input plan and of the current plan after every round, accepted=int64[N], table=
+    int32[N, cap, 6] and length=int32[N] of the returned plans (one schedule.decode or decode_dyn) -- and status=int32[N]
+    (zeros), with trace=True also trace=int32[rounds, N, 3], the move each round took ((0, 0, 0): none; indices into the
+    plan the round started from).
     ValueError for arguments improve refuses, neighbours > 64, tenure < 0 and a plan that does not decode; FjspError
-    where the library refuses (MO_DFJSP, an env's working set beyond a CU's LDS: EnvBatch.search_lds)."""
+    where the library refuses (an env's working set beyond a CU's LDS: EnvBatch.search_lds, search_dyn_lds)."""
     from . import schedule as sch
     b, _ = _unwrap(batch, None)
-    if objective not in sch.SEARCH_OBJECTIVES:
-        raise ValueError("objective must be one of %s" % (sch.SEARCH_OBJECTIVES,))
+    dyn = b.variant == sch.VARIANT_MO_DFJSP
+    objectives = sch.SEARCH_DYN_OBJECTIVES if dyn else sch.SEARCH_OBJECTIVES
+    if objective not in objectives:
+        raise ValueError("objective must be one of %s" % (objectives,))
     if neighbourhood not in sch.SEARCH_NEIGHBOURHOODS:
         raise ValueError("neighbourhood must be one of %s" % (sch.SEARCH_NEIGHBOURHOODS,))
     if accept not in sch.SEARCH_ACCEPT:
         raise ValueError("accept must be one of %s" % (sch.SEARCH_ACCEPT,))
+    if dyn and neighbourhood != "uniform":
+        raise ValueError("neighbourhood %r: critical paths are not analysed on MO_DFJSP (breakdown shifts are not additive in the "
+                         "durations): neighbourhood must be 'uniform'" % (neighbourhood,))
     if neighbourhood != "uniform" and objective != "makespan":
         raise ValueError("neighbourhood %r follows the critical path of the makespan: objective must be 'makespan'" % (neighbourhood,))
     rounds, Q, tenure = int(rounds), int(neighbours), int(tenure)
     if rounds < 0 or not 1 <= Q <= sch.SEARCH_MAX_NEIGHBOURS or tenure < 0:
         raise ValueError("local_search needs rounds >= 0, neighbours in 1..%d and tenure >= 0" % sch.SEARCH_MAX_NEIGHBOURS)
-    res = sch.search(b, plan, rounds, Q, sch.SEARCH_OBJECTIVES.index(objective), sch.SEARCH_NEIGHBOURHOODS.index(neighbourhood),
-                     sch.SEARCH_ACCEPT.index(accept), tenure, seed, trace)
+    if dyn:
+        res = sch.search_dyn(b, plan, rounds, Q, objectives.index(objective), sch.SEARCH_ACCEPT.index(accept), tenure, seed, trace)
+    else:
+        res = sch.search(b, plan, rounds, Q, objectives.index(objective), sch.SEARCH_NEIGHBOURHOODS.index(neighbourhood),
+                         sch.SEARCH_ACCEPT.index(accept), tenure, seed, trace)
     if bool((res["status"] != 0).any()):
         raise ValueError("local_search: a plan does not decode (status %s)" % sorted(set(res["status"].tolist()) - {0}))
-    last = sch.decode(b, res["plan"], want_table=True)
+    last = (sch.decode_dyn if dyn else sch.decode)(b, res["plan"], want_table=True)
     out = dict(plan=res["plan"], objective=res["objective"], history=res["history"], accepted=res["accepted"].to(torch.int64),
                table=last["table"][:, 0], length=last["length"][:, 0], status=res["status"])
     if trace:

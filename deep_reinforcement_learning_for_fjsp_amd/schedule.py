@@ -17,6 +17,7 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     critical(batch, table, n_cand, max_moves)   tails, critical flags, one critical path and its moves, on the device
     begin_order(table)                          the same schedule with its rows sorted by begin: (plan, table)
     search(batch, plan, rounds, n_cand, ...)    hill climbing / tabu search, all rounds in one launch (fjsp_schedule_search)
+    search_dyn(batch, plan, rounds, n_cand, ...) the same on MO_DFJSP: uniform neighbourhood, energy as a third objective
     search_draws(seed, env, first, n)           the draw stream of that search, on the host
 
 `inst` is anything with the instance arrays of instances.InstanceArrays: Jr[R], p[K][M] (0 = ineligible),
@@ -412,6 +413,7 @@ def begin_order(table):
 
 
 SEARCH_OBJECTIVES = ("makespan", "tardiness")
+SEARCH_DYN_OBJECTIVES = ("makespan", "tardiness", "energy")
 SEARCH_NEIGHBOURHOODS = ("uniform", "critical", "mixed")
 SEARCH_ACCEPT = ("strict", "sideways", "tabu")
 SEARCH_MAX_NEIGHBOURS = 64
@@ -436,6 +438,17 @@ def search(batch, plan, rounds, n_cand, objective=0, neighbourhood=0, accept=1, 
     are the indices of SEARCH_OBJECTIVES, SEARCH_NEIGHBOURHOODS and SEARCH_ACCEPT.  Passes batch.first_env.  Returns dict(plan=
     int32[N, cap, 3], objective=int64[N, 2], history=int64[rounds + 1, N], accepted=int32[N], status=int32[N], trace=
     int32[rounds, N, 3] or None), device tensors.  ValueError for a plan of another shape; FjspError where the library refuses."""
+    return _search(batch, plan, rounds, "fjsp_schedule_search", 2, (int(n_cand), int(objective), int(neighbourhood), int(accept), int(tenure)), seed, trace)
+
+
+def search_dyn(batch, plan, rounds, n_cand, objective=0, accept=1, tenure=0, seed=0, trace=False):
+    """search on a MO_DFJSP batch (fjsp_schedule_search_dyn): the uniform neighbourhood, every decode decode_dyn's, objective
+    an index of SEARCH_DYN_OBJECTIVES.  The same draws, accept modes and dict, with objective=int64[N, 3] (makespan, total
+    tardiness, energy).  FjspError on a batch that is not MO_DFJSP."""
+    return _search(batch, plan, rounds, "fjsp_schedule_search_dyn", 3, (int(n_cand), int(objective), int(accept), int(tenure)), seed, trace)
+
+
+def _search(batch, plan, rounds, entry, n_obj, codes, seed, trace):
     import torch
     from ._capi import check, ptr
     b = getattr(batch, "batch", batch)
@@ -446,11 +459,10 @@ def search(batch, plan, rounds, n_cand, objective=0, neighbourhood=0, accept=1, 
         raise ValueError("plan must have shape %s, got %s" % ((b.N, cap, 3), tuple(plan.shape)))
     plan = plan.to(device=b.device, dtype=torch.int32).contiguous()
     rows = max(int(rounds), 0)
-    out = dict(plan=torch.empty_like(plan), objective=torch.empty(b.N, 2, dtype=torch.int64, device=b.device),
+    out = dict(plan=torch.empty_like(plan), objective=torch.empty(b.N, n_obj, dtype=torch.int64, device=b.device),
                history=torch.empty(rows + 1, b.N, dtype=torch.int64, device=b.device),
                accepted=torch.empty(b.N, dtype=torch.int32, device=b.device), status=torch.empty(b.N, dtype=torch.int32, device=b.device),
                trace=torch.empty(rows, b.N, 3, dtype=torch.int32, device=b.device) if trace else None)
-    check(b._lib.fjsp_schedule_search(b._h, ptr(plan), int(rounds), int(n_cand), int(objective), int(neighbourhood), int(accept), int(tenure),
-                                      int(seed) & (2 ** 64 - 1), int(b.first_env), ptr(out["plan"]), ptr(out["objective"]), ptr(out["history"]),
-                                      ptr(out["accepted"]), ptr(out["status"]), ptr(out["trace"]), b._stream()))
+    check(getattr(b._lib, entry)(b._h, ptr(plan), int(rounds), *codes, int(seed) & (2 ** 64 - 1), int(b.first_env), ptr(out["plan"]),
+                                 ptr(out["objective"]), ptr(out["history"]), ptr(out["accepted"]), ptr(out["status"]), ptr(out["trace"]), b._stream()))
     return out

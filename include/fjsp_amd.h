@@ -810,8 +810,9 @@ int fjsp_schedule_decode_group(const fjsp_env *e);
  * the candidates one workgroup decodes, 0 where the state does not fit or the batch is not MO_DFJSP.
  * FJSP_E_ARG, FJSP_E_STATE: as fjsp_schedule_decode.  FJSP_E_UNSUPPORTED: a handle that is not FJSP_VARIANT_MO_DFJSP
  * (fjsp_schedule_decode decodes those), a state beyond the limit.
- * Not decoded for MO_DFJSP: fjsp_schedule_critical and fjsp_schedule_search keep refusing it -- the critical-path
- * analysis is additive in durations and window shifts are not. */
+ * No critical paths for MO_DFJSP: fjsp_schedule_critical refuses it, and so do the critical neighbourhoods of
+ * fjsp_schedule_search with the whole of that entry -- the critical-path analysis is additive in durations and window
+ * shifts are not.  The uniform neighbourhood needs a decode only: fjsp_schedule_search_dyn searches MO_DFJSP with it. */
 int fjsp_schedule_decode_dyn(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
                              int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream);
 int fjsp_schedule_decode_dyn_group(const fjsp_env *e);
@@ -897,14 +898,50 @@ int fjsp_schedule_critical(fjsp_env *e, const int32_t *d_table, int32_t n_cand, 
  * sum in bytes, 0 where it does not fit or the batch is MO_DFJSP.
  * FJSP_E_ARG: a null e, d_plan or output other than d_trace, n_cand outside 1..64, rounds < 0, tenure < 0, an objective
  * outside 0..1, a neighbourhood or accept outside 0..2, neighbourhood != 0 with objective != 0, 3 x rounds x n_cand > 2^32 - 1.
- * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP, a working set beyond the limit (the message gives the bytes).  FJSP_E_STATE: a
- * generated handle whose last regenerate failed. */
+ * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP (fjsp_schedule_search_dyn searches those), a working set beyond the limit (the
+ * message gives the bytes).  FJSP_E_STATE: a generated handle whose last regenerate failed. */
 #define FJSP_SEARCH_STREAM 0x8CB92BA72F3D8DD7ULL
 int fjsp_schedule_search(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, int32_t objective, int32_t neighbourhood,
                          int32_t accept, int32_t tenure, uint64_t seed, int64_t first_env, int32_t *d_plan_out, int64_t *d_objective,
                          int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream);
 int fjsp_schedule_search_lds(const fjsp_env *e);
 int fjsp_search_draws(uint64_t seed, int64_t env, uint32_t first, int32_t n, uint64_t *h_out);
+
+/* Hill climbing and tabu search on explicit schedules of MO_DFJSP, every round of every env in ONE launch (schedule.search_dyn,
+ * policy_search.local_search on such a batch; csrc/fjsp_decode.hip, schedule_search_kernel<true>: that kernel's text
+ * compiled with the MO_DFJSP decode).  The contract is fjsp_schedule_search's, restated where it differs;
+ * tests/search_dyn_reference.py restates it in numpy, bit for bit.
+ *
+ * Arguments: fjsp_schedule_search's without `neighbourhood`.  Only the uniform neighbourhood exists here (the critical ones
+ * need tails that add up along a path, and window shifts do not): the plan is never reordered and candidate q of a round
+ * is drawn as neighbourhood 0 draws it.  objective is 0, 1 or 2: makespan, total tardiness, energy.
+ * Decoding: every decode -- the input plan, each candidate's move applied while the plan is read -- is
+ * fjsp_schedule_decode_dyn's rule, windows and energy included.
+ * Draws: the same stream, s_g = draw(seed ^ FJSP_SEARCH_STREAM, (uint32_t)g), candidate q of round t owns draws
+ * 3 (t n_cand + q) + c; fjsp_search_draws serves both entries, and a shard [k, k + n) with first_env = k reproduces those
+ * envs of the whole batch.
+ * Selection and accept modes: unchanged.  The winner is the least chosen objective among the unmasked candidates of
+ * status 0, the lowest q among equals; accept 0 strict, 1 sideways, 2 tabu with until[identity], aspiration against the
+ * best chosen objective seen, no-op moves masked, until = t + 1 + tenure saturating at 2^31 - 1; the best plan is replaced
+ * only on strict improvement of the chosen objective.  The other two objectives travel with the plans and decide nothing.
+ * Outputs: d_objective i64[N][3] = the returned plan's (makespan, total tardiness, energy), all -1 for an env whose input
+ * plan does not decode; d_history i64[rounds + 1][N] of the chosen column; d_plan_out, d_accepted, d_status and d_trace
+ * (nullable) as fjsp_schedule_search writes them; an env whose plan fails is copied through and the others are not
+ * affected.
+ *
+ * Stream-ordered, no host synchronisation, no atomics, two launches for any number of rounds.
+ * Limit: 64 candidate states of fjsp_schedule_decode_dyn (5 bytes per job rounded up to 16 jobs + 8 per machine) and 24
+ * bytes per row of the longest plan (the row with its operation type and identity, 20, and until, 4) must fit the 160 KB
+ * of a CU's LDS: 64 x (5 x jobs16 + 8 x MP) + 24 x rows; fjsp_schedule_search_dyn_lds is that sum in bytes, 0 where it
+ * does not fit or the batch is not MO_DFJSP.
+ * FJSP_E_ARG: a null e, d_plan or output other than d_trace, n_cand outside 1..64, rounds < 0, tenure < 0, an objective
+ * or accept outside 0..2, 3 x rounds x n_cand > 2^32 - 1.  FJSP_E_UNSUPPORTED: a handle that is not FJSP_VARIANT_MO_DFJSP
+ * (fjsp_schedule_search searches those), a working set beyond the limit (the message gives the bytes).  FJSP_E_STATE: a
+ * generated handle whose last regenerate failed.  Every check runs before any device call. */
+int fjsp_schedule_search_dyn(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, int32_t objective, int32_t accept,
+                             int32_t tenure, uint64_t seed, int64_t first_env, int32_t *d_plan_out, int64_t *d_objective,
+                             int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream);
+int fjsp_schedule_search_dyn_lds(const fjsp_env *e);
 
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
