@@ -41,6 +41,9 @@
 // built from the same device functions (its own head comment is at schedule_search_kernel; its barriers are those of a
 // one-wave workgroup around its LDS plan).  fjsp_schedule_search_dyn is that kernel text compiled with DYN for MO_DFJSP
 // handles (schedule_search_kernel<true>): the uniform neighbourhood only, every decode decode_plan<true>, three objectives.
+// fjsp_schedule_search_front is the same text once more, for both families (schedule_search_kernel<DYN, FrontArgs>): the
+// uniform neighbourhood, the selection by a weighted sum of the objectives, and per env the Pareto archive of every vector
+// the search decodes, kept in LDS by the wave (ballots and prefix counts; no atomics).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -502,17 +505,57 @@ __host__ __device__ inline size_t search_dyn_words(int JW, int MP, int cap) { re
 
 __device__ __forceinline__ uint32_t search_pick(uint64_t d, uint32_t n) { return (uint32_t)(((d >> 32) * (uint64_t)n) >> 32); }
 
+// fjsp_schedule_search_front: the search steered by a weighted sum of the objectives, with the Pareto archive of everything
+// it decodes.  The kernel is schedule_search_kernel's text compiled with these arguments in place of SearchArgs.
+struct FrontArgs : SearchArgs {
+    const int64_t *weights;  // i64[N][NO]
+    int64_t *front_obj;      // i64[N][cap_front][NO]
+    int32_t *front_src;      // i32[N][cap_front][2]
+    int32_t *front_plan;     // i32[N][cap_front][cap][3], nullable
+    int32_t *front_count, *front_dropped;   // i32[N]
+    int cap_front;
+};
+
+// words of LDS of that search, both families (states = state_words or dyn_state_words): the 64 states, rows 5 and until 1
+// per plan row, and the archive -- vector (NO i64) and source (2) per slot, the round's candidate vectors (NO i64 per lane)
+// and the slot of the r-th free one (1 per lane)
+__host__ __device__ inline size_t search_front_words(int states, int cap, int cap_front, int NO) {
+    return (size_t)states * 64 + (size_t)cap * 6 + (size_t)cap_front * (size_t)(2 * NO + 2) + (size_t)64 * (size_t)(2 * NO + 1);
+}
+
+// a key's products and partial sums saturate here, one below the "no candidate" sentinel (weights and objectives are >= 0)
+constexpr long long kKeyMax = 0x7ffffffffffffffeLL;
+__device__ __forceinline__ long long key_mul(long long w, long long x) {
+    long long p;
+    return (__builtin_mul_overflow(w, x, &p) || p > kKeyMax) ? kKeyMax : p;
+}
+__device__ __forceinline__ long long key_add(long long x, long long y) {
+    long long s;
+    return (__builtin_add_overflow(x, y, &s) || s > kKeyMax) ? kKeyMax : s;
+}
+
 // DYN (fjsp_schedule_search_dyn, MO_DFJSP): every decode is decode_plan<true> on a state a word per machine longer, the
 // objective has the energy as a third entry carried beside the other two, and the neighbourhood is the uniform one: nbh is
 // 0 at compile time, so the critical block and its arrays are not in that kernel.  The template sits on the kernel itself:
 // behind a __device__ wrapper the compiler allocated the plain kernel's registers differently and its uniform round ran
 // 1.5 % slower; in this form it compiles to the instructions it had before the switch, but for a few reordered ones
 // (which is also why the best plan's update below compares first and selects the column after).
-template <bool DYN>
-__global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchArgs a) {
+//
+// A = FrontArgs (fjsp_schedule_search_front, both families): the same switch, one level up.  The neighbourhood is the
+// uniform one at compile time, "the chosen objective" is the key sum_c w[c] obj[c] of the env's weights, saturating below
+// the sentinel, and the env keeps the Pareto archive of every vector it decodes in LDS behind until[]: per slot the vector
+// and its source (round, q), (-1, -1) = free.  Per round, between the decodes and the move taken: the lanes put their
+// vectors into LDS; lane = candidate checks itself against the members (broadcast reads, a loop over the bits of the held
+// slots' mask) and, if it is past them, against the other candidates that are -> the entrants, a ballot; lane = slot checks
+// its member against the entrants and leaves if one dominates it -> the free slots, a ballot; free slot s of rank r (prefix
+// count of the ballot) writes fslot[r] = s, entrant of rank r takes fslot[r] and the wave writes its plan, rows read through
+// the move's index map.  No lane does the wave's work alone; the loops over members and entrants are wave-uniform.
+template <bool DYN, class A = SearchArgs>
+__global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, A a) {
     constexpr int NO = DYN ? 3 : 2;
+    constexpr bool FRONT = std::is_same<A, FrontArgs>::value;
     const int q = (int)threadIdx.x, env = (int)blockIdx.x, inst = env % b.n_inst;
-    const int cap = a.cap, Q = a.n_cand, N = b.N, nbh = DYN ? 0 : a.nbh;
+    const int cap = a.cap, Q = a.n_cand, N = b.N, nbh = (DYN || FRONT) ? 0 : a.nbh;
     const Shop sh = shop_of(b, a.kinds, inst, a.JW);
     const State st = state_at(decode_lds, q, 64, a.JW);
     DynShop dy{};
@@ -524,13 +567,33 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
     const int32_t *pl = a.plan + (size_t)env * cap * 3;
     int32_t *po = a.plan_out + (size_t)env * cap * 3;
 
+    // ---- the archive (FRONT): vectors, the round's candidate vectors, sources, the slot of the r-th free one; the weights
+    long long *fobj = reinterpret_cast<long long *>(until + cap), *cvec = fobj;
+    int32_t *fsrc = nullptr, *fslot = nullptr, *fplan = nullptr;
+    long long w0 = 0, w1 = 0, w2 = 0;
+    int F = 0, dropped = 0;
+    bool bad_w = false;
+    if constexpr (FRONT) {
+        F = a.cap_front;
+        cvec = fobj + (size_t)F * NO;
+        fsrc = reinterpret_cast<int32_t *>(cvec + 64 * NO); fslot = fsrc + 2 * F;
+        if (a.front_plan) fplan = a.front_plan + (size_t)env * F * cap * 3;
+        const long long *w = reinterpret_cast<const long long *>(a.weights) + NO * (size_t)env;
+        w0 = w[0]; w1 = w[1];
+        if constexpr (DYN) w2 = w[2];
+        bad_w = w0 < 0 || w1 < 0 || w2 < 0 || (w0 | w1 | w2) == 0;
+    }
+
     // ---- the input plan: copied through, decoded by every lane (one address to the wave), kept by lane 0
     for (int i = q; i < cap * 3; i += 64) po[i] = pl[i];
     int L = 0;
     long long cur_mk = 0, cur_td = 0, cur_en = 0;
-    // the chosen objective of (makespan, tardiness, energy)
-    auto chosen = [&](long long mk, long long td, long long en) { return DYN && a.col == 2 ? en : (a.col ? td : mk); };
-    const int st0 = decode_plan<DYN>(b, sh, st, [&](int idx) { return row_at(pl, idx); }, cap, no_move(), [&](int t, const Row &x, const Step &d) {
+    // the chosen objective of (makespan, tardiness, energy); FRONT: their key
+    auto chosen = [&](long long mk, long long td, long long en) {
+        if constexpr (FRONT) return key_add(key_add(key_mul(w0, mk), key_mul(w1, td)), DYN ? key_mul(w2, en) : 0LL);
+        else return DYN && a.col == 2 ? en : (a.col ? td : mk);
+    };
+    const int st0 = bad_w ? 5 : decode_plan<DYN>(b, sh, st, [&](int idx) { return row_at(pl, idx); }, cap, no_move(), [&](int t, const Row &x, const Step &d) {
         if (q == 0) { int32_t *o = rows + (size_t)t * 5; o[0] = x.r; o[1] = x.n; o[2] = x.m; o[3] = d.k; o[4] = t; until[t] = 0; }
     }, L, cur_mk, cur_td, &dy, &cur_en);
     if (st0 != 0) {                                                      // (the same in every lane)
@@ -541,11 +604,25 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
         for (int t = q; t <= a.rounds; t += 64) a.history[(size_t)t * N + env] = -1;
         if (a.trace)
             for (int i = q; i < a.rounds * 3; i += 64) a.trace[((size_t)(i / 3) * N + env) * 3 + i % 3] = 0;
+        if constexpr (FRONT) {                                           // an empty archive
+            if (q < F) {
+                for (int c = 0; c < NO; ++c) a.front_obj[((size_t)env * F + q) * NO + c] = -1;
+                a.front_src[((size_t)env * F + q) * 2] = -1; a.front_src[((size_t)env * F + q) * 2 + 1] = -1;
+            }
+            if (q == 0) { a.front_count[env] = 0; a.front_dropped[env] = 0; }
+            if (fplan)
+                for (size_t i = q; i < (size_t)F * cap * 3; i += 64) fplan[i] = -1;
+        }
         return;
+    }
+    if constexpr (FRONT) {                                               // the archive is {the input plan} in slot 0
+        if (q < F) { fsrc[2 * q] = -1; fsrc[2 * q + 1] = q == 0 ? 0 : -1; }
+        if (q == 0) { fobj[0] = cur_mk; fobj[1] = cur_td; if constexpr (DYN) fobj[2] = cur_en; }
     }
     __syncthreads();
     long long best_mk = cur_mk, best_td = cur_td, best_en = cur_en;      // of the plan in plan_out (tabu)
     int taken = 0, n_list = 0;
+    unsigned long long heldm = 1ULL;                                     // FRONT: the slots that hold a member, the same in every lane
     if (q == 0) a.history[env] = chosen(cur_mk, cur_td, cur_en);
     const uint64_t sg = gen::draw(a.seed, (uint32_t)(a.first_env + env));
     auto lrow = [&](int idx) { const int32_t *o = rows + (size_t)idx * 5; return idx < L ? Row{o[0], o[1], o[2]} : Row{-1, -1, -1}; };
@@ -555,6 +632,9 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
             po[3 * t] = x.r; po[3 * t + 1] = x.n; po[3 * t + 2] = x.m;
         }
     };
+    if constexpr (FRONT)
+        if (fplan)
+            for (int i = q; i < cap; i += 64) { const Row x = lrow(i); fplan[3 * i] = x.r; fplan[3 * i + 1] = x.n; fplan[3 * i + 2] = x.m; }
 
     for (int t = 0; t < a.rounds; ++t) {
         if (nbh != 0) {
@@ -616,6 +696,7 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
         long long mk = 0, td = 0, en = 0, key = 0x7fffffffffffffffLL;
         Move mv = no_move();
         int id_a = 0, id_b = -1;                                         // identities of the rows the move moves
+        bool decoded = false;                                            // a candidate of the archive: status 0, tabu or not
         if (!masked) {
             mv = move_of(kind, u, third, cap, lrow);
             int len = 0;
@@ -625,6 +706,7 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
                 if (move_past(mv, len)) err = 4;
             }
             bool ok = err == 0;
+            decoded = ok;
             if (ok && a.accept == 2) {
                 id_a = rows[(size_t)u * 5 + 4];
                 if (kind != 1) id_b = rows[(size_t)(kind == 2 ? u + 1 : mv.pv) * 5 + 4];
@@ -633,6 +715,63 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
                 ok = !same && (!tabu || chosen(mk, td, en) < chosen(best_mk, best_td, best_en));
             }
             if (ok) key = chosen(mk, td, en);
+        }
+        if constexpr (FRONT) {
+            // ---- the archive takes the round's candidates, before the move taken is applied
+            auto le = [&](const long long *x, long long y0, long long y1, long long y2) { return x[0] <= y0 && x[1] <= y1 && (!DYN || x[2] <= y2); };
+            cvec[q * NO] = mk; cvec[q * NO + 1] = td;
+            if constexpr (DYN) cvec[q * NO + 2] = en;
+            // lane = candidate: no member <= it ...
+            bool ent = decoded;
+            for (unsigned long long m = heldm; m; m &= m - 1)
+                if (le(fobj + (__ffsll(m) - 1) * NO, mk, td, en)) ent = false;
+            const unsigned long long past = __ballot(ent);
+            __syncthreads();
+            // ... no other candidate dominates it, none of lower q equals it.  Only the candidates that are past the members
+            // need looking at: where a member is <= a candidate, it is <= everything that candidate dominates or equals
+            for (unsigned long long m = past; m; m &= m - 1) {
+                const int o = __ffsll(m) - 1;
+                const long long *x = cvec + o * NO;
+                if (o != q && le(x, mk, td, en) && (o < q || x[0] != mk || x[1] != td || (DYN && x[2] != en))) ent = false;
+            }
+            const unsigned long long ents = __ballot(ent);
+            // lane = slot: a member that an entrant dominates leaves (no member is <= an entrant, so <= is domination)
+            bool held = (heldm >> q) & 1ULL;
+            if (held) {
+                const long long m0 = fobj[q * NO], m1 = fobj[q * NO + 1], m2 = DYN ? fobj[q * NO + 2] : 0;
+                for (unsigned long long m = ents; m; m &= m - 1)
+                    if (le(cvec + (__ffsll(m) - 1) * NO, m0, m1, m2)) held = false;
+            }
+            const unsigned long long freem = __ballot(q < F && !held), below = (1ULL << q) - 1ULL;
+            if (q < F && !held) { fslot[__popcll(freem & below)] = q; fsrc[2 * q] = -1; fsrc[2 * q + 1] = -1; }
+            __syncthreads();
+            // entrants take the lowest free slots in ascending q; the others are dropped
+            const int n_free = __popcll(freem), n_ent = __popcll(ents), rank = __popcll(ents & below);
+            int slot = -1;
+            if (ent && rank < n_free) {
+                slot = fslot[rank];
+                fobj[slot * NO] = mk; fobj[slot * NO + 1] = td;
+                if constexpr (DYN) fobj[slot * NO + 2] = en;
+                fsrc[2 * slot] = t; fsrc[2 * slot + 1] = q;
+            }
+            if (n_ent > n_free) dropped += n_ent - n_free;
+            if (fplan) {
+                for (unsigned long long m = ents; m; m &= m - 1) {
+                    const int o = __ffsll(m) - 1, so = __shfl(slot, o);
+                    if (so < 0) break;                                   // (nor do the entrants behind it find a slot)
+                    Move w = no_move();
+                    w.kind = __shfl(mv.kind, o); w.u = __shfl(mv.u, o); w.m_new = __shfl(mv.m_new, o);
+                    w.pu = __shfl(mv.pu, o); w.pw = __shfl(mv.pw, o); w.pv = __shfl(mv.pv, o);
+                    int32_t *fp = fplan + (size_t)so * cap * 3;
+                    for (int i = q; i < cap; i += 64) {
+                        Row x = lrow(move_src(w, i));
+                        if (w.kind == 1 && i == w.u) x.m = w.m_new;
+                        fp[3 * i] = x.r; fp[3 * i + 1] = x.n; fp[3 * i + 2] = x.m;
+                    }
+                }
+            }
+            __syncthreads();
+            heldm = __ballot(q < F && fsrc[2 * q + 1] != -1);
         }
         // ---- the least (objective, q) of the wave
         int wq = q;
@@ -682,7 +821,8 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
             }
             ++taken;
             __syncthreads();
-            if (a.accept == 2 && (DYN && a.col == 2 ? cur_en < best_en : (a.col ? cur_td < best_td : cur_mk < best_mk))) { best_mk = cur_mk; best_td = cur_td; best_en = cur_en; write_out(); }
+            if (a.accept == 2 && (FRONT ? chosen(cur_mk, cur_td, cur_en) < chosen(best_mk, best_td, best_en)
+                                        : (DYN && a.col == 2 ? cur_en < best_en : (a.col ? cur_td < best_td : cur_mk < best_mk)))) { best_mk = cur_mk; best_td = cur_td; best_en = cur_en; write_out(); }
         }
         if (q == 0) {
             a.history[(size_t)(t + 1) * N + env] = chosen(cur_mk, cur_td, cur_en);
@@ -696,6 +836,19 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, SearchA
     if (q == 0) {
         a.status[env] = 0; a.accepted[env] = taken; a.objective[NO * (size_t)env] = best_mk; a.objective[NO * (size_t)env + 1] = best_td;
         if constexpr (DYN) a.objective[NO * (size_t)env + 2] = best_en;
+    }
+    if constexpr (FRONT) {                                               // the archive as it stands; free slots' plans cleared
+        const bool held = q < F && fsrc[2 * q + 1] != -1;
+        if (q < F) {
+            for (int c = 0; c < NO; ++c) a.front_obj[((size_t)env * F + q) * NO + c] = held ? fobj[q * NO + c] : -1;
+            a.front_src[((size_t)env * F + q) * 2] = fsrc[2 * q]; a.front_src[((size_t)env * F + q) * 2 + 1] = fsrc[2 * q + 1];
+        }
+        const unsigned long long heldm = __ballot(held);
+        if (q == 0) { a.front_count[env] = __popcll(heldm); a.front_dropped[env] = dropped; }
+        if (fplan)
+            for (int s = 0; s < F; ++s)
+                if (!((heldm >> s) & 1ULL))
+                    for (int i = q; i < cap * 3; i += 64) fplan[(size_t)s * cap * 3 + i] = -1;
     }
 }
 
@@ -882,4 +1035,61 @@ extern "C" int fjsp_schedule_search_dyn(fjsp_env *e, const int32_t *d_plan, int3
                                         int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream) {
     return schedule_search(true, e, d_plan, rounds, n_cand, objective, 0, accept, tenure, seed, first_env, d_plan_out, d_objective, d_history,
                            d_accepted, d_status, d_trace, stream);
+}
+
+// bytes of an env's working set in fjsp_schedule_search_front, whatever the limit (the kernel lays LDS out by the same words)
+static size_t search_front_bytes(const fjsp_env *e, int cap_front) {
+    const DevBatch &b = e->b;
+    const bool dyn = b.variant == FJSP_VARIANT_MO_DFJSP;
+    return search_front_words(dyn ? dyn_state_words(b.jcap, b.MP) : state_words(b.jcap, b.MP), e->ops_max, cap_front, dyn ? 3 : 2) * 4;
+}
+
+extern "C" int fjsp_schedule_search_front_lds(const fjsp_env *e, int32_t cap_front) {
+    if (!e || e->ops_max <= 0 || cap_front < 1 || cap_front > 64) return 0;
+    const size_t bytes = search_front_bytes(e, cap_front);
+    return bytes <= kLdsCu ? (int)bytes : 0;
+}
+
+extern "C" int fjsp_schedule_search_front(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, const int64_t *d_weights,
+                                          int32_t accept, int32_t tenure, uint64_t seed, int64_t first_env, int32_t cap_front,
+                                          int32_t *d_plan_out, int64_t *d_objective, int64_t *d_history, int32_t *d_accepted, int32_t *d_status,
+                                          int32_t *d_trace, int64_t *d_front_obj, int32_t *d_front_src, int32_t *d_front_plan,
+                                          int32_t *d_front_count, int32_t *d_front_dropped, void *stream) {
+    const std::string fn = "fjsp_schedule_search_front";
+    if (!e || !d_plan || !d_weights || !d_plan_out || !d_objective || !d_history || !d_accepted || !d_status || !d_front_obj || !d_front_src ||
+        !d_front_count || !d_front_dropped) {
+        set_error(fn + ": null env, plan, weights or output pointer"); return FJSP_E_ARG;
+    }
+    if (e->gen_failed) { set_error(fn + ": the last regenerate of this handle failed"); return FJSP_E_STATE; }
+    if (n_cand < 1 || n_cand > 64 || cap_front < 1 || cap_front > 64 || rounds < 0 || tenure < 0) {
+        set_error(fn + ": needs n_cand and cap_front in 1..64, rounds >= 0 and tenure >= 0"); return FJSP_E_ARG;
+    }
+    if (accept < 0 || accept > 2) { set_error(fn + ": accept is 0, 1 or 2"); return FJSP_E_ARG; }
+    if (3ULL * (unsigned long long)rounds * (unsigned long long)n_cand > 0xFFFFFFFFULL) {
+        set_error(fn + ": 3 x rounds x n_cand draws per env exceed 2^32 - 1"); return FJSP_E_ARG;
+    }
+    const DevBatch &b = e->b;
+    if (e->ops_max <= 0) { set_error(fn + ": no operations"); return FJSP_E_ARG; }
+    const bool dyn = b.variant == FJSP_VARIANT_MO_DFJSP;
+    const int NO = dyn ? 3 : 2;
+    const size_t lds = search_front_bytes(e, cap_front);
+    if (lds > kLdsCu) {
+        set_error(fn + ": an env's working set (64 candidate states of " + std::to_string((dyn ? dyn_state_words(b.jcap, b.MP) : state_words(b.jcap, b.MP)) * 4) +
+                  " bytes, 24 bytes per operation, " + std::to_string(8 * NO + 8) + " per archive slot and " + std::to_string(64 * (8 * NO + 4)) +
+                  " more: " + std::to_string(lds) + " bytes) exceeds the " + std::to_string(kLdsCu) + " bytes of a CU's LDS");
+        return FJSP_E_UNSUPPORTED;
+    }
+    DeviceGuard guard(e->device);
+    if (!e->d_decode_kinds && !dev_alloc(e, (size_t)b.n_inst * (size_t)(b.KP + 1) * sizeof(uint2), &e->d_decode_kinds, "hipMalloc (decode kind table)")) return FJSP_E_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch(decode_kinds_kernel, dim3((unsigned)((b.n_inst + 63) / 64)), dim3(64), 0, st, b, e->d_decode_kinds) != 0) {
+        set_error("decode_kinds_kernel launch failed"); return FJSP_E_HIP;
+    }
+    const FrontArgs a{{d_plan, d_plan_out, d_objective, d_history, d_accepted, d_status, d_trace, e->d_decode_kinds, seed ^ FJSP_SEARCH_STREAM,
+                       (long long)first_env, (int)rounds, (int)n_cand, 0, 0, (int)accept, (int)tenure, e->ops_max, b.jcap},
+                      d_weights, d_front_obj, d_front_src, d_front_plan, d_front_count, d_front_dropped, (int)cap_front};
+    const int rc = dyn ? launch(schedule_search_kernel<true, FrontArgs>, dim3((unsigned)b.N), dim3(64), lds, st, b, a)
+                       : launch(schedule_search_kernel<false, FrontArgs>, dim3((unsigned)b.N), dim3(64), lds, st, b, a);
+    if (rc != 0) { set_error(std::string(dyn ? "schedule_search_kernel<true, FrontArgs>" : "schedule_search_kernel<false, FrontArgs>") + " launch failed"); return FJSP_E_HIP; }
+    return FJSP_OK;
 }

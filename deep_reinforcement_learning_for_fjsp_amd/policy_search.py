@@ -35,6 +35,9 @@ slowly.
 - local_search: improve's search, descent or tabu, as one launch for all its rounds (schedule.search, fjsp_schedule_search;
   on a MO_DFJSP batch schedule.search_dyn, fjsp_schedule_search_dyn: uniform neighbourhood, "energy" an objective):
   a wavefront per env, a lane per neighbour, the plan in LDS, on a counter-based draw stream that shards reproduce.
+- front_search: local_search steered by a weighted sum of the objectives, one weight vector per env, that keeps the Pareto
+  archive of every schedule it decodes in the same launch (schedule.search_front, fjsp_schedule_search_front), and with
+  merge=True the front per instance over its envs' archives (pareto.select).
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -732,4 +735,86 @@ def local_search(batch, plan, rounds, neighbours=64, objective="makespan", seed=
                table=last["table"][:, 0], length=last["length"][:, 0], status=res["status"])
     if trace:
         out["trace"] = res["trace"]
+    return out
+
+
+def merge_fronts(front_obj, held, n_inst):
+    """The front per instance over the archives of its envs (front_search's merge=True): front_obj int64[N, F, NO], held
+    bool[N, F] (the slot has a member), env e on instance e % n_inst -> (merged_front f64[n_inst, C, NO], NaN past the front,
+    merged_count int32[n_inst]) through pareto.select, C = ceil(N / n_inst) x F.  ValueError if C exceeds pareto.select's 1024
+    candidates or a member is 2^53 or more (the vectors go through f64)."""
+    N, F, n_obj = front_obj.shape
+    n_group, dev = -(-N // n_inst), front_obj.device
+    if n_group * F > pareto.MAX_CANDIDATES:
+        raise ValueError("merge: %d envs of an instance x cap_front %d exceed pareto.select's %d candidates" % (n_group, F, pareto.MAX_CANDIDATES))
+    if bool(((front_obj >= 2 ** 53) & held[..., None]).any()):
+        raise ValueError("merge: an objective of 2^53 or more does not pass through f64")
+    pad = n_group * n_inst - N
+    held = torch.cat([held, torch.zeros(pad, F, dtype=torch.bool, device=dev)])
+    vec = torch.cat([front_obj, torch.full((pad, F, n_obj), -1, dtype=torch.int64, device=dev)]).to(torch.float64)
+    # candidate-major: candidate k * F + s of instance i is slot s of env k * n_inst + i
+    vec = vec.reshape(n_group, n_inst, F, n_obj).permute(0, 2, 1, 3).reshape(n_group * F, n_inst, n_obj).contiguous()
+    held = held.reshape(n_group, n_inst, F).permute(0, 2, 1).reshape(n_group * F, n_inst)
+    index, count, _ = pareto.select(vec, held)
+    return pareto.front_points(vec, index), count
+
+
+def front_search(batch, plan, rounds, weights=None, neighbours=64, cap_front=64, accept="tabu", tenure=8, seed=0, merge=False):
+    """local_search for a front, not a minimum (schedule.search_front, fjsp_schedule_search_front, csrc/fjsp_decode.hip): the
+    same one-launch search on either family, steered per env by the key sum_c weights[e, c] * objective[c], and every
+    vector it decodes -- the input plan, every neighbour of every round, taken or not -- offered to the env's Pareto
+    archive of `cap_front` slots (1..64), which the wave keeps in LDS.  Envs that share an instance and differ in their
+    weights sweep the weight simplex over it.
+
+    weights: None (ones), a vector of NO non-negative integers that are not all zero (every env's), or [N, NO]; NO = 3
+    (makespan, tardiness, energy) on MO_DFJSP, 2 elsewhere.  The other arguments are local_search's; the neighbourhood is
+    the uniform one.
+
+    Returns local_search's dict, history holding the key, and
+      front      int64[N, cap_front, NO]  the archive's members first, in ascending lexicographic order of their vectors
+                                          (fjsp_pareto_select's order), -1 past count
+      front_plan int32[N, cap_front, cap, 3], front_src int32[N, cap_front, 2]  their plans and the (round, q) that found
+                                          them ((-1, 0): the input plan), permuted alike, -1 past count
+      count      int32[N]                 members;  dropped int32[N]: entrants that found no free slot and were lost --
+                                          raise cap_front or split the weights over more envs
+    and with merge=True, per instance, merged_front f64[n_inst, C, NO] (NaN past the front) and merged_count int32[n_inst]:
+    the front (pareto.select) of the archives of all envs i with i % n_inst the instance, C = envs of an instance x
+    cap_front, which must not exceed 1024.
+    ValueError for arguments local_search refuses, cap_front outside 1..64, weights of another shape, negative or all zero,
+    a plan that does not decode, and with merge C > 1024 or a member >= 2^53 (the vectors go through f64); FjspError where
+    the library refuses (EnvBatch.search_front_lds)."""
+    from . import schedule as sch
+    b, _ = _unwrap(batch, None)
+    n_obj = 3 if b.variant == sch.VARIANT_MO_DFJSP else 2
+    if accept not in sch.SEARCH_ACCEPT:
+        raise ValueError("accept must be one of %s" % (sch.SEARCH_ACCEPT,))
+    rounds, Q, F, tenure = int(rounds), int(neighbours), int(cap_front), int(tenure)
+    if rounds < 0 or not 1 <= Q <= sch.SEARCH_MAX_NEIGHBOURS or not 1 <= F <= 64 or tenure < 0:
+        raise ValueError("front_search needs rounds >= 0, neighbours in 1..%d, cap_front in 1..64 and tenure >= 0" % sch.SEARCH_MAX_NEIGHBOURS)
+    dev, N = b.device, b.N
+    w = torch.ones(n_obj, dtype=torch.int64) if weights is None else torch.as_tensor(weights)
+    if w.is_floating_point() or w.dim() not in (1, 2) or w.shape[-1] != n_obj or (w.dim() == 2 and w.shape[0] != N):
+        raise ValueError("weights must be integers of shape (%d,) or (%d, %d)" % (n_obj, N, n_obj))
+    w = w.to(device=dev, dtype=torch.int64).expand(N, n_obj).contiguous()
+    if bool(((w < 0).any(1) | (w == 0).all(1)).any()):
+        raise ValueError("weights must be non-negative and not all zero in every env")
+    n_group = -(-N // b.n_inst)
+    if merge and n_group * F > pareto.MAX_CANDIDATES:
+        raise ValueError("merge: %d envs of an instance x cap_front %d exceed pareto.select's %d candidates" % (n_group, F, pareto.MAX_CANDIDATES))
+    res = sch.search_front(b, plan, w, rounds, Q, F, sch.SEARCH_ACCEPT.index(accept), tenure, seed)
+    if bool((res["status"] != 0).any()):
+        raise ValueError("front_search: a plan does not decode (status %s)" % sorted(set(res["status"].tolist()) - {0}))
+    last = (sch.decode_dyn if n_obj == 3 else sch.decode)(b, res["plan"], want_table=True)
+    # members first, in ascending lexicographic order: stable sorts from the least significant column up, free slots last
+    obj, src = res["front_obj"], res["front_src"]
+    order = torch.arange(F, device=dev).expand(N, F)
+    for key in [obj[..., c] for c in range(n_obj - 1, -1, -1)] + [(src[..., 1] < 0).to(torch.int64)]:
+        order = torch.gather(order, 1, torch.sort(torch.gather(key, 1, order), dim=1, stable=True).indices)
+    out = dict(plan=res["plan"], objective=res["objective"], history=res["history"], accepted=res["accepted"].to(torch.int64),
+               table=last["table"][:, 0], length=last["length"][:, 0], status=res["status"],
+               front=torch.gather(obj, 1, order[..., None].expand(N, F, n_obj)),
+               front_plan=torch.gather(res["front_plan"], 1, order[..., None, None].expand(N, F, *res["front_plan"].shape[2:])),
+               front_src=torch.gather(src, 1, order[..., None].expand(N, F, 2)), count=res["front_count"], dropped=res["front_dropped"])
+    if merge:
+        out["merged_front"], out["merged_count"] = merge_fronts(obj, src[..., 1] >= 0, b.n_inst)
     return out

@@ -18,6 +18,7 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     begin_order(table)                          the same schedule with its rows sorted by begin: (plan, table)
     search(batch, plan, rounds, n_cand, ...)    hill climbing / tabu search, all rounds in one launch (fjsp_schedule_search)
     search_dyn(batch, plan, rounds, n_cand, ...) the same on MO_DFJSP: uniform neighbourhood, energy as a third objective
+    search_front(batch, plan, weights, ...)     that search steered by a weighted sum, keeping the Pareto archive of its decodes
     search_draws(seed, env, first, n)           the draw stream of that search, on the host
 
 `inst` is anything with the instance arrays of instances.InstanceArrays: Jr[R], p[K][M] (0 = ineligible),
@@ -446,6 +447,43 @@ def search_dyn(batch, plan, rounds, n_cand, objective=0, accept=1, tenure=0, see
     an index of SEARCH_DYN_OBJECTIVES.  The same draws, accept modes and dict, with objective=int64[N, 3] (makespan, total
     tardiness, energy).  FjspError on a batch that is not MO_DFJSP."""
     return _search(batch, plan, rounds, "fjsp_schedule_search_dyn", 3, (int(n_cand), int(objective), int(accept), int(tenure)), seed, trace)
+
+
+def search_front(batch, plan, weights, rounds, n_cand, cap_front=64, accept=1, tenure=0, seed=0, trace=False, want_plans=True):
+    """fjsp_schedule_search_front on the current stream: search steered by the key sum_c weights[e, c] * objective[c], and the
+    Pareto archive of every vector the search decodes, in one launch (the contract is in include/fjsp_amd.h;
+    policy_search.front_search is the checked form).  Either family: NO = 3 objectives on MO_DFJSP, 2 elsewhere.  plan:
+    int32[N, cap, 3]; weights: int64[N, NO]; accept an index of SEARCH_ACCEPT.  Passes batch.first_env.  Returns search's
+    dict (history holds the key) and front_obj=int64[N, cap_front, NO], front_src=int32[N, cap_front, 2], front_plan=
+    int32[N, cap_front, cap, 3] or None (want_plans=False), front_count=int32[N], front_dropped=int32[N], device tensors.
+    ValueError for a plan or weights of another shape; FjspError where the library refuses."""
+    import torch
+    from ._capi import check, ptr
+    b = getattr(batch, "batch", batch)
+    cap = int(b._lib.fjsp_schedule_decode_capacity(b._h))
+    n_obj = 3 if b.variant == VARIANT_MO_DFJSP else 2
+    if not torch.is_tensor(plan):
+        plan = torch.as_tensor(np.asarray(plan))
+    if tuple(plan.shape) != (b.N, cap, 3):
+        raise ValueError("plan must have shape %s, got %s" % ((b.N, cap, 3), tuple(plan.shape)))
+    if not torch.is_tensor(weights):
+        weights = torch.as_tensor(np.asarray(weights, np.int64))
+    if tuple(weights.shape) != (b.N, n_obj):
+        raise ValueError("weights must have shape %s, got %s" % ((b.N, n_obj), tuple(weights.shape)))
+    plan = plan.to(device=b.device, dtype=torch.int32).contiguous()
+    weights = weights.to(device=b.device, dtype=torch.int64).contiguous()
+    rows, F = max(int(rounds), 0), min(max(int(cap_front), 0), 64)
+    new = lambda *shape, dtype=torch.int32: torch.empty(shape, dtype=dtype, device=b.device)
+    out = dict(plan=torch.empty_like(plan), objective=new(b.N, n_obj, dtype=torch.int64), history=new(rows + 1, b.N, dtype=torch.int64),
+               accepted=new(b.N), status=new(b.N), trace=new(rows, b.N, 3) if trace else None,
+               front_obj=new(b.N, F, n_obj, dtype=torch.int64), front_src=new(b.N, F, 2),
+               front_plan=new(b.N, F, cap, 3) if want_plans else None, front_count=new(b.N), front_dropped=new(b.N))
+    check(b._lib.fjsp_schedule_search_front(b._h, ptr(plan), int(rounds), int(n_cand), ptr(weights), int(accept), int(tenure),
+                                            int(seed) & (2 ** 64 - 1), int(b.first_env), int(cap_front), ptr(out["plan"]), ptr(out["objective"]),
+                                            ptr(out["history"]), ptr(out["accepted"]), ptr(out["status"]), ptr(out["trace"]),
+                                            ptr(out["front_obj"]), ptr(out["front_src"]), ptr(out["front_plan"]), ptr(out["front_count"]),
+                                            ptr(out["front_dropped"]), b._stream()))
+    return out
 
 
 def _search(batch, plan, rounds, entry, n_obj, codes, seed, trace):

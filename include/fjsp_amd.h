@@ -943,6 +943,64 @@ int fjsp_schedule_search_dyn(fjsp_env *e, const int32_t *d_plan, int32_t rounds,
                              int64_t *d_history, int32_t *d_accepted, int32_t *d_status, int32_t *d_trace, void *stream);
 int fjsp_schedule_search_dyn_lds(const fjsp_env *e);
 
+/* Search explicit schedules for Pareto fronts, every round of every env in ONE launch (schedule.search_front,
+ * policy_search.front_search; csrc/fjsp_decode.hip, schedule_search_kernel<DYN, FrontArgs>: that kernel's text compiled
+ * with a weighted key and an archive).  The search is fjsp_schedule_search_dyn's, steered by a weighted sum of the
+ * objectives with one weight vector per env -- a batch sweeps the weight simplex over one instance --, and it keeps the
+ * Pareto archive of every vector it decodes.  The result is a function of the arguments alone;
+ * tests/search_front_reference.py restates it in numpy and Python integers, bit for bit.
+ *
+ * One entry serves both families.  On a FJSP_VARIANT_MO_DFJSP handle every decode is fjsp_schedule_decode_dyn's and NO = 3
+ * (makespan, total tardiness, energy); on every other handle every decode is fjsp_schedule_decode's and NO = 2.  Only the
+ * uniform neighbourhood exists here (the critical ones follow the makespan alone).
+ *
+ * Arguments: fjsp_schedule_search_dyn's with `objective` replaced by d_weights i64[N][NO], one weight vector per env, and
+ * cap_front (1..64), the slots of an env's archive, and the archive outputs behind d_trace.
+ * Key: key = sum over c of w[c] * obj[c] in int64; every product and every partial sum (left to right) saturates at
+ * 2^63 - 2, so a key never reaches the "no candidate" sentinel 2^63 - 1.  The weights are checked per env on the device
+ * before anything else: a negative weight or an all-zero vector gives status 5, which outranks the plan's decode status;
+ * such an env is copied through exactly as one whose plan does not decode, and its archive is empty.
+ * Search: fjsp_schedule_search_dyn's with "chosen objective" read as "key" -- the draw stream (s_g = draw(seed ^
+ * FJSP_SEARCH_STREAM, (uint32_t)g), three draws per round and candidate, fjsp_search_draws, global env ids so a shard
+ * reproduces its envs), candidate q even (1, u, m) / odd (2, u, 0), selection by the least key and the lowest q, accept 0
+ * strict / 1 sideways / 2 tabu with until[identity], aspiration against the best key seen, masked no-ops, until = t + 1 +
+ * tenure saturating at 2^31 - 1, the best plan replaced only on strict improvement of the key.
+ * d_history i64[rounds + 1][N]: the key of the input plan, then of the current plan after every round.  d_objective
+ * i64[N][NO]: the vector of the returned plan.  d_plan_out, d_accepted, d_status, d_trace (nullable): as the siblings.
+ *
+ * Archive, per env, defined on sets.  It starts as {the input plan's vector} in slot 0 with source (-1, 0).  In round t the
+ * round's candidates are every q < n_cand whose decode has status 0, tabu and no-op candidates too.  A candidate is an
+ * entrant if no archive member is <= it in every objective (equal included), no other candidate of the round dominates it
+ * (<= in every objective and < in one) and no candidate of lower q in the round has the same vector.  Every member that an
+ * entrant dominates leaves, whether or not that entrant finds a slot; the entrants then take the lowest free slots in
+ * ascending q, and those that find none are counted in d_front_dropped and lost.  A member never moves to another slot.
+ * The archive is updated before the round's accepted move is applied: an entrant's plan is the round's start plan with
+ * its move applied, as schedule.apply_moves applies it.
+ *   d_front_obj     i64[N][cap_front][NO]       member vectors, -1 in free slots
+ *   d_front_src     i32[N][cap_front][2]        (round, q) that found the member, (-1, 0) the input plan, (-1, -1) free
+ *   d_front_plan    i32[N][cap_front][cap][3]   nullable: member plans, -1 rows past a plan's end (slot 0 holds the input
+ *                                               plan's rows up to its first -1 row), all -1 in free slots
+ *   d_front_count   i32[N]                      members
+ *   d_front_dropped i32[N]                      entrants that found no slot
+ * An env with a status other than 0 has count 0, dropped 0 and every slot free.
+ *
+ * Stream-ordered, no host synchronisation, no atomics, two launches for any number of rounds; capturable.
+ * Limit: the 64 candidate states of the family's decode (5 bytes per job rounded up to 16 jobs + 4 per machine, 8 per
+ * machine on MO_DFJSP), 24 bytes per row of the longest plan, 8 NO + 8 per archive slot (vector, source) and 64 x (8 NO + 4)
+ * (the round's candidate vectors, the free slots in order) must fit the 160 KB of a CU's LDS:
+ *   64 x state + 24 x rows + cap_front x (8 NO + 8) + 64 x (8 NO + 4)
+ * fjsp_schedule_search_front_lds(e, cap_front) is that sum in bytes, 0 where it does not fit or cap_front is outside 1..64.
+ * FJSP_E_ARG: a null e, d_plan, d_weights or output other than d_trace and d_front_plan, n_cand or cap_front outside 1..64,
+ * rounds < 0, tenure < 0, accept outside 0..2, 3 x rounds x n_cand > 2^32 - 1.  FJSP_E_UNSUPPORTED: a working set beyond the
+ * limit (the message gives the bytes).  FJSP_E_STATE: a generated handle whose last regenerate failed.  Every check runs
+ * before any device call. */
+int fjsp_schedule_search_front(fjsp_env *e, const int32_t *d_plan, int32_t rounds, int32_t n_cand, const int64_t *d_weights,
+                               int32_t accept, int32_t tenure, uint64_t seed, int64_t first_env, int32_t cap_front,
+                               int32_t *d_plan_out, int64_t *d_objective, int64_t *d_history, int32_t *d_accepted, int32_t *d_status,
+                               int32_t *d_trace, int64_t *d_front_obj, int32_t *d_front_src, int32_t *d_front_plan,
+                               int32_t *d_front_count, int32_t *d_front_dropped, void *stream);
+int fjsp_schedule_search_front_lds(const fjsp_env *e, int32_t cap_front);
+
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
  *
