@@ -705,6 +705,11 @@ class EnvBatch(object):
         (fjsp_schedule_search_front_lds, either family); 0: an env's working set exceeds a CU's LDS, or cap_front is outside 1..64."""
         return int(self._lib.fjsp_schedule_search_front_lds(self._h, int(cap_front)))
 
+    def evolve_lds(self):
+        """LDS bytes a workgroup of policy_search.genetic_search takes on this batch (fjsp_schedule_evolve_lds, either
+        family); 0: an env's working set exceeds a CU's LDS."""
+        return int(self._lib.fjsp_schedule_evolve_lds(self._h))
+
     def set_lp_threads(self, n_threads):
         """Host threads of the order-arrival LP service (0 = all cores).  The asynchronous service builds its worker pool
         at the first step_async and reads this once, there: call it before that."""

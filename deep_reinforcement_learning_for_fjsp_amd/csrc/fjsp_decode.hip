@@ -201,9 +201,13 @@ __device__ __forceinline__ DynShop dyn_shop_of(const DevBatch &b, const Shop &sh
 // time t0 = max(ready, free) is shifted by the machine's windows, walked from the first in file order at every row as the
 // reference walks them; free[m] and ready[job] become the MACHINE's end, which a window that starts exactly at the task's
 // end moves on its own; *energy gathers power x duration and idle power x the gap from the last task's end to t0.
-template <bool DYN = false, class RowAt, class Sink>
+// fix(t, row, operation type), which only fjsp_schedule_evolve passes, may put row t on another machine once its stage is
+// known and before its machine is checked; the callers that do not pass it compile to what they compiled to without it.
+struct NoFix { __device__ __forceinline__ void operator()(int, Row &, int) const {} };
+template <bool DYN = false, class RowAt, class Sink, class Fix = NoFix>
 __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, const State &st, RowAt row, int cap, const Move &mv, Sink sink,
-                                           int &L, long long &makespan, long long &tard, const DynShop *dy = nullptr, long long *energy = nullptr) {
+                                           int &L, long long &makespan, long long &tard, const DynShop *dy = nullptr, long long *energy = nullptr,
+                                           Fix fix = Fix{}) {
     const int G = st.G, JW = sh.JW, MP = sh.MP;
     const int32_t *oarr = reinterpret_cast<const int32_t *>(sh.ir + b.L.i_oarr);
     const uint16_t *ocnt = reinterpret_cast<const uint16_t *>(sh.ir + b.L.i_ocnt);
@@ -240,6 +244,7 @@ __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, co
         uint8_t *sj = st.stage + (size_t)(j >> 2) * 4 * G + (j & 3);
         const int stg = (int)*sj;
         if (stg >= Jr || koff + stg >= sh.KP) { err = 2; continue; }
+        fix(t, x, koff + stg);
         if (x.m < 0 || x.m >= sh.M) { err = 3; continue; }
         const int pv = (int)sh.p[(size_t)(koff + stg) * MP + x.m];
         if (pv == 0) { err = 3; continue; }
@@ -853,6 +858,195 @@ __global__ __launch_bounds__(64) void schedule_search_kernel(DevBatch b, A a) {
 }
 
 
+// ---- fjsp_schedule_evolve: a genetic algorithm on explicit schedules, every generation of every env in ONE launch.  One
+// 64-lane workgroup owns one env, lane q owns individual q and decodes it on its own banked state (G = 64, the decoder's
+// layout and text).  Beside the states the env keeps in LDS the job set of every lane's crossover (one bit per job, words
+// banked like the state) and two rows of 64 keys, written in turn, so that one barrier per generation hands both the keys
+// and the children on.  The population lives in global memory and goes to and fro between pop_out and work (generation 1
+// reads pop): a child is written by its lane with plain stores and read in the next generation, after the workgroup's
+// barrier, with plain loads by whichever lanes drew it as a parent -- a hand-off inside one workgroup, so the barrier's
+// workgroup-scope release / acquire is all it needs; none of the three pointers is const __restrict__.
+//   A child does not exist before it is decoded: the accessor below merges its parents' rows while decode_plan asks for
+//   them, the fix puts the mutated row on its machine once the decode knows the row's stage, and the sink writes the row
+//   into the other buffer.  The least (key, index) is the search kernel's butterfly; the tournament reads keys from LDS.
+struct EvolveArgs {
+    const int32_t *pop;      // i32[N][P][cap][3]
+    int32_t *pop_out, *work; // i32[N][P][cap][3] each
+    const int64_t *weights;  // i64[N][NO]
+    int64_t *pop_obj;        // i64[N][P][NO]
+    int32_t *best_plan;      // i32[N][cap][3]
+    int64_t *objective;      // i64[N][NO]
+    int64_t *history;        // i64[generations + 1][N]
+    int32_t *status;         // i32[N]
+    int32_t *trace;          // i32[generations][N][P][3], nullable
+    const uint2 *kinds;      // [n_inst][KP + 1]
+    unsigned long long seed; // of the evolve stream (the caller's seed ^ FJSP_EVOLVE_STREAM)
+    long long first_env;
+    int P, generations, mut_rate, cap, JW;
+};
+
+// words of a lane's job set; words of LDS of an env: the 64 states (states = state_words or dyn_state_words), the 64 job
+// sets, two rows of 64 keys (i64)
+__host__ __device__ inline int evolve_set_words(int JW) { return (JW + 31) / 32; }
+__host__ __device__ inline size_t evolve_words(int states, int JW) { return (size_t)(states + evolve_set_words(JW)) * 64 + 2 * 64 * 2; }
+
+template <bool DYN>
+__global__ __launch_bounds__(64) void schedule_evolve_kernel(DevBatch b, EvolveArgs a) {
+    constexpr int NO = DYN ? 3 : 2;
+    constexpr long long kNone = 0x7fffffffffffffffLL;                    // the key of a lane without an individual, or of a child that failed
+    const int q = (int)threadIdx.x, env = (int)blockIdx.x, inst = env % b.n_inst;
+    const int cap = a.cap, P = a.P, N = b.N, T = a.generations;
+    const Shop sh = shop_of(b, a.kinds, inst, a.JW);
+    const State st = state_at(decode_lds, q, 64, a.JW);
+    DynShop dy{};
+    if constexpr (DYN) dy = dyn_shop_of(b, sh, st, dyn_windows(b));
+    const int SW = DYN ? dyn_state_words(a.JW, b.MP) : state_words(a.JW, b.MP), JS = evolve_set_words(a.JW);
+    uint32_t *jset = decode_lds + (size_t)SW * 64 + q;                   // word w of this lane's set at jset[w * 64]
+    long long *keys = reinterpret_cast<long long *>(decode_lds + (size_t)(SW + JS) * 64);     // [2][64]
+    const size_t PW = (size_t)cap * 3, base = (size_t)env * P * PW;      // words of a plan; the env's first word in a population
+
+    const long long *w = reinterpret_cast<const long long *>(a.weights) + NO * (size_t)env;
+    const long long w0 = w[0], w1 = w[1], w2 = DYN ? w[2] : 0;
+    const bool bad_w = w0 < 0 || w1 < 0 || w2 < 0 || (w0 | w1 | w2) == 0;
+    auto chosen = [&](long long mk, long long td, long long en) { return key_add(key_add(key_mul(w0, mk), key_mul(w1, td)), DYN ? key_mul(w2, en) : 0LL); };
+    // the least (key, index) of the wave, the same in every lane
+    auto least = [&](long long key, long long &bkey, int &bq) {
+        bkey = key; bq = q;
+        for (int off = 32; off > 0; off >>= 1) {
+            const long long ok2 = __shfl_xor(bkey, off);
+            const int oq = __shfl_xor(bq, off);
+            if (ok2 < bkey || (ok2 == bkey && oq < bq)) { bkey = ok2; bq = oq; }
+        }
+    };
+
+    // ---- generation 0: every individual of pop decoded by its lane
+    int L = 0, st0 = 0;
+    long long mk = 0, td = 0, en = 0, key = kNone;
+    if (q < P && !bad_w) {
+        const int32_t *pl = a.pop + base + (size_t)q * PW;
+        st0 = decode_plan<DYN>(b, sh, st, [&](int idx) { return row_at(pl, idx); }, cap, no_move(), [](int, const Row &, const Step &) {}, L, mk, td, &dy, &en);
+        if (st0 == 0) key = chosen(mk, td, en);
+    }
+    const unsigned long long failed = __ballot(st0 != 0);
+    const int status = bad_w ? 5 : (failed ? __shfl(st0, __ffsll(failed) - 1) : 0);
+    if (status != 0) {                                                   // (the same in every lane) the env is copied through
+        for (size_t i = q; i < (size_t)P * PW; i += 64) a.pop_out[base + i] = a.pop[base + i];
+        for (size_t i = q; i < PW; i += 64) a.best_plan[(size_t)env * PW + i] = a.pop[base + i];
+        if (q < P)
+            for (int c = 0; c < NO; ++c) a.pop_obj[((size_t)env * P + q) * NO + c] = -1;
+        if (q == 0) {
+            a.status[env] = status;
+            for (int c = 0; c < NO; ++c) a.objective[NO * (size_t)env + c] = -1;
+        }
+        for (int t = q; t <= T; t += 64) a.history[(size_t)t * N + env] = -1;
+        if (a.trace)
+            for (int t = 0; t < T; ++t)
+                for (int i = q; i < P * 3; i += 64) a.trace[((size_t)t * N + env) * (size_t)P * 3 + i] = 0;
+        return;
+    }
+    if (T == 0) {                                                        // the outputs describe the input population: the wave copies it
+        for (int p = 0; p < P; ++p) {
+            const int Lp = __shfl(L, p);
+            const int32_t *pl = a.pop + base + (size_t)p * PW;
+            int32_t *o = a.pop_out + base + (size_t)p * PW;
+            for (int i = q; i < cap * 3; i += 64) o[i] = i < Lp * 3 ? pl[i] : -1;
+        }
+    }
+    keys[q] = key;
+    __syncthreads();
+
+    const uint64_t sg = gen::draw(a.seed, (uint32_t)(a.first_env + env));
+    const int32_t *src = a.pop + base;
+    for (int t = 1; t <= T; ++t) {
+        long long bkey;
+        int bq;
+        least(key, bkey, bq);
+        if (q == 0) a.history[(size_t)(t - 1) * N + env] = bkey;
+        int32_t *dst = (((T - t) & 1) ? a.work : a.pop_out) + base;      // the last generation lands in pop_out
+        const long long *kprev = keys + ((t - 1) & 1) * 64;
+        if (q < P) {
+            const uint64_t c = gen::draw(sg, (uint32_t)(t - 1) * (uint32_t)P + (uint32_t)q);
+            int pa = bq, pb = bq, mrow = -1;
+            const bool elite = q == 0;                                   // both parents the best individual, every job from A, no mutation
+            if (!elite) {
+                auto tournament = [&](uint32_t i) {
+                    const int x = (int)search_pick(gen::draw(c, i), (uint32_t)P), y = (int)search_pick(gen::draw(c, i + 1u), (uint32_t)P);
+                    const long long kx = kprev[x], ky = kprev[y];
+                    return (ky < kx || (ky == kx && y < x)) ? y : x;
+                };
+                pa = tournament(0u); pb = tournament(2u);
+                for (int i = 0; i < JS; ++i) jset[(size_t)i * 64] = (uint32_t)(gen::draw(c, 8u + (uint32_t)(i >> 1)) >> (32 * (i & 1)));
+                if ((int)search_pick(gen::draw(c, 4u), 65536u) < a.mut_rate && sh.ops > 0) mrow = (int)search_pick(gen::draw(c, 5u), (uint32_t)sh.ops);
+            }
+            const int32_t *A = src + (size_t)pa * PW, *B = src + (size_t)pb * PW;
+            int32_t *ch = dst + (size_t)q * PW;
+            // is the row's job in J1?  (a row whose kind or job number is out of range is in no set; the decode refuses it)
+            auto in_set = [&](const Row &x) {
+                if (elite) return true;
+                if (x.r < 0 || x.r >= sh.R) return false;
+                const uint32_t ka = sh.kinds[1 + x.r].x;
+                const int j = (int)(ka & 0xFFFFu) + x.n;
+                if (x.n < 0 || x.n >= (int)(ka >> 16) || j >= sh.JW) return false;
+                return ((jset[(size_t)(j >> 5) * 64] >> (j & 31)) & 1u) != 0u;
+            };
+            // The child's rows: decode_plan asks for rows 0, 1, 2 ... in this order, each once, when the move is none (or of kind
+            // 1), so B's cursor lives here and only moves forward.  It stays below cap; where it runs out the child ends.
+            int cur = 0;
+            auto row = [&](int idx) {
+                const Row x = row_at(A, idx);
+                if (is_end(x) || in_set(x)) return x;
+                while (cur < cap) {
+                    const Row y = row_at(B, cur++);
+                    if (is_end(y)) break;
+                    if (!in_set(y)) return y;
+                }
+                return Row{-1, -1, -1};
+            };
+            // the mutation: row mrow runs on the pick(d6, n_e)-th of the n_e eligible machines of its operation, ascending
+            auto fix = [&](int i, Row &x, int k) {
+                if (i != mrow) return;
+                const uint16_t *pk = sh.p + (size_t)k * sh.MP;
+                int n_e = 0;
+                for (int m = 0; m < sh.M; ++m) n_e += pk[m] != 0 ? 1 : 0;
+                if (n_e == 0) return;
+                int left = (int)search_pick(gen::draw(c, 6u), (uint32_t)n_e);
+                for (int m = 0; m < sh.M; ++m)
+                    if (pk[m] != 0 && left-- == 0) { x.m = m; break; }
+            };
+            const int err = decode_plan<DYN>(b, sh, st, row, cap, no_move(), [&](int i, const Row &x, const Step &) {
+                ch[3 * i] = x.r; ch[3 * i + 1] = x.n; ch[3 * i + 2] = x.m;
+            }, L, mk, td, &dy, &en, fix);
+            key = err ? kNone : chosen(mk, td, en);                      // a child that failed loses every comparison; its plan is empty
+            for (int i = err ? 0 : L; i < cap; ++i) { ch[3 * i] = -1; ch[3 * i + 1] = -1; ch[3 * i + 2] = -1; }
+            if (a.trace) {
+                int32_t *o = a.trace + (((size_t)(t - 1) * N + env) * (size_t)P + q) * 3;
+                o[0] = pa; o[1] = pb; o[2] = mrow;
+            }
+        }
+        keys[(t & 1) * 64 + q] = key;
+        __syncthreads();                                                 // the children and their keys are handed on
+        src = dst;
+    }
+
+    long long bkey;
+    int bq;
+    least(key, bkey, bq);
+    const long long b_mk = __shfl(mk, bq), b_td = __shfl(td, bq), b_en = __shfl(en, bq);
+    if (q == 0) {
+        a.history[(size_t)T * N + env] = bkey;
+        a.status[env] = 0;
+        a.objective[NO * (size_t)env] = b_mk; a.objective[NO * (size_t)env + 1] = b_td;
+        if constexpr (DYN) a.objective[NO * (size_t)env + 2] = b_en;
+    }
+    if (q < P) {
+        int64_t *o = a.pop_obj + ((size_t)env * P + q) * NO;
+        o[0] = mk; o[1] = td;
+        if constexpr (DYN) o[2] = en;
+    }
+    __syncthreads();                                                     // (T = 0: the rows above)
+    for (size_t i = q; i < PW; i += 64) a.best_plan[(size_t)env * PW + i] = a.pop_out[base + (size_t)bq * PW + i];
+}
+
 // candidates per workgroup, 0 = the state of 32 candidates does not fit the LDS of a CU
 int decode_group(size_t bytes) {
     for (int G = 256; G >= 64; G >>= 1)
@@ -1091,5 +1285,56 @@ extern "C" int fjsp_schedule_search_front(fjsp_env *e, const int32_t *d_plan, in
     const int rc = dyn ? launch(schedule_search_kernel<true, FrontArgs>, dim3((unsigned)b.N), dim3(64), lds, st, b, a)
                        : launch(schedule_search_kernel<false, FrontArgs>, dim3((unsigned)b.N), dim3(64), lds, st, b, a);
     if (rc != 0) { set_error(std::string(dyn ? "schedule_search_kernel<true, FrontArgs>" : "schedule_search_kernel<false, FrontArgs>") + " launch failed"); return FJSP_E_HIP; }
+    return FJSP_OK;
+}
+
+// bytes of an env's working set in fjsp_schedule_evolve, whatever the limit (the kernel lays LDS out by the same words)
+static size_t evolve_bytes(const fjsp_env *e) {
+    const DevBatch &b = e->b;
+    return evolve_words(b.variant == FJSP_VARIANT_MO_DFJSP ? dyn_state_words(b.jcap, b.MP) : state_words(b.jcap, b.MP), b.jcap) * 4;
+}
+
+extern "C" int fjsp_schedule_evolve_lds(const fjsp_env *e) {
+    if (!e || e->ops_max <= 0) return 0;
+    const size_t bytes = evolve_bytes(e);
+    return bytes <= kLdsCu ? (int)bytes : 0;
+}
+
+extern "C" int fjsp_schedule_evolve(fjsp_env *e, const int32_t *d_pop, int32_t pop, int32_t generations, const int64_t *d_weights,
+                                    int32_t mut_rate, uint64_t seed, int64_t first_env, int32_t *d_pop_out, int32_t *d_work,
+                                    int64_t *d_pop_obj, int32_t *d_best_plan, int64_t *d_objective, int64_t *d_history, int32_t *d_status,
+                                    int32_t *d_trace, void *stream) {
+    const std::string fn = "fjsp_schedule_evolve";
+    if (!e || !d_pop || !d_weights || !d_pop_out || !d_work || !d_pop_obj || !d_best_plan || !d_objective || !d_history || !d_status) {
+        set_error(fn + ": null env, population, weights or output pointer"); return FJSP_E_ARG;
+    }
+    if (e->gen_failed) { set_error(fn + ": the last regenerate of this handle failed"); return FJSP_E_STATE; }
+    if (pop < 1 || pop > 64 || generations < 0 || mut_rate < 0 || mut_rate > 65536) {
+        set_error(fn + ": needs pop in 1..64, generations >= 0 and mut_rate in 0..65536"); return FJSP_E_ARG;
+    }
+    if ((unsigned long long)generations * (unsigned long long)pop > 0xFFFFFFFFULL) {
+        set_error(fn + ": generations x pop children per env exceed 2^32 - 1"); return FJSP_E_ARG;
+    }
+    const DevBatch &b = e->b;
+    if (e->ops_max <= 0) { set_error(fn + ": no operations"); return FJSP_E_ARG; }
+    const bool dyn = b.variant == FJSP_VARIANT_MO_DFJSP;
+    const size_t lds = evolve_bytes(e);
+    if (lds > kLdsCu) {
+        set_error(fn + ": an env's working set (64 individuals' states of " + std::to_string((dyn ? dyn_state_words(b.jcap, b.MP) : state_words(b.jcap, b.MP)) * 4) +
+                  " bytes, 64 job sets of " + std::to_string(evolve_set_words(b.jcap) * 4) + " and 1024 more: " + std::to_string(lds) + " bytes) exceeds the " +
+                  std::to_string(kLdsCu) + " bytes of a CU's LDS");
+        return FJSP_E_UNSUPPORTED;
+    }
+    DeviceGuard guard(e->device);
+    if (!e->d_decode_kinds && !dev_alloc(e, (size_t)b.n_inst * (size_t)(b.KP + 1) * sizeof(uint2), &e->d_decode_kinds, "hipMalloc (decode kind table)")) return FJSP_E_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch(decode_kinds_kernel, dim3((unsigned)((b.n_inst + 63) / 64)), dim3(64), 0, st, b, e->d_decode_kinds) != 0) {
+        set_error("decode_kinds_kernel launch failed"); return FJSP_E_HIP;
+    }
+    const EvolveArgs a{d_pop, d_pop_out, d_work, d_weights, d_pop_obj, d_best_plan, d_objective, d_history, d_status, d_trace, e->d_decode_kinds,
+                       seed ^ FJSP_EVOLVE_STREAM, (long long)first_env, (int)pop, (int)generations, (int)mut_rate, e->ops_max, b.jcap};
+    const int rc = dyn ? launch(schedule_evolve_kernel<true>, dim3((unsigned)b.N), dim3(64), lds, st, b, a)
+                       : launch(schedule_evolve_kernel<false>, dim3((unsigned)b.N), dim3(64), lds, st, b, a);
+    if (rc != 0) { set_error(std::string(dyn ? "schedule_evolve_kernel<true>" : "schedule_evolve_kernel<false>") + " launch failed"); return FJSP_E_HIP; }
     return FJSP_OK;
 }

@@ -38,6 +38,9 @@ slowly.
 - front_search: local_search steered by a weighted sum of the objectives, one weight vector per env, that keeps the Pareto
   archive of every schedule it decodes in the same launch (schedule.search_front, fjsp_schedule_search_front), and with
   merge=True the front per instance over its envs' archives (pareto.select).
+- seed_population, genetic_search: a population search on the same plans -- the GA baseline of the FJSP literature -- with all
+  its generations in one launch (schedule.evolve, fjsp_schedule_evolve): a lane per individual, which decodes its child
+  while it merges it from two parents; seeded from recorded or sampled schedules.
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -817,4 +820,105 @@ def front_search(batch, plan, rounds, weights=None, neighbours=64, cap_front=64,
                front_src=torch.gather(src, 1, order[..., None].expand(N, F, 2)), count=res["front_count"], dropped=res["front_dropped"])
     if merge:
         out["merged_front"], out["merged_count"] = merge_fronts(obj, src[..., 1] >= 0, b.n_inst)
+    return out
+
+
+def seed_population(batch, plan, population, shake=4, seed=0):
+    """A start population for genetic_search from one or a few plans per env: int32[N, population, cap, 3].  plan: int32[N,
+    cap, 3] or [N, P0, cap, 3] (e.g. schedule.plan_of of a recorded schedule, or the K schedules best_of / pareto_front
+    sampled); individual q is plan q mod P0, and for q >= P0 that plan after `shake` successive random moves of improve's
+    uniform neighbourhood (_uniform_moves: a uniform row on a machine drawn uniformly from its operation's eligible ones, or
+    a uniform row exchanged with its successor, in turns), applied by schedule.apply_moves.  Drawn on the device from a
+    torch.Generator seeded with `seed`: the same arguments give the same population.  Neither move can make a plan invalid,
+    so every individual decodes when the sources do.  ValueError for population outside 1..64, shake < 0, a plan of
+    another shape or one that does not decode."""
+    from . import schedule as sch
+    b, _ = _unwrap(batch, None)
+    P, shake = int(population), int(shake)
+    if not 1 <= P <= sch.EVOLVE_MAX_POPULATION or shake < 0:
+        raise ValueError("seed_population needs population in 1..%d and shake >= 0" % sch.EVOLVE_MAX_POPULATION)
+    dev, N, cap = b.device, b.N, b.decode_capacity()
+    plan = torch.as_tensor(plan).to(device=dev, dtype=torch.int32)
+    if plan.dim() == 3:
+        plan = plan[:, None]
+    if plan.dim() != 4 or tuple(plan.shape) != (N, plan.shape[1], cap, 3) or plan.shape[1] < 1:
+        raise ValueError("plan must have shape %s or %s, got %s" % ((N, cap, 3), (N, "P0", cap, 3), tuple(plan.shape)))
+    P0 = int(plan.shape[1])
+    pop = plan[:, torch.arange(P, device=dev) % P0].contiguous()
+    first = (sch.decode_dyn if b.variant == sch.VARIANT_MO_DFJSP else sch.decode)(b, pop, n_cand=P, want_table=True)
+    if bool((first["status"] != 0).any()):
+        raise ValueError("seed_population: a plan does not decode (status %s)" % sorted(set(first["status"].flatten().tolist()) - {0}))
+    if shake == 0 or P <= P0:
+        return pop
+    koff, elig = _machine_tables(b)
+    inst = (torch.arange(N, device=dev) % b.n_inst).repeat_interleave(P)
+    tab = first["table"].reshape(N * P, cap, 6).to(torch.int64)
+    L = first["length"].reshape(N * P).to(torch.int64)
+    k = torch.where(tab[..., 0] >= 0, koff[inst[:, None], tab[..., 0].clamp(min=0)] + tab[..., 1], torch.full_like(tab[..., 0], -1))
+    # rows (r, n, m, k): the operation type travels with its row (neither move changes a row's stage)
+    rows = torch.cat([pop.reshape(N * P, cap, 3).to(torch.int64), k[..., None]], -1).to(torch.int32)
+    q = torch.arange(P, device=dev).repeat(N)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    for s in range(shake):
+        draw = torch.rand(2, N * P, 1, generator=gen, device=dev, dtype=torch.float64)
+        moves = _uniform_moves(sch, draw, L, rows[..., 3], elig, inst, ((q + s) % 2 == 1)[:, None])
+        moves[q < P0, 0, 0] = sch.MOVE_NONE                                                             # the given plans stay
+        rows = sch.apply_moves(rows, moves)[:, 0]
+    return rows[..., :3].reshape(N, P, cap, 3).contiguous()
+
+
+def genetic_search(batch, population, generations, objective="makespan", weights=None, mutation=0.1, seed=0, merge=False):
+    """A genetic algorithm on explicit schedules, every generation of every env in ONE launch (schedule.evolve,
+    fjsp_schedule_evolve, csrc/fjsp_decode.hip): a wavefront owns an env, a lane an individual.  Per generation child 0 is
+    the best individual unchanged (the elite); every other child draws two parents by binary tournaments, takes the rows of
+    a random set of jobs from the first in place and the remaining rows from the second in its order (precedence-preserving
+    order crossover; a row keeps its machine), is mutated with probability `mutation` (one uniform row on a machine drawn
+    uniformly from its operation's eligible ones), and is decoded by the lane while it is built.  Draws are a counter-based
+    splitmix64 stream of (seed, global env id, generation, child): a shard of a batch evolves exactly as those envs of the
+    whole batch do.
+
+    population: int32[N, P, cap, 3], P in 1..64, every plan must decode (seed_population makes one).  objective: the
+    single objective minimised, "makespan" or "tardiness", on MO_DFJSP also "energy"; weights, if given, replace it as in
+    front_search: a vector of NO non-negative integers that are not all zero, or [N, NO], the key being their weighted sum.
+
+    Returns dict(plan=int32[N, cap, 3] and objective=int64[N, NO] of the best individual of the last generation,
+    history=int64[generations + 1, N] the least key of every generation (it never increases), population=int32[N, P, cap, 3]
+    and population_objective=int64[N, P, NO] the last generation, status=int32[N] (zeros)) and with merge=True, per instance,
+    merged_front f64[n_inst, C, NO] (NaN past the front) and merged_count int32[n_inst]: the front (pareto.select) of the
+    last generations of all envs i with i % n_inst the instance, C = envs of an instance x P, which must not exceed 1024.
+    ValueError for an unknown objective, generations < 0, mutation outside 0..1, a population or weights of another shape,
+    bad weights, a plan that does not decode, and with merge C > 1024 or an objective >= 2^53; FjspError where the library
+    refuses (EnvBatch.evolve_lds)."""
+    from . import schedule as sch
+    b, _ = _unwrap(batch, None)
+    objectives = sch.SEARCH_DYN_OBJECTIVES if b.variant == sch.VARIANT_MO_DFJSP else sch.SEARCH_OBJECTIVES
+    n_obj = len(objectives)
+    if weights is None and objective not in objectives:
+        raise ValueError("objective must be one of %s" % (objectives,))
+    generations, mutation = int(generations), float(mutation)
+    if generations < 0 or not 0.0 <= mutation <= 1.0:
+        raise ValueError("genetic_search needs generations >= 0 and mutation in 0..1")
+    dev, N = b.device, b.N
+    population = torch.as_tensor(population)
+    if population.dim() != 4 or not 1 <= population.shape[1] <= sch.EVOLVE_MAX_POPULATION:
+        raise ValueError("population must be [N, P, cap, 3] with P in 1..%d, got %s" % (sch.EVOLVE_MAX_POPULATION, tuple(population.shape)))
+    P = int(population.shape[1])
+    w = torch.eye(n_obj, dtype=torch.int64)[objectives.index(objective)] if weights is None else torch.as_tensor(weights)
+    if w.is_floating_point() or w.dim() not in (1, 2) or w.shape[-1] != n_obj or (w.dim() == 2 and w.shape[0] != N):
+        raise ValueError("weights must be integers of shape (%d,) or (%d, %d)" % (n_obj, N, n_obj))
+    w = w.to(device=dev, dtype=torch.int64).expand(N, n_obj).contiguous()
+    if bool(((w < 0).any(1) | (w == 0).all(1)).any()):
+        raise ValueError("weights must be non-negative and not all zero in every env")
+    n_group = -(-N // b.n_inst)
+    if merge and n_group * P > pareto.MAX_CANDIDATES:
+        raise ValueError("merge: %d envs of an instance x population %d exceed pareto.select's %d candidates" % (n_group, P, pareto.MAX_CANDIDATES))
+    res = sch.evolve(b, population, generations, w, int(round(mutation * sch.EVOLVE_MUT_ONE)), seed)
+    if bool((res["status"] != 0).any()):
+        raise ValueError("genetic_search: a plan does not decode (status %s)" % sorted(set(res["status"].tolist()) - {0}))
+    out = dict(plan=res["plan"], objective=res["objective"], history=res["history"], population=res["population"],
+               population_objective=res["population_objective"], status=res["status"])
+    if merge:
+        held = torch.ones(N, P, dtype=torch.bool, device=dev)
+        out["merged_front"], out["merged_count"] = merge_fronts(res["population_objective"], held, b.n_inst)
     return out

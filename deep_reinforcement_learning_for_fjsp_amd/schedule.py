@@ -20,6 +20,7 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     search_dyn(batch, plan, rounds, n_cand, ...) the same on MO_DFJSP: uniform neighbourhood, energy as a third objective
     search_front(batch, plan, weights, ...)     that search steered by a weighted sum, keeping the Pareto archive of its decodes
     search_draws(seed, env, first, n)           the draw stream of that search, on the host
+    evolve(batch, pop_plans, generations, ...)  a genetic algorithm on populations of plans, all generations in one launch
 
 `inst` is anything with the instance arrays of instances.InstanceArrays: Jr[R], p[K][M] (0 = ineligible),
 count[S][R], arrive[S], delivery[S] (and bk_n[M], bk[W][2] for MO_DFJSP breakdown windows).
@@ -483,6 +484,51 @@ def search_front(batch, plan, weights, rounds, n_cand, cap_front=64, accept=1, t
                                             ptr(out["history"]), ptr(out["accepted"]), ptr(out["status"]), ptr(out["trace"]),
                                             ptr(out["front_obj"]), ptr(out["front_src"]), ptr(out["front_plan"]), ptr(out["front_count"]),
                                             ptr(out["front_dropped"]), b._stream()))
+    return out
+
+
+EVOLVE_MAX_POPULATION = 64
+EVOLVE_MUT_ONE = 65536                          # mut_rate of a mutation in every child
+
+
+def evolve(batch, pop_plans, generations, weights=None, mut_rate=6554, seed=0, trace=False):
+    """fjsp_schedule_evolve on the current stream: `generations` generations of a genetic algorithm on a population of plans
+    per env -- tournament selection by the key sum_c weights[e, c] * objective[c], precedence-preserving order crossover,
+    a machine mutation in mut_rate / 65536 of the children, one elite -- in one launch (the contract is in
+    include/fjsp_amd.h; policy_search.genetic_search is the checked form).  Either family: NO = 3 objectives on MO_DFJSP, 2
+    elsewhere.  pop_plans: int32[N, P, cap, 3], P in 1..64; weights: None (the makespan alone) or int64[N, NO].  Passes
+    batch.first_env.  Returns dict(population=int32[N, P, cap, 3] the last generation, population_objective=int64[N, P, NO],
+    plan=int32[N, cap, 3] and objective=int64[N, NO] of the individual of least (key, index), history=int64[generations + 1,
+    N] the least key of every generation, status=int32[N], trace=int32[generations, N, P, 3] (parent A, parent B, mutated row
+    or -1) or None), device tensors.  ValueError for a population or weights of another shape; FjspError where the library
+    refuses."""
+    import torch
+    from ._capi import check, ptr
+    b = getattr(batch, "batch", batch)
+    cap = int(b._lib.fjsp_schedule_decode_capacity(b._h))
+    n_obj = 3 if b.variant == VARIANT_MO_DFJSP else 2
+    if not torch.is_tensor(pop_plans):
+        pop_plans = torch.as_tensor(np.asarray(pop_plans))
+    if pop_plans.dim() != 4 or tuple(pop_plans.shape) != (b.N, pop_plans.shape[1], cap, 3):
+        raise ValueError("pop_plans must have shape %s, got %s" % ((b.N, "P", cap, 3), tuple(pop_plans.shape)))
+    P = int(pop_plans.shape[1])
+    if weights is None:
+        weights = torch.tensor([1] + [0] * (n_obj - 1), dtype=torch.int64).expand(b.N, n_obj)
+    elif not torch.is_tensor(weights):
+        weights = torch.as_tensor(np.asarray(weights, np.int64))
+    if tuple(weights.shape) != (b.N, n_obj):
+        raise ValueError("weights must have shape %s, got %s" % ((b.N, n_obj), tuple(weights.shape)))
+    pop_plans = pop_plans.to(device=b.device, dtype=torch.int32).contiguous()
+    weights = weights.to(device=b.device, dtype=torch.int64).contiguous()
+    rows = max(int(generations), 0)
+    new = lambda *shape, dtype=torch.int32: torch.empty(shape, dtype=dtype, device=b.device)
+    out = dict(population=torch.empty_like(pop_plans), population_objective=new(b.N, P, n_obj, dtype=torch.int64), plan=new(b.N, cap, 3),
+               objective=new(b.N, n_obj, dtype=torch.int64), history=new(rows + 1, b.N, dtype=torch.int64), status=new(b.N),
+               trace=new(rows, b.N, P, 3) if trace else None)
+    work = torch.empty_like(pop_plans)
+    check(b._lib.fjsp_schedule_evolve(b._h, ptr(pop_plans), P, int(generations), ptr(weights), int(mut_rate), int(seed) & (2 ** 64 - 1),
+                                      int(b.first_env), ptr(out["population"]), ptr(work), ptr(out["population_objective"]), ptr(out["plan"]),
+                                      ptr(out["objective"]), ptr(out["history"]), ptr(out["status"]), ptr(out["trace"]), b._stream()))
     return out
 
 

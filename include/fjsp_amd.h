@@ -1001,6 +1001,74 @@ int fjsp_schedule_search_front(fjsp_env *e, const int32_t *d_plan, int32_t round
                                int32_t *d_front_count, int32_t *d_front_dropped, void *stream);
 int fjsp_schedule_search_front_lds(const fjsp_env *e, int32_t cap_front);
 
+/* Evolve populations of explicit schedules, every generation of every env in ONE launch (schedule.evolve,
+ * policy_search.genetic_search; csrc/fjsp_decode.hip, schedule_evolve_kernel<DYN>): a genetic algorithm with tournament
+ * selection, a precedence-preserving order crossover, a machine mutation and one elite, the non-learning baseline of the
+ * FJSP literature, on the instances, objectives and decode rules of the entries above.  The result is a function of the
+ * arguments alone; tests/evolve_reference.py restates it in numpy and Python integers, bit for bit.
+ *
+ * One entry serves both families.  On a FJSP_VARIANT_MO_DFJSP handle every decode is fjsp_schedule_decode_dyn's and NO = 3
+ * (makespan, total tardiness, energy); on every other handle every decode is fjsp_schedule_decode's and NO = 2.
+ *
+ *   d_pop        i32[N][pop][cap][3]  the start population: pop (1..64) plans per env, as decode takes them
+ *   d_weights    i64[N][NO]           the key, fjsp_schedule_search_front's: sum over c of w[c] * obj[c], every product and
+ *                                     partial sum saturating at 2^63 - 2; a unit vector is a single objective
+ *   mut_rate     0..65536             a child is mutated with probability mut_rate / 65536
+ *   d_pop_out    i32[N][pop][cap][3]  the last generation, -1 rows past a plan's end
+ *   d_work       i32[N][pop][cap][3]  the other population buffer; its content after the call is unspecified
+ *   d_pop_obj    i64[N][pop][NO]      the vectors of d_pop_out's individuals
+ *   d_best_plan  i32[N][cap][3], d_objective i64[N][NO]   the individual of d_pop_out with the least (key, index)
+ *   d_history    i64[generations + 1][N]   the least key of every generation, the start population's first; it never
+ *                                     increases, because of the elite
+ *   d_status     i32[N]
+ *   d_trace      nullable, i32[generations][N][pop][3]   per child (parent A, parent B, the mutated row or -1)
+ * d_pop, d_pop_out and d_work must not overlap.  Generation t reads one of d_pop_out / d_work and writes the other
+ * (generation 1 reads d_pop); the first buffer is picked by the parity of `generations`, so that the last lands in
+ * d_pop_out.  With generations = 0 the outputs describe the start population (d_pop_out = its rows, -1 past each plan's end).
+ *
+ * Draws: splitmix64 as everywhere (draw(seed, i)), in a stream of its own: env g = first_env + e has s_g = draw(seed ^
+ * FJSP_EVOLVE_STREAM, (uint32_t)g), child q of generation t (1-based) has c = draw(s_g, (uint32_t)((t - 1) * pop + q)), and its
+ * draws are d_i = draw(c, i): i = 0..3 the tournaments, 4, 5, 6 the mutation, 8 + w word w of the job set.  pick(d, n) =
+ * ((d >> 32) * n) >> 32, as in fjsp_schedule_search.  A shard with first_env = k reproduces its envs of the whole batch.
+ *
+ * Generation 0: every individual of d_pop is decoded.  Bad weights (a negative one, or all zero) give the env status 5;
+ * otherwise, if an individual has a decode status other than 0, the env's status is that of the lowest such q.  An env
+ * whose status is not 0 is copied through, and the other envs are not affected: d_pop_out = the input rows as they came,
+ * d_best_plan = individual 0, d_pop_obj, d_objective and its d_history column -1, its trace zeros.
+ *
+ * Generation t >= 1, child q, from generation t - 1:
+ *   parents    q = 0 is the elite: A = B = the individual with the least (key, index), every job in J1, no mutation.
+ *              q > 0: A = whichever of pick(d0, pop), pick(d1, pop) has the lesser (key, index), B the same of d2, d3.
+ *   job set    job j is in J1 iff bit (j & 63) of draw(c, 8 + (j >> 6)) is set; j numbers the jobs over the instance's
+ *              kinds in order (the first job of kind r, + n), as the decoder's state does.
+ *   crossover  precedence-preserving order crossover: position t' = 0 .. L - 1 of the child is row A[t'] if its job is in
+ *              J1, else the next row of B whose job is not in J1, from a cursor that starts at 0 and only moves forward.
+ *              Rows travel whole, (r, n, m).
+ *   mutation   iff pick(d4, 65536) < mut_rate: child row u = pick(d5, L) runs on the pick(d6, n_e)-th of the n_e eligible
+ *              machines of its operation, ascending (the kind-1 candidate of the searches; it may be the row's own).
+ *   decode     by the family's rule; the child's vector and key are recorded.
+ * The child always decodes: both parents decoded with status 0 on the same instance, so they hold the same operations --
+ * the positions of A whose job is outside J1 are as many as the rows of B whose job is outside J1, so the cursor never runs
+ * out --, the rows of one job come from one parent and keep that parent's order, so every job meets its stages in order,
+ * and every row keeps a machine that was eligible for it, or is moved to one.  The kernel does not rely on it: the cursor is
+ * bounded by cap and the child ends where it runs out, every check of the decode runs on every child, and a child that
+ * failed would hold no rows and the key 2^63 - 1, which loses every comparison.  Nothing is left to fault.
+ *
+ * Stream-ordered, no host synchronisation, no atomics, two launches for any number of generations; capturable.
+ * Limit: the 64 individuals' states of the family's decode (5 bytes per job rounded up to 16 jobs + 4 per machine, 8 per
+ * machine on MO_DFJSP), per individual one bit per job in words of 4 bytes, and two rows of 64 keys must fit the 160 KB of
+ * a CU's LDS:   64 x (state + 4 x ceil(jobs16 / 32)) + 1024
+ * fjsp_schedule_evolve_lds(e) is that sum in bytes, 0 where it does not fit.
+ * FJSP_E_ARG: a null e, d_pop, d_weights or output other than d_trace, pop outside 1..64, generations < 0, mut_rate outside
+ * 0..65536, generations x pop > 2^32 - 1.  FJSP_E_UNSUPPORTED: a working set beyond the limit (the message gives the
+ * bytes).  FJSP_E_STATE: a generated handle whose last regenerate failed.  Every check runs before any device call. */
+#define FJSP_EVOLVE_STREAM 0xC2B2AE3D27D4EB4FULL
+int fjsp_schedule_evolve(fjsp_env *e, const int32_t *d_pop, int32_t pop, int32_t generations, const int64_t *d_weights,
+                         int32_t mut_rate, uint64_t seed, int64_t first_env,
+                         int32_t *d_pop_out, int32_t *d_work, int64_t *d_pop_obj, int32_t *d_best_plan, int64_t *d_objective,
+                         int64_t *d_history, int32_t *d_status, int32_t *d_trace, void *stream);
+int fjsp_schedule_evolve_lds(const fjsp_env *e);
+
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
  *
