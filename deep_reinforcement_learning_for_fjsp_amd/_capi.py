@@ -176,6 +176,9 @@ SIGNATURES = {
     "fjsp_schedule_decode": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_schedule_decode_capacity": (C.c_int, [_vp]),
     "fjsp_schedule_decode_group": (C.c_int, [_vp]),
+    "fjsp_schedule_decode_active": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fjsp_schedule_decode_active_group": (C.c_int, [_vp]),
+    "fjsp_schedule_decode_active_resident": (C.c_int, [_vp]),
     "fjsp_schedule_decode_dyn": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_schedule_decode_dyn_group": (C.c_int, [_vp]),
     "fjsp_schedule_critical": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -674,6 +674,21 @@ class EnvBatch(object):
         from . import schedule
         return schedule.decode(self, plan, moves, n_cand, want_table)
 
+    def decode_active_group(self):
+        """Candidates one workgroup of the active decode kernel takes (fjsp_schedule_decode_active_group): decode_group()."""
+        return int(self._lib.fjsp_schedule_decode_active_group(self._h))
+
+    def decode_active_resident(self):
+        """Candidates of a decode_active call that are resident at once (fjsp_schedule_decode_active_resident): the bounded
+        grid's workgroups x decode_active_group(); the handle's workspace holds 8 x decode_capacity() bytes for each."""
+        return int(self._lib.fjsp_schedule_decode_active_resident(self._h))
+
+    def decode_active(self, plan, moves=None, n_cand=1, want_table=False):
+        """schedule.decode_active on this batch's instances: explicit schedules decoded with insertion into machine gaps ->
+        objectives, status, tables, lengths, inserted rows."""
+        from . import schedule
+        return schedule.decode_active(self, plan, moves, n_cand, want_table)
+
     def decode_dyn_group(self):
         """Candidates one workgroup of the MO_DFJSP decode kernel takes (fjsp_schedule_decode_dyn_group); 0: the batch is
         not MO_DFJSP, or a candidate's state exceeds the limit."""

@@ -26,6 +26,11 @@
 // keeps one more banked word per machine, the end of its last task; free[m] is the machine's end there and the objective
 // has a third entry, energy.  The three kernels without DYN compile to what they compiled to before the switch.
 //
+// fjsp_schedule_decode_active is the plain kernel text once more with a placement policy (Gaps, at its definition): a row
+// goes into the earliest idle interval of its machine that fits, the intervals of a candidate in a workspace of the handle,
+// a bounded grid whose workgroups loop over the call's groups (schedule_decode_active_kernel).  The kernels without the
+// policy compile to what they compiled to before it.
+//
 // fjsp_schedule_critical is the decode run backwards, on the tables decode writes: one lane per table, the same grouping,
 // the same banked words -- per job and per machine "tail + duration of the latest row seen", as decode keeps ready / free.
 // A forward scan finds the table's end, checks every index it supplies, and the first row that ends at the makespan; the
@@ -203,11 +208,15 @@ __device__ __forceinline__ DynShop dyn_shop_of(const DevBatch &b, const Shop &sh
 // end moves on its own; *energy gathers power x duration and idle power x the gap from the last task's end to t0.
 // fix(t, row, operation type), which only fjsp_schedule_evolve passes, may put row t on another machine once its stage is
 // known and before its machine is checked; the callers that do not pass it compile to what they compiled to without it.
+// gaps, which only fjsp_schedule_decode_active passes (Gaps, below; the caller's object, which counts), places a row in the
+// earliest idle interval of its machine in place of max(ready, free): free[m] is then the policy's word (the machine's
+// latest interval), not a clock.
 struct NoFix { __device__ __forceinline__ void operator()(int, Row &, int) const {} };
-template <bool DYN = false, class RowAt, class Sink, class Fix = NoFix>
+struct NoGaps { static constexpr bool on = false; };
+template <bool DYN = false, class RowAt, class Sink, class Fix = NoFix, class Place = NoGaps>
 __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, const State &st, RowAt row, int cap, const Move &mv, Sink sink,
                                            int &L, long long &makespan, long long &tard, const DynShop *dy = nullptr, long long *energy = nullptr,
-                                           Fix fix = Fix{}) {
+                                           Fix fix = Fix{}, Place *gaps = nullptr) {
     const int G = st.G, JW = sh.JW, MP = sh.MP;
     const int32_t *oarr = reinterpret_cast<const int32_t *>(sh.ir + b.L.i_oarr);
     const uint16_t *ocnt = reinterpret_cast<const uint16_t *>(sh.ir + b.L.i_ocnt);
@@ -248,7 +257,10 @@ __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, co
         if (x.m < 0 || x.m >= sh.M) { err = 3; continue; }
         const int pv = (int)sh.p[(size_t)(koff + stg) * MP + x.m];
         if (pv == 0) { err = 3; continue; }
-        int begin = max((int)st.ready[(size_t)j * G], (int)st.mfree[(size_t)x.m * G]), end = begin + pv;
+        int begin;
+        if constexpr (Place::on) begin = gaps->place(t, (int)st.ready[(size_t)j * G], pv, st.mfree + (size_t)x.m * G);
+        else begin = max((int)st.ready[(size_t)j * G], (int)st.mfree[(size_t)x.m * G]);
+        int end = begin + pv;
         if constexpr (DYN) {
             const int t0 = begin;
             int mend = end;
@@ -268,7 +280,7 @@ __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, co
             st.mfree[(size_t)x.m * G] = (uint32_t)mend;
         } else {
             st.ready[(size_t)j * G] = (uint32_t)end;
-            st.mfree[(size_t)x.m * G] = (uint32_t)end;
+            if constexpr (!Place::on) st.mfree[(size_t)x.m * G] = (uint32_t)end;
         }
         *sj = (uint8_t)(stg + 1);
         makespan = max(makespan, (long long)end);
@@ -279,13 +291,51 @@ __device__ __forceinline__ int decode_plan(const DevBatch &b, const Shop &sh, co
     return err;
 }
 
-// One candidate of schedule_decode_kernel (objective i64[2]) and of schedule_decode_dyn_kernel (DYN: MO_DFJSP, objective
-// i64[3] with the energy, the state a word per machine longer)
-template <bool DYN>
-__device__ __forceinline__ void decode_candidate(const DevBatch &b, const DecodeArgs &a, int BW) {
+// ---- fjsp_schedule_decode_active: insertion into machine gaps.  A candidate keeps the busy intervals of its machines in
+// global memory, one entry per decoded row: entry t (the row at plan position t) is the pair (begin, duration | pred <<
+// 16), pred = the entry in front of it on its machine, 1-based, 0 = none (a plan has at most 65535 rows and p is 16 bits
+// wide, fjsp_env_create).  The chain of a machine is followed from its LATEST interval, which free[m]'s word holds
+// (1-based, 0 = an idle machine: what decode_plan initialises it to): the contract walks the intervals from the first and
+// takes the first gap that fits; the intervals of a machine are disjoint, so their ends ascend with their begins, gap i
+// (behind interval i, in front of interval i + 1) fits iff max(s, e_i) + d <= b_{i + 1}, and no gap in front of an
+// interval that ends at or before s can fit -- so the walk from the back, down to the first such interval, that keeps
+// the LOWEST gap that fits finds the same one, and is as long as the intervals that end after the job is ready, not as
+// the machine's whole list.  Entry i of the candidate in slot s of workgroup w is ws[(w * cap + i) * G + s]: the lanes of
+// a wave that touch entry i of their candidates read one 8-byte word each at consecutive addresses.  A lane reads only
+// entries it reaches from a tail word that it reset itself, and each of those it wrote in this decode: what an earlier
+// candidate left in the slot is never looked at, and the workspace needs no clearing between candidates, groups or calls.
+struct Gaps {
+    static constexpr bool on = true;
+    uint2 *ws;               // entry 0 of this lane's slot
+    int G;
+    int inserted;            // rows placed in front of an interval
+    __device__ __forceinline__ int place(int t, int s, int d, uint32_t *tail) {
+        uint32_t cur = *tail, succ = 0, succ_y = 0, at_pred = cur, at_succ = 0, at_succ_y = 0;
+        int nb = 0x7fffffff, start = s;                                  // begin of the interval behind the gap looked at
+        for (int n = 0; n <= t; ++n) {                                   // (a chain holds at most the t rows decoded so far)
+            const uint2 x = cur ? ws[(size_t)(cur - 1) * G] : make_uint2(0u, 0u);
+            const int e = cur ? (int)(x.x + (x.y & 0xFFFFu)) : s;
+            const int at = max(s, e);
+            if (at + d <= nb) { start = at; at_pred = cur; at_succ = succ; at_succ_y = succ_y; }
+            if (e <= s) break;                                           // (the front of the list included)
+            nb = (int)x.x; succ = cur; succ_y = x.y; cur = x.y >> 16;
+        }
+        ws[(size_t)t * G] = make_uint2((uint32_t)start, (uint32_t)d | (at_pred << 16));
+        if (at_succ) { ws[(size_t)(at_succ - 1) * G].y = (at_succ_y & 0xFFFFu) | ((uint32_t)(t + 1) << 16); ++inserted; }
+        else *tail = (uint32_t)(t + 1);
+        return start;
+    }
+};
+
+// One candidate of schedule_decode_kernel (objective i64[2]), of schedule_decode_dyn_kernel (DYN: MO_DFJSP, objective
+// i64[3] with the energy, the state a word per machine longer) and of schedule_decode_active_kernel (ACTIVE: group grp of
+// the call, its intervals in the workgroup's part `ws` of the workspace)
+template <bool DYN, bool ACTIVE = false>
+__device__ __forceinline__ void decode_candidate(const DevBatch &b, const DecodeArgs &a, int BW, long long grp, uint2 *ws = nullptr,
+                                                 int32_t *d_inserted = nullptr) {
     constexpr int NO = DYN ? 3 : 2;
     const int s = (int)threadIdx.x;
-    const long long g = (long long)blockIdx.x * a.G + s;
+    const long long g = grp * a.G + s;
     if (s >= a.G || g >= a.total) return;
     const int env = (int)(g / a.n_cand), q = (int)(g - (long long)env * a.n_cand), inst = env % b.n_inst;
     const int cap = a.cap;
@@ -306,16 +356,24 @@ __device__ __forceinline__ void decode_candidate(const DevBatch &b, const Decode
     DynShop dy{};
     if constexpr (DYN) dy = dyn_shop_of(b, sh, st, BW);
     int32_t *tab = a.table ? a.table + (size_t)g * (size_t)cap * 6 : nullptr;
+    int inserted = 0;
     if (!mv.bad) {
-        err = decode_plan<DYN>(b, sh, st, row, cap, mv, [&](int t, const Row &x, const Step &d) {
+        auto sink = [&](int t, const Row &x, const Step &d) {
             if (tab) {
                 int32_t *o = tab + (size_t)t * 6;
                 o[0] = x.r; o[1] = d.stg; o[2] = x.n; o[3] = x.m; o[4] = d.begin; o[5] = d.end;
             }
-        }, L, makespan, tard, &dy, &energy);
+        };
+        if constexpr (ACTIVE) {
+            Gaps gaps{ws + s, a.G, 0};
+            err = decode_plan<DYN>(b, sh, st, row, cap, mv, sink, L, makespan, tard, &dy, &energy, NoFix{}, &gaps);
+            inserted = gaps.inserted;
+        } else err = decode_plan<DYN>(b, sh, st, row, cap, mv, sink, L, makespan, tard, &dy, &energy);
         if (move_past(mv, L)) mv.bad = true;
     }
     const int stt = mv.bad ? 4 : err;
+    if constexpr (ACTIVE)
+        if (d_inserted) d_inserted[g] = stt ? 0 : inserted;
     a.status[g] = stt;
     a.objective[NO * g] = stt ? -1 : makespan;
     a.objective[NO * g + 1] = stt ? -1 : tard;
@@ -329,8 +387,14 @@ __device__ __forceinline__ void decode_candidate(const DevBatch &b, const Decode
     }
 }
 
-__global__ __launch_bounds__(256) void schedule_decode_kernel(DevBatch b, DecodeArgs a) { decode_candidate<false>(b, a, 0); }
-__global__ __launch_bounds__(256) void schedule_decode_dyn_kernel(DevBatch b, DecodeArgs a, int BW) { decode_candidate<true>(b, a, BW); }
+__global__ __launch_bounds__(256) void schedule_decode_kernel(DevBatch b, DecodeArgs a) { decode_candidate<false>(b, a, 0, (long long)blockIdx.x); }
+__global__ __launch_bounds__(256) void schedule_decode_dyn_kernel(DevBatch b, DecodeArgs a, int BW) { decode_candidate<true>(b, a, BW, (long long)blockIdx.x); }
+// A bounded grid: workgroup w decodes the groups w, w + gridDim.x, ... of the call one after the other, all of them on
+// its own cap x G entries of the workspace.  A lane's state words and entries are its own, so nothing orders the groups.
+__global__ __launch_bounds__(256) void schedule_decode_active_kernel(DevBatch b, DecodeArgs a, uint2 *ws, int32_t *d_inserted) {
+    uint2 *mine = ws + (size_t)blockIdx.x * (size_t)a.cap * (size_t)a.G;
+    for (long long grp = blockIdx.x; grp * a.G < a.total; grp += gridDim.x) decode_candidate<false, true>(b, a, 0, grp, mine, d_inserted);
+}
 
 // ---- fjsp_schedule_critical: the decode run backwards, one lane per table, the same grouping and banked layout
 struct CriticalArgs {
@@ -1106,6 +1170,59 @@ static int schedule_decode(bool dyn, fjsp_env *e, const int32_t *d_plan, int32_t
 extern "C" int fjsp_schedule_decode(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
                                     int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, void *stream) {
     return schedule_decode(false, e, d_plan, q_plans, d_moves, n_cand, d_objective, d_status, d_table, d_len, stream);
+}
+
+// workgroups of fjsp_schedule_decode_active's grid, each with cap x G entries of 8 bytes: as many as the workspace bound
+// pays for, at least one, at most FJSP_DECODE_ACTIVE_MAX_GROUPS
+static int active_groups(const fjsp_env *e, int G) {
+    const long long per = 8LL * (long long)e->ops_max * (long long)G;
+    const long long n = per > 0 ? (long long)FJSP_DECODE_ACTIVE_WORKSPACE_BYTES / per : 0;
+    return (int)(n < 1 ? 1 : (n > FJSP_DECODE_ACTIVE_MAX_GROUPS ? FJSP_DECODE_ACTIVE_MAX_GROUPS : n));
+}
+
+extern "C" int fjsp_schedule_decode_active_group(const fjsp_env *e) { return fjsp_schedule_decode_group(e); }
+
+extern "C" int fjsp_schedule_decode_active_resident(const fjsp_env *e) {
+    const int G = fjsp_schedule_decode_group(e);
+    return (G > 0 && e->ops_max > 0) ? active_groups(e, G) * G : 0;
+}
+
+extern "C" int fjsp_schedule_decode_active(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
+                                           int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, int32_t *d_inserted,
+                                           void *stream) {
+    const std::string fn = "fjsp_schedule_decode_active";
+    if (!e || !d_plan || !d_objective || !d_status) { set_error(fn + ": null env, plan, objective or status pointer"); return FJSP_E_ARG; }
+    if (n_cand < 1 || (q_plans != 1 && q_plans != n_cand)) { set_error(fn + ": needs n_cand >= 1 and q_plans = 1 or n_cand"); return FJSP_E_ARG; }
+    if (e->b.variant == FJSP_VARIANT_MO_DFJSP) {
+        set_error(fn + ": MO_DFJSP batches are not decoded here (an insertion under breakdown shifts is not defined): fjsp_schedule_decode_dyn decodes them");
+        return FJSP_E_UNSUPPORTED;
+    }
+    if (e->gen_failed) { set_error(fn + ": the last regenerate of this handle failed"); return FJSP_E_STATE; }
+    const DevBatch &b = e->b;
+    const size_t bytes = (size_t)state_words(b.jcap, b.MP) * 4;
+    const int G = decode_group(bytes);
+    if (G == 0) {
+        set_error(fn + ": a candidate's state (5 bytes per job of the largest instance, rounded up to 16 jobs, + 4 per machine: " +
+                  std::to_string(bytes) + " bytes) exceeds 5120 bytes");
+        return FJSP_E_UNSUPPORTED;
+    }
+    const long long total = (long long)b.N * (long long)n_cand;
+    if (e->ops_max <= 0 || total > 0x7fffffffLL) { set_error(fn + ": no operations, or more than 2^31 - 1 candidates"); return FJSP_E_ARG; }
+    DeviceGuard guard(e->device);
+    if (!e->d_decode_kinds && !dev_alloc(e, (size_t)b.n_inst * (size_t)(b.KP + 1) * sizeof(uint2), &e->d_decode_kinds, "hipMalloc (decode kind table)")) return FJSP_E_HIP;
+    const int groups = active_groups(e, G);
+    if (!e->d_active_ws && !dev_alloc(e, (size_t)groups * (size_t)e->ops_max * (size_t)G * sizeof(uint2), &e->d_active_ws, "hipMalloc (active decode workspace)")) return FJSP_E_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch(decode_kinds_kernel, dim3((unsigned)((b.n_inst + 63) / 64)), dim3(64), 0, st, b, e->d_decode_kinds) != 0) {
+        set_error("decode_kinds_kernel launch failed"); return FJSP_E_HIP;
+    }
+    const DecodeArgs a{d_plan, d_moves, d_objective, d_status, d_table, d_len, e->d_decode_kinds, total, (int)n_cand, (int)q_plans, e->ops_max, G, b.jcap};
+    const long long need = (total + G - 1) / G;
+    const dim3 grid((unsigned)(need < groups ? need : groups)), block((unsigned)(G < 64 ? 64 : G));
+    if (launch(schedule_decode_active_kernel, grid, block, bytes * (size_t)G, st, b, a, e->d_active_ws, d_inserted) != 0) {
+        set_error("schedule_decode_active_kernel launch failed"); return FJSP_E_HIP;
+    }
+    return FJSP_OK;
 }
 
 extern "C" int fjsp_schedule_decode_dyn_group(const fjsp_env *e) {

@@ -66,6 +66,7 @@ struct fjsp_env {
     int64_t step_bytes = 0;
     uint8_t *d_done_scratch = nullptr; // scratch for the non-fused rollout fallback
     uint2 *d_decode_kinds = nullptr;   // fjsp_schedule_decode's kind table, [n_inst][KP + 1] (first use; refilled by every call)
+    uint2 *d_active_ws = nullptr;      // fjsp_schedule_decode_active's interval entries, [groups][cap][G] (first use; shared by the handle's calls)
     double *d_seg_reward = nullptr;    // fjsp_env_rollout_policy_orders between its segments: reward f64[N] | next_t i32[N] | parked u8[N] (first use)
     const fjsp_instances *src = nullptr;   // the instances [first, first + n_inst) the batch plays (the host LPs read them)
     int first = 0;

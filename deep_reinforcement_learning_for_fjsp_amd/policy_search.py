@@ -32,6 +32,9 @@ slowly.
   reassignments and adjacent swaps, or drawn from the neighbourhood of the plan's critical path (schedule.critical,
   fjsp_schedule_critical).  A MO_DFJSP batch is decoded with its breakdown windows and energy (schedule.decode_dyn,
   fjsp_schedule_decode_dyn): "energy" is an objective there, and the moves are the uniform ones.
+- left_shift: the active schedule of a plan -- every operation in the earliest idle interval of its machine that is long
+  enough (schedule.decode_active, fjsp_schedule_decode_active) -- handed back as a begin-ordered plan that every search here
+  takes; for one plan per env or a whole population.
 - local_search: improve's search, descent or tabu, as one launch for all its rounds (schedule.search, fjsp_schedule_search;
   on a MO_DFJSP batch schedule.search_dyn, fjsp_schedule_search_dyn: uniform neighbourhood, "energy" an objective):
   a wavefront per env, a lane per neighbour, the plan in LDS, on a counter-based draw stream that shards reproduce.
@@ -739,6 +742,40 @@ def local_search(batch, plan, rounds, neighbours=64, objective="makespan", seed=
     if trace:
         out["trace"] = res["trace"]
     return out
+
+
+def left_shift(batch, plan):
+    """The active schedules of explicit plans, as plans every other entry takes: schedule.decode_active
+    (fjsp_schedule_decode_active: each operation goes into the earliest idle interval of its machine that is long enough and
+    begins no earlier than its job is ready), then schedule.begin_order of its tables.
+
+    plan: int32[N, cap, 3] or [N, K, cap, 3] (for instance genetic_search's population), every plan must decode.
+    Returns dict(plan=int32 of plan's shape, the begin-ordered plan of the active table; table=int32[..., cap, 6] in begin
+    order; objective=int64[..., 2] of it; inserted=int32[...] the rows that went into a gap; before=int64[..., 2], what
+    schedule.decode makes of the input plan), device tensors.  No entry of objective exceeds before's: every row ends no
+    later than in the semi-active decode of the same plan.
+    The returned plan decodes through schedule.decode to exactly `table` and `objective`.  Closure: sorting stably by begin
+    keeps every job's and every machine's sequence of the active table, because begin increases strictly along both (p >
+    0); the semi-active decode of that plan gives every row max(end of its job predecessor or its arrival, end of its
+    machine predecessor), which is at most its active begin (induction over the rows), and no less: the machine is idle
+    from that time to the row's active begin in the finished table, so it was when the row was placed, and the row, ready
+    by then, would have started there.  So improve, local_search, front_search, seed_population and
+    genetic_search can start from a left-shifted plan without knowing this function.
+    ValueError for a plan of another shape or one that does not decode; FjspError where the library refuses (MO_DFJSP)."""
+    from . import schedule as sch
+    b, _ = _unwrap(batch, None)
+    if not torch.is_tensor(plan):
+        plan = torch.as_tensor(np.asarray(plan))
+    if plan.dim() not in (3, 4):
+        raise ValueError("plan must be [N, cap, 3] or [N, K, cap, 3], got %s" % (tuple(plan.shape),))
+    K = 1 if plan.dim() == 3 else int(plan.shape[1])
+    act = sch.decode_active(b, plan, None, K, want_table=True)
+    if bool((act["status"] != 0).any()):
+        raise ValueError("left_shift: a plan does not decode (status %s)" % sorted(set(act["status"].flatten().tolist()) - {0}))
+    before = sch.decode(b, plan, None, K)["objective"]
+    new_plan, table = sch.begin_order(act["table"])
+    out = dict(plan=new_plan.contiguous(), table=table, objective=act["objective"], inserted=act["inserted"], before=before)
+    return {k: v[:, 0] for k, v in out.items()} if plan.dim() == 3 else out
 
 
 def merge_fronts(front_obj, held, n_inst):

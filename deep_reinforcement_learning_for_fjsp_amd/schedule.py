@@ -12,6 +12,7 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     plan_of(table)                              the (r, n, m) columns of a table: the explicit schedule it records
     decode(batch, plan, moves, n_cand)          times and objectives of explicit schedules, on the device
     decode_dyn(batch, plan, moves, n_cand)      the same on MO_DFJSP: breakdown shifts, and energy as a third objective
+    decode_active(batch, plan, moves, n_cand)   decode with insertion into machine gaps (active schedules), and the rows inserted
     apply_moves(plan, moves)                    the plans that decode's moves stand for, materialised
     pair_move(u, v, w)                          the MOVE_PAIR that puts rows u and v, v first, behind row w
     critical(batch, table, n_cand, max_moves)   tails, critical flags, one critical path and its moves, on the device
@@ -318,6 +319,18 @@ def decode_dyn(batch, plan, moves=None, n_cand=1, want_table=False):
     return _decode(batch, plan, moves, n_cand, want_table, "fjsp_schedule_decode_dyn", 3)
 
 
+def decode_active(batch, plan, moves=None, n_cand=1, want_table=False):
+    """decode with insertion into machine gaps (fjsp_schedule_decode_active), the active decoder of the FJSP literature:
+    the same arguments, checks, moves, status codes and results, but a row starts in the earliest idle interval of its
+    machine that is long enough and begins no earlier than its job is ready, not behind everything the machine holds.  No
+    row ends later than in decode's table of the same plan.  The table's rows stand at their plan positions, so it is not in
+    begin order: begin_order(table) gives the plan that decode decodes to the same schedule.
+    Returns decode's dict and inserted=int32[N, n_cand], the rows placed in front of an interval already on their machine
+    (0 for a failed candidate; where it is 0 the table is decode's).  The calls on one batch share a device workspace:
+    issue them on one stream.  FjspError on MO_DFJSP (an insertion under breakdown shifts is not defined)."""
+    return _decode(batch, plan, moves, n_cand, want_table, "fjsp_schedule_decode_active", 2)
+
+
 def _decode(batch, plan, moves, n_cand, want_table, entry, n_obj):
     import torch
     from ._capi import check, ptr
@@ -345,8 +358,13 @@ def _decode(batch, plan, moves, n_cand, want_table, entry, n_obj):
     status = torch.empty(b.N, n_cand, dtype=torch.int32, device=b.device)
     length = torch.empty(b.N, n_cand, dtype=torch.int32, device=b.device)
     table = torch.empty(b.N, n_cand, cap, 6, dtype=torch.int32, device=b.device) if want_table else None
-    check(getattr(b._lib, entry)(b._h, ptr(plan), q_plans, ptr(moves), n_cand, ptr(objective), ptr(status), ptr(table), ptr(length), b._stream()))
-    return dict(objective=objective, status=status, table=table, length=length)
+    out = dict(objective=objective, status=status, table=table, length=length)
+    more = ()
+    if entry == "fjsp_schedule_decode_active":
+        out["inserted"] = torch.empty(b.N, n_cand, dtype=torch.int32, device=b.device)
+        more = (ptr(out["inserted"]),)
+    check(getattr(b._lib, entry)(b._h, ptr(plan), q_plans, ptr(moves), n_cand, ptr(objective), ptr(status), ptr(table), ptr(length), *more, b._stream()))
+    return out
 
 
 CRITICAL_OK, CRITICAL_BAD_ROW, CRITICAL_EMPTY = range(3)

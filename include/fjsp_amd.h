@@ -771,6 +771,49 @@ int fjsp_schedule_decode(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, co
 int fjsp_schedule_decode_capacity(const fjsp_env *e);
 int fjsp_schedule_decode_group(const fjsp_env *e);
 
+/* Explicit schedules decoded ACTIVELY on the device (schedule.decode_active, policy_search.left_shift;
+ * csrc/fjsp_decode.hip): fjsp_schedule_decode with insertion into machine gaps, the decoder the FJSP literature uses for
+ * operation-sequence chromosomes.  Everything not said here is fjsp_schedule_decode's, unchanged: the plans, q_plans and
+ * the moves (kinds 0, 1, 2, 4) applied while the plan is read; the status codes 0 to 4 and their precedence; a failed
+ * candidate (objective -1, length 0, a table of -1, the others unaffected); d_objective i64[N][n_cand][2]; d_table rows
+ * written AT THEIR PLAN POSITION t (not in begin order), -1 past d_len; the limit on a candidate's state and the group
+ * size; FJSP_E_ARG and FJSP_E_STATE; stream order, no host synchronisation, no atomics.
+ *
+ * Decoding.  Jobs are ready at their order's arrival.  Every machine has an empty list of busy intervals, kept in
+ * ascending begin order.  For plan row (r, n, m), with stage the job's next stage and k its operation type, d = p[k][m]
+ * and s = ready[job]; machine m's intervals (b, e) are walked from the first:
+ *     s + d <= b    the row takes [s, s + d) in front of that interval (touching is allowed) and the walk stops;
+ *     else          s = max(s, e) and the walk goes on;
+ * past the last interval the row takes [s, s + d).  Then ready[job] = s + d; makespan and tardiness as
+ * fjsp_schedule_decode.  32-bit integers, exact.  Every row ends no later than in fjsp_schedule_decode's table of the same
+ * plan (induction over the rows: appending behind the machine's latest interval is always available, and that interval
+ * ends at or before the semi-active free[m]), so no clock exceeds its semi-active value and the bound of fjsp_env_create
+ * that keeps those below 2^31 covers this entry.
+ * The result is an active schedule.  Sorting the table's rows stably by begin (schedule.begin_order) gives a plan that
+ * fjsp_schedule_decode decodes to the same table row for row, and that this entry decodes to it with nothing inserted.
+ *
+ * d_inserted (nullable) i32[N][n_cand]: the rows placed in front of at least one interval already on their machine; 0
+ * for a failed candidate.  Where it is 0 the table is fjsp_schedule_decode's.
+ *
+ * One path for every plan size: a candidate's intervals live in a device workspace that the handle owns, 8 bytes per plan
+ * row (begin, duration | predecessor on the machine), allocated by the handle's first call and never cleared -- a
+ * candidate reads only entries it wrote itself.  The grid is bounded: groups = min(FJSP_DECODE_ACTIVE_MAX_GROUPS, max(1,
+ * FJSP_DECODE_ACTIVE_WORKSPACE_BYTES / (8 cap G))) workgroups of G = fjsp_schedule_decode_group candidates loop over the
+ * call's ceil(N n_cand / G) groups, so groups x G candidates are resident at once (fjsp_schedule_decode_active_resident)
+ * and the workspace is 8 cap G groups bytes (cap = fjsp_schedule_decode_capacity) whatever N and n_cand are; entry i of
+ * the candidates of a workgroup are G consecutive 8-byte words.  ORDERING: the calls on one handle share the workspace,
+ * so they must be ordered on one stream (or by events); calls on different handles are independent.
+ * fjsp_schedule_decode_active_group: G, 0 where fjsp_schedule_decode_group is 0.
+ * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP (an insertion under breakdown shifts is not defined by the reference), a
+ * state beyond fjsp_schedule_decode's limit.  FJSP_E_HIP: the workspace could not be allocated. */
+#define FJSP_DECODE_ACTIVE_WORKSPACE_BYTES (128 * 1024 * 1024)
+#define FJSP_DECODE_ACTIVE_MAX_GROUPS 512
+int fjsp_schedule_decode_active(fjsp_env *e, const int32_t *d_plan, int32_t q_plans, const int32_t *d_moves, int32_t n_cand,
+                                int64_t *d_objective, int32_t *d_status, int32_t *d_table, int32_t *d_len, int32_t *d_inserted,
+                                void *stream);
+int fjsp_schedule_decode_active_group(const fjsp_env *e);
+int fjsp_schedule_decode_active_resident(const fjsp_env *e);
+
 /* Explicit schedules of MO_DFJSP decoded on the device (schedule.decode_dyn, policy_search.improve on such a batch;
  * csrc/fjsp_decode.hip): fjsp_schedule_decode with the machines' breakdown windows and the third objective, energy.
  * Arguments, plans, moves, the checks, the status codes 0 to 4, d_table, d_len and the handling of a failed candidate are
