@@ -191,6 +191,8 @@ SIGNATURES = {
     "fjsp_schedule_search_front_lds": (C.c_int, [_vp, _i32]),
     "fjsp_schedule_evolve": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fjsp_schedule_evolve_lds": (C.c_int, [_vp]),
+    "fjsp_schedule_evolve_active": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fjsp_schedule_evolve_active_resident": (C.c_int, [_vp]),
     "fjsp_search_draws": (C.c_int, [_u64, _i64, C.c_uint32, _i32, C.POINTER(C.c_uint64)]),
     "fjsp_policy_pair_sample": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
 }

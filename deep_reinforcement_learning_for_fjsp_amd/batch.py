@@ -725,6 +725,17 @@ class EnvBatch(object):
         family); 0: an env's working set exceeds a CU's LDS."""
         return int(self._lib.fjsp_schedule_evolve_lds(self._h))
 
+    def evolve_active_resident(self):
+        """Envs of an evolve_active call that are resident at once (fjsp_schedule_evolve_active_resident):
+        decode_active_resident() // 64, the workgroups of its bounded grid; 0 on MO_DFJSP."""
+        return int(self._lib.fjsp_schedule_evolve_active_resident(self._h))
+
+    def evolve_active(self, pop_plans, generations, weights=None, mut_rate=6554, seed=0, trace=False):
+        """schedule.evolve_active on this batch's instances: the genetic algorithm of schedule.evolve with every individual
+        scored by the active decoder -> evolve's dict and the rows each individual of the last generation inserted."""
+        from . import schedule
+        return schedule.evolve_active(self, pop_plans, generations, weights, mut_rate, seed, trace)
+
     def set_lp_threads(self, n_threads):
         """Host threads of the order-arrival LP service (0 = all cores).  The asynchronous service builds its worker pool
         at the first step_async and reads this once, there: call it before that."""

@@ -49,6 +49,9 @@
 // fjsp_schedule_search_front is the same text once more, for both families (schedule_search_kernel<DYN, FrontArgs>): the
 // uniform neighbourhood, the selection by a weighted sum of the objectives, and per env the Pareto archive of every vector
 // the search decodes, kept in LDS by the wave (ballots and prefix counts; no atomics).
+//
+// fjsp_schedule_evolve is a genetic algorithm on those decodes (its head comment is at EvolveArgs); fjsp_schedule_evolve_active
+// is its text with Gaps in every decode, on decode_active's workspace and bounded grid (schedule_evolve_active_kernel).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -954,161 +957,55 @@ struct EvolveArgs {
 __host__ __device__ inline int evolve_set_words(int JW) { return (JW + 31) / 32; }
 __host__ __device__ inline size_t evolve_words(int states, int JW) { return (size_t)(states + evolve_set_words(JW)) * 64 + 2 * 64 * 2; }
 
+// The lane's placement policy in the text of an env (fjsp_evolve_env.inc): none, or a Gaps object on slot q of the
+// workgroup's part of the workspace, whose count is one decode's
+template <bool ACTIVE> __device__ __forceinline__ auto evolve_gaps(uint2 *ws, int q) {
+    if constexpr (ACTIVE) return Gaps{ws + q, 64, 0};
+    else return NoGaps{};
+}
+__device__ __forceinline__ Gaps *evolve_gaps_ptr(Gaps &g) { return &g; }
+__device__ __forceinline__ NoGaps *evolve_gaps_ptr(NoGaps &) { return nullptr; }
+__device__ __forceinline__ void evolve_gaps_reset(Gaps *g) { g->inserted = 0; }
+__device__ __forceinline__ void evolve_gaps_reset(NoGaps *) {}
+__device__ __forceinline__ int evolve_gaps_count(const Gaps *g) { return g->inserted; }
+__device__ __forceinline__ int evolve_gaps_count(const NoGaps *) { return 0; }
+
+// The text of one env is fjsp_evolve_env.inc, included by both kernels: it stands IN the kernel, because as a device
+// function that both call (by reference or by value, the env passed or read from blockIdx) schedule_evolve_kernel<false>
+// and <true> no longer compiled to the instructions they had (tools/isa_compare.py).  It reads DYN, ACTIVE, b, a, env,
+// ws (the workgroup's part of the workspace), ins (nullable: the counts) and leaves an env by FJSP_EVOLVE_DONE.
 template <bool DYN>
 __global__ __launch_bounds__(64) void schedule_evolve_kernel(DevBatch b, EvolveArgs a) {
-    constexpr int NO = DYN ? 3 : 2;
-    constexpr long long kNone = 0x7fffffffffffffffLL;                    // the key of a lane without an individual, or of a child that failed
-    const int q = (int)threadIdx.x, env = (int)blockIdx.x, inst = env % b.n_inst;
-    const int cap = a.cap, P = a.P, N = b.N, T = a.generations;
-    const Shop sh = shop_of(b, a.kinds, inst, a.JW);
-    const State st = state_at(decode_lds, q, 64, a.JW);
-    DynShop dy{};
-    if constexpr (DYN) dy = dyn_shop_of(b, sh, st, dyn_windows(b));
-    const int SW = DYN ? dyn_state_words(a.JW, b.MP) : state_words(a.JW, b.MP), JS = evolve_set_words(a.JW);
-    uint32_t *jset = decode_lds + (size_t)SW * 64 + q;                   // word w of this lane's set at jset[w * 64]
-    long long *keys = reinterpret_cast<long long *>(decode_lds + (size_t)(SW + JS) * 64);     // [2][64]
-    const size_t PW = (size_t)cap * 3, base = (size_t)env * P * PW;      // words of a plan; the env's first word in a population
+    constexpr bool ACTIVE = false;
+    const int env = (int)blockIdx.x;
+    uint2 *const ws = nullptr;
+    int32_t *const ins = nullptr;
+#define FJSP_EVOLVE_DONE return
+#include "fjsp_evolve_env.inc"
+#undef FJSP_EVOLVE_DONE
+}
 
-    const long long *w = reinterpret_cast<const long long *>(a.weights) + NO * (size_t)env;
-    const long long w0 = w[0], w1 = w[1], w2 = DYN ? w[2] : 0;
-    const bool bad_w = w0 < 0 || w1 < 0 || w2 < 0 || (w0 | w1 | w2) == 0;
-    auto chosen = [&](long long mk, long long td, long long en) { return key_add(key_add(key_mul(w0, mk), key_mul(w1, td)), DYN ? key_mul(w2, en) : 0LL); };
-    // the least (key, index) of the wave, the same in every lane
-    auto least = [&](long long key, long long &bkey, int &bq) {
-        bkey = key; bq = q;
-        for (int off = 32; off > 0; off >>= 1) {
-            const long long ok2 = __shfl_xor(bkey, off);
-            const int oq = __shfl_xor(bq, off);
-            if (ok2 < bkey || (ok2 == bkey && oq < bq)) { bkey = ok2; bq = oq; }
-        }
-    };
-
-    // ---- generation 0: every individual of pop decoded by its lane
-    int L = 0, st0 = 0;
-    long long mk = 0, td = 0, en = 0, key = kNone;
-    if (q < P && !bad_w) {
-        const int32_t *pl = a.pop + base + (size_t)q * PW;
-        st0 = decode_plan<DYN>(b, sh, st, [&](int idx) { return row_at(pl, idx); }, cap, no_move(), [](int, const Row &, const Step &) {}, L, mk, td, &dy, &en);
-        if (st0 == 0) key = chosen(mk, td, en);
+// fjsp_schedule_evolve_active: a bounded grid, as schedule_decode_active_kernel's.  Workgroup w evolves the envs w, w +
+// gridDim.x, ... one after the other, every lane's intervals in its slot of the workgroup's own cap x 64 entries of the
+// workspace (the index is the workgroup's, not the env's; an entry is read only behind a tail word that the same decode
+// reset, so nothing an earlier env, call or entry left there is looked at).
+//   What one env leaves in LDS for the next: a lane's state words and its job set are read and written by that lane alone
+//   (state_at and jset are indexed by q), so program order covers them.  The two key rows are the only words a lane reads
+//   that another wrote: generation t reads row (t - 1) & 1 and is closed by the generation's barrier; behind the last of
+//   them (T = 0: behind the barrier that follows keys[q]) no lane reads a key again -- the final least() runs on
+//   registers -- and every lane still passes the barrier in front of the best_plan copy before it goes on.  So the first
+//   write of the next env to a key row comes after two barriers that every lane passed after its last read.  An env with
+//   a status is left before it has written or read a key, and its predecessor's reads ended as said; it passes no
+//   barrier, which is sound because the status is the same in every lane and no lane waits at one.  In global memory
+//   an env touches only its own rows of every array.
+__global__ __launch_bounds__(64) void schedule_evolve_active_kernel(DevBatch b, EvolveArgs a, uint2 *d_ws, int32_t *ins) {
+    constexpr bool DYN = false, ACTIVE = true;
+    uint2 *const ws = d_ws + (size_t)blockIdx.x * (size_t)a.cap * 64;
+    for (int env = (int)blockIdx.x; env < b.N; env += (int)gridDim.x) {
+#define FJSP_EVOLVE_DONE continue
+#include "fjsp_evolve_env.inc"
+#undef FJSP_EVOLVE_DONE
     }
-    const unsigned long long failed = __ballot(st0 != 0);
-    const int status = bad_w ? 5 : (failed ? __shfl(st0, __ffsll(failed) - 1) : 0);
-    if (status != 0) {                                                   // (the same in every lane) the env is copied through
-        for (size_t i = q; i < (size_t)P * PW; i += 64) a.pop_out[base + i] = a.pop[base + i];
-        for (size_t i = q; i < PW; i += 64) a.best_plan[(size_t)env * PW + i] = a.pop[base + i];
-        if (q < P)
-            for (int c = 0; c < NO; ++c) a.pop_obj[((size_t)env * P + q) * NO + c] = -1;
-        if (q == 0) {
-            a.status[env] = status;
-            for (int c = 0; c < NO; ++c) a.objective[NO * (size_t)env + c] = -1;
-        }
-        for (int t = q; t <= T; t += 64) a.history[(size_t)t * N + env] = -1;
-        if (a.trace)
-            for (int t = 0; t < T; ++t)
-                for (int i = q; i < P * 3; i += 64) a.trace[((size_t)t * N + env) * (size_t)P * 3 + i] = 0;
-        return;
-    }
-    if (T == 0) {                                                        // the outputs describe the input population: the wave copies it
-        for (int p = 0; p < P; ++p) {
-            const int Lp = __shfl(L, p);
-            const int32_t *pl = a.pop + base + (size_t)p * PW;
-            int32_t *o = a.pop_out + base + (size_t)p * PW;
-            for (int i = q; i < cap * 3; i += 64) o[i] = i < Lp * 3 ? pl[i] : -1;
-        }
-    }
-    keys[q] = key;
-    __syncthreads();
-
-    const uint64_t sg = gen::draw(a.seed, (uint32_t)(a.first_env + env));
-    const int32_t *src = a.pop + base;
-    for (int t = 1; t <= T; ++t) {
-        long long bkey;
-        int bq;
-        least(key, bkey, bq);
-        if (q == 0) a.history[(size_t)(t - 1) * N + env] = bkey;
-        int32_t *dst = (((T - t) & 1) ? a.work : a.pop_out) + base;      // the last generation lands in pop_out
-        const long long *kprev = keys + ((t - 1) & 1) * 64;
-        if (q < P) {
-            const uint64_t c = gen::draw(sg, (uint32_t)(t - 1) * (uint32_t)P + (uint32_t)q);
-            int pa = bq, pb = bq, mrow = -1;
-            const bool elite = q == 0;                                   // both parents the best individual, every job from A, no mutation
-            if (!elite) {
-                auto tournament = [&](uint32_t i) {
-                    const int x = (int)search_pick(gen::draw(c, i), (uint32_t)P), y = (int)search_pick(gen::draw(c, i + 1u), (uint32_t)P);
-                    const long long kx = kprev[x], ky = kprev[y];
-                    return (ky < kx || (ky == kx && y < x)) ? y : x;
-                };
-                pa = tournament(0u); pb = tournament(2u);
-                for (int i = 0; i < JS; ++i) jset[(size_t)i * 64] = (uint32_t)(gen::draw(c, 8u + (uint32_t)(i >> 1)) >> (32 * (i & 1)));
-                if ((int)search_pick(gen::draw(c, 4u), 65536u) < a.mut_rate && sh.ops > 0) mrow = (int)search_pick(gen::draw(c, 5u), (uint32_t)sh.ops);
-            }
-            const int32_t *A = src + (size_t)pa * PW, *B = src + (size_t)pb * PW;
-            int32_t *ch = dst + (size_t)q * PW;
-            // is the row's job in J1?  (a row whose kind or job number is out of range is in no set; the decode refuses it)
-            auto in_set = [&](const Row &x) {
-                if (elite) return true;
-                if (x.r < 0 || x.r >= sh.R) return false;
-                const uint32_t ka = sh.kinds[1 + x.r].x;
-                const int j = (int)(ka & 0xFFFFu) + x.n;
-                if (x.n < 0 || x.n >= (int)(ka >> 16) || j >= sh.JW) return false;
-                return ((jset[(size_t)(j >> 5) * 64] >> (j & 31)) & 1u) != 0u;
-            };
-            // The child's rows: decode_plan asks for rows 0, 1, 2 ... in this order, each once, when the move is none (or of kind
-            // 1), so B's cursor lives here and only moves forward.  It stays below cap; where it runs out the child ends.
-            int cur = 0;
-            auto row = [&](int idx) {
-                const Row x = row_at(A, idx);
-                if (is_end(x) || in_set(x)) return x;
-                while (cur < cap) {
-                    const Row y = row_at(B, cur++);
-                    if (is_end(y)) break;
-                    if (!in_set(y)) return y;
-                }
-                return Row{-1, -1, -1};
-            };
-            // the mutation: row mrow runs on the pick(d6, n_e)-th of the n_e eligible machines of its operation, ascending
-            auto fix = [&](int i, Row &x, int k) {
-                if (i != mrow) return;
-                const uint16_t *pk = sh.p + (size_t)k * sh.MP;
-                int n_e = 0;
-                for (int m = 0; m < sh.M; ++m) n_e += pk[m] != 0 ? 1 : 0;
-                if (n_e == 0) return;
-                int left = (int)search_pick(gen::draw(c, 6u), (uint32_t)n_e);
-                for (int m = 0; m < sh.M; ++m)
-                    if (pk[m] != 0 && left-- == 0) { x.m = m; break; }
-            };
-            const int err = decode_plan<DYN>(b, sh, st, row, cap, no_move(), [&](int i, const Row &x, const Step &) {
-                ch[3 * i] = x.r; ch[3 * i + 1] = x.n; ch[3 * i + 2] = x.m;
-            }, L, mk, td, &dy, &en, fix);
-            key = err ? kNone : chosen(mk, td, en);                      // a child that failed loses every comparison; its plan is empty
-            for (int i = err ? 0 : L; i < cap; ++i) { ch[3 * i] = -1; ch[3 * i + 1] = -1; ch[3 * i + 2] = -1; }
-            if (a.trace) {
-                int32_t *o = a.trace + (((size_t)(t - 1) * N + env) * (size_t)P + q) * 3;
-                o[0] = pa; o[1] = pb; o[2] = mrow;
-            }
-        }
-        keys[(t & 1) * 64 + q] = key;
-        __syncthreads();                                                 // the children and their keys are handed on
-        src = dst;
-    }
-
-    long long bkey;
-    int bq;
-    least(key, bkey, bq);
-    const long long b_mk = __shfl(mk, bq), b_td = __shfl(td, bq), b_en = __shfl(en, bq);
-    if (q == 0) {
-        a.history[(size_t)T * N + env] = bkey;
-        a.status[env] = 0;
-        a.objective[NO * (size_t)env] = b_mk; a.objective[NO * (size_t)env + 1] = b_td;
-        if constexpr (DYN) a.objective[NO * (size_t)env + 2] = b_en;
-    }
-    if (q < P) {
-        int64_t *o = a.pop_obj + ((size_t)env * P + q) * NO;
-        o[0] = mk; o[1] = td;
-        if constexpr (DYN) o[2] = en;
-    }
-    __syncthreads();                                                     // (T = 0: the rows above)
-    for (size_t i = q; i < PW; i += 64) a.best_plan[(size_t)env * PW + i] = a.pop_out[base + (size_t)bq * PW + i];
 }
 
 // candidates per workgroup, 0 = the state of 32 candidates does not fit the LDS of a CU
@@ -1417,11 +1314,14 @@ extern "C" int fjsp_schedule_evolve_lds(const fjsp_env *e) {
     return bytes <= kLdsCu ? (int)bytes : 0;
 }
 
-extern "C" int fjsp_schedule_evolve(fjsp_env *e, const int32_t *d_pop, int32_t pop, int32_t generations, const int64_t *d_weights,
-                                    int32_t mut_rate, uint64_t seed, int64_t first_env, int32_t *d_pop_out, int32_t *d_work,
-                                    int64_t *d_pop_obj, int32_t *d_best_plan, int64_t *d_objective, int64_t *d_history, int32_t *d_status,
-                                    int32_t *d_trace, void *stream) {
-    const std::string fn = "fjsp_schedule_evolve";
+extern "C" int fjsp_schedule_evolve_active_resident(const fjsp_env *e) { return fjsp_schedule_decode_active_resident(e) / 64; }
+
+// fjsp_schedule_evolve (active false) and fjsp_schedule_evolve_active: one set of checks, in one order
+static int schedule_evolve(bool active, fjsp_env *e, const int32_t *d_pop, int32_t pop, int32_t generations, const int64_t *d_weights,
+                           int32_t mut_rate, uint64_t seed, int64_t first_env, int32_t *d_pop_out, int32_t *d_work, int64_t *d_pop_obj,
+                           int32_t *d_best_plan, int64_t *d_objective, int64_t *d_history, int32_t *d_status, int32_t *d_trace,
+                           int32_t *d_pop_inserted, void *stream) {
+    const std::string fn = active ? "fjsp_schedule_evolve_active" : "fjsp_schedule_evolve";
     if (!e || !d_pop || !d_weights || !d_pop_out || !d_work || !d_pop_obj || !d_best_plan || !d_objective || !d_history || !d_status) {
         set_error(fn + ": null env, population, weights or output pointer"); return FJSP_E_ARG;
     }
@@ -1435,6 +1335,10 @@ extern "C" int fjsp_schedule_evolve(fjsp_env *e, const int32_t *d_pop, int32_t p
     const DevBatch &b = e->b;
     if (e->ops_max <= 0) { set_error(fn + ": no operations"); return FJSP_E_ARG; }
     const bool dyn = b.variant == FJSP_VARIANT_MO_DFJSP;
+    if (active && dyn) {
+        set_error(fn + ": MO_DFJSP batches are not decoded here (an insertion under breakdown shifts is not defined): fjsp_schedule_evolve evolves them");
+        return FJSP_E_UNSUPPORTED;
+    }
     const size_t lds = evolve_bytes(e);
     if (lds > kLdsCu) {
         set_error(fn + ": an env's working set (64 individuals' states of " + std::to_string((dyn ? dyn_state_words(b.jcap, b.MP) : state_words(b.jcap, b.MP)) * 4) +
@@ -1442,16 +1346,45 @@ extern "C" int fjsp_schedule_evolve(fjsp_env *e, const int32_t *d_pop, int32_t p
                   std::to_string(kLdsCu) + " bytes of a CU's LDS");
         return FJSP_E_UNSUPPORTED;
     }
+    // (a working set within the limit has decode_group >= 64, so at least one env is resident)
+    const int resident = active ? fjsp_schedule_evolve_active_resident(e) : 0;
+    if (active && resident < 1) { set_error(fn + ": the workspace of fjsp_schedule_decode_active holds no env of 64 individuals"); return FJSP_E_UNSUPPORTED; }
     DeviceGuard guard(e->device);
     if (!e->d_decode_kinds && !dev_alloc(e, (size_t)b.n_inst * (size_t)(b.KP + 1) * sizeof(uint2), &e->d_decode_kinds, "hipMalloc (decode kind table)")) return FJSP_E_HIP;
+    if (active && !e->d_active_ws) {                                     // decode_active's workspace, at decode_active's size
+        const int G = decode_group(b);
+        if (!dev_alloc(e, (size_t)active_groups(e, G) * (size_t)e->ops_max * (size_t)G * sizeof(uint2), &e->d_active_ws, "hipMalloc (active decode workspace)")) return FJSP_E_HIP;
+    }
     hipStream_t st = (hipStream_t)stream;
     if (launch(decode_kinds_kernel, dim3((unsigned)((b.n_inst + 63) / 64)), dim3(64), 0, st, b, e->d_decode_kinds) != 0) {
         set_error("decode_kinds_kernel launch failed"); return FJSP_E_HIP;
     }
     const EvolveArgs a{d_pop, d_pop_out, d_work, d_weights, d_pop_obj, d_best_plan, d_objective, d_history, d_status, d_trace, e->d_decode_kinds,
                        seed ^ FJSP_EVOLVE_STREAM, (long long)first_env, (int)pop, (int)generations, (int)mut_rate, e->ops_max, b.jcap};
+    if (active) {
+        if (launch(schedule_evolve_active_kernel, dim3((unsigned)(b.N < resident ? b.N : resident)), dim3(64), lds, st, b, a, e->d_active_ws, d_pop_inserted) != 0) {
+            set_error("schedule_evolve_active_kernel launch failed"); return FJSP_E_HIP;
+        }
+        return FJSP_OK;
+    }
     const int rc = dyn ? launch(schedule_evolve_kernel<true>, dim3((unsigned)b.N), dim3(64), lds, st, b, a)
                        : launch(schedule_evolve_kernel<false>, dim3((unsigned)b.N), dim3(64), lds, st, b, a);
     if (rc != 0) { set_error(std::string(dyn ? "schedule_evolve_kernel<true>" : "schedule_evolve_kernel<false>") + " launch failed"); return FJSP_E_HIP; }
     return FJSP_OK;
+}
+
+extern "C" int fjsp_schedule_evolve(fjsp_env *e, const int32_t *d_pop, int32_t pop, int32_t generations, const int64_t *d_weights,
+                                    int32_t mut_rate, uint64_t seed, int64_t first_env, int32_t *d_pop_out, int32_t *d_work,
+                                    int64_t *d_pop_obj, int32_t *d_best_plan, int64_t *d_objective, int64_t *d_history, int32_t *d_status,
+                                    int32_t *d_trace, void *stream) {
+    return schedule_evolve(false, e, d_pop, pop, generations, d_weights, mut_rate, seed, first_env, d_pop_out, d_work, d_pop_obj, d_best_plan,
+                           d_objective, d_history, d_status, d_trace, nullptr, stream);
+}
+
+extern "C" int fjsp_schedule_evolve_active(fjsp_env *e, const int32_t *d_pop, int32_t pop, int32_t generations, const int64_t *d_weights,
+                                           int32_t mut_rate, uint64_t seed, int64_t first_env, int32_t *d_pop_out, int32_t *d_work,
+                                           int64_t *d_pop_obj, int32_t *d_best_plan, int64_t *d_objective, int64_t *d_history,
+                                           int32_t *d_status, int32_t *d_trace, int32_t *d_pop_inserted, void *stream) {
+    return schedule_evolve(true, e, d_pop, pop, generations, d_weights, mut_rate, seed, first_env, d_pop_out, d_work, d_pop_obj, d_best_plan,
+                           d_objective, d_history, d_status, d_trace, d_pop_inserted, stream);
 }

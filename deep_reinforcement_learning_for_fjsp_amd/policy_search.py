@@ -43,7 +43,8 @@ slowly.
   merge=True the front per instance over its envs' archives (pareto.select).
 - seed_population, genetic_search: a population search on the same plans -- the GA baseline of the FJSP literature -- with all
   its generations in one launch (schedule.evolve, fjsp_schedule_evolve): a lane per individual, which decodes its child
-  while it merges it from two parents; seeded from recorded or sampled schedules.
+  while it merges it from two parents; seeded from recorded or sampled schedules.  decoder="active" scores every
+  individual with left_shift's decoder inside the same launch (schedule.evolve_active, fjsp_schedule_evolve_active).
 
 Every function takes an EnvBatch or a Batched* wrapper (whose `mo` is used when none is given).  The source's state rows
 must hold its envs' current states, as reset() and step() / rollout() with a state leave them: the actor reads them.
@@ -905,7 +906,8 @@ def seed_population(batch, plan, population, shake=4, seed=0):
     return rows[..., :3].reshape(N, P, cap, 3).contiguous()
 
 
-def genetic_search(batch, population, generations, objective="makespan", weights=None, mutation=0.1, seed=0, merge=False):
+def genetic_search(batch, population, generations, objective="makespan", weights=None, mutation=0.1, seed=0, merge=False,
+                   decoder="semi_active"):
     """A genetic algorithm on explicit schedules, every generation of every env in ONE launch (schedule.evolve,
     fjsp_schedule_evolve, csrc/fjsp_decode.hip): a wavefront owns an env, a lane an individual.  Per generation child 0 is
     the best individual unchanged (the elite); every other child draws two parents by binary tournaments, takes the rows of
@@ -924,11 +926,22 @@ def genetic_search(batch, population, generations, objective="makespan", weights
     and population_objective=int64[N, P, NO] the last generation, status=int32[N] (zeros)) and with merge=True, per instance,
     merged_front f64[n_inst, C, NO] (NaN past the front) and merged_count int32[n_inst]: the front (pareto.select) of the
     last generations of all envs i with i % n_inst the instance, C = envs of an instance x P, which must not exceed 1024.
-    ValueError for an unknown objective, generations < 0, mutation outside 0..1, a population or weights of another shape,
-    bad weights, a plan that does not decode, and with merge C > 1024 or an objective >= 2^53; FjspError where the library
-    refuses (EnvBatch.evolve_lds)."""
+    decoder: "semi_active" scores every individual with schedule.decode (decode_dyn on MO_DFJSP): a row starts behind
+    everything its machine holds.  "active" scores it with schedule.decode_active, the decoder of the FJSP literature: a
+    row takes the earliest idle interval of its machine that fits (schedule.evolve_active, fjsp_schedule_evolve_active, the
+    same one launch).  The chromosomes are not rewritten: plan and population hold the rows as the crossover merged them,
+    objective, population_objective and history are their ACTIVE objectives, and the dict gains inserted=int32[N, P] (the rows
+    each individual of the last generation placed in a gap) and active_plan=int32[N, cap, 3], table=int32[N, cap, 6]: the
+    left_shift of `plan`, in begin order, which schedule.decode decodes to `objective` -- the form the other searches take.
+    RuntimeError if left_shift's objective is not `objective` (the two entries disagree).
+
+    ValueError for an unknown objective or decoder, generations < 0, mutation outside 0..1, a population or weights of
+    another shape, bad weights, a plan that does not decode, and with merge C > 1024 or an objective >= 2^53; FjspError
+    where the library refuses (EnvBatch.evolve_lds; decoder="active" on MO_DFJSP)."""
     from . import schedule as sch
     b, _ = _unwrap(batch, None)
+    if decoder not in ("semi_active", "active"):
+        raise ValueError("decoder must be \"semi_active\" or \"active\", got %r" % (decoder,))
     objectives = sch.SEARCH_DYN_OBJECTIVES if b.variant == sch.VARIANT_MO_DFJSP else sch.SEARCH_OBJECTIVES
     n_obj = len(objectives)
     if weights is None and objective not in objectives:
@@ -950,11 +963,17 @@ def genetic_search(batch, population, generations, objective="makespan", weights
     n_group = -(-N // b.n_inst)
     if merge and n_group * P > pareto.MAX_CANDIDATES:
         raise ValueError("merge: %d envs of an instance x population %d exceed pareto.select's %d candidates" % (n_group, P, pareto.MAX_CANDIDATES))
-    res = sch.evolve(b, population, generations, w, int(round(mutation * sch.EVOLVE_MUT_ONE)), seed)
+    run = sch.evolve_active if decoder == "active" else sch.evolve
+    res = run(b, population, generations, w, int(round(mutation * sch.EVOLVE_MUT_ONE)), seed)
     if bool((res["status"] != 0).any()):
         raise ValueError("genetic_search: a plan does not decode (status %s)" % sorted(set(res["status"].tolist()) - {0}))
     out = dict(plan=res["plan"], objective=res["objective"], history=res["history"], population=res["population"],
                population_objective=res["population_objective"], status=res["status"])
+    if decoder == "active":
+        shifted = left_shift(b, res["plan"])
+        if not torch.equal(shifted["objective"], res["objective"]):
+            raise RuntimeError("genetic_search: decode_active of the winner does not give evolve_active's objective")
+        out.update(inserted=res["inserted"], active_plan=shifted["plan"], table=shifted["table"])
     if merge:
         held = torch.ones(N, P, dtype=torch.bool, device=dev)
         out["merged_front"], out["merged_count"] = merge_fronts(res["population_objective"], held, b.n_inst)

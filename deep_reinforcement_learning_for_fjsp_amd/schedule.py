@@ -22,6 +22,7 @@ dispatch sets them (SO_FJSSP.py:176-196, shifted by machine breakdowns in MO_DFJ
     search_front(batch, plan, weights, ...)     that search steered by a weighted sum, keeping the Pareto archive of its decodes
     search_draws(seed, env, first, n)           the draw stream of that search, on the host
     evolve(batch, pop_plans, generations, ...)  a genetic algorithm on populations of plans, all generations in one launch
+    evolve_active(batch, pop_plans, ...)        evolve with every individual scored by the active decoder, and the rows inserted
 
 `inst` is anything with the instance arrays of instances.InstanceArrays: Jr[R], p[K][M] (0 = ineligible),
 count[S][R], arrive[S], delivery[S] (and bk_n[M], bk[W][2] for MO_DFJSP breakdown windows).
@@ -520,6 +521,22 @@ def evolve(batch, pop_plans, generations, weights=None, mut_rate=6554, seed=0, t
     N] the least key of every generation, status=int32[N], trace=int32[generations, N, P, 3] (parent A, parent B, mutated row
     or -1) or None), device tensors.  ValueError for a population or weights of another shape; FjspError where the library
     refuses."""
+    return _evolve(batch, pop_plans, generations, weights, mut_rate, seed, trace, "fjsp_schedule_evolve")
+
+
+def evolve_active(batch, pop_plans, generations, weights=None, mut_rate=6554, seed=0, trace=False):
+    """evolve with every individual scored by the active decoder (fjsp_schedule_evolve_active), the genetic algorithm as
+    the FJSP literature scores it: the same arguments, checks, draws and results, but generation 0 and every child are
+    decoded by decode_active's rule, so the keys of the tournaments, population_objective, objective and history are the
+    active objectives.  The plans are not rewritten: population and plan hold the merged rows in merge order, which
+    decode_active decodes to those objectives (policy_search.left_shift gives the begin-ordered plans).
+    Returns evolve's dict and inserted=int32[N, P], the rows each individual of the last generation placed in front of an
+    interval (zeros for an env with a status).  Shares decode_active's device workspace: issue the calls of both on one
+    stream.  FjspError on MO_DFJSP (an insertion under breakdown shifts is not defined) and where evolve refuses."""
+    return _evolve(batch, pop_plans, generations, weights, mut_rate, seed, trace, "fjsp_schedule_evolve_active")
+
+
+def _evolve(batch, pop_plans, generations, weights, mut_rate, seed, trace, entry):
     import torch
     from ._capi import check, ptr
     b = getattr(batch, "batch", batch)
@@ -544,9 +561,13 @@ def evolve(batch, pop_plans, generations, weights=None, mut_rate=6554, seed=0, t
                objective=new(b.N, n_obj, dtype=torch.int64), history=new(rows + 1, b.N, dtype=torch.int64), status=new(b.N),
                trace=new(rows, b.N, P, 3) if trace else None)
     work = torch.empty_like(pop_plans)
-    check(b._lib.fjsp_schedule_evolve(b._h, ptr(pop_plans), P, int(generations), ptr(weights), int(mut_rate), int(seed) & (2 ** 64 - 1),
-                                      int(b.first_env), ptr(out["population"]), ptr(work), ptr(out["population_objective"]), ptr(out["plan"]),
-                                      ptr(out["objective"]), ptr(out["history"]), ptr(out["status"]), ptr(out["trace"]), b._stream()))
+    more = ()
+    if entry == "fjsp_schedule_evolve_active":
+        out["inserted"] = new(b.N, P)
+        more = (ptr(out["inserted"]),)
+    check(getattr(b._lib, entry)(b._h, ptr(pop_plans), P, int(generations), ptr(weights), int(mut_rate), int(seed) & (2 ** 64 - 1),
+                                 int(b.first_env), ptr(out["population"]), ptr(work), ptr(out["population_objective"]), ptr(out["plan"]),
+                                 ptr(out["objective"]), ptr(out["history"]), ptr(out["status"]), ptr(out["trace"]), *more, b._stream()))
     return out
 
 

@@ -802,7 +802,8 @@ int fjsp_schedule_decode_group(const fjsp_env *e);
  * call's ceil(N n_cand / G) groups, so groups x G candidates are resident at once (fjsp_schedule_decode_active_resident)
  * and the workspace is 8 cap G groups bytes (cap = fjsp_schedule_decode_capacity) whatever N and n_cand are; entry i of
  * the candidates of a workgroup are G consecutive 8-byte words.  ORDERING: the calls on one handle share the workspace,
- * so they must be ordered on one stream (or by events); calls on different handles are independent.
+ * fjsp_schedule_evolve_active's among them, so they must be ordered on one stream (or by events); calls on different
+ * handles are independent.
  * fjsp_schedule_decode_active_group: G, 0 where fjsp_schedule_decode_group is 0.
  * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP (an insertion under breakdown shifts is not defined by the reference), a
  * state beyond fjsp_schedule_decode's limit.  FJSP_E_HIP: the workspace could not be allocated. */
@@ -1111,6 +1112,40 @@ int fjsp_schedule_evolve(fjsp_env *e, const int32_t *d_pop, int32_t pop, int32_t
                          int32_t *d_pop_out, int32_t *d_work, int64_t *d_pop_obj, int32_t *d_best_plan, int64_t *d_objective,
                          int64_t *d_history, int32_t *d_status, int32_t *d_trace, void *stream);
 int fjsp_schedule_evolve_lds(const fjsp_env *e);
+
+/* fjsp_schedule_evolve under the ACTIVE decoder (schedule.evolve_active, policy_search.genetic_search(decoder="active");
+ * csrc/fjsp_decode.hip, schedule_evolve_active_kernel): the genetic algorithm the FJSP literature scores with insertion
+ * into machine gaps.  fjsp_schedule_evolve's arguments in its order, plus d_pop_inserted in front of the stream, and
+ * fjsp_schedule_evolve's contract word for word -- the draw stream (FJSP_EVOLVE_STREAM, global env id, generation, child),
+ * the key, the parents, job set, crossover and mutation, the status codes 0 to 3 and 5 and the env copied through on one,
+ * generations = 0, d_trace, first_env, pop <= 64, the limits on generations and mut_rate, FJSP_E_ARG and FJSP_E_STATE --
+ * with ONE change: every decode is fjsp_schedule_decode_active's rule, generation 0 and every child, the mutated row put
+ * on its machine before it is placed.  tests/evolve_active_reference.py restates it, bit for bit.
+ *
+ * Chromosomes are not rewritten (a Baldwinian GA): a child's rows in d_pop_out and d_best_plan are the merged rows in
+ * merge order, as fjsp_schedule_evolve writes them; d_pop_obj, d_objective, d_history and the keys of the tournaments are
+ * the ACTIVE objectives of those rows, so fjsp_schedule_decode_active of d_pop_out gives d_pop_obj and of d_best_plan
+ * d_objective (fjsp_schedule_decode of them gives no less in either entry).
+ *   d_pop_inserted   nullable, i32[N][pop]   per individual of d_pop_out, the rows its decode placed in front of an
+ *                    interval (fjsp_schedule_decode_active's d_inserted); zeros for an env with a status.
+ *
+ * Intervals live in the handle's workspace of fjsp_schedule_decode_active: the same allocation, of the same size whichever
+ * of the two entries makes it first, the same 8-byte entries, never cleared.  A one-wave workgroup owns an env and cap x 64
+ * entries, entry i of individual q of workgroup w at ws[(w cap + i) 64 + q] -- the workgroup's index, not the env's --,
+ * and the grid is bounded: min(N, fjsp_schedule_evolve_active_resident(e)) workgroups, workgroup w evolving the envs w,
+ * w + grid, ... one after the other.  fjsp_schedule_evolve_active_resident = fjsp_schedule_decode_active_resident / 64:
+ * the envs resident at once; 0 where that is 0 (MO_DFJSP included).  ORDERING: as fjsp_schedule_decode_active -- the calls
+ * of both entries on one handle share the workspace, so they must be ordered on one stream (or by events).
+ * Stream-ordered, no host synchronisation, no atomics, two launches for any number of generations; capturable.
+ * Limit: fjsp_schedule_evolve's, unchanged (the LDS layout is the same; fjsp_schedule_evolve_lds).
+ * FJSP_E_UNSUPPORTED: FJSP_VARIANT_MO_DFJSP (an insertion under breakdown shifts is not defined by the reference:
+ * fjsp_schedule_evolve evolves such a handle), a working set beyond the limit.  FJSP_E_HIP: the workspace could not be
+ * allocated.  Every check runs before any device call. */
+int fjsp_schedule_evolve_active(fjsp_env *e, const int32_t *d_pop, int32_t pop, int32_t generations, const int64_t *d_weights,
+                                int32_t mut_rate, uint64_t seed, int64_t first_env,
+                                int32_t *d_pop_out, int32_t *d_work, int64_t *d_pop_obj, int32_t *d_best_plan, int64_t *d_objective,
+                                int64_t *d_history, int32_t *d_status, int32_t *d_trace, int32_t *d_pop_inserted, void *stream);
+int fjsp_schedule_evolve_active_resident(const fjsp_env *e);
 
 /* ---- fused pieces of the clipped-PPO learning iteration (agents/MPPPO/MPPPO.py:314-370; csrc/fjsp_ppo.hip).
  * All pointers are device pointers, f32; *d_count is the (global) number of samples the losses average over.
